@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of the MAX-GRNet per-frame path (224x224, fp32) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, optionally writes the outputs of the last timed step (--dump-outputs), and prints
+the result line: the headline figure, its config, and a roofline computed from the timed wall time and the launch list alone.  Everything
+else it can measure or check runs with --full only (see below).
 
 A "step" is one pass of the hot path over one clip of 16 synthetic frames per GPU (BASELINE.json
 configs[1]: 1 clip x 16 x 224 x 224, fp32), frames already resident in HBM.  With N > 1 (one process
@@ -16,11 +20,18 @@ command) every process is one rank (RANK / LOCAL_RANK / WORLD_SIZE from the envi
 process has made any GPU call -- relays rank 0's JSON line and exits with the child's code.
 
 Rank 0 prints ONE JSON line.  `roofline.achieved` follows SURVEY 8(d): frames/s per GPU x F_frame (the
-algorithmic convolution FLOPs of one frame) -- the whole step's wall time is charged to the convolutions;
-`roofline.conv_only_*` is the same FLOPs over the wall time of the conv launches alone (HIP events on the
-launch stream).  `cpu_baseline` times the oracle (a port of the reference's CPU path; the reference itself
-cannot travel to the GPU box) on the host cores; `parity` is BASELINE.json's second metric (MPJPE / max
-relative error of the GPU outputs vs that oracle on the same 16 frames).
+algorithmic convolution FLOPs of one frame) -- the whole step's wall time is charged to the convolutions.
+With --full the line also carries: `roofline.conv_only_*` (the same FLOPs over the wall time of the conv
+launches alone, HIP events on the launch stream) and `roofline.dominant_kernel` (per-shape timing runs);
+`cpu_baseline`, which times the oracle (a port of the reference's CPU path) on the host cores; `parity`,
+BASELINE.json's second metric (MPJPE / max relative error of the GPU outputs vs that oracle on the same 16
+frames), or the workload's own check; the exchange proof of N > 1 runs; and `secondary`, the other
+single-GPU configs of BASELINE.json, after a default 1-GPU fp32 run.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as
+DIR/<name>.npy (float32).  Inputs and weights are seed-defined, so the same arguments give the same inputs
+on every run and two builds can be compared output for output.  Above 64 MB in all, every array keeps the
+same fixed, seeded sample of its rows (first axis, in order).
 """
 import argparse
 import importlib
@@ -47,7 +58,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default: 20; 1 for --workload batchgen)")
     ap.add_argument("--frames", type=int, default=FRAMES_PER_GPU, help="frames per GPU per step (default: configs[1])")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: roofline.conv_only_* and "
+                    "dominant_kernel (timing runs of their own), cpu_baseline + parity (or the workload's own check), the exchange proof (N > 1) "
+                    "and the `secondary` legs of a default 1-GPU fp32 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32; a fixed, "
+                    "seeded sample of rows when they exceed 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline (and with it the fp32 parity)")
     ap.add_argument("--inflight", type=int, default=1, help="clips in flight per GPU: 1 = strictly one clip at a time (headline); "
                     "k > 1 alternates k independent model instances on k streams so consecutive clips overlap (throughput mode)")
     ap.add_argument("--tune-level", type=int, default=1, help="0: cost model only, 1: per-shape measurement (~0.1 s), "
@@ -69,8 +85,8 @@ def parse_args(argv=None):
     ap.add_argument("--exchange", choices=("auto", "capi", "torch"), default="torch", help="N > 1: who owns the all-gather. torch (default): the launcher's process group "
                     "(RCCL on the nccl backend); capi: the C ABI's own RCCL communicator (grnet_comm_create / grnet_allgather; a second communicator next to the launcher's, "
                     "verified on one rank only so far); auto: capi if every rank can bootstrap it, else torch")
-    ap.add_argument("--no-kernel-table", action="store_true", help="skip roofline.dominant_kernel (its per-shape timing launches would sit in a profiler's dispatch list)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the legs of BASELINE configs[2] (bf16, 256 frames), [3] (batchgen at 1 GPU) and [4] (tracks) that the default 1-GPU fp32 run appends as the `secondary` list")
+    ap.add_argument("--no-kernel-table", action="store_true", help="--full: skip roofline.dominant_kernel (its per-shape timing launches would sit in a profiler's dispatch list)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the legs of BASELINE configs[2] (bf16, 256 frames), [3] (batchgen at 1 GPU) and [4] (tracks) that the default 1-GPU fp32 run appends as the `secondary` list")
     a = ap.parse_args(argv)
     if a.dtype is None:
         a.dtype = "bf16" if a.workload == "tracks" else "f32"
@@ -411,6 +427,33 @@ def bf16_parity(pkg, got, frames_np):
             "vs": "oracle (CPU port of the reference path, fp32) and its bf16-storage emulation on the same frames and weights (tests/test_gpu_bf16.py states the same bound)"}
 
 
+DUMP_BUDGET = 63 * 10 ** 6      # bytes of all --dump-outputs arrays together: 64 MB with the .npy headers
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, tensors, budget=DUMP_BUDGET):
+    """--dump-outputs: every array of `tensors` (name -> tensor, the last timed step's outputs) as DIR/<name>.npy in float32.  When they
+    exceed `budget` bytes together, every array with more than one row keeps the same share of its rows (first axis), drawn with a fixed
+    seed and kept in order -- arrays with the same number of rows keep the same rows.  Returns the `outputs` object of the JSON line."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in tensors.items()}
+    fixed = sum(a.nbytes for a in arrays.values() if a.ndim == 0 or a.shape[0] <= 1)
+    rows = [a for a in arrays.values() if a.ndim and a.shape[0] > 1]
+    total = fixed + sum(a.nbytes for a in rows)
+    # k = max(1, floor(rows x share)) rows stay of each array: at most share x its bytes + one row, so the sum stays within the budget
+    share = 1.0 if total <= budget else max(0.0, budget - fixed - sum(a.nbytes // a.shape[0] for a in rows)) / max(sum(a.nbytes for a in rows), 1)
+    os.makedirs(directory, exist_ok=True)
+    shapes = {}
+    for name, a in sorted(arrays.items()):
+        if share < 1.0 and a.ndim and a.shape[0] > 1:
+            k = max(1, int(a.shape[0] * share))
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        shapes[name] = list(a.shape)
+    return {"dir": directory, "arrays": shapes, "dtype": "float32",
+            "sample": None if share >= 1.0 else f"rows drawn with numpy default_rng({DUMP_SEED}).choice without replacement, sorted; whole outputs are {total} bytes"}
+
+
 # ------------------------------------------------------------------------------------------- one rank
 class GpuWorkload:
     """The real thing: the synthetic MAX-GRNet model of this rank + its resident 16-frame shard."""
@@ -470,19 +513,25 @@ class GpuWorkload:
 
     def roofline(self, fps_per_gpu):
         model, n, pkg = self.model, self.n, self.pkg
-        conv_ms = min(model.time_convs(n) for _ in range(5))
+        full = getattr(self.args, "full", False)                 # a plain run launches nothing beyond its steps: no conv-only / serial / per-kernel timing
+        conv_ms = min(model.time_convs(n) for _ in range(5)) if full else None
         conv_ms_serial = None
-        if not getattr(self.args, "light", False):
+        if full and not getattr(self.args, "light", False):
             model.set_option(pkg._lib.OPT_MULTI_LANE, 0)      # the same launches one after another on one stream
             conv_ms_serial = min(model.time_convs(n) for _ in range(3))
             model.set_option(pkg._lib.OPT_MULTI_LANE, 1)
         alg_bytes = pkg.accounting.step_algorithmic_bytes(model.describe_convs(), n, 4 if self.args.dtype == "f32" else 2)
         extra = stored_traffic(n, self.args.dtype, alg_bytes)
-        if self.rank == 0 and not getattr(self.args, "light", False) and not getattr(self.args, "no_kernel_table", False):
+        if full and self.rank == 0 and not getattr(self.args, "light", False) and not getattr(self.args, "no_kernel_table", False):
             extra["dominant_kernel"], extra["kernels_by_time_alone"] = kernel_objects(model.kernel_table(n), self.args.dtype)
         return roofline_object(fps_per_gpu, self.args.dtype, model.conv_flops_per_frame(), conv_ms, conv_ms_serial,
                                model.num_conv_launches(), n, extra,
                                executed_flops_per_frame=model.conv_executed_flops_per_frame(n))
+
+    def outputs(self):
+        """What the last step handed its caller: the clip's per-frame records (every rank's frames after the exchange) + this rank's verts / rotmat."""
+        r = self.runners[(self.step_no - 1) % len(self.runners)]
+        return dict(r.sequence(), verts=r.verts, rotmat=r.rotmat)
 
     def outputs_np(self, k=None):
         """One more step; the first k frames' outputs as numpy (all frames: k = None)."""
@@ -565,6 +614,11 @@ class BatchgenWorkload:
                                {"note": "frames/s per GPU of the WHOLE job (per-frame path + exchange + replicated temporal branch) x the convolution FLOPs of a frame"},
                                executed_flops_per_frame=model.conv_executed_flops_per_frame(n))
 
+    def outputs(self):
+        """The job's results after the temporal branch (grnet_gait_correct: theta, verts, kp_2d, kp_3d, rotmat, pred_avg, pred_phase, pred_cparam,
+        point_local_feat), replicated on every rank."""
+        return self.runner.result
+
     def extras(self, line):
         line["phases"] = self.runner.phases()                  # of the latest job on this rank: per-frame path / exchange / replicated temporal branch
 
@@ -628,6 +682,11 @@ class TracksWorkload:
                                {"note": "frames/s per GPU of the whole step (crops + forwards of all tracks) x the convolution FLOPs of a frame"},
                                executed_flops_per_frame=model.conv_executed_flops_per_frame(n))
 
+    def outputs(self):
+        """Every track's results of the last step, tracks one after another along the frame axis."""
+        res = self.runner.results
+        return {name: self.torch.cat([r[name] for r in res]) for name in res[0]}
+
     def extras(self, line):
         """parity: the overlapped, fixed-buffer loop against crop + forward of each track one after another through the allocating host API."""
         torch, model = self.torch, self.model
@@ -657,15 +716,19 @@ def run_rank(args, make_workload=GpuWorkload, out=None):
     tracks = getattr(args, "workload", "clip") == "tracks"
     if tracks and make_workload is GpuWorkload:
         make_workload = TracksWorkload
+    full = getattr(args, "full", False)
     wl = make_workload(args, world, rank, local_rank, dist)
     elapsed = timed_steps(wl.step, wl.sync, args.steps, args.warmup, dist, reduce_device)
+    dumped = None
+    if rank == 0 and getattr(args, "dump_outputs", None):         # the last timed step's results, before anything else launches
+        dumped = dump_outputs(args.dump_outputs, wl.outputs())
     line = None
     n = args.tracks * args.track_frames if tracks else args.frames
     total_frames = (args.total_frames if batchgen else n * world) * args.steps
     fps = total_frames / elapsed
     roof = wl.roofline(fps / world)                            # every rank runs it (keeps the ranks in step), rank 0 reports
     proof = None
-    if world > 1 and hasattr(wl, "exchange_state"):            # every rank: one more step, then the slot-by-slot check of what the collective delivered
+    if full and world > 1 and hasattr(wl, "exchange_state"):   # every rank: one more step, then the slot-by-slot check of what the collective delivered
         wl.step()
         wl.sync()
         st = wl.exchange_state()
@@ -680,10 +743,13 @@ def run_rank(args, make_workload=GpuWorkload, out=None):
             line["config"].update(proof)
         elif world == 1:
             line["config"].update(exchange_ranks=1, frames_total=total_frames // args.steps)
-        wl.extras(line)
+        if dumped:
+            line["outputs"] = dumped
+        if full:
+            wl.extras(line)
     wl.close()
     if rank == 0:
-        if world == 1 and make_workload is GpuWorkload and args.dtype == "f32" and args.frames == FRAMES_PER_GPU and not args.no_secondary and not batchgen:
+        if full and world == 1 and make_workload is GpuWorkload and args.dtype == "f32" and args.frames == FRAMES_PER_GPU and not args.no_secondary and not batchgen:
             line["secondary"] = secondary_legs(args)
         print(json.dumps(line), file=out or sys.stdout, flush=True)
     if dist is not None:

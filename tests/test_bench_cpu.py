@@ -1,11 +1,15 @@
 """bench.py's launch and rank logic without a GPU: the self-launch of `python bench.py --gpus N` (a CHILD
 torch.distributed.run, never an exec), barrier + MAX-over-ranks timing and the rank-0 JSON line, driven with a
-stand-in workload under gloo (world size 2)."""
+stand-in workload under gloo (world size 2); what a plain run leaves to --full, and the files of --dump-outputs."""
+import importlib
+import io
 import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 from .conftest import ROOT
@@ -50,7 +54,7 @@ def test_two_ranks_end_to_end_through_the_launcher():
         out.append(p)
         return p
 
-    rc = bench.self_launch(["--gpus", "2", "--steps", "20", "--warmup", "2", "--frames", "16"], 2, run=run, script=FAKE)
+    rc = bench.self_launch(["--gpus", "2", "--steps", "20", "--warmup", "2", "--frames", "16", "--full"], 2, run=run, script=FAKE)
     p = out[0]
     assert rc == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -149,3 +153,129 @@ def test_tools_compile():
     for f in sorted(os.listdir(tools)):
         if f.endswith(".py"):
             py_compile.compile(os.path.join(tools, f), doraise=True)
+
+
+class _Recorder:
+    """A one-rank stand-in that counts its steps and records which of bench.py's measurements beside the timed steps ran."""
+    made = []
+
+    def __init__(self, args, world, rank, local_rank, dist):
+        import torch
+        self.torch, self.steps, self.calls = torch, 0, []
+        _Recorder.made.append(self)
+
+    def step(self):
+        time.sleep(0.001)
+        self.steps += 1
+
+    def sync(self):
+        pass
+
+    def config(self):
+        return {"workload": "stand-in", "steps_done": self.steps}
+
+    def roofline(self, fps_per_gpu):
+        self.calls.append("roofline")
+        return bench.roofline_object(fps_per_gpu, "f32", bench.F_FRAME_FLOP, None, None, 316, 16)
+
+    def outputs(self):
+        torch = self.torch
+        return {"theta": torch.full((16, 85), float(self.steps), dtype=torch.float64),
+                "verts": torch.randn(16, 6890, 3, generator=torch.Generator().manual_seed(5))}
+
+    def extras(self, line):
+        self.calls.append("extras")
+        line["parity"] = {"ok": True}
+
+    def close(self):
+        self.calls.append("close")
+
+
+def _run_one_rank(monkeypatch, argv):
+    """bench.run_rank at world 1 with the stand-in in the place of the default workload (so the `secondary` rule sees the default run)."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "GpuWorkload", _Recorder)
+    legs = []
+    monkeypatch.setattr(bench, "secondary_legs", lambda args: legs.append(args) or [{"metric": "leg"}])
+    _Recorder.made.clear()
+    out = io.StringIO()
+    line = bench.run_rank(bench.parse_args(argv), make_workload=_Recorder, out=out)
+    printed = [ln for ln in out.getvalue().splitlines() if ln.startswith("{")]
+    assert len(printed) == 1 and json.loads(printed[0]) == json.loads(json.dumps(line))
+    return line, _Recorder.made[-1], legs
+
+
+def test_plain_run_does_only_the_headline(monkeypatch):
+    """No --full: warm-up + exactly --steps timed steps, the result line, nothing else (no extras, no secondary legs)."""
+    line, wl, legs = _run_one_rank(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert wl.steps == 7 + 3 and wl.calls == ["roofline", "close"] and legs == []
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config", "roofline"} <= set(line)
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 16 * 1e3 / line["ms_per_step"]) / line["value"] < 1e-3
+    assert not {"parity", "cpu_baseline", "secondary", "outputs"} & set(line)
+
+
+def test_full_run_adds_the_other_measurements(monkeypatch):
+    line, wl, legs = _run_one_rank(monkeypatch, ["--steps", "4", "--warmup", "1", "--full"])
+    assert wl.steps == 5 and wl.calls == ["roofline", "extras", "close"] and line["parity"] == {"ok": True}
+    assert len(legs) == 1 and line["secondary"] == [{"metric": "leg"}]
+    line, wl, legs = _run_one_rank(monkeypatch, ["--steps", "4", "--warmup", "1", "--full", "--no-secondary"])
+    assert "extras" in wl.calls and legs == [] and "secondary" not in line
+
+
+def test_gpu_workload_roofline_times_nothing_in_a_plain_run():
+    """GpuWorkload.roofline: the conv-only, serial and per-kernel timings (launches of their own) run with --full only."""
+    calls = []
+
+    class Model:
+        def time_convs(self, n):
+            calls.append("time_convs")
+            return 2.0
+
+        def set_option(self, *a):
+            pass
+
+        def kernel_table(self, n):
+            calls.append("kernel_table")
+            return [{"name": "k", "launches": 1, "total_us": 10.0, "avg_us": 10.0, "gflop": 1.0, "executed_gflop": 1.0}]
+
+        describe_convs = lambda self: []
+        conv_flops_per_frame = lambda self: bench.F_FRAME_FLOP
+        conv_executed_flops_per_frame = lambda self, n=None: bench.F_FRAME_FLOP / 3
+        num_conv_launches = lambda self: 290
+
+    wl = bench.GpuWorkload.__new__(bench.GpuWorkload)
+    wl.model, wl.n, wl.rank, wl.pkg = Model(), 16, 0, importlib.import_module("video-based-gait-analysis-for-dementia_amd")
+    wl.args = bench.parse_args([])
+    r = wl.roofline(4000.0)
+    assert calls == [] and "conv_only_ms_per_step" not in r and "dominant_kernel" not in r and 0 < r["frac"] < 1
+    wl.args = bench.parse_args(["--full"])
+    r = wl.roofline(4000.0)
+    assert calls.count("time_convs") == 8 and "kernel_table" in calls and r["conv_only_ms_per_step"] == 2.0 and r["dominant_kernel"]["name"] == "k"
+
+
+def test_dump_outputs_hold_the_last_timed_step(monkeypatch, tmp_path):
+    d = tmp_path / "out"
+    line, wl, _ = _run_one_rank(monkeypatch, ["--steps", "6", "--warmup", "2", "--dump-outputs", str(d)])
+    theta, verts = np.load(d / "theta.npy"), np.load(d / "verts.npy")
+    assert theta.dtype == np.float32 and verts.dtype == np.float32 and theta.shape == (16, 85) and verts.shape == (16, 6890, 3)
+    assert (theta == 8.0).all()                                           # written after the 2 + 6 steps, by the last one
+    assert line["outputs"]["arrays"] == {"theta": [16, 85], "verts": [16, 6890, 3]} and line["outputs"]["sample"] is None
+    assert sorted(os.listdir(d)) == ["theta.npy", "verts.npy"]
+
+
+def test_dump_outputs_sample_rows_within_the_budget(tmp_path):
+    """Above the budget every array keeps the same seeded rows, in order; the files stay within it and repeat from run to run."""
+    import torch
+    g = torch.Generator().manual_seed(0)
+    t = {"a": torch.randn(1000, 50, generator=g), "b": torch.arange(1000, dtype=torch.float32)[:, None].repeat(1, 7), "c": torch.ones(1, 3)}
+    budget = 60_000
+    obj = bench.dump_outputs(str(tmp_path / "x"), t, budget=budget)
+    files = {k: np.load(tmp_path / "x" / f"{k}.npy") for k in "abc"}
+    assert sum(os.path.getsize(tmp_path / "x" / f"{k}.npy") - 128 for k in "abc") <= budget and obj["sample"]
+    rows = files["b"][:, 0].astype(np.int64)                              # b's rows carry their own index
+    assert len(rows) == files["a"].shape[0] > 0 and (np.diff(rows) > 0).all()
+    assert np.array_equal(files["a"], t["a"].numpy()[rows]) and np.array_equal(files["c"], np.ones((1, 3), np.float32))
+    assert bench.DUMP_BUDGET + 64 * 1024 <= 64e6                          # the default: 64 MB in all, .npy headers included
+    bench.dump_outputs(str(tmp_path / "y"), t, budget=budget)
+    assert all(np.array_equal(files[k], np.load(tmp_path / "y" / f"{k}.npy")) for k in "abc")
