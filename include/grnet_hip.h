@@ -194,6 +194,11 @@ int grnet_time_convs(grnet_t* h, int n_frames, void* stream, float* ms_out);
 int grnet_op_conv2d(grnet_t* h, const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host,
                     const float* bias_host, int cout, int ks, int stride, int relu, const float* add_dev,
                     float* out_dev, int tile_hint, void* stream);
+/* bf16 handles: grnet_op_conv2d with n_add (<= 3) addends.  Addend k: (n,add_ctot[k],ho>>add_shift[k],wo>>add_shift[k]) f32 NCHW, of which
+ * the launch adds channels add_coff[k] .. add_coff[k]+cout-1, nearest-upsampled by 2^add_shift[k] (the fuse layers' addend views). */
+int grnet_op_conv2d_adds(grnet_t* h, const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host, const float* bias_host, int cout, int ks,
+                         int stride, int relu, int n_add, const float* const* adds_dev, const int* add_ctot, const int* add_coff, const int* add_shift,
+                         float* out_dev, int tile_hint, void* stream);
 /* (a bf16 handle runs the bf16 path's NHWC kernel between two layout conversions: c a multiple of 8) */
 int grnet_op_bilinear2x(grnet_t* h, const float* in_dev, int n, int c, int hgt, int wid, float* out_dev, void* stream);
 /* bf16 handles: a chain of nconv (even, <= 8) 3x3 stride-1 convolutions c -> c on (n,c,wid,wid) maps as ONE launch with the frame resident in LDS
@@ -273,9 +278,14 @@ int grnet_crop_normalise_cv_maps(grnet_t* h, const unsigned char* images_dev, in
 
 /* Copy a named intermediate of the LAST forward (first n_frames images) into out_dev as a dense
  * (n,C,H,W) tensor; shape_out[3] receives C,H,W (out_dev may be NULL to query the shape).  Names:
- * stem_conv1, stem_conv2, layer1, stage{2,3,4}.{branch}, up{2,3,4}.{layer}.{bilinear,conv}, and per HR module
- * stage{2,3,4}.{module}.x{branch} (the branch outputs = the fuse layer's inputs) / .y{branch} (the module's outputs).
- * Parity tests compare these with the oracle's taps of hrnet.py:469-536. */
+ * stem_conv1, stem_conv2, layer1, layer1.{0..3}, transition1.{0,1}, transition2.2, transition3.3, stage{2,3,4}.{branch},
+ * up{2,3,4}.{layer}.{bilinear,conv}, cat (the 480-channel backbone output), head.{first,part_feats,heat,smpl_feats,cam_shape}
+ * (head.first: the two 480 -> 128 first convolutions side by side), and per HR module stage{2,3,4}.{module}.x{branch} (the branch
+ * outputs = the fuse layer's inputs) / .y{branch} (the module's outputs).  Parity tests compare these with the oracle's taps of
+ * hrnet.py:469-536 and pare.py:305-336.
+ * GRNET_EINVAL if n_frames is outside [1, frames of the last forward] (nothing is copied); GRNET_ESTATE if the last forward did not
+ * write the tensor to memory (bf16, large calls: a convolution inside a row-walking or chain launch other than its last one, e.g.
+ * stem_conv1 from 64 frames on) -- the buffer would hold an earlier forward's values. */
 int grnet_debug_tensor(grnet_t* h, const char* name, int n_frames, float* out_dev, int64_t* shape_out, void* stream);
 
 /* ---- the exchange: all-gather of the per-frame records of a sharded clip (SURVEY 8b `grnet_allgather`, 8e) -------------------------------------

@@ -227,6 +227,48 @@ def test_bf16_stride2_band_kernel(bmodel, oracle, case):
         for sl in (np.s_[:, :, 0], np.s_[:, :, -1], np.s_[:, :, :, 0], np.s_[:, :, :, -1]):
             assert np.all(np.abs(got[sl] - ref[sl]) <= np.abs(ref[sl]) * 2.0 ** -8 + 1e-5)
 
+S2_ROWS = [(32, 64, 56), (32, 32, 56), (64, 64, 28)]
+
+def _s2_rows_call_sizes(wo):
+    """Call sizes that give conv_bf16_s2_rows 4 / 2 / 1 row segments per frame (launch_s2_rows, from the device's CU count: 4 below 2 x CUs frames -- only
+    on 28-row outputs --, 2 below 4 x CUs, 1 from there on)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return ({4: 5, 2: 2 * cus, 1: 4 * cus} if wo == 28 else {2: 5, 1: 4 * cus}), cus
+
+@pytest.mark.parametrize("case", S2_ROWS, ids=lambda c: "x".join(map(str, c)))
+def test_bf16_stride2_row_walk_at_every_segment_count(bmodel, oracle, pkg, case):
+    """conv_bf16_s2_rows at the call sizes that split a frame into 4, 2 and 1 row segments (the forward reaches 4 and 2 only; 1 from 4 x CUs frames), plainly
+    and in the fuse layers' finishing-link form: ReLU over three addends read through channel-offset views, the last one a nearest-upsampled (shift 1) term.
+    5 distinct frames tiled: every copy gives the same bits, and the oracle runs on the distinct ones (fp32 on the same bf16 operands, one output rounding)."""
+    cin, cout, h = case
+    ho = h // 2
+    g = np.random.Generator(np.random.Philox(key=[93, cin * 1000 + cout + h]))
+    x = _rb(g.standard_normal((5, cin, h, h)))
+    w = _rb(g.standard_normal((cout, cin, 3, 3)) * np.sqrt(2.0 / (cin * 9)))
+    b = (g.standard_normal((cout,)) * 0.1).astype(np.float32)
+    adds = [(_rb(g.standard_normal((5, cout, ho, ho))), 0, 0), (_rb(g.standard_normal((5, cout + 32, ho, ho))), 32, 0),
+            (_rb(g.standard_normal((5, cout + 64, ho // 2, ho // 2))), 64, 1)]
+    lin = oracle.conv2d(x, w, stride=2, bias=b).numpy()
+    three = lin + adds[0][0] + adds[1][0][:, 32:] + oracle.upsample_nearest(torch.from_numpy(adds[2][0][:, 64:]), 2).numpy()
+    sizes, cus = _s2_rows_call_sizes(ho)
+    assert sizes[1] == 4 * cus and 2 * cus <= 1024
+    for segs, n in sizes.items():
+        idx = torch.arange(n) % 5
+        tile = lambda a: torch.from_numpy(a)[idx].contiguous().cuda()
+        for relu, with_adds in ((False, False), (True, True)):
+            got = bmodel.op_conv2d_adds(tile(x), w, b, stride=2, relu=relu, adds=[(tile(a), off, sh) for a, off, sh in adds] if with_adds else (), tile_hint=3004)
+            assert torch.equal(got, got[:5][idx.cuda()]), (segs, n)                                     # every copy of a frame: the same bits
+            got = got[:5].cpu().numpy()
+            ref = np.maximum(three, 0) if with_adds else lin
+            assert got.shape == ref.shape and np.array_equal(got, _rb(got))
+            rows = -(-ho // segs)
+            for sl in (np.s_[:], np.s_[:, :, 0], np.s_[:, :, -1], np.s_[:, :, :, 0], np.s_[:, :, :, -1],
+                       np.s_[:, :, sorted({r for k in range(rows, ho, rows) for r in (k - 1, k)})] if segs > 1 else np.s_[:, :, :1]):
+                assert np.all(np.abs(got[sl] - ref[sl]) <= np.abs(ref[sl]) * 2.0 ** -8 + 1e-5), (segs, n, relu, float(np.abs(got[sl] - ref[sl]).max()))
+        del got
+    with pytest.raises(pkg._lib.GrnetError, match="bad addend"):                                        # a view past the addend's channels is refused
+        bmodel.op_conv2d_adds(torch.zeros(1, cin, h, h).cuda(), w, b, stride=2, adds=[(torch.zeros(1, cout, ho, ho).cuda(), 8, 0)], tile_hint=3004)
+
 def test_bf16_stride2_kernels_refuse_other_shapes(bmodel, pkg):
     """Forced onto the stride-2 kernels (tile_hint 3004), a shape none of them is built for is refused, not run on something else: a 128-channel input (four
     passes of the band kernel lose to the generic one, the row walk holds 32 / 64 input channels), a stride-1 layer, an odd map."""

@@ -701,20 +701,25 @@ struct grnet {
         solo_region = false;
         std::vector<View> xs;
         xs.push_back(conv_bn(x, b + "transition1.0.0.weight", b + "transition1.0.1", 32, 3, 1, true));
+        name_view("transition1.0", xs.back());
         cur_lane = 1;
         xs.push_back(conv_bn(x, b + "transition1.1.0.0.weight", b + "transition1.1.0.1", 64, 3, 2, true));
+        name_view("transition1.1", xs.back());
         cur_lane = 0;
         xs = hr_module(xs, b + "stage2.0.", nullptr);
         for (size_t i = 0; i < xs.size(); ++i) name_view("stage2." + std::to_string(i), xs[i]);
         cur_lane = 2;
         xs.push_back(conv_bn(xs.back(), b + "transition2.2.0.0.weight", b + "transition2.2.0.1", 128, 3, 2, true));
+        name_view("transition2.2", xs.back());
         cur_lane = 0;
         for (int m = 0; m < 4; ++m) xs = hr_module(xs, b + "stage3." + std::to_string(m) + ".", nullptr);
         for (size_t i = 0; i < xs.size(); ++i) name_view("stage3." + std::to_string(i), xs[i]);
         cur_lane = 3;
         xs.push_back(conv_bn(xs.back(), b + "transition3.3.0.0.weight", b + "transition3.3.0.1", 256, 3, 2, true));
+        name_view("transition3.3", xs.back());
         cur_lane = 0;
         v_cat = new_buffer(480, 56, 56);                    // torch.cat([x0, x1, x2, x3], 1) (hrnet.py:524)
+        name_view("cat", v_cat);
         for (int m = 0; m < 3; ++m) {
             View o0 = slice(v_cat, 0, 32);
             xs = hr_module(xs, b + "stage4." + std::to_string(m) + ".", m == 2 ? &o0 : nullptr);
@@ -745,11 +750,16 @@ struct grnet {
                               {ConvSeg{hd + "keypoint_deconv_layers.0.weight", hd + "keypoint_deconv_layers.1", "", 128},
                                ConvSeg{hd + "smpl_deconv_layers.0.weight", hd + "smpl_deconv_layers.1", "", 128}},
                               3, 1, true);
+        name_view("head.first", first);
         View part_feats = conv_bn(slice(first, 0, 128), hd + "keypoint_deconv_layers.3.weight", hd + "keypoint_deconv_layers.4", 128, 3, 1, true);
+        name_view("head.part_feats", part_feats);
         v_heat = add_conv(part_feats, {ConvSeg{hd + "keypoint_final_layer.weight", "", hd + "keypoint_final_layer.bias", 25}}, 1, 1, false);
+        name_view("head.heat", v_heat);
         cur_lane = 1;                                       // the 3D branch runs beside the 2D branch
         v_smpl_feats = conv_bn(slice(first, 128, 128), hd + "smpl_deconv_layers.3.weight", hd + "smpl_deconv_layers.4", 128, 3, 1, true);
+        name_view("head.smpl_feats", v_smpl_feats);
         v_csmap = add_conv(v_smpl_feats, {ConvSeg{hd + "smpl_final_layer.weight", "", hd + "smpl_final_layer.bias", 64}}, 1, 1, false);
+        name_view("head.cam_shape", v_csmap);
         cur_lane = 0;
         solo_region = false;
         Op op;
@@ -1547,6 +1557,19 @@ struct grnet {
     bool pair_active(int n) const { return dtype == 1 && (chain_mode & 64) && !conv_tile_hint && (long)n * 56 * 56 >= 256L * 112 * 2; }      // (geometric: GRNET_OPT_BF16_MIN_FRAMES does not lower it)
     int bf16_min_frames = 0;                         // GRNET_OPT_BF16_MIN_FRAMES: 0 = every kernel group of chain_mode from its own smallest call (64 / 32 / 64 / 19 / 42 frames), else from this many
 
+    // grnet_debug_tensor: did the last forward write view v to memory?  A convolution inside a row-walking or chain launch (conv_bf16_roll.hip, conv_bf16_chain.hip)
+    // keeps its output in LDS unless it is the group's last one; the buffer then holds whatever an earlier forward left there.  (The pair's member writes its output.)
+    bool tap_written(const View& v) const {
+        for (const ConvLayer& L : convs) {
+            if (L.out.p != v.p || L.out.coff != v.coff || L.out.c != v.c) continue;
+            switch (kernel_for(L, last_n)) {
+                case K_BF16_ROLL: case K_BF16_ROLL_MEMBER: return L.roll_pos == (int)rolls[L.roll].convs.size() - 1;
+                case K_BF16_CHAIN: case K_BF16_CHAIN_MEMBER: return L.chain_pos == (int)chains[L.chain].convs.size() - 1;
+                default: return true;
+            }
+        }
+        return true;
+    }
     // Which kernel runs convolution L in a call of n frames: ONE place, used by the launcher, by the executed-FLOP report and by the
     // per-kernel table of bench.py (round-3 review: the report read a hidden "latest n" and ignored the environment masks).
     enum ConvKernel { K_BF16, K_BF16_STEM, K_BF16_ROLL, K_BF16_ROLL_MEMBER, K_BF16_CHAIN, K_BF16_CHAIN_MEMBER, K_BF16_PAIR, K_BF16_PAIR_MEMBER, K_BF16_WIDE, K_BF16_S2, K_WINO4S, K_PW, K_STEM, K_WINO4, K_DIRECT };
@@ -1873,9 +1896,19 @@ struct grnet {
         return 0;
     }
 
-    // Test hook on a bf16 handle: (n,cin,h,w) f32 NCHW in / out, converted to and from NHWC bf16 around ONE conv launch.
+    // Test hook on a bf16 handle: (n,cin,h,w) f32 NCHW in / out, converted to and from NHWC bf16 around ONE conv launch.  Addend k (grnet_op_conv2d_adds) is an
+    // (n,add_ctot[k],ho>>add_shift[k],wo>>add_shift[k]) f32 tensor, stored as NHWC bf16 with all its channels (padded to a multiple of 8); the launch
+    // reads channels add_coff[k] .. + cout of it.
     int op_conv2d_bf16(const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host, const float* bias_host, int cout, int ks,
                        int stride, int relu, const float* add_dev, float* out_dev, int tile_hint, hipStream_t s) {
+        const int zero = 0;
+        return op_conv2d_bf16_adds(in_dev, n, cin, hgt, wid, w_host, bias_host, cout, ks, stride, relu, add_dev ? 1 : 0, &add_dev, &cout, &zero, &zero, out_dev,
+                                   tile_hint, s);
+    }
+    int op_conv2d_bf16_adds(const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host, const float* bias_host, int cout, int ks, int stride,
+                            int relu, int n_add, const float* const* adds_dev, const int* add_ctot, const int* add_coff, const int* add_shift, float* out_dev,
+                            int tile_hint, hipStream_t s) {
+        const float* add_dev = n_add ? adds_dev[0] : nullptr;
         const int taps = ks * ks, pad = ks / 2, cin8 = (cin + 7) / 8 * 8, cin_pad = (cin + 31) / 32 * 32, cout_pad = (cout + 31) / 32 * 32;
         const int ho = (hgt + 2 * pad - ks) / stride + 1, wo = (wid + 2 * pad - ks) / stride + 1, cout8 = (cout + 7) / 8 * 8;
         std::vector<uint16_t> wp((size_t)taps * cout_pad * cin_pad, 0);
@@ -1905,33 +1938,49 @@ struct grnet {
             if (e != hipSuccess || e2 != hipSuccess) return fail(GRNET_EHIP, std::string("bf16 stem conv: ") + hipGetErrorString(e != hipSuccess ? e : e2));
             return 0;
         }
-        void *wd = nullptr, *bd = nullptr, *xin = nullptr, *xadd = nullptr, *xout = nullptr;
+        if (n_add < 0 || n_add > kMaxAdd) return fail(GRNET_EINVAL, "at most " + std::to_string(kMaxAdd) + " addends");
+        for (int k = 0; k < n_add; ++k)
+            if (!adds_dev[k] || add_ctot[k] < 1 || add_coff[k] < 0 || add_coff[k] + cout > add_ctot[k] || add_shift[k] < 0 || add_shift[k] > 3 ||
+                ho % (1 << add_shift[k]) != 0 || wo % (1 << add_shift[k]) != 0)
+                return fail(GRNET_EINVAL, "bad addend " + std::to_string(k) + " (channels holding [coff, coff + cout), a map of (ho, wo) >> shift)");
+        void *wd = nullptr, *bd = nullptr, *xin = nullptr, *xout = nullptr;
+        void* xadds[kMaxAdd] = {};
+        int add_ct8[kMaxAdd] = {};
+        for (int k = 0; k < n_add; ++k) add_ct8[k] = (add_ctot[k] + 7) / 8 * 8;
         const size_t in_b = (size_t)n * hgt * wid * cin8 * 2, out_b = (size_t)n * ho * wo * cout8 * 2;
-        if (hipMalloc(&wd, wp.size() * 2) != hipSuccess || hipMalloc(&bd, bp.size() * 4) != hipSuccess || hipMalloc(&xin, in_b) != hipSuccess ||
-            hipMalloc(&xout, out_b) != hipSuccess || (add_dev && hipMalloc(&xadd, out_b) != hipSuccess))
-            return fail(GRNET_ENOMEM, "hipMalloc failed");
+        auto free_all = [&]() {
+            hipFree(wd); hipFree(bd); hipFree(xin); hipFree(xout);
+            for (void* p : xadds) if (p) hipFree(p);
+        };
+        bool alloc_ok = hipMalloc(&wd, wp.size() * 2) == hipSuccess && hipMalloc(&bd, bp.size() * 4) == hipSuccess && hipMalloc(&xin, in_b) == hipSuccess &&
+                        hipMalloc(&xout, out_b) == hipSuccess;
+        for (int k = 0; k < n_add && alloc_ok; ++k)
+            alloc_ok = hipMalloc(&xadds[k], (size_t)n * (ho >> add_shift[k]) * (wo >> add_shift[k]) * add_ct8[k] * 2) == hipSuccess;
+        if (!alloc_ok) { free_all(); return fail(GRNET_ENOMEM, "hipMalloc failed"); }
         if (hipMemcpy(wd, wp.data(), wp.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(bd, bp.data(), bp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(wd); hipFree(bd); hipFree(xin); hipFree(xout);
-            if (xadd) hipFree(xadd);
+            free_all();
             return fail(GRNET_EHIP, "hipMemcpy of the test weights failed");
         }
         hipError_t e = launch_nchw_f32_to_nhwc_bf16(in_dev, xin, n, cin, hgt, wid, cin8, s);
-        if (e == hipSuccess && add_dev) e = launch_nchw_f32_to_nhwc_bf16(add_dev, xadd, n, cout, ho, wo, cout8, s);
+        for (int k = 0; k < n_add && e == hipSuccess; ++k)
+            e = launch_nchw_f32_to_nhwc_bf16(adds_dev[k], xadds[k], n, add_ctot[k], ho >> add_shift[k], wo >> add_shift[k], add_ct8[k], s);
         ConvArgs a{};
         a.in = static_cast<const float*>(xin); a.in_ctot = cin8; a.in_coff = 0; a.N = n; a.Cin = cin8; a.H = hgt; a.W = wid;
         a.Cout = cout; a.Ho = ho; a.Wo = wo;
         a.out = static_cast<float*>(xout); a.out_ctot = cout8; a.out_coff = 0;
         a.w = static_cast<const float*>(wd); a.bias = static_cast<const float*>(bd); a.CinPad = cin_pad; a.CoutPad = cout_pad;
         a.ks = ks; a.stride = stride; a.relu = relu;
-        if (add_dev) { a.n_add = 1; a.add[0] = static_cast<const float*>(xadd); a.add_ctot[0] = cout8; a.add_coff[0] = 0; a.add_shift[0] = 0; }
+        a.n_add = n_add;
+        for (int k = 0; k < n_add; ++k) {
+            a.add[k] = static_cast<const float*>(xadds[k]); a.add_ctot[k] = add_ct8[k]; a.add_coff[k] = add_coff[k]; a.add_shift[k] = add_shift[k];
+        }
         a.zeros = zeros;
         a.pw_stream = 1;
         if (const char* d = GRNET_AB_STR(CONV_DBG)) a.dbg = atoi(d);
         const bool wide = tile_hint == 3003, s2 = tile_hint == 3004;      // conv_bf16_wide_band / conv_bf16_s2_band on this one convolution
         if ((wide && !conv_bf16_wide_eligible(a)) || (s2 && !conv_bf16_s2_eligible(a))) {
-            hipFree(wd); hipFree(bd); hipFree(xin); hipFree(xout);
-            if (xadd) hipFree(xadd);
+            free_all();
             return fail(GRNET_EINVAL, "shape not eligible for the band kernel");
         }
         auto launch_one = [&]() { return wide ? launch_conv_bf16_wide(a, s) : s2 ? launch_conv_bf16_s2(a, s) : launch_conv_bf16(a, s, tile_hint); };
@@ -1953,8 +2002,7 @@ struct grnet {
         }
         if (e == hipSuccess) e = launch_nhwc_bf16_to_nchw_f32(xout, out_dev, n, cout, ho, wo, cout8, 0, s);
         hipError_t e2 = hipStreamSynchronize(s);
-        hipFree(wd); hipFree(bd); hipFree(xin); hipFree(xout);
-        if (xadd) hipFree(xadd);
+        free_all();
         if (e != hipSuccess) return fail(GRNET_EHIP, std::string("bf16 conv: ") + hipGetErrorString(e));
         if (e2 != hipSuccess) return fail(GRNET_EHIP, std::string("bf16 conv kernel: ") + hipGetErrorString(e2));
         return 0;
@@ -2590,6 +2638,16 @@ int grnet_time_convs(grnet_t* h, int n_frames, void* stream, float* ms_out) {
     return rc;
 }
 
+int grnet_op_conv2d_adds(grnet_t* h, const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host, const float* bias_host, int cout, int ks,
+                         int stride, int relu, int n_add, const float* const* adds_dev, const int* add_ctot, const int* add_coff, const int* add_shift,
+                         float* out_dev, int tile_hint, void* stream) {
+    if (!h || !in_dev || !w_host || !out_dev || n < 1 || (n_add && (!adds_dev || !add_ctot || !add_coff || !add_shift))) return GRNET_EINVAL;
+    if (h->dtype != 1) return h->fail(GRNET_ESTATE, "grnet_op_conv2d_adds needs a bf16 handle");
+    DeviceGuard guard(h->device);
+    return h->op_conv2d_bf16_adds(in_dev, n, cin, hgt, wid, w_host, bias_host, cout, ks, stride, relu, n_add, adds_dev, add_ctot, add_coff, add_shift, out_dev,
+                                  tile_hint, static_cast<hipStream_t>(stream));
+}
+
 int grnet_op_conv2d(grnet_t* h, const float* in_dev, int n, int cin, int hgt, int wid, const float* w_host, const float* bias_host,
                     int cout, int ks, int stride, int relu, const float* add_dev, float* out_dev, int tile_hint, void* stream) {
     if (!h || !in_dev || !w_host || !out_dev) return GRNET_EINVAL;
@@ -2734,10 +2792,16 @@ int grnet_op_bilinear2x(grnet_t* h, const float* in_dev, int n, int c, int hgt, 
 
 int grnet_debug_tensor(grnet_t* h, const char* name, int n_frames, float* out_dev, int64_t* shape_out, void* stream) {
     if (!h || !name) return GRNET_EINVAL;
+    if (n_frames < 1 || n_frames > h->last_n || n_frames > h->max_frames)         // the buffers hold last_n frames (the last buffer ends at the arena's end): never read past them
+        return h->fail(GRNET_EINVAL, "debug tensor " + std::string(name) + ": n_frames " + std::to_string(n_frames) + " outside [1, frames of the last forward = " +
+                                         std::to_string(h->last_n) + "]");
     DeviceGuard guard(h->device);
     for (auto& nv : h->named) {
         if (nv.first != name) continue;
         const View& v = nv.second;
+        if (!h->tap_written(v))
+            return h->fail(GRNET_ESTATE, "debug tensor " + std::string(name) + " was not written by the last forward (" + std::to_string(h->last_n) +
+                                             " frames): its producer ran inside a fused launch that keeps it on chip");
         if (shape_out) { shape_out[0] = v.c; shape_out[1] = v.h; shape_out[2] = v.w; }
         if (!out_dev) return 0;
         const size_t plane = (size_t)v.h * v.w;

@@ -321,6 +321,17 @@ class GRNet:
             r["avg_us"] = r["total_us"] / r["launches"]
         return out
 
+    def conv_kernels(self, n_frames):
+        """Per convolution-class launch of the plan, in launch order: (weight key of its first segment, kernel family<shape> that runs it in a call of
+        n_frames frames) -- grnet_conv_kernel_info.  A name ending in '+' runs inside the launch of its group's first member."""
+        self.finalize()
+        out = []
+        for pos, c in enumerate(self.describe_convs()):
+            name = C.create_string_buffer(96)
+            _lib.check(self._lib, self._h, self._lib.grnet_conv_kernel_info(self._h, pos, int(n_frames), name, 96, None), "grnet_conv_kernel_info")
+            out.append((c["name"], name.value.decode()))
+        return out
+
     def describe_convs(self):
         """The convolution launches of one forward in launch order: list of dicts (shape, fused addends, weight key, MACs per frame).
         An entry with cin == 0 is the grouped launch of an HR module's 1x1 fuse terms (csrc/hr_fuse.hip)."""
@@ -506,6 +517,29 @@ class GRNet:
                                        int(relu), add.data_ptr() if add is not None else None, out.data_ptr(),
                                        tile_hint, stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_conv2d")
+        return out
+
+    def op_conv2d_adds(self, x, w, bias=None, stride=1, relu=False, adds=(), tile_hint=0):
+        """bf16 handles: op_conv2d with up to three addends, each (tensor (n,ctot,ho>>shift,wo>>shift) f32, channel offset, shift): the launch adds
+        channels offset .. offset+cout-1 of it, nearest-upsampled by 2**shift (grnet_op_conv2d_adds)."""
+        n, cin, h, wd = x.shape
+        cout, _, ks, _ = w.shape
+        pad = ks // 2
+        ho, wo = (h + 2 * pad - ks) // stride + 1, (wd + 2 * pad - ks) // stride + 1
+        out = torch.empty(n, cout, ho, wo, dtype=torch.float32, device=x.device)
+        wn = _np32(w)
+        bn = _np32(bias) if bias is not None else None
+        k = len(adds)
+        tens = [a[0].contiguous() for a in adds]
+        ptrs = (C.c_void_p * max(k, 1))(*[t.data_ptr() for t in tens])
+        ctot = (C.c_int * max(k, 1))(*[t.shape[1] for t in tens])
+        coff = (C.c_int * max(k, 1))(*[int(a[1]) for a in adds])
+        shift = (C.c_int * max(k, 1))(*[int(a[2]) for a in adds])
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        rc = self._lib.grnet_op_conv2d_adds(self._h, x.data_ptr(), n, cin, h, wd, wn.ctypes.data_as(C.c_void_p),
+                                            bn.ctypes.data_as(C.c_void_p) if bn is not None else None, cout, ks, stride, int(relu), k, ptrs, ctot, coff,
+                                            shift, out.data_ptr(), tile_hint, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_conv2d_adds")
         return out
 
     def op_conv_chain(self, x, ws, bs, reps=0):
