@@ -180,6 +180,14 @@ double grnet_describe_conv_macs(grnet_t* h, int pos);
  * first; the launch reads and writes its own planned buffers, whose contents are garbage afterwards like after any forward). */
 int grnet_conv_kernel_info(grnet_t* h, int pos, int n_frames, char* name, int name_size, double* executed_macs_per_frame);
 int grnet_time_conv(grnet_t* h, int pos, int n_frames, int reps, void* stream, float* us_out);
+/* fp32 handles: the launch form the pos-th launch (positions as in grnet_describe_conv) takes in a call of n_frames frames under the tile hint
+ * in effect, as one text line "<family> key=value ...", from the launchers' own choice functions:
+ *   direct split_k=<0 whole-K tiles | 1 split-K> pixel_tile= channel_tile= waves= width_variant=<edge-pointer variant's width, 0: generic> rows= hint=
+ *   wino4 waves=4 nb= gx= gy= xcd= split=<1: the last round as half-size workgroups> full= rest=   |   wino4w waves=8 npw= gx= gy= xcd= split=0
+ *   wino4s images_per_tile= row_tiles= partial=<1: the last row tile holds fewer images>   |   pw   |   stem   |   fuse_up
+ * *tuning_index (may be NULL) receives the convolution index grnet_set_tuning's table uses for it (-1: fuse_up, which takes no hint).
+ * GRNET_EINVAL (with a message) if the hint in effect is not valid for that layer or buf is too small; GRNET_ESTATE on bf16 handles. */
+int grnet_conv_launch_form(grnet_t* h, int pos, int n_frames, char* buf, int size, int* tuning_index);
 /* Diagnostic: ONE eager forward on the lane streams with a HIP timing event in front of and behind every op (placed after the op's
  * cross-lane waits), after two untimed warm passes; no profiler involved.  Writes one text line per op in enqueue order --
  * "index lane start_us end_us label", times relative to the first op's start -- into buf and returns the text's length (< 0: error;
@@ -278,10 +286,12 @@ int grnet_crop_normalise_cv_maps(grnet_t* h, const unsigned char* images_dev, in
 
 /* Copy a named intermediate of the LAST forward (first n_frames images) into out_dev as a dense
  * (n,C,H,W) tensor; shape_out[3] receives C,H,W (out_dev may be NULL to query the shape).  Names:
- * stem_conv1, stem_conv2, layer1, layer1.{0..3}, transition1.{0,1}, transition2.2, transition3.3, stage{2,3,4}.{branch},
+ * stem_conv1, stem_conv2, layer1, layer1.{0..3}, layer1.{0..3}.{conv1,conv2}, layer1.0.downsample (unless the bf16 plan merges it into conv3),
+ * transition1.{0,1}, transition2.2, transition3.3, stage{2,3,4}.{branch},
  * up{2,3,4}.{layer}.{bilinear,conv}, cat (the 480-channel backbone output), head.{first,part_feats,heat,smpl_feats,cam_shape}
  * (head.first: the two 480 -> 128 first convolutions side by side), and per HR module stage{2,3,4}.{module}.x{branch} (the branch
- * outputs = the fuse layer's inputs) / .y{branch} (the module's outputs).  Parity tests compare these with the oracle's taps of
+ * outputs = the fuse layer's inputs) / .y{branch} (the module's outputs) / .b{branch}.{block}.conv1 (a BasicBlock's first convolution) /
+ * .b{branch}.{block} (its output; block 3's is .x{branch}).  Parity tests compare these with the oracle's taps of
  * hrnet.py:469-536 and pare.py:305-336.
  * GRNET_EINVAL if n_frames is outside [1, frames of the last forward] (nothing is copied); GRNET_ESTATE if the last forward did not
  * write the tensor to memory (bf16, large calls: a convolution inside a row-walking or chain launch other than its last one, e.g.

@@ -52,12 +52,17 @@ def _t(a):
 def conv2d(x, w, stride=1, bias=None):
     """nn.Conv2d with padding = k//2 (every conv on the path: hrnet.py:24-27,67-73; pare.py:388-395)."""
     w = _t(w)
+    if _F64:
+        return F.conv2d(_t(x).double(), w.double(), None if bias is None else _t(bias).double(), stride=stride, padding=w.shape[-1] // 2)
     return F.conv2d(_t(x), w, None if bias is None else _t(bias), stride=stride, padding=w.shape[-1] // 2)
 
 
 def batchnorm(x, sd, prefix):
     """BatchNorm2d in eval mode: (x-mean)/sqrt(var+1e-5)*gamma+beta; torch's CPU kernel, as the
     reference's own CPU path uses (the explicit formula is ``batchnorm_explicit``, checked equal in the tests)."""
+    if _F64:
+        p = [_t(sd[prefix + k]).double() for k in (".running_mean", ".running_var", ".weight", ".bias")]
+        return F.batch_norm(_t(x).double(), *p, training=False, eps=BN_EPS)
     return F.batch_norm(x, _t(sd[prefix + ".running_mean"]), _t(sd[prefix + ".running_var"]), _t(sd[prefix + ".weight"]),
                         _t(sd[prefix + ".bias"]), training=False, eps=BN_EPS)
 
@@ -91,6 +96,28 @@ def _q(t):
     return t.to(torch.bfloat16).to(torch.float32) if _BF16 else t
 
 
+# float64 mode: the teacher-forced stage tests of the fp32 path (tests/test_gpu_f32_stages.py) compare ONE launch with a reference on the
+# launch's own fp32 input; computed in float64, the reference's own rounding stays far below the kernels' (~1e-7 against 1e-6 .. 1e-5 of a
+# tensor's scale).  Under float64(): conv2d, batchnorm, conv_bn, basic_block, bottleneck, hr_fuse, upsample_nearest, upsample_bilinear2x,
+# keypoint_attention and head_tail take float32 inputs and return float64; geometry and SMPL stay float32.  Outside it nothing changes.
+_F64 = False
+
+
+class float64:
+    def __enter__(self):
+        global _F64
+        self._old, _F64 = _F64, True
+        return self
+
+    def __exit__(self, *a):
+        global _F64
+        _F64 = self._old
+
+
+def _d(t):
+    return _t(t).double() if _F64 else t
+
+
 def conv_bn(x, sd, conv_key, bn_prefix, stride=1, relu=False, residual=None):
     if _BF16:
         g, b = _t(sd[bn_prefix + ".weight"]).double(), _t(sd[bn_prefix + ".bias"]).double()
@@ -107,13 +134,13 @@ def conv_bn(x, sd, conv_key, bn_prefix, stride=1, relu=False, residual=None):
 
 def upsample_nearest(x, factor):
     """nn.Upsample(scale_factor=2**k, mode='nearest') (hrnet.py:208): out[y,x] = in[y//f, x//f]."""
-    return F.interpolate(x, scale_factor=factor, mode="nearest")
+    return F.interpolate(_d(x), scale_factor=factor, mode="nearest")
 
 
 def upsample_bilinear2x(x):
     """nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) (hrnet.py:443), torch's CPU kernel
     (the explicit two-tap formula is ``upsample_bilinear2x_explicit``, checked equal in the tests)."""
-    return _q(F.interpolate(_t(x), scale_factor=2, mode="bilinear", align_corners=True))
+    return _q(F.interpolate(_d(_t(x)), scale_factor=2, mode="bilinear", align_corners=True))
 
 
 def upsample_bilinear2x_explicit(x):
@@ -158,6 +185,7 @@ def hr_fuse(xs, sd, p):
     j > i: conv1x1 + BN + nearest upsample, j == i: identity, j < i: i-j stride-2 conv3x3 + BN (ReLU between them); summed in the
     reference's order j = 0 .. nb-1, then ReLU."""
     nb = len(xs)
+    xs = [_d(x) for x in xs]
     outs = []
     for i in range(nb):
         y = None
@@ -242,28 +270,31 @@ def head_features(feats, sd, p="head."):
 def keypoint_attention(feat, heat):
     """softmax over H*W per (frame, joint), then attention-weighted feature sum
     (keypoint_attention.py:42-48).  numpy, float64 softmax denominators avoided on purpose:
-    float32 throughout like the reference."""
-    feat = np.asarray(feat, np.float32)
-    heat = np.asarray(heat, np.float32)
+    float32 throughout like the reference (float64 throughout under float64())."""
+    dt = np.float64 if _F64 else np.float32
+    feat = np.asarray(feat, dt)
+    heat = np.asarray(heat, dt)
     n, j = heat.shape[:2]
     c = feat.shape[1]
     h = heat.reshape(n, j, -1)
     e = np.exp(h - h.max(-1, keepdims=True))
     pnorm = e / e.sum(-1, keepdims=True)
     f = feat.reshape(n, c, -1)
-    return np.einsum("njp,ncp->ncj", pnorm, f).astype(np.float32)      # (N, C, J)
+    return np.einsum("njp,ncp->ncj", pnorm, f).astype(dt)              # (N, C, J)
 
 
 def head_tail(plf, csf, sd, p="head."):
     """_pare_get_final_preds (pare.py:338-375) without iteration: per-joint 128->6, Linear 1536->10/3."""
-    plf = np.asarray(plf, np.float32)
-    csf = np.asarray(csf, np.float32)
-    wp = np.asarray(sd[p + "pose_mlp.weight"])[0, :, :, :, 0, 0]          # (6,128,24)
+    dt = np.float64 if _F64 else np.float32
+    w = (lambda k: np.asarray(sd[p + k], np.float64)) if _F64 else (lambda k: np.asarray(sd[p + k]))
+    plf = np.asarray(plf, dt)
+    csf = np.asarray(csf, dt)
+    wp = w("pose_mlp.weight")[0, :, :, :, 0, 0]                            # (6,128,24)
     pose = np.einsum("ncj,ocj->njo", plf, wp)                               # (N,24,6)
     flat = csf.reshape(csf.shape[0], -1)                                    # index c*24+j
-    shape = flat @ np.asarray(sd[p + "shape_mlp.weight"]).T + np.asarray(sd[p + "shape_mlp.bias"])
-    cam = flat @ np.asarray(sd[p + "cam_mlp.weight"]).T + np.asarray(sd[p + "cam_mlp.bias"])
-    return pose.astype(np.float32), shape.astype(np.float32), cam.astype(np.float32)
+    shape = flat @ w("shape_mlp.weight").T + w("shape_mlp.bias")
+    cam = flat @ w("cam_mlp.weight").T + w("cam_mlp.bias")
+    return pose.astype(dt), shape.astype(dt), cam.astype(dt)
 
 
 # ----------------------------------------------------------------------------- geometry

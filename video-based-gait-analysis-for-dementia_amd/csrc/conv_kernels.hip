@@ -831,6 +831,9 @@ size_t lds_bytes(const ConvArgs& a, const Cfg& c) {
     return sizeof(float) * (staging > red ? staging : red);
 }
 
+// waves per workgroup of a configuration (the whole-K instantiations of dispatch(): 256 threads but for the 7-tile 32-channel one)
+static int cfg_waves(const Cfg& c) { return c.family == 0 ? ((c.tps == 14) ? 4 : (c.tcs == 4 ? 4 : 2)) : c.nw; }
+
 // MFMA-issue model: the chip has 1024 SIMDs; a wave issues `chain` MFMAs of 32 cycles back to back.
 // cost ~ chain x number of rounds the waves need; split-K pays its extra staging traffic as a 15 % penalty.
 double cfg_cost(ConvArgs a, const Cfg& c, bool* ok) {
@@ -840,15 +843,9 @@ double cfg_cost(ConvArgs a, const Cfg& c, bool* ok) {
     if (!*ok) return 0;
     const double blocks = (double)a.tiles_y * a.groups * (a.CoutPad / (c.tcs * 16));
     const int kgroups = a.CinPad / 4, taps = a.ks * a.ks;
-    double waves, chain;
-    if (c.family == 0) {
-        const int nw = (c.tps == 14) ? 4 : (c.tcs == 4 ? 4 : 2);
-        waves = blocks * nw;
-        chain = (double)kgroups * taps * 7 * (c.tps == 14 ? c.tcs / 2 : 1);
-    } else {
-        waves = blocks * c.nw;
-        chain = (double)((kgroups + c.nw - 1) / c.nw) * taps * c.tps * c.tcs;
-    }
+    const double waves = blocks * cfg_waves(c);
+    const double chain = c.family == 0 ? (double)kgroups * taps * 7 * (c.tps == 14 ? c.tcs / 2 : 1)
+                                       : (double)((kgroups + c.nw - 1) / c.nw) * taps * c.tps * c.tcs;
     const double rounds = waves / 1024.0 < 1.0 ? 1.0 : waves / 1024.0;
     double cost = chain * rounds * (c.family == 1 ? 1.15 : 1.0) + 300.0;   // + fixed prologue/epilogue
     // whole-K tiles of a 1x1 convolution do ~14 MFMAs per 8-channel chunk: with less than one workgroup per CU
@@ -966,7 +963,8 @@ const char* conv_dominant_kernel_name() { return "conv_mfma_f32 / conv_splitk_f3
 
 // tile_hint: 0 = cost model; 7 / 14 = whole-K family with that pixel tile; 1000 + 10*psw + csw = split-K
 // family (1071, 1072, 1041, 1042), + 100 = eight split-K waves per workgroup (1171, 1141).  Hints exist for the per-kernel parity tests and for tuning.
-hipError_t launch_conv(ConvArgs a, hipStream_t s, int tile_hint) {
+// The configuration launch_conv runs for (a, tile_hint) -- ONE place, also read by grnet_conv_launch_form.  hipErrorInvalidValue: no valid configuration.
+hipError_t conv_choose(const ConvArgs& a, int tile_hint, ConvChoice* out) {
     const int TCpack = conv_pick_tc(a.Cout);
     if (a.CoutPad % TCpack != 0 || a.CinPad % kConvCK != 0) return hipErrorInvalidValue;
     if (!((a.ks == 1 && a.stride == 1) || (a.ks == 3 && (a.stride == 1 || a.stride == 2)))) return hipErrorInvalidValue;
@@ -1008,6 +1006,18 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s, int tile_hint) {
         }
     }
     if (!found) return hipErrorInvalidValue;
+    ConvArgs t = a;
+    plan_tile(t, best.tps, best.family);
+    out->family = best.family; out->tps = best.tps; out->tcs = best.tcs; out->nw = best.nw; out->waves = cfg_waves(best);
+    out->width_variant = splitk_width_variant(t, best);
+    out->rows = t.R;
+    return hipSuccess;
+}
+
+hipError_t launch_conv(ConvArgs a, hipStream_t s, int tile_hint) {
+    ConvChoice ch;
+    if (hipError_t e = conv_choose(a, tile_hint, &ch); e != hipSuccess) return e;
+    const Cfg best{ch.family, ch.tps, ch.tcs, ch.nw};
     plan_tile(a, best.tps, best.family);
     a.TC = best.tcs * 16;
     const size_t lds = lds_bytes(a, best);

@@ -625,13 +625,52 @@ static size_t wino4_lds() {
     return kLdsB + pad;
 }
 
+// The launch form of layer `a` in a call of a.N frames: ONE place, read by the launchers below and by grnet_conv_launch_form.  Four-wave
+// workgroups: TRG tile rows of one image x nb 16-channel blocks; eight-wave ones (conv_wino4w_f32; test hint 2003, dbg bit 5, forces the 4-wave
+// kernel): npw blocks per wave.  XCD-aware workgroup order where the tile count is a multiple of the 8 XCDs; a last round of 4-wave workgroups
+// that is at most half full runs as twice as many half-size workgroups (the 32-channel kernel on half a 64-channel block).
+hipError_t conv_wino4_form(const ConvArgs& a, Wino4Form* f) {
+    *f = Wino4Form{};
+    f->nb = conv_wino4_blocks(a.Cout, a.W);
+    if (!conv_wino4_eligible(a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.n_add) || a.CinPad % kCK != 0 || a.CoutPad % (f->nb * 16) != 0) return hipErrorInvalidValue;
+    if (a.n_add == 1 && a.add_shift[0] != 0) return hipErrorInvalidValue;
+    const int npw = conv_wino4_wide(a.Cout, a.W);
+    if (npw && a.CinPad % kCKW == 0 && a.CoutPad % (npw * 32) == 0 && !(a.dbg & 32)) {
+        const int trg = a.W == 56 ? 1 : 2;
+        f->waves = 8;
+        f->npw = npw;
+        f->gx = a.N * (((a.H >> 2) + trg - 1) / trg);
+        f->gy = a.CoutPad / (npw * 32);
+        f->xcd = f->gx % 8 == 0 && f->gx >= 16 ? 1 : 0;
+        f->full = f->gx * f->gy;
+        return hipSuccess;
+    }
+    const int trg = 14 / (a.W / 4);
+    f->waves = 4;
+    f->gx = a.N * (((a.H >> 2) + trg - 1) / trg);
+    f->gy = a.CoutPad / (f->nb * 16);
+    f->xcd = f->gx % 8 == 0 && f->gx >= 16 ? 1 : 0;
+    const int total = f->gx * f->gy;
+    f->full = total;
+    if (f->nb == 2) return hipSuccess;
+    static const int split_env = GRNET_AB(WINO_SPLIT, 1);
+    int kCUs = 0;                                        // workgroups per round = CUs of this device (one workgroup fits a CU)
+    if (hipError_t e = device_cu_count(&kCUs); e != hipSuccess) return e;
+    const int full = total / kCUs * kCUs, rest = total - full;
+    if (split_env && full > 0 && rest > 0 && 2 * rest <= kCUs && (!f->xcd || full % 8 == 0)) {
+        f->split = 1;
+        f->full = full;
+        f->rest = rest;
+    }
+    return hipSuccess;
+}
+
 template <int WD>
-static hipError_t launch_wino4_w(ConvArgs a, hipStream_t s, int nb, int* n_launches) {
-    constexpr int TRG = 14 / (WD / 4);
+static hipError_t launch_wino4_w(ConvArgs a, hipStream_t s, const Wino4Form& f, int* n_launches) {
     const size_t kLdsB = wino4_lds();
-    a.gx = a.N * (((a.H >> 2) + TRG - 1) / TRG);
-    a.gy = a.CoutPad / (nb * 16);
-    a.xcd = a.gx % 8 == 0 && a.gx >= 16 ? 1 : 0;
+    a.gx = f.gx;
+    a.gy = f.gy;
+    a.xcd = f.xcd;
     a.blk0 = 0;
     a.wsplit = 0;
     if (n_launches) *n_launches = 1;
@@ -646,19 +685,14 @@ static hipError_t launch_wino4_w(ConvArgs a, hipStream_t s, int nb, int* n_launc
         }
     }
 #endif
-    if (nb == 2) return launch_k(conv_wino4_f32<2, WD>, dim3(total), dim3(256), kLdsB, s, a);
-    // a last round of workgroups that is at most half full runs as twice as many half-size workgroups
-    static const int split_env = GRNET_AB(WINO_SPLIT, 1);
-    int kCUs = 0;                                        // workgroups per round = CUs of this device (one workgroup fits a CU)
-    if (hipError_t e = device_cu_count(&kCUs); e != hipSuccess) return e;
-    const int full = total / kCUs * kCUs, rest = total - full;
-    if (split_env && full > 0 && rest > 0 && 2 * rest <= kCUs && (!a.xcd || full % 8 == 0)) {
-        hipError_t e = launch_k(conv_wino4_f32<4, WD>, dim3(full), dim3(256), kLdsB, s, a);
+    if (f.nb == 2) return launch_k(conv_wino4_f32<2, WD>, dim3(total), dim3(256), kLdsB, s, a);
+    if (f.split) {
+        hipError_t e = launch_k(conv_wino4_f32<4, WD>, dim3(f.full), dim3(256), kLdsB, s, a);
         if (e != hipSuccess) return e;
-        a.blk0 = full;
+        a.blk0 = f.full;
         a.wsplit = 1;
         if (n_launches) *n_launches = 2;
-        return launch_k(conv_wino4_f32<2, WD, 0, true>, dim3(2 * rest), dim3(256), kLdsB, s, a);
+        return launch_k(conv_wino4_f32<2, WD, 0, true>, dim3(2 * f.rest), dim3(256), kLdsB, s, a);
     }
     return launch_k(conv_wino4_f32<4, WD>, dim3(total), dim3(256), kLdsB, s, a);
 }
@@ -677,38 +711,34 @@ hipError_t launch_conv_wino4(ConvArgs a, hipStream_t s, int* n_launches) {
             setw(conv_wino4w_f32<56, 4>); setw(conv_wino4w_f32<56, 2>); setw(conv_wino4w_f32<28, 4>); setw(conv_wino4w_f32<28, 2>);
             return e;
         }); e != hipSuccess) return e;
-    const int nb = conv_wino4_blocks(a.Cout, a.W);
-    if (!conv_wino4_eligible(a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.n_add) || a.CinPad % kCK != 0 || a.CoutPad % (nb * 16) != 0) return hipErrorInvalidValue;
-    if (a.n_add == 1 && a.add_shift[0] != 0) return hipErrorInvalidValue;
-    // eight-wave workgroups (conv_wino4w_f32) where the layer's shape has them; test hint 2003 (dbg bit 5) forces the 4-wave kernel
-    const int npw = conv_wino4_wide(a.Cout, a.W);
-    if (npw && a.CinPad % kCKW == 0 && a.CoutPad % (npw * 32) == 0 && !(a.dbg & 32)) {
-        const int trg = a.W == 56 ? 1 : 2;
-        a.gx = a.N * (((a.H >> 2) + trg - 1) / trg);
-        a.gy = a.CoutPad / (npw * 32);
-        a.xcd = a.gx % 8 == 0 && a.gx >= 16 ? 1 : 0;
+    Wino4Form f;
+    if (hipError_t e = conv_wino4_form(a, &f); e != hipSuccess) return e;
+    if (f.waves == 8) {
+        a.gx = f.gx;
+        a.gy = f.gy;
+        a.xcd = f.xcd;
         a.blk0 = 0;
         a.wsplit = 0;
         if (n_launches) *n_launches = 1;
         const dim3 grid(a.gx * a.gy);
-        if (a.W == 56) return npw == 4 ? launch_k(conv_wino4w_f32<56, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<56, 2>, grid, dim3(512), kLdsW, s, a);
-        return npw == 4 ? launch_k(conv_wino4w_f32<28, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<28, 2>, grid, dim3(512), kLdsW, s, a);
+        if (a.W == 56) return f.npw == 4 ? launch_k(conv_wino4w_f32<56, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<56, 2>, grid, dim3(512), kLdsW, s, a);
+        return f.npw == 4 ? launch_k(conv_wino4w_f32<28, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<28, 2>, grid, dim3(512), kLdsW, s, a);
     }
 #ifdef GRNET_ABLATION
     if (GRNET_AB_SET(W4_PHASES)) {
         a.dbg |= 8;
-        const hipError_t e = a.W == 56 ? launch_wino4_w<56>(a, s, nb, n_launches) : launch_wino4_w<28>(a, s, nb, n_launches);
+        const hipError_t e = a.W == 56 ? launch_wino4_w<56>(a, s, f, n_launches) : launch_wino4_w<28>(a, s, f, n_launches);
         unsigned long long h[8] = {}, z[8] = {};
         hipStreamSynchronize(s);
         hipMemcpyFromSymbol(h, HIP_SYMBOL(g_w4phase), sizeof(h));
         hipMemcpyToSymbol(HIP_SYMBOL(g_w4phase), z, sizeof(z));
         const double n = h[4] ? (double)h[4] : 1.0;
         fprintf(stderr, "[wino4 phases] %d->%d @%d N%d add %d nb %d wgs %llu: per WG ticks  prologue %.0f  first transform %.0f  chunk loop %.0f (%d chunks)  epilogue %.0f\n",
-                a.Cin, a.Cout, a.W, a.N, a.n_add, nb, h[4], h[0] / n, h[1] / n, h[2] / n, a.CinPad / kCK, h[3] / n);
+                a.Cin, a.Cout, a.W, a.N, a.n_add, f.nb, h[4], h[0] / n, h[1] / n, h[2] / n, a.CinPad / kCK, h[3] / n);
         return e;
     }
 #endif
-    return a.W == 56 ? launch_wino4_w<56>(a, s, nb, n_launches) : launch_wino4_w<28>(a, s, nb, n_launches);
+    return a.W == 56 ? launch_wino4_w<56>(a, s, f, n_launches) : launch_wino4_w<28>(a, s, f, n_launches);
 }
 
 // the filter transform of F(4x4,3x3), U = G g G^T, in fp64: g (3,3) row-major -> u[i * 6 + j]

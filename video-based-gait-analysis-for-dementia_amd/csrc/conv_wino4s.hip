@@ -252,11 +252,19 @@ hipError_t launch_s(const ConvArgs& a, hipStream_t s) {
     if (hipError_t e = once_per_device(attr, dev, [](int*) {
             return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino4s_f32<WD, C, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
         }); e != hipSuccess) return e;
-    const int groups = (a.N + G::IPW - 1) / G::IPW;
+    const int groups = conv_wino4s_row_tiles(WD, a.N, nullptr);
     return launch_k(conv_wino4s_f32<WD, C, KS>, dim3(groups * (C / 16)), dim3(64 * KS), G::lds_bytes, s, a);
 }
 
 }  // namespace
+
+int conv_wino4s_images_per_tile(int map_width) { return map_width == 14 ? GeoS<14, 4>::IPW : GeoS<7, 4>::IPW; }
+
+int conv_wino4s_row_tiles(int map_width, int n_images, int* last_tile_images) {
+    const int ipw = conv_wino4s_images_per_tile(map_width), tiles = (n_images + ipw - 1) / ipw;
+    if (last_tile_images) *last_tile_images = n_images - (tiles - 1) * ipw;
+    return tiles;
+}
 
 bool conv_wino4s_eligible(int cin, int cout, int ks, int stride, int h, int w, int n_add) {
     return ks == 3 && stride == 1 && cin == cout && n_add <= 1 && ((h == 14 && w == 14 && (cin == 128 || cin == 256)) || (h == 7 && w == 7 && cin == 256));

@@ -343,18 +343,21 @@ struct grnet {
         std::vector<int> branch_tail(nb, -1);                               // plan index of the launch that writes x_b
         cur_lane = 0;
         std::vector<std::vector<int>> branch_ops(nb);                       // plan indices of the branch's convolutions, in order
+        const std::string tag = p.substr(p.find("stage"));                  // "stage3.1."
         for (int k = 0; k < 4; ++k) {
             std::vector<View> y(nb);
             for (int b = 0; b < nb; ++b) {
                 cur_lane = b;
                 const std::string q = p + "branches." + std::to_string(b) + "." + std::to_string(k) + ".";
                 y[b] = conv_bn(xs[b], q + "conv1.weight", q + "bn1", kBranchCh[b], 3, 1, true);
+                name_view(tag + "b" + std::to_string(b) + "." + std::to_string(k) + ".conv1", y[b]);
                 branch_ops[b].push_back((int)ops.size() - 1);
             }
             for (int b = 0; b < nb; ++b) {
                 cur_lane = b;
                 const std::string q = p + "branches." + std::to_string(b) + "." + std::to_string(k) + ".";
                 xs[b] = conv_bn(y[b], q + "conv2.weight", q + "bn2", kBranchCh[b], 3, 1, true, {AddRef{xs[b], 0}});
+                name_view(tag + "b" + std::to_string(b) + "." + std::to_string(k), xs[b]);
                 branch_tail[b] = (int)ops.size() - 1;
                 branch_ops[b].push_back((int)ops.size() - 1);
             }
@@ -376,7 +379,6 @@ struct grnet {
                 }
                 chains.push_back(cp);
             }
-        const std::string tag = p.substr(p.find("stage"));                  // "stage3.1."
         for (int b = 0; b < nb; ++b) name_view(tag + "x" + std::to_string(b), xs[b]);
         // GRNET_FUSE_UP=0: the round-3 fuse layer (one 1x1 launch per up term, an elementwise launch for output 0)
         // (GRNET_BF16_FUSE_UP=0 does the same for the bf16 path, which has the grouped launch since round 5)
@@ -678,9 +680,12 @@ struct grnet {
             // BatchNorms folded into their halves of the weights, the shifts summed): the 411 MB downsample tensor (at 256 frames) is neither written nor read
             // back, and a launch goes away.  GRNET_BF16_MERGE_DS=0: the two launches of the reference's graph (hrnet.py:80-100, 389-406).
             static const int merge_ds = GRNET_AB(BF16_MERGE_DS, 1);
+            const std::string tq = "layer1." + std::to_string(k) + ".";
             if (k == 0 && dtype == 1 && merge_ds) {
                 View y = conv_bn(x, q + "conv1.weight", q + "bn1", 64, 1, 1, true);
+                name_view(tq + "conv1", y);
                 y = conv_bn(y, q + "conv2.weight", q + "bn2", 64, 3, 1, true);
+                name_view(tq + "conv2", y);
                 View xin = x;
                 x = conv_bn(y, q + "conv3.weight", q + "bn3", 256, 1, 1, true);
                 convs.back().in2 = xin;
@@ -691,8 +696,11 @@ struct grnet {
                 continue;
             }
             View res = k == 0 ? conv_bn(x, q + "downsample.0.weight", q + "downsample.1", 256, 1, 1, false) : x;
+            if (k == 0) name_view(tq + "downsample", res);
             View y = conv_bn(x, q + "conv1.weight", q + "bn1", 64, 1, 1, true);
+            name_view(tq + "conv1", y);
             y = conv_bn(y, q + "conv2.weight", q + "bn2", 64, 3, 1, true);
+            name_view(tq + "conv2", y);
             x = conv_bn(y, q + "conv3.weight", q + "bn3", 256, 1, 1, true, {AddRef{res, 0}});
             if (dtype == 1 && k > 0) add_roll(2, 3);
             name_view("layer1." + std::to_string(k), x);
@@ -1653,6 +1661,42 @@ struct grnet {
             default: snprintf(b, sizeof b, "conv_direct_f32 %dx%d s%d", L.ks, L.ks, L.stride); return b;
         }
     }
+    // grnet_conv_launch_form: what a call of n frames launches for L under the hint in effect, from the launchers' own choice functions
+    // (conv_choose, conv_wino4_form, conv_wino4s_images_per_tile).  fp32 handles.
+    int launch_form(const ConvLayer& L, int n, std::string* out) {
+        char b[192];
+        ConvArgs a = conv_args(L, nullptr, n);
+        switch (kernel_for(L, n)) {
+            case K_WINO4S: {
+                const int ipw = conv_wino4s_images_per_tile(L.in.w);
+                int last = 0;
+                const int tiles = conv_wino4s_row_tiles(L.in.w, n, &last);
+                snprintf(b, sizeof b, "wino4s images_per_tile=%d row_tiles=%d partial=%d", ipw, tiles, last < ipw ? 1 : 0);
+                break;
+            }
+            case K_PW: snprintf(b, sizeof b, "pw"); break;
+            case K_STEM: snprintf(b, sizeof b, "stem"); break;
+            case K_WINO4: {
+                Wino4Form f;
+                if (conv_wino4_form(a, &f) != hipSuccess) return fail(GRNET_EINVAL, "no F(4x4,3x3) launch for " + L.segs[0].wkey);
+                if (f.waves == 8) snprintf(b, sizeof b, "wino4w waves=8 npw=%d gx=%d gy=%d xcd=%d split=0", f.npw, f.gx, f.gy, f.xcd);
+                else snprintf(b, sizeof b, "wino4 waves=4 nb=%d gx=%d gy=%d xcd=%d split=%d full=%d rest=%d", f.nb, f.gx, f.gy, f.xcd, f.split, f.full, f.rest);
+                break;
+            }
+            case K_DIRECT: {
+                const int hint = hint_for(L, n);
+                ConvChoice c;
+                if (conv_choose(a, hint, &c) != hipSuccess)
+                    return fail(GRNET_EINVAL, "tile hint " + std::to_string(hint) + " is not valid for " + L.segs[0].wkey + " at " + std::to_string(n) + " frames");
+                snprintf(b, sizeof b, "direct split_k=%d pixel_tile=%d channel_tile=%d waves=%d width_variant=%d rows=%d hint=%d", c.family, c.tps * 16, c.tcs * 16,
+                         c.waves, c.width_variant, c.rows, hint);
+                break;
+            }
+            default: return fail(GRNET_ESTATE, "not an fp32 launch");
+        }
+        *out = b;
+        return 0;
+    }
     int launch_conv_op(const ConvLayer& L, const float* frames, int n, hipStream_t s, int* n_launches) {
         static const int w4s_ks = GRNET_AB(WINO4S_KS, 0);
         *n_launches = 1;
@@ -2584,6 +2628,25 @@ int grnet_conv_kernel_info(grnet_t* h, int pos, int n_frames, char* name, int na
     const ConvLayer& L = h->convs[op->conv_idx];
     if (name && name_size > 0) snprintf(name, name_size, "%s", h->kernel_name(L, n_frames).c_str());
     if (executed_macs_per_frame) *executed_macs_per_frame = L.macs_per_frame * h->executed_ratio(L, n_frames);
+    return 0;
+}
+
+int grnet_conv_launch_form(grnet_t* h, int pos, int n_frames, char* buf, int size, int* tuning_index) {
+    if (!h || !h->finalized || pos < 0 || n_frames < 1 || !buf || size < 1) return GRNET_EINVAL;
+    if (h->dtype != 0) return h->fail(GRNET_ESTATE, "grnet_conv_launch_form reports the launches of fp32 handles");
+    const Op* op = nth_conv_op(h, pos);
+    if (!op) return GRNET_EINVAL;
+    DeviceGuard guard(h->device);                          // conv_wino4_form reads the CU count of the current device
+    std::string text;
+    if (op->kind == Op::FUSEUP) {
+        text = "fuse_up";
+        if (tuning_index) *tuning_index = -1;
+    } else {
+        if (int rc = h->launch_form(h->convs[op->conv_idx], n_frames, &text)) return rc;
+        if (tuning_index) *tuning_index = op->conv_idx;
+    }
+    if ((int)text.size() + 1 > size) return h->fail(GRNET_EINVAL, "grnet_conv_launch_form: buffer too small");
+    memcpy(buf, text.c_str(), text.size() + 1);
     return 0;
 }
 

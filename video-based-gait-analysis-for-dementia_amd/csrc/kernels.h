@@ -166,6 +166,11 @@ struct ConvArgs {
 
 // Returns hipSuccess or the launch error.  `tile_hint`: 0 = auto, 7 / 14 = force pixel sub-tiles.
 hipError_t launch_conv(ConvArgs a, hipStream_t s, int tile_hint = 0);
+// The configuration launch_conv runs: family 0 = whole-K tiles (conv_mfma_f32), 1 = split-K (conv_splitk_f32); tps = pixel tile / 16, tcs = channel
+// tile / 16, nw = split-K waves (Cfg::nw), waves = waves per workgroup, width_variant = the image width of the edge-pointer split-K variant (0: generic),
+// rows = output rows per tile
+struct ConvChoice { int family = 0, tps = 0, tcs = 0, nw = 0, waves = 0, width_variant = 0, rows = 0; };
+hipError_t conv_choose(const ConvArgs& a, int tile_hint, ConvChoice* out);
 int conv_pick_tc(int Cout);                 // cout tile (32 or 64) -> defines CoutPad at pack time
 hipError_t conv_init();                     // sets max dynamic LDS on every instantiation
 const char* conv_dominant_kernel_name();
@@ -177,6 +182,10 @@ void pack_wino4_weights(const double* w_folded /* (cout,cin,3,3) */, int cout, i
 int conv_wino4_blocks(int cout, int map_width);   // 16-channel blocks per workgroup of that layer (4 or 2)
 int conv_wino4_wide(int cout, int map_width);     // > 0: the layer runs conv_wino4w_f32 (eight waves) with that many 16-channel blocks per wave (4: 128 output channels per
                                                   // workgroup, 2: 64); weights packed as for 4 blocks
+// What launch_conv_wino4 launches for `a` (a.N frames): waves per workgroup (4 / 8), nb (4-wave) or npw (8-wave) 16-channel blocks, the grid gx x gy,
+// XCD-aware order, and split = 1: `full` workgroups of the 4-wave kernel, then the last `rest` as 2 * rest half-size ones
+struct Wino4Form { int waves = 0, nb = 0, npw = 0, gx = 0, gy = 0, xcd = 0, split = 0, full = 0, rest = 0; };
+hipError_t conv_wino4_form(const ConvArgs& a, Wino4Form* f);
 
 void wino4_transform_filter(const double* g33, double* u36);   // U = G g G^T of F(4x4,3x3) in fp64
 // ---- register-resident F(4x4,3x3) for the small maps (conv_wino4s.hip): 128 -> 128 @14x14, 256 -> 256 @7x7 (HR branches 2, 3), 256 -> 256 @14x14
@@ -189,6 +198,9 @@ hipError_t launch_conv_stem(ConvArgs a, hipStream_t s);                   // a.w
 void pack_stem_weights(const double* w_folded /* (64,3,3,3) */, float* out /* 7*4*64 */);
 bool conv_wino4s_eligible(int cin, int cout, int ks, int stride, int h, int w, int n_add);
 hipError_t launch_conv_wino4s(ConvArgs a, hipStream_t s, int ksplit);      // a.w = pack_wino4r_weights; ksplit 0: the shape's default
+int conv_wino4s_images_per_tile(int map_width);                             // images per MFMA row tile (7x7: 4, 14x14: 1)
+int conv_wino4s_row_tiles(int map_width, int n_images, int* last_tile_images);   // row tiles (workgroups per channel block) of a
+                                                                                 // launch of n_images; *last_tile_images: images in the last one
 void pack_wino4r_weights(const double* w_folded /* (cout,cin,3,3) */, int cout, int cin, float* out /* 36*cin*cout */);
 // out = relu?( sum_k nearest_up(add_k) ), 1..4 addends, out and every addend are Views.
 struct SumArgs {

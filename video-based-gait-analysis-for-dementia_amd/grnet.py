@@ -332,6 +332,26 @@ class GRNet:
             out.append((c["name"], name.value.decode()))
         return out
 
+    def conv_launch_forms(self, n_frames):
+        """fp32 handles, per convolution-class launch of the plan in launch order: (weight key of its first segment, launch form as a dict, tuning
+        index) for a call of n_frames frames under the tile hints in effect -- grnet_conv_launch_form.  The dict holds "family" (direct, wino4,
+        wino4w, wino4s, pw, stem, fuse_up) and the integer fields of that family; the tuning index is the one grnet_set_tuning's table uses (-1: none).
+        A layer whose hint in effect is not valid for it raises GrnetError."""
+        self.finalize()
+        out = []
+        for pos, c in enumerate(self.describe_convs()):
+            out.append((c["name"],) + self.conv_launch_form(pos, n_frames))
+        return out
+
+    def conv_launch_form(self, pos, n_frames):
+        """(launch form dict, tuning index) of the pos-th launch (see conv_launch_forms)."""
+        buf, idx = C.create_string_buffer(256), C.c_int(-1)
+        _lib.check(self._lib, self._h, self._lib.grnet_conv_launch_form(self._h, int(pos), int(n_frames), buf, len(buf), C.byref(idx)), "grnet_conv_launch_form")
+        fam, *kv = buf.value.decode().split()
+        form = {"family": fam}
+        form.update((k, int(v)) for k, v in (t.split("=") for t in kv))
+        return form, idx.value
+
     def describe_convs(self):
         """The convolution launches of one forward in launch order: list of dicts (shape, fused addends, weight key, MACs per frame).
         An entry with cin == 0 is the grouped launch of an HR module's 1x1 fuse terms (csrc/hr_fuse.hip)."""
