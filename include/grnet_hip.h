@@ -225,6 +225,27 @@ int grnet_op_conv_chain(grnet_t* h, const float* in_dev, int n, int c, int wid, 
 int grnet_smpl_forward(grnet_t* h, const float* betas_dev, const float* rotmat_dev, const float* cam_dev, int n, float* verts_dev,
                        float* kp3d_dev, float* kp2d_dev, void* stream);
 
+/* VPRegressor.forward's J_regressor override -- lib/models/pare.py:70-76 (the evaluation path: MPJPE on Human3.6M / 3DPW is computed on the
+ * joints a dataset's own regressor takes from the predicted mesh): pred_joints = J_regressor (rows,6890) @ verts, then [:, H36M_TO_J14] for
+ * tables of fewer than 24 rows (lib/models/smpl.py:93-94).  J_host: (rows,6890) host floats, read during the call only; any finite content
+ * (dense or sparse, signed, rows of any sum).  select: n_select row indices applied after the product, or NULL for all rows; it is resolved
+ * here on the host, so only the selected rows are uploaded and computed: 1 <= rows written per frame <= GRNET_JOINT_REGRESSOR_MAX_ROWS.
+ * Replaces a table set earlier; J_host == NULL clears it.  Allowed before or after grnet_finalize_weights.  Allocates the table and the
+ * workspace of grnet_regress_joints (sized for max_frames) and synchronises the device before it frees the table it replaces.
+ * GRNET_EINVAL (with a message): rows < 1, n_select < 1, an index outside [0, rows), more rows than the limit, a non-finite entry.
+ * Every failure (these, GRNET_ENOMEM, GRNET_EHIP) leaves the table set before in place: the new one is allocated and filled first. */
+#define GRNET_JOINT_REGRESSOR_MAX_ROWS 64
+int grnet_set_joint_regressor(grnet_t* h, const float* J_host, int rows, const int32_t* select, int n_select);
+int grnet_joint_regressor_rows(grnet_t* h);      /* rows grnet_regress_joints writes per frame; 0: none set */
+/* verts_dev (n,6890,3) -> joints_dev (n,Jout,3); device pointers, verts_dev 8-byte aligned; 1 <= n <= max_frames; enqueued on `stream`
+ * (two launches, csrc/joint_regress.hip), no allocation, no host synchronisation.  fp32 fma chains on the fp32 matrix cores over a FIXED
+ * split of the vertices: the joints of a frame are bit-identical whatever the size of the call and wherever the frame sits in it.  Whoever
+ * holds `verts` calls it (after grnet_forward, grnet_head_forward, grnet_gait_correct -- on the FINAL vertices, grnet.py:171 -- or
+ * grnet_smpl_forward); kp_3d of those calls stays the 29 "spin2" joints.  GRNET_ESTATE if no table is set.
+ * The slice partials go through ONE workspace per handle: calls on a handle must be ordered (one stream, or events between streams), as for
+ * grnet_forward's arena; a call may not overlap grnet_set_joint_regressor either (that one synchronises the device itself). */
+int grnet_regress_joints(grnet_t* h, const float* verts_dev, int n, float* joints_dev, void* stream);
+
 /* PareHead.forward + VPRegressor.forward from GIVEN pooled features -- lib/models/pare.py:271-303 (_pare_get_final_preds :338-375:
  * per-joint 128->6, Linear 1536->10/3, rot6d_to_rotmat) and :52-91 (SMPL, projection, rotmat -> axis-angle, theta packing).  This is
  * the second head pass of the use_gait_feat branch (grnet.py:165,171: head(new_point_local_feat, cam_shape_feats, ...) then the

@@ -181,6 +181,16 @@ struct grnet {
     SmplTables smpl{};
     GruWeights gruw{};
     std::vector<float> J_regressor_host;
+    // grnet_set_joint_regressor: the selected rows in MFMA fragment order and the slice partials of grnet_regress_joints (max_frames frames)
+    float *jreg_pack = nullptr, *jreg_ws = nullptr;
+    int jreg_rows = 0;
+    void jreg_clear() {
+        if (jreg_pack || jreg_ws) (void)hipDeviceSynchronize();         // a call that reads them may still be running
+        if (jreg_pack) (void)hipFree(jreg_pack);
+        if (jreg_ws) (void)hipFree(jreg_ws);
+        jreg_pack = jreg_ws = nullptr;
+        jreg_rows = 0;
+    }
 
     struct GraphKey {
         int n; const void* in; grnet_outputs_t o;
@@ -265,6 +275,7 @@ struct grnet {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         for (hipEvent_t e : op_events_flat) if (e) (void)hipEventDestroy(e);
         for (void* p : dev_allocs) (void)hipFree(p);
+        jreg_clear();
         if (temporal_ws) (void)hipFree(temporal_ws);
         if (gru_fault) (void)hipHostFree(gru_fault);
         if (arena) (void)hipFree(arena);
@@ -2890,6 +2901,65 @@ int grnet_smpl_forward(grnet_t* h, const float* betas_dev, const float* rotmat_d
     hipError_t e = launch_smpl(betas_dev, rotmat_dev, cam_dev, h->smpl, h->d_A, verts_dev, kp3d_dev, kp2d_dev, n,
                                static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("smpl: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// VPRegressor.forward's J_regressor override -- lib/models/pare.py:70-76.  The selection ([:, H36M_TO_J14]) is applied to the table's rows here,
+// so the kernel computes the surviving rows only.
+int grnet_set_joint_regressor(grnet_t* h, const float* J_host, int rows, const int32_t* select, int n_select) {
+    if (!h) return GRNET_EINVAL;
+    DeviceGuard guard(h->device);
+    if (!J_host) { h->jreg_clear(); return 0; }
+    if (rows < 1) return h->fail(GRNET_EINVAL, "joint regressor: rows must be >= 1");
+    if (select && n_select < 1) return h->fail(GRNET_EINVAL, "joint regressor: an empty selection");
+    const int jout = select ? n_select : rows;
+    if (jout > kJregMaxRows)
+        return h->fail(GRNET_EINVAL, "joint regressor: " + std::to_string(jout) + " output rows exceed the limit of " + std::to_string(kJregMaxRows));
+    const size_t V = 6890;
+    std::vector<float> W((size_t)jout * V);
+    for (int j = 0; j < jout; ++j) {
+        const int r = select ? select[j] : j;
+        if (r < 0 || r >= rows)
+            return h->fail(GRNET_EINVAL, "joint regressor: selected row " + std::to_string(r) + " is outside [0, " + std::to_string(rows) + ")");
+        const float* src = J_host + (size_t)r * V;
+        for (size_t v = 0; v < V; ++v) {
+            if (!std::isfinite(src[v]))
+                return h->fail(GRNET_EINVAL, "joint regressor: non-finite entry in row " + std::to_string(r) + ", column " + std::to_string(v));
+            W[(size_t)j * V + v] = src[v];
+        }
+    }
+    std::vector<float> pack(joint_regress_pack_floats(jout));
+    joint_regress_pack(W.data(), jout, pack.data());
+    void *p = nullptr, *ws = nullptr;                      // allocate and fill first: a failure leaves the earlier table in place, like a refusal
+    if (hipMalloc(&p, pack.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc(&ws, joint_regress_workspace_floats(jout, h->max_frames) * sizeof(float)) != hipSuccess) {
+        if (p) (void)hipFree(p);
+        return h->fail(GRNET_ENOMEM, "joint regressor: hipMalloc of the table / workspace failed");
+    }
+    hipError_t e = hipMemcpy(p, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p); (void)hipFree(ws);
+        return h->fail(GRNET_EHIP, std::string("joint regressor upload: ") + hipGetErrorString(e));
+    }
+    h->jreg_clear();
+    h->jreg_pack = static_cast<float*>(p);
+    h->jreg_ws = static_cast<float*>(ws);
+    h->jreg_rows = jout;
+    return 0;
+}
+
+int grnet_joint_regressor_rows(grnet_t* h) { return h ? h->jreg_rows : GRNET_EINVAL; }
+
+int grnet_regress_joints(grnet_t* h, const float* verts_dev, int n, float* joints_dev, void* stream) {
+    if (!h) return GRNET_EINVAL;
+    if (!h->jreg_rows) return h->fail(GRNET_ESTATE, "grnet_regress_joints without a table (grnet_set_joint_regressor)");
+    if (!verts_dev || !joints_dev) return h->fail(GRNET_EINVAL, "grnet_regress_joints: null pointer");
+    if (reinterpret_cast<uintptr_t>(verts_dev) & 7) return h->fail(GRNET_EINVAL, "grnet_regress_joints: verts_dev must be 8-byte aligned");
+    if (n < 1 || n > h->max_frames)
+        return h->fail(GRNET_EINVAL, "grnet_regress_joints: n " + std::to_string(n) + " outside [1, max_frames=" + std::to_string(h->max_frames) + "]");
+    DeviceGuard guard(h->device);
+    hipError_t e = launch_joint_regress(verts_dev, h->jreg_pack, h->jreg_rows, h->jreg_ws, joints_dev, n, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("joint_regress: ") + hipGetErrorString(e));
     return 0;
 }
 

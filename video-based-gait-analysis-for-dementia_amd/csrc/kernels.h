@@ -286,6 +286,16 @@ struct SmplTables {
 hipError_t launch_smpl(const float* betas, const float* rotmat, const float* cam, SmplTables t, float* A_ws,
                        float* verts, float* kp3d, float* kp2d, int N, hipStream_t s);
 
+// Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
+constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
+constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order
+constexpr int kJregChunks = 16;    // frame chunks per call = table reads per call (8: 24 us, 16: 19 us, 32: 21 us at 400 frames)
+size_t joint_regress_pack_floats(int jout);
+size_t joint_regress_workspace_floats(int jout, int max_frames);
+void joint_regress_pack(const float* W /* (jout,6890) host */, int jout, float* out /* joint_regress_pack_floats(jout) host */);
+// verts (n,6890,3), 8-byte aligned -> joints (n,jout,3); partial: joint_regress_workspace_floats(jout, >= n) device floats
+hipError_t launch_joint_regress(const float* verts, const float* wpack, int jout, float* partial, float* joints, int n, hipStream_t s);
+
 // GRU gait encoder (gait_feat_encoder.py:79-104) ------------------------------------------------
 struct GruWeights {
     const float* cparam_w;                 // (128,3,24)

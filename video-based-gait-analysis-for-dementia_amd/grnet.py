@@ -11,6 +11,10 @@ checkpoint (weights arrive through ``load_state_dict`` / ``load_pare_dict``) and
 ``map_location='cpu'``.  ``use_gait_feat=True`` runs the temporal branch of ``grnet.py:154-173`` with the
 names the reference's FeatCorrector leaves undefined bound as DESIGN.md records (feature_correction.py:40-62,144);
 ``featcorr`` must describe the one configuration the class can run in (configs/config_grnet.yaml).
+
+``J_regressor`` (the evaluation path, pare.py:70-76) replaces ``kp_3d`` by the joints the caller's table takes from the FINAL
+vertices (grnet_regress_joints, csrc/joint_regress.hip); ``theta``, ``verts``, ``kp_2d`` (29 joints) and ``rotmat`` are untouched.
+harness.py's pose record and the entry points keep the 29 joints: demo.py and batch_generation.py never pass a regressor.
 """
 import ctypes as C
 import logging
@@ -34,6 +38,36 @@ def _np32(t):
     if torch.is_tensor(t):
         t = t.detach().cpu().numpy()
     return np.ascontiguousarray(np.asarray(t), dtype=np.float32)
+
+
+def reference_selection(rows):
+    """The rows VPRegressor.forward keeps of a table of ``rows`` rows (pare.py:73-75): H36M_TO_J14 below 24 rows, else all (None)."""
+    if rows >= 24:
+        return None
+    if rows <= max(netspec.H36M_TO_J14):
+        raise ValueError(f"a J_regressor of {rows} rows cannot be indexed with H36M_TO_J14 (needs >= 17 rows; pare.py:73-74)")
+    return list(netspec.H36M_TO_J14)
+
+
+def resolve_joint_regressor(J, select="reference"):
+    """Argument checks of GRNet.set_joint_regressor that need no handle: J (rows,6890) tensor / array -> (contiguous f32 array, row
+    indices or None).  select "reference": what VPRegressor.forward does (pare.py:70-76) -- netspec.H36M_TO_J14 when rows < 24, all rows
+    otherwise; fewer than 17 rows raise ValueError there (the reference's indexing fails with an IndexError); None: all rows; or a
+    sequence of row indices applied after the product."""
+    W = _np32(J)
+    if W.ndim != 2 or W.shape[1] != netspec.NUM_VERTS or W.shape[0] < 1:
+        raise ValueError(f"J_regressor must be (rows,{netspec.NUM_VERTS}), got {tuple(W.shape)}")
+    rows = W.shape[0]
+    if isinstance(select, str):
+        if select != "reference":
+            raise ValueError("select must be 'reference', None or a sequence of row indices")
+        return W, reference_selection(rows)
+    if select is None:
+        return W, None
+    sel = [int(i) for i in select]
+    if not sel or min(sel) < 0 or max(sel) >= rows:
+        raise ValueError(f"select must hold row indices in [0, {rows})")
+    return W, sel
 
 
 class GRNet:
@@ -69,6 +103,8 @@ class GRNet:
         self._finalized = False
         self._smpl_loaded = False
         self._loaded = set()
+        self._jreg = None                 # (host copy of the table, selection, the object it came from, its version) of the table on the device
+        self.joint_regressor_uploads = 0  # tables handed to grnet_set_joint_regressor so far
         self.seqlen = seqlen
         self.training = False
         self.focal_length = focal_length
@@ -159,6 +195,62 @@ class GRNet:
     def set_option(self, option, value):
         _lib.check(self._lib, self._h, self._lib.grnet_set_option(self._h, option, value), "grnet_set_option")
 
+    # ------------------------------------------------------------------ J_regressor override (pare.py:70-76)
+    def set_joint_regressor(self, J, select="reference"):
+        """Upload the (rows,6890) table regress_joints uses; see resolve_joint_regressor for ``select``.  ``J=None`` clears it."""
+        if J is None:
+            _lib.check(self._lib, self._h, self._lib.grnet_set_joint_regressor(self._h, None, 0, None, 0), "grnet_set_joint_regressor")
+            self._jreg = None
+            return self
+        W, sel = resolve_joint_regressor(J, select)
+        self._upload_joint_regressor(W, sel, J)
+        return self
+
+    def _upload_joint_regressor(self, W, sel, src):
+        self._jreg = None                                        # a refused table leaves the earlier one on the device; it is then re-sent on its next use
+        arr = (C.c_int32 * len(sel))(*sel) if sel is not None else None
+        rc = self._lib.grnet_set_joint_regressor(self._h, W.ctypes.data_as(C.c_void_p), W.shape[0], arr, len(sel) if sel is not None else 0)
+        _lib.check(self._lib, self._h, rc, "grnet_set_joint_regressor")
+        self.joint_regressor_uploads += 1
+        self._jreg = (W.copy(), sel, src, getattr(src, "_version", None))
+
+    def _use_joint_regressor(self, J):
+        """forward's J_regressor argument: upload only when the table, or the reference's selection for its row count, differs from what
+        the handle holds.  The same tensor object, unmodified, costs nothing; any other object is brought to the host (a device-to-host copy
+        for a CUDA tensor) and compared with the kept copy -- so an evaluation loop passes the SAME object every time, or calls
+        set_joint_regressor once and regress_joints on the vertices, rather than a fresh ``J.to(device)`` per batch."""
+        cur = self._jreg
+        if cur is not None and cur[2] is J and cur[3] == getattr(J, "_version", None) and torch.is_tensor(J) \
+                and cur[1] == reference_selection(cur[0].shape[0]):        # the table on the device may carry another selection (set_joint_regressor)
+            return
+        W, sel = resolve_joint_regressor(J, "reference")
+        if cur is not None and cur[1] == sel and cur[0].shape == W.shape and np.array_equal(cur[0], W):
+            self._jreg = (cur[0], sel, J, getattr(J, "_version", None))
+            return
+        self._upload_joint_regressor(W, sel, J)
+
+    def joint_regressor_rows(self):
+        return self._lib.grnet_joint_regressor_rows(self._h)
+
+    def regress_joints(self, verts):
+        """verts (n,6890,3) or (b,t,6890,3) on the handle's device -> (n,Jout,3) / (b,t,Jout,3): the set table's (selected) rows times the
+        vertices, fp32, bit-identical per frame whatever the call size (grnet_regress_joints)."""
+        if verts.dim() not in (3, 4) or tuple(verts.shape[-2:]) != (netspec.NUM_VERTS, 3):
+            raise ValueError(f"verts must be (n,6890,3) or (b,t,6890,3), got {tuple(verts.shape)}")
+        if verts.device != self.device:
+            raise RuntimeError(f"verts live on {verts.device} but this model's handle is bound to {self.device}")
+        lead = tuple(verts.shape[:-2])
+        v = verts.to(torch.float32).reshape(-1, netspec.NUM_VERTS, 3).contiguous()
+        n = v.shape[0]
+        jout = max(self.joint_regressor_rows(), 0)
+        out = torch.empty(n, jout, 3, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        for s in range(0, max(n, 1), self.max_frames):
+            m = min(self.max_frames, n - s)
+            rc = self._lib.grnet_regress_joints(self._h, v[s:s + m].data_ptr(), m, out[s:s + m].data_ptr() if jout else None, stream)
+            _lib.check(self._lib, self._h, rc, "grnet_regress_joints")
+        return out.reshape(*lead, jout, 3)
+
     # ------------------------------------------------------------------ forward
     def forward(self, features, bbox=None, cimg=None, J_regressor=None, extras=()):
         if features.dim() == 5:
@@ -172,7 +264,7 @@ class GRNet:
         if (nc, h, w) != (3, 224, 224):
             raise ValueError(f"expected frames of shape (3,224,224), got {(nc, h, w)}")
         if J_regressor is not None:
-            raise NotImplementedError("J_regressor override (evaluation-only, pare.py:70-76) is outside the inference path")
+            self._use_joint_regressor(J_regressor)              # checked (and uploaded, if it is a new table) before anything is enqueued
         if self.use_gait_feat:
             assert (bbox is not None) and (cimg is not None)                     # grnet.py:133
             if bbox.dim() == 2:
@@ -217,6 +309,8 @@ class GRNet:
             res["pred_avg"], res["pred_phase"] = g["pred_avg"], g["pred_phase"]
             res["pred_cparam"] = g["pred_cparam"]
             res["point_local_feat"] = g["point_local_feat"]
+        if J_regressor is not None:                            # pare.py:70-76 on the FINAL vertices (grnet.py:171)
+            res["kp_3d"] = self.regress_joints(res["verts"])
         return [res]
 
     __call__ = forward
@@ -388,9 +482,12 @@ class GRNet:
         _lib.check(self._lib, self._h, self._lib.grnet_time_convs(self._h, n_frames, stream, C.byref(ms)), "grnet_time_convs")
         return ms.value
 
-    def smpl_forward(self, betas, rotmat, cam=None):
-        """SMPL LBS on the GPU: betas (n,10), rotmat (n,24,3,3) [, cam (n,3)] -> verts, kp_3d (29 spin2 joints) [, kp_2d]."""
+    def smpl_forward(self, betas, rotmat, cam=None, J_regressor=None):
+        """SMPL LBS on the GPU: betas (n,10), rotmat (n,24,3,3) [, cam (n,3)] -> verts, kp_3d (29 spin2 joints) [, kp_2d].
+        J_regressor (rows,6890): kp_3d is replaced as VPRegressor.forward replaces it (pare.py:70-76); verts and kp_2d are not touched."""
         self.finalize()
+        if J_regressor is not None:
+            self._use_joint_regressor(J_regressor)
         n = betas.shape[0]
         dev = self.device
         b = betas.to(dev, torch.float32).contiguous()
@@ -406,6 +503,8 @@ class GRNet:
                                               m, verts[s0:].data_ptr(), kp3d[s0:].data_ptr(),
                                               kp2d[s0:].data_ptr() if kp2d is not None else None, stream)
             _lib.check(self._lib, self._h, rc, "grnet_smpl_forward")
+        if J_regressor is not None:
+            kp3d = self.regress_joints(verts)
         return verts, kp3d, kp2d
 
     def crop_normalise(self, images, bboxes, scale=1.0, bgr=False, mode="cv2"):

@@ -6,6 +6,9 @@ Reference counterparts: the model loops of ``demo.py:126-188`` and
 the reference's runnable configuration (``grnet.py:136-152``), so a clip shards into contiguous
 frame ranges with no data-path collective; the only exchange is the all-gather of the per-frame
 results before anything temporal (the GRU gait encoder) runs on the whole sequence.
+
+The pose record and the entry points keep ``kp_3d`` at the 29 "spin2" joints: ``demo.py`` and ``batch_generation.py`` never pass a
+``J_regressor`` (pare.py:70-76).  An evaluation loop that needs a dataset's joints calls ``GRNet.regress_joints`` on the vertices it holds.
 """
 import ctypes as C
 

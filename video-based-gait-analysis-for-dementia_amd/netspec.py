@@ -36,6 +36,9 @@ SPIN49_FROM_54 = [24, 12, 17, 19, 21, 16, 18, 20, 0, 2, 5, 8, 1, 4, 7, 25, 26, 2
 # spin2 (29 joints) -> kinectv2 (25 joints) index map (kp_utils.py:211-242,904-931).
 SPIN2_TO_KINECTV2 = [0, 6, 12, 15, 16, 18, 20, 22, 17, 19, 21, 23, 1, 4, 7, 10, 2, 5, 8, 11,
                      28, 25, 24, 27, 26]
+# rows VPRegressor.forward keeps of the joints a caller's J_regressor of fewer than 24 rows gives (pare.py:70-76; smpl.py:93-94): the 17 H36M
+# joints -> the 14 LSP joints the evaluation protocols score
+H36M_TO_J14 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10]
 
 
 def _bn(spec, prefix, c, role="bn"):

@@ -166,6 +166,26 @@ def make_smpl_tables(seed=SMPL_SEED):
     }
 
 
+def make_joint_regressor(rows, nnz=None, signed=False, seed=SMPL_SEED):
+    """A (rows,6890) f32 joint regressor for the J_regressor override (pare.py:70-76), defined by its recipe (rows, nnz, signed, seed).
+
+    ``nnz=None``: every entry non-zero; otherwise ``nnz`` non-zeros per row at random vertices.  ``signed=False``: positive rows that sum
+    to 1 (what SMPL and dataset regressors look like); ``signed=True``: N(0, sigma^2) entries, sigma = 1/80 dense (about 1/sqrt(6890)) or
+    1/sqrt(nnz), rows of any sum.  Drawn from a stream of its own, so no other ``make_*`` result depends on it.
+    """
+    V = netspec.NUM_VERTS
+    g = _rng(seed, f"jreg_{rows}_{nnz}_{int(bool(signed))}")
+    m = np.zeros((rows, V), np.float64)
+    for r in range(rows):
+        idx = np.arange(V) if nnz is None else g.choice(V, size=int(nnz), replace=False)
+        if signed:
+            m[r, idx] = g.standard_normal(len(idx)) * (1.0 / 80.0 if nnz is None else 1.0 / np.sqrt(nnz))
+        else:
+            w = g.uniform(0.1, 1.0, len(idx))
+            m[r, idx] = w / w.sum()
+    return m.astype(np.float32)
+
+
 def make_frames(n, seed=FRAME_SEED, start=0):
     """``n`` pre-normalised frames (n,3,224,224) f32, i.i.d. N(0,1).
 
