@@ -109,6 +109,28 @@ int grnet_gru_forward(grnet_t* h, const float* x_dev, const float* cparams_dev, 
  * -> y (b,n,3072); device pointers. */
 int grnet_tsattn_forward(grnet_t* h, const float* x_dev, const float* xs_dev, int b, int n, float* y_dev, void* stream);
 
+/* What grnet_tsattn_forward / grnet_gait_correct do with a clip of n frames on this handle's device, computed by the functions the
+ * launcher itself calls (the blocked kernel's threshold, the key-part count from the device's CU count): plan[0] temporal-attention
+ * kernel (0: one workgroup per query, 1: blocked, 128 queries per workgroup), plan[1] key parts per (query tile, head) (1: the kernel
+ * normalises and stores itself, no combine launch), plan[2] key blocks of 32 keys (0 for the per-query kernel), plan[3] dynamic LDS
+ * bytes of the attention launch.  GRNET_EINVAL beyond the per-clip limit. */
+int grnet_tsattn_plan(grnet_t* h, int n, int32_t* plan);
+
+/* Taps of the temporal branch (tests / diagnosis).  Arms the NEXT grnet_gru_forward, grnet_tsattn_forward or grnet_gait_correct on
+ * this handle (and this host thread): behind every launch of that call, a device-to-device copy of the launch's output into buf_dev is
+ * enqueued on the call's stream -- the temporal scratch itself cannot be read after the call (x_t is gated in place, the key-part
+ * partials share memory with y_t | y_s | x1, the GRU's gi becomes the heads' hidden buffer).  The launches, their order, their buffers
+ * and their aliasing are the production ones, so the call's outputs are bit-identical armed and unarmed; unarmed, nothing extra is
+ * enqueued.  A buffer smaller than what the armed call copies is refused by that call, before anything is enqueued, with the size
+ * needed in grnet_last_error; the call disarms the taps either way.  buf_dev NULL or floats 0: disarm. */
+int grnet_temporal_taps(grnet_t* h, float* buf_dev, size_t floats);
+
+/* The layout of what the last armed call copied, one text line per entry: "tap <name> <offset in floats> <dims...>" in launch order
+ * (names gru.*, ts.*, fc.*: the GRU, the attention block, the corrector around them; ts.part_o / ts.part_ml are the per-part
+ * (O, m, l) of a clip whose keys were split), and "gemm <M> <N> <K> <slices>" for every launch of the fp32 GEMM (slices > 1: split-K).
+ * buf NULL: returns the bytes needed; else the length written, or GRNET_EINVAL if buf_size is too small. */
+int grnet_temporal_tap_layout(grnet_t* h, char* buf, int buf_size);
+
 #define GRNET_OPT_USE_GRAPH 1     /* 1: capture each distinct (n, pointers) forward into a hipGraph and replay it */
 #define GRNET_OPT_CONV_TILE 2     /* 0 = cost model; 7 / 14 = whole-K tiles; 1071/1072/1041/1042/1171/1141 = split-K (psw,csw[,8 waves]) (tests / tuning); any forced
                                    * tile also switches the Winograd layers back to the direct kernels */

@@ -100,6 +100,10 @@ def _q(t):
 # launch's own fp32 input; computed in float64, the reference's own rounding stays far below the kernels' (~1e-7 against 1e-6 .. 1e-5 of a
 # tensor's scale).  Under float64(): conv2d, batchnorm, conv_bn, basic_block, bottleneck, hr_fuse, upsample_nearest, upsample_bilinear2x,
 # keypoint_attention and head_tail take float32 inputs and return float64; geometry and SMPL stay float32.  Outside it nothing changes.
+# The temporal modules follow the same rule (tests/test_gpu_temporal_stages.py): layer_normalization, _softmax, _gelu, multi_attention, joint_wise_ffn,
+# ts_attn_block, gru_direction, _mlp, gru_forward, gait_cparams and feat_corrector return float64 under float64(); each is then the composition of the
+# per-launch stage functions at the end of this file (ts_stage_* / gru_stage_* / fc_stage_*: one function per GPU launch, float64 output from that launch's
+# fp32 input), which outside the context compute the same stage in plain float32 -- the rounding floor of an honest fp32 implementation of that launch.
 _F64 = False
 
 
@@ -116,6 +120,10 @@ class float64:
 
 def _d(t):
     return _t(t).double() if _F64 else t
+
+
+def _dt():
+    return np.float64 if _F64 else np.float32
 
 
 def conv_bn(x, sd, conv_key, bn_prefix, stride=1, relu=False, residual=None):
@@ -452,6 +460,8 @@ def _sigmoid(x):
 
 def gru_direction(x, w_ih, w_hh, b_ih, b_hh, reverse):
     """One nn.GRU direction, gate order (r,z,n), h0 = 0."""
+    if _F64:
+        return gru_stage_recurrence(linear(x, w_ih, b_ih), w_hh, b_hh, reverse)
     b, T, _ = x.shape
     H = w_hh.shape[1]
     gi_all = x @ w_ih.T + b_ih
@@ -470,6 +480,8 @@ def gru_direction(x, w_ih, w_hh, b_ih, b_hh, reverse):
 
 
 def _mlp(x, sd, name, act_tanh=False):
+    if _F64:
+        return gru_stage_mlp_out(linear(x, sd[name + ".0.weight"], sd[name + ".0.bias"]), sd, name, act_tanh)
     h = x @ sd[name + ".0.weight"].T + sd[name + ".0.bias"]
     h = np.where(h > 0, h, np.float32(0.05) * h)                            # LeakyReLU(0.05)
     y = h @ sd[name + ".2.weight"].T + sd[name + ".2.bias"]
@@ -481,6 +493,9 @@ def gru_forward(x, cparams, sd):
 
     x (b,T,3072) laid out c*24+j; cparams (b,T,3).  Returns y (b,3), phase (b,T,4), xc (b,T,3072).
     """
+    if _F64:
+        st = gru_stages(x, cparams, sd)
+        return st["avg"], st["phase"], st["xc"]
     x = np.asarray(x, np.float32)
     cp = np.asarray(cparams, np.float32)
     wc = sd["cparam_mpl.weight"][0, :, :, :, 0, 0]                          # (128,3,24)
@@ -635,29 +650,33 @@ def crop_normalise_box_cv(img_u8, bbox, scale=1.0, crop=224):
 # ----------------------------------------------------------------------------- temporal/spatial attention block (row f2)
 def layer_normalization(z, gamma, beta, eps=1e-6):
     """The reference's own LayerNormalization (attention_utils.py:10-27): UNBIASED std and (std + eps), not nn.LayerNorm."""
-    z = np.asarray(z, np.float32)
-    mean = z.mean(-1, keepdims=True, dtype=np.float32)
-    std = z.std(-1, keepdims=True, ddof=1, dtype=np.float32)
-    return (np.asarray(gamma, np.float32) * ((z - mean) / (std + np.float32(eps))) + np.asarray(beta, np.float32)).astype(np.float32)
+    dt = _dt()
+    z = np.asarray(z, dt)
+    mean = z.mean(-1, keepdims=True, dtype=dt)
+    std = z.std(-1, keepdims=True, ddof=1, dtype=dt)
+    return (np.asarray(gamma, dt) * ((z - mean) / (std + dt(eps))) + np.asarray(beta, dt)).astype(dt)
 
 
 def _softmax(a, axis=-1):
     a = a - a.max(axis, keepdims=True)
     e = np.exp(a)
-    return (e / e.sum(axis, keepdims=True)).astype(np.float32)
+    return (e / e.sum(axis, keepdims=True)).astype(_dt())
 
 
 def _gelu(x):
     """nn.GELU() default (exact erf form)."""
     from math import sqrt
     from scipy.special import erf
-    return (0.5 * x * (1.0 + erf(x / sqrt(2.0)))).astype(np.float32)
+    return (0.5 * x * (1.0 + erf(x / sqrt(2.0)))).astype(_dt())
 
 
 def multi_attention(x, xs, sd, p, num_heads=4):
     """MultiAttention.forward (attention_utils.py:164-217): temporal attention over the n frames of a clip and spatial
     attention over the 25 tokens of a frame run side by side and are mixed by a softmax gate computed from their clip mean.
     x (b,n,128,24), xs (b,n,128,25) -> (b,n,3072)."""
+    if _F64:
+        st = ts_stages(x, xs, sd, p, upto="y_s")
+        return st["y_t"] + st["y_s"]
     x, xs = np.asarray(x, np.float32), np.asarray(xs, np.float32)
     b, n = x.shape[:2]
     n_tks = xs.shape[-1]
@@ -682,6 +701,8 @@ def multi_attention(x, xs, sd, p, num_heads=4):
 def joint_wise_ffn(x, sd, p, num_token=24):
     """JointWiseFeedForward.forward (attention_utils.py:123-130): two per-token locally connected layers
     (locallyconnected2d.py:39-48, kernel 1) with an exact GELU in between.  x (b,n,3072) index c*24+j."""
+    if _F64:
+        return ts_stage_jwff(x, sd, p, num_token)
     b, n, f = x.shape
     w1 = np.asarray(sd[p + "jwff_layer1.weight"], np.float32)[0, :, :, :, 0, 0]      # (64,128,24)
     w2 = np.asarray(sd[p + "jwff_layer2.weight"], np.float32)[0, :, :, :, 0, 0]      # (128,64,24)
@@ -692,6 +713,8 @@ def joint_wise_ffn(x, sd, p, num_token=24):
 
 def ts_attn_block(x, xs, sd, p="", num_heads=4, num_token=24):
     """TSAttnBlock.forward with use_jwff=True, eval (attention_utils.py:261-270)."""
+    if _F64:
+        return ts_stages(x, xs, sd, p, num_heads)["out"]
     x = np.asarray(x, np.float32)
     b, n = x.shape[:2]
     y = x.reshape(b, n, -1) + multi_attention(x, xs, sd, p + "mulattn.", num_heads)
@@ -709,6 +732,9 @@ def feat_corrector(x, cparams, sd, p="pfeat_corrector."):
 
     x (b,n,3072) index c*24+j, cparams (b,n,3) -> y (b*n,128,24), pred_avg (b,3), pred_phase (b,n,4).
     """
+    if _F64:
+        st = fc_stages(x, cparams, sd, p)
+        return st["out"].reshape(st["out"].shape[0], -1, 24), st["avg"], st["phase"]
     x = np.asarray(x, np.float32)
     b, n, _ = x.shape
     gsd = {k[len(p + "featnet."):]: v for k, v in sd.items() if k.startswith(p + "featnet.")}
@@ -740,12 +766,13 @@ def feat_corrector(x, cparams, sd, p="pfeat_corrector."):
 
 def gait_cparams(pred_cam, bbox, cimg):
     """grnet.py:156-160: camera parameters in the full image from the crop camera and the box."""
-    cam = np.asarray(pred_cam, np.float32).reshape(-1, 3)
-    bbox, cimg = np.asarray(bbox, np.float32), np.asarray(cimg, np.float32)
-    bs = bbox[..., 2] / np.float32(224.0)
+    dt = _dt()
+    cam = np.asarray(pred_cam, dt).reshape(-1, 3)
+    bbox, cimg = np.asarray(bbox, dt), np.asarray(cimg, dt)
+    bs = bbox[..., 2] / dt(224.0)
     t_bb = bbox[..., :2] - cimg
     scale = bs.reshape(-1, 1) * cam[:, 0:1]
-    return np.concatenate([scale, t_bb.reshape(-1, 2) / scale / np.float32(112.0) + cam[:, 1:]], -1).astype(np.float32)
+    return np.concatenate([scale, t_bb.reshape(-1, 2) / scale / dt(112.0) + cam[:, 1:]], -1).astype(dt)
 
 
 def grnet_forward_gait(frames, bbox, cimg, sd, smpl):
@@ -767,3 +794,243 @@ def grnet_forward_gait(frames, bbox, cimg, sd, smpl):
     return {"theta": theta.reshape(b, t, 85), "verts": verts.reshape(b, t, -1, 3), "kp_2d": kp2d.reshape(b, t, -1, 2),
             "kp_3d": kp3d.reshape(b, t, -1, 3), "rotmat": rotmat.reshape(b, t, 24, 3, 3), "pred_avg": pred_avg,
             "pred_phase": pred_phase, "pred_cparam": cparams, "point_local_feat": new_plf, "first_pass": first}
+
+
+# ----------------------------------------------------------------------------- temporal branch, one function per GPU launch
+# Each takes the launch's own input (fp32, as tapped from the GPU: grnet_temporal_taps) and returns the launch's output: float64 under float64(), plain
+# float32 outside it.  ts_stages / gru_stages / fc_stages chain them (every stage on the previous stage's output ROUNDED TO FP32, as a launch reads it).
+LOG2E = 1.4426950408889634
+
+
+def _f32(a):
+    """What the next launch reads: the stage's output stored as fp32."""
+    return np.asarray(a, np.float32)
+
+
+def linear(v, w, bias=None):
+    """nn.Linear on the rows of v: v (..., K) . w (N, K)^T + bias (gemm_nt_bias_f32)."""
+    dt = _dt()
+    y = np.asarray(v, dt) @ np.asarray(w, dt).T
+    return y if bias is None else y + np.asarray(bias, dt)
+
+
+def ts_key_part_ranges(n, parts, block=32):
+    """Key ranges [k0, k1) of the parts the blocked kernel splits a clip of n frames into: whole blocks of 32 keys, block index floor(nblk * p / parts)."""
+    nblk = (n + block - 1) // block
+    return [((nblk * p // parts) * block, min(n, (nblk * (p + 1) // parts) * block)) for p in range(parts)]
+
+
+def ts_stage_temporal_attention(qkv_t, rows=None, num_heads=4, chunk=256, key_range=None, partial=False):
+    """MultiAttention's temporal attention (attention_utils.py:190-205) from qkv_t (b,n,3E): softmax over the n frames of a clip per head, scaled by
+    1/sqrt(dim_head).  Chunked over queries (at 10 000 frames one head's score matrix is 0.8 GB in float64); `rows`: the query frames wanted (default all)
+    -> x_t (b, len(rows), E).  key_range (k0, k1): the softmax over those keys only; partial=True: that range's share as the blocked kernel leaves it for
+    the merge, reduced to what the merge depends on -- (O / l (b,rows,E), m + log2 l (b,rows,H)) with base-2 scores s log2(e) / sqrt(dim_head)."""
+    dt = _dt()
+    qkv_t = np.asarray(qkv_t)
+    b, n, e3 = qkv_t.shape
+    E = e3 // 3
+    dh = E // num_heads
+    rows = np.arange(n) if rows is None else np.asarray(rows)
+    k0, k1 = (0, n) if key_range is None else key_range
+    out = np.empty((b, len(rows), E), dt)
+    lse = np.empty((b, len(rows), num_heads), dt)
+    for bi in range(b):
+        for h in range(num_heads):
+            k = np.asarray(qkv_t[bi, k0:k1, E + h * dh:E + (h + 1) * dh], dt)
+            v = np.asarray(qkv_t[bi, k0:k1, 2 * E + h * dh:2 * E + (h + 1) * dh], dt)
+            for c0 in range(0, len(rows), chunk):
+                r = rows[c0:c0 + chunk]
+                q = np.asarray(qkv_t[bi, r, h * dh:(h + 1) * dh], dt)
+                a = q @ k.T / dt(np.sqrt(dh))
+                m = a.max(-1, keepdims=True)
+                ex = np.exp(a - m)
+                l = ex.sum(-1, keepdims=True)
+                out[bi, c0:c0 + len(r), h * dh:(h + 1) * dh] = ((ex / l).astype(dt)) @ v
+                lse[bi, c0:c0 + len(r), h] = (m[:, 0] + np.log(l[:, 0])) * dt(LOG2E)
+    return (out, lse) if partial else out
+
+
+def ts_stage_spatial_attention(qkv_s, num_heads=4, n_tks=25):
+    """MultiAttention's spatial attention (attention_utils.py:175-181, 207-217) from qkv_s (R,3E): per frame and head the dim_head values are (C, tokens);
+    tokens x tokens scores, NOT scaled; the output index is c * tokens + t."""
+    dt = _dt()
+    qkv_s = np.asarray(qkv_s, dt)
+    R = qkv_s.shape[0]
+    E = qkv_s.shape[1] // 3
+    dh = E // num_heads
+    z = qkv_s.reshape(R, 3, num_heads, dh // n_tks, n_tks)
+    qs, ks, vs = z[:, 0], z[:, 1], z[:, 2]
+    attn = _softmax(qs.transpose(0, 1, 3, 2) @ ks)
+    return (attn @ vs.transpose(0, 1, 3, 2)).transpose(0, 1, 3, 2).reshape(R, E)
+
+
+def ts_stage_clip_mean(x_t, x_s):
+    """The gate's clip mean (attention_utils.py:183-184): x_t, x_s (b,n,E) -> (b,2E)."""
+    dt = _dt()
+    return np.concatenate([np.asarray(x_t, dt), np.asarray(x_s, dt)], -1).mean(1, dtype=dt)
+
+
+def ts_stage_gate_apply(logits, x_t, x_s):
+    """alpha = softmax over the pairs (2e, 2e+1) of the gate logits (b,2E); x_t * alpha0, x_s * alpha1 (attention_utils.py:185-188)."""
+    dt = _dt()
+    b = logits.shape[0]
+    alpha = _softmax(np.asarray(logits, dt).reshape(b, 1, -1, 2))
+    return np.asarray(x_t, dt) * alpha[..., 0], np.asarray(x_s, dt) * alpha[..., 1]
+
+
+def ts_stage_residual_ln(x, y_t, y_s, sd, p=""):
+    """x1 = LN1(x + (y_t + y_s)) on rows (attention_utils.py:188, 265-266)."""
+    dt = _dt()
+    return layer_normalization(np.asarray(x, dt) + (np.asarray(y_t, dt) + np.asarray(y_s, dt)), sd[p + "norm1.gamma"], sd[p + "norm1.beta"])
+
+
+def ts_stage_jwff(x, sd, p, num_token=24):
+    """JointWiseFeedForward (attention_utils.py:123-130) on rows x (..., 3072), one matrix product per joint."""
+    dt = _dt()
+    x = np.asarray(x, dt)
+    w1 = np.asarray(sd[p + "jwff_layer1.weight"], dt)[0, :, :, :, 0, 0]              # (64,128,24)
+    w2 = np.asarray(sd[p + "jwff_layer2.weight"], dt)[0, :, :, :, 0, 0]              # (128,64,24)
+    v = x.reshape(-1, x.shape[-1] // num_token, num_token).transpose(2, 0, 1)          # (24, rows, 128)
+    h = _gelu(v @ w1.transpose(2, 1, 0))                                               # (24, rows, 64)
+    return (h @ w2.transpose(2, 1, 0)).transpose(1, 2, 0).reshape(x.shape).astype(dt)
+
+
+def ts_stage_jwff_ln(x1, sd, p=""):
+    """out = LN2(JWFF(x1) + x1) on rows (attention_utils.py:267-268)."""
+    dt = _dt()
+    x1 = np.asarray(x1, dt)
+    return layer_normalization(ts_stage_jwff(x1, sd, p + "ffn.") + x1, sd[p + "norm2.gamma"], sd[p + "norm2.beta"])
+
+
+def ts_stages(x, xs, sd, p="", num_heads=4, upto=None):
+    """The attention block launch by launch; p: the block's key prefix ("" for TSAttnBlock keys, or a MultiAttention prefix with upto="y_s").
+    x (b,n,128,24), xs (b,n,128,25) -> dict of qkv_t, qkv_s, x_t, x_s, mean, logits, x_t_gated, x_s_gated, y_t, y_s, x1, out."""
+    b, n = np.asarray(x).shape[:2]
+    ma = p if upto == "y_s" else p + "mulattn."
+    W = lambda k: sd[ma + k]
+    st = {}
+    st["qkv_t"] = linear(_f32(x).reshape(b, n, -1), W("qkv_t.weight"), W("qkv_t.bias"))
+    st["qkv_s"] = linear(_f32(xs).reshape(b, n, -1), W("qkv_s.weight"), W("qkv_s.bias"))
+    st["x_t"] = ts_stage_temporal_attention(_f32(st["qkv_t"]), num_heads=num_heads)
+    st["x_s"] = ts_stage_spatial_attention(_f32(st["qkv_s"]).reshape(b * n, -1), num_heads).reshape(b, n, -1)
+    st["mean"] = ts_stage_clip_mean(_f32(st["x_t"]), _f32(st["x_s"]))
+    st["logits"] = linear(_f32(st["mean"]), W("ts_attn.weight"), W("ts_attn.bias"))
+    st["x_t_gated"], st["x_s_gated"] = ts_stage_gate_apply(_f32(st["logits"]), _f32(st["x_t"]), _f32(st["x_s"]))
+    st["y_t"] = linear(_f32(st["x_t_gated"]), W("fc_t.weight"), W("fc_t.bias"))
+    st["y_s"] = linear(_f32(st["x_s_gated"]), W("fc_s.weight"), W("fc_s.bias"))
+    if upto == "y_s":
+        return st
+    st["x1"] = ts_stage_residual_ln(_f32(x).reshape(b, n, -1), _f32(st["y_t"]), _f32(st["y_s"]), sd, p)
+    st["out"] = ts_stage_jwff_ln(_f32(st["x1"]), sd, p)
+    return st
+
+
+def gru_stage_prep(x, cparams, sd):
+    """xc = cparam_mpl(cparams) (per-joint 3 -> 128), xin = x + xc (gait_feat_encoder.py:85)."""
+    dt = _dt()
+    cp = np.asarray(cparams, dt)
+    wc = np.asarray(sd["cparam_mpl.weight"], dt)[0, :, :, :, 0, 0]                   # (128,3,24)
+    xc = np.einsum("btf,cfj->btcj", cp, wc).reshape(*cp.shape[:2], -1).astype(dt)
+    return xc, np.asarray(x, dt) + xc
+
+
+def gru_stage_recurrence(gi_all, w_hh, b_hh, reverse):
+    """One nn.GRU direction from its input products gi (b,T,3H), gate order (r,z,n), h0 = 0 -> (outputs (b,T,H), final h)."""
+    dt = _dt()
+    gi_all = np.asarray(gi_all, dt)
+    w_hhT, b_hh = np.ascontiguousarray(np.asarray(w_hh, dt).T), np.asarray(b_hh, dt)
+    b, T, _ = gi_all.shape
+    H = w_hhT.shape[0]
+    h = np.zeros((b, H), dt)
+    out = np.empty((b, T, H), dt)
+    for t in (range(T - 1, -1, -1) if reverse else range(T)):
+        gi = gi_all[:, t]
+        gh = h @ w_hhT + b_hh
+        r = _sigmoid(gi[:, :H] + gh[:, :H])
+        z = _sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        n = np.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        h = ((1 - z) * n + z * h).astype(dt)
+        out[:, t] = h
+    return out, h
+
+
+def gru_stage_mlp_out(hidden, sd, name, act_tanh=False):
+    """LeakyReLU(0.05) -> Linear(100 -> nout) [-> tanh] on the hidden PRE-activations (mlp_out_kernel)."""
+    dt = _dt()
+    h = np.asarray(hidden, dt)
+    h = np.where(h > 0, h, dt(0.05) * h)
+    y = h @ np.asarray(sd[name + ".2.weight"], dt).T + np.asarray(sd[name + ".2.bias"], dt)
+    return np.tanh(y) if act_tanh else y
+
+
+def gru_stages(x, cparams, sd):
+    """The GRU encoder launch by launch: dict of xc, xin, gi{layer}{dir}, l0, l1, hfin, hid_speed, hid_step, hid_phase, avg, phase."""
+    st = {}
+    st["xc"], st["xin"] = gru_stage_prep(_f32(x), _f32(cparams), sd)
+    layer_in, finals = _f32(st["xin"]), []
+    for layer in range(2):
+        outs = []
+        for d, suf in enumerate(("", "_reverse")):
+            gi = linear(layer_in, sd[f"rnn.weight_ih_l{layer}{suf}"], sd[f"rnn.bias_ih_l{layer}{suf}"])
+            st[f"gi{layer}{d}"] = gi
+            o, hT = gru_stage_recurrence(_f32(gi), sd[f"rnn.weight_hh_l{layer}{suf}"], sd[f"rnn.bias_hh_l{layer}{suf}"], bool(d))
+            outs.append(o)
+            finals.append(hT)
+        st[f"l{layer}"] = np.concatenate(outs, -1)
+        layer_in = _f32(st[f"l{layer}"])
+    st["hfin"] = np.concatenate(finals, -1)                                          # [l0f,l0b,l1f,l1b] -> (b,1200)
+    hf = _f32(st["hfin"])
+    st["hid_speed"] = linear(hf, sd["speed_mlp.0.weight"], sd["speed_mlp.0.bias"])
+    st["hid_step"] = linear(hf, sd["step_mlp.0.weight"], sd["step_mlp.0.bias"])
+    st["hid_phase"] = linear(layer_in, sd["phase_mlp.0.weight"], sd["phase_mlp.0.bias"])
+    st["avg"] = np.concatenate([gru_stage_mlp_out(_f32(st["hid_speed"]), sd, "speed_mlp"), gru_stage_mlp_out(_f32(st["hid_step"]), sd, "step_mlp")], -1)
+    st["phase"] = gru_stage_mlp_out(_f32(st["hid_phase"]), sd, "phase_mlp", act_tanh=True)
+    return st
+
+
+def fc_stage_hidden(avg, phase, sd, p="pfeat_corrector."):
+    """gfeat_hidden_kernel: raw = [avg | phase pairs normalised], hid_t = LeakyReLU(W_t0 raw + b) (M,1536), g_s = W_s3 LeakyReLU(W_s0 raw + b) + b (M,128)
+    (feature_correction.py:117-129)."""
+    dt = _dt()
+    avg, ph = np.asarray(avg, dt), np.asarray(phase, dt)
+    b, n = ph.shape[:2]
+    n1 = np.linalg.norm(ph[:, :, :2], axis=-1, keepdims=True)
+    n2 = np.linalg.norm(ph[:, :, 2:], axis=-1, keepdims=True)
+    raw = np.concatenate([np.broadcast_to(avg[:, None, :], (b, n, avg.shape[-1])), ph / np.concatenate([n1, n1, n2, n2], -1)], -1).astype(dt)
+    lrelu = lambda h: np.where(h > 0, h, dt(0.05) * h)
+    W = lambda k: np.asarray(sd[p + k], dt)
+    hid_t = lrelu(raw @ W("gfeat_mpl_t.0.weight").T + W("gfeat_mpl_t.0.bias"))
+    hs = lrelu(raw @ W("gfeat_mpl_s.0.weight").T + W("gfeat_mpl_s.0.bias"))
+    return hid_t.reshape(b * n, -1), (hs @ W("gfeat_mpl_s.3.weight").T + W("gfeat_mpl_s.3.bias")).reshape(b * n, -1)
+
+
+def fc_stage_bn(x, g_t, g_s, sd, p="pfeat_corrector."):
+    """featcorr_bn_kernel: y = BN1d(x + g_t) (M,3072), y_s = BN1d_s([x | g_s]) (M,3200), running statistics, eps 1e-5 (feature_correction.py:130-139)."""
+    dt = _dt()
+    x = np.asarray(x, dt)
+
+    def bn1d(z, name):
+        g, be = np.asarray(sd[f"{p}{name}.weight"], dt), np.asarray(sd[f"{p}{name}.bias"], dt)
+        m, v = np.asarray(sd[f"{p}{name}.running_mean"], dt), np.asarray(sd[f"{p}{name}.running_var"], dt)
+        return ((z - m) / np.sqrt(v + dt(1e-5)) * g + be).astype(dt)
+
+    return bn1d(x + np.asarray(g_t, dt), "bn_in"), bn1d(np.concatenate([x, np.asarray(g_s, dt)], -1), "bn_in_s")
+
+
+def fc_stages(x, cparams, sd, p="pfeat_corrector."):
+    """The corrector launch by launch (x (b,n,3072), cparams (b,n,3)): the GRU's stages, then hid_t, g_s, g_t, y, y_s, the attention block's stages
+    under "ts.<name>", att and out."""
+    dt = _dt()
+    x = _f32(x)
+    b, n, _ = x.shape
+    gsd = {k[len(p + "featnet."):]: v for k, v in sd.items() if k.startswith(p + "featnet.")}
+    tsd = {k[len(p + "featTencoder.0."):]: v for k, v in sd.items() if k.startswith(p + "featTencoder.0.")}
+    st = gru_stages(x, cparams, gsd)
+    st["hid_t"], st["g_s"] = fc_stage_hidden(_f32(st["avg"]), _f32(st["phase"]), sd, p)
+    st["g_t"] = linear(_f32(st["hid_t"]), sd[p + "gfeat_mpl_t.3.weight"], sd[p + "gfeat_mpl_t.3.bias"])
+    st["y"], st["y_s"] = fc_stage_bn(x.reshape(b * n, -1), _f32(st["g_t"]), _f32(st["g_s"]), sd, p)
+    ts = ts_stages(_f32(st["y"]).reshape(b, n, 128, -1), _f32(st["y_s"]).reshape(b, n, 128, -1), tsd)
+    st.update({"ts." + k: v for k, v in ts.items()})
+    st["att"] = ts["out"]
+    st["out"] = np.asarray(_f32(st["att"]).reshape(b * n, -1), dt) + np.asarray(x.reshape(b * n, -1), dt)
+    return st

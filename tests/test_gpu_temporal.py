@@ -1,6 +1,6 @@
 """The temporal branch (grnet.py:154-173): FeatCorrector (feature_correction.py:104-157) and the gait branch against goldens made by the reference's own code,
 frame shards gathered before the temporal branch, the attention block (attention_utils.py:261-270) on clips of 4 200 / 17 000 / 2 x 1 100 frames (per-query and
-blocked kernels, the > 64 KB LDS launch), and every form of the GRU recurrence (gait_feat_encoder.py:79-104; GRNET_OPT_GRU_MODE) on long sequences.
+blocked kernels), and every form of the GRU recurrence (gait_feat_encoder.py:79-104; GRNET_OPT_GRU_MODE) on long sequences.
 Regrouped by component in round 6; the tests themselves are unchanged."""
 import importlib
 import os
@@ -114,16 +114,24 @@ def test_attention_block_takes_clips_longer_than_4096_frames(pkg, oracle):
                         torch.zeros(1, t, 2).cuda(), 1, t)
     mg.close()
 
-def test_attention_block_large_lds_branch_17000_frames(pkg, oracle):
-    """The temporal attention keeps one softmax row over the clip's frames in LDS; beyond ~15 800 frames that is more than 64 KB and the
-    launcher raises the kernel's dynamic-LDS limit (up to the 160 KB of gfx950, from which the 32 768-frame limit follows; both read from
-    the device).  A 17 000-frame clip made of a 50-frame pattern repeated 340 times: every distinct key appears 340 times with the same
-    logit, so each frame's attention output -- and the clip means of the gate -- equal those of the 50-frame clip, which the CPU oracle
-    computes in a moment.  Covers the large-LDS launch, which no test ran before (round-3 advisor)."""
+def test_attention_block_17000_frames_periodic_clip_on_blocked_kernel(pkg, oracle):
+    """A 17 000-frame clip made of a 50-frame pattern repeated 340 times: every distinct key appears 340 times with the same logit, so each frame's attention
+    output -- and the clip means of the gate -- equal those of the 50-frame clip, which the CPU oracle computes in a moment.  What runs is the BLOCKED kernel
+    (every clip from 384 frames on): 532 key blocks of 32, split over the key parts the plan query reports (8 on 256 CUs), merged by the combine kernel -- asserted
+    below from grnet_tsattn_plan.  (The per-query kernel's launch with more than 64 KB of dynamic LDS, which this test was written for, is reachable only in
+    ablation builds since the blocked kernel's threshold became a constant.)  A whole lost key block moves this check's error to about 3x its bar and a handful
+    of lost keys passes it: the sharp check of a 17 000-frame clip -- non-periodic input, x_t and each part's (O, m, l) against float64 on sampled rows -- is
+    tests/test_gpu_temporal_stages.py::test_attention_block_every_launch_against_float64[1x17000]."""
+    import torch as _torch
+    from .helpers import temporal_checks as tc
     m = pkg.build_synthetic_model(max_frames=2, with_gru=True, with_tsattn=True, use_gait_feat=False)
     tsd = pkg.synth.make_tsattn_state_dict()
     x, xs = pkg.synth.make_tsattn_inputs(1, 50)
     reps = 340
+    plan = m.tsattn_plan(50 * reps)
+    assert plan["kernel"] == "blocked" and plan["key_blocks"] == 532 and plan["lds_bytes"] == 132608
+    assert plan["parts"] == tc.flash_key_parts(50 * reps, _torch.cuda.get_device_properties(0).multi_processor_count) and 1 <= plan["parts"] <= 8
+    assert m.tsattn_plan(50)["kernel"] == "per_query"
     xl, xsl = np.tile(x, (1, reps, 1, 1)), np.tile(xs, (1, reps, 1, 1))
     y = m.tsattn_forward(torch.from_numpy(xl).cuda(), torch.from_numpy(xsl).cuda()).cpu().numpy()
     ref = oracle.ts_attn_block(x, xs, tsd)

@@ -37,6 +37,9 @@ EXPORTS = {
     "grnet_gru_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "grnet_tsattn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grnet_tsattn_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "grnet_temporal_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "grnet_temporal_tap_layout": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "grnet_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "grnet_tune": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "grnet_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),

@@ -91,8 +91,17 @@ size_t featcorr_ws_floats(int b, int n) {
     return M * (1536 + 3072 + 128 + 3072 + 3200 + 3072) + tsattn_ws_floats(b, n) + 256;
 }
 
+hipError_t featcorr_tap_floats(int b, int n, size_t* floats) {
+    size_t ts = 0;
+    GRK_TRY(tsattn_tap_floats(b, n, &ts));
+    const size_t M = (size_t)b * n;
+    *floats = M * (3 + 1536 + 128 + 3072 + 3072 + 3200 + 3072 + 3072) + ts;
+    return hipSuccess;
+}
+
 hipError_t launch_gait_cparams(const float* cam, int cam_ld, const float* bbox, const float* cimg, float* cparams, int M, hipStream_t s) {
     GRK_TRY(launch_k(gait_cparams_kernel, dim3((M + 255) / 256), dim3(256), 0, s, cam, cam_ld, bbox, cimg, cparams, M));
+    GRK_TRY(tap("fc.cparams", cparams, {(size_t)M, 3}, s));
     return hipGetLastError();
 }
 
@@ -108,12 +117,19 @@ hipError_t launch_featcorr(const float* x, const float* avg, const float* phase,
     float* att = ys + M * 3200;
     float* tws = att + M * 3072;
     GRK_TRY(launch_k(gfeat_hidden_kernel, dim3((unsigned)M), dim3(256), 0, s, avg, phase, w, hid_t, g_s, n));
+    GRK_TRY(tap("fc.hid_t", hid_t, {M, 1536}, s));
+    GRK_TRY(tap("fc.g_s", g_s, {M, 128}, s));
     GRK_TRY(launch_gemm_nt_bias(hid_t, w.t3_w, w.t3_b, g_t, (int)M, 3072, 1536, 3072, s));
+    GRK_TRY(tap("fc.g_t", g_t, {M, 3072}, s));
     int blocks = (int)((M * 3200 + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     GRK_TRY(launch_k(featcorr_bn_kernel, dim3(blocks), dim3(256), 0, s, x, (const float*)g_t, (const float*)g_s, w, y, ys, (long)M));
+    GRK_TRY(tap("fc.y", y, {M, 3072}, s));
+    GRK_TRY(tap("fc.y_s", ys, {M, 3200}, s));
     GRK_TRY(launch_tsattn(y, ys, tw, tws, att, b, n, s));
+    GRK_TRY(tap("fc.att", att, {M, 3072}, s));
     GRK_TRY(launch_k(residual_add_kernel, dim3(blocks), dim3(256), 0, s, (const float*)att, x, out, (long)(M * 3072)));
+    GRK_TRY(tap("fc.out", out, {M, 3072}, s));
     return hipGetLastError();
 }
 

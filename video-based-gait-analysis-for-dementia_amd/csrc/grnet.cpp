@@ -127,6 +127,13 @@ struct GemmWorkspaceLease {
     GemmWorkspaceLease(const GemmWorkspaceLease&) = delete;
     GemmWorkspaceLease& operator=(const GemmWorkspaceLease&) = delete;
 };
+// The same for the tap sink of an armed temporal call: installed for the launchers of that call, gone on every way out of it.
+struct TapLease {
+    explicit TapLease(TapSink* t) { g_taps = t; }
+    ~TapLease() { g_taps = nullptr; }
+    TapLease(const TapLease&) = delete;
+    TapLease& operator=(const TapLease&) = delete;
+};
 
 struct DeviceGuard {
     int prev = -1;
@@ -251,6 +258,20 @@ struct grnet {
     // with a size seen before allocates nothing (graph-capturable, no allocator traffic per call).  Growing synchronises the device.
     float* temporal_ws = nullptr;
     size_t temporal_ws_floats = 0;
+    // grnet_temporal_taps: armed for the NEXT temporal call only; that call checks the buffer against what it will copy before it enqueues anything,
+    // installs the sink for its launchers (TapLease) and leaves the layout of what it copied in tap_sink.layout for grnet_temporal_tap_layout
+    TapSink tap_sink;
+    bool taps_armed = false;
+    int taps_begin(size_t need, const char* what) {
+        taps_armed = false;
+        if (tap_sink.floats < need)
+            return fail(GRNET_EINVAL, "the tap buffer holds " + std::to_string(tap_sink.floats) + " floats, " + what + " of this size copies " + std::to_string(need) +
+                                          " floats: nothing was enqueued");
+        tap_sink.used = 0;
+        tap_sink.layout.clear();
+        return 0;
+    }
+
     int temporal_scratch(size_t floats, float** out) {
         if (floats > temporal_ws_floats) {
             if (temporal_ws) { (void)hipDeviceSynchronize(); (void)hipFree(temporal_ws); temporal_ws = nullptr; temporal_ws_floats = 0; }
@@ -2138,6 +2159,12 @@ struct grnet {
                      const grnet_outputs_t& o, const grnet_gait_outputs_t& g, hipStream_t s) {
         if (int rc = gru_fault_check()) return rc;
         const size_t M = (size_t)b * T;
+        const bool taps = taps_armed;
+        if (taps) {
+            size_t need = 0;
+            if (featcorr_tap_floats(b, T, &need) != hipSuccess) { taps_armed = false; return fail(GRNET_EHIP, "device query for the tap layout failed"); }
+            if (int rc = taps_begin(need + gru_tap_floats(b, T), "a gait-correction call")) return rc;
+        }
         const size_t gru_need = M * 3072 * 2 + 2 * M * 900 + 2 * M * 600 + (size_t)b * 1200 + (size_t)b * 2 * kGruXbufU64PerSeq + 1024;
         auto al = [](size_t f) { return (f + 63) & ~(size_t)63; };         // every sub-buffer starts 256-byte aligned (16-byte vector loads, 8-byte granules)
         const size_t own = al(M * 3) + al((size_t)b * 3) + al(M * 4) + al(M * 3072);
@@ -2159,9 +2186,12 @@ struct grnet {
         w.xbuf = reinterpret_cast<unsigned long long*>(w.hfin + (((size_t)b * 1200 + 63) & ~(size_t)63));
         w.mode = gru_mode; w.fault = gru_fault_dev;
         float* fws = p + gru_need;
-        HIP_TRY(launch_gait_cparams(cam, cam_ld, bbox, cimg, cparams, (int)M, s));
-        HIP_TRY(launch_gru(plf, cparams, gruw, w, avg, phase, xc_buf, b, T, s));
-        HIP_TRY(launch_featcorr(plf, avg, phase, fcw, tsw, fws, new_plf, b, T, s));
+        {
+            TapLease tap_lease(taps ? &tap_sink : nullptr);   // the temporal launches only: the second head pass below is not tapped
+            HIP_TRY(launch_gait_cparams(cam, cam_ld, bbox, cimg, cparams, (int)M, s));
+            HIP_TRY(launch_gru(plf, cparams, gruw, w, avg, phase, xc_buf, b, T, s));
+            HIP_TRY(launch_featcorr(plf, avg, phase, fcw, tsw, fws, new_plf, b, T, s));
+        }
         for (size_t s0 = 0; s0 < M; s0 += (size_t)max_frames) {
             const int m = (int)std::min<size_t>((size_t)max_frames, M - s0);
             grnet_outputs_t oc{};
@@ -2452,6 +2482,9 @@ int grnet_gru_forward(grnet_t* h, const float* x, const float* cp, int b, int T,
     if (int rc = h->gru_fault_check()) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t rows = (size_t)b * T;
+    const bool taps = h->taps_armed;
+    if (taps) if (int rc = h->taps_begin(gru_tap_floats(b, T), "a GRU call")) return rc;
+    TapLease tap_lease(taps ? &h->tap_sink : nullptr);
     float* ws = nullptr;                                   // handle-owned scratch: no allocation once a size has been seen
     const size_t need = rows * 3072 * 2 + 2 * rows * 900 + 2 * rows * 600 + (size_t)b * 1200 + (size_t)b * 2 * kGruXbufU64PerSeq + 1024;
     if (int rc = h->temporal_scratch(kGemmWsFloats + need, &ws)) return rc;
@@ -2479,11 +2512,47 @@ int grnet_tsattn_forward(grnet_t* h, const float* x, const float* xs, int b, int
     if (!h->tsattn_ready)
         return h->fail(GRNET_ESTATE, "attention-block weights were not loaded (keys tsattn.* or pfeat_corrector.featTencoder.0.*)");
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool taps = h->taps_armed;
+    if (taps) {
+        size_t need = 0;
+        if (tsattn_tap_floats(b, n, &need) != hipSuccess) { h->taps_armed = false; return h->fail(GRNET_EHIP, "device query for the tap layout failed"); }
+        if (int rc = h->taps_begin(need, "an attention-block call")) return rc;
+    }
+    TapLease tap_lease(taps ? &h->tap_sink : nullptr);
     float* ws = nullptr;                                   // handle-owned scratch, like the GRU's
     if (int rc = h->temporal_scratch(kGemmWsFloats + tsattn_ws_floats(b, n), &ws)) return rc;
     GemmWorkspaceLease lease(ws, kGemmWsFloats);
     hipError_t e = launch_tsattn(x, xs, h->tsw, ws + kGemmWsFloats, y, b, n, s);
     if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("launch_tsattn: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int grnet_temporal_taps(grnet_t* h, float* buf_dev, size_t floats) {
+    if (!h) return GRNET_EINVAL;
+    if (!buf_dev || floats == 0) { h->taps_armed = false; return 0; }
+    h->tap_sink.buf = buf_dev;
+    h->tap_sink.floats = floats;
+    h->taps_armed = true;
+    return 0;
+}
+
+int grnet_temporal_tap_layout(grnet_t* h, char* buf, int buf_size) {
+    if (!h) return GRNET_EINVAL;
+    const std::string& out = h->tap_sink.layout;
+    if (!buf) return (int)out.size() + 1;
+    if ((int)out.size() + 1 > buf_size) return h->fail(GRNET_EINVAL, "buffer too small: the layout is " + std::to_string(out.size() + 1) + " bytes");
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return (int)out.size();
+}
+
+int grnet_tsattn_plan(grnet_t* h, int n, int32_t* plan) {
+    if (!h || !plan || n < 1) return GRNET_EINVAL;
+    DeviceGuard guard(h->device);                          // the CU count and the LDS limit are the handle's device's
+    if (n > tsattn_max_frames()) return h->fail(GRNET_EINVAL, "a clip of " + std::to_string(n) + " frames exceeds the attention block's limit of " +
+                                                             std::to_string(tsattn_max_frames()) + " frames per clip");
+    int p[4];
+    if (tsattn_plan(n, p) != hipSuccess) return h->fail(GRNET_EHIP, "device query failed");
+    for (int i = 0; i < 4; ++i) plan[i] = p[i];
     return 0;
 }
 

@@ -99,6 +99,23 @@ thread_local float* g_gemm_ws = nullptr;       // split-K partial sums: scratch 
 thread_local size_t g_gemm_ws_floats = 0;
 void set_gemm_workspace(float* ws, size_t floats) { g_gemm_ws = ws; g_gemm_ws_floats = floats; }
 
+thread_local TapSink* g_taps = nullptr;        // installed by the C entry points for ONE armed temporal call (grnet_temporal_taps)
+hipError_t tap_copy(const char* name, const float* src, std::initializer_list<size_t> shape, hipStream_t s) {
+    TapSink& t = *g_taps;
+    size_t count = 1;
+    std::string line = std::string("tap ") + name + " " + std::to_string(t.used);
+    for (size_t d : shape) { count *= d; line += " " + std::to_string(d); }
+    if (t.used + count > t.floats) return hipErrorInvalidValue;      // the entry point sized the buffer with *_tap_floats: never reached unless they disagree
+    GRK_TRY(hipMemcpyAsync(t.buf + t.used, src, count * sizeof(float), hipMemcpyDeviceToDevice, s));
+    t.used += count;
+    t.layout += line + "\n";
+    return hipSuccess;
+}
+size_t gru_tap_floats(int b, int T) {
+    const size_t rows = (size_t)b * T;
+    return rows * (2 * 3072 + 4 * 900 + 2 * 600 + 100 + 4) + (size_t)b * (1200 + 2 * 100 + 3);
+}
+
 hipError_t launch_gemm_nt_bias(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, int ldc, hipStream_t s) {
     if (K % 4 != 0) return hipErrorInvalidValue;
     const int blocks = ((N + 63) / 64) * ((M + 63) / 64);
@@ -108,6 +125,11 @@ hipError_t launch_gemm_nt_bias(const float* A, const float* B, const float* bias
         splits = (512 + blocks - 1) / blocks;
         if (splits > 16) splits = 16;
         if (splits > K / 128) splits = K / 128;
+    }
+    if (g_taps) {                                             // the census of GEMM shapes an armed call ran, with the slice count the launch below takes
+        int sp = splits;
+        if (sp > 1) sp = (K + (((K + sp - 1) / sp + 31) / 32 * 32) - 1) / (((K + sp - 1) / sp + 31) / 32 * 32);
+        g_taps->layout += "gemm " + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(K) + " " + std::to_string(sp) + "\n";
     }
     if (splits <= 1) {
         GRK_TRY(launch_k(gemm_nt_bias_f32, dim3((N + 63) / 64, (M + 63) / 64, 1), dim3(256), 0, s, A, B, bias, C, M, N, K, ldc, K, (size_t)0));
@@ -463,6 +485,9 @@ hipError_t launch_gru(const float* x, const float* cparams, GruWeights w, GruWor
     int blocks = (int)((rows * 3072 + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     GRK_TRY(launch_k(gru_prep_kernel, dim3(blocks), dim3(256), 0, s, x, cparams, w.cparam_w, xc, ws.xin, rows));
+    const size_t urows = (size_t)rows, ub = (size_t)b;
+    GRK_TRY(tap("gru.xc", xc, {urows, 3072}, s));
+    GRK_TRY(tap("gru.xin", ws.xin, {urows, 3072}, s));
     const float* layer_in = ws.xin;
     int in_size = 3072;
     float* layer_out[2] = {ws.l0, ws.l1};
@@ -470,6 +495,8 @@ hipError_t launch_gru(const float* x, const float* cparams, GruWeights w, GruWor
         for (int d = 0; d < 2; ++d) {
             e = launch_gemm_nt_bias(layer_in, w.w_ih[layer][d], w.b_ih[layer][d], ws.gi + (size_t)d * rows * 900, (int)rows, 900, in_size, 900, s);
             if (e != hipSuccess) return e;
+            static const char* const gi_name[2][2] = {{"gru.gi00", "gru.gi01"}, {"gru.gi10", "gru.gi11"}};
+            GRK_TRY(tap(gi_name[layer][d], ws.gi + (size_t)d * rows * 900, {urows, 900}, s));
         }
         const int split_env = ws.mode & 15;                  // GRNET_OPT_GRU_MODE; 0 = one workgroup per (sequence, direction)
         // the 8 slices of a (sequence, direction) spin on each other: every workgroup of the grid must be resident at once, i.e. the
@@ -494,19 +521,26 @@ hipError_t launch_gru(const float* x, const float* cparams, GruWeights w, GruWor
             GRK_TRY(launch_k(gru_recurrent_kernel, dim3(b, 2), dim3(1024), 0, s, ws.gi, w.w_hh[layer][0], w.w_hh[layer][1],
                              w.b_hh[layer][0], w.b_hh[layer][1], layer_out[layer], ws.hfin, layer * 600, b, T));
         }
+        GRK_TRY(tap(layer ? "gru.l1" : "gru.l0", layer_out[layer], {urows, 600}, s));
         layer_in = layer_out[layer];
         in_size = 600;
     }
+    GRK_TRY(tap("gru.hfin", ws.hfin, {ub, 1200}, s));
     // heads: hidden activations reuse the gi workspace
     float* hid = ws.gi;
     if ((e = launch_gemm_nt_bias(ws.hfin, w.speed_w0, w.speed_b0, hid, b, 100, 1200, 100, s)) != hipSuccess) return e;
+    GRK_TRY(tap("gru.hid_speed", hid, {ub, 100}, s));
     GRK_TRY(launch_k(mlp_out_kernel, dim3(b), dim3(64), 0, s, hid, w.speed_w2, w.speed_b2, y, 1, 3, 0, 0));
     float* hid2 = hid + (size_t)b * 100;
     if ((e = launch_gemm_nt_bias(ws.hfin, w.step_w0, w.step_b0, hid2, b, 100, 1200, 100, s)) != hipSuccess) return e;
+    GRK_TRY(tap("gru.hid_step", hid2, {ub, 100}, s));
     GRK_TRY(launch_k(mlp_out_kernel, dim3(b), dim3(64), 0, s, hid2, w.step_w2, w.step_b2, y, 2, 3, 1, 0));
+    GRK_TRY(tap("gru.avg", y, {ub, 3}, s));
     float* hid3 = hid2 + (size_t)b * 100;
     if ((e = launch_gemm_nt_bias(ws.l1, w.phase_w0, w.phase_b0, hid3, (int)rows, 100, 600, 100, s)) != hipSuccess) return e;
+    GRK_TRY(tap("gru.hid_phase", hid3, {urows, 100}, s));
     GRK_TRY(launch_k(mlp_out_kernel, dim3((unsigned)rows), dim3(64), 0, s, hid3, w.phase_w2, w.phase_b2, phase, 4, 4, 0, 1));
+    GRK_TRY(tap("gru.phase", phase, {urows, 4}, s));
     return hipGetLastError();
 }
 

@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <mutex>
+#include <string>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -367,6 +369,25 @@ constexpr size_t kGemmWsFloats = (size_t)16 * 128 * 4096;
 void set_gemm_workspace(float* ws, size_t floats);
 hipError_t launch_gemm_nt_bias(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, int ldc, hipStream_t s);
 
+// Temporal taps (grnet_temporal_taps): while a sink is installed on this thread, launch_gru / launch_tsattn / launch_featcorr / launch_gait_cparams enqueue a
+// device-to-device copy of each stage's output right behind the launch that wrote it -- the temporal scratch cannot be read after the call (x_t is gated in place,
+// yt | ys | x1 hold the key-part partials before their own values, the GRU's gi becomes the heads' hidden buffer).  The launches, their order, buffers and aliasing
+// are the production ones; without a sink tap() is one pointer test and enqueues nothing.  `layout` gets one line per copy, "tap <name> <offset> <dims...>", and
+// one per GEMM, "gemm <M> <N> <K> <splits>" (launch_gemm_nt_bias).
+struct TapSink {
+    float* buf = nullptr;
+    size_t floats = 0, used = 0;
+    std::string layout;
+};
+extern thread_local TapSink* g_taps;
+hipError_t tap_copy(const char* name, const float* src, std::initializer_list<size_t> shape, hipStream_t s);
+inline hipError_t tap(const char* name, const float* src, std::initializer_list<size_t> shape, hipStream_t s) {
+    return g_taps ? tap_copy(name, src, shape, s) : hipSuccess;
+}
+size_t gru_tap_floats(int b, int T);
+hipError_t tsattn_tap_floats(int b, int n, size_t* floats);
+hipError_t featcorr_tap_floats(int b, int n, size_t* floats);      // launch_gait_cparams + launch_featcorr (the attention block included)
+
 // TSAttnBlock (attention_utils.py:219-270) weights, reference layouts: Linear weights (out, in); jw1 (64,128,24), jw2 (128,64,24).
 struct TsAttnWeights {
     const float *n1_g, *n1_b, *n2_g, *n2_b;
@@ -379,6 +400,9 @@ constexpr int kTsAttnMaxFrames = 32768;
 int tsattn_max_frames();        // min(kTsAttnMaxFrames, what the CURRENT device's LDS per workgroup holds): the up-front refusal matches the device
 // x (b,n,3072) index c*24+j, xs (b,n,3200) index c*25+t -> y (b,n,3072); ws: tsattn_ws_floats(b, n) floats of scratch.
 hipError_t launch_tsattn(const float* x, const float* xs, const TsAttnWeights& w, float* ws, float* y, int b, int n, hipStream_t s);
+// what launch_tsattn does with a clip of n frames on the CURRENT device, from the functions it calls itself: plan[0] kernel (0 per-query, 1 blocked),
+// plan[1] key parts per (query tile, head) (1: no combine launch), plan[2] key blocks of 32 (per-query: 0), plan[3] dynamic LDS bytes of the attention launch
+hipError_t tsattn_plan(int n, int plan[4]);
 
 // FeatCorrector (feature_correction.py:104-157) pieces around the GRU and the attention block; BatchNorm1d folded to scale / shift at load.
 struct FeatCorrWeights {

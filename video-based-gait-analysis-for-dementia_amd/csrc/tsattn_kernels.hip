@@ -254,11 +254,17 @@ __global__ __launch_bounds__(256) void temporal_attn_combine_kernel(const float*
 
 // Key parts per (query tile, head) of a clip of n frames: the count that minimises rounds of workgroups per part on `cus` CUs (one workgroup per CU: 133 KB of
 // LDS), from n alone -- a clip's result does not depend on what else is in the batch.
+// A part's accumulators (O, l) run over its keys one block after the other in fp32, and their rounding grows with the square root of that chain: x_t against a
+// float64 reference, at the tensor's scale, is off by 1.2e-6 at 2 500 keys per part (10 000 frames in 4 parts), 3.4e-6 at 7 169 keys in one part and 7.5e-6 at
+// 32 768 keys in one part -- 18 x the rounding floor of a plain fp32 softmax(QK^T)V at that size (tests/test_gpu_temporal_stages.py).  So a clip of more than
+// 8 192 frames is split into parts of at most 4 096 keys (32 768 frames: 8 parts instead of 1; 32 rounds of workgroups / 8 instead of 4 / 1 on 256 CUs).
+constexpr int kFlashOnePartMaxKeys = 8192, kFlashMaxPartKeys = 4096;
 static int flash_key_parts(int n, int cus) {
     const long wgs = (long)((n + kFQ - 1) / kFQ) * kH;
-    int best = 1;
+    const int pmin = n <= kFlashOnePartMaxKeys ? 1 : std::min(kFlashMaxParts, (n + kFlashMaxPartKeys - 1) / kFlashMaxPartKeys);
+    int best = pmin;
     double best_cost = 1e30;
-    for (int p = 1; p <= kFlashMaxParts; ++p) {
+    for (int p = pmin; p <= kFlashMaxParts; ++p) {
         if (p > 1 && n / p < GRNET_AB(TSATTN_PART_KEYS, kFlashMinPartKeys)) break;
         const double cost = (double)((wgs * p + cus - 1) / cus) / p + 0.01 * p;          // rounds x part length (+ a little per part for the merge)
         if (cost < best_cost - 1e-9) { best_cost = cost; best = p; }
@@ -434,6 +440,25 @@ int tsattn_max_frames() {
     return (fm > 0 && fm - 1 <= pq) ? kTsAttnMaxFrames : pq;
 }
 
+hipError_t tsattn_plan(int n, int plan[4]) {
+    const bool flash = tsattn_flash_min() > 0 && n >= tsattn_flash_min();
+    int cus = 0;
+    if (flash) GRK_TRY(device_cu_count(&cus));
+    plan[0] = flash ? 1 : 0;
+    plan[1] = flash ? flash_key_parts(n, cus) : 1;
+    plan[2] = flash ? (n + kFK - 1) / kFK : 0;
+    plan[3] = flash ? (int)(kFlashLdsFloats * sizeof(float)) : (int)((256 + (size_t)n + 256) * sizeof(float));
+    return hipSuccess;
+}
+
+hipError_t tsattn_tap_floats(int b, int n, size_t* floats) {
+    int plan[4];
+    GRK_TRY(tsattn_plan(n, plan));
+    const size_t R = (size_t)b * n;
+    *floats = R * (2 * 3 * kE + 4 * kE + 4 * kD) + (size_t)b * 4 * kE + (plan[1] > 1 ? (size_t)plan[1] * R * (kE + 2 * kH) : 0);
+    return hipSuccess;
+}
+
 hipError_t launch_tsattn(const float* x, const float* xs, const TsAttnWeights& w, float* ws, float* y, int b, int n, hipStream_t s) {
     if (b < 1 || n < 1 || n > tsattn_max_frames()) return hipErrorInvalidValue;
     const bool flash = tsattn_flash_min() > 0 && n >= tsattn_flash_min();
@@ -459,7 +484,9 @@ hipError_t launch_tsattn(const float* x, const float* xs, const TsAttnWeights& w
     float* ys = yt + R * kD;
     float* x1 = ys + R * kD;
     GRK_TRY(launch_gemm_nt_bias(x, w.qkv_t_w, w.qkv_t_b, qkv_t, (int)R, 3 * kE, kD, 3 * kE, s));
+    GRK_TRY(tap("ts.qkv_t", qkv_t, {R, (size_t)3 * kE}, s));
     GRK_TRY(launch_gemm_nt_bias(xs, w.qkv_s_w, w.qkv_s_b, qkv_s, (int)R, 3 * kE, kD + kF, 3 * kE, s));
+    GRK_TRY(tap("ts.qkv_s", qkv_s, {R, (size_t)3 * kE}, s));
     // clips of >= 384 frames: the blocked kernel (keys / values read once per 128 queries, fp32 matrix cores); shorter clips: one workgroup per query
     if (flash) {
         static PerDeviceOnce fattr;
@@ -475,23 +502,37 @@ hipError_t launch_tsattn(const float* x, const float* xs, const TsAttnWeights& w
         float* part_ml = part_o + (size_t)kparts * R * kE;
         GRK_TRY(launch_k(temporal_attn_flash_kernel, dim3((n + kFQ - 1) / kFQ, kH, b * kparts), dim3(64 * kFW), kFlashLdsFloats * sizeof(float), s, (const float*)qkv_t, xt, n,
                          kparts, part_o, part_ml));
+        if (kparts > 1) {
+            GRK_TRY(tap("ts.part_o", part_o, {(size_t)kparts, R, (size_t)kE}, s));
+            GRK_TRY(tap("ts.part_ml", part_ml, {(size_t)kparts, R, (size_t)kH, 2}, s));
+        }
         if (kparts > 1) GRK_TRY(launch_k(temporal_attn_combine_kernel, dim3((unsigned)R), dim3(256), 0, s, (const float*)part_o, (const float*)part_ml, xt, R, kparts));
     } else {
         GRK_TRY(launch_k(temporal_attn_kernel, dim3(n, kH, b), dim3(256), attn_lds, s, qkv_t, xt, n));
     }
+    GRK_TRY(tap("ts.x_t", xt, {R, (size_t)kE}, s));
     GRK_TRY(launch_k(spatial_attn_kernel, dim3((unsigned)R, kH), dim3(256), 0, s, qkv_s, xsp));
+    GRK_TRY(tap("ts.x_s", xsp, {R, (size_t)kE}, s));
     {   // partial sums in yt (free until the fc_t GEMM writes it: nblk x 2000 <= n x 3072 floats per clip)
         const int nblk = (n + kMeanRows - 1) / kMeanRows;
         GRK_TRY(launch_k(gate_mean_partial_kernel, dim3((2 * kE + 255) / 256, b, nblk), dim3(256), 0, s, (const float*)xt, (const float*)xsp, yt, n, nblk));
         GRK_TRY(launch_k(gate_mean_final_kernel, dim3((2 * kE + 255) / 256, b), dim3(256), 0, s, (const float*)yt, mean, n, nblk));
     }
+    GRK_TRY(tap("ts.mean", mean, {(size_t)b, (size_t)2 * kE}, s));
     GRK_TRY(launch_gemm_nt_bias(mean, w.ts_w, w.ts_b, logits, b, 2 * kE, 2 * kE, 2 * kE, s));
+    GRK_TRY(tap("ts.logits", logits, {(size_t)b, (size_t)2 * kE}, s));
     const long total = (long)R * kE;
     GRK_TRY(launch_k(gate_apply_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, logits, xt, xsp, n, total));
+    GRK_TRY(tap("ts.x_t_gated", xt, {R, (size_t)kE}, s));
+    GRK_TRY(tap("ts.x_s_gated", xsp, {R, (size_t)kE}, s));
     GRK_TRY(launch_gemm_nt_bias(xt, w.fc_t_w, w.fc_t_b, yt, (int)R, kD, kE, kD, s));
+    GRK_TRY(tap("ts.y_t", yt, {R, (size_t)kD}, s));
     GRK_TRY(launch_gemm_nt_bias(xsp, w.fc_s_w, w.fc_s_b, ys, (int)R, kD, kE, kD, s));
+    GRK_TRY(tap("ts.y_s", ys, {R, (size_t)kD}, s));
     GRK_TRY(launch_k(residual_ln_kernel, dim3((unsigned)R), dim3(256), 0, s, x, yt, ys, w.n1_g, w.n1_b, x1));
+    GRK_TRY(tap("ts.x1", x1, {R, (size_t)kD}, s));
     GRK_TRY(launch_k(jwff_ln_kernel, dim3((unsigned)R), dim3(256), 0, s, x1, w.jw1, w.jw2, w.n2_g, w.n2_b, y));
+    GRK_TRY(tap("ts.out", y, {R, (size_t)kD}, s));
     return hipGetLastError();
 }
 

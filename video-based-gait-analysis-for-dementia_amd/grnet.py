@@ -550,6 +550,51 @@ class GRNet:
                                                                      stream), "grnet_debug_tensor")
         return out
 
+    def tsattn_plan(self, n):
+        """What the attention block does with a clip of n frames on this device (grnet_tsattn_plan):
+        dict(kernel 'per_query' | 'blocked', parts, key_blocks, lds_bytes)."""
+        plan = (C.c_int32 * 4)()
+        _lib.check(self._lib, self._h, self._lib.grnet_tsattn_plan(self._h, int(n), plan), "grnet_tsattn_plan")
+        return {"kernel": "blocked" if plan[0] else "per_query", "parts": plan[1], "key_blocks": plan[2], "lds_bytes": plan[3]}
+
+    def arm_temporal_taps(self, buf):
+        """Arm the taps of the NEXT gru_forward / tsattn_forward / gait_correct (grnet_temporal_taps): ``buf`` is a float32 device
+        tensor that receives a copy of every launch's output; read it with temporal_taps() after the call.  None disarms."""
+        if buf is None:
+            _lib.check(self._lib, self._h, self._lib.grnet_temporal_taps(self._h, None, 0), "grnet_temporal_taps")
+            return
+        if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device.type != "cuda":
+            raise ValueError("the tap buffer must be a contiguous float32 device tensor")
+        _lib.check(self._lib, self._h, self._lib.grnet_temporal_taps(self._h, buf.data_ptr(), buf.numel()), "grnet_temporal_taps")
+
+    def temporal_tap_layout(self):
+        """(taps, gemms) of the last armed call: taps {name: (offset, shape)} in launch order, gemms [(M, N, K, slices)]."""
+        need = self._lib.grnet_temporal_tap_layout(self._h, None, 0)
+        text = C.create_string_buffer(max(need, 1))
+        rc = self._lib.grnet_temporal_tap_layout(self._h, text, need)
+        if rc < 0:
+            _lib.check(self._lib, self._h, rc, "grnet_temporal_tap_layout")
+        taps, gemms = {}, []
+        for line in text.value.decode().splitlines():
+            f = line.split()
+            if f[0] == "tap":
+                taps[f[1]] = (int(f[2]), tuple(int(v) for v in f[3:]))
+            elif f[0] == "gemm":
+                gemms.append(tuple(int(v) for v in f[1:5]))
+        return taps, gemms
+
+    def temporal_taps(self, buf):
+        """Views into ``buf`` of everything the last armed call copied: {name: tensor of the tap's shape}."""
+        taps, _ = self.temporal_tap_layout()
+        flat = buf.reshape(-1)
+        out = {}
+        for name, (off, shape) in taps.items():
+            count = 1
+            for d in shape:
+                count *= d
+            out[name] = flat[off:off + count].reshape(shape)
+        return out
+
     def gru_forward(self, x, cparams):
         """BidirectionalModel.forward on this handle's GRU weights (keys gru.* / pfeat_corrector.featnet.*)."""
         self.finalize()
