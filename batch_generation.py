@@ -44,7 +44,7 @@ def flush_windows(n_videos, max_vid):
 
 
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
-                 model_factory=None, backend="nccl", exchange="torch"):
+                 model_factory=None, backend="nccl", exchange="torch", full_arena=False):
     """model_factory(local_rank) -> model and backend="gloo" are the seam of the CPU tests (tests/test_host_cpu.py): the window / plan /
     run / gather / flush logic below then runs under two gloo ranks with a stand-in model and tensors on the CPU.
     exchange: "torch" = the window's all-gather through the launcher's process group; "capi" = through the C ABI's own RCCL communicator
@@ -73,12 +73,16 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     if model_factory is not None:
         model = model_factory(local_rank)
     elif synthetic_weights:
-        model = pkg.build_synthetic_model(max_frames=max_frames, device_id=local_rank, with_gru=False, dtype=dtype)
+        model = pkg.build_synthetic_model(max_frames=max_frames, device_id=local_rank, with_gru=False, dtype=dtype, compact_arena=not full_arena)
     else:
-        model = pkg.GRNet(writer=None, seqlen=100, featcorr=None, max_frames=max_frames, device_id=local_rank, dtype=dtype)
+        model = pkg.GRNet(writer=None, seqlen=100, featcorr=None, max_frames=max_frames, device_id=local_rank, dtype=dtype, compact_arena=not full_arena)
         ckpt = torch.load(pretrained_file, map_location="cpu")["gen_state_dict"]
         model.load_state_dict(ckpt, strict=True)              # batch_generation.py:218
         model.finalize()
+    if rank == 0 and hasattr(model, "arena_info"):
+        ai = model.arena_info()
+        print(f"Activation arena: {ai['bytes'] / 2**20:.0f} MiB for calls of up to {max_frames} frames "
+              f"({'one buffer per tensor' if full_arena else 'buffers shared by liveness'}; the full layout takes {ai['full_bytes'] / 2**20:.0f} MiB)")
     chunk = int(chunk or max_frames)
     dev = torch.device("cuda", local_rank) if on_gpu else torch.device("cpu")
     comm = None
@@ -149,7 +153,9 @@ if __name__ == "__main__":
     p.add_argument("--max_frames", type=int, default=400, help="frames per grnet_forward call (activation buffers are sized for it; 400 = the reference's MAX_seqlen: larger calls run the convolutions at a higher rate, 5 800 / 5 880 / 5 930 frames/s at 128 / 256 / 400)")
     p.add_argument("--chunk", type=int, default=None, help="frames per multi-GPU work item (default: --max_frames)")
     p.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
+    p.add_argument("--full_arena", action="store_true", help="one buffer per intermediate tensor (the library's default layout: 41 GB at 400 frames in f32 "
+                   "against 5.5 GB); this script never reads intermediates, so it shares buffers by liveness -- same launches, bit-identical outputs")
     p.add_argument("--exchange", choices=("torch", "capi"), default="torch", help="multi-GPU: the all-gather through torch.distributed or through the C ABI's grnet_allgather")
     a = p.parse_args()
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
-                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange)
+                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena)

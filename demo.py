@@ -39,10 +39,10 @@ def load_cfg(path):
 def build_model(pkg, args, seqlen):
     import torch
     if args.synthetic_weights:
-        return pkg.build_synthetic_model(max_frames=args.max_frames, with_gru=False, dtype=args.dtype)
+        return pkg.build_synthetic_model(max_frames=args.max_frames, with_gru=False, dtype=args.dtype, compact_arena=not args.full_arena)
     if not args.ckpt:
         sys.exit("!!! Please provide a pretrained checkpoint (--ckpt) or --synthetic_weights !!!")
-    model = pkg.GRNet(writer=None, seqlen=seqlen, featcorr=None, max_frames=args.max_frames, dtype=args.dtype)
+    model = pkg.GRNet(writer=None, seqlen=seqlen, featcorr=None, max_frames=args.max_frames, dtype=args.dtype, compact_arena=not args.full_arena)
     ckpt = torch.load(args.ckpt, map_location="cpu")["gen_state_dict"]
     print(f"Load pretrained weights from '{args.ckpt}'")
     res = model.load_state_dict(ckpt, strict=False)
@@ -76,6 +76,9 @@ def main(args):
         if tracking[pid]["frames"].shape[0] < MIN_NUM_FRAMES:
             del tracking[pid]
     model = build_model(pkg, args, cfg["DATASET"]["SEQLEN"])
+    ai = model.arena_info()
+    print(f"Activation arena: {ai['bytes'] / 2**20:.0f} MiB for calls of up to {args.max_frames} frames "
+          f"({'one buffer per tensor' if args.full_arena else 'buffers shared by liveness'}; the full layout takes {ai['full_bytes'] / 2**20:.0f} MiB)")
     smpl_tables = None
     if args.smooth:
         if args.synthetic_weights:
@@ -148,6 +151,8 @@ def parser():
     p.add_argument("--smpl_dir", type=str, default="data/smpl_data")
     p.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="f32: the reference's precision; bf16: bf16 storage, fp32 accumulation")
     p.add_argument("--max_frames", type=int, default=64, help="frames per grnet_forward call (activation buffers are sized for it)")
+    p.add_argument("--full_arena", action="store_true", help="one buffer per intermediate tensor (the library's default layout, 7.5x the memory in f32); "
+                   "this script never reads intermediates, so it shares buffers by liveness -- same launches, bit-identical outputs")
     return p
 
 

@@ -53,6 +53,47 @@ typedef struct grnet grnet_t;
  * (pooling sums, MLPs, SMPL) -- BASELINE configs 3 and 5; inputs and outputs of every entry point stay fp32. */
 int grnet_create(grnet_t** out_handle, int device_id, int dtype, int max_frames);
 
+/* The same constructor with named precisions and flags; grnet_create(out, dev, p, n) == grnet_create_ex(out, dev, p, n, 0).
+ * GRNET_CREATE_COMPACT_ARENA: intermediate tensors whose lifetimes cannot overlap share memory: 13.7 MB per frame of
+ * max_frames in fp32 (14.2 MB on a bf16 handle) against the 103.8 MB of the default layout, which gives every intermediate its own buffer.  A tensor may
+ * lie under a later one only if every launch that reads or writes it is ordered before every launch that writes the later one by the
+ * plan's OWN read-after-write dependencies, in every launch form (any call size, tuning table or GRNET_OPT_BF16_CHAIN mask): no launch,
+ * event or wait is added or moved, and every output of every entry point is bit-identical to a default handle's.
+ * What a compact handle cannot do: grnet_debug_tensor serves only tensors nothing is placed over later in the forward (cat and the views
+ * that write it, head.heat, head.smpl_feats, head.cam_shape and whatever else the layout leaves last in its bytes -- a static property of
+ * the layout, listed by grnet_arena_layout); every other name returns GRNET_ESTATE.  grnet_tune and grnet_time_conv work as before (they
+ * leave garbage in the buffers on either kind of handle).
+ * GRNET_EINVAL: an unknown flag or precision, max_frames outside [1, 2048]. */
+#define GRNET_PRECISION_F32 0
+#define GRNET_PRECISION_BF16 1
+#define GRNET_CREATE_COMPACT_ARENA 1u
+int grnet_create_ex(grnet_t** out_handle, int device_id, int precision, int max_frames, unsigned flags);
+
+/* The activation arena of a handle that grnet_create_ex(precision, max_frames, flags) would make, computed on the host: no handle, no
+ * device, no HIP call (a machine without a GPU can size a deployment, and the tests prove the layout there).
+ * info[0] bytes this layout allocates, info[1] bytes the default (full) layout allocates, info[2] a lower bound for any layout under the
+ * sharing rule -- the largest sum of tensors alive across one launch (written by it or before it, used by it or after it), over every op
+ * and every launch group, plus the fixed blocks --, info[3] the number of tensors, info[4] how many of them share bytes with another.
+ * All three sizes include the 256-byte zero block in front and the 256 bytes of tail. */
+int grnet_arena_query(int precision, int max_frames, unsigned flags, int64_t* info /* 5 */);
+/* The same layout as text, one line per item:
+ *   tensor <id> <debug name or -> <floats per frame> <offset in floats from the arena's base>
+ *   op <index> <kind> reads <tensor ids...> writes <tensor ids...>      the plan in the order it is written; the last one, COPYOUT, stands
+ *                                                                       for the forward's copies of cat / head.heat / head.smpl_feats
+ *   group <op indices...>                                               ops that some launch form runs as ONE launch (bf16 kernel groups)
+ * A tensor occupies floats-per-frame x max_frames floats rounded up to 256 bytes (bf16 handles size their buffers in floats as well).
+ * buf NULL: returns the bytes needed; else the length written, or GRNET_EINVAL if size is too small. */
+int grnet_arena_layout(int precision, int max_frames, unsigned flags, char* buf, int size);
+/* info[0..4] of grnet_arena_query for a live handle (equal to the query's for the handle's precision, max_frames and flags). */
+int grnet_arena_info(grnet_t* h, int64_t* info /* 5 */);
+/* Diagnostic: fills the whole arena behind the leading zero block with a 32-bit pattern (hipMemsetD32Async on `stream`).  A forward reads
+ * nothing it did not write, so its outputs do not depend on the pattern (tests/test_gpu_compact_arena.py). */
+int grnet_arena_fill(grnet_t* h, uint32_t pattern, void* stream);
+/* The assignment itself, on any conflict graph: n buffers of sizes[i] bytes, n_pairs pairs (conflict_pairs[2k], conflict_pairs[2k+1]) that
+ * may not overlap.  Largest buffer first (ties: lowest index), each at the lowest 256-byte aligned offset where it overlaps no conflicting
+ * buffer placed before it: a deterministic function of its arguments.  offsets[i] in bytes, *total = the end of the last buffer. */
+int grnet_arena_assign(int n, const int64_t* sizes, int n_pairs, const int32_t* conflict_pairs, int64_t* offsets, int64_t* total);
+
 /* model.load_state_dict(...) -- demo.py:116-122, batch_generation.py:214-218, and
  * GRNet.load_pare_dict / load_ckpt_w_prefix -- grnet.py:93-109, lib/utils/utils.py:185-196.
  * Called once per checkpoint tensor under its REFERENCE key name ("backbone.conv1.weight",
@@ -338,7 +379,8 @@ int grnet_crop_normalise_cv_maps(grnet_t* h, const unsigned char* images_dev, in
  * hrnet.py:469-536 and pare.py:305-336.
  * GRNET_EINVAL if n_frames is outside [1, frames of the last forward] (nothing is copied); GRNET_ESTATE if the last forward did not
  * write the tensor to memory (bf16, large calls: a convolution inside a row-walking or chain launch other than its last one, e.g.
- * stem_conv1 from 64 frames on) -- the buffer would hold an earlier forward's values. */
+ * stem_conv1 from 64 frames on) -- the buffer would hold an earlier forward's values; GRNET_ESTATE as well on a compact-arena handle
+ * (grnet_create_ex) for every tensor a later one of the forward is placed over. */
 int grnet_debug_tensor(grnet_t* h, const char* name, int n_frames, float* out_dev, int64_t* shape_out, void* stream);
 
 /* ---- the exchange: all-gather of the per-frame records of a sharded clip (SURVEY 8b `grnet_allgather`, 8e) -------------------------------------

@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("GRNET_LIB_PATH") or os.path.join(_HERE, "libgrnet_hip
 
 OK, EINVAL, ENOENT, ENOMEM, EHIP, ESTATE = 0, -22, -2, -12, -5, -1
 DTYPE_F32, DTYPE_I64 = 0, 1
+PRECISION_F32, PRECISION_BF16 = 0, 1
+CREATE_COMPACT_ARENA = 1
 JOINT_REGRESSOR_MAX_ROWS = 64
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
@@ -30,6 +32,13 @@ class GaitOutputs(C.Structure):
 
 EXPORTS = {
     "grnet_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
+    "grnet_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_uint]),
+    "grnet_arena_query": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int64)]),
+    "grnet_arena_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint, C.c_char_p, C.c_int]),
+    "grnet_arena_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "grnet_arena_fill": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "grnet_arena_assign": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
     "grnet_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int]),
     "grnet_load_smpl": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "grnet_finalize_weights": (C.c_int, [C.c_void_p]),

@@ -8,7 +8,8 @@
 //   regressor lib/models/pare.py:52-91, lib/models/smpl.py:149-191
 // Data layout: fp32 NCHW, one buffer per intermediate tensor sized for max_frames images (the whole
 // activation set is ~103 MB / frame, so 1 250 frames still fit the 288 GB of HBM3E); image stride is
-// independent of the number of frames in a call, so a plan built once serves any n <= max_frames.
+// independent of the number of frames in a call, so a plan built once serves any n <= max_frames.  grnet_create_ex(GRNET_CREATE_COMPACT_ARENA)
+// lets tensors whose lifetimes cannot overlap share memory instead (plan_arena: ~13.7 MB / frame, same launches, same bits).
 #include "../../include/grnet_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -76,6 +77,7 @@ struct ConvLayer {
     int chain = -1, chain_pos = 0;   // bf16: member chain_pos of BasicBlock chain `chain` (conv_bf16_chain.hip); position 0 launches the whole chain in large calls
     int roll = -1, roll_pos = 0;     // bf16: member roll_pos of the row-walking launch `roll` (conv_bf16_roll.hip: the stem pair, a layer1 Bottleneck); position 0 launches it in large calls
     std::map<int, int> tuned;   // n_frames -> launch configuration (tile hint) measured fastest by grnet_tune
+    int out_slot = -1;          // the planned buffer `out` is a view of (annotate_plan): tensor identity once buffers share addresses
 };
 
 // The up half of one HR module's fuse layer (hr_fuse.hip): outputs 0 .. nb-2 in one launch.
@@ -114,6 +116,7 @@ struct Op {
     int follow = -1;          // plan index of an op this one depends on and whose stream it must share (the lane scheduler keeps them together)
     std::vector<int> waits;   // ops (on other lanes) whose completion event this op waits for
     bool record = false;      // some op on another lane consumes this op's output
+    std::vector<int> rd, wr;  // planned buffers (slot indices) the op reads / writes (annotate_plan): dependency tracking is keyed on these, never on addresses
 };
 
 constexpr int kLanes = 8;            // streams available to the lane scheduler (the hand-written plan uses 4)
@@ -143,6 +146,37 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
+
+// Offsets for n buffers of which some pairs may not overlap (grnet_arena_assign): largest first (ties: lowest index), each at the lowest
+// aligned offset where it overlaps no conflicting buffer placed before it.  A deterministic function of (sizes, conflicts).  Sizes, offsets
+// and the total are in one unit (bytes at the ABI, floats inside the library); `align` is in that unit.
+void arena_first_fit(const std::vector<int64_t>& sizes, const std::vector<std::vector<int>>& adj, int64_t align, std::vector<int64_t>& off, int64_t* total) {
+    const int n = (int)sizes.size();
+    std::vector<int64_t> sz(n);
+    for (int i = 0; i < n; ++i) sz[i] = (sizes[i] + align - 1) / align * align;
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sz[a] > sz[b]; });
+    off.assign(n, 0);
+    std::vector<char> placed(n, 0);
+    std::vector<std::pair<int64_t, int64_t>> busy;
+    int64_t end = 0;
+    for (int t : order) {
+        busy.clear();
+        for (int u : adj[t])
+            if (placed[u] && sz[u] > 0) busy.emplace_back(off[u], off[u] + sz[u]);
+        std::sort(busy.begin(), busy.end());
+        int64_t cur = 0;
+        for (auto& iv : busy) {
+            if (cur + sz[t] <= iv.first) break;
+            cur = std::max(cur, iv.second);
+        }
+        off[t] = cur;
+        placed[t] = 1;
+        end = std::max(end, cur + sz[t]);
+    }
+    *total = end;
+}
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
@@ -806,6 +840,7 @@ struct grnet {
         op.kind = Op::POOL; ops.push_back(op);
         op.kind = Op::TAIL; ops.push_back(op);
         op.kind = Op::SMPL; ops.push_back(op);
+        annotate_plan();
     }
 
     float* resolve_ptr(float* tag) const {
@@ -825,19 +860,16 @@ struct grnet {
     }
 
     int allocate() {
-        size_t total = 64;   // leading zero block
-        std::vector<size_t> offs;
-        for (auto& pr : pending) {
-            offs.push_back(total);
-            size_t fl = pr.second * (size_t)max_frames;
-            total += (fl + 63) / 64 * 64;               // 256-byte aligned buffers
-        }
-        total += 64;                                    // 256 bytes of tail: conv_wino4s_f32's 16-byte row loads on 7-wide maps touch (and mask) one float past a row,
-                                                        // i.e. 4 bytes past the LAST buffer's end for its last row -- they stay inside the arena
+        // 64 floats of leading zero block, 256-byte aligned buffers (one after the other, or shared by liveness: plan_arena), 256 bytes of tail:
+        // conv_wino4s_f32's 16-byte row loads on 7-wide maps touch (and mask) one float past a row, i.e. 4 bytes past the LAST buffer's end
+        // for its last row -- they stay inside the arena (in a compact one such a masked read may land in another tenant's bytes)
+        if (plan_arena(compact, arena_plan)) return fail(GRNET_ESTATE, "the activation arena could not be planned: a launch group or the assignment violates the sharing rule");
+        const std::vector<int64_t>& offs = arena_plan.off;
+        const size_t total = (size_t)arena_plan.total;
         arena_floats = total;
         void* q = nullptr;
         if (hipMalloc(&q, total * sizeof(float)) != hipSuccess)
-            return fail(GRNET_ENOMEM, "hipMalloc of the activation arena (" + std::to_string(total * 4 >> 20) + " MiB) failed");
+            return fail(GRNET_ENOMEM, std::string("hipMalloc of the ") + (compact ? "compact " : "") + "activation arena (" + std::to_string(total * 4 >> 20) + " MiB) failed");
         arena = static_cast<float*>(q);
         if (hipMemset(arena, 0, 64 * sizeof(float)) != hipSuccess) return fail(GRNET_EHIP, "hipMemset failed");
         zeros = arena;
@@ -878,46 +910,230 @@ struct grnet {
         return 0;
     }
 
-    // Read-after-write edges between lanes.  Every op writes a buffer nobody has written before (no
-    // buffer reuse; the writers of the concat buffer own disjoint channel slices), so RAW edges are the
-    // only hazards inside one forward; forwards are separated by the join at the end of enqueue().
-    // Buffers an op reads / the buffer it writes (nullptr: caller-owned outputs).
-    void op_reads(const Op& op, std::vector<const float*>& r) const {
+    // Read-after-write edges between lanes.  Every op writes a tensor nobody has written before (the writers of the concat buffer own
+    // disjoint channel slices), so RAW edges are the only hazards the schedule has to order inside one forward; forwards are separated by
+    // the join at the end of enqueue().  A tensor is a planned buffer (slot), not an address and not a view: in a compact arena
+    // (GRNET_CREATE_COMPACT_ARENA) several tensors live at one address, and the sharing rule of plan_arena() makes the RAW edges computed
+    // here order them as well -- a compact handle gets exactly the edges, lanes and events of a full one.
+    // Slots an op reads / writes (-1, dropped: the caller's frames).  Valid on the unresolved plan only (views still carry their tag).
+    int slot_of(const View& v) const {
+        const uintptr_t t = reinterpret_cast<uintptr_t>(v.p);
+        if (t == ~(uintptr_t)0 || t == 0) return -1;
+        auto it = view_slot.find((int)(t - 1));
+        return it == view_slot.end() ? -1 : (int)it->second;
+    }
+    void op_reads(const Op& op, std::vector<int>& r) const {
         r.clear();
+        auto put = [&](const View& v) { const int s = slot_of(v); if (s >= 0) r.push_back(s); };
         switch (op.kind) {
             case Op::CONV: {
                 const ConvLayer& L = convs[op.conv_idx];
-                r.push_back(L.in.p);
-                if (L.in2.c) r.push_back(L.in2.p);
-                for (auto& a : L.adds) r.push_back(a.v.p);
+                put(L.in);
+                if (L.in2.c) put(L.in2);
+                for (auto& a : L.adds) put(a.v);
                 break;
             }
             case Op::SUM:
-                for (auto& a : sum_views[op.conv_idx].second) r.push_back(a.v.p);
+                for (auto& a : sum_views[op.conv_idx].second) put(a.v);
                 break;
-            case Op::BILINEAR: r.push_back(op.bin.p); break;
+            case Op::BILINEAR: put(op.bin); break;
             case Op::FUSEUP:
             {
                 const FuseUpPlan& fp = fuse_ups[op.conv_idx];
-                for (size_t j = fp.only < 0 ? 0 : fp.only; j < fp.xs.size(); ++j) r.push_back(fp.xs[j].p);
+                for (size_t j = fp.only < 0 ? 0 : fp.only; j < fp.xs.size(); ++j) put(fp.xs[j]);
                 for (size_t i = 0; i < fp.extra.size(); ++i)
-                    if (fp.only < 0 || fp.only == (int)i) for (auto& v : fp.extra[i]) r.push_back(v.p);
+                    if (fp.only < 0 || fp.only == (int)i) for (auto& v : fp.extra[i]) put(v);
             }
                 break;
-            case Op::POOL: r.push_back(v_heat.p); r.push_back(v_smpl_feats.p); r.push_back(v_csmap.p); break;
+            case Op::POOL: put(v_heat); put(v_smpl_feats); put(v_csmap); break;
             default: break;                                     // TAIL / SMPL follow POOL on lane 0
         }
     }
-    void op_writes(const Op& op, std::vector<const float*>& w) const {
+    void op_writes(const Op& op, std::vector<int>& w) const {
         w.clear();
-        if (op.kind == Op::CONV) w.push_back(convs[op.conv_idx].out.p);
-        else if (op.kind == Op::SUM) w.push_back(sum_views[op.conv_idx].first.p);
-        else if (op.kind == Op::BILINEAR) w.push_back(op.bout.p);
-        else if (op.kind == Op::CONVERT) w.push_back(v_in8.p);
+        auto put = [&](const View& v) { const int s = slot_of(v); if (s >= 0) w.push_back(s); };
+        if (op.kind == Op::CONV) put(convs[op.conv_idx].out);
+        else if (op.kind == Op::SUM) put(sum_views[op.conv_idx].first);
+        else if (op.kind == Op::BILINEAR) put(op.bout);
+        else if (op.kind == Op::CONVERT) put(v_in8);
         else if (op.kind == Op::FUSEUP) {
             const FuseUpPlan& fp = fuse_ups[op.conv_idx];
-            for (size_t i = 0; i < fp.outs.size(); ++i) if (fp.only < 0 || fp.only == (int)i) w.push_back(fp.outs[i].p);
+            for (size_t i = 0; i < fp.outs.size(); ++i) if (fp.only < 0 || fp.only == (int)i) put(fp.outs[i]);
         }
+    }
+    // End of build_plan(): every op, convolution and named view learns its slots while the views still carry them.
+    void annotate_plan() {
+        for (Op& op : ops) { op_reads(op, op.rd); op_writes(op, op.wr); }
+        for (ConvLayer& L : convs) L.out_slot = slot_of(L.out);
+        named_slot.clear();
+        for (auto& nv : named) named_slot.push_back(slot_of(nv.second));
+        end_reads = {slot_of(v_cat), slot_of(v_heat), slot_of(v_smpl_feats)};
+    }
+    std::vector<int> named_slot;     // slot of named[i]
+    std::vector<int> end_reads;      // read after the op list by the forward's copy-outs (conv_out / copy_out): cat, heat, smpl_feats
+
+
+    // ------------------------------------------------------------------ the activation arena
+    // Full layout (the default): every tensor has its own bytes, so every intermediate of a forward can be read afterwards (grnet_debug_tensor).
+    // Compact layout (GRNET_CREATE_COMPACT_ARENA): tensors whose lifetimes cannot overlap share bytes.  THE RULE: A may lie under B only if every op
+    // that reads or writes A is a strict ancestor, in the read-after-write DAG of the plan, of every op that writes B.  Nothing is added to make that
+    // true -- no edge, no event, no wait: FIFO streams and the events analyze_dependencies() places anyway enforce ancestor order for any lane
+    // schedule, so the launches, the schedule, the captured graph and the outputs of a compact handle are those of a full one.  Strictness keeps an
+    // op's output off its own inputs.
+    // The rule has to hold for every launch form the plan can take (any call size, any tuning table, any GRNET_OPT_BF16_CHAIN mask).  The bf16 kernel
+    // groups run several member ops as ONE launch (BasicBlock chains, row walkers, the layer1 expansion + reduction pair): that launch reads the
+    // group's inputs for as long as it writes the group's outputs, although in the un-grouped DAG a chain's input is dead before the chain's last
+    // convolution writes.  So every tensor a group member writes also conflicts with every tensor any member touches -- which is the rule again on
+    // the DAG with the group contracted to one node -- and the conflict relation is the union over the un-grouped form and every group.
+    // (The fp32 fuse launch is ONE op that reads and writes what all its per-output forms together would: FuseUpPlan::only < 0 in op_reads.)
+    // Tensors the forward's copy-outs read after the op list (end_reads) are touched by a virtual last op: nothing is ever placed over them.
+    struct ArenaPlan {
+        std::vector<int64_t> floats;        // per slot, at max_frames, 256-byte aligned
+        std::vector<int64_t> off;           // floats from the arena's base (the leading zero block included)
+        int64_t total = 0, full_total = 0, bound = 0;   // floats, head and tail blocks included
+        int n_shared = 0;
+        std::vector<char> final_tenant;     // nothing is placed over the slot's bytes later in the forward
+        std::vector<std::vector<int>> groups;   // op indices (plan order) some launch form runs as one launch
+        std::vector<std::vector<int>> rd, wr;   // per op, + the virtual copy-out op at the end
+    };
+    static constexpr int64_t kArenaHead = 64, kArenaTail = 64, kArenaAlign = 64;   // floats: the zero block, conv_wino4s_f32's masked over-read, 256-byte buffers
+    ArenaPlan arena_plan;
+    bool compact = false;
+
+    std::vector<std::vector<int>> launch_groups() const {
+        std::vector<std::vector<int>> g;
+        std::vector<int> op_of(convs.size(), -1);
+        for (int i = 0; i < (int)ops.size(); ++i)
+            if (ops[i].kind == Op::CONV) op_of[ops[i].conv_idx] = i;
+        auto add = [&](const std::vector<int>& cv) {
+            std::vector<int> m;
+            for (int c : cv) if (op_of[c] >= 0) m.push_back(op_of[c]);
+            std::sort(m.begin(), m.end());
+            if (m.size() >= 2) g.push_back(m);
+        };
+        for (const ChainPlan& c : chains) add(c.convs);
+        for (const RollPlan& r : rolls) add(r.convs);
+        for (int i = 0; i < (int)convs.size(); ++i)
+            if (convs[i].pair_next >= 0) add({i, convs[i].pair_next});
+        return g;
+    }
+
+    // Host code only (no HIP call): grnet_arena_query / grnet_arena_layout run it on a plan that never sees a device.
+    int plan_arena(bool compact_layout, ArenaPlan& ap) const {
+        const int nt = (int)pending.size(), m = (int)ops.size() + 1;      // + the virtual copy-out op
+        ap = ArenaPlan();
+        ap.floats.resize(nt);
+        for (int t = 0; t < nt; ++t) ap.floats[t] = ((int64_t)pending[t].second * max_frames + kArenaAlign - 1) / kArenaAlign * kArenaAlign;
+        ap.rd.resize(m); ap.wr.resize(m);
+        for (int i = 0; i + 1 < m; ++i) { ap.rd[i] = ops[i].rd; ap.wr[i] = ops[i].wr; }
+        for (int s : end_reads) if (s >= 0) ap.rd[m - 1].push_back(s);
+        ap.groups = launch_groups();
+        // strict ancestors over the RAW edges, as analyze_dependencies() derives them (plan order is a topological order)
+        const int words = (m + 63) / 64;
+        std::vector<std::vector<uint64_t>> anc(m, std::vector<uint64_t>(words, 0));
+        auto is_anc = [&](int a, int of) { return (anc[of][a >> 6] >> (a & 63)) & 1; };
+        std::vector<std::vector<int>> writers(nt), touch(nt);
+        for (int i = 0; i < m; ++i) {
+            for (int t : ap.rd[i])
+                for (int w : writers[t]) {
+                    for (int k = 0; k < words; ++k) anc[i][k] |= anc[w][k];
+                    anc[i][w >> 6] |= 1ull << (w & 63);
+                }
+            for (int t : ap.wr[i]) writers[t].push_back(i);
+            for (int t : ap.rd[i]) if (touch[t].empty() || touch[t].back() != i) touch[t].push_back(i);
+            for (int t : ap.wr[i]) if (touch[t].empty() || touch[t].back() != i) touch[t].push_back(i);
+        }
+        // a group launch sits at its first member's place: no op outside the group may lie between two members in the DAG
+        for (auto& g : ap.groups)
+            for (int x = 0; x < m; ++x) {
+                if (std::find(g.begin(), g.end(), x) != g.end()) continue;
+                bool below = false, above = false;
+                for (int a : g) { below |= (bool)is_anc(a, x); above |= (bool)is_anc(x, a); }
+                if (below && above) return GRNET_ESTATE;
+            }
+        // earlier(a, b): every op that touches a is a strict ancestor of every op that writes b
+        auto earlier = [&](int a, int b) {
+            if (touch[a].empty() || writers[b].empty()) return false;
+            for (int x : touch[a]) for (int w : writers[b]) if (x == w || !is_anc(x, w)) return false;
+            return true;
+        };
+        std::vector<std::vector<char>> conf(nt, std::vector<char>(nt, 0));
+        for (int a = 0; a < nt; ++a)
+            for (int b = a + 1; b < nt; ++b)
+                if (!earlier(a, b) && !earlier(b, a)) conf[a][b] = conf[b][a] = 1;
+        for (auto& g : ap.groups) {
+            std::vector<int> w, t;
+            for (int i : g) { w.insert(w.end(), ap.wr[i].begin(), ap.wr[i].end()); t.insert(t.end(), ap.wr[i].begin(), ap.wr[i].end()); t.insert(t.end(), ap.rd[i].begin(), ap.rd[i].end()); }
+            for (int a : w) for (int b : t) if (a != b) conf[a][b] = conf[b][a] = 1;
+        }
+        // lower bound: the tensors alive across one node -- written by the node or an ancestor, touched by the node or a descendant -- conflict
+        // pairwise, so no layout is smaller than their sum; the largest such sum over the ops and over the groups (each contracted alone).
+        auto live_sum = [&](const std::vector<int>& node) {
+            int64_t sum = 0;
+            for (int t = 0; t < nt; ++t) {
+                bool before = false, after = false;
+                for (int w : writers[t]) for (int x : node) before |= w == x || is_anc(w, x);
+                for (int u : touch[t]) for (int x : node) after |= u == x || is_anc(x, u);
+                if (before && after) sum += ap.floats[t];
+            }
+            return sum;
+        };
+        int64_t best = 0;
+        for (int i = 0; i < m; ++i) best = std::max(best, live_sum({i}));
+        for (auto& g : ap.groups) best = std::max(best, live_sum(g));
+        ap.bound = kArenaHead + best + kArenaTail;
+        ap.full_total = kArenaHead + kArenaTail;
+        for (int t = 0; t < nt; ++t) ap.full_total += ap.floats[t];
+        ap.off.resize(nt);
+        if (!compact_layout) {
+            int64_t at = kArenaHead;
+            for (int t = 0; t < nt; ++t) { ap.off[t] = at; at += ap.floats[t]; }
+            ap.total = ap.full_total;
+        } else {
+            std::vector<std::vector<int>> adj(nt);
+            for (int a = 0; a < nt; ++a) for (int b = 0; b < nt; ++b) if (conf[a][b]) adj[a].push_back(b);
+            int64_t tot = 0;
+            arena_first_fit(ap.floats, adj, kArenaAlign, ap.off, &tot);
+            for (int t = 0; t < nt; ++t) ap.off[t] += kArenaHead;
+            ap.total = kArenaHead + tot + kArenaTail;
+        }
+        ap.final_tenant.assign(nt, 1);
+        std::vector<char> shares(nt, 0);
+        for (int a = 0; a < nt; ++a)
+            for (int b = 0; b < nt; ++b) {
+                if (a == b || ap.floats[a] == 0 || ap.floats[b] == 0) continue;
+                if (ap.off[a] >= ap.off[b] + ap.floats[b] || ap.off[b] >= ap.off[a] + ap.floats[a]) continue;
+                if (conf[a][b]) return GRNET_ESTATE;                 // the assignment broke its own contract
+                shares[a] = 1;
+                if (!earlier(b, a)) ap.final_tenant[a] = 0;
+            }
+        for (int t = 0; t < nt; ++t) ap.n_shared += shares[t];
+        return 0;
+    }
+    void arena_info(const ArenaPlan& ap, int64_t* info) const {
+        info[0] = ap.total * 4; info[1] = ap.full_total * 4; info[2] = ap.bound * 4; info[3] = (int64_t)ap.floats.size(); info[4] = ap.n_shared;
+    }
+    std::string arena_text(const ArenaPlan& ap) const {
+        static const char* kinds[] = {"CONV", "SUM", "BILINEAR", "POOL", "TAIL", "SMPL", "CONVERT", "FUSEUP"};
+        std::string out;
+        for (size_t t = 0; t < ap.floats.size(); ++t) {
+            std::string nm = "-";
+            for (size_t i = 0; i < named.size(); ++i) if (named_slot[i] == (int)t) { nm = named[i].first; break; }
+            out += "tensor " + std::to_string(t) + " " + nm + " " + std::to_string(pending[t].second) + " " + std::to_string(ap.off[t]) + "\n";
+        }
+        for (size_t i = 0; i < ap.rd.size(); ++i) {
+            out += "op " + std::to_string(i) + " " + (i < ops.size() ? kinds[ops[i].kind] : "COPYOUT") + " reads";
+            for (int t : ap.rd[i]) out += " " + std::to_string(t);
+            out += " writes";
+            for (int t : ap.wr[i]) out += " " + std::to_string(t);
+            out += "\n";
+        }
+        for (auto& g : ap.groups) {
+            out += "group";
+            for (int i : g) out += " " + std::to_string(i);
+            out += "\n";
+        }
+        return out;
     }
 
     // Static list scheduling of the op list onto the kLanes streams.  The plan writes "branch b on lane b",
@@ -956,8 +1172,7 @@ struct grnet {
         const int m = (int)list.size();
         std::vector<double> est(m), blevel(m, 0.0);
         std::vector<std::vector<int>> deps(m), users(m);
-        std::map<const float*, std::vector<int>> writers;
-        std::vector<const float*> r, wr;
+        std::map<int, std::vector<int>> writers;               // slot -> ops that wrote (part of) it
         int prev_tail = -1;
         static const double fix_us = GRNET_AB_F(SCHED_FIX, 6.0);
         static const double hop_us = GRNET_AB_F(SCHED_HOP, 4.0);
@@ -983,8 +1198,7 @@ struct grnet {
                 case Op::SMPL: est[i] = 60; break;
                 default: est[i] = 8; break;
             }
-            op_reads(op, r);
-            for (const float* b : r) {
+            for (int b : op.rd) {
                 auto it = writers.find(b);
                 if (it == writers.end()) continue;
                 for (int w : it->second)
@@ -994,8 +1208,7 @@ struct grnet {
                 if (prev_tail >= 0) deps[i].push_back(prev_tail);
                 prev_tail = i;
             }
-            op_writes(op, wr);
-            for (const float* o : wr) writers[o].push_back(i);
+            for (int o : op.wr) writers[o].push_back(i);
         }
         for (int i = 0; i < m; ++i)
             for (int d : deps[i]) users[d].push_back(i);
@@ -1061,12 +1274,10 @@ struct grnet {
     }
 
     void analyze_dependencies(std::vector<Op>& ops, std::vector<hipEvent_t>& op_events) {
-        std::map<const float*, std::vector<int>> writers;      // buffer base -> ops that wrote (part of) it
-        std::vector<const float*> r, wr;
+        std::map<int, std::vector<int>> writers;               // slot -> ops that wrote (part of) it
         for (int i = 0; i < (int)ops.size(); ++i) {
             Op& op = ops[i];
-            op_reads(op, r);
-            for (const float* buf : r) {
+            for (int buf : op.rd) {
                 auto it = writers.find(buf);
                 if (it == writers.end()) continue;              // the caller's frames
                 for (int w : it->second)
@@ -1077,8 +1288,7 @@ struct grnet {
                         ops[w].record = true;
                     }
             }
-            op_writes(op, wr);
-            for (const float* out : wr) writers[out].push_back(i);
+            for (int out : op.wr) writers[out].push_back(i);
         }
         op_events.assign(ops.size(), nullptr);
         if (getenv("GRNET_TRACE")) {
@@ -1599,9 +1809,9 @@ struct grnet {
 
     // grnet_debug_tensor: did the last forward write view v to memory?  A convolution inside a row-walking or chain launch (conv_bf16_roll.hip, conv_bf16_chain.hip)
     // keeps its output in LDS unless it is the group's last one; the buffer then holds whatever an earlier forward left there.  (The pair's member writes its output.)
-    bool tap_written(const View& v) const {
+    bool tap_written(const View& v, int slot) const {
         for (const ConvLayer& L : convs) {
-            if (L.out.p != v.p || L.out.coff != v.coff || L.out.c != v.c) continue;
+            if (L.out_slot != slot || L.out.coff != v.coff || L.out.c != v.c) continue;
             switch (kernel_for(L, last_n)) {
                 case K_BF16_ROLL: case K_BF16_ROLL_MEMBER: return L.roll_pos == (int)rolls[L.roll].convs.size() - 1;
                 case K_BF16_CHAIN: case K_BF16_CHAIN_MEMBER: return L.chain_pos == (int)chains[L.chain].convs.size() - 1;
@@ -2334,8 +2544,10 @@ extern "C" {
 
 const char* grnet_version(void) { return "grnet_hip 0.1 (gfx950, fp32 MFMA)"; }
 
-int grnet_create(grnet_t** out_handle, int device_id, int dtype, int max_frames) {
-    if (!out_handle || max_frames < 1 || max_frames > 2048 || (dtype != 0 && dtype != 1)) return GRNET_EINVAL;
+int grnet_create(grnet_t** out_handle, int device_id, int dtype, int max_frames) { return grnet_create_ex(out_handle, device_id, dtype, max_frames, 0u); }
+
+int grnet_create_ex(grnet_t** out_handle, int device_id, int dtype, int max_frames, unsigned flags) {
+    if (!out_handle || max_frames < 1 || max_frames > 2048 || (dtype != 0 && dtype != 1) || (flags & ~(unsigned)GRNET_CREATE_COMPACT_ARENA)) return GRNET_EINVAL;
     *out_handle = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return GRNET_EHIP;
@@ -2344,6 +2556,7 @@ int grnet_create(grnet_t** out_handle, int device_id, int dtype, int max_frames)
     h->device = device_id;
     h->max_frames = max_frames;
     h->dtype = dtype;
+    h->compact = (flags & GRNET_CREATE_COMPACT_ARENA) != 0;
     if (const char* ml = getenv("GRNET_MULTI_LANE")) h->multi_lane = atoi(ml) != 0;   // profiling: per-kernel times without overlap
     if (const char* wn = getenv("GRNET_WINO")) h->wino_mode = atoi(wn) != 0;
     h->build_plan();
@@ -2351,6 +2564,72 @@ int grnet_create(grnet_t** out_handle, int device_id, int dtype, int max_frames)
     if (rc) { fprintf(stderr, "grnet_create: %s\n", h->err.c_str()); return rc; }
     if (conv_init() != hipSuccess || conv_bf16_init() != hipSuccess || conv_bf16_chain_init() != hipSuccess || conv_bf16_roll_init() != hipSuccess) { fprintf(stderr, "grnet_create: conv_init failed\n"); return GRNET_EHIP; }
     *out_handle = h.release();
+    return 0;
+}
+
+// The plan of (precision, max_frames) and its arena, on the host alone: no device, no HIP call.
+static int arena_plan_on_host(int precision, int max_frames, unsigned flags, std::unique_ptr<grnet>& g) {
+    if (max_frames < 1 || max_frames > 2048 || (precision != 0 && precision != 1) || (flags & ~(unsigned)GRNET_CREATE_COMPACT_ARENA)) return GRNET_EINVAL;
+    g.reset(new grnet());
+    g->max_frames = max_frames;
+    g->dtype = precision;
+    g->compact = (flags & GRNET_CREATE_COMPACT_ARENA) != 0;
+    g->build_plan();
+    return g->plan_arena(g->compact, g->arena_plan);
+}
+
+int grnet_arena_query(int precision, int max_frames, unsigned flags, int64_t* info) {
+    if (!info) return GRNET_EINVAL;
+    std::unique_ptr<grnet> g;
+    if (int rc = arena_plan_on_host(precision, max_frames, flags, g)) return rc;
+    g->arena_info(g->arena_plan, info);
+    return 0;
+}
+
+int grnet_arena_layout(int precision, int max_frames, unsigned flags, char* buf, int size) {
+    std::unique_ptr<grnet> g;
+    if (int rc = arena_plan_on_host(precision, max_frames, flags, g)) return rc;
+    const std::string out = g->arena_text(g->arena_plan);
+    if (!buf) return (int)out.size() + 1;
+    if ((int)out.size() + 1 > size) return GRNET_EINVAL;
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return (int)out.size();
+}
+
+int grnet_arena_info(grnet_t* h, int64_t* info) {
+    if (!h || !info) return GRNET_EINVAL;
+    h->arena_info(h->arena_plan, info);
+    return 0;
+}
+
+int grnet_arena_fill(grnet_t* h, uint32_t pattern, void* stream) {
+    if (!h) return GRNET_EINVAL;
+    DeviceGuard guard(h->device);
+    const size_t head = (size_t)grnet::kArenaHead;
+    hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->arena + head), (int)pattern, h->arena_floats - head, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int grnet_arena_assign(int n, const int64_t* sizes, int n_pairs, const int32_t* conflict_pairs, int64_t* offsets, int64_t* total) {
+    if (n < 0 || n_pairs < 0 || (n && (!sizes || !offsets)) || (n_pairs && !conflict_pairs) || !total) return GRNET_EINVAL;
+    std::vector<int64_t> sz(n), off;
+    std::vector<std::vector<int>> adj(n);
+    for (int i = 0; i < n; ++i) {
+        if (sizes[i] < 0) return GRNET_EINVAL;
+        sz[i] = sizes[i];
+    }
+    for (int k = 0; k < n_pairs; ++k) {
+        const int a = conflict_pairs[2 * k], b = conflict_pairs[2 * k + 1];
+        if (a < 0 || a >= n || b < 0 || b >= n) return GRNET_EINVAL;
+        if (a == b) continue;
+        adj[a].push_back(b);
+        adj[b].push_back(a);
+    }
+    int64_t tot = 0;
+    arena_first_fit(sz, adj, 256, off, &tot);
+    for (int i = 0; i < n; ++i) offsets[i] = off[i];
+    *total = tot;
     return 0;
 }
 
@@ -2939,10 +3218,15 @@ int grnet_debug_tensor(grnet_t* h, const char* name, int n_frames, float* out_de
         return h->fail(GRNET_EINVAL, "debug tensor " + std::string(name) + ": n_frames " + std::to_string(n_frames) + " outside [1, frames of the last forward = " +
                                          std::to_string(h->last_n) + "]");
     DeviceGuard guard(h->device);
-    for (auto& nv : h->named) {
+    for (size_t ni = 0; ni < h->named.size(); ++ni) {
+        auto& nv = h->named[ni];
         if (nv.first != name) continue;
         const View& v = nv.second;
-        if (!h->tap_written(v))
+        const int slot = h->named_slot[ni];
+        if (h->compact && (slot < 0 || !h->arena_plan.final_tenant[slot]))
+            return h->fail(GRNET_ESTATE, "debug tensor " + std::string(name) + " cannot be read back from a compact arena: a later tensor of the forward is placed over it. "
+                                             "Create the handle without GRNET_CREATE_COMPACT_ARENA to read every intermediate");
+        if (!h->tap_written(v, slot))
             return h->fail(GRNET_ESTATE, "debug tensor " + std::string(name) + " was not written by the last forward (" + std::to_string(h->last_n) +
                                              " frames): its producer ran inside a fused launch that keeps it on chip");
         if (shape_out) { shape_out[0] = v.c; shape_out[1] = v.h; shape_out[2] = v.w; }

@@ -70,13 +70,43 @@ def resolve_joint_regressor(J, select="reference"):
     return W, sel
 
 
+_ARENA_FIELDS = ("bytes", "full_bytes", "lower_bound_bytes", "tensors", "shared_tensors")
+
+
+def arena_query(dtype="f32", max_frames=64, compact=False):
+    """The arena GRNet(dtype=, max_frames=, compact_arena=) would allocate, computed on the host -- no GPU, no handle (grnet_arena_query):
+    dict(bytes, full_bytes, lower_bound_bytes, tensors, shared_tensors)."""
+    if dtype not in ("f32", "bf16"):
+        raise ValueError("dtype must be 'f32' or 'bf16'")
+    info = (C.c_int64 * 5)()
+    rc = _lib.load().grnet_arena_query(_lib.PRECISION_BF16 if dtype == "bf16" else _lib.PRECISION_F32, int(max_frames),
+                                       _lib.CREATE_COMPACT_ARENA if compact else 0, info)
+    if rc != 0:
+        raise _lib.GrnetError(f"grnet_arena_query failed with code {rc} (max_frames is 1 .. 2048)")
+    return dict(zip(_ARENA_FIELDS, (int(v) for v in info)))
+
+
+def arena_layout(dtype="f32", max_frames=64, compact=False):
+    """The layout as text (grnet_arena_layout): tensor / op / group lines."""
+    lib = _lib.load()
+    args = (_lib.PRECISION_BF16 if dtype == "bf16" else _lib.PRECISION_F32, int(max_frames), _lib.CREATE_COMPACT_ARENA if compact else 0)
+    need = lib.grnet_arena_layout(*args, None, 0)
+    if need < 0:
+        raise _lib.GrnetError(f"grnet_arena_layout failed with code {need}")
+    buf = C.create_string_buffer(need)
+    n = lib.grnet_arena_layout(*args, buf, need)
+    if n < 0:
+        raise _lib.GrnetError(f"grnet_arena_layout failed with code {n}")
+    return buf.value.decode()
+
+
 class GRNet:
     is_demo = False
 
     def __init__(self, num_joints=24, num_input_features=480, num_features_pare=128, num_features_smpl=64,
                  backbone='hrnet_w32', focal_length=5000., img_res=224, pretrained_pare=None, writer=None, seqlen=50,
                  pretrained_hrnet=None, use_gait_feat=False, featcorr=None, use_pose_encoder=False,
-                 use_shpcam_encoder=False, max_frames=64, device_id=0, dtype="f32"):
+                 use_shpcam_encoder=False, max_frames=64, device_id=0, dtype="f32", compact_arena=False):
         if (num_joints, num_input_features, num_features_pare, num_features_smpl) != (24, 480, 128, 64) \
                 or backbone != 'hrnet_w32' or focal_length != 5000. or img_res != 224:
             raise ValueError("the HIP path implements the reference's fixed configuration "
@@ -96,7 +126,11 @@ class GRNet:
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' (the reference's precision) or 'bf16' (bf16 storage, fp32 accumulation; BASELINE configs 3/5)")
         self.dtype = dtype
-        rc = self._lib.grnet_create(C.byref(h), device_id, 1 if dtype == "bf16" else 0, self.max_frames)
+        # compact_arena: intermediates whose lifetimes cannot overlap share memory (grnet_create_ex; same launches, bit-identical outputs, 13.7 instead
+        # of 103.8 MB per frame in fp32); debug_tensor then serves only the tensors nothing is placed over.  The default keeps every intermediate readable.
+        self.compact_arena = bool(compact_arena)
+        rc = self._lib.grnet_create_ex(C.byref(h), device_id, _lib.PRECISION_BF16 if dtype == "bf16" else _lib.PRECISION_F32, self.max_frames,
+                                       _lib.CREATE_COMPACT_ARENA if self.compact_arena else 0)
         if rc != 0:
             raise _lib.GrnetError(f"grnet_create failed with code {rc} (is a GPU visible?)")
         self._h = h
@@ -550,6 +584,17 @@ class GRNet:
                                                                      stream), "grnet_debug_tensor")
         return out
 
+    def arena_info(self):
+        """The handle's activation arena (grnet_arena_info): dict(bytes, full_bytes, lower_bound_bytes, tensors, shared_tensors)."""
+        info = (C.c_int64 * 5)()
+        _lib.check(self._lib, self._h, self._lib.grnet_arena_info(self._h, info), "grnet_arena_info")
+        return dict(zip(_ARENA_FIELDS, (int(v) for v in info)))
+
+    def arena_fill(self, pattern):
+        """Diagnostic: fill the arena behind its zero block with a 32-bit pattern on the current stream (grnet_arena_fill)."""
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib, self._h, self._lib.grnet_arena_fill(self._h, int(pattern) & 0xffffffff, stream), "grnet_arena_fill")
+
     def tsattn_plan(self, n):
         """What the attention block does with a clip of n frames on this device (grnet_tsattn_plan):
         dict(kernel 'per_query' | 'blocked', parts, key_blocks, lds_bytes)."""
@@ -740,11 +785,11 @@ class GRNet:
             pass
 
 
-def build_synthetic_model(max_frames=64, device_id=0, with_gru=True, with_tsattn=False, dtype="f32", use_gait_feat=False):
+def build_synthetic_model(max_frames=64, device_id=0, with_gru=True, with_tsattn=False, dtype="f32", use_gait_feat=False, compact_arena=False):
     """GRNet with the seed-defined weights / SMPL tables of synth.py (no checkpoint exists offline).  use_gait_feat: the whole
     pose-feature corrector under its checkpoint keys (pfeat_corrector.*: GRU, gait-token MLPs, BatchNorm1d, attention block)."""
     from . import synth
-    m = GRNet(max_frames=max_frames, device_id=device_id, dtype=dtype, use_gait_feat=use_gait_feat,
+    m = GRNet(max_frames=max_frames, device_id=device_id, dtype=dtype, use_gait_feat=use_gait_feat, compact_arena=compact_arena,
               featcorr=dict(AVG_DIM=3, ESTIM_PHASE=True, NUM_LAYERS=1, H_SIZE=1024, NUM_HEADS=4, USE_JWFF=True) if use_gait_feat else None)
     sd = synth.make_state_dict()
     if use_gait_feat:
