@@ -80,7 +80,7 @@ def main(args):
     print(f"Activation arena: {ai['bytes'] / 2**20:.0f} MiB for calls of up to {args.max_frames} frames "
           f"({'one buffer per tensor' if args.full_arena else 'buffers shared by liveness'}; the full layout takes {ai['full_bytes'] / 2**20:.0f} MiB)")
     smpl_tables = None
-    if args.smooth:
+    if args.smooth and args.smooth_on_host:                    # the host statement forms the 49 joints with J_regressor_extra on the CPU
         if args.synthetic_weights:
             smpl_tables = pkg.synth.make_smpl_tables()
         else:
@@ -90,13 +90,22 @@ def main(args):
     for pid, tr in tracking.items():
         bboxes, frames = np.asarray(tr["bbox"], np.float32).copy(), np.asarray(tr["frames"])
         ds = pipe.InferenceFrames(args.img_folder, frames, bboxes, scale=1.0)
-        pred = pipe.run_tracklet(model, ds.batches(args.grnet_batch_size, model=model))
+        on_device = args.smooth and not args.smooth_on_host
+        pred = pipe.run_tracklet(model, ds.batches(args.grnet_batch_size, model=model), on_device=on_device)
         w, h = ds.image_size()
         if args.smooth:                                        # demo.py:191-196
             print(f"Running smoothing on person {pid}, min_cutoff: {args.smooth_min_cutoff}, beta: {args.smooth_beta}")
-            pred["verts"], pred["pose"], pred["joints3d"] = pipe.smooth_pose(
-                model, pred["pose"], pred["betas"], min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta,
-                smpl_tables=smpl_tables)
+            if on_device:
+                # filter, Rodrigues, SMPL and the 49 joints on the GPU, reading theta in place; only what the pickle holds is downloaded
+                # (the first pass's verts and joints3d are dropped on the device)
+                theta = pred.pop("theta")
+                pred["verts"], pred["pose"], pred["joints3d"] = model.smooth_pose(
+                    theta, theta[:, 75:], min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta, joints="spin49")
+                pred = {k: v.cpu().numpy() for k, v in pred.items()}
+            else:
+                pred["verts"], pred["pose"], pred["joints3d"] = pipe.smooth_pose(
+                    model, pred["pose"], pred["betas"], min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta,
+                    smpl_tables=smpl_tables)
         results[pid] = pipe.make_demo_result(pred, ds.bboxes, ds.frames, w, h)
         if args.joint_type != "spin":                          # demo.py:224-229
             # the reference converts with src='spin' (49 joints); without --smooth the path emits the 29 'spin2' joints, on which
@@ -141,6 +150,8 @@ def parser():
     p.add_argument("--smooth", action="store_true")
     p.add_argument("--smooth_min_cutoff", type=float, default=0.004)
     p.add_argument("--smooth_beta", type=float, default=0.7)
+    p.add_argument("--smooth_on_host", action="store_true", help="--smooth with the filter, Rodrigues and the 49-joint regression on the CPU "
+                   "(pipeline.smooth_pose, the host statement the device path is tested against); default: all of it on the GPU")
     p.add_argument("--tracking_path", type=str, default=None)
     p.add_argument("--img_folder", type=str, default=None)
     p.add_argument("--joint_type", type=str, default="spin")

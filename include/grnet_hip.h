@@ -104,7 +104,8 @@ int grnet_load_tensor(grnet_t* h, const char* state_dict_key, const void* host_p
 
 /* SMPL(...) buffers -- lib/models/smpl.py:97-106,144 (smplx.SMPL tables + J_regressor_extra).
  * v_template (6890,3), shapedirs (6890,3,10), posedirs (207,20670), J_regressor (24,6890),
- * lbs_weights (6890,24), parents (24), J_regressor_extra (9,6890); host pointers. */
+ * lbs_weights (6890,24), parents (24), J_regressor_extra (9,6890); host pointers.  Of J_regressor_extra the non-zero entries of every row are
+ * kept on the device (row 5, 'Thorax (MPII)', for the 29 joints of every forward; all nine for grnet_smooth_pose's 49). */
 int grnet_load_smpl(grnet_t* h, const float* v_template, const float* shapedirs, const float* posedirs,
                     const float* J_regressor, const float* lbs_weights, const int32_t* parents,
                     const float* J_regressor_extra);
@@ -340,6 +341,33 @@ int grnet_gait_correct(grnet_t* h, const float* point_local_feat_dev, const floa
  * reference's edge-case vectors (degenerate 6-D pairs, the four quaternion branches, near-pi rotations) reach the GPU code. */
 int grnet_op_rot6d_to_rotmat(grnet_t* h, const float* rot6d_dev, int m, float* rotmat_dev, void* stream);
 int grnet_op_rotmat_to_aa(grnet_t* h, const float* rotmat_dev, int m, float* aa_dev, void* stream);
+/* Axis-angle -> rotation matrix as smplx.SMPL converts the poses smooth_pose.py:99 hands it (batch_rodrigues: angle = |aa + 1e-8|,
+ * R = I + sin K + (1 - cos) K^2, accurate sinf / cosf): (m,3) -> (m,3,3). */
+int grnet_op_aa_to_rotmat(grnet_t* h, const float* aa_dev, int m, float* rotmat_dev, void* stream);
+
+/* ---- the --smooth step on device-resident results -- lib/utils/smooth_pose.py:28-116, lib/utils/one_euro_filter.py:5-46 ----------------------
+ * OneEuroFilter as smooth_pose drives it (unit time steps, state x[0] and dx = 0): x_dev is T rows of 72 channels with a row stride of
+ * ld >= 72 floats (72, or 85 with the pointer at theta + 3 to filter theta's pose columns in place) -> xhat_dev (T,72), dense.  One launch,
+ * one workgroup; frames are staged through LDS in blocks of 32.  The arithmetic is the reference's float32 numpy arithmetic operation by
+ * operation (one rounding each, IEEE division, no fused multiply-add): the result is BIT-IDENTICAL to the reference's, and frame t depends
+ * on frames 0..t only.  T = 1 copies the frame.  GRNET_EINVAL (with a message): T < 1, ld < 72, a null pointer, a non-finite parameter. */
+int grnet_op_one_euro(grnet_t* h, const float* x_dev, int ld, int T, float min_cutoff, float beta, float d_cutoff, float* xhat_dev, void* stream);
+
+/* smooth_pose(pred_pose, pred_betas, min_cutoff, beta) for axis-angle poses: the filter above over all T frames (d_cutoff = 1), then SMPL on
+ * the filtered pose with the betas of frame 0 for every frame (smooth_pose.py:97; only row 0 of betas_dev is read) and the joints in the
+ * skeleton asked for: the 49 SPIN joints (smpl.py:119-121 -- what the reference's demo.py --smooth stores), the 29 'spin2' joints
+ * grnet_smpl_forward returns, or the 25 kinectv2 joints convert_kps takes from those.  pose_dev: T rows with stride pose_ld >= 72;
+ * pose_hat_dev (T,72), joints_dev (T,49|29|25,3) and, unless NULL, verts_dev (T,6890,3) are written.  T is NOT limited by max_frames: the
+ * SMPL part runs in chunks of max_frames in stream order (Rodrigues + betas broadcast, the launches of grnet_smpl_forward, one joints
+ * launch per chunk).  No host synchronisation; the only allocation is a (max_frames x 313 floats) workspace at the first call on the handle,
+ * outside the activation arena.  It shares grnet_smpl_forward's workspace: calls on a handle must be ordered as for that function.
+ * GRNET_EINVAL (with a message): T < 1, pose_ld < 72, a null pose / betas / pose_hat / joints pointer, an unknown joints_kind, a non-finite
+ * min_cutoff or beta; GRNET_ESTATE: no SMPL tables, or before grnet_finalize_weights. */
+#define GRNET_JOINTS_SPIN49   0
+#define GRNET_JOINTS_SPIN2    1
+#define GRNET_JOINTS_KINECTV2 2
+int grnet_smooth_pose(grnet_t* h, const float* pose_dev, int pose_ld, const float* betas_dev, int T, float min_cutoff, float beta, int joints_kind,
+                      float* pose_hat_dev, float* verts_dev, float* joints_dev, void* stream);
 
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single

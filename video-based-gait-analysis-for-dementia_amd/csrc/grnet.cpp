@@ -225,6 +225,8 @@ struct grnet {
     // grnet_set_joint_regressor: the selected rows in MFMA fragment order and the slice partials of grnet_regress_joints (max_frames frames)
     float *jreg_pack = nullptr, *jreg_ws = nullptr;
     int jreg_rows = 0;
+    // grnet_smooth_pose: rotations (max_frames,24,9) | betas (max_frames,10) | kp (max_frames,29,3), allocated at the first call, outside the arena
+    float* smooth_ws = nullptr;
     void jreg_clear() {
         if (jreg_pack || jreg_ws) (void)hipDeviceSynchronize();         // a call that reads them may still be running
         if (jreg_pack) (void)hipFree(jreg_pack);
@@ -2713,6 +2715,23 @@ int grnet_load_smpl(grnet_t* h, const float* v_template, const float* shapedirs,
         if ((rc = h->upload(idx_f, &p))) return rc;
         h->smpl.thorax_idx = reinterpret_cast<const int*>(p);
     }
+    {   // all 9 rows of J_regressor_extra as one (vertex, weight) list with row offsets: the 49-joint SPIN skeleton of grnet_smooth_pose (smpl.py:119-121)
+        std::vector<float> w, idx_f;
+        for (int r = 0; r < 9; ++r) {
+            h->smpl.extra_ptr[r] = (int)w.size();
+            for (int v = 0; v < V; ++v) {
+                const float x = J_regressor_extra[(size_t)r * V + v];
+                if (x != 0.f) { w.push_back(x); int32_t i = v; float f; memcpy(&f, &i, 4); idx_f.push_back(f); }
+            }
+        }
+        h->smpl.extra_ptr[9] = (int)w.size();
+        if (w.empty()) { w.push_back(0.f); idx_f.push_back(0.f); }
+        float* p = nullptr;
+        if ((rc = h->upload(w, &p))) return rc;
+        h->smpl.extra_w = p;
+        if ((rc = h->upload(idx_f, &p))) return rc;
+        h->smpl.extra_idx = reinterpret_cast<const int*>(p);
+    }
     // the joint regressor is linear: apply it to the tables once, in fp64
     std::vector<float> Jt(72), Js(720);
     for (int j = 0; j < 24; ++j)
@@ -3384,6 +3403,76 @@ int grnet_op_rot6d_to_rotmat(grnet_t* h, const float* rot6d_dev, int m, float* r
     DeviceGuard guard(h->device);
     hipError_t e = launch_rot6d_to_rotmat(rot6d_dev, rotmat_dev, m, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("rot6d_to_rotmat: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// The constants of the One-Euro recurrence as the reference's float32 numpy forms them (one_euro_filter.py:5-7,32 with t_e = 1): 2 pi, min_cutoff
+// and beta rounded to float32 once, a_d = r_d / (r_d + 1) with r_d = f32(2 pi d_cutoff), and 1 - a_d.
+static OneEuroCoef one_euro_coef(float min_cutoff, float beta, float d_cutoff) {
+    const double two_pi = 6.283185307179586476925286766559;
+    OneEuroCoef c;
+    const volatile float r_d = (float)(two_pi * (double)d_cutoff);      // volatile: each step is rounded to float32 whatever the host's evaluation mode
+    const volatile float r_d1 = r_d + 1.f;
+    const volatile float a_d = r_d / r_d1;
+    c.a_d = a_d;
+    c.one_minus_a_d = 1.f - a_d;
+    c.two_pi = (float)two_pi;
+    c.min_cutoff = min_cutoff;
+    c.beta = beta;
+    return c;
+}
+
+int grnet_op_one_euro(grnet_t* h, const float* x_dev, int ld, int T, float min_cutoff, float beta, float d_cutoff, float* xhat_dev, void* stream) {
+    if (!h) return GRNET_EINVAL;
+    if (!x_dev || !xhat_dev) return h->fail(GRNET_EINVAL, "grnet_op_one_euro: null pointer");
+    if (T < 1) return h->fail(GRNET_EINVAL, "grnet_op_one_euro: T " + std::to_string(T) + " < 1");
+    if (ld < 72) return h->fail(GRNET_EINVAL, "grnet_op_one_euro: row stride " + std::to_string(ld) + " < 72");
+    if (!std::isfinite(min_cutoff) || !std::isfinite(beta) || !std::isfinite(d_cutoff))
+        return h->fail(GRNET_EINVAL, "grnet_op_one_euro: min_cutoff, beta and d_cutoff must be finite");
+    DeviceGuard guard(h->device);
+    hipError_t e = launch_one_euro(x_dev, ld, T, one_euro_coef(min_cutoff, beta, d_cutoff), xhat_dev, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("one_euro: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int grnet_op_aa_to_rotmat(grnet_t* h, const float* aa_dev, int m, float* rotmat_dev, void* stream) {
+    if (!h || !aa_dev || !rotmat_dev || m < 1) return GRNET_EINVAL;
+    DeviceGuard guard(h->device);
+    hipError_t e = launch_aa_to_rotmat(aa_dev, rotmat_dev, m, nullptr, nullptr, 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("aa_to_rotmat: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// lib/utils/smooth_pose.py:28-116 for axis-angle poses: the filter over all T frames in one launch, then SMPL on the filtered pose with the
+// betas of frame 0 (:97) in chunks of max_frames, each chunk's joints written in the caller's skeleton.
+int grnet_smooth_pose(grnet_t* h, const float* pose_dev, int pose_ld, const float* betas_dev, int T, float min_cutoff, float beta, int joints_kind,
+                      float* pose_hat_dev, float* verts_dev, float* joints_dev, void* stream) {
+    if (!h) return GRNET_EINVAL;
+    if (!pose_dev || !betas_dev || !pose_hat_dev || !joints_dev) return h->fail(GRNET_EINVAL, "grnet_smooth_pose: null pointer (only verts_dev may be NULL)");
+    if (T < 1) return h->fail(GRNET_EINVAL, "grnet_smooth_pose: T " + std::to_string(T) + " < 1");
+    if (pose_ld < 72) return h->fail(GRNET_EINVAL, "grnet_smooth_pose: pose row stride " + std::to_string(pose_ld) + " < 72");
+    const int nj = smooth_joint_count(joints_kind);
+    if (!nj) return h->fail(GRNET_EINVAL, "grnet_smooth_pose: unknown joints_kind " + std::to_string(joints_kind) + " (GRNET_JOINTS_SPIN49 / _SPIN2 / _KINECTV2)");
+    if (!std::isfinite(min_cutoff) || !std::isfinite(beta)) return h->fail(GRNET_EINVAL, "grnet_smooth_pose: min_cutoff and beta must be finite");
+    if (!h->smpl_loaded) return h->fail(GRNET_ESTATE, "grnet_smooth_pose: SMPL tables were not loaded");
+    if (!h->d_A) return h->fail(GRNET_ESTATE, "grnet_smooth_pose before grnet_finalize_weights (the SMPL workspace is allocated there)");
+    DeviceGuard guard(h->device);
+    const size_t mf = (size_t)h->max_frames;
+    if (!h->smooth_ws) {
+        if (int rc = h->dev_alloc(&h->smooth_ws, mf * (216 + 10 + 87))) return rc;
+    }
+    float *rot = h->smooth_ws, *betas = rot + mf * 216, *kp = betas + mf * 10;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch_one_euro(pose_dev, pose_ld, T, one_euro_coef(min_cutoff, beta, 1.f), pose_hat_dev, s);
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("smooth_pose (filter): ") + hipGetErrorString(e));
+    for (int f0 = 0; f0 < T; f0 += h->max_frames) {
+        const int n = std::min(h->max_frames, T - f0);
+        float* verts = verts_dev ? verts_dev + (size_t)f0 * 6890 * 3 : h->d_verts;
+        e = launch_aa_to_rotmat(pose_hat_dev + (size_t)f0 * 72, rot, n * 24, betas_dev, betas, n, s);
+        if (e == hipSuccess) e = launch_smpl(betas, rot, nullptr, h->smpl, h->d_A, verts, kp, nullptr, n, s);
+        if (e == hipSuccess) e = launch_smpl_joints54(kp, verts, h->smpl, joints_kind, joints_dev + (size_t)f0 * nj * 3, n, s);
+        if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("smooth_pose (SMPL): ") + hipGetErrorString(e));
+    }
     return 0;
 }
 

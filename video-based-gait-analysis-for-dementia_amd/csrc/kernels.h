@@ -283,10 +283,24 @@ struct SmplTables {
     const float* thorax_w;     // ... and weights
     int thorax_n;
     const int* parents;        // (24)
+    int extra_ptr[10];         // all 9 rows of J_regressor_extra as one (vertex, weight) list: row r is entries extra_ptr[r] .. extra_ptr[r+1]-1,
+    const int* extra_idx;      // vertex ids ascending within a row (csrc/smooth_kernels.hip; the thorax list above stays what launch_smpl reads)
+    const float* extra_w;
 };
 // betas (N,10), rotmat (N,24,9), cam (N,3) -> verts (N,6890,3), kp3d (N,29,3), kp2d (N,29,2)
 hipError_t launch_smpl(const float* betas, const float* rotmat, const float* cam, SmplTables t, float* A_ws,
                        float* verts, float* kp3d, float* kp2d, int N, hipStream_t s);
+
+// The --smooth step (smooth_pose.py:28-116; csrc/smooth_kernels.hip, compiled without fma contraction) ----
+constexpr int kOneEuroBlock = 32;  // frames per LDS staging block of the filter
+struct OneEuroCoef { float a_d, one_minus_a_d, two_pi, min_cutoff, beta; };     // float32 constants of the recurrence, rounded once on the host
+// x (T,72) with row stride ld >= 72 -> xhat (T,72): one workgroup, one sequence
+hipError_t launch_one_euro(const float* x, int ld, int T, OneEuroCoef c, float* xhat, hipStream_t s);
+// aa (m,3) -> R (m,3,3), smplx batch_rodrigues; betas_out != NULL: also betas_out (nb,10) = row betas0 (10) repeated (nb * 10 <= m)
+hipError_t launch_aa_to_rotmat(const float* aa, float* R, int m, const float* betas0, float* betas_out, int nb, hipStream_t s);
+int smooth_joint_count(int kind);  // 49 / 29 / 25 for GRNET_JOINTS_SPIN49 / _SPIN2 / _KINECTV2, 0: unknown
+// kp29 (n,29,3) as launch_smpl wrote it (rows 0..23 are read), verts (n,6890,3) -> joints (n,smooth_joint_count(kind),3)
+hipError_t launch_smpl_joints54(const float* kp29, const float* verts, SmplTables t, int kind, float* joints, int n, hipStream_t s);
 
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)

@@ -711,6 +711,69 @@ class GRNet:
                    "grnet_op_rotmat_to_aa")
         return out
 
+    # ------------------------------------------------------------------ --smooth on the device (smooth_pose.py:28-116)
+    def _pose_rows(self, x, what):
+        """(T,72) or (T,85) theta, host or device -> (tensor kept alive, pointer to the first pose column, row stride in floats).  A
+        device float32 tensor whose rows are contiguous is read in place (a theta is entered at column 3), whatever its row stride."""
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError(f"{what} must be (T,72) or a (T,85) theta with T >= 1, got {tuple(x.shape)}")
+        if x.shape[1] == 96:
+            raise ValueError(f"{what} is 96 wide: quaternion poses (24 x 4) are not implemented on the device -- the filter and SMPL "
+                             "run on axis-angle poses (T,72), the only form the reference's entry points pass to smooth_pose")
+        if x.shape[1] not in (72, 85):
+            raise ValueError(f"{what} must be (T,72) or a (T,85) theta, got {tuple(x.shape)}")
+        x = x.to(self.device, torch.float32)
+        if x.stride(1) != 1 or x.stride(0) < 72:
+            x = x.contiguous()
+        off = 3 if x.shape[1] == 85 else 0
+        return x, x.data_ptr() + 4 * off, x.stride(0)
+
+    def one_euro(self, x, min_cutoff=0.004, beta=0.7, d_cutoff=1.0):
+        """The reference's OneEuroFilter over a sequence (grnet_op_one_euro): x (T,72), or a (T,85) theta whose pose columns are filtered
+        in place -> (T,72) device tensor, bit-identical to the reference's float32 numpy arithmetic."""
+        x, ptr, ld = self._pose_rows(x, "x")
+        out = torch.empty(x.shape[0], 72, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib, self._h, self._lib.grnet_op_one_euro(self._h, ptr, ld, x.shape[0], min_cutoff, beta, d_cutoff, out.data_ptr(), stream),
+                   "grnet_op_one_euro")
+        return out
+
+    def aa_to_rotmat(self, aa):
+        """Axis-angle (...,3) -> (m,3,3), smplx's batch_rodrigues (grnet_op_aa_to_rotmat)."""
+        aa = torch.as_tensor(aa).to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        out = torch.empty(aa.shape[0], 3, 3, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib, self._h, self._lib.grnet_op_aa_to_rotmat(self._h, aa.data_ptr(), aa.shape[0], out.data_ptr(), stream),
+                   "grnet_op_aa_to_rotmat")
+        return out
+
+    _JOINT_KINDS = {"spin49": (_lib.JOINTS_SPIN49, 49), "spin2": (_lib.JOINTS_SPIN2, 29), "kinectv2": (_lib.JOINTS_KINECTV2, 25)}
+
+    def smooth_pose(self, pose, betas, min_cutoff=0.004, beta=0.7, joints="spin49", return_verts=True):
+        """smooth_pose.py:28-116 on the device (grnet_smooth_pose): One-Euro filter over the pose, SMPL with the betas of frame 0, the joints
+        in the skeleton asked for.  pose (T,72) or a (T,85) theta (read in place), betas (T,10) -- host or device; T is not limited by
+        max_frames.  Returns device tensors (verts (T,6890,3) or None, pose_hat (T,72), joints (T,49|29|25,3)); nothing synchronises."""
+        if joints not in self._JOINT_KINDS:
+            raise ValueError(f"joints must be one of {sorted(self._JOINT_KINDS)}, got {joints!r}")
+        self.finalize()
+        kind, nj = self._JOINT_KINDS[joints]
+        x, ptr, ld = self._pose_rows(pose, "pose")
+        T = x.shape[0]
+        b = torch.as_tensor(betas).to(self.device, torch.float32)
+        if b.dim() != 2 or b.shape[1] != 10 or b.shape[0] < 1:
+            raise ValueError(f"betas must be (T,10), got {tuple(b.shape)}")
+        b0 = b[0].contiguous()
+        pose_hat = torch.empty(T, 72, dtype=torch.float32, device=self.device)
+        verts = torch.empty(T, 6890, 3, dtype=torch.float32, device=self.device) if return_verts else None
+        out = torch.empty(T, nj, 3, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_smooth_pose(self._h, ptr, ld, b0.data_ptr(), T, min_cutoff, beta, kind, pose_hat.data_ptr(),
+                                         verts.data_ptr() if return_verts else None, out.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_smooth_pose")
+        return verts, pose_hat, out
+
     # single-op hooks for kernel parity tests
     def op_conv2d(self, x, w, bias=None, stride=1, relu=False, add=None, tile_hint=0):
         n, cin, h, wd = x.shape

@@ -142,6 +142,18 @@ def smooth_pose(model, pred_pose, pred_betas, min_cutoff=0.004, beta=0.7, kinect
     return verts, pose_hat.reshape(T, 72), joints
 
 
+def smooth_pose_device(model, pred_pose, pred_betas, min_cutoff=0.004, beta=0.7, kinectv2=False):
+    """smooth_pose() with every step on the GPU (GRNet.smooth_pose: filter, Rodrigues, SMPL and the joint selection in one C call):
+    pred_pose (T,72) or a (T,85) theta and pred_betas (T,10), host arrays or device tensors.  Same return contract as smooth_pose --
+    numpy (verts, pose_hat, joints3d), joints3d the 49 SPIN joints in float32 or, with kinectv2, 25 joints in float64 as convert_kps
+    returns them -- and no smpl_tables argument: the handle holds all nine rows of J_regressor_extra.  The filtered pose is the
+    reference's bit for bit (smooth_pose's one_euro_filter forms a_d in double and is within 1e-6 of it)."""
+    verts, pose_hat, joints = model.smooth_pose(pred_pose, pred_betas, min_cutoff=min_cutoff, beta=beta,
+                                                joints="kinectv2" if kinectv2 else "spin49")
+    joints = joints.cpu().numpy()
+    return verts.cpu().numpy(), pose_hat.cpu().numpy(), joints.astype(np.float64) if kinectv2 else joints
+
+
 # ----------------------------------------------------------------------------- the crop's affine map, as the reference forms it
 def _affine_from_box(cx, cy, w, h, dst_w, dst_h, scale):
     """gen_trans_from_patch_cv (img_utils.py:54-88, rot = 0) + cv2.getAffineTransform, then the inversion cv2.warpAffine applies:
@@ -280,8 +292,10 @@ class InferenceFrames:
 
 
 # ----------------------------------------------------------------------------- model loops
-def run_tracklet(model, batches, device="cuda"):
-    """demo.py:151-188: feed (<=batch,3,224,224) batches, slice theta, concatenate, to numpy."""
+def run_tracklet(model, batches, device="cuda", on_device=False):
+    """demo.py:151-188: feed (<=batch,3,224,224) batches, slice theta, concatenate, to numpy.
+    on_device: the same dict as tensors on ``device`` plus "theta" (T,85), whose rows GRNet.smooth_pose reads in place; nothing is
+    downloaded and nothing synchronises with the host."""
     acc = defaultdict(list)
     for batch in batches:
         x = torch.as_tensor(batch, dtype=torch.float32).unsqueeze(0).to(device)
@@ -293,6 +307,10 @@ def run_tracklet(model, batches, device="cuda"):
         acc["betas"].append(out["theta"][:, :, 75:].reshape(bs * t, -1))
         acc["joints3d"].append(out["kp_3d"].reshape(bs * t, -1, 3))
         acc["smpl_joints2d"].append(out["kp_2d"].reshape(bs * t, -1, 2))
+        if on_device:
+            acc["theta"].append(out["theta"].reshape(bs * t, -1))
+    if on_device:
+        return {k: torch.cat(v, 0) for k, v in acc.items()}
     return {k: torch.cat(v, 0).cpu().numpy() for k, v in acc.items()}
 
 
