@@ -77,7 +77,6 @@ struct ConvLayer {
     int chain = -1, chain_pos = 0;   // bf16: member chain_pos of BasicBlock chain `chain` (conv_bf16_chain.hip); position 0 launches the whole chain in large calls
     int roll = -1, roll_pos = 0;     // bf16: member roll_pos of the row-walking launch `roll` (conv_bf16_roll.hip: the stem pair, a layer1 Bottleneck); position 0 launches it in large calls
     std::map<int, int> tuned;   // n_frames -> launch configuration (tile hint) measured fastest by grnet_tune
-    int out_slot = -1;          // the planned buffer `out` is a view of (annotate_plan): tensor identity once buffers share addresses
 };
 
 // The up half of one HR module's fuse layer (hr_fuse.hip): outputs 0 .. nb-2 in one launch.
@@ -205,9 +204,7 @@ struct grnet {
     std::vector<hipEvent_t> op_events_flat;
     int wino_mode = 1;                               // GRNET_OPT_WINOGRAD: 1 = the eligible 3x3 layers on 56x56 maps run the Winograd kernel
 
-    // planned buffers: (pointer slot, floats per image)
-    std::vector<std::pair<float**, size_t>> pending;   // pointers patched after the arena exists
-    std::vector<std::unique_ptr<float*>> slots;
+    std::vector<size_t> buffer_floats;   // planned buffers in creation order (View::slot indexes it): floats per image
     float* arena = nullptr;
     size_t arena_floats = 0;
     std::vector<void*> dev_allocs;
@@ -344,19 +341,13 @@ struct grnet {
 
     // ------------------------------------------------------------------ plan construction
     View new_buffer(int c, int h, int w) {
-        slots.emplace_back(new float*(nullptr));
         const int ct = dtype == 1 ? (c + 7) / 8 * 8 : c;     // NHWC bf16: 16-byte channel groups (the 25 heat channels -> 32)
-        pending.emplace_back(slots.back().get(), (size_t)ct * h * w);
         View v;
-        v.p = nullptr;
+        v.slot = (int)buffer_floats.size();
         v.ctot = ct; v.coff = 0; v.c = c; v.h = h; v.w = w;
-        // p is resolved through slot index stored in coff-independent table: keep index in a side map
-        view_slot[(int)views_created] = slots.size() - 1;
-        v.p = reinterpret_cast<float*>(views_created++ + 1);   // temporary tag, replaced in resolve()
+        buffer_floats.push_back((size_t)ct * h * w);
         return v;
     }
-    std::unordered_map<int, size_t> view_slot;
-    size_t views_created = 0;
 
     static View slice(View v, int coff, int c) {
         v.coff += coff;
@@ -641,8 +632,8 @@ struct grnet {
             sa.C = kBranchCh[0]; sa.H = xs[0].h; sa.W = xs[0].w; sa.relu = 1;
             sa.n_add = nb;
             sum_views.push_back({o, {}});
-            sum_views.back().second.push_back(AddRef{xs[0], 0});
-            for (int j = 1; j < nb; ++j) sum_views.back().second.push_back(AddRef{t[0][j], j});
+            sum_views.back().adds.push_back(AddRef{xs[0], 0});
+            for (int j = 1; j < nb; ++j) sum_views.back().adds.push_back(AddRef{t[0][j], j});
             op.conv_idx = (int)sum_views.size() - 1;
             ops.push_back(op);
             outs[0] = o;
@@ -697,15 +688,16 @@ struct grnet {
         cur_lane = 0;
         return outs;
     }
-    std::vector<std::pair<View, std::vector<AddRef>>> sum_views;
+    struct SumPlan { View out; std::vector<AddRef> adds; };   // Op::SUM: out = relu(sum of the addends)
+    std::vector<SumPlan> sum_views;
     std::vector<std::pair<std::string, View>> named;   // intermediate tensors exposed to grnet_debug_tensor
     void name_view(const std::string& n, const View& v) { named.emplace_back(n, v); }
 
     void build_plan() {
         const std::string b = "backbone.";
-        v_input.p = nullptr; v_input.ctot = 3; v_input.coff = 0; v_input.c = 3; v_input.h = 224; v_input.w = 224;
+        v_input.ctot = 3; v_input.coff = 0; v_input.c = 3; v_input.h = 224; v_input.w = 224;
         View in = v_input;
-        in.p = reinterpret_cast<float*>(~(uintptr_t)0);   // tag: caller's frames pointer
+        in.slot = View::kFrames;
         // bf16: the stem's first convolution reads the caller's fp32 frames itself (conv_bf16_stem, round 4); GRNET_BF16_STEM=0 restores the
         // conversion launch -- frames (N,3,224,224) f32 -> NHWC bf16, 8 channels per pixel -- in front of the generic kernel
         static const int bf16_stem_env = GRNET_AB(BF16_STEM, 1);
@@ -845,14 +837,6 @@ struct grnet {
         annotate_plan();
     }
 
-    float* resolve_ptr(float* tag) const {
-        const uintptr_t t = reinterpret_cast<uintptr_t>(tag);
-        if (t == ~(uintptr_t)0 || t == 0) return tag;
-        auto it = view_slot.find((int)(t - 1));
-        return *slots[it->second];
-    }
-    void resolve(View& v) const { v.p = resolve_ptr(v.p); }
-
     int dev_alloc(float** p, size_t floats) {
         void* q = nullptr;
         if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) return fail(GRNET_ENOMEM, "hipMalloc failed");
@@ -866,7 +850,6 @@ struct grnet {
         // conv_wino4s_f32's 16-byte row loads on 7-wide maps touch (and mask) one float past a row, i.e. 4 bytes past the LAST buffer's end
         // for its last row -- they stay inside the arena (in a compact one such a masked read may land in another tenant's bytes)
         if (plan_arena(compact, arena_plan)) return fail(GRNET_ESTATE, "the activation arena could not be planned: a launch group or the assignment violates the sharing rule");
-        const std::vector<int64_t>& offs = arena_plan.off;
         const size_t total = (size_t)arena_plan.total;
         arena_floats = total;
         void* q = nullptr;
@@ -875,22 +858,6 @@ struct grnet {
         arena = static_cast<float*>(q);
         if (hipMemset(arena, 0, 64 * sizeof(float)) != hipSuccess) return fail(GRNET_EHIP, "hipMemset failed");
         zeros = arena;
-        for (size_t i = 0; i < pending.size(); ++i) *pending[i].first = arena + offs[i];
-        for (auto& L : convs) {
-            resolve(L.in); resolve(L.out);
-            if (L.in2.c) resolve(L.in2);
-            for (auto& a : L.adds) resolve(a.v);
-        }
-        for (auto& op : ops) { resolve(op.bin); resolve(op.bout); }
-        for (auto& sv : sum_views) { resolve(sv.first); for (auto& a : sv.second) resolve(a.v); }
-        for (auto& fp : fuse_ups) {
-            for (auto& v : fp.xs) resolve(v);
-            for (auto& v : fp.outs) resolve(v);
-            for (auto& e : fp.extra) for (auto& v : e) resolve(v);
-        }
-        for (auto& nv : named) resolve(nv.second);
-        resolve(v_cat); resolve(v_heat); resolve(v_smpl_feats); resolve(v_csmap);
-        if (dtype == 1 && !bf16_stem) resolve(v_in8);
         // streams / events of the parallel lanes are created here, never inside a stream capture
         if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return fail(GRNET_EHIP, "hipEventCreate failed");
         if (int rc = install_schedule(max_frames)) return rc;
@@ -917,16 +884,10 @@ struct grnet {
     // the join at the end of enqueue().  A tensor is a planned buffer (slot), not an address and not a view: in a compact arena
     // (GRNET_CREATE_COMPACT_ARENA) several tensors live at one address, and the sharing rule of plan_arena() makes the RAW edges computed
     // here order them as well -- a compact handle gets exactly the edges, lanes and events of a full one.
-    // Slots an op reads / writes (-1, dropped: the caller's frames).  Valid on the unresolved plan only (views still carry their tag).
-    int slot_of(const View& v) const {
-        const uintptr_t t = reinterpret_cast<uintptr_t>(v.p);
-        if (t == ~(uintptr_t)0 || t == 0) return -1;
-        auto it = view_slot.find((int)(t - 1));
-        return it == view_slot.end() ? -1 : (int)it->second;
-    }
+    // Slots an op reads / writes (the caller's frames are no planned buffer: dropped).
     void op_reads(const Op& op, std::vector<int>& r) const {
         r.clear();
-        auto put = [&](const View& v) { const int s = slot_of(v); if (s >= 0) r.push_back(s); };
+        auto put = [&](const View& v) { if (v.slot >= 0) r.push_back(v.slot); };
         switch (op.kind) {
             case Op::CONV: {
                 const ConvLayer& L = convs[op.conv_idx];
@@ -936,7 +897,7 @@ struct grnet {
                 break;
             }
             case Op::SUM:
-                for (auto& a : sum_views[op.conv_idx].second) put(a.v);
+                for (auto& a : sum_views[op.conv_idx].adds) put(a.v);
                 break;
             case Op::BILINEAR: put(op.bin); break;
             case Op::FUSEUP:
@@ -953,9 +914,9 @@ struct grnet {
     }
     void op_writes(const Op& op, std::vector<int>& w) const {
         w.clear();
-        auto put = [&](const View& v) { const int s = slot_of(v); if (s >= 0) w.push_back(s); };
+        auto put = [&](const View& v) { if (v.slot >= 0) w.push_back(v.slot); };
         if (op.kind == Op::CONV) put(convs[op.conv_idx].out);
-        else if (op.kind == Op::SUM) put(sum_views[op.conv_idx].first);
+        else if (op.kind == Op::SUM) put(sum_views[op.conv_idx].out);
         else if (op.kind == Op::BILINEAR) put(op.bout);
         else if (op.kind == Op::CONVERT) put(v_in8);
         else if (op.kind == Op::FUSEUP) {
@@ -963,15 +924,11 @@ struct grnet {
             for (size_t i = 0; i < fp.outs.size(); ++i) if (fp.only < 0 || fp.only == (int)i) put(fp.outs[i]);
         }
     }
-    // End of build_plan(): every op, convolution and named view learns its slots while the views still carry them.
+    // End of build_plan(): what the lane scheduler and the arena planner read.
     void annotate_plan() {
         for (Op& op : ops) { op_reads(op, op.rd); op_writes(op, op.wr); }
-        for (ConvLayer& L : convs) L.out_slot = slot_of(L.out);
-        named_slot.clear();
-        for (auto& nv : named) named_slot.push_back(slot_of(nv.second));
-        end_reads = {slot_of(v_cat), slot_of(v_heat), slot_of(v_smpl_feats)};
+        end_reads = {v_cat.slot, v_heat.slot, v_smpl_feats.slot};
     }
-    std::vector<int> named_slot;     // slot of named[i]
     std::vector<int> end_reads;      // read after the op list by the forward's copy-outs (conv_out / copy_out): cat, heat, smpl_feats
 
 
@@ -1022,10 +979,10 @@ struct grnet {
 
     // Host code only (no HIP call): grnet_arena_query / grnet_arena_layout run it on a plan that never sees a device.
     int plan_arena(bool compact_layout, ArenaPlan& ap) const {
-        const int nt = (int)pending.size(), m = (int)ops.size() + 1;      // + the virtual copy-out op
+        const int nt = (int)buffer_floats.size(), m = (int)ops.size() + 1;      // + the virtual copy-out op
         ap = ArenaPlan();
         ap.floats.resize(nt);
-        for (int t = 0; t < nt; ++t) ap.floats[t] = ((int64_t)pending[t].second * max_frames + kArenaAlign - 1) / kArenaAlign * kArenaAlign;
+        for (int t = 0; t < nt; ++t) ap.floats[t] = ((int64_t)buffer_floats[t] * max_frames + kArenaAlign - 1) / kArenaAlign * kArenaAlign;
         ap.rd.resize(m); ap.wr.resize(m);
         for (int i = 0; i + 1 < m; ++i) { ap.rd[i] = ops[i].rd; ap.wr[i] = ops[i].wr; }
         for (int s : end_reads) if (s >= 0) ap.rd[m - 1].push_back(s);
@@ -1120,8 +1077,8 @@ struct grnet {
         std::string out;
         for (size_t t = 0; t < ap.floats.size(); ++t) {
             std::string nm = "-";
-            for (size_t i = 0; i < named.size(); ++i) if (named_slot[i] == (int)t) { nm = named[i].first; break; }
-            out += "tensor " + std::to_string(t) + " " + nm + " " + std::to_string(pending[t].second) + " " + std::to_string(ap.off[t]) + "\n";
+            for (auto& nv : named) if (nv.second.slot == (int)t) { nm = nv.first; break; }
+            out += "tensor " + std::to_string(t) + " " + nm + " " + std::to_string(buffer_floats[t]) + " " + std::to_string(ap.off[t]) + "\n";
         }
         for (size_t i = 0; i < ap.rd.size(); ++i) {
             out += "op " + std::to_string(i) + " " + (i < ops.size() ? kinds[ops[i].kind] : "COPYOUT") + " reads";
@@ -1338,7 +1295,7 @@ struct grnet {
         // GRNET_STEM is the fp32 A/B switch only: a bf16 plan built for conv_bf16_stem (GRNET_BF16_STEM) has no NHWC copy of the frames, so its first
         // convolution MUST get the stem kernel's weights whatever GRNET_STEM says (round-4 advice: the generic kernel then read fp32 NCHW frames as NHWC bf16)
         const bool stem = !bf && stem_env && stem_shape, stem_bf = bf && bf16_stem && stem_shape;
-        if (bf && bf16_stem && reinterpret_cast<uintptr_t>(L.in.p) == ~(uintptr_t)0 && !stem_bf)
+        if (bf && bf16_stem && L.in.slot == View::kFrames && !stem_bf)
             return fail(GRNET_ESTATE, "bf16 plan without a conversion launch, but its first convolution is not eligible for conv_bf16_stem");
         std::vector<double> wfold(wino4 || wino4s || stem || stem_bf ? (size_t)L.cout * cin * 9 : 0);     // BN-folded weights (cout, cin, 3, 3) for the filter transform
         int co0 = 0;
@@ -1664,7 +1621,7 @@ struct grnet {
             float best = 1e30f, t_model = 1e30f;
             int best_hint = 0;
             for (int hint : cands) {
-                ConvArgs a = conv_args(L, v_cat.p, n);        // any readable buffer stands in for the caller's frames
+                ConvArgs a = conv_args(L, base(v_cat), n);        // any readable buffer stands in for the caller's frames
                 if (launch_conv(a, s, hint) != hipSuccess) { (void)hipGetLastError(); continue; }
                 HIP_TRY(hipEventRecord(e0, s));
                 for (int r = 0; r < 3; ++r) (void)launch_conv(a, s, hint);
@@ -1695,11 +1652,11 @@ struct grnet {
             tuned_mode[n] = mode;
             drop_graphs();
             seen_once.clear();
-            int rc = forward(v_cat.p, n, nullptr, s);          // first sight of the key: eager
-            if (!rc) rc = forward(v_cat.p, n, nullptr, s);     // second: builds the graph, first replay
+            int rc = forward(base(v_cat), n, nullptr, s);          // first sight of the key: eager
+            if (!rc) rc = forward(base(v_cat), n, nullptr, s);     // second: builds the graph, first replay
             if (rc) return rc;
             HIP_TRY(hipEventRecord(e0, s));
-            for (int r = 0; r < 3; ++r) if ((rc = forward(v_cat.p, n, nullptr, s))) return rc;
+            for (int r = 0; r < 3; ++r) if ((rc = forward(base(v_cat), n, nullptr, s))) return rc;
             HIP_TRY(hipEventRecord(e1, s));
             HIP_TRY(hipEventSynchronize(e1));
             HIP_TRY(hipEventElapsedTime(&t_mode[mode], e0, e1));
@@ -1721,13 +1678,13 @@ struct grnet {
             auto time_forward = [&](float* out_ms) -> int {
                 drop_graphs();
                 seen_once.clear();
-                int rc = forward(v_cat.p, n, nullptr, s);
-                if (!rc) rc = forward(v_cat.p, n, nullptr, s);
+                int rc = forward(base(v_cat), n, nullptr, s);
+                if (!rc) rc = forward(base(v_cat), n, nullptr, s);
                 if (rc) return rc;
                 float best_ms = 1e30f;
                 for (int rep2 = 0; rep2 < 2; ++rep2) {
                     HIP_TRY(hipEventRecord(e0, s));
-                    for (int r = 0; r < 2; ++r) if ((rc = forward(v_cat.p, n, nullptr, s))) return rc;
+                    for (int r = 0; r < 2; ++r) if ((rc = forward(base(v_cat), n, nullptr, s))) return rc;
                     HIP_TRY(hipEventRecord(e1, s));
                     HIP_TRY(hipEventSynchronize(e1));
                     float ms = 0;
@@ -1757,7 +1714,7 @@ struct grnet {
                     bool valid = true;
                     for (auto& L : convs)
                         if (key_of(L) == ok.second) {
-                            ConvArgs a = conv_args(L, v_cat.p, n);
+                            ConvArgs a = conv_args(L, base(v_cat), n);
                             if (launch_conv(a, s, hint) != hipSuccess) { (void)hipGetLastError(); valid = false; }
                             break;
                         }
@@ -1780,27 +1737,35 @@ struct grnet {
         return 0;
     }
     // ------------------------------------------------------------------ execution
-    static const void* bf16_at(const View& v) { return reinterpret_cast<const uint16_t*>(v.p) + v.coff; }   // first channel of an NHWC bf16 view
+    // A view becomes an address here, at the launch, and nowhere else: the base (image 0, channel 0) of its buffer in the arena, or `frames` (only
+    // ever read) for the caller's frames.  Meaningful on an allocated handle only: the host-only plans of grnet_arena_query / grnet_arena_layout have no arena.
+    float* base(const View& v, const float* frames = nullptr) const {
+        if (v.slot >= 0) return arena + arena_plan.off[v.slot];
+        return v.slot == View::kFrames ? const_cast<float*>(frames) : nullptr;
+    }
+    // ... and the (pointer, ctot, coff) triple of a kernel argument struct (float or void pointers: a bf16 handle keeps NHWC bf16 behind the same fields)
+    template <class P>
+    void bind(const View& v, P*& p, int& ctot, int& coff, const float* frames = nullptr) const { p = base(v, frames); ctot = v.ctot; coff = v.coff; }
+    const void* bf16_at(const View& v) const { return reinterpret_cast<const uint16_t*>(base(v)) + v.coff; }   // first channel of an NHWC bf16 view
     ConvArgs conv_args(const ConvLayer& L, const float* frames, int n) const {
         ConvArgs a{};
-        a.in = reinterpret_cast<uintptr_t>(L.in.p) == ~(uintptr_t)0 ? frames : L.in.p;
-        a.in_ctot = L.in.ctot; a.in_coff = L.in.coff;
+        bind(L.in, a.in, a.in_ctot, a.in_coff, frames);
         a.N = n; a.Cin = L.in.c; a.H = L.in.h; a.W = L.in.w;
-        a.out = L.out.p; a.out_ctot = L.out.ctot; a.out_coff = L.out.coff;
+        bind(L.out, a.out, a.out_ctot, a.out_coff);
         a.Cout = L.cout; a.Ho = L.out.h; a.Wo = L.out.w;
         a.w = L.w_dev; a.bias = L.b_dev; a.CinPad = L.cin_pad; a.CoutPad = L.cout_pad;
         a.ks = L.ks; a.stride = L.stride; a.relu = L.relu; a.relu_from = L.relu_from;
         a.n_add = (int)L.adds.size();
         for (int k = 0; k < a.n_add; ++k) {
-            a.add[k] = L.adds[k].v.p; a.add_ctot[k] = L.adds[k].v.ctot; a.add_coff[k] = L.adds[k].v.coff;
+            bind(L.adds[k].v, a.add[k], a.add_ctot[k], a.add_coff[k]);
             a.add_shift[k] = L.adds[k].shift;
         }
         a.zeros = zeros;
         a.pw_stream = !(chain_mode & 128) ? 0 : bf16_min_frames ? 2 : 1;
-        if (L.in2.c) { a.in2 = L.in2.p; a.in2_ctot = L.in2.ctot; a.in2_coff = L.in2.coff; a.cin_split = L.in.c; a.Cin = L.in.c + L.in2.c; }
+        if (L.in2.c) { bind(L.in2, a.in2, a.in2_ctot, a.in2_coff); a.cin_split = L.in.c; a.Cin = L.in.c + L.in2.c; }
         if (L.pair_next >= 0 && pair_active(n)) {
             const ConvLayer& F = convs[L.pair_next];
-            a.w2 = F.w_dev; a.bias2 = F.b_dev; a.out2 = F.out.p; a.out2_ctot = F.out.ctot; a.out2_coff = F.out.coff; a.relu2 = F.relu;
+            a.w2 = F.w_dev; a.bias2 = F.b_dev; bind(F.out, a.out2, a.out2_ctot, a.out2_coff); a.relu2 = F.relu;
         }
         return a;
     }
@@ -1811,9 +1776,9 @@ struct grnet {
 
     // grnet_debug_tensor: did the last forward write view v to memory?  A convolution inside a row-walking or chain launch (conv_bf16_roll.hip, conv_bf16_chain.hip)
     // keeps its output in LDS unless it is the group's last one; the buffer then holds whatever an earlier forward left there.  (The pair's member writes its output.)
-    bool tap_written(const View& v, int slot) const {
+    bool tap_written(const View& v) const {
         for (const ConvLayer& L : convs) {
-            if (L.out_slot != slot || L.out.coff != v.coff || L.out.c != v.c) continue;
+            if (L.out.slot != v.slot || L.out.coff != v.coff || L.out.c != v.c) continue;
             switch (kernel_for(L, last_n)) {
                 case K_BF16_ROLL: case K_BF16_ROLL_MEMBER: return L.roll_pos == (int)rolls[L.roll].convs.size() - 1;
                 case K_BF16_CHAIN: case K_BF16_CHAIN_MEMBER: return L.chain_pos == (int)chains[L.chain].convs.size() - 1;
@@ -1946,19 +1911,17 @@ struct grnet {
         *n_launches = 1;
         switch (kernel_for(L, n)) {
             case K_BF16: HIP_TRY(launch_conv_bf16(conv_args(L, frames, n), s, hint_for(L, n))); break;
-            case K_BF16_STEM: HIP_TRY(launch_conv_bf16_stem(frames, L.stem_dev, L.b_dev, L.out.p, L.out.ctot, L.out.coff, n, L.relu, s)); break;
+            case K_BF16_STEM: HIP_TRY(launch_conv_bf16_stem(frames, L.stem_dev, L.b_dev, base(L.out), L.out.ctot, L.out.coff, n, L.relu, s)); break;
             case K_BF16_CHAIN: {
                 const ChainPlan& cp = chains[L.chain];
                 const ConvLayer& last = convs[cp.convs.back()];
                 ChainArgs ca{};
-                ca.in = L.in.p; ca.in_ctot = L.in.ctot; ca.in_coff = L.in.coff;
-                ca.out = last.out.p; ca.out_ctot = last.out.ctot; ca.out_coff = last.out.coff;
+                bind(L.in, ca.in, ca.in_ctot, ca.in_coff);
+                bind(last.out, ca.out, ca.out_ctot, ca.out_coff);
                 ca.N = n; ca.nconv = (int)cp.convs.size();
                 for (int i = 0; i < ca.nconv; ++i) { ca.w[i] = convs[cp.convs[i]].w_dev; ca.bias[i] = convs[cp.convs[i]].b_dev; }
-                for (int k = 0; k + 1 < ca.nconv / 2; ++k) {          // the 56x56 branch runs one launch per BasicBlock: the blocks' own output buffers carry the hand-over
-                    const View& m = convs[cp.convs[2 * k + 1]].out;
-                    ca.mid[k] = m.p; ca.mid_ctot[k] = m.ctot; ca.mid_coff[k] = m.coff;
-                }
+                for (int k = 0; k + 1 < ca.nconv / 2; ++k)            // the 56x56 branch runs one launch per BasicBlock: the blocks' own output buffers carry the hand-over
+                    bind(convs[cp.convs[2 * k + 1]].out, ca.mid[k], ca.mid_ctot[k], ca.mid_coff[k]);
                 HIP_TRY(launch_conv_bf16_chain(ca, cp.c, cp.w, s));
                 *n_launches = conv_bf16_chain_launches(cp.c, cp.w, ca.nconv);
                 break;
@@ -1969,10 +1932,10 @@ struct grnet {
                 const ConvLayer& last = convs[rp.convs.back()];
                 if (rp.kind == 0) {
                     const ConvLayer& c2 = convs[rp.convs[1]];
-                    HIP_TRY(launch_conv_bf16_stem_pair(frames, last.out.p, last.out.ctot, last.out.coff, n, L.stem_dev, L.b_dev, c2.w_dev, c2.b_dev, s));
+                    HIP_TRY(launch_conv_bf16_stem_pair(frames, base(last.out), last.out.ctot, last.out.coff, n, L.stem_dev, L.b_dev, c2.w_dev, c2.b_dev, s));
                 } else {
                     const ConvLayer &c2 = convs[rp.convs[1]], &c3 = convs[rp.convs[2]];
-                    HIP_TRY(launch_conv_bf16_bneck(L.in.p, L.in.ctot, L.in.coff, last.out.p, last.out.ctot, last.out.coff, n, rp.kind == 1, L.w_dev, L.b_dev, c2.w_dev, c2.b_dev,
+                    HIP_TRY(launch_conv_bf16_bneck(base(L.in), L.in.ctot, L.in.coff, base(last.out), last.out.ctot, last.out.coff, n, rp.kind == 1, L.w_dev, L.b_dev, c2.w_dev, c2.b_dev,
                                                    c3.w_dev, c3.b_dev, s));
                 }
                 break;
@@ -2017,13 +1980,17 @@ struct grnet {
         for (int i = 0; i < fp.nb - 1; ++i) {
             if (fp.only >= 0 && fp.only != i) continue;
             FuseUpOut& fo = a.o[i];
-            fo.out = fp.outs[i].p; fo.out_ctot = fp.outs[i].ctot; fo.out_coff = fp.outs[i].coff;
-            fo.base = fp.xs[i].p; fo.base_ctot = fp.xs[i].ctot; fo.base_coff = fp.xs[i].coff;
+            bind(fp.outs[i], fo.out, fo.out_ctot, fo.out_coff);
+            bind(fp.xs[i], fo.base, fo.base_ctot, fo.base_coff);
             fo.bias = fp.b_dev[i];
             fo.relu = 1;
             fo.n_extra = (int)fp.extra[i].size();
-            for (int k = 0; k < fo.n_extra; ++k) { fo.extra[k] = fp.extra[i][k].p; fo.extra_ctot[k] = fp.extra[i][k].ctot; fo.extra_coff[k] = fp.extra[i][k].coff; }
-            for (int j = i + 1; j < fp.nb; ++j) fo.src[j - i - 1] = FuseUpSrc{fp.xs[j].p, fp.xs[j].ctot, fp.xs[j].coff, fp.w_dev[i][j - i - 1]};
+            for (int k = 0; k < fo.n_extra; ++k) bind(fp.extra[i][k], fo.extra[k], fo.extra_ctot[k], fo.extra_coff[k]);
+            for (int j = i + 1; j < fp.nb; ++j) {
+                FuseUpSrc& src = fo.src[j - i - 1];
+                bind(fp.xs[j], src.x, src.ctot, src.coff);
+                src.w = fp.w_dev[i][j - i - 1];
+            }
         }
         HIP_TRY(dtype == 1 ? launch_hr_fuse_up_bf16(a, s) : launch_hr_fuse_up(a, s));
         return 0;
@@ -2091,7 +2058,7 @@ struct grnet {
             }
             switch (op.kind) {
                 case Op::CONVERT:
-                    HIP_TRY(launch_nchw_f32_to_nhwc_bf16(frames, v_in8.p, n, 3, 224, 224, 8, s));
+                    HIP_TRY(launch_nchw_f32_to_nhwc_bf16(frames, base(v_in8), n, 3, 224, 224, 8, s));
                     ++launches;
                     break;
                 case Op::CONV: {
@@ -2104,10 +2071,10 @@ struct grnet {
                     const auto& sv = sum_views[op.conv_idx];
                     SumArgs a = op.sum;
                     a.N = n;
-                    a.out = sv.first.p; a.out_ctot = sv.first.ctot; a.out_coff = sv.first.coff;
+                    bind(sv.out, a.out, a.out_ctot, a.out_coff);
                     for (int k = 0; k < a.n_add; ++k) {
-                        a.add[k] = sv.second[k].v.p; a.add_ctot[k] = sv.second[k].v.ctot; a.add_coff[k] = sv.second[k].v.coff;
-                        a.add_shift[k] = sv.second[k].shift;
+                        bind(sv.adds[k].v, a.add[k], a.add_ctot[k], a.add_coff[k]);
+                        a.add_shift[k] = sv.adds[k].shift;
                     }
                     if (dtype == 1) HIP_TRY(launch_fuse_sum_bf16(a, s));
                     else HIP_TRY(launch_fuse_sum(a, s));
@@ -2119,16 +2086,16 @@ struct grnet {
                     ++launches;
                     break;
                 case Op::BILINEAR:
-                    if (dtype == 1) HIP_TRY(launch_bilinear2x_bf16(op.bin.p, op.bout.p, n, op.bin.c, op.bin.h, op.bin.w, s));
-                    else HIP_TRY(launch_bilinear2x(op.bin.p, op.bout.p, n, op.bin.c, op.bin.h, op.bin.w, s));
+                    if (dtype == 1) HIP_TRY(launch_bilinear2x_bf16(base(op.bin), base(op.bout), n, op.bin.c, op.bin.h, op.bin.w, s));
+                    else HIP_TRY(launch_bilinear2x(base(op.bin), base(op.bout), n, op.bin.c, op.bin.h, op.bin.w, s));
                     ++launches;
                     break;
                 case Op::POOL:
                     if (dtype == 1)
-                        HIP_TRY(launch_softmax_pool_bf16(v_heat.p, v_heat.ctot, bf16_at(v_smpl_feats), 128, v_smpl_feats.ctot, bf16_at(v_csmap), 64,
+                        HIP_TRY(launch_softmax_pool_bf16(base(v_heat), v_heat.ctot, bf16_at(v_smpl_feats), 128, v_smpl_feats.ctot, bf16_at(v_csmap), 64,
                                                          v_csmap.ctot, d_stats, n, 56 * 56, s));
                     else
-                        HIP_TRY(launch_softmax_pool(v_heat.p, 25, v_smpl_feats.p, 128, v_csmap.p, 64, plf, csf, d_stats, n, 56 * 56, s));
+                        HIP_TRY(launch_softmax_pool(base(v_heat), 25, base(v_smpl_feats), 128, base(v_csmap), 64, plf, csf, d_stats, n, 56 * 56, s));
                     ++launches;
                     break;
                 case Op::TAIL:
@@ -2168,16 +2135,16 @@ struct grnet {
                         rec->deps.clear();
                         for (hipGraphNode_t nd : lane_last) if (nd) rec->deps.push_back(nd);
                     }
-                    HIP_TRY(launch_nhwc_bf16_to_nchw_f32(v.p, dst, n, v.c, v.h, v.w, v.ctot, v.coff, s));
+                    HIP_TRY(launch_nhwc_bf16_to_nchw_f32(base(v), dst, n, v.c, v.h, v.w, v.ctot, v.coff, s));
                     return 0;
                 };
                 if ((rc = conv_out(o.features, v_cat))) return rc;
                 if ((rc = conv_out(o.part_attn, v_heat))) return rc;
                 if ((rc = conv_out(o.smpl_feats, v_smpl_feats))) return rc;
             } else {
-            if ((rc = copy_out(o.features, v_cat.p, (size_t)n * 480 * 3136 * 4))) return rc;
-            if ((rc = copy_out(o.part_attn, v_heat.p, (size_t)n * 25 * 3136 * 4))) return rc;
-            if ((rc = copy_out(o.smpl_feats, v_smpl_feats.p, (size_t)n * 128 * 3136 * 4))) return rc;
+            if ((rc = copy_out(o.features, base(v_cat), (size_t)n * 480 * 3136 * 4))) return rc;
+            if ((rc = copy_out(o.part_attn, base(v_heat), (size_t)n * 25 * 3136 * 4))) return rc;
+            if ((rc = copy_out(o.smpl_feats, base(v_smpl_feats), (size_t)n * 128 * 3136 * 4))) return rc;
             }
             launches_last = launches;
         }
@@ -3037,7 +3004,7 @@ int grnet_time_conv(grnet_t* h, int pos, int n_frames, int reps, void* stream, f
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return GRNET_EHIP; }
     int rc = 0, nl = 0;
-    auto once = [&]() { return op->kind == Op::FUSEUP ? h->launch_fuse_up_op(h->fuse_ups[op->conv_idx], n_frames, s) : h->launch_conv_op(h->convs[op->conv_idx], h->v_cat.p, n_frames, s, &nl); };
+    auto once = [&]() { return op->kind == Op::FUSEUP ? h->launch_fuse_up_op(h->fuse_ups[op->conv_idx], n_frames, s) : h->launch_conv_op(h->convs[op->conv_idx], h->base(h->v_cat), n_frames, s, &nl); };
     for (int r = 0; r < 2 && !rc; ++r) rc = once();              // warm: weights and inputs in the caches, as between two steps
     (void)hipEventRecord(e0, s);
     for (int r = 0; r < reps && !rc; ++r) rc = once();
@@ -3070,7 +3037,7 @@ int grnet_time_convs(grnet_t* h, int n_frames, void* stream, float* ms_out) {
     grnet_outputs_t o{};
     hipEventRecord(e0, s);
     // the frames pointer of the first conv is only read; reuse the concat buffer as a stand-in input
-    int rc = h->enqueue(h->v_cat.p, n_frames, o, s, true);
+    int rc = h->enqueue(h->base(h->v_cat), n_frames, o, s, true);
     hipEventRecord(e1, s);
     hipEventSynchronize(e1);
     hipEventElapsedTime(ms_out, e0, e1);
@@ -3237,26 +3204,24 @@ int grnet_debug_tensor(grnet_t* h, const char* name, int n_frames, float* out_de
         return h->fail(GRNET_EINVAL, "debug tensor " + std::string(name) + ": n_frames " + std::to_string(n_frames) + " outside [1, frames of the last forward = " +
                                          std::to_string(h->last_n) + "]");
     DeviceGuard guard(h->device);
-    for (size_t ni = 0; ni < h->named.size(); ++ni) {
-        auto& nv = h->named[ni];
+    for (auto& nv : h->named) {
         if (nv.first != name) continue;
         const View& v = nv.second;
-        const int slot = h->named_slot[ni];
-        if (h->compact && (slot < 0 || !h->arena_plan.final_tenant[slot]))
+        if (h->compact && (v.slot < 0 || !h->arena_plan.final_tenant[v.slot]))
             return h->fail(GRNET_ESTATE, "debug tensor " + std::string(name) + " cannot be read back from a compact arena: a later tensor of the forward is placed over it. "
                                              "Create the handle without GRNET_CREATE_COMPACT_ARENA to read every intermediate");
-        if (!h->tap_written(v, slot))
+        if (!h->tap_written(v))
             return h->fail(GRNET_ESTATE, "debug tensor " + std::string(name) + " was not written by the last forward (" + std::to_string(h->last_n) +
                                              " frames): its producer ran inside a fused launch that keeps it on chip");
         if (shape_out) { shape_out[0] = v.c; shape_out[1] = v.h; shape_out[2] = v.w; }
         if (!out_dev) return 0;
         const size_t plane = (size_t)v.h * v.w;
         if (h->dtype == 1) {
-            hipError_t eb = launch_nhwc_bf16_to_nchw_f32(v.p, out_dev, n_frames, v.c, v.h, v.w, v.ctot, v.coff, static_cast<hipStream_t>(stream));
+            hipError_t eb = launch_nhwc_bf16_to_nchw_f32(h->base(v), out_dev, n_frames, v.c, v.h, v.w, v.ctot, v.coff, static_cast<hipStream_t>(stream));
             if (eb != hipSuccess) return h->fail(GRNET_EHIP, std::string("debug convert: ") + hipGetErrorString(eb));
             return 0;
         }
-        hipError_t e = hipMemcpy2DAsync(out_dev, (size_t)v.c * plane * 4, v.p + (size_t)v.coff * plane, (size_t)v.ctot * plane * 4,
+        hipError_t e = hipMemcpy2DAsync(out_dev, (size_t)v.c * plane * 4, h->base(v) + (size_t)v.coff * plane, (size_t)v.ctot * plane * 4,
                                         (size_t)v.c * plane * 4, n_frames, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("debug copy: ") + hipGetErrorString(e));
         return 0;

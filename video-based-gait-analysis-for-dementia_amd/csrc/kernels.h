@@ -1,6 +1,7 @@
 // Internal launch interface between the network plan (grnet.cpp) and the HIP kernels.
-// All tensors are fp32 NCHW in HBM; a View addresses a channel slice [coff, coff+c) of a
-// buffer that holds ctot channels per image, so producers write straight into their slice of
+// Activations live in HBM as fp32 NCHW (fp32 handles) or bf16 NHWC with channels padded to a multiple of 8
+// (bf16 handles; the tail after the pooling is fp32 either way).  A View names a channel slice [coff, coff+c)
+// of a planned buffer that holds ctot channels per image, so producers write straight into their slice of
 // the 480-channel concat buffer (reference: torch.cat, hrnet.py:524) with no copy kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -123,8 +124,12 @@ hipError_t launch_k(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem,
     return launch_k_impl(kern, grid, block, shmem, s, std::index_sequence_for<KArgs...>{}, std::forward<Args>(args)...);
 }
 
+// Plan-side only (no kernel sees one): a view holds the identity of its buffer, never an address.  The handle turns it into
+// the buffer's base (image 0, channel 0) at the launch: grnet::base().
 struct View {
-    float* p = nullptr;   // base of the whole buffer (image 0, channel 0)
+    static constexpr int kNone = -1;     // no buffer
+    static constexpr int kFrames = -2;   // the caller's frames: the pointer each forward is given
+    int slot = kNone;     // planned buffer, numbered in creation order (grnet::new_buffer)
     int ctot = 0;         // channels per image in the underlying buffer
     int coff = 0;         // first channel of this view
     int c = 0, h = 0, w = 0;
