@@ -81,7 +81,7 @@ def _t(a):
 
 
 def _fuse(oracle, xs, sd, p):
-    """The bf16 plan's fuse layer (csrc/grnet.cpp hr_fuse_separate) on the branch outputs xs, rounding where it stores: every 1x1 up term W_ij x_j (+ BN) is
+    """The bf16 plan's fuse layer (csrc/grnet_plan.cpp hr_fuse_separate) on the branch outputs xs, rounding where it stores: every 1x1 up term W_ij x_j (+ BN) is
     stored in bf16 at the source resolution and nearest-upsampled where it is consumed; every link of a down chain D_ij (j < i-1) is stored in bf16; output 0
     is an elementwise fp32 sum of x_0 and the up terms, rounded once (fuse_sum_bf16); output i >= 1 is the stride-2 convolution from branch i-1 with x_i,
     the D_ij and the up terms added in its fp32 epilogue -- that link is NOT rounded before the sum -- then ReLU and one rounding.  (oracle.hr_fuse
@@ -130,7 +130,7 @@ def _s2_rows_per_segment(n, wo):
 @pytest.mark.parametrize("n", SIZES)
 def test_stages_run_on_the_production_kernels(pkg, n):
     """grnet_conv_kernel_info at n frames: the stages checked below really are the LDS-resident kernels (a plan change that moves one back to the generic
-    kernel would otherwise leave this file checking the generic kernel).  Names are families (grnet.cpp kernel_name); within a family the launcher picks by
+    kernel would otherwise leave this file checking the generic kernel).  Names are families (grnet_run.cpp kernel_name); within a family the launcher picks by
     shape: conv_bf16_chain<256,7> is the frame-pair kernel (a grid of (N+1)/2), <32,56> the 8-convolution pipeline; conv_bf16_s2<28> on 32 -> 64 / 32 -> 32
     and conv_bf16_s2<14> on 64 -> 64 are the row walks conv_bf16_s2_rows, the other stride-2 shapes the band kernel; conv_bf16_wide<128,56> on 480 -> 256 is
     conv_bf16_wide_ring<256,56,4,true>."""

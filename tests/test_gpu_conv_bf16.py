@@ -305,7 +305,7 @@ FUSE_MODULES = [("stage2", 0, 2)] + [("stage3", m, 3) for m in range(4)] + [("st
 def fmodel(pkg):
     """The bf16 plan's fuse layer (hr_fuse_separate: one merged 1x1 launch per source branch, every output finished by its stride-2 convolution's epilogue, output 0
     by an elementwise sum).  Round 5 also measured two layouts around the grouped launch hr_fuse_up_bf16 (output 0 only / the fp32 path's layout); both lost and are
-    A/B variants of diagnostic builds only (GRNET_AB(BF16_FUSE_UP) in csrc/grnet.cpp) -- this fixture used to build them through an environment variable."""
+    A/B variants of diagnostic builds only (GRNET_AB(BF16_FUSE_UP) in csrc/grnet_plan.cpp) -- this fixture used to build them through an environment variable."""
     m = pkg.build_synthetic_model(max_frames=16, with_gru=False, dtype="bf16")
     yield m
     m.close()

@@ -365,7 +365,7 @@ def test_every_tuner_candidate_on_the_direct_launches(pkg, oracle, synth_weights
 def test_graph_replay_equals_eager_tap_for_tap(pkg):
     """The 16-frame forward replayed from a captured hipGraph (GRNET_OPT_USE_GRAPH) equals the eager lane streams in every tap and output, bit for
     bit (only digests of the eager run are kept).  A graph is keyed by the call's frame and output pointers and captured the second time its key
-    is seen (grnet.cpp forward), so the graph calls go through grnet_forward with ONE frames buffer and ONE set of output buffers: other frames
+    is seen (grnet_run.cpp forward), so the graph calls go through grnet_forward with ONE frames buffer and ONE set of output buffers: other frames
     (first sight: eager), the checked frames (captured, then replayed), other frames (replay), the checked frames again -- a replay."""
     n = 16
     digest = lambda got: {k: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for k, v in got.items()}

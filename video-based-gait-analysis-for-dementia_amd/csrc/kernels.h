@@ -1,4 +1,4 @@
-// Internal launch interface between the network plan (grnet.cpp) and the HIP kernels.
+// Internal launch interface between the runtime (grnet_impl.h: the plan of grnet_plan.cpp, the launch path of grnet_run.cpp) and the HIP kernels.
 // Activations live in HBM as fp32 NCHW (fp32 handles) or bf16 NHWC with channels padded to a multiple of 8
 // (bf16 handles; the tail after the pooling is fp32 either way).  A View names a channel slice [coff, coff+c)
 // of a planned buffer that holds ctot channels per image, so producers write straight into their slice of
@@ -71,7 +71,7 @@ inline hipError_t device_cu_count(int* cus) {                        // CUs of t
 }
 
 // Every kernel launch of the library goes through launch_k().  Normally it is a plain launch on the
-// given stream; while a GraphRecorder is installed (grnet.cpp builds the per-forward hipGraph with the
+// given stream; while a GraphRecorder is installed (grnet_run.cpp builds the per-forward hipGraph with the
 // explicit node API, one parallel branch per lane) it appends a kernel node that depends on
 // `rec->deps` instead, and leaves {that node} as the dependency of the next launch of the same op.
 struct GraphRecorder {
