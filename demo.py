@@ -2,15 +2,19 @@
 """demo.py of the MI355X-native path: same flags, model loop and .pkl schema as the reference's
 demo.py (argparse :391-456, loop :126-231, pickle :254-267), with the model running in libgrnet_hip.so.
 
-Out of scope here (rows 12, 17, 19): ffmpeg video decoding, the YOLOv3+SORT tracker and the
-matplotlib / pyrender output video.  So this entry point takes what the reference takes once those
-steps are done: --img_folder (extracted frames) and --tracking_path (joblib {id: {'bbox','frames'}}).
+Out of scope here (rows 12, 17): ffmpeg video decoding and the YOLOv3+SORT tracker.  So this entry point takes what the
+reference takes once those steps are done: --img_folder (extracted frames) and --tracking_path (joblib {id: {'bbox','frames'}}).
+--mesh_render draws the overlay frames (demo.py:269-385) with the library's own rasteriser: OpenGL's geometry rules, a stated Lambert
+shading that is NOT pyrender's; --wireframe, --display and the matplotlib skeleton view stay refused.
 The reference's --cpu_only (demo.py:46-49,403) is accepted and refused with one line: there is deliberately no CPU fallback.
 """
 import argparse
+import colorsys
 import importlib
 import os
 import os.path as osp
+import shutil
+import subprocess
 import sys
 import time
 
@@ -58,6 +62,80 @@ def build_model(pkg, args, seqlen):
     return model.finalize()
 
 
+RENDER_CHUNK = 16            # frames uploaded, drawn and downloaded together
+
+
+def refusal(a):
+    """One line for a flag this build parses and refuses, None otherwise."""
+    if a.cpu_only:
+        return CPU_ONLY_MESSAGE
+    if a.wireframe:
+        return "--wireframe needs OpenGL's line rasterisation, which the library's triangle rasteriser does not have: not implemented"
+    if a.display:
+        return "--display opens a window (cv2.imshow / matplotlib) and is not implemented: the frames of --mesh_render are written to disk"
+    return None
+
+
+def render_overlay(model, pipe, args, results, verts_dev, output_path, stem):
+    """demo.py:269-385 with --mesh_render: every image of the folder is written as %06d.png -- the persons of the frame drawn far to near, each
+    in its random HSV colour, over the frame; with --sideview the same meshes turned by 270 degrees about y on black, appended to the right of
+    EVERY frame (the reference widens only frames with a person; frames of one size are what a video needs).  A frame without a person is its
+    input.  --save_obj writes the turned mesh per person and frame, with or without --mesh_render."""
+    import torch
+    from PIL import Image
+    names = sorted(x for x in os.listdir(args.img_folder) if x.endswith((".png", ".jpg")))
+    every = sorted(x for x in os.listdir(args.img_folder) if x.endswith((".png", ".jpg", ".npy")))
+    if args.mesh_render and (not names or names != every):
+        sys.exit("--mesh_render draws over image frames (.png / .jpg): this folder holds ready .npy crops")
+    n_frames = len(every)
+    last = max((int(np.max(r["frame_ids"])) for r in results.values() if len(r["frame_ids"])), default=-1)
+    if last >= n_frames:
+        sys.exit(f"the tracking file names frame {last}, but {args.img_folder} holds {n_frames} frames")
+    frame_results = pipe.prepare_rendering_results(results, list(range(n_frames)))
+    mesh_color = {k: colorsys.hsv_to_rgb(np.random.rand(), 0.5, 1.0) for k in results}       # demo.py:277
+    folder = osp.join(output_path, stem + "_output")
+    if args.mesh_render:
+        os.makedirs(folder, exist_ok=True)
+        print(f"Rendering output video, writing frames to {folder}.")
+    for s in range(0, n_frames, RENDER_CHUNK):
+        idxs = range(s, min(n_frames, s + RENDER_CHUNK))
+        rows, cams, cols, where = [], [], [], []
+        for k, fi in enumerate(idxs):
+            for pid, pd in frame_results[fi].items():
+                cams.append(pd["cam"]), cols.append(mesh_color[pid]), where.append(k)
+                if args.mesh_render:
+                    rows.append(verts_dev[pid][pd["row"]])
+                if args.save_obj:                                                            # demo.py:332-335
+                    obj_dir = osp.join(output_path, "rendered", f"{pid:04d}")
+                    os.makedirs(obj_dir, exist_ok=True)
+                    pipe.write_obj(osp.join(obj_dir, f"{fi:06d}.obj"), pd["verts"], model.faces)
+        if not args.mesh_render:
+            continue
+        imgs = torch.from_numpy(np.stack([np.asarray(Image.open(osp.join(args.img_folder, names[i])).convert("RGB")) for i in idxs])).to(model.device)
+        verts = torch.stack(rows) if rows else None
+        if rows:
+            model.render(imgs, verts, np.stack(cams), cols, where)
+        if args.sideview:
+            side = torch.zeros_like(imgs)
+            if rows:
+                model.render(side, verts, np.stack(cams), cols, where, M=model.SIDE_VIEW)
+            imgs = torch.cat([imgs, side], 2)
+        out = imgs.cpu().numpy()
+        for k, fi in enumerate(idxs):
+            Image.fromarray(out[k]).save(osp.join(folder, f"{fi:06d}.png"))
+    if not args.mesh_render:
+        return None
+    if args.save_vid and shutil.which("ffmpeg"):                                             # demo.py:379-383, demo_utils.py:160-173
+        save_name = osp.join(output_path, stem + ".mp4")
+        command = ["ffmpeg", "-y", "-threads", "16", "-start_number", "0", "-i", f"{folder}/%06d.png", "-profile:v", "baseline", "-level", "3.0",
+                   "-c:v", "libx264", "-pix_fmt", "yuv420p", "-an", "-v", "error", save_name]
+        print(f"Saving result video to {save_name}")
+        subprocess.call(command)
+    else:
+        print(f"The rendered frames are in {folder} (no video: {'--save_vid switches it off' if not args.save_vid else 'no ffmpeg on PATH'}).")
+    return folder
+
+
 def main(args):
     import joblib
     pkg = importlib.import_module(PKG)
@@ -76,6 +154,8 @@ def main(args):
         if tracking[pid]["frames"].shape[0] < MIN_NUM_FRAMES:
             del tracking[pid]
     model = build_model(pkg, args, cfg["DATASET"]["SEQLEN"])
+    if (args.mesh_render or args.save_obj) and model.faces is None:
+        sys.exit("--mesh_render / --save_obj need the face table: the checkpoint holds no regressor.smpl.smpl.faces_tensor and SMPL_NEUTRAL.npz was not read")
     ai = model.arena_info()
     print(f"Activation arena: {ai['bytes'] / 2**20:.0f} MiB for calls of up to {args.max_frames} frames "
           f"({'one buffer per tensor' if args.full_arena else 'buffers shared by liveness'}; the full layout takes {ai['full_bytes'] / 2**20:.0f} MiB)")
@@ -86,26 +166,32 @@ def main(args):
         else:
             smpl_tables = {"J_regressor_extra": np.load(osp.join(args.smpl_dir, "J_regressor_extra.npy"))}
     t0 = time.time()
-    results, n_frames = {}, 0
+    results, verts_dev, n_frames = {}, {}, 0
     for pid, tr in tracking.items():
         bboxes, frames = np.asarray(tr["bbox"], np.float32).copy(), np.asarray(tr["frames"])
         ds = pipe.InferenceFrames(args.img_folder, frames, bboxes, scale=1.0)
-        on_device = args.smooth and not args.smooth_on_host
+        device_smooth = args.smooth and not args.smooth_on_host
+        on_device = device_smooth or args.mesh_render          # the overlay draws the vertices where the forward left them
         pred = pipe.run_tracklet(model, ds.batches(args.grnet_batch_size, model=model), on_device=on_device)
         w, h = ds.image_size()
+        theta = pred.pop("theta", None)
         if args.smooth:                                        # demo.py:191-196
             print(f"Running smoothing on person {pid}, min_cutoff: {args.smooth_min_cutoff}, beta: {args.smooth_beta}")
-            if on_device:
+            if device_smooth:
                 # filter, Rodrigues, SMPL and the 49 joints on the GPU, reading theta in place; only what the pickle holds is downloaded
                 # (the first pass's verts and joints3d are dropped on the device)
-                theta = pred.pop("theta")
                 pred["verts"], pred["pose"], pred["joints3d"] = model.smooth_pose(
                     theta, theta[:, 75:], min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta, joints="spin49")
-                pred = {k: v.cpu().numpy() for k, v in pred.items()}
             else:
+                if on_device:                                  # the host statement takes and returns numpy
+                    pred = {k: v.cpu().numpy() for k, v in pred.items()}
                 pred["verts"], pred["pose"], pred["joints3d"] = pipe.smooth_pose(
                     model, pred["pose"], pred["betas"], min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta,
                     smpl_tables=smpl_tables)
+        if args.mesh_render:
+            import torch
+            verts_dev[pid] = torch.as_tensor(pred["verts"]).to(model.device)
+        pred = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in pred.items()}
         results[pid] = pipe.make_demo_result(pred, ds.bboxes, ds.frames, w, h)
         if args.joint_type != "spin":                          # demo.py:224-229
             # the reference converts with src='spin' (49 joints); without --smooth the path emits the 29 'spin2' joints, on which
@@ -129,6 +215,8 @@ def main(args):
         out = osp.join(output_path, f"{stem}{idx}.pkl")
     joblib.dump(results, out)
     print(f'Saving output results to "{out}".')
+    if args.mesh_render or args.save_obj:
+        render_overlay(model, pipe, args, results, verts_dev, output_path, osp.basename(out)[:-len(".pkl")])
     return out
 
 
@@ -142,11 +230,11 @@ def parser():
     p.add_argument("--yolo_img_size", type=int, default=416)
     p.add_argument("--tracker_batch_size", type=int, default=12)
     p.add_argument("--grnet_batch_size", type=int, default=450)
-    p.add_argument("--display", action="store_true")
-    p.add_argument("--mesh_render", action="store_true")
-    p.add_argument("--wireframe", action="store_true")
-    p.add_argument("--sideview", action="store_true")
-    p.add_argument("--save_obj", action="store_true")
+    p.add_argument("--display", action="store_true", help="parsed, and refused: no window is opened")
+    p.add_argument("--mesh_render", action="store_true", help="write the overlay frames (and the video, if ffmpeg is on PATH): the meshes drawn over the input frames on the GPU")
+    p.add_argument("--wireframe", action="store_true", help="parsed, and refused: needs line rasterisation")
+    p.add_argument("--sideview", action="store_true", help="with --mesh_render: append the meshes seen from the side, on black, to the right of every frame")
+    p.add_argument("--save_obj", action="store_true", help="write rendered/<person>/<frame>.obj, the mesh as the renderer turns it")
     p.add_argument("--smooth", action="store_true")
     p.add_argument("--smooth_min_cutoff", type=float, default=0.004)
     p.add_argument("--smooth_beta", type=float, default=0.7)
@@ -155,7 +243,7 @@ def parser():
     p.add_argument("--tracking_path", type=str, default=None)
     p.add_argument("--img_folder", type=str, default=None)
     p.add_argument("--joint_type", type=str, default="spin")
-    p.add_argument("--save_vid", action="store_false")
+    p.add_argument("--save_vid", action="store_false", help="as in the reference this switch turns the video OFF (store_false): the frames are kept, ffmpeg is not run")
     p.add_argument("--cpu_only", action="store_true", help="the reference's CPU switch (demo.py:403): parsed, and refused -- this build has no CPU path")
     # additions of this implementation
     p.add_argument("--synthetic_weights", action="store_true", help="seed-defined weights (no checkpoint exists offline)")
@@ -169,13 +257,13 @@ def parser():
 
 if __name__ == "__main__":
     a = parser().parse_args()
-    if a.cpu_only:
-        sys.exit(CPU_ONLY_MESSAGE)
-    for flag in ("mesh_render", "display", "save_obj"):
-        if getattr(a, flag):
-            sys.exit(f"--{flag} belongs to steps outside the per-frame path (SURVEY 8f) and is not implemented")
+    if refusal(a):
+        sys.exit(refusal(a))
     d = parser().parse_args([])
-    for flag in ("detector", "yolo_img_size", "tracker_batch_size", "wireframe", "sideview", "save_vid"):
+    for flag in ("detector", "yolo_img_size", "tracker_batch_size"):
         if getattr(a, flag) != getattr(d, flag):
-            print(f"warning: --{flag} configures a step outside the per-frame path (tracker / renderer, SURVEY 8f) and has no effect here")
+            print(f"warning: --{flag} configures a step outside the per-frame path (the tracker, SURVEY 8f) and has no effect here")
+    for flag in ("sideview", "save_vid"):
+        if getattr(a, flag) != getattr(d, flag) and not a.mesh_render:
+            print(f"warning: --{flag} configures the output video and has no effect without --mesh_render")
     main(a)

@@ -369,6 +369,45 @@ int grnet_op_one_euro(grnet_t* h, const float* x_dev, int ld, int T, float min_c
 int grnet_smooth_pose(grnet_t* h, const float* pose_dev, int pose_ld, const float* betas_dev, int T, float min_cutoff, float beta, int joints_kind,
                       float* pose_hat_dev, float* verts_dev, float* joints_dev, void* stream);
 
+/* ---- the mesh overlay of demo.py --mesh_render -- lib/utils/renderer.py:78-126 (csrc/render_kernels.hip; the rules in full: DESIGN.md 4.5) ---------
+ * What the reference asks of pyrender, on the device: one opaque triangle mesh per call of Renderer.render, a weak-perspective camera, a z-buffer,
+ * and the mask composite over the frame.  GEOMETRY follows OpenGL's rules: q = M (x, -y, -z); x_ndc = sx (q.x + tx), y_ndc = sy (q.y - ty),
+ * z_ndc = -q.z; window coordinates with the origin at the bottom-left, snapped to 8 sub-pixel bits; the pixel centre is the sample; faces whose
+ * doubled signed area in window space is <= 0 are culled (counter-clockwise is the front); a centre exactly on an edge is covered only if the edge is
+ * a top or a left edge in image space; fragments with z outside [-1, 1] are discarded; GL_LESS, the lower face index winning at equal fp32 depth;
+ * image row = H - 1 - GL row.  Coverage and the winning face do not depend on execution order.  SHADING is a stated Lambert model -- ambient 0.3 and
+ * the reference's three point lights at (0,-1,1), (0,1,1), (1,1,2) in q space, shade = 0.3 + sum max(0, n.l) / (pi d^2) on the interpolated
+ * area-weighted vertex normal -- and is NOT pyrender's metallic-roughness shader: pixel parity with pyrender is not claimed.
+ *
+ * grnet_load_faces: the (n_faces,3) int32 face table of the 6890-vertex mesh (smpl.faces / SMPL_NEUTRAL.npz 'f'), host pointer; indices are
+ * validated (GRNET_EINVAL names the first bad one) and the vertex -> face table of the normals is built.  Before or after
+ * grnet_finalize_weights; a second call replaces the table (it synchronises the device first); a failed call leaves the earlier table in place. */
+int grnet_load_faces(grnet_t* h, const int32_t* faces_host, int n_faces);
+/* Draws n meshes: verts_dev (n,6890,3) and cams_dev (n,4) rows [sx, sy, tx, ty] are device pointers; colours_host (n,3), in the image's MEMORY
+ * order of channels, and image_index_host (n) are host pointers; M_host: 9 floats, row-major, or NULL for the identity (the main view; the
+ * reference's --sideview is the rotation by 270 degrees about y, {0,0,-1, 0,1,0, 1,0,0}).  images_dev: uint8 (F,H,W,3), in/out: byte k of a covered
+ * pixel becomes floor(255 min(1, colour_k shade) + 0.5), EVERY other byte is left as it is.  Meshes aimed at the same image are drawn in call order,
+ * later over earlier, each with a fresh depth buffer (the reference's loop over the persons of a frame, far to near).
+ * Everything is enqueued on `stream`, no host synchronisation.  n is NOT limited by max_frames.  Workspace: ONE allocation of 128 MiB + 3.8 MiB at
+ * the first call on the handle, outside the activation arena (grnet_arena_query / grnet_arena_info are unchanged): the depth images (8 bytes a
+ * pixel) of one launch group share the 128 MiB, which is one 4096 x 4096 image, and 16 meshes' vertex records take the rest.  A launch group is
+ * min(16, 4096 * 4096 / (H * W)) meshes of different images (7 at 1920 x 1080); the host splits the call into layers holding the k-th mesh of
+ * every image and each layer into such groups, in stream order; a group is five launches and a 256-byte memset.  Depth clears and the resolve are
+ * confined to each mesh's bounding box.  Calls on a handle must be ordered (one stream, or events between streams), as for grnet_forward's arena.
+ * GRNET_EINVAL (with a message): n < 0, H or W outside [1, 4096], F < 1, an image_index outside [0, F), a null pointer; GRNET_ESTATE: before
+ * grnet_load_faces.  n == 0 is a no-op that reads no pointer; the checks of n, H, W, F and of the face table come first, so an empty call with
+ * a bad size, or on a handle without faces, is still refused. */
+int grnet_render_meshes(grnet_t* h, const float* verts_dev, int n, const float* cams_dev, const float* colours_host, const int32_t* image_index_host,
+                        const float* M_host, unsigned char* images_dev, int F, int H, int W, void* stream);
+/* The stages alone, on ANY small mesh: V vertices, F faces (faces_host (F,3) int32, validated against V), one camera cam_dev (4).
+ * grnet_op_raster_setup: verts_dev (V,3) -> xy_dev (V,2) int32 snapped window coordinates, z_dev (V) z_ndc, normals_dev (V,3) unit vertex normals.
+ * grnet_op_raster: xy_dev, z_dev as above -> winner_dev (H,W) int32 in image rows: the winning face per pixel, -1 where uncovered.
+ * Both allocate temporaries and synchronise `stream` before they return (test hooks, like grnet_op_conv2d). */
+int grnet_op_raster_setup(grnet_t* h, const float* verts_dev, int V, const int32_t* faces_host, int F, const float* cam_dev, const float* M_host,
+                          int H, int W, int32_t* xy_dev, float* z_dev, float* normals_dev, void* stream);
+int grnet_op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W, int32_t* winner_dev,
+                    void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

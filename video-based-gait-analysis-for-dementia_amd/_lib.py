@@ -16,6 +16,7 @@ PRECISION_F32, PRECISION_BF16 = 0, 1
 CREATE_COMPACT_ARENA = 1
 JOINT_REGRESSOR_MAX_ROWS = 64
 JOINTS_SPIN49, JOINTS_SPIN2, JOINTS_KINECTV2 = 0, 1, 2
+RASTER_MAX_DIM, RASTER_SLOTS = 4096, 16
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
 
@@ -94,6 +95,12 @@ EXPORTS = {
     "grnet_op_one_euro": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "grnet_smooth_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "grnet_load_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "grnet_render_meshes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p]),
+    "grnet_op_raster_setup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grnet_op_raster": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "grnet_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "grnet_comm_probe": (C.c_int, []),
     "grnet_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int]),

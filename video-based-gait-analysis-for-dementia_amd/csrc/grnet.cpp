@@ -23,6 +23,8 @@ grnet::~grnet() {
     for (hipEvent_t e : op_events_flat) if (e) (void)hipEventDestroy(e);
     for (void* p : dev_allocs) (void)hipFree(p);
     jreg_clear();
+    faces_clear();
+    if (raster_ws) (void)hipFree(raster_ws);
     if (temporal_ws) (void)hipFree(temporal_ws);
     if (gru_fault) (void)hipHostFree(gru_fault);
     if (arena) (void)hipFree(arena);

@@ -3,6 +3,7 @@
 //   grnet_weights.cpp  the weight loader (reference state_dict keys -> BN-folded, kernel-layout weights) and its entry points
 //   grnet_run.cpp      allocation, kernel choice, the launch path, the graph cache, the tuner
 //   grnet_hooks.cpp    the single-op test and timing hooks
+//   grnet_render.cpp   the mesh overlay: the face table, grnet_render_meshes and its two stage hooks
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -224,6 +225,11 @@ struct grnet {
     int jreg_rows = 0;
     // grnet_smooth_pose: rotations (max_frames,24,9) | betas (max_frames,10) | kp (max_frames,29,3), allocated at the first call, outside the arena
     float* smooth_ws = nullptr;
+    // grnet_load_faces: the face table with its vertex -> face rows (one device block); grnet_render_meshes: the vertex records and depth images of
+    // up to kRasterSlots meshes, allocated at the first call, outside the arena (grnet_render.cpp)
+    RasterMesh rmesh{};
+    void* rmesh_block = nullptr;
+    void* raster_ws = nullptr;
 
     // ------------------------------------------------------------------ the schedule, the tuning tables and the graph cache (grnet_run.cpp)
     std::vector<Op> ops_flat;   // the same ops placed on the lane streams by schedule_lanes(): the enqueue order
@@ -365,6 +371,7 @@ struct grnet {
     ~grnet();
     int dev_alloc(float** p, size_t floats);
     void jreg_clear();
+    void faces_clear();
     const Op* nth_conv_op(int pos) const;
     int gru_fault_check();
     int taps_begin(size_t need, const char* what);

@@ -317,6 +317,42 @@ void joint_regress_pack(const float* W /* (jout,6890) host */, int jout, float* 
 // verts (n,6890,3), 8-byte aligned -> joints (n,jout,3); partial: joint_regress_workspace_floats(jout, >= n) device floats
 hipError_t launch_joint_regress(const float* verts, const float* wpack, int jout, float* partial, float* joints, int n, hipStream_t s);
 
+// The mesh overlay of demo.py --mesh_render (lib/utils/renderer.py:78-126; csrc/render_kernels.hip) ----
+constexpr int kRasterSlots = 16;             // meshes per launch group: each has its own depth image and vertex records in the workspace
+constexpr int kRasterMaxDim = 4096;          // largest image side
+constexpr int kRasterSnapBits = 8;           // sub-pixel bits of the snapped window coordinates
+constexpr int kRasterCoordLimit = 1 << 28;   // |X|, |Y| are clamped here: coordinate differences < 2^29 + 2^21, edge products < 2^59, their sums fit int64
+struct RasterView { float M[9]; int H, W; };                      // q = M (x, -y, -z); the viewport
+struct RasterMesh {                                               // the topology of one mesh, device pointers (grnet_load_faces)
+    const int* faces;      // (n_faces,3)
+    const int* vf_off;     // (n_verts+1) row offsets of ...
+    const int* vf_idx;     // ... the faces at each vertex, ascending face index
+    int n_verts, n_faces;
+};
+struct RasterWork {                                               // per slot s: element s * n_verts of the vertex records, s * H * W of depth
+    float* q;              // (slots,n_verts,3) transformed positions
+    int* xy;               // (slots,n_verts,2) snapped window coordinates
+    float* z;              // (slots,n_verts)   z_ndc
+    float* nrm;            // (slots,n_verts,3) unit vertex normals in q space
+    int* bbox;             // (slots,4) max over the vertices of (-X, -Y, X, Y)
+    unsigned long long* depth;   // (slots,H,W) (ordered z << 32) | face, GL rows
+};
+struct RasterChunk {                                              // what the host knows about the meshes of one launch group
+    int n;                          // <= kRasterSlots
+    int mesh[kRasterSlots];         // index into verts / cams of the call
+    int image[kRasterSlots];
+    float colour[kRasterSlots][3];  // in the image's memory order
+};
+size_t raster_depth_words(int H, int W);     // 64-bit words of one depth image
+// verts (n,n_verts,3), cams (n,4) -> the vertex records and the bounding box of every slot of the chunk (a memset and two launches)
+hipError_t launch_raster_setup(const float* verts, const float* cams, const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s);
+// depth of every slot: cleared inside the mesh's bounding box, then the z-buffer over the faces (two launches)
+hipError_t launch_raster_cover(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s);
+// shade the covered pixels of every slot into its image: images (F,H,W,3) uint8, every other byte untouched
+hipError_t launch_raster_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s);
+// slot 0's winning face per pixel in IMAGE rows, -1 where uncovered: winner (H,W) int32, every element written
+hipError_t launch_raster_winner(const RasterView& v, RasterWork w, int* winner, hipStream_t s);
+
 // GRU gait encoder (gait_feat_encoder.py:79-104) ------------------------------------------------
 struct GruWeights {
     const float* cparam_w;                 // (128,3,24)

@@ -30,7 +30,7 @@ _IncompatibleKeys = namedtuple("_IncompatibleKeys", ["missing_keys", "unexpected
 
 SMPL_PREFIX = "regressor.smpl.smpl."
 _SMPL_KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "parents", "J_regressor_extra")
-_TOLERATED_SMPL_KEYS = ("faces_tensor", "vertex_joint_selector.extra_joints_idxs", "betas", "global_orient",
+_TOLERATED_SMPL_KEYS = ("vertex_joint_selector.extra_joints_idxs", "betas", "global_orient",
                         "body_pose", "transl")
 
 
@@ -136,6 +136,7 @@ class GRNet:
         self._h = h
         self._finalized = False
         self._smpl_loaded = False
+        self.faces = None                 # host copy of the (F,3) int32 face table render() draws (load_faces)
         self._loaded = set()
         self._jreg = None                 # (host copy of the table, selection, the object it came from, its version) of the table on the device
         self.joint_regressor_uploads = 0  # tables handed to grnet_set_joint_regressor so far
@@ -174,18 +175,34 @@ class GRNet:
                                        ptr(parents), ptr(extra))
         _lib.check(self._lib, self._h, rc, "grnet_load_smpl")
         self._smpl_loaded = True
+        if "f" in tables:                    # SMPL_NEUTRAL.npz carries the face table the overlay draws
+            self.load_faces(tables["f"])
+
+    def load_faces(self, faces):
+        """The (F,3) face table of the 6890-vertex mesh (smplx's faces_tensor, 'f' of SMPL_NEUTRAL.npz) for render(); before or after
+        finalize(), a second table replaces the first (grnet_load_faces)."""
+        if torch.is_tensor(faces):
+            faces = faces.detach().cpu().numpy()
+        f = np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+            raise ValueError(f"faces must be an integer (F,3) table, got {f.dtype} {f.shape}")
+        f = np.ascontiguousarray(f.astype(np.int64).clip(-1, 2**31 - 1), dtype=np.int32)     # an index that does not fit stays out of range
+        _lib.check(self._lib, self._h, self._lib.grnet_load_faces(self._h, f.ctypes.data_as(C.c_void_p), f.shape[0]), "grnet_load_faces")
+        self.faces = f
 
     def load_state_dict(self, state_dict, strict=True):
         """Reference key names (demo.py:116-122; batch_generation.py:214-218)."""
         if self._finalized:
             raise RuntimeError("weights are already finalized on the device")
         spec = netspec.grnet_spec()
-        unexpected, smpl = [], {}
+        unexpected, smpl, faces = [], {}, None
         for k, v in state_dict.items():
             if k.startswith(SMPL_PREFIX):
                 name = k[len(SMPL_PREFIX):]
                 if name in _SMPL_KEYS:
                     smpl[name] = v
+                elif name == "faces_tensor":
+                    faces = v
                 elif name not in _TOLERATED_SMPL_KEYS:
                     unexpected.append(k)
             elif k in spec or k.startswith(("pfeat_corrector.", "gru.", "tsattn.")):
@@ -201,6 +218,8 @@ class GRNet:
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for GRNet: missing {missing[:5]}{'...' if len(missing) > 5 else ''}"
                                f" unexpected {unexpected[:5]}{'...' if len(unexpected) > 5 else ''}")
+        if faces is not None:                # after the checks above: a state dict they reject leaves the handle's face table as it was
+            self.load_faces(faces)
         return _IncompatibleKeys(missing, unexpected)
 
     def load_pare_dict(self, pretrained_pare):
@@ -774,6 +793,66 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_smooth_pose")
         return verts, pose_hat, out
 
+    # ------------------------------------------------------------------ the mesh overlay (demo.py --mesh_render)
+    SIDE_VIEW = (0.0, 0.0, -1.0, 0.0, 1.0, 0.0, 1.0, 0.0, 0.0)      # the reference's --sideview: rotation by 270 degrees about y (demo.py:351-352)
+
+    def render(self, images, verts, cams, colours, image_index, M=None, rgb=True):
+        """Draw n meshes into uint8 device images (F,H,W,3) IN PLACE and return them (grnet_render_meshes; the rules: DESIGN.md 4.5).  verts
+        (n,6890,3) and cams (n,4) rows [sx,sy,tx,ty] -- host or device; colours (n,3): the (r,g,b) triples the reference hands to
+        Renderer.render; image_index (n): the image each mesh is drawn into.  Meshes of one image are drawn in the order given, later over
+        earlier.  M: 9 floats, None for the main view, GRNet.SIDE_VIEW for --sideview.  Nothing synchronises; n is not limited by max_frames.
+        rgb: the reference writes its (r,g,b) triple into a BGR image (cv2) WITHOUT swapping, so what it shows is (b,g,r) of the triple.
+        pipeline keeps frames in RGB, so the triple goes down reversed to put the same colour on the screen; rgb=False: BGR frames, as is."""
+        if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda \
+                or not images.is_contiguous():
+            raise ValueError("images must be a contiguous uint8 (F,H,W,3) tensor on the device")
+        F, H, W = images.shape[:3]
+        v = torch.as_tensor(verts).to(self.device, torch.float32).contiguous()
+        if v.dim() != 3 or tuple(v.shape[1:]) != (6890, 3):
+            raise ValueError(f"verts must be (n,6890,3), got {tuple(v.shape)}")
+        n = v.shape[0]
+        c = torch.as_tensor(cams).to(self.device, torch.float32).reshape(-1, 4).contiguous()
+        col = np.ascontiguousarray(np.asarray(colours, np.float32).reshape(-1, 3)[:, ::-1] if rgb else np.asarray(colours, np.float32).reshape(-1, 3))
+        idx = np.ascontiguousarray(np.asarray(image_index, np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
+        if not (c.shape[0] == col.shape[0] == idx.shape[0] == n):
+            raise ValueError(f"verts, cams, colours and image_index disagree on n: {n}, {c.shape[0]}, {col.shape[0]}, {idx.shape[0]}")
+        Mh = None if M is None else np.ascontiguousarray(np.asarray(M, np.float32).reshape(9))
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_render_meshes(self._h, v.data_ptr(), n, c.data_ptr(), col.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                           Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, images.data_ptr(), F, H, W, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_render_meshes")
+        return images
+
+    def op_raster_setup(self, verts, faces, cam, H, W, M=None):
+        """verts (V,3), faces (F,3), cam (4) -> (xy (V,2) int32 snapped window coordinates, z (V), unit vertex normals (V,3)) on the device
+        (grnet_op_raster_setup)."""
+        v = torch.as_tensor(verts).to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
+        c = torch.as_tensor(cam).to(self.device, torch.float32).reshape(4).contiguous()
+        Mh = None if M is None else np.ascontiguousarray(np.asarray(M, np.float32).reshape(9))
+        V = v.shape[0]
+        xy = torch.empty(V, 2, dtype=torch.int32, device=self.device)
+        z = torch.empty(V, dtype=torch.float32, device=self.device)
+        nrm = torch.empty(V, 3, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_raster_setup(self._h, v.data_ptr(), V, f.ctypes.data_as(C.c_void_p), f.shape[0], c.data_ptr(),
+                                             Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, H, W, xy.data_ptr(), z.data_ptr(), nrm.data_ptr(),
+                                             stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_raster_setup")
+        return xy, z, nrm
+
+    def op_raster(self, xy, z, faces, H, W):
+        """Snapped vertices xy (V,2) int32 and z (V) -> the winning face per pixel (H,W) int32 in image rows, -1 where uncovered (grnet_op_raster)."""
+        xy = torch.as_tensor(xy).to(self.device, torch.int32).reshape(-1, 2).contiguous()
+        z = torch.as_tensor(z).to(self.device, torch.float32).reshape(-1).contiguous()
+        f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
+        out = torch.empty(H, W, dtype=torch.int32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_raster(self._h, xy.data_ptr(), z.data_ptr(), xy.shape[0], f.ctypes.data_as(C.c_void_p), f.shape[0], H, W, out.data_ptr(),
+                                       stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_raster")
+        return out
+
     # single-op hooks for kernel parity tests
     def op_conv2d(self, x, w, bias=None, stride=1, relu=False, add=None, tile_hint=0):
         n, cin, h, wd = x.shape
@@ -864,4 +943,5 @@ def build_synthetic_model(max_frames=64, device_id=0, with_gru=True, with_tsattn
         sd.update({"tsattn." + k: v for k, v in synth.make_tsattn_state_dict().items()})
     m.load_state_dict(sd, strict=True)
     m.load_smpl(synth.make_smpl_tables())
+    m.load_faces(synth.make_faces())
     return m.finalize()

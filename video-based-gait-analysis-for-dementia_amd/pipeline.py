@@ -376,6 +376,39 @@ def make_demo_result(pred, bboxes, frames, orig_width, orig_height):
     }
 
 
+def prepare_rendering_results(results, nframes):
+    """demo_utils.py:212-247 in its non-concat form: {person: per-person dict} -> {frame: OrderedDict person -> {'verts','cam','j3d','j2d'}}
+    for the frames listed in ``nframes``, the persons of a frame sorted far to near by the y-scale of the camera in the original image
+    (orig_cam[1] ascending, :242-246).  Added here: 'row', the index of the frame in the person's arrays, so that a caller which keeps the
+    vertices on the device draws row ``row`` of its own tensor instead of the host copy."""
+    from collections import OrderedDict
+    if not isinstance(nframes, list):
+        raise TypeError("Input should be list of valid frames !!")
+    frame_results = {nf: {} for nf in nframes}
+    for person_id, person_data in results.items():
+        for idx, frame_id in enumerate(person_data["frame_ids"]):
+            frame_results[int(frame_id)][person_id] = {
+                "verts": person_data["verts"][idx],
+                "cam": person_data["orig_cam"][idx],
+                "j3d": person_data["joints3d"][idx],
+                "j2d": person_data["joints2d"][idx],
+                "row": idx,
+            }
+    for frame_id, frame_data in frame_results.items():
+        keys = list(frame_data.keys())
+        sort_idx = np.argsort([frame_data[k]["cam"][1] for k in keys])
+        frame_results[frame_id] = OrderedDict((keys[i], frame_data[keys[i]]) for i in sort_idx)
+    return frame_results
+
+
+def write_obj(path, verts, faces):
+    """The mesh renderer.py:82-86 exports per person and frame: the vertices turned by 180 degrees about x, (x, -y, -z), and the faces, 1-based."""
+    v = np.asarray(verts, np.float64) * np.array([1.0, -1.0, -1.0])
+    with open(path, "w") as f:
+        f.write("".join(f"v {x:.8f} {y:.8f} {z:.8f}\n" for x, y, z in v))
+        f.write("".join(f"f {a} {b} {c}\n" for a, b, c in np.asarray(faces, np.int64) + 1))
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped

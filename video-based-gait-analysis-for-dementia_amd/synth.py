@@ -166,6 +166,19 @@ def make_smpl_tables(seed=SMPL_SEED):
     }
 
 
+def make_faces(nu=65, nv=106):
+    """A (13780,3) int32 face table over the 6890 synthetic vertices, so --synthetic_weights has something to draw: vertex i * nv + j is
+    taken as node (i, j) of an nu x nv grid that closes on itself in both directions (a torus), two triangles per cell.  Seed-free; closed
+    (every edge has two faces).  The synthetic vertices are a point cloud, so the picture is a tangle of triangles -- it exercises the
+    renderer, it does not look like a body."""
+    if nu * nv != netspec.NUM_VERTS:
+        raise ValueError(f"nu * nv must be {netspec.NUM_VERTS}")
+    idx = np.arange(nu * nv, dtype=np.int32).reshape(nu, nv)
+    a, b = idx, np.roll(idx, -1, 0)
+    c, d = np.roll(b, -1, 1), np.roll(idx, -1, 1)
+    return np.ascontiguousarray(np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)]))
+
+
 def make_joint_regressor(rows, nnz=None, signed=False, seed=SMPL_SEED):
     """A (rows,6890) f32 joint regressor for the J_regressor override (pare.py:70-76), defined by its recipe (rows, nnz, signed, seed).
 
