@@ -184,7 +184,7 @@ int grnet_temporal_tap_layout(grnet_t* h, char* buf, int buf_size);
                                    * convolution is the direct implicit GEMM.  grnet_op_conv2d tile hints 2001 / 2020 (+ K split) run the two kernels on
                                    * one convolution.  (Options 4, 5, 6 -- grouped launches, the persistent dataflow launch and its fence -- were removed
                                    * in round 3 after losing every measurement; their sources are in the history: commit 8d3a931.) */
-#define GRNET_OPT_BF16_CHAIN 8    /* bf16 handles, a mask of the band- / frame-resident kernel groups of csrc/conv_bf16_chain.hip and csrc/conv_bf16.hip (default: all bits = -1;
+#define GRNET_OPT_BF16_CHAIN 8    /* bf16 handles, a mask of the band- / frame-resident kernel groups of csrc/conv_bf16_chain.hip, conv_bf16_wide.hip, conv_bf16_s2.hip and csrc/conv_bf16.hip (default: all bits = -1;
                                    * process-wide default from the environment variable GRNET_BF16_CHAIN; 0: one launch of the generic kernel per convolution at every
                                    * call size).  Bits 0-3: the four BasicBlocks (8 convolutions, lib/models/hrnet.py:141-187) of an HR branch as ONE launch with the
                                    * frame resident in LDS, in calls of >= 64 frames -- bit 0: 64 ch @28x28, bit 1: 128 ch @14x14, bit 2: 256 ch @7x7, bit 3: 32 ch

@@ -121,7 +121,7 @@ def _slices(h, segs=()):
 
 
 def _s2_rows_per_segment(n, wo):
-    """conv_bf16_s2_rows' rows per workgroup at n frames (csrc/conv_bf16_chain.hip launch_s2_rows, from the device's CU count)."""
+    """conv_bf16_s2_rows' rows per workgroup at n frames (csrc/conv_bf16_s2.hip launch_s2_rows, from the device's CU count)."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     segs = 1 if n >= 4 * cus else 4 if wo == 28 and 2 * n < 4 * cus else 2
     return -(-wo // segs), segs

@@ -1,4 +1,4 @@
-"""bf16 convolution kernels of csrc/conv_bf16_chain.hip and csrc/conv_bf16.hip (round 5): BasicBlock chains with the frame resident in LDS (hrnet.py:30-59,
+"""bf16 convolution kernels of csrc/conv_bf16_chain.hip, conv_bf16_wide.hip, conv_bf16_s2.hip and csrc/conv_bf16.hip (round 5): BasicBlock chains with the frame resident in LDS (hrnet.py:30-59,
 141-187), wide-band / ring kernels, stride-2 band kernel, layer1's 1x1 pairs and stream kernel, the bf16 fuse layer, bilinear x2 on NHWC bf16.
 Bar (bf16 has no reference mode; stated as in test_gpu_bf16.py): every intermediate is rounded to bf16 exactly where the launch-per-convolution path stores it, so a
 fused launch must equal (i) the fp32 oracle on bf16-rounded operands with the intermediates rounded to bf16 and (ii) the launch-per-convolution kernels, both up

@@ -15,6 +15,7 @@
 // Patch slots are 80 bytes (64 B of data + 16 B of padding) and weight rows are XOR-swizzled, so the 16-lane b128
 // operand reads fall on distinct banks.
 #include "kernels.h"
+#include "device.h"
 
 #include <cstring>
 
@@ -23,48 +24,14 @@
 
 namespace grk {
 
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
-
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kCK = 32;        // input channels per K chunk (= one MFMA k-step per tap)
-
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((unsigned)h << 16); }
-// two floats -> two bf16 (round to nearest even) in ONE instruction, v_cvt_pk_bf16_f32 (round 5; the integer form (u + 0x7fff + (u >> 16 & 1)) >> 16 is five vector instructions per value,
-// and the epilogues of the 1x1 and narrow layers are dozens of such values per handful of MFMAs)
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2)); }
-// q / d for 0 <= q < 2^20 through one fp32 reciprocal multiply (exact: the +0.5 keeps exact multiples off the rounding edge);
-// an integer division by a run-time value costs ~40 VALU instructions, and a tile of a 32-channel layer has only ~1000 cycles of MFMAs
-__device__ __forceinline__ int fdiv(int q, float inv_d) { return (int)(((float)q + 0.5f) * inv_d); }
-
-// LDS-DMA: lane l's 16 bytes land at lds_wave_base + 16*l; the source address is per lane.
-#define GRNET_GLOBAL_AS __attribute__((address_space(1)))
-#define GRNET_LDS_AS __attribute__((address_space(3)))
-// (round 6) Inline asm, NOT __builtin_amdgcn_global_load_lds: while an LDS-DMA hipcc knows of is in flight, every wait it puts in front of an LDS operand read is
-// lgkmcnt(0) and the reads are not hoisted -- conv_bf16_nhwc's tap loop was `ds_read, s_waitcnt lgkmcnt(0), v_mfma` 63 times over, one exposed LDS round trip per
-// MFMA.  The kernel waits for its pieces itself (s_waitcnt vmcnt(0) in front of every chunk's barrier), so the compiler does not have to know.  M0 = the wave's LDS
-// byte address (one wait state between its write and the DMA); every lane is on (padding units fetch zeros).
-__device__ __forceinline__ void dma16(const u16* src, u16* lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(__builtin_amdgcn_readfirstlane((unsigned)(size_t)lds_wave_base)) : "memory");
-}
 
 // Diagnostic build only (make ABLATION=1, GRNET_BF16_PHASES=1): where a workgroup of the bf16 kernel spends its life, in shader-clock
 // ticks summed over workgroups: [0] table build, [1] wait for the first chunk, [2] chunk loop (MFMAs + waits), [3] epilogue, [4] workgroups.
 #ifdef GRNET_ABLATION
 __device__ unsigned long long g_phase[8];
-#define GRK_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#define GRK_PHASE(i, t0, t1) do { if (threadIdx.x == 0) atomicAdd(&g_phase[i], (t1) - (t0)); } while (0)
-#else
-#define GRK_TICK(var) do { } while (0)
-#define GRK_PHASE(i, t0, t1) do { } while (0)
 #endif
 
 constexpr int kSlotU = 5;      // 16-byte DMA units per patch slot: 4 of data + 1 of padding (80-byte stride: conflict-free b128 reads)
@@ -109,7 +76,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
     const u16* zeros = reinterpret_cast<const u16*>(a.zeros);
 
     const float inv_RinWp = 1.0f / (float)RinWp, inv_Wp = 1.0f / (float)a.Wp, inv_RW = 1.0f / (float)RW, inv_Wo = 1.0f / (float)a.Wo;
-    GRK_TICK(t_start);
+    abl::Ticks<5> ticks(abl::bit(a.dbg, 8));              // phase accounting on request only: 5 atomics per workgroup on one line distort the timing
     auto slot_pixel = [&](int idx) {                       // input pixel of patch slot idx, -1 = zero padding / outside the batch
         const int gl = fdiv(idx, inv_RinWp), rem = idx - gl * RinWp;
         const int ry = fdiv(rem, inv_Wp), rx = rem - ry * a.Wp;
@@ -151,9 +118,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
                 const unsigned o = uoff[i];
                 const int c = c0 + (int)(o & 7u) * 8;
                 const u16* src = (o != 0xffffffffu && c < a.Cin) ? in + (size_t)(o & ~7u) + c : zeros;
-#ifdef GRNET_ABLATION
-                if (a.dbg & 2) src = zeros;
-#endif
+                if (abl::bit(a.dbg, 2)) src = zeros;
                 dma16(src, adst + ub * 8);
             }
             return;
@@ -161,9 +126,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
         for (int ub = wave * 64; ub < aunits; ub += NT) {
             const int u = ub + lane, slot = (int)(((unsigned)u * 52429u) >> 18), q = u - slot * kSlotU;      // u / 5 for u < 2^16
             const u16* src = zeros;
-#ifdef GRNET_ABLATION
-            if (a.dbg & 2) { dma16(src, adst + ub * 8); continue; }      // timing only: no HBM reads of the patch
-#endif
+            if (abl::bit(a.dbg, 2)) { dma16(src, adst + ub * 8); continue; }      // timing only: no HBM reads of the patch
             if (q < 4 && slot < a.PSTR) {
                 const int off = tab[slot], c = c0 + q * 8;
                 if (off >= 0 && c < a.Cin) {
@@ -182,7 +145,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
         for (int ps = 0; ps < PSW; ++ps) acc[cs][ps] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int nchunks = a.CinPad / kCK;
-    GRK_TICK(t_tab);
+    ticks.mark(0);
     stage(0, 0);
     // 1x1 layers (layer1's 64 -> 256 with its residual: 925 MB per launch at 256 frames, 3.6 TB/s): a workgroup's life is a chain of round trips --
     // patch DMA, a handful of MFMAs, addend loads, LDS transpose, stores.  The first addend does not depend on anything the workgroup computes: it
@@ -225,9 +188,6 @@ void conv_bf16_nhwc(const ConvArgs a) {
     for (int cs = 0; cs < CSW; ++cs) wlane[cs] = wg + ((size_t)co0 + (wc * CSW + cs) * 16 + l15) * 32 + lq * 8;
     const size_t wtap = (size_t)a.CoutPad * 32;            // elements between taps
 
-#ifdef GRNET_ABLATION
-    unsigned long long t_first = 0;
-#endif
     // Weight fragments live in registers a chunk ahead: chunk 0's are requested here, under the first patch's flight, and every tap
     // re-requests ITS registers for the next chunk right behind the MFMAs that consumed them -- the L2 round trip of a chunk's
     // weights (1-2 us, formerly exposed after every barrier: the chunk loop ran at 4-8x its MFMA time) hides under the rest of the
@@ -250,9 +210,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
         const int buf = nbuf == 2 ? (ch & 1) : 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of chunk ch has landed, and so have its weight fragments
         __syncthreads();                                     // ... and everybody else's; with two buffers the other one is free
-#ifdef GRNET_ABLATION
-        if (ch == 0) t_first = __builtin_readcyclecounter();
-#endif
+        if (ch == 0) ticks.mark(1);
         if (nbuf == 2 && ch + 1 < nchunks) stage(ch + 1, buf ^ 1);
         const size_t wnext = (size_t)(ch + 1 < nchunks ? ch + 1 : ch) * TAPS * wtap;
         const u16* al = a_lds + (size_t)buf * aunits * 8;
@@ -275,7 +233,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
         }
     }
 
-    GRK_TICK(t_loop);
+    ticks.mark(2);
     // ---- epilogue: lane holds channels co..co+3 of pixel l15 of each sub-tile.  Every load (bias, addends) is issued before the
     // first store: loads and stores share vmcnt on CDNA, so a load behind a store waits for that store's round trip to memory
     // (measured with the phase ticks above: 0.75 us per tile when the bias was loaded tile by tile).
@@ -348,9 +306,7 @@ void conv_bf16_nhwc(const ConvArgs a) {
         const int img = g0 + gl, pix = y0 * a.Wo + rem;
         if (img >= a.N || pix >= HoWo || co0 + part * 8 >= cstore) continue;
         const u32x4 v = *reinterpret_cast<const u32x4*>(o_lds + pl * TCP + part * 8);
-#ifdef GRNET_ABLATION
-        if ((a.dbg & 4) && v[0] != 0x12345678u) continue;               // timing only: no stores
-#endif
+        if (abl::bit(a.dbg, 4) && v[0] != 0x12345678u) continue;        // timing only: no stores
         *reinterpret_cast<u32x4*>(out + ((size_t)img * HoWo + pix) * a.out_ctot + a.out_coff + co0 + part * 8) = v;
     }
     // ---- second stage of a 1x1 PAIR (round 5; layer1, hrnet.py:80-100): the workgroup holds all 256 output channels of its 112 pixels in LDS, bf16, exactly
@@ -387,16 +343,9 @@ void conv_bf16_nhwc(const ConvArgs a) {
             }
         }
     }
-#ifdef GRNET_ABLATION
-    if (a.dbg & 8) {                                       // phase accounting on request only: 5 atomics per workgroup on one line distort the timing
-        GRK_TICK(t_end);
-        GRK_PHASE(0, t_start, t_tab);
-        GRK_PHASE(1, t_tab, t_first);
-        GRK_PHASE(2, t_first, t_loop);
-        GRK_PHASE(3, t_loop, t_end);
-        if (threadIdx.x == 0) atomicAdd(&g_phase[4], 1ull);
-    }
-#endif
+    ticks.mark(3);
+    ticks.count(4);
+    ticks.flush(GRK_ABL_COUNTERS(g_phase), threadIdx.x == 0);
 }
 
 // ---- Register-resident kernel for the narrow 3x3 stride-1 layers with as many output as input channels (C = 32 on 56x56 maps, C = 64
@@ -770,117 +719,17 @@ __global__ __launch_bounds__(256) void fuse_sum_bf16_kernel(const SumArgs a) {
     }
 }
 
-// (attn_pool_bf16x_kernel below is the form that runs since round 5: the same workgroup, but the GEMM on the bf16 matrix cores -- the probabilities as hi + lo bf16 pairs,
-// the features transposed out of their NHWC rows by ds_read_b64_tr_b16 -- and the range's features requested at once: 254 -> 171 us at 256 frames, results equal to 1e-6.
-// This fp32-MFMA form stays as the A/B reference, GRNET_BF16_POOL_X16=0.)
-// Attention pooling on NHWC bf16 maps (keypoint_attention.py:42-48): per frame the GEMM out[c][j] = sum_p feat[p][c] * prob[p][j] on the
-// fp32 matrix cores, the structure of the fp32 path's attn_pool_kernel (head_kernels.hip): workgroup = (frame, 96 channels, one of
-// kPoolSplit position ranges) = 6 waves; the range's exp(h - range max) is built once per workgroup in LDS (fp32) and the softmax over
-// all positions is finished by head_tail_kernel from the (max, sum) pairs of the ranges.  NHWC makes the position axis the slow one, so
-// a lane's A operand of a k-step is ONE bf16 (channel l15 of position p0 + 4 lq + s: 16 lanes = 32 contiguous bytes of a pixel), widened
-// to fp32 in the register; the products are exact and the sums fp32, as in the vector-ALU kernel this replaces (284 + 137 us for the
-// pooling and its statistics pass at 256 frames).
+// Attention pooling on NHWC bf16 maps (keypoint_attention.py:42-48): per frame the GEMM out[c][j] = sum_p feat[p][c] * prob[p][j], the structure
+// of the fp32 path's attn_pool_kernel (head_kernels.hip): workgroup = (frame, one of kPoolSplit position ranges); the range's exp(h - range max)
+// is built once per workgroup in LDS and the softmax over all positions is finished by head_tail_kernel from the (max, sum) pairs of the ranges.
+// The GEMM runs on the bf16 matrix cores -- the probabilities as hi + lo bf16 pairs, the features transposed out of their NHWC rows by
+// ds_read_b64_tr_b16 -- and the range's features are requested at once.  (The fp32-MFMA form this replaced, and two 6-wave workgroups of 96
+// channels instead of one of 12 waves: NOTES_rejected.md.)
 constexpr int kPoolChunkB = 448, kPoolStrideB = kPoolChunkB + 4;
-__device__ __forceinline__ float wave_max_b(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_b(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 constexpr int kPoolPB = 64;                                // positions per staging buffer (448 = 7 x 64)
-constexpr int kPoolFS = 96 + 8;                            // bf16 per staged position: 96 channels + 16 bytes (the four positions of a k-step land on different banks)
-__global__ __launch_bounds__(384) void attn_pool_bf16_kernel(const u16* __restrict__ heat, int hc, const u16* __restrict__ featA, int CA, int ctA,
-                                                               const u16* __restrict__ featB, int CB, int ctB, float* __restrict__ stats,
-                                                               float* __restrict__ part, int P) {
-    __shared__ __align__(16) float prob[24 * kPoolStrideB];
-    __shared__ __align__(16) u16 fst[2][kPoolPB * kPoolFS];    // two buffers of 64 positions x 96 channels, as they lie in memory (NHWC); 70 KB of LDS in all
-    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int pbeg = blockIdx.z * kPoolChunkB, cb = blockIdx.y * 96;      // first channel of this workgroup in [featA | featB]
-    // staging: 64 positions x 12 units of 16 bytes = two units per thread (positions spp and spp + 32); a unit lies entirely in featA or in featB
-    // (128 = 8 x 16).  Round 5: 64 instead of 32 positions per barrier -- the loop is a chain of load -> LDS -> barrier -> 16 MFMAs round trips
-    const int spp = tid / 12, sq = tid - spp * 12, sc = cb + sq * 8;
-    const u16* ssrc = sc < CA ? featA + ((size_t)n * P + pbeg + spp) * ctA + sc : featB + ((size_t)n * P + pbeg + spp) * ctB + (sc - CA);
-    const size_t sstride = sc < CA ? ctA : ctB;
-    auto stage = [&](int p0, int buf) {
-        const u32x4 v0 = *reinterpret_cast<const u32x4*>(ssrc + (size_t)p0 * sstride), v1 = *reinterpret_cast<const u32x4*>(ssrc + (size_t)(p0 + 32) * sstride);
-        *reinterpret_cast<u32x4*>(&fst[buf][spp * kPoolFS + sq * 8]) = v0;
-        *reinterpret_cast<u32x4*>(&fst[buf][(spp + 32) * kPoolFS + sq * 8]) = v1;
-    };
-    stage(0, 0);
-    // heat rows of the range -> LDS: thread = (position, 8 joints)
-    for (int u = tid; u < kPoolChunkB * 3; u += 384) {
-        const int p = u / 3, jg = u - p * 3;
-        const u32x4 h8 = *reinterpret_cast<const u32x4*>(heat + ((size_t)n * P + pbeg + p) * hc + jg * 8);      // channels 8 jg .. 8 jg + 7 (channel 0 = background)
-        const u16 nx = heat[((size_t)n * P + pbeg + p) * hc + jg * 8 + 8];                                          // channel 8 jg + 8 = joint 8 jg + 7
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int ch = k + 1;                                                                                   // joint 8 jg + k is channel 8 jg + k + 1
-            const u16 v = ch < 8 ? (u16)(h8[ch >> 1] >> (16 * (ch & 1))) : nx;
-            prob[(jg * 8 + k) * kPoolStrideB + p] = bf2f(v);
-        }
-    }
-    __syncthreads();
-    for (int j = (tid >> 6) * 4; j < (tid >> 6) * 4 + 4; ++j) {
-        float* row = prob + j * kPoolStrideB;
-        float hv[kPoolChunkB / 64], m = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < kPoolChunkB / 64; ++i) { hv[i] = row[lane + 64 * i]; m = fmaxf(m, hv[i]); }
-        m = wave_max_b(m);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < kPoolChunkB / 64; ++i) { const float e = expf(hv[i] - m); row[lane + 64 * i] = e; sum += e; }
-        sum = wave_sum_b(sum);
-        if (lane == 0 && blockIdx.y == 0) {
-            float* st = stats + (((size_t)n * kPoolSplit + blockIdx.z) * 24 + j) * 2;      // [n][range][joint][max, sum]
-            st[0] = m;
-            st[1] = sum;
-        }
-    }
-    const int wv = tid >> 6;                                            // row tile of this wave: channels cb + 16 wv .. + 15
-    const float* b0 = prob + l15 * kPoolStrideB + 4 * lq;
-    const float* b1 = prob + (16 + (l15 & 7)) * kPoolStrideB + 4 * lq;  // joints 16..23; lanes 8..15 of the second column tile are zero columns
-    const bool j1 = l15 < 8;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int p0 = 0; p0 < kPoolChunkB; p0 += kPoolPB) {
-        const int buf = (p0 / kPoolPB) & 1;
-        __syncthreads();                                                // buffer `buf` is staged (and the probabilities are final); the other one is free
-        if (p0 + kPoolPB < kPoolChunkB) stage(p0 + kPoolPB, buf ^ 1);
-        const u16* fs = &fst[buf][(4 * lq) * kPoolFS + wv * 16 + l15];
-#pragma unroll
-        for (int g = 0; g < kPoolPB / 16; ++g) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(b0 + p0 + 16 * g);
-            f32x4 v = *reinterpret_cast<const f32x4*>(b1 + p0 + 16 * g);
-            if (!j1) v = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float f = bf2f(fs[(16 * g + k) * kPoolFS]);       // channel l15 of position p0 + 16 g + 4 lq + k
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(f, u[k], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(f, v[k], acc1, 0, 0, 0);
-            }
-        }
-    }
-    const int ct = blockIdx.y * 6 + wv;
-    float* o = part + (((size_t)n * kPoolSplit + blockIdx.z) * (CA + CB) + ct * 16 + 4 * lq) * 24;      // [n][split][192][24]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        o[r * 24 + l15] = acc0[r];
-        if (l15 < 8) o[r * 24 + 16 + l15] = acc1[r];
-    }
-}
-
-// workgroup barrier for LDS data only: s_waitcnt lgkmcnt(0) + s_barrier.  (__syncthreads() also waits for vmcnt(0): with the range's features requested up front it held
-// every barrier of attn_pool_bf16x_kernel until all 86 KB had arrived)
-__device__ __forceinline__ void pool_lds_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// NW: waves = 16-channel tiles of the workgroup.  6: two workgroups per (frame, range), 96 channels each, both building the range's softmax; 12 (round 5): ONE workgroup
-// for all 192 channels -- the softmax (heat staging, exp, hi / lo split: most of the kernel's vector instructions) is built once, by twice the waves.
+// NW: waves = 16-channel tiles of the workgroup: 12, ONE workgroup for all 192 channels -- the softmax (heat staging, exp, hi / lo split: most of the
+// kernel's vector instructions) is built once.  Its barriers are lds_barrier(): with the range's features requested up front __syncthreads() held every
+// one of them until all 86 KB had arrived.
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void attn_pool_bf16x_kernel(const u16* __restrict__ heat, int hc, const u16* __restrict__ featA, int CA, int ctA,
                                                                const u16* __restrict__ featB, int CB, int ctB, float* __restrict__ stats,
@@ -936,17 +785,17 @@ __global__ __launch_bounds__(NW * 64) void attn_pool_bf16x_kernel(const u16* __r
             prob[(jg * 8 + k) * kPoolStrideB + p] = bf2f(v);
         }
     }
-    pool_lds_sync();
+    lds_barrier();
     for (int j = (tid >> 6) * (24 / NW); j < (tid >> 6) * (24 / NW) + 24 / NW; ++j) {
         float* row = prob + j * kPoolStrideB;
         float hv[kPoolChunkB / 64], m = -INFINITY;
 #pragma unroll
         for (int i = 0; i < kPoolChunkB / 64; ++i) { hv[i] = row[lane + 64 * i]; m = fmaxf(m, hv[i]); }
-        m = wave_max_b(m);
+        m = wave_max(m);
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < kPoolChunkB / 64; ++i) { hv[i] = __builtin_amdgcn_exp2f((hv[i] - m) * 1.442695040888963f); sum += hv[i]; }      // v_exp_f32 (1 ulp; arguments <= 0): libm's expf was a third of this workgroup's instructions
-        sum = wave_sum_b(sum);
+        sum = wave_sum(sum);
         // the row in place as TWO bf16 rows: e = hi + lo (hi = bf16(e), lo = bf16(e - hi): 16 bits of mantissa, 2^-17 relative) -- [hi 448][lo 448] in the 452 floats
         // of the fp32 row; every lane holds its 7 values, and the wave (one row at a time) has read the whole row before it writes
         {
@@ -971,7 +820,6 @@ __global__ __launch_bounds__(NW * 64) void attn_pool_bf16x_kernel(const u16* __r
     // (lane 4q + p supplies row q, channels 4p .. 4p + 3), two of them make the lane's 8 positions of the k-step; B (joints x positions) is 16 contiguous bytes
     // of the joint's hi / lo row.  4 MFMAs (16 cycles) per 32 positions instead of 16 fp32 ones (32 cycles).
     typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __bf16 bf16x8p __attribute__((ext_vector_type(8)));
     const unsigned char* pb0 = reinterpret_cast<const unsigned char*>(prob) + (size_t)l15 * kPoolStrideB * 4 + lq * 16;                // joints 0 .. 15
     const unsigned char* pb1 = reinterpret_cast<const unsigned char*>(prob) + (size_t)(16 + (l15 & 7)) * kPoolStrideB * 4 + lq * 16;    // joints 16 .. 23 (lanes 8 .. 15: copies, columns never stored)
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -979,17 +827,17 @@ __global__ __launch_bounds__(NW * 64) void attn_pool_bf16x_kernel(const u16* __r
 #pragma unroll
     for (int b = 0; b < NBLK; ++b) {
         const int buf = b & 1, p0 = b * kPoolPB;
-        pool_lds_sync();                                                // buffer `buf` is staged (and the probabilities are final); the other one is free
+        lds_barrier();                                                // buffer `buf` is staged (and the probabilities are final); the other one is free
         if (b + 1 < NBLK) deposit(b + 1, buf ^ 1);
         const u16* fs = &fst[buf][(8 * lq + (l15 >> 2)) * FS + wv * 16 + 4 * (l15 & 3)];
 #pragma unroll
         for (int g = 0; g < kPoolPB / 32; ++g) {
             const s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fs + (32 * g) * FS));
             const s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fs + (32 * g + 4) * FS));
-            const bf16x8p af = __builtin_bit_cast(bf16x8p, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
+            const bf16x8 af = __builtin_bit_cast(bf16x8, __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7));
             const int pe = (p0 + 32 * g) * 2;
-            const bf16x8p h0 = *reinterpret_cast<const bf16x8p*>(pb0 + pe), l0 = *reinterpret_cast<const bf16x8p*>(pb0 + kPoolChunkB * 2 + pe);
-            const bf16x8p h1 = *reinterpret_cast<const bf16x8p*>(pb1 + pe), l1 = *reinterpret_cast<const bf16x8p*>(pb1 + kPoolChunkB * 2 + pe);
+            const bf16x8 h0 = *reinterpret_cast<const bf16x8*>(pb0 + pe), l0 = *reinterpret_cast<const bf16x8*>(pb0 + kPoolChunkB * 2 + pe);
+            const bf16x8 h1 = *reinterpret_cast<const bf16x8*>(pb1 + pe), l1 = *reinterpret_cast<const bf16x8*>(pb1 + kPoolChunkB * 2 + pe);
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, h0, acc0, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, l0, acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, h1, acc1, 0, 0, 0);
@@ -1266,7 +1114,6 @@ hipError_t launch_pw_stream(const ConvArgs& a, hipStream_t s) {
 
 hipError_t conv_bf16_init() {
     GRK_TRY(set_lds_bf16(conv_bf16_nhwc<1, 1, 7, 16, 1, 4>));
-    GRK_TRY(set_lds_bf16(attn_pool_bf16x_kernel<6>));
     GRK_TRY(set_lds_bf16(attn_pool_bf16x_kernel<12>));
     GRK_TRY((init_bf16_ks<1, 1>()));
     GRK_TRY((init_bf16_ks<3, 1>()));
@@ -1310,10 +1157,8 @@ hipError_t launch_conv_bf16(ConvArgs a, hipStream_t s, int tile_hint) {
 #ifdef GRNET_ABLATION
     static const bool phases = GRNET_AB_SET(BF16_PHASES);
     if (phases && e == hipSuccess) {
-        unsigned long long h[8] = {}, z[8] = {};
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z));
+        unsigned long long h[8] = {};
+        abl::take_counters(HIP_SYMBOL(g_phase), h, s);
         const double n = h[4] ? (double)h[4] : 1.0;
         fprintf(stderr, "[bf16 phases] %d->%d k%d s%d %dx%d N%d tps %d tc %d nbuf %d wgs %llu: per WG ticks  table %.0f  first-wait %.0f  loop %.0f (%d chunks)  epilogue %.0f\n",
                 a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.N, tps, tc, a.nbuf, h[4], h[0] / n, h[1] / n, h[2] / n, a.CinPad / kCK, h[3] / n);
@@ -1368,16 +1213,7 @@ hipError_t launch_softmax_pool_bf16(const void* heat, int hc, const void* featA,
                                     int P, hipStream_t s) {
     if (CA != 128 || CB != 64 || P != kPoolChunkB * kPoolSplit || hc < 32 || hc % 8 != 0 || ctA % 8 != 0 || ctB % 8 != 0) return hipErrorInvalidValue;
     float* part = pool_ws + (size_t)N * kPoolStatsFloats;
-    const int x16 = GRNET_AB(BF16_POOL_X16, 1);     // 0: the fp32-MFMA form (A/B; read per launch)
-    if (x16)
-        {
-            static const int nw_env = GRNET_AB(BF16_POOL_WAVES, 12);      // 12 (default): one workgroup for all 192 channels; 6: two of 96
-            if (nw_env == 12) return launch_k(attn_pool_bf16x_kernel<12>, dim3(N, 1, kPoolSplit), dim3(768), (size_t)24 * kPoolStrideB * 4 + 2 * kPoolPB * (12 * 16 + 8) * 2, s, reinterpret_cast<const u16*>(heat), hc, reinterpret_cast<const u16*>(featA),
-                        CA, ctA, reinterpret_cast<const u16*>(featB), CB, ctB, pool_ws, part, P);
-            return launch_k(attn_pool_bf16x_kernel<6>, dim3(N, (CA + CB) / 96, kPoolSplit), dim3(384), (size_t)24 * kPoolStrideB * 4 + 2 * kPoolPB * (6 * 16 + 8) * 2, s, reinterpret_cast<const u16*>(heat), hc, reinterpret_cast<const u16*>(featA),
-                        CA, ctA, reinterpret_cast<const u16*>(featB), CB, ctB, pool_ws, part, P);
-        }
-    return launch_k(attn_pool_bf16_kernel, dim3(N, (CA + CB) / 96, kPoolSplit), dim3(384), 0, s, reinterpret_cast<const u16*>(heat), hc, reinterpret_cast<const u16*>(featA),
+    return launch_k(attn_pool_bf16x_kernel<12>, dim3(N, 1, kPoolSplit), dim3(768), (size_t)24 * kPoolStrideB * 4 + 2 * kPoolPB * (12 * 16 + 8) * 2, s, reinterpret_cast<const u16*>(heat), hc, reinterpret_cast<const u16*>(featA),
                     CA, ctA, reinterpret_cast<const u16*>(featB), CB, ctB, pool_ws, part, P);
 }
 

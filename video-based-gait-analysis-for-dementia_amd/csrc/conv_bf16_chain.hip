@@ -26,38 +26,16 @@
 // x + bias2 -- conv2 then ends with relu(acc).  Halo slots are never written, so they stay zero for the whole chain.
 //
 // Parity: every intermediate is rounded to bf16 exactly where the unfused path stores it, so the chain equals the launch-per-convolution
-// path up to fp32 summation order (output-rounding ties); tests/test_gpu_round5.py compares both and the fp32 oracle on bf16-rounded operands.
+// path up to fp32 summation order (output-rounding ties); tests/test_gpu_conv_bf16.py compares both and the fp32 oracle on bf16-rounded operands.
 #include "kernels.h"
+#include "device.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace grk {
 
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
-
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// two floats -> two bf16 (round to nearest even) in ONE instruction: v_cvt_pk_bf16_f32.  The integer form ((u + 0x7fff + (u >> 16 & 1)) >> 16, five
-// vector instructions per value) made the in-place epilogue -- 4 values x CS x PS tiles per wave and convolution -- cost a third of a k-loop.
-typedef __bf16 bf16x2_c __attribute__((ext_vector_type(2)));
-typedef float f32x2_c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack2_c(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_c{lo, hi}, bf16x2_c)); }
-// relu on the bits: negative floats (and -0) are negative integers; one v_max_i32, where fmaxf(x, 0) costs a canonicalising v_max first
-__device__ __forceinline__ float relu_c(float x) { const int i = __float_as_int(x); return __int_as_float(i > 0 ? i : 0); }
-typedef short s16x2_c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned relu_pk(unsigned v) {      // max(x, 0) on two packed bf16: v_pk_max_i16
-    const s16x2_c a = __builtin_bit_cast(s16x2_c, v);
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, s16x2_c{0, 0}));
-}
-__device__ __forceinline__ float bf_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
 
 // F frames per workgroup (round 6; F = 2 for the 256-channel 7x7 chain): the frames are stacked in ONE flattened plane, a zero row between them (plane rows 1 .. W:
 // frame 0, W + 1: zero, W + 2 .. 2 W + 1: frame 1), so a workgroup's weight stream -- 9.4 MB per chain from L2, the bound of that chain: two single-frame workgroups
@@ -86,7 +64,7 @@ struct ChainGeom {
     static_assert(F > 1 || (PS - 1) * 16 * SB + (2 * P + 2) * SB + (C / 32) * 64 < 65536, "ds_read immediates");      // (F = 2: 70 KB of plane, hipcc keeps a second base register)
 };
 
-// One convolution's k-loop over the LDS plane, shared by the frame-resident chain and the band-resident block kernel.
+// One convolution's k-loop over the LDS plane of the frame-resident chain.
 // Per k-step (tap x 32-channel chunk): CS weight fragments requested two steps ahead (ring of three register sets), and per column tile
 // one pixel fragment: tile ps of step s + 1 is requested right behind the MFMAs of tile ps of step s, into the register set they have
 // just read -- a read has PS - 1 MFMA pairs (and the SIMD's other wave) to land.  Left to itself hipcc sinks every read and every
@@ -226,7 +204,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 256 &&
                 u32x2 r = u32x2{0u, 0u};
                 if (first) r = *reinterpret_cast<const u32x2*>(pos);
                 const f32x4 v = acc[cs][ps];
-                const u32x2 pk = u32x2{pack2_c(relu_c(v[0]), relu_c(v[1])), pack2_c(relu_c(v[2]), relu_c(v[3]))};
+                const u32x2 pk = u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))};
                 if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(pos) = pk;
                 f32x4 nx = bnext[cs];
                 if (first) { nx[0] += bf_lo(r[0]); nx[1] += bf_hi(r[0]); nx[2] += bf_lo(r[1]); nx[3] += bf_hi(r[1]); }
@@ -249,12 +227,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 256 &&
 
 
 // ---- ONE BasicBlock of the 32-channel 56x56 branch with a BAND of the frame resident in LDS (a whole 56x56x32 frame is 200 KB: it does not fit).
-// The launch-per-convolution kernel (conv_bf16_direct) runs these layers at 37.9 us = 0.16 of the matrix peak at 256 frames: they move 2-3
-// tensors of 51 MB each per launch.  Here a workgroup owns R = 19 output rows of one frame (3 bands per frame = 768 workgroups = 3 per CU):
-// input rows y0 - 2 .. y0 + R + 1 (rows outside the image are zero) -> LDS in the flattened, pitch-57 image of the chain kernel; conv1 on
-// rows y0 - 1 .. y0 + R (its rows outside the image are conv2's zero padding: not written, the slots keep their zeros), in place; conv2 on
-// the same R + 2 rows (the two outer ones are dropped: 10 % of the MFMAs buy one tile map and the residual-in-place trick for both
-// convolutions); rows y0 .. y0 + R - 1 -> HBM.  HBM sees 23/19 of the input once and the output once instead of five passes.
+// The plane of a band of R output rows: input rows y0 - 2 .. y0 + R + 1 (rows outside the image are zero) in the flattened, pitch-57 image of the chain
+// kernel; conv1 on rows y0 - 1 .. y0 + R (its rows outside the image are conv2's zero padding: not written, the slots keep their zeros), in place; conv2
+// reads them; rows y0 .. y0 + R - 1 -> HBM.  (A kernel with the workgroup = one band, one or two per CU, measured 51-53 us per block against 43 for the
+// frame-persistent kernel below: NOTES_rejected.md.)
 template <int C, int W, int R>
 struct BandGeom {
     static constexpr int P = W + 1, SB = 2 * C + 32;
@@ -272,107 +248,8 @@ struct BandGeom {
     static_assert((PS - 1) * 16 * SB + (2 * P + 2) * SB + (C / 32) * 64 < 65536, "ds_read immediates");
 };
 
-template <int C, int W, int R, int WPE>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void conv_bf16_block_band(const ChainArgs a) {
-    typedef BandGeom<C, W, R> G;
-    constexpr int P = G::P, SB = G::SB, CS = G::CS, PS = G::PS, UPP = G::UPP;
-    extern __shared__ __align__(16) unsigned char plane[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cb = wave % G::WCB, pg = wave / G::WCB;
-    const int n = blockIdx.x / G::NB, band = blockIdx.x - n * G::NB;
-    if (n >= a.N) return;
-    const int y0 = band * R;
-
-    const u16* inb = reinterpret_cast<const u16*>(a.in) + (size_t)n * W * W * a.in_ctot + a.in_coff;
-    u32x4 stage[G::NUI];
-#pragma unroll
-    for (int i = 0; i < G::NUI; ++i) {
-        const int u = tid + i * 512, px = u / UPP, part = u - px * UPP, r = px / W, x = px - r * W, y = y0 - 2 + r;
-        stage[i] = u32x4{0u, 0u, 0u, 0u};
-        if (u < G::ROWS * W * UPP && y >= 0 && y < W) stage[i] = *reinterpret_cast<const u32x4*>(inb + ((size_t)y * W + x) * a.in_ctot + part * 8);
-    }
-    for (int u = tid; u < G::LDS / 16; u += 512) reinterpret_cast<u32x4*>(plane)[u] = u32x4{0u, 0u, 0u, 0u};
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < G::NUI; ++i) {
-        const int u = tid + i * 512, px = u / UPP, part = u - px * UPP, r = px / W, x = px - r * W;
-        if (u < G::ROWS * W * UPP) *reinterpret_cast<u32x4*>(plane + (r * P + x + 1) * SB + part * 16) = stage[i];
-    }
-
-    const int o_first = G::O0 + pg * PS * 16 + l15;
-    const unsigned char* bread = plane + (o_first - P - 1) * SB + lq * 16;
-    unsigned char* owrite = plane + o_first * SB + (cb * CS * 16 + lq * 4) * 2;
-    unsigned valid1 = 0, valid2 = 0;                          // bit ps: conv1 / conv2 write column tile ps of this lane
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) {
-        const int o = o_first + ps * 16, r = o / P, y = y0 - 2 + r;
-        const bool px_ok = o - r * P != 0 && r >= 1 && r <= R + 2 && y >= 0 && y < W;
-        if (px_ok) valid1 |= 1u << ps;
-        if (px_ok && r >= 2 && r <= R + 1) valid2 |= 1u << ps;
-    }
-    const unsigned wlb = ((cb * CS * 16 + l15) * 32 + lq * 8) * 2;
-    const int co = cb * CS * 16 + lq * 4;
-
-    f32x4 acc[CS][PS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias[0] + co + cs * 16);
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) acc[cs][ps] = bv;
-    }
-    bf16x8 wr[3][CS];
-    const u16* w0 = reinterpret_cast<const u16*>(a.w[0]);
-    const u16* w1 = reinterpret_cast<const u16*>(a.w[1]);
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        wr[0][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(w0 + (0 * C + cs * 16) * 32) + wlb);
-        wr[1][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(w0 + (1 * C + cs * 16) * 32) + wlb);
-    }
-    __syncthreads();
-
-    // conv1: t = relu(conv(x) + b1) replaces x (where t exists); conv2's accumulators start from x + b2
-    chain_kloop<C, P, SB, CS, PS>(acc, wr, bread, w0, w1, wlb);
-    f32x4 b2[CS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) b2[cs] = *reinterpret_cast<const f32x4*>(a.bias[1] + co + cs * 16);
-    __syncthreads();
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            unsigned char* pos = owrite + ps * 16 * SB + cs * 32;
-            const u32x2 r = *reinterpret_cast<const u32x2*>(pos);
-            const f32x4 v = acc[cs][ps];
-            if (valid1 & (1u << ps)) *reinterpret_cast<u32x2*>(pos) = u32x2{pack2_c(relu_c(v[0]), relu_c(v[1])), pack2_c(relu_c(v[2]), relu_c(v[3]))};
-            f32x4 nx = b2[cs];
-            nx[0] += bf_lo(r[0]); nx[1] += bf_hi(r[0]); nx[2] += bf_lo(r[1]); nx[3] += bf_hi(r[1]);
-            acc[cs][ps] = nx;
-        }
-    __syncthreads();
-    // conv2: y = relu(conv(t) + b2 + x), rows y0 .. y0 + R - 1
-    chain_kloop<C, P, SB, CS, PS>(acc, wr, bread, w1, w1, wlb);
-    __syncthreads();
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            const f32x4 v = acc[cs][ps];
-            if (valid2 & (1u << ps))
-                *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 32) = u32x2{pack2_c(relu_c(v[0]), relu_c(v[1])), pack2_c(relu_c(v[2]), relu_c(v[3]))};
-        }
-    __syncthreads();
-    u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff;
-#pragma unroll
-    for (int i = 0; i < G::NUO; ++i) {
-        const int u = tid + i * 512, px = u / UPP, part = u - px * UPP, r = px / W, x = px - r * W, y = y0 + r;
-        if (u < R * W * UPP && y < W)
-            *reinterpret_cast<u32x4*>(outb + ((size_t)y * W + x) * a.out_ctot + part * 8) = *reinterpret_cast<const u32x4*>(plane + ((r + 2) * P + x + 1) * SB + part * 16);
-    }
-}
-
 // ---- The same block with the WORKGROUP = ONE FRAME walking its NB = 56 / R bands, the next band arriving by LDS-DMA under the current band's MFMAs.
-// The band kernel above spends two thirds of a workgroup's life in its load and store phases (one workgroup per CU: nothing overlaps them; 51 us
+// A workgroup per band spends two thirds of its life in its load and store phases (one workgroup per CU: nothing overlaps them; 51 us
 // per BasicBlock at 256 frames against 11.8 us of MFMAs at peak and 22 us of HBM time).  A first persistent version kept the next band in
 // registers (R = 14): 256 VGPRs + 160-284 bytes of scratch, and hipcc parked the prefetched rows in scratch right behind their loads, i.e.
 // waited for them -- no overlap.  So the prefetch takes no registers at all:
@@ -385,26 +262,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 //   * barriers are raw s_barrier + lgkmcnt(0): __syncthreads() would drain the DMAs (a pending DMA is a pending LDS write to its fence).
 // LDS: weights 36 KB + plane (R = 8: 12 rows, 72.7 KB) + staging (12 x 56 x 64 B = 43 KB) = 152 KB.  R = 8 tiles the 56 rows exactly (7 bands);
 // 10 of 12 plane rows carry outputs of conv1, 8 of conv2's, 569 of 640 MFMA columns are real: 0.72 of the MFMAs are useful, HBM reads 1.5 x the input.
-#define GRNET_GLOBAL_AS __attribute__((address_space(1)))
-#define GRNET_LDS_AS __attribute__((address_space(3)))
-__device__ __forceinline__ void dma16_c(const u16* src, unsigned char* lds_wave_base) {      // lane l's 16 bytes land at lds_wave_base + 16 l
-    __builtin_amdgcn_global_load_lds((const GRNET_GLOBAL_AS void*)src, (GRNET_LDS_AS void*)lds_wave_base, 16, 0, 0);
-}
-// LDS-DMA pieces the compiler does not know of: lane l's 16 bytes land at lds + 16 l (M0 = LDS byte address of the piece).
-// uniform base + 32-bit lane offset, only the lanes of `mask` (all lanes are on around it: the callers are in uniform control flow)
-__device__ __forceinline__ void dma16_masked(unsigned off, const void* base, unsigned lds, unsigned long long mask) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_mov_b64 exec, %3\n\tglobal_load_lds_dwordx4 %0, %1\n\ts_mov_b64 exec, -1" ::"v"(off), "s"(base), "s"(lds), "s"(mask) : "memory");
-}
-// all lanes (the weights).  One wait state between the M0 write and the DMA that reads it.
-__device__ __forceinline__ void dma16_hidden_s(unsigned off, const void* base, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
 
-__device__ __forceinline__ void lds_barrier() {               // every wave's LDS operations so far are done; vector-memory operations (DMAs, stores) stay in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // k-loop of one 32 -> 32 convolution with the weights in LDS: per tap CS weight fragments (one tap ahead, two register sets) and PS pixel fragments
 // (ring as in chain_kloop); no vector-memory operation.  wl: this lane's fragment of tap 0, block 0 (swizzled part); 2 KB per tap, 1 KB per block.
@@ -479,7 +337,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
             const int ub = i * 512 + wave * 64, u = ub + lane;
             const unsigned pk = upk[i >> 1] >> (16 * (i & 1));
             const int r = (pk >> 8) & 15, x = (pk >> 2) & 63, part = pk & 3, y = y0 - 2 + r;
-            if (u < F::STAGE_UNITS && y >= 0 && y < W) dma16_c(inb + ((size_t)y * W + x) * a.in_ctot + part * 8, stg + ub * 16);
+            if (u < F::STAGE_UNITS && y >= 0 && y < W) dma16_builtin(inb + ((size_t)y * W + x) * a.in_ctot + part * 8, stg + ub * 16);
         }
     };
     auto deposit = [&](int y0) {                               // staging -> interior slots of every plane row; zeros where the band hangs over the image
@@ -558,9 +416,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
         for (int cs = 0; cs < CS; ++cs)
 #pragma unroll
             for (int ps = 0; ps < PS; ++ps) acc[cs][ps] = b1[cs];
-#ifdef GRNET_ABLATION
-        if (!(a.flags & 16))
-#endif
+        if (!abl::bit(a.flags, 16))
         chain_kloop_ldsw<P, SB, CS, PS>(acc, bread, wl0);
         if (direct_store) {
             // conv2's accumulators start from x + bias2, read at conv2's OWN columns while the plane still holds x (nobody has written yet)
@@ -582,12 +438,10 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
 #pragma unroll
             for (int ps = 0; ps < PS; ++ps) {
                 const f32x4 A = acc[0][ps], B = acc[1][ps];
-                if (valid1 & (1u << ps)) *reinterpret_cast<u32x4*>(owrite + ps * 16 * SB) = u32x4{pack2_c(relu_c(A[0]), relu_c(A[1])), pack2_c(relu_c(A[2]), relu_c(A[3])), pack2_c(relu_c(B[0]), relu_c(B[1])), pack2_c(relu_c(B[2]), relu_c(B[3]))};
+                if (valid1 & (1u << ps)) *reinterpret_cast<u32x4*>(owrite + ps * 16 * SB) = u32x4{pack2(relu_bits(A[0]), relu_bits(A[1])), pack2(relu_bits(A[2]), relu_bits(A[3])), pack2(relu_bits(B[0]), relu_bits(B[1])), pack2(relu_bits(B[2]), relu_bits(B[3]))};
             }
             lds_barrier();
-#ifdef GRNET_ABLATION
-            if (!(a.flags & 32))
-#endif
+            if (!abl::bit(a.flags, 32))
             chain_kloop_ldsw<P, SB, CS, PS2>(acc2, bread2, wl1);
             // the block's output rows leave straight from the accumulators (round 5: was in place through the plane, a barrier, then 16-byte stores): 8 bytes per lane, the
             // four k-groups of a pixel make 32 contiguous bytes, the two channel blocks its 64-byte row; nothing of this band's output is needed in LDS again.
@@ -602,7 +456,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
                 const int o = of + ps * 16, r = o / P, x = o - r * P - 1;
                 u16* op = outb + ((size_t)(y0 + r - 2) * W + x) * a.out_ctot + lq * 8;
                 const f32x4 A = acc2[0][ps], B = acc2[1][ps];
-                if (v2 & (1u << ps)) *reinterpret_cast<u32x4*>(op) = u32x4{pack2_c(relu_c(A[0]), relu_c(A[1])), pack2_c(relu_c(A[2]), relu_c(A[3])), pack2_c(relu_c(B[0]), relu_c(B[1])), pack2_c(relu_c(B[2]), relu_c(B[3]))};       // 16 bytes per lane: a pixel's 64-byte row by four lanes
+                if (v2 & (1u << ps)) *reinterpret_cast<u32x4*>(op) = u32x4{pack2(relu_bits(A[0]), relu_bits(A[1])), pack2(relu_bits(A[2]), relu_bits(A[3])), pack2(relu_bits(B[0]), relu_bits(B[1])), pack2(relu_bits(B[2]), relu_bits(B[3]))};       // 16 bytes per lane: a pixel's 64-byte row by four lanes
             }
         } else {
         lds_barrier();
@@ -613,7 +467,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
                 unsigned char* pos = owrite + ps * 16 * SB + cs * 8;
                 const u32x2 r = *reinterpret_cast<const u32x2*>(pos);
                 const f32x4 v = acc[cs][ps];
-                if (valid1 & (1u << ps)) *reinterpret_cast<u32x2*>(pos) = u32x2{pack2_c(relu_c(v[0]), relu_c(v[1])), pack2_c(relu_c(v[2]), relu_c(v[3]))};
+                if (valid1 & (1u << ps)) *reinterpret_cast<u32x2*>(pos) = u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))};
                 f32x4 nx = b2[cs];
                 nx[0] += bf_lo(r[0]); nx[1] += bf_hi(r[0]); nx[2] += bf_lo(r[1]); nx[3] += bf_hi(r[1]);
                 acc[cs][ps] = nx;
@@ -627,7 +481,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
             for (int cs = 0; cs < CS; ++cs) {
                 const f32x4 v = acc[cs][ps];
                 if (valid2 & (1u << ps))
-                    *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 8) = u32x2{pack2_c(relu_c(v[0]), relu_c(v[1])), pack2_c(relu_c(v[2]), relu_c(v[3]))};
+                    *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 8) = u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))};
             }
         // the next band's DMAs (issued a whole band ago) and the previous band's stores are the only vector-memory operations in flight: wait for
         // them HERE, in front of this band's stores, so that the wait does not include those stores' round trip
@@ -642,9 +496,7 @@ __global__ __launch_bounds__(512) void conv_bf16_block_frame(const ChainArgs a) 
         }
         if (band + 1 < NB) {
             lds_barrier();                                     // the band's rows have been read out of the plane
-#ifdef GRNET_ABLATION
-            if (!(a.flags & 64))
-#endif
+            if (!abl::bit(a.flags, 64))
             deposit(y0 + R);
             lds_barrier();                                     // staging is free, the plane holds the next band
             if (band + 2 < NB) request(y0 + 2 * R);
@@ -674,10 +526,7 @@ struct PipeGeom {
 };
 
 #ifdef GRNET_ABLATION
-__device__ unsigned long long g_pipe_phase[8][4];             // diagnostic builds, GRNET_PIPE_PHASES: clock ticks per wave: request / compute + store / DMA wait / barrier
-#define PIPE_TICK(k) do { if (a.flags & 128) { const unsigned long long t_ = __builtin_readcyclecounter(); tacc_[k] += t_ - tick_; tick_ = t_; } } while (0)
-#else
-#define PIPE_TICK(k) do { } while (0)
+__device__ unsigned long long g_pipe_phase[8 * 4];            // diagnostic builds, GRNET_PIPE_PHASES: clock ticks per wave: request / compute + store / DMA wait / barrier
 #endif
 __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
     typedef PipeGeom G;
@@ -736,13 +585,10 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
     auto wrap = [](int i, int nrows) { return i >= nrows ? i - nrows : i; };
     auto compute_row = [&](int r) {
         (void)r;
-#ifdef GRNET_ABLATION
-        if (a.flags & 64) {
+        if (abl::bit(a.flags, 64)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc[0][j] = bias[0]; acc[1][j] = bias[1]; }
-        } else
-#endif
-        if (second) {
+        } else if (second) {
             const unsigned char* xr = lds + (f_res + i_res) * G::ROWB + off[1];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -758,9 +604,7 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc[0][j] = bias[0]; acc[1][j] = bias[1]; }
         }
-#ifdef GRNET_ABLATION
-        if (a.flags & 16) return;
-#endif
+        if (abl::bit(a.flags, 16)) return;
         const unsigned char* rb[3];
         rb[0] = lds + (f_in + i_in) * G::ROWB;
         rb[1] = lds + (f_in + wrap(i_in + 1, n_in)) * G::ROWB;
@@ -785,9 +629,7 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
     };
     // acc (row r) -> ReLU, bf16 -> ring s + 1 (the last convolution: HBM); zero: the padding rows -1 and 56 of the next convolution's input
     auto store_row = [&](int r, int i_row, bool zero) {            // i_row: ring row of image row r in the output ring
-#ifdef GRNET_ABLATION
-        if (a.flags & 32) return;
-#endif
+        if (abl::bit(a.flags, 32)) return;
         unsigned char* orow = lds + (f_out + i_row) * G::ROWB + off[1];
         if (zero) {
             if (!last) {
@@ -801,7 +643,7 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
             // round to bf16, THEN clamp at zero on the packed halves (v_pk_max_i16: a negative bf16 is a negative 16-bit integer, -0 included) -- the bits of
             // relu-then-round (rounding keeps the sign) in 8 vector instructions per tile instead of 12
             const f32x4 A = acc[0][j], B = acc[1][j];
-            u32x4 v = u32x4{relu_pk(pack2_c(A[0], A[1])), relu_pk(pack2_c(A[2], A[3])), relu_pk(pack2_c(B[0], B[1])), relu_pk(pack2_c(B[2], B[3]))};
+            u32x4 v = u32x4{relu_pk(pack2(A[0], A[1])), relu_pk(pack2(A[2], A[3])), relu_pk(pack2(B[0], B[1])), relu_pk(pack2(B[2], B[3]))};
             const int x = 16 * j + l15;
             if (last) {
                 if (j < 3 || x < W) *reinterpret_cast<u32x4*>(outb + ((size_t)r * W + x) * a.out_ctot + lq * 8) = v;
@@ -825,9 +667,7 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
         i_in = (r0 - 1 + 120) % n_in; i_res = (r0 + 120) % n_res; i_out = (r0 + 120) % n_out; i_dma = (-4 + 3 + 120) % 6;
     }
 
-#ifdef GRNET_ABLATION
-    unsigned long long tacc_[4] = {0, 0, 0, 0}, tick_ = __builtin_readcyclecounter();
-#endif
+    abl::Ticks<4> ticks(abl::bit(a.flags, 128));
 #pragma unroll 1
     for (int t = -4; t < t_end; ++t) {
         if (t + 3 == W && wv == 0) {                           // ring 0's row for image row 56 (the bottom padding) held row 50: zero it (slots 0 .. 63)
@@ -838,7 +678,7 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
         const bool asks = wv < 4 && t + 3 >= 0 && t + 3 < W;
         if (asks) request(t + 3, i_dma);
         const int r = t - c_s;
-        PIPE_TICK(0);
+        ticks.mark(0);
         if (second) {
             if (pending) store_row(r - 1, i_out == 0 ? n_out - 1 : i_out - 1, pending == 2);
             pending = 0;
@@ -850,740 +690,17 @@ __global__ __launch_bounds__(512) void conv_bf16_chain_pipe(const ChainArgs a) {
             store_row(r, i_out, pad);
         }
         i_in = wrap(i_in + 1, n_in); i_res = wrap(i_res + 1, n_res); i_out = wrap(i_out + 1, n_out); i_dma = wrap(i_dma + 1, 6);
-        PIPE_TICK(1);
+        ticks.mark(1);
         // the row this wave requested one step ago has landed (this step's may still fly; a step without a request leaves nothing in flight)
         if (asks) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else if (wv < 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PIPE_TICK(2);
-#ifdef GRNET_ABLATION
-        if (!(a.flags & 256))
-#endif
+        ticks.mark(2);
+        if (!abl::bit(a.flags, 256))
         lds_barrier();
-        PIPE_TICK(3);
+        ticks.mark(3);
     }
-#ifdef GRNET_ABLATION
-    if ((a.flags & 128) && lane == 0)
-        for (int k = 0; k < 4; ++k) atomicAdd(&g_pipe_phase[wv][k], tacc_[k]);
-#endif
+    ticks.flush(GRK_ABL_COUNTERS(g_pipe_phase) + wv * 4, lane == 0);
 }
-
-// ---- ONE wide 3x3 stride-1 convolution (upsample heads hrnet.py:440-453, PARE head pare.py:377-400, layer1's 3x3 hrnet.py:80-100) with a band of
-// the input resident in LDS.  conv_bf16_nhwc runs these layers at 0.25-0.45 of the matrix peak: 224-pixel x 64-channel tiles, 32 input
-// channels per barrier (126 MFMAs per wave between two barriers, each with a vmcnt(0) in front).  Here a workgroup owns R output rows of one
-// frame x CT = CP output channels (CP = 128, or 64 for the 64-channel layers): the R + 2 input rows go HBM -> LDS by LDS-DMA straight into the
-// padded, flattened plane of the chain kernel (the pad units and every zero -- halo column, rows outside the image -- come from a block of
-// zeros: the DMA writes lane-linear, so it cannot skip them), CP input channels per pass; between two barriers a wave issues 9 x CP/32 x 26
-// MFMAs (936 for CP = 128).  Layers with more than CP input channels take several passes (480 = 128 + 128 + 128 + 96) into the same
-// accumulators; their weights are one contiguous stream ([chunk][tap][CoutPad][32]), so the ring of weight fragments runs across passes.
-// The tile leaves through the plane (in place, as in the chain kernel) as whole channel rows.
-template <int CP, int CT, int W, int R>
-struct WideGeom {
-    static constexpr int P = W + 1, SB = 2 * CP + 32, UPS = SB / 16;
-    static constexpr int ROWS = R + 2;                      // plane rows: image rows y0 - 1 .. y0 + R
-    static constexpr int O0 = P + 1, NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;    // CT output channels per workgroup (CT <= CP: the tile leaves through the first 2 CT bytes of the plane's slots)
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int NSLOT = O0 + NT * 16 + P + 2;
-    static constexpr int LDS = NSLOT * SB;
-    static constexpr int FILL_UNITS = ((ROWS * P + 1) * UPS + 63) / 64 * 64;      // slots 0 .. ROWS * P (the last one: the right halo of the last row), whole wave-instructions
-    static constexpr int NFILL = (FILL_UNITS / 64 + 7) / 8;                        // wave-instructions per wave
-    static constexpr int UPP = CT / 8, NUO = (R * W * UPP + 511) / 512;
-    static constexpr int NB = (W + R - 1) / R;
-    static_assert(((SB / 32) % 2) == 1 && LDS <= 160 * 1024 && PS <= 32 && FILL_UNITS * 16 <= LDS && CT <= CP && CT % 32 == 0 && 8 % (CT / 32) == 0, "wide-band geometry");
-    // (with CP = 128 the farthest pixel fragment lies 89 KB behind the lane's base: past the 16-bit ds_read immediate, hipcc keeps a second base register)
-};
-
-// chain_kloop with a run-time chunk count and weight stride (the output-channel padding of the layer): wc = the pass's first k-step, wtap = elements
-// per k-step (CoutPad x 32); the ring's two leading steps of the NEXT pass are simply the next two k-steps of the stream -- except behind the very
-// last chunk of the layer (last), where the stream ends: the pass's own first steps are re-requested (nobody waits for them).
-template <int P, int SB, int CS, int PS>
-__device__ __forceinline__ void wide_kloop(f32x4 (&acc)[CS][PS], bf16x8 (&wr)[3][CS], const unsigned char* bread, const u16* wc, size_t wtap, int nch, bool last, unsigned wlb) {
-    bf16x8 bfr[PS];
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB);
-#pragma unroll 1
-    for (int chunk = 0; chunk < nch; ++chunk) {
-        const unsigned char* bch = bread + chunk * 64;
-        const u16* wch = wc + (size_t)chunk * 9 * wtap;
-        const bool lastc = last && chunk == nch - 1;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            {
-                const u16* src = wch + (size_t)(tap + 2) * wtap;
-                if (tap >= 7) src = lastc ? wc + (size_t)(tap - 7) * wtap : src;
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) wr[(tap + 2) % 3][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(src + cs * 16 * 32) + wlb);
-            }
-            const int noff = tap < 8 ? (((tap + 1) / 3) * P + ((tap + 1) % 3)) * SB : 64;
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[tap % 3][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(bch + ps * 16 * SB + noff);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
-
-template <int CP, int CT, int W, int R>
-__global__ __launch_bounds__(512) void conv_bf16_wide_band(const ConvArgs a) {
-    typedef WideGeom<CP, CT, W, R> G;
-    constexpr int P = G::P, SB = G::SB, CS = G::CS, PS = G::PS, UPS = G::UPS, UPP = G::UPP;
-    extern __shared__ __align__(16) unsigned char plane[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wcb = wave % G::WCB, pg = wave / G::WCB;
-    const int ncb = a.CoutPad / CT;                            // output-channel tiles of the layer
-    // workgroups go to the 8 XCDs round-robin by blockIdx: with a.xcd the ids are re-dealt so that CONSECUTIVE tiles -- the ncb output-channel tiles of a band,
-    // then the frame's next band (which shares two halo rows) -- run on ONE XCD at about the same time and meet in its L2
-    int bid = blockIdx.x;
-    if (a.xcd && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int cbo = bid % ncb, nb = bid / ncb, n = nb / G::NB, band = nb - n * G::NB;
-    if (n >= a.N) return;
-    const int y0 = band * R;
-    const u16* inb = reinterpret_cast<const u16*>(a.in) + (size_t)n * W * W * a.in_ctot + a.in_coff;
-    const u16* zeros = reinterpret_cast<const u16*>(a.zeros);
-
-    // DMA unit u = (slot, 16-byte part) of the plane in memory order.  The unit -> pixel map does not depend on the pass, and hipcc would hoist it
-    // out of the pass loop into 2 x NFILL registers held beside the accumulators (164-212 bytes of scratch): the lane index is laundered through an
-    // empty asm per pass, so the map is recomputed (~20 scalar-free instructions per unit, 19 units per pass) instead of kept.
-    auto fill = [&](int c0, int cw) {                          // input channels c0 .. c0 + cw - 1 of the band -> plane, by LDS-DMA
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-#pragma unroll
-        for (int i = 0; i < G::NFILL; ++i) {
-            const int ub = (i * 8 + wave) * 64;
-            if (ub >= G::FILL_UNITS) break;                    // wave-uniform
-            const int u = ub + ln, slot = u / UPS, part = u - slot * UPS, r = slot / P, xx = slot - r * P, y = y0 - 1 + r;
-            const bool data = r < G::ROWS && xx != 0 && y >= 0 && y < W && part * 8 < cw;
-            dma16_c(data ? inb + (size_t)(y * W + xx - 1) * a.in_ctot + c0 + part * 8 : zeros, plane + ub * 16);
-        }
-    };
-
-    const int o_first = G::O0 + pg * PS * 16 + l15;
-    const unsigned char* bread = plane + (o_first - P - 1) * SB + lq * 16;
-    unsigned char* owrite = plane + o_first * SB + (wcb * CS * 16 + lq * 4) * 2;
-    unsigned valid = 0;
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) {
-        const int o = o_first + ps * 16, r = o / P;
-        if (o - r * P != 0 && r >= 1 && r <= R && y0 + r - 1 < W) valid |= 1u << ps;
-    }
-    const int co = cbo * CT + wcb * CS * 16;                   // first output channel of this wave
-    const unsigned wlb = ((co + l15) * 32 + lq * 8) * 2;
-    const size_t wtap = (size_t)a.CoutPad * 32;
-    const u16* wg = reinterpret_cast<const u16*>(a.w);
-    f32x4 acc[CS][PS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + co + cs * 16 + lq * 4);
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) acc[cs][ps] = bv;
-    }
-    bf16x8 wr[3][CS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        wr[0][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(wg + cs * 16 * 32) + wlb);
-        wr[1][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(wg + wtap + cs * 16 * 32) + wlb);
-    }
-    const int npass = (a.CinPad + CP - 1) / CP;
-#pragma unroll 1
-    for (int pass = 0; pass < npass; ++pass) {
-        const int c0 = pass * CP, cw = a.CinPad - c0 < CP ? a.CinPad - c0 : CP;
-        if (pass) __syncthreads();                             // every wave has finished reading the previous pass's plane
-#ifdef GRNET_ABLATION                                                  // timing-only builds (make ABLATION=1; GRNET_WIDE_DBG bit 0: no fill, bit 1: no k-loop)
-        if (!(a.dbg & 1) || pass == 0)
-#endif
-        fill(c0, cw);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#ifdef GRNET_ABLATION
-        if (!(a.dbg & 2))
-#endif
-        wide_kloop<P, SB, CS, PS>(acc, wr, bread, wg + (size_t)(c0 / 32) * 9 * wtap, wtap, cw / 32, pass == npass - 1, wlb);
-    }
-    // ---- the tile: bias is in the accumulators; ReLU, bf16, in place through the plane, rows y0 .. y0 + R - 1 -> HBM as whole channel rows
-    __syncthreads();
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_c(v[0]); v[1] = relu_c(v[1]); v[2] = relu_c(v[2]); v[3] = relu_c(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 32) = u32x2{pack2_c(v[0], v[1]), pack2_c(v[2], v[3])};
-        }
-    __syncthreads();
-    u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff + cbo * CT;
-    const int cstore = a.Cout - cbo * CT;                      // real channels of this tile (CoutPad may exceed Cout)
-#pragma unroll
-    for (int i = 0; i < G::NUO; ++i) {
-        const int u = i * 512 + tid, px = u / UPP, part = u - px * UPP, r = px / W, x = px - r * W;
-        if (u < R * W * UPP && y0 + r < W && part * 8 < cstore)
-            *reinterpret_cast<u32x4*>(outb + ((size_t)(y0 + r) * W + x) * a.out_ctot + part * 8) = *reinterpret_cast<const u32x4*>(plane + ((r + 1) * P + x + 1) * SB + part * 16);
-    }
-}
-
-// ---- The wide 3x3 convolution again, with BOTH operands streamed through LDS by DMA under the MFMAs (round 5).  conv_bf16_wide_band holds CP = 128
-// channels of the band in one plane and refills it between passes: fill -> vmcnt(0) -> barrier -> 936 MFMAs per wave -> barrier, nothing overlapped (one
-// workgroup per CU owns the whole LDS).  Ablated at 256 frames (make ABLATION=1, GRNET_WIDE_DBG): 480 -> 256 @56 takes 1 277 us, 1 054 without the three
-// refills, 177 without any k-loop (first fill + store): the k-loop alone runs at 2.0 PFLOP/s -- the MFMA issue rate at the clock the chip holds under this
-// load -- and 0.4 of 1.28 ms is exposed fill and store.
-// Here a plane holds ONE 32-channel chunk of the band (slot stride 64 + 32 bytes: 32 * odd, conflict-free b128 reads as before) and two planes alternate:
-// chunk c is computed from plane c % 2 while the pieces of chunk c + 1 land in the other one.  ONE barrier per chunk, behind tap 7: every wave's reads of
-// chunk c are done by then (tap 8's fragments are in registers) and its pieces of chunk c + 1 have landed, so tap 8 reads ahead into chunk c + 1 and the
-// first piece of chunk c + 2 goes out; 234 MFMAs per wave between barriers.
-// vmcnt retires in order, and hipcc drains it to ZERO in front of every use of a loaded register while an LDS-DMA it knows of is in flight (seen in the ISA of
-// a first version with the weights by global_load: one vmcnt(0) per tap).  So NO register-returning vector load is left in the loop: the weights go through
-// LDS too -- every wave DMAs the 2 KiB (32 output channels x 32 k) of its own fragments per k-step into a private ring of three slots, two steps ahead, XOR-
-// swizzled like the frame kernel's -- every DMA is inline asm the compiler does not count, and the waits are explicit: per tap the wave issues W(t+2) (two
-// pieces) and at most one plane piece, and waits in the middle of the tap with vmcnt(2 + I(t-1) + I(t)) -- everything up to W(t+1) has landed, the plane
-// pieces of this and the previous tap may still fly -- then reads W(t+1)'s fragments for the next tap.  I(t) = 1 on the taps that carry a plane piece
-// (tap 8 and taps 0 .. NFILL-2: every wave issues the same count -- a wave without an own last piece re-requests the plane's last one, and behind the
-// last chunk the pieces fetch zeros into the plane nobody reads any more).
-template <int CT, int W, int R, bool DIRECT = false>
-struct RingGeom {
-    static constexpr int P = W + 1, SB = 96, UPS = SB / 16;
-    static constexpr int ROWS = R + 2;
-    static constexpr int O0 = P + 1, NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int NPIECE = ((ROWS * P + 1) * UPS + 63) / 64;                 // one-KiB DMA pieces of a plane: slots 0 .. ROWS * P
-    static constexpr int PB = NPIECE * 1024;                                        // plane stride, bytes
-    static constexpr int NFILL = (NPIECE + 7) / 8;                                  // pieces per wave and chunk
-    static constexpr int WRING = 2 * PB;                                            // the waves' weight rings: 8 x 3 slots x 2 KiB (a plane's dead columns read into them: garbage, never stored)
-    static constexpr int OSB = 2 * CT + 32;                                         // slot stride of the output tile (staged over everything)
-    static constexpr int LDS = WRING + 8 * 3 * 2048;
-    static constexpr int UPP = CT / 8, NUO = (R * W * UPP + 511) / 512;
-    static constexpr int NB = (W + R - 1) / R;
-    static constexpr bool piece_at(int tap) { return tap == 8 || tap < NFILL - 1; }
-    static_assert(LDS <= 160 * 1024 && NFILL >= 2 && NFILL <= 7 && PS <= 32 && (DIRECT || (O0 + NT * 16) * OSB <= LDS) && CT % 32 == 0 && 8 % (CT / 32) == 0, "ring geometry");
-    static_assert((PS - 1) * 16 * SB + (2 * P + 2) * SB + 64 < 65536 && (O0 + NT * 16 + P + 2) * SB + 64 <= LDS - PB, "ds_read immediates / the farthest dead read stays inside the allocation");
-};
-
-template <int CT, int W, int R, bool DIRECT = false>
-__global__ __launch_bounds__(512) void conv_bf16_wide_ring(const ConvArgs a) {
-    typedef RingGeom<CT, W, R, DIRECT> G;
-    constexpr int P = G::P, SB = G::SB, CS = G::CS, PS = G::PS, UPS = G::UPS, UPP = G::UPP, PB = G::PB, NFILL = G::NFILL, OSB = G::OSB;
-    extern __shared__ __align__(16) unsigned char plane[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wcb = wave % G::WCB, pg = wave / G::WCB;
-    const int ncb = a.CoutPad / CT;
-    int bid = blockIdx.x;                                                           // a.xcd: consecutive tiles on ONE XCD (see conv_bf16_wide_band)
-    if (a.xcd && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int cbo = bid % ncb, nb = bid / ncb, n = nb / G::NB, band = nb - n * G::NB;
-    if (n >= a.N) return;
-    const int y0 = band * R;
-    const unsigned char* inb = reinterpret_cast<const unsigned char*>(reinterpret_cast<const u16*>(a.in) + (size_t)n * W * W * a.in_ctot + a.in_coff);
-    const int nch = a.CinPad / 32, nstep = nch * 9;
-    const unsigned lds0 = (unsigned)(size_t)plane;                                  // LDS byte address of the allocation (M0 takes byte addresses)
-
-    // this lane's share of plane piece i: byte offset of its 16 bytes of chunk 0 in the frame (chunk c: + 64 c).  Units that must read zero -- halo column, rows
-    // outside the image -- are the same for every chunk: they are zeroed ONCE below and their lanes are switched off in every piece (EXEC), so a piece needs
-    // no second source and is `global_load_lds v_off, s[base]`; the pad units (never read) stay on and fetch the frame's first bytes, so that no piece is empty
-    // (an instruction without lanes would not count in vmcnt, and the waits below count instructions)
-    unsigned poff[NFILL];
-    int pdst[NFILL];
-    unsigned long long pmask[NFILL];
-#pragma unroll
-    for (int i = 0; i < NFILL; ++i) {
-        int pc = i * 8 + wave;
-        pc = pc < G::NPIECE ? pc : G::NPIECE - 1;                                   // no own last piece: the plane's last one again
-        const int u = pc * 64 + lane, slot = u / UPS, part = u - slot * UPS, r = slot / P, xx = slot - r * P, y = y0 - 1 + r;
-        const bool data = part < 4 && r < G::ROWS && xx != 0 && y >= 0 && y < W;
-        poff[i] = data ? (unsigned)(((y * W + xx - 1) * a.in_ctot + part * 8) * 2) : 0u;
-        pdst[i] = pc * 1024;
-        pmask[i] = __ballot(data || part >= 4);
-        if (!data && part < 4) {                                                    // both planes: never written again
-            *reinterpret_cast<u32x4*>(plane + pdst[i] + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4*>(plane + PB + pdst[i] + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-    auto piece = [&](int i, int c, int pl) {                                        // behind the last chunk: chunk 0 again, into the plane nobody reads any more
-        int ce = c < nch ? c : 0;
-#ifdef GRNET_ABLATION
-        if (a.dbg & 8) ce = 0;                                                      // bit 3: every piece fetches chunk 0 (cache hits): issue cost without the memory latency
-#endif
-        dma16_masked(poff[i], inb + ce * 64, lds0 + pl + pdst[i], pmask[i]);
-    };
-    // weights of k-step s for this wave: rows co .. co + 31 of [step][CoutPad][32]; piece cs = 16 rows x 64 B, lane (row = l >> 2, unit = l & 3) fetches the unit
-    // (l & 3) ^ 2 (row >> 3 & 1) of its row: the fragment read below finds k-group lq of row l15 at unit lq ^ 2 (l15 >> 3) -- conflict-free b128 reads of 64-byte rows
-    const int co = cbo * CT + wcb * CS * 16;
-    const unsigned wlane = (unsigned)(((co + (lane >> 2)) * 32 + (((lane & 3) ^ (2 * ((lane >> 5) & 1))) * 8)) * 2);
-    const size_t wstep = (size_t)a.CoutPad * 64;                                    // bytes per k-step
-    const unsigned char* wg = reinterpret_cast<const unsigned char*>(a.w);
-    const unsigned wring = lds0 + G::WRING + wave * (3 * 2048);
-    auto wdma = [&](int s, int slot) {                                              // behind the layer's last step the stream ends: its first steps again (nobody reads them)
-        const unsigned char* base = wg + (size_t)(s < nstep ? s : s - nstep) * wstep;
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) dma16_hidden_s(wlane + cs * 1024, base, wring + slot * 2048 + cs * 1024);
-    };
-    const unsigned char* aread = plane + G::WRING + wave * (3 * 2048) + l15 * 64 + ((lq ^ (2 * (l15 >> 3))) * 16);
-
-    const int o_first = G::O0 + pg * PS * 16 + l15;
-    const unsigned char* bread = plane + (o_first - P - 1) * SB + lq * 16;
-    unsigned valid = 0;
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) {
-        const int o = o_first + ps * 16, r = o / P;
-        if (o - r * P != 0 && r >= 1 && r <= R && y0 + r - 1 < W) valid |= 1u << ps;
-    }
-    f32x4 acc[CS][PS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + co + cs * 16 + lq * 4);
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) acc[cs][ps] = bv;
-    }
-    // ---- prologue: chunk 0 -> plane 0, k-steps 0 and 1, the last piece of chunk 1 (the piece "tap 8 of chunk -1" would have issued)
-#pragma unroll
-    for (int i = 0; i < NFILL; ++i) piece(i, 0, 0);
-    wdma(0, 0);
-    wdma(1, 1);
-    piece(NFILL - 1, 1, PB);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CS + 1) : "memory");                   // in order: chunk 0 and step 0 have landed; step 1 and the piece of chunk 1 may fly
-    __syncthreads();                                                                // (and the zeroed halo units are everybody's)
-    bf16x8 bfr[PS], afr[3][CS];                                                     // fragment sets in ring order too: step s0 + tap uses set tap % 3 (9 = 3 x 3)
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) afr[0][cs] = *reinterpret_cast<const bf16x8*>(aread + cs * 1024);
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB);
-    int cur = 0, nxt = PB;
-#pragma unroll 1
-    for (int c = 0; c < nch; ++c) {
-        const unsigned char* bc = bread + cur;
-        const unsigned char* bn = bread + nxt;
-        const int s0 = c * 9;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            // k-step s0 + tap + 2 -> ring slot (tap + 2) % 3 (9 = 3 x 3: the slot is static), then this tap's plane piece: chunk c + 1 on taps 0 .. NFILL-2
-            // (pieces 0 .. NFILL-2; into the other plane), chunk c + 2 on tap 8 (piece NFILL-1; into THIS plane, which the barrier behind tap 7 has freed)
-#ifdef GRNET_ABLATION                                                  // timing-only builds (make ABLATION=1; GRNET_WIDE_DBG bit 0: no plane pieces, bit 1: no weight pieces, bit 2: no waits)
-            if (!(a.dbg & 2))
-#endif
-            wdma(s0 + tap + 2, (tap + 2) % 3);
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 1)) {
-#endif
-            if (tap == 8) piece(NFILL - 1, c + 2, cur);
-            else if (tap < NFILL - 1) piece(tap, c + 1, nxt);
-#ifdef GRNET_ABLATION
-            }
-#endif
-            const unsigned char* nb_ = tap < 8 ? bc + (((tap + 1) / 3) * P + ((tap + 1) % 3)) * SB : bn;
-            constexpr int HALF = PS / 2;
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-                if (ps == HALF) {
-                    // everything up to k-step s0 + tap + 1 has landed (issued one tap ago); behind it: that tap's plane piece, this tap's two weight pieces and plane piece
-#ifdef GRNET_ABLATION
-                    if (!(a.dbg & 4))
-#endif
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CS + (G::piece_at((tap + 8) % 9) ? 1 : 0) + (G::piece_at(tap) ? 1 : 0)) : "memory");
-#pragma unroll
-                    for (int cs = 0; cs < CS; ++cs) afr[(tap + 1) % 3][cs] = *reinterpret_cast<const bf16x8*>(aread + ((tap + 1) % 3) * 2048 + cs * 1024);
-                }
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[tap % 3][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(nb_ + ps * 16 * SB);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (tap == 7) {
-                // every read of chunk c has returned (tap 8's fragments included); this wave's pieces of chunk c + 1 landed with the wait in the middle of this tap
-                // (the last one went out on tap NFILL-2 <= 5)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-            }
-        }
-        const int t = cur; cur = nxt; nxt = t;
-    }
-    if constexpr (DIRECT) {
-        // 256 output channels per workgroup: the tile (R x W pixels x 512 bytes) does not fit the LDS beside nothing -- it leaves straight from the accumulators, 8 bytes per
-        // lane and block (a pixel's 64 bytes of this wave are two stores back to back; the eight channel waves complete its 512-byte row in L2)
-        const int cstore = a.Cout - cbo * CT;
-        u16* outw = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff + cbo * CT + wcb * CS * 16 + lq * 4;
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) {
-            const int o = o_first + ps * 16, r = o / P, x = o - r * P - 1;
-            u16* op = outw + ((size_t)(y0 + r - 1) * W + x) * a.out_ctot;
-#pragma unroll
-            for (int cs = 0; cs < CS; ++cs) {
-                f32x4 v = acc[cs][ps];
-                if (a.relu) { v[0] = relu_c(v[0]); v[1] = relu_c(v[1]); v[2] = relu_c(v[2]); v[3] = relu_c(v[3]); }
-                if ((valid & (1u << ps)) && wcb * CS * 16 + cs * 16 + lq * 4 < cstore) *reinterpret_cast<u32x2*>(op + cs * 16) = u32x2{pack2_c(v[0], v[1]), pack2_c(v[2], v[3])};
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // no piece may land in an LDS that already belongs to somebody else
-        return;
-    }
-    // ---- the tile: ReLU, bf16, staged over planes and rings (every piece has landed, every wave is done reading), rows y0 .. y0 + R - 1 -> HBM as whole channel rows
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned char* owrite = plane + o_first * OSB + (wcb * CS * 16 + lq * 4) * 2;
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_c(v[0]); v[1] = relu_c(v[1]); v[2] = relu_c(v[2]); v[3] = relu_c(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = u32x2{pack2_c(v[0], v[1]), pack2_c(v[2], v[3])};
-        }
-    __syncthreads();
-    u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff + cbo * CT;
-    const int cstore = a.Cout - cbo * CT;
-#pragma unroll
-    for (int i = 0; i < G::NUO; ++i) {
-        const int u = i * 512 + tid, px = u / UPP, part = u - px * UPP, r = px / W, x = px - r * W;
-        if (u < R * W * UPP && y0 + r < W && part * 8 < cstore)
-            *reinterpret_cast<u32x4*>(outb + ((size_t)(y0 + r) * W + x) * a.out_ctot + part * 8) = *reinterpret_cast<const u32x4*>(plane + ((r + 1) * P + x + 1) * OSB + part * 16);
-    }
-}
-
-// ---- ONE 3x3 STRIDE-2 convolution (fuse layers' down paths hrnet.py:213-241, transitions hrnet.py:348-387, the stem's second convolution hrnet.py:470-475) with a
-// band of the input resident in LDS.  conv_bf16_nhwc runs these layers at 0.05-0.16 of the matrix peak and 2-3 x their HBM time: 112-pixel tiles of ~60
-// MFMAs per wave behind a slot table, a DMA wait, an LDS transpose and two barriers, 1 500 ms-scale launches of them per step (1.5 ms of 11).
-// Stride 2 breaks the flattened plane of the stride-1 kernels (tap (dy, dx) of output (Y, X) is input (2Y + dy - 1, 2X + dx - 1): not a constant slot offset)
-// -- unless the input is DE-INTERLEAVED by row and column parity into four sub-planes sub(py, px)[Y'][X'] = in[2Y' + py][2X' + px]: then tap (dy, dx) reads
-// sub(py, px) at (Y + oy, X + ox) with py = (dy != 1), oy = -(dy == 0) and likewise for x, and inside its sub-plane every tap IS a constant offset again.
-// The LDS-DMA does the de-interleaving for free: its source address is per lane.  Each sub-plane is flattened with pitch Wo + 1 (column X' = -1 is the shared
-// zero column, row Y' = y0 - 1 the zero / halo row), R + 1 rows; output column o = (Y - y0)(Wo + 1) + X.  Everything else -- CP input channels per pass,
-// weight ring, MFMA roles, in-place tile through LDS -- is conv_bf16_wide_band's; the epilogue adds the layer's fused addends (nearest-upsampled terms of
-// the fuse sum, hrnet.py:258-265) before the ReLU.
-template <int CP, int CT, int WO, int R>
-struct S2Geom {
-    static constexpr int P = WO + 1, SB = 2 * CP + 32, UPS = SB / 16, OSB = 2 * CT + 32;
-    static constexpr int NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int SUBROWS = R + 1;
-    static constexpr int SUB = (SUBROWS * P > NT * 16 + P + 1 ? SUBROWS * P : NT * 16 + P + 1);      // slots per sub-plane: its rows, or what the farthest tap of the last column tile reaches
-    static constexpr int FILL_UNITS = (4 * SUB * UPS + 63) / 64 * 64;
-    static constexpr int NFILL = (FILL_UNITS / 64 + 7) / 8;
-    static constexpr int LDS = (4 * SUB * SB + SB > FILL_UNITS * 16 ? 4 * SUB * SB + SB : FILL_UNITS * 16);
-    static constexpr int UPP = CT / 8, NUO = (R * WO * UPP + 511) / 512;
-    static constexpr int NB = (WO + R - 1) / R;
-    static_assert(((SB / 32) % 2) == 1 && LDS <= 160 * 1024 && PS <= 32 && NT * 16 * OSB <= LDS && CT % 32 == 0 && 8 % (CT / 32) == 0, "stride-2 band geometry");
-    // byte offset of tap (dy, dx) from the lane's base (sub-plane (0,0), row 0, column slot 0)
-    static constexpr int toff(int tap) {
-        const int dy = tap / 3, dx = tap % 3, py = dy != 1, px = dx != 1, oy = dy == 0 ? -1 : 0, ox = dx == 0 ? -1 : 0;
-        return ((py * 2 + px) * SUB + (oy + 1) * P + (ox + 1)) * SB;
-    }
-};
-
-template <typename G, int CS, int PS>
-__device__ __forceinline__ void s2_kloop(f32x4 (&acc)[CS][PS], bf16x8 (&wr)[3][CS], const unsigned char* bread, const u16* wc, size_t wtap, int nch, bool last, unsigned wlb) {
-    constexpr int SB = G::SB;
-    bf16x8 bfr[PS];
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB + G::toff(0));
-#pragma unroll 1
-    for (int chunk = 0; chunk < nch; ++chunk) {
-        const unsigned char* bch = bread + chunk * 64;
-        const u16* wch = wc + (size_t)chunk * 9 * wtap;
-        const bool lastc = last && chunk == nch - 1;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            {
-                const u16* src = wch + (size_t)(tap + 2) * wtap;
-                if (tap >= 7) src = lastc ? wc + (size_t)(tap - 7) * wtap : src;
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) wr[(tap + 2) % 3][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(src + cs * 16 * 32) + wlb);
-            }
-            const int noff = tap < 8 ? G::toff(tap + 1) : G::toff(0) + 64;      // the next chunk's first tap; behind the last chunk it reads ahead into padding / the spare slot
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[tap % 3][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(bch + ps * 16 * SB + noff);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
-
-template <int CP, int CT, int WO, int R>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(S2Geom<CP, CT, WO, R>::LDS <= 80 * 1024 ? 4 : 2))) void conv_bf16_s2_band(const ConvArgs a) {
-    typedef S2Geom<CP, CT, WO, R> G;
-    constexpr int P = G::P, SB = G::SB, CS = G::CS, PS = G::PS, UPS = G::UPS, UPP = G::UPP, OSB = G::OSB, WI = 2 * WO;
-    extern __shared__ __align__(16) unsigned char plane[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wcb = wave % G::WCB, pg = wave / G::WCB;
-    const int ncb = a.CoutPad / CT;
-    const int cbo = blockIdx.x % ncb, nb = blockIdx.x / ncb, n = nb / G::NB, band = nb - n * G::NB;
-    if (n >= a.N) return;
-    const int y0 = band * R;
-    const u16* inb = reinterpret_cast<const u16*>(a.in) + (size_t)n * WI * WI * a.in_ctot + a.in_coff;
-    const u16* zeros = reinterpret_cast<const u16*>(a.zeros);
-
-    auto fill = [&](int c0, int cw) {                          // input channels c0 .. c0 + cw - 1 of the band, de-interleaved -> the four sub-planes, by LDS-DMA
-        int ln = lane;
-        asm volatile("" : "+v"(ln));                           // (keeps hipcc from hoisting the unit -> pixel map out of the pass loop into registers, as in the wide kernel)
-#pragma unroll
-        for (int i = 0; i < G::NFILL; ++i) {
-            const int ub = (i * 8 + wave) * 64;
-            if (ub >= G::FILL_UNITS) break;                    // wave-uniform
-            const int u = ub + ln, slot = u / UPS, part = u - slot * UPS, sub = slot / G::SUB, ss = slot - sub * G::SUB, rr = ss / P, xx = ss - rr * P;
-            const int py = sub >> 1, px = sub & 1, row = 2 * (y0 - 1 + rr) + py, col = 2 * (xx - 1) + px;
-            const bool data = sub < 4 && rr < G::SUBROWS && !(py == 0 && rr == 0) && row >= 0 && row < WI && col >= 0 && col < WI && part * 8 < cw;
-            dma16_c(data ? inb + (size_t)(row * WI + col) * a.in_ctot + c0 + part * 8 : zeros, plane + ub * 16);
-        }
-    };
-
-    const int o_first = pg * PS * 16 + l15;
-    const unsigned char* bread = plane + o_first * SB + lq * 16;
-    const int co = cbo * CT + wcb * CS * 16;
-    const unsigned wlb = ((co + l15) * 32 + lq * 8) * 2;
-    const size_t wtap = (size_t)a.CoutPad * 32;
-    const u16* wg = reinterpret_cast<const u16*>(a.w);
-    f32x4 acc[CS][PS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + co + cs * 16 + lq * 4);
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) acc[cs][ps] = bv;
-    }
-    bf16x8 wr[3][CS];
-#pragma unroll
-    for (int cs = 0; cs < CS; ++cs) {
-        wr[0][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(wg + cs * 16 * 32) + wlb);
-        wr[1][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(wg + wtap + cs * 16 * 32) + wlb);
-    }
-    const int npass = (a.CinPad + CP - 1) / CP;
-#pragma unroll 1
-    for (int pass = 0; pass < npass; ++pass) {
-        const int c0 = pass * CP, cw = a.CinPad - c0 < CP ? a.CinPad - c0 : CP;
-        if (pass) __syncthreads();
-        fill(c0, cw);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        s2_kloop<G, CS, PS>(acc, wr, bread, wg + (size_t)(c0 / 32) * 9 * wtap, wtap, cw / 32, pass == npass - 1, wlb);
-    }
-    // ---- epilogue: + fused addends (nearest-upsampled by 2^shift), ReLU, bf16; through LDS as whole channel rows
-    const int Ho = WO;
-    unsigned valid = 0;
-    int pix[PS];                                               // (Y << 8) | X of this lane's column of tile ps
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) {
-        const int o = o_first + ps * 16, yy = o / P, X = o - yy * P;
-        pix[ps] = ((y0 + yy) << 8) | X;
-        if (X < WO && yy < R && y0 + yy < Ho) valid |= 1u << ps;
-    }
-#pragma unroll
-    for (int k = 0; k < kMaxAdd; ++k) {
-        if (k >= a.n_add) break;
-        const int sh = a.add_shift[k], hs = Ho >> sh, ws = WO >> sh;
-        const u16* ab = reinterpret_cast<const u16*>(a.add[k]) + (size_t)n * hs * ws * a.add_ctot[k] + a.add_coff[k] + co + lq * 4;
-        u32x2 r[PS][CS];
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps) {
-            const bool ok = (valid >> ps) & 1u;
-            const int Y = ok ? pix[ps] >> 8 : 0, X = ok ? pix[ps] & 255 : 0;
-            const u16* ap = ab + ((size_t)(Y >> sh) * ws + (X >> sh)) * a.add_ctot[k];
-#pragma unroll
-            for (int cs = 0; cs < CS; ++cs) r[ps][cs] = ok ? *reinterpret_cast<const u32x2*>(ap + cs * 16) : u32x2{0u, 0u};
-        }
-#pragma unroll
-        for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-            for (int cs = 0; cs < CS; ++cs) {
-                acc[cs][ps][0] += bf_lo(r[ps][cs][0]); acc[cs][ps][1] += bf_hi(r[ps][cs][0]);
-                acc[cs][ps][2] += bf_lo(r[ps][cs][1]); acc[cs][ps][3] += bf_hi(r[ps][cs][1]);
-            }
-    }
-    __syncthreads();                                           // every wave has finished reading the sub-planes
-    unsigned char* owrite = plane + o_first * OSB + (wcb * CS * 16 + lq * 4) * 2;
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps)
-#pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_c(v[0]); v[1] = relu_c(v[1]); v[2] = relu_c(v[2]); v[3] = relu_c(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = u32x2{pack2_c(v[0], v[1]), pack2_c(v[2], v[3])};
-        }
-    __syncthreads();
-    u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * Ho * WO * a.out_ctot + a.out_coff + cbo * CT;
-    const int cstore = a.Cout - cbo * CT;
-#pragma unroll
-    for (int i = 0; i < G::NUO; ++i) {
-        const int u = i * 512 + tid, px = u / UPP, part = u - px * UPP, yy = px / WO, X = px - yy * WO;
-        if (u < R * WO * UPP && y0 + yy < Ho && part * 8 < cstore)
-            *reinterpret_cast<u32x4*>(outb + ((size_t)(y0 + yy) * WO + X) * a.out_ctot + part * 8) = *reinterpret_cast<const u32x4*>(plane + (yy * P + X) * OSB + part * 16);
-    }
-}
-
-// ---- The narrow 3x3 stride-2 layers of the fuse down paths (32 / 64 input channels) as a WALK OVER OUTPUT ROWS.  These launches are neither compute- nor
-// byte-bound in the band kernel above or in conv_bf16_nhwc (0.05-0.15 of the matrix peak at 1.9 TB/s: fill -> barrier -> k-loop -> epilogue -> store, one after
-// another per workgroup).  Here a workgroup owns a segment of a frame's output rows; per output row Y it needs input rows 2Y - 1 .. 2Y + 1, of which two are new:
-// they arrive by LDS-DMA one step ahead, DE-INTERLEAVED by column parity (odd columns with a leading zero slot, then even columns: tap dx reads odd index x, even
-// index x, odd index x + 1 -- 16 consecutive slots for 16 output pixels), 16-byte parts XOR-swizzled by slot bits so that every fragment read is conflict-free.  A
-// wave owns one (16-pixel tile, 16-channel block) of the row with that block's weights in its registers for the whole launch (9 x Cin/32 A fragments), so a step is
-// 9 or 18 MFMAs per wave, an epilogue straight from the accumulators (bias, fused addends, ReLU, 8-byte stores) and ONE barrier; the ring is 6 input rows (25 KB), so
-// four workgroups share a CU and cover each other's memory round trips.  Results equal the band kernel's bit for bit (same k order, same epilogue order).
-template <int CIN, int COUT, int WO>
-struct S2RowsGeom {
-    static constexpr int WI = 2 * WO, SB = 2 * CIN, UPS = SB / 16, KS = CIN / 32;
-    static constexpr int MT = (WO + 15) / 16, NBK = COUT / 16, ITEMS = MT * NBK;
-    static constexpr int PO = 16 * MT + 1, PE = 16 * MT, SLOTS = PO + PE;      // odd-column plane (index 0 = column -1), even-column plane
-    static constexpr int ROWB = SLOTS * SB, RING = 6;
-    static constexpr int UNITS = SLOTS * UPS, NDMA = (UNITS + 63) / 64;      // 16-byte units of a row; wave-instructions per row
-    static constexpr int LDS = RING * ROWB + 64 * 16;                         // + what the last instruction of the last row writes past it (masked lanes write nothing)
-    static_assert(ITEMS <= 8 && 2 * NDMA <= 16 && (CIN == 32 || CIN == 64) && COUT % 16 == 0 && LDS <= 64 * 1024, "stride-2 row geometry");
-    static __device__ __forceinline__ int swz(int slot) { return CIN == 32 ? (((slot >> 2) & 1) << 1) : (((slot >> 1) & 3) << 1); }
-};
-
-template <int CIN, int COUT, int WO>
-__global__ __launch_bounds__(512) void conv_bf16_s2_rows(const ConvArgs a, int segs) {
-    typedef S2RowsGeom<CIN, COUT, WO> G;
-    constexpr int WI = G::WI, SB = G::SB, KS = G::KS;
-    extern __shared__ __align__(16) unsigned char ring[];
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = blockIdx.x / segs, seg = blockIdx.x - n * segs;
-    if (n >= a.N) return;
-    const int rows_per = (WO + segs - 1) / segs, y_lo = seg * rows_per, y_hi = min(WO, y_lo + rows_per);
-    const u16* inb = reinterpret_cast<const u16*>(a.in) + (size_t)n * WI * WI * a.in_ctot + a.in_coff;
-    u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * WO * WO * a.out_ctot + a.out_coff;
-    const bool works = wave < G::ITEMS;
-    const int nb = wave % G::NBK, mt = wave / G::NBK, co = nb * 16;
-
-    bf16x8 wf[KS][9];
-    f32x4 bias = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (works) {
-        const u16* wg = reinterpret_cast<const u16*>(a.w);
-#pragma unroll
-        for (int kc = 0; kc < KS; ++kc)
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) wf[kc][tap] = *reinterpret_cast<const bf16x8*>(wg + (((size_t)kc * 9 + tap) * a.CoutPad + co + l15) * 32 + 8 * lq);
-        bias = *reinterpret_cast<const f32x4*>(a.bias + co + 4 * lq);
-    }
-    for (int u = tid; u < G::LDS / 16; u += 512) reinterpret_cast<u32x4*>(ring)[u] = u32x4{0u, 0u, 0u, 0u};
-    // this wave's share of a step's two new rows: wave-instructions q = wave, wave + 8 of the 2 x NDMA (row q / NDMA, instruction q % NDMA); per lane the unit's
-    // (validity, source offset inside an input row): unit d = (slot, stored part) -> column 2 i - 1 (odd plane, i = slot) or 2 j (even plane), part = stored ^ swz(slot)
-    int dq_row[2], dq_k[2], dq_off[2];
-    bool dq_on[2], dq_lane[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int q = wave + 8 * i;
-        dq_on[i] = q < 2 * G::NDMA;
-        dq_row[i] = q / G::NDMA; dq_k[i] = q - dq_row[i] * G::NDMA;
-        const int d = dq_k[i] * 64 + lane, slot = d / G::UPS, sp = d - slot * G::UPS;
-        const int col = slot < G::PO ? 2 * slot - 1 : 2 * (slot - G::PO);
-        dq_lane[i] = dq_on[i] && d < G::UNITS && col >= 0 && col < WI && (slot < G::PO ? slot <= WO : slot - G::PO < WO);
-        dq_off[i] = col * a.in_ctot + (sp ^ G::swz(slot)) * 8;
-    }
-    // fragment offsets of this wave's tile inside a ring row: tap dx reads odd index x (dx = 0), even index x (1), odd index x + 1 (2), x = 16 mt + l15
-    unsigned foff[3][KS];
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-        const int x = 16 * mt + l15, slot = dx == 1 ? G::PO + x : x + (dx >> 1);
-#pragma unroll
-        for (int kc = 0; kc < KS; ++kc) foff[dx][kc] = (unsigned)(slot * SB + (((4 * kc + lq) ^ G::swz(slot)) * 16));
-    }
-    auto request = [&](int y, int rr0) {                       // input rows 2 y, 2 y + 1 -> ring rows rr0, rr0 + 1 (wrapped by the caller)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            if (dq_on[i]) {
-                const int row = 2 * y + dq_row[i];
-                int rr = rr0 + dq_row[i];
-                rr = rr >= G::RING ? rr - G::RING : rr;
-                if (dq_lane[i] && row < WI) dma16_c(inb + (size_t)row * WI * a.in_ctot + dq_off[i], ring + rr * G::ROWB + dq_k[i] * 1024);
-            }
-    };
-    lds_barrier();                                             // the ring is zero (the halo slots and the row above the image stay zero: no DMA ever writes them ... see below)
-    // ring row of input row r: (r + 2) mod 6 by a wrapping counter; row 2 y_lo - 1 (or the zero row above the image) sits at `cur`
-    int cur = 0;
-    if (y_lo > 0 && wave == 0) {                               // the segment's first output row needs input row 2 y_lo - 1: one extra row, by wave 0
-#pragma unroll
-        for (int k = 0; k < G::NDMA; ++k) {
-            const int d = k * 64 + lane, slot = d / G::UPS, sp = d - slot * G::UPS;
-            const int col = slot < G::PO ? 2 * slot - 1 : 2 * (slot - G::PO);
-            const bool ok = d < G::UNITS && col >= 0 && col < WI && (slot < G::PO ? slot <= WO : slot - G::PO < WO);
-            if (ok) dma16_c(inb + ((size_t)(2 * y_lo - 1) * WI + col) * a.in_ctot + (sp ^ G::swz(slot)) * 8, ring + cur * G::ROWB + k * 1024);
-        }
-    }
-    request(y_lo, cur + 1);
-#pragma unroll 1
-    for (int y = y_lo; y < y_hi; ++y) {
-        // fused addends of this row (nearest-upsampled by 2^shift), requested before the wait below so that it covers them
-        u32x2 av[kMaxAdd];
-        const int x = 16 * mt + l15;
-        const bool px_ok = works && x < WO;
-#pragma unroll
-        for (int k = 0; k < kMaxAdd; ++k) {
-            av[k] = u32x2{0u, 0u};
-            if (k < a.n_add && px_ok) {
-                const int sh = a.add_shift[k], ws = WO >> sh;
-                av[k] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const u16*>(a.add[k]) + ((size_t)n * (WO >> sh) * ws + (size_t)(y >> sh) * ws + (x >> sh)) * a.add_ctot[k] + a.add_coff[k] + co + 4 * lq);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of rows 2 y, 2 y + 1 (requested a step ago) have landed
-        lds_barrier();                                         // ... and everybody's; every wave is done with row 2 y - 2 (the next request overwrites it)
-        f32x4 af[kMaxAdd];                                     // the addends as floats HERE: hipcc's own wait for their loads must not land behind the next request
-#pragma unroll
-        for (int k = 0; k < kMaxAdd; ++k) af[k] = f32x4{bf_lo(av[k][0]), bf_hi(av[k][0]), bf_lo(av[k][1]), bf_hi(av[k][1])};
-        __builtin_amdgcn_sched_barrier(0);
-        int nxt = cur + 3;
-        nxt = nxt >= G::RING ? nxt - G::RING : nxt;
-        if (y + 1 < y_hi) request(y + 1, nxt);
-        if (works) {
-            f32x4 acc = bias;
-            const unsigned char* r0 = ring + cur * G::ROWB;
-            int c1 = cur + 1, c2 = cur + 2;
-            c1 = c1 >= G::RING ? c1 - G::RING : c1; c2 = c2 >= G::RING ? c2 - G::RING : c2;
-            const unsigned char* r1 = ring + c1 * G::ROWB;
-            const unsigned char* r2 = ring + c2 * G::ROWB;
-#pragma unroll
-            for (int kc = 0; kc < KS; ++kc)
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const unsigned char* rb = tap < 3 ? r0 : tap < 6 ? r1 : r2;
-                    const bf16x8 px = *reinterpret_cast<const bf16x8*>(rb + foff[tap % 3][kc]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kc][tap], px, acc, 0, 0, 0);
-                }
-#pragma unroll
-            for (int k = 0; k < kMaxAdd; ++k)
-                if (k < a.n_add) { acc[0] += af[k][0]; acc[1] += af[k][1]; acc[2] += af[k][2]; acc[3] += af[k][3]; }
-            if (a.relu) { acc[0] = relu_c(acc[0]); acc[1] = relu_c(acc[1]); acc[2] = relu_c(acc[2]); acc[3] = relu_c(acc[3]); }
-            if (px_ok) *reinterpret_cast<u32x2*>(outb + ((size_t)y * WO + x) * a.out_ctot + co + 4 * lq) = u32x2{pack2_c(acc[0], acc[1]), pack2_c(acc[2], acc[3])};
-        }
-        cur += 2;
-        cur = cur >= G::RING ? cur - G::RING : cur;
-    }
-}
-// (the three shapes the band kernel lost on; on its own shapes -- 64 -> 128, 32 -> 128, 32 -> 32 @28->14 -- the walk ties with it: 15.1 against 14.5 us, not instantiated)
-#define GRK_S2R_SHAPES(X) X(32, 64, 28) X(32, 32, 28) X(64, 64, 14)
-template <int CIN, int COUT, int WO>
-hipError_t launch_s2_rows(const ConvArgs& a, hipStream_t s) {
-    typedef S2RowsGeom<CIN, COUT, WO> G;
-    int cus = 0;
-    GRK_TRY(device_cu_count(&cus));
-    // segments of output rows per frame: several workgroups per CU where the frame count allows it, but never fewer than 7 rows per workgroup (each one loads
-    // its channel blocks' weights: 18-74 KB from L2)
-    int segs = 1;
-    if (a.N < 4 * cus) segs = 2;
-    if (WO == 28 && a.N * 2 < 4 * cus) segs = 4;
-    return launch_k(conv_bf16_s2_rows<CIN, COUT, WO>, dim3(a.N * segs), dim3(512), G::LDS, s, a, segs);
-}
-
-template <int CP, int CT, int WO, int R>
-hipError_t set_s2_lds() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_s2_band<CP, CT, WO, R>), hipFuncAttributeMaxDynamicSharedMemorySize, S2Geom<CP, CT, WO, R>::LDS);
-}
-template <int CP, int CT, int WO, int R>
-hipError_t launch_s2(const ConvArgs& a, hipStream_t s) {
-    typedef S2Geom<CP, CT, WO, R> G;
-    return launch_k(conv_bf16_s2_band<CP, CT, WO, R>, dim3(a.N * G::NB * (a.CoutPad / CT)), dim3(512), G::LDS, s, a);
-}
-// (CP, CT, Wo, R) per layer shape: the band is as tall as the four sub-planes' LDS allows
-// Measured at 256 frames against conv_bf16_nhwc (profiles/r05_s2_band_vs_generic.txt): the band kernel wins where a workgroup's MFMA share is large enough to
-// carry its fill -> barrier -> store round trip -- 64 -> 128 @28->14 (20.6 / 23.1 us against 30.2 / 35.1), 32 -> 128 @28->14 (10.5 / 17.3), 32 -> 32 @28->14
-// (7.8 / 9.8), the stem's 64 -> 64 @112->56 (216 / 237) -- ties on the 14->7 layers and loses on 256 -> 64 (four passes, each with an exposed fill:
-// 174 / 144), 32 -> 32 and 32 -> 64 @56->28 (7-row bands 26.7 / 40.7 against 27.6 / 34.4; 3-row bands with two workgroups per CU 35.0 / 47.5),
-// 64 -> 64 @28->14 (17.7 / 12.9), 128 -> 256 @14->7 (30.1 / 24.0): those stay on the generic kernel and are not instantiated.
-#define GRK_S2_SHAPES(X) X(64, 64, 56, 3) X(64, 128, 14, 14) X(32, 128, 14, 14) X(32, 32, 14, 14)
 
 template <int C, int W>
 hipError_t set_chain_lds() {
@@ -1597,25 +714,14 @@ hipError_t conv_bf16_chain_init() {
     GRK_TRY((set_chain_lds<128, 14>()));
     GRK_TRY((set_chain_lds<256, 7>()));
     GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_chain<256, 7, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, ChainGeom<256, 7, 2>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_block_band<32, 56, 19, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, BandGeom<32, 56, 19>::LDS));
-#define GRK_S2_SET(cp, ct, wo, r) GRK_TRY((set_s2_lds<cp, ct, wo, r>()));
-    GRK_S2_SHAPES(GRK_S2_SET)
-#undef GRK_S2_SET
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_band<128, 128, 56, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, WideGeom<128, 128, 56, 7>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_band<128, 128, 28, 14>), hipFuncAttributeMaxDynamicSharedMemorySize, WideGeom<128, 128, 28, 14>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_band<64, 64, 56, 14>), hipFuncAttributeMaxDynamicSharedMemorySize, WideGeom<64, 64, 56, 14>::LDS));
     GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_block_frame<56, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, FrameGeom<56, 8>::LDS));
     GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_chain_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, PipeGeom::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_ring<128, 56, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, RingGeom<128, 56, 8>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_ring<256, 56, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, RingGeom<256, 56, 4, true>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_ring<32, 56, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, RingGeom<32, 56, 8>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_wide_ring<128, 28, 14>), hipFuncAttributeMaxDynamicSharedMemorySize, RingGeom<128, 28, 14>::LDS));
-    GRK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bf16_block_band<32, 56, 8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, BandGeom<32, 56, 8>::LDS));
-    return hipSuccess;
+    GRK_TRY(conv_bf16_wide_init());                          // the two other families of LDS-resident kernels (conv_bf16_wide.hip, conv_bf16_s2.hip)
+    return conv_bf16_s2_init();
 }
 
 bool conv_bf16_chain_eligible(int c, int w) { return (c == 64 && w == 28) || (c == 128 && w == 14) || (c == 256 && w == 7) || (c == 32 && w == 56); }
-// the 56x56 branch: ONE launch for a whole module's chain (conv_bf16_chain_pipe, 8 convolutions), otherwise one band-resident launch per BasicBlock
+// the 56x56 branch: ONE launch for a whole module's chain (conv_bf16_chain_pipe, 8 convolutions), otherwise one launch per BasicBlock (conv_bf16_block_frame)
 int conv_bf16_chain_launches(int c, int w, int nconv) { return c == 32 && w == 56 && !(nconv == 8 && GRNET_AB(BF16_PIPE, 1)) ? nconv / 2 : 1; }
 
 // a.in / a.out: NHWC bf16 views of (N, W, W, C) tensors (channel strides in_ctot / out_ctot, first channels in_coff / out_coff, multiples of 8);
@@ -1630,12 +736,9 @@ hipError_t launch_conv_bf16_chain(const ChainArgs& a, int c, int w, hipStream_t 
 #ifdef GRNET_ABLATION
         if (GRNET_AB_SET(PIPE_PHASES)) {
             b.flags |= 128;
-            unsigned long long z[32] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pipe_phase), z, sizeof(z));
             GRK_TRY(launch_k(conv_bf16_chain_pipe, dim3(a.N), dim3(512), PipeGeom::LDS, s, b));
-            (void)hipStreamSynchronize(s);
             unsigned long long h[32] = {};
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pipe_phase), sizeof(h));
+            abl::take_counters(HIP_SYMBOL(g_pipe_phase), h, s);
             const double d = (double)a.N * 79.0;                 // per workgroup and step
             for (int w = 0; w < 8; ++w)
                 fprintf(stderr, "[pipe phases] wave %d (conv %d): ticks per step  request %.0f  compute+store %.0f  dma wait %.0f  barrier %.0f\n", w, w < 4 ? 2 * w : 2 * (w - 4) + 1,
@@ -1656,13 +759,10 @@ hipError_t launch_conv_bf16_chain(const ChainArgs& a, int c, int w, hipStream_t 
                 if (!a.mid[k] || a.mid_ctot[k] % 8 != 0 || a.mid_coff[k] % 8 != 0) return hipErrorInvalidValue;
                 b.out = a.mid[k]; b.out_ctot = a.mid_ctot[k]; b.out_coff = a.mid_coff[k];
             } else { b.out = a.out; b.out_ctot = a.out_ctot; b.out_coff = a.out_coff; }
-            // 0 (default): workgroup = frame, seven bands of 8 rows, the next band by LDS-DMA under the current band's MFMAs; 19: workgroup = band, one per CU; 8: two per CU
+            // workgroup = frame, seven bands of 8 rows, the next band by LDS-DMA under the current band's MFMAs
             static const int frame_direct = GRNET_AB(BF16_FRAME_DIRECT, 1);
             b.flags = (frame_direct ? 0 : 1) | (GRNET_AB(BF16_FRAME_DBG, 0) << 4);      // (diagnostic builds: timing-only ablation bits 16 / 32 / 64 = no conv1 k-loop / no conv2 k-loop / no deposit)
-            static const int band_rows = GRNET_AB(BF16_BAND, 0);
-            if (band_rows == 0) GRK_TRY(launch_k(conv_bf16_block_frame<56, 8>, dim3(a.N), dim3(512), FrameGeom<56, 8>::LDS, s, b));
-            else if (band_rows == 19) GRK_TRY(launch_k(conv_bf16_block_band<32, 56, 19, 2>, dim3(a.N * BandGeom<32, 56, 19>::NB), dim3(512), BandGeom<32, 56, 19>::LDS, s, b));
-            else GRK_TRY(launch_k(conv_bf16_block_band<32, 56, 8, 4>, dim3(a.N * BandGeom<32, 56, 8>::NB), dim3(512), BandGeom<32, 56, 8>::LDS, s, b));
+            GRK_TRY(launch_k(conv_bf16_block_frame<56, 8>, dim3(a.N), dim3(512), FrameGeom<56, 8>::LDS, s, b));
         }
         return hipSuccess;
     }
@@ -1670,86 +770,6 @@ hipError_t launch_conv_bf16_chain(const ChainArgs& a, int c, int w, hipStream_t 
     if (c == 128) return launch_k(conv_bf16_chain<128, 14>, dim3(a.N), dim3(512), ChainGeom<128, 14>::LDS, s, a);
     if (GRNET_AB(BF16_CHAIN7_PAIR, 1) && a.N >= 2) return launch_k(conv_bf16_chain<256, 7, 2>, dim3((a.N + 1) / 2), dim3(512), ChainGeom<256, 7, 2>::LDS, s, a);
     return launch_k(conv_bf16_chain<256, 7>, dim3(a.N), dim3(512), ChainGeom<256, 7>::LDS, s, a);
-}
-
-// Wide-band kernel: 3x3, stride 1, no fused addend, 56x56 or 28x28 maps, CinPad a multiple of 32; output channels in tiles of 128 (Cin >= 128) or
-// 64 (Cin = 64 -> 64); every 16-byte group of the output view must lie inside the buffer.  (A 32-channel tile for transition1's 256 -> 32 -- 6-row bands,
-// 3 column tiles per wave -- measured 245 us against the generic kernel's 228 at 256 frames: every pixel fragment feeds two MFMAs only.  Not instantiated.)
-bool conv_bf16_wide_eligible(const ConvArgs& a) {
-    if (a.ks != 3 || a.stride != 1 || a.n_add != 0 || a.H != a.W || a.Ho != a.H || a.Wo != a.W || a.CinPad % 32 != 0) return false;
-    if (a.in_ctot % 8 != 0 || a.in_coff % 8 != 0 || a.out_ctot % 8 != 0 || a.out_coff % 8 != 0 || a.Cout % 8 != 0) return false;
-    if (a.W == 56 && a.CinPad == 64 && a.CoutPad == 64) return true;
-    // transition1's 256 -> 32 (hrnet.py:348-387): the ring kernel with ONE 32-channel block, every wave a column group (conv_bf16_nhwc ran it at 0.18 of the peak, 2.0 TB/s)
-    static const int ct32_env = GRNET_AB(BF16_WIDE_CT32, 1);
-    if (ct32_env && a.W == 56 && a.CinPad >= 128 && a.CoutPad == 32) return true;
-    return (a.W == 56 || a.W == 28) && a.CinPad >= 128 && a.CoutPad % 128 == 0;
-}
-hipError_t launch_conv_bf16_wide(const ConvArgs& a0, hipStream_t s) {
-    if (!conv_bf16_wide_eligible(a0) || a0.N < 1) return hipErrorInvalidValue;
-    static const int xcd_env = GRNET_AB(BF16_XCD, 1);
-    ConvArgs a = a0;
-    a.xcd = xcd_env;
-#ifdef GRNET_ABLATION
-    a.dbg = GRNET_AB(WIDE_DBG, 0);
-#endif
-    // (64 -> 64 on the ring kernel -- 7-row bands, two chunks: the second streams under the first -- measured 93 us against the band kernel's 79: stays here)
-    if (a.CinPad == 64) return launch_k(conv_bf16_wide_band<64, 64, 56, 14>, dim3(a.N * WideGeom<64, 64, 56, 14>::NB), dim3(512), WideGeom<64, 64, 56, 14>::LDS, s, a);
-    if (a.CoutPad == 32) return launch_k(conv_bf16_wide_ring<32, 56, 8>, dim3(a.N * RingGeom<32, 56, 8>::NB), dim3(512), RingGeom<32, 56, 8>::LDS, s, a);
-    const int ncb = a.CoutPad / 128;
-    // 1 (default): the ring of one-chunk planes; 0: the 128-channel plane refilled between passes (A/B)
-    static const int ring_env = GRNET_AB(BF16_WIDE_RING, 1);
-    if (ring_env && a.CinPad >= 64) {
-        // 256 output channels at 56x56: ONE workgroup for all channels of a 4-row band (eight channel waves, 15 column tiles each) -- the band is fetched once, not once per
-        // 128-channel tile: 6 input rows per 4 output rows instead of 2 x 10 per 8, 5 plane pieces per chunk and wave instead of 7; the tile leaves from the accumulators.
-        // Alone it ties the 128-channel tiles (1 222 / 1 221 us for 480 -> 256, 644 / 647 for 256 -> 256 at 256 frames); in the step 10.49 against 10.51-10.53 ms (two pairs).
-        // GRNET_BF16_WIDE_CT256=0: 128-channel tiles
-        static const int ct256_env = GRNET_AB(BF16_WIDE_CT256, 1);
-        if (ct256_env && a.W == 56 && a.CoutPad == 256)
-            return launch_k(conv_bf16_wide_ring<256, 56, 4, true>, dim3(a.N * RingGeom<256, 56, 4, true>::NB), dim3(512), RingGeom<256, 56, 4, true>::LDS, s, a);
-        // 56x56: 8-row bands (7 per frame, 15 column tiles per wave, 244 registers) measured against 7-row ones (8 per frame): 480 -> 256 1 240 / 1 240 us,
-        // 256 -> 256 648 / 666, 128 -> 128 210 / 216 at 256 frames
-        if (a.W == 56) return launch_k(conv_bf16_wide_ring<128, 56, 8>, dim3(a.N * RingGeom<128, 56, 8>::NB * ncb), dim3(512), RingGeom<128, 56, 8>::LDS, s, a);
-        return launch_k(conv_bf16_wide_ring<128, 28, 14>, dim3(a.N * RingGeom<128, 28, 14>::NB * ncb), dim3(512), RingGeom<128, 28, 14>::LDS, s, a);
-    }
-    if (a.W == 56) return launch_k(conv_bf16_wide_band<128, 128, 56, 7>, dim3(a.N * WideGeom<128, 128, 56, 7>::NB * ncb), dim3(512), WideGeom<128, 128, 56, 7>::LDS, s, a);
-    return launch_k(conv_bf16_wide_band<128, 128, 28, 14>, dim3(a.N * WideGeom<128, 128, 28, 14>::NB * ncb), dim3(512), WideGeom<128, 128, 28, 14>::LDS, s, a);
-}
-
-// Stride-2 band kernel: 3x3, stride 2, even input size, <= 3 fused addends; (input channels per pass, output-channel tile) by the layer's channel counts.
-static int s2_cp(const ConvArgs& a) { return a.CinPad >= 64 ? 64 : 32; }
-static int s2_ct(const ConvArgs& a) { return a.CoutPad >= 128 ? 128 : a.CoutPad; }
-static bool s2_rows_shape(const ConvArgs& a) {                 // the row-walking kernel's shapes (every add view 4-channel aligned: checked by the caller)
-    if (!GRNET_AB(BF16_S2_ROWS, 1)) return false;
-#define GRK_S2R_HAS(ci_, co_, wo_) if (a.CinPad == ci_ && a.Cin == ci_ && a.Cout == co_ && a.Wo == wo_) return true;
-    GRK_S2R_SHAPES(GRK_S2R_HAS)
-#undef GRK_S2R_HAS
-    return false;
-}
-bool conv_bf16_s2_eligible(const ConvArgs& a) {
-    if (a.ks != 3 || a.stride != 2 || a.H != a.W || a.Ho != a.Wo || a.H != 2 * a.Ho || a.CinPad % 32 != 0 || a.n_add > kMaxAdd || a.relu_from != 0) return false;
-    if (a.in_ctot % 8 != 0 || a.in_coff % 8 != 0 || a.out_ctot % 8 != 0 || a.out_coff % 8 != 0 || a.Cout % 32 != 0 || a.CoutPad != a.Cout) return false;
-    for (int k = 0; k < a.n_add; ++k)
-        if (a.add_ctot[k] % 4 != 0 || a.add_coff[k] % 4 != 0) return false;
-    if (s2_rows_shape(a)) return true;
-    const int cp = s2_cp(a), ct = s2_ct(a);
-    if (a.CinPad != cp) return false;                          // one pass (layers with more input channels lose to the generic kernel: see GRK_S2_SHAPES)
-#define GRK_S2_HAS(cp_, ct_, wo_, r_) if (cp == cp_ && ct == ct_ && a.Wo == wo_) return true;
-    GRK_S2_SHAPES(GRK_S2_HAS)
-#undef GRK_S2_HAS
-    return false;
-}
-hipError_t launch_conv_bf16_s2(const ConvArgs& a, hipStream_t s) {
-    if (!conv_bf16_s2_eligible(a) || a.N < 1) return hipErrorInvalidValue;
-    if (s2_rows_shape(a)) {
-#define GRK_S2R_GO(ci_, co_, wo_) if (a.CinPad == ci_ && a.Cout == co_ && a.Wo == wo_) return launch_s2_rows<ci_, co_, wo_>(a, s);
-        GRK_S2R_SHAPES(GRK_S2R_GO)
-#undef GRK_S2R_GO
-    }
-    const int cp = s2_cp(a), ct = s2_ct(a);
-#define GRK_S2_GO(cp_, ct_, wo_, r_) if (cp == cp_ && ct == ct_ && a.Wo == wo_) return launch_s2<cp_, ct_, wo_, r_>(a, s);
-    GRK_S2_SHAPES(GRK_S2_GO)
-#undef GRK_S2_GO
-    return hipErrorInvalidValue;
 }
 
 }  // namespace grk

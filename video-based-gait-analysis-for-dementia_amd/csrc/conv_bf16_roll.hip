@@ -20,34 +20,16 @@
 // k order = input-channel chunk (32) outer, tap inner -- the order of the launch-per-convolution kernels, so a fused launch differs from them by
 // fp32 summation order inside a k-step at most (tests: equal to the fp32 oracle on bf16-rounded operands with bf16-rounded intermediates).
 #include "kernels.h"
+#include "device.h"
 
 #include <cstdio>
 #include <type_traits>
 
 namespace grk {
 
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
-
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_r __attribute__((ext_vector_type(2)));
-typedef float f32x2_r __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2_r(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_r{lo, hi}, bf16x2_r)); }
-__device__ __forceinline__ float relu_r(float x) { const int i = __float_as_int(x); return __int_as_float(i > 0 ? i : 0); }
-__device__ __forceinline__ float bflo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bfhi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-__device__ __forceinline__ u32x2 pack4_relu(const f32x4 v) { return u32x2{pack2_r(relu_r(v[0]), relu_r(v[1])), pack2_r(relu_r(v[2]), relu_r(v[3]))}; }
-__device__ __forceinline__ void lds_sync() {                  // every wave's LDS operations so far are done; global loads and stores stay in flight
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
+__device__ __forceinline__ u32x2 pack4_relu(const f32x4 v) { return u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))}; }
 
 constexpr int kW2Bytes = 2 * 9 * 64 * 64;                     // the 64 -> 64 3x3 weights: [chunk 2][tap 9][cout 64][32 k] bf16, 64-byte rows
 constexpr int kTSB = 160;                                     // slot stride of a 64-channel pixel in LDS: 128 + 32 bytes = 32 x odd (conflict-free b128 reads of 16 consecutive slots)
@@ -164,9 +146,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
     u32x4 nxa[NXU], nxb[NXU];
     auto request = [&](int y, u32x4 (&nx)[NXU]) {               // x row y -> registers
         const u16* rowp = inb + (size_t)(y < 0 ? 0 : y < W ? y : W - 1) * W * a.in_ctot;
-#ifdef GRNET_ABLATION
-        if (a.dbg & 16) return;
-#endif
+        if (abl::bit(a.dbg, 16)) return;
 #pragma unroll
         for (int i = 0; i < NXU; ++i) nx[i] = *reinterpret_cast<const u32x4*>(rowp + xg[i]);
     };
@@ -199,7 +179,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
         for (int T = 0; T < 4; ++T) res_cur[bi][T] = res_nxt[bi][T] = u32x2{0u, 0u};
-    lds_sync();
+    lds_barrier();
 
     auto step = [&](auto out_tag, int y, u32x4 (&nx)[NXU]) {
         constexpr bool OUT = decltype(out_tag)::value;          // the step finishes output row y - 1
@@ -212,14 +192,12 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
                 if (i * 512 + tid < UPR) *reinterpret_cast<u32x4*>(xr + xl[i]) = nx[i];      // (a thread past the row's end holds a second copy of a tail unit: loaded, not written)
         }
         request(y + 2, nx);
-        lds_sync();
+        lds_barrier();
         // ---- 2. reduce -> ring row y (a zero row for y = 56), residual capture
         unsigned char* trow = tring + ((y + 3) % 3) * (TSLOTS * kTSB);
         if (has_x) {
             f32x4 acc[2] = {b1v, b1v};
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 1))
-#endif
+            if (!abl::bit(a.dbg, 1))
 #pragma unroll
             for (int c = 0; c < KC1; ++c)
 #pragma unroll
@@ -241,7 +219,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
         } else if (tid < W * 8) {
             *reinterpret_cast<u32x4*>(trow + ((tid >> 3) + 1) * kTSB + (tid & 7) * 16) = u32x4{0u, 0u, 0u, 0u};
         }
-        lds_sync();
+        lds_barrier();
         if constexpr (OUT) {                                    // output row y - 1 (rows s0 .. s1 - 1)
             const int yo = y - 1;
             // ---- 3. 3x3 -> u
@@ -250,9 +228,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) rb[dy] = tring + ((yo - 1 + dy + 3) % 3) * (TSLOTS * kTSB) + l15 * kTSB + lq * 16;
                 f32x4 acc[2] = {b2v, b2v};
-#ifdef GRNET_ABLATION
-                if (!(a.dbg & 2))
-#endif
+                if (!abl::bit(a.dbg, 2))
                 conv3x3_row(acc, rb, wl, tp, [](int dx) { return dx * kTSB; }, 16 * kTSB);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
@@ -260,7 +236,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
                     if (px < W) *reinterpret_cast<u32x2*>(ubuf + px * kTSB + (blk * 16 + lq * 4) * 2) = pack4_relu(acc[i]);
                 }
             }
-            lds_sync();
+            lds_barrier();
             // ---- 4. expand (+ residual) -> staging
             {
                 f32x4 acc[2][4];
@@ -269,9 +245,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
 #pragma unroll
                     for (int T = 0; T < 4; ++T) acc[bi][T] = b3v[bi];
                 const unsigned char* xo = xrow + (yo & 1) * XROW;     // FIRST: x row yo
-#ifdef GRNET_ABLATION
-                if (!(a.dbg & 4))
-#endif
+                if (!abl::bit(a.dbg, 4))
 #pragma unroll
                 for (int c = 0; c < KC3; ++c)
 #pragma unroll
@@ -288,17 +262,15 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
                         f32x4 v = acc[bi][T];
                         if (!FIRST) {
                             const u32x2 r = res_cur[bi][T];
-                            v[0] += bflo(r[0]); v[1] += bfhi(r[0]); v[2] += bflo(r[1]); v[3] += bfhi(r[1]);
+                            v[0] += bf_lo(r[0]); v[1] += bf_hi(r[0]); v[2] += bf_lo(r[1]); v[3] += bf_hi(r[1]);
                         }
                         if (16 * T + l15 < W) *reinterpret_cast<u32x2*>(ostage + (16 * T + l15) * OSB + ((2 * wave + bi) * 16 + lq * 4) * 2) = pack4_relu(v);
                     }
             }
-            lds_sync();
+            lds_barrier();
             // ---- 5. staging -> HBM: unit i of the staging is unit i of the x row this thread writes in the next step's phase 1 (FIRST: a buffer of its own, next
             // written three barriers on) -- no barrier in between
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 8))
-#endif
+            if (!abl::bit(a.dbg, 8))
             {
                 u16* rowp = outb + (size_t)yo * W * a.out_ctot;
 #pragma unroll
@@ -337,16 +309,10 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck(const RollArgs a) {
 // Steps, barriers and arithmetic are those of the kernel above.
 #ifdef GRNET_ABLATION
 __device__ unsigned long long g_roll_phase[8];                 // diagnostic builds, GRNET_ROLL_PHASES: clock ticks of wave 0 of every workgroup per phase of conv_bf16_bneck_dma
-#define ROLL_TICK(k) do { if (a.dbg & 32) { const unsigned long long t_ = __builtin_readcyclecounter(); tacc_[k] += t_ - tick_; tick_ = t_; } } while (0)
-#else
-#define ROLL_TICK(k) do { } while (0)
 #endif
 constexpr int kXRowB = 56 * 512;
 constexpr int kBneckDmaLds = 9 * 64 * 64 + 3 * 58 * kTSB + 56 * kTSB + 3 * kXRowB + 384 * 4;      // 161 216
 static_assert(kBneckDmaLds <= 160 * 1024, "LDS");
-__device__ __forceinline__ void dma16_row(unsigned off, const void* base, unsigned lds) {      // lane l's 16 bytes at base + off land at lds + 16 l; one wait state between the M0 write and the DMA
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
 
 __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
     constexpr int W = 56, TSLOTS = 58, TROW = TSLOTS * kTSB;
@@ -373,12 +339,10 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
     auto request = [&](int y) {                                 // x row y -> buffer (y + 2) & 1 (rows outside the frame: clamped, landed and never used -- the counts stay the same)
         const u16* rowp = inb + (size_t)(y < 0 ? 0 : y < W ? y : W - 1) * W * a.in_ctot;
         const unsigned dst = lds0 + (unsigned)(xb - lds) + ((y + 2) & 1) * kXRowB + wave * 1024;
-#ifdef GRNET_ABLATION
-        if (a.dbg & 16) return;
-#endif
+        if (abl::bit(a.dbg, 16)) return;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (j < ND) dma16_row(doff0 + j * dstep, rowp, dst + j * 8192);
+            if (j < ND) dma16_uniform(doff0 + j * dstep, rowp, dst + j * 8192);
     };
     request(s0 - 1);
     request(s0);
@@ -422,14 +386,12 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
 #pragma unroll
         for (int T = 0; T < 4; ++T) res_cur[bi][T] = res_nxt[bi][T] = u32x2{0u, 0u};
 
-#ifdef GRNET_ABLATION
-    unsigned long long tick_ = __builtin_readcyclecounter(), tacc_[8] = {};
-#endif
+    abl::Ticks<8> ticks(abl::bit(a.dbg, 32));
     auto step = [&](auto out_tag, auto steady_tag, int y) {
         constexpr bool OUT = decltype(out_tag)::value, STEADY = decltype(steady_tag)::value;
         const bool has_x = y >= 0 && y < W;
         const unsigned char* xr = xb + ((y + 2) & 1) * kXRowB;
-        ROLL_TICK(7);
+        ticks.mark(7);
         // ---- 1. this wave's pieces of row y have landed; everybody's
         if (STEADY) {
             if (wave < 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -437,17 +399,15 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        ROLL_TICK(0);
-        lds_sync();
-        ROLL_TICK(1);
+        ticks.mark(0);
+        lds_barrier();
+        ticks.mark(1);
         // ---- 2. reduce -> ring row y (a zero row outside the frame), residual capture
         unsigned char* trow = tring + ((y + 3) % 3) * TROW;
         if (has_x) {
             const f32x4 b1v = *reinterpret_cast<const f32x4*>(b1p);
             f32x4 acc[2] = {b1v, b1v};
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 1))
-#endif
+            if (!abl::bit(a.dbg, 1))
             {   // the row's fragments in two batches of eight reads, the second requested in front of the first one's MFMAs (left to itself hipcc keeps one or two reads
                 // in flight: 16 LDS latencies in a row were 1 500 of the phase's 2 400 cycles, GRNET_ROLL_PHASES)
                 bf16x8 bt[2][4][2];
@@ -479,10 +439,10 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
         } else if (tid < W * 8) {
             *reinterpret_cast<u32x4*>(trow + ((tid >> 3) + 1) * kTSB + (tid & 7) * 16) = u32x4{0u, 0u, 0u, 0u};
         }
-        lds_sync();
-        ROLL_TICK(2);
+        lds_barrier();
+        ticks.mark(2);
         request(y + 2);                                         // the buffer of row y is free
-        ROLL_TICK(3);
+        ticks.mark(3);
         if constexpr (OUT) {
             const int yo = y - 1;
             // ---- 3. 3x3 -> u: chunk 0's weights from LDS, chunk 1's from registers
@@ -492,9 +452,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
                 for (int dy = 0; dy < 3; ++dy) rb[dy] = tring + ((yo - 1 + dy + 3) % 3) * TROW + l15 * kTSB + lq * 16;
                 const f32x4 b2v = *reinterpret_cast<const f32x4*>(b1p + 64);
                 f32x4 acc[2] = {b2v, b2v};
-#ifdef GRNET_ABLATION
-                if (!(a.dbg & 2))
-#endif
+                if (!abl::bit(a.dbg, 2))
                 {   // six groups (chunk, tap row) of 3 tap columns x 2 tiles; the next group's fragments are requested in front of this group's MFMAs
                     bf16x8 bfr[2][3][2], afl[2][3];
                     auto fetch = [&](int g, int slot) {
@@ -524,8 +482,8 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
                     if (px < W) *reinterpret_cast<u32x2*>(ubuf + px * kTSB + (blk * 16 + lq * 4) * 2) = pack4_relu(acc[i]);
                 }
             }
-            lds_sync();
-            ROLL_TICK(4);
+            lds_barrier();
+            ticks.mark(4);
             // ---- 4. expand + residual -> staging row
             {
                 f32x4 acc[2][4];
@@ -533,9 +491,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
                 for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
                     for (int T = 0; T < 4; ++T) acc[bi][T] = *reinterpret_cast<const f32x4*>(b3p + bi * 16);
-#ifdef GRNET_ABLATION
-                if (!(a.dbg & 4))
-#endif
+                if (!abl::bit(a.dbg, 4))
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -550,23 +506,21 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
                     for (int T = 0; T < 4; ++T) {
                         f32x4 v = acc[bi][T];
                         const u32x2 r = res_cur[bi][T];
-                        v[0] += bflo(r[0]); v[1] += bfhi(r[0]); v[2] += bflo(r[1]); v[3] += bfhi(r[1]);
+                        v[0] += bf_lo(r[0]); v[1] += bf_hi(r[0]); v[2] += bf_lo(r[1]); v[3] += bf_hi(r[1]);
                         if (16 * T + l15 < W) *reinterpret_cast<u32x2*>(ost + xat(16 * T + l15, (2 * wave + bi) * 2 + (lq >> 1)) + (lq & 1) * 8) = pack4_relu(v);
                     }
             }
-            lds_sync();
-            ROLL_TICK(5);
+            lds_barrier();
+            ticks.mark(5);
             // ---- 5. staging row -> HBM (the staging is next written three barriers on)
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 8))
-#endif
+            if (!abl::bit(a.dbg, 8))
             {
                 u16* rowp = outb + (size_t)yo * W * a.out_ctot;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (i < ND) *reinterpret_cast<u32x4*>(rowp + sg0 + i * sgstep) = *reinterpret_cast<const u32x4*>(ost + (i * 512 + tid) * 16);
             }
-            ROLL_TICK(6);
+            ticks.mark(6);
         }
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi)
@@ -580,10 +534,7 @@ __global__ __launch_bounds__(512) void conv_bf16_bneck_dma(const RollArgs a) {
 #pragma unroll 1
     for (int y = s0 + 3; y <= s1; ++y) step(std::true_type{}, std::true_type{}, y);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (the clamped pieces of the rows past the segment)
-#ifdef GRNET_ABLATION
-    if ((a.dbg & 32) && tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_roll_phase[k], tacc_[k]);
-#endif
+    ticks.flush(GRK_ABL_COUNTERS(g_roll_phase), tid == 0);
 }
 
 // ---- the stem pair.  conv1 as conv_bf16_stem computes it (K = (channel, tap) flattened to ONE 32-wide k-step, B gathered from the fp32 frame and rounded
@@ -632,9 +583,7 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
     // just before: gathers, stores and MFMA phases added up exactly, tools/roll_micro.py).
     auto gather = [&](int y1r) {
         const int y1 = y1r < 0 ? 0 : y1r > 111 ? 111 : y1r;
-#ifdef GRNET_ABLATION
-        if (a.dbg & 16) return;
-#endif
+        if (abl::bit(a.dbg, 16)) return;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int x = 16 * (ct0 + (i < nct ? i : 0)) + l15;
@@ -653,7 +602,7 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
     const int blk = wave & 3, tp = wave >> 2;
     const f32x4 b2v = *reinterpret_cast<const f32x4*>(a.b2 + blk * 16 + lq * 4);
     const unsigned char* wl = w2l + (blk * 16 + l15) * 64 + ((lq ^ (((l15 >> 3) & 1) << 1)) * 16);
-    lds_sync();
+    lds_barrier();
 
     auto conv1_rows = [&](int Y) {                               // conv1 rows 2Y, 2Y + 1 -> ring slots (row + 3) % 3 (rows above the frame: nothing is written, the slot keeps its zeros)
         const int y1 = 2 * Y + crow;
@@ -662,7 +611,7 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (i >= nct) break;
-            const u32x4 bp = {pack2_r(g[i][0], g[i][1]), pack2_r(g[i][2], g[i][3]), pack2_r(g[i][4], g[i][5]), pack2_r(g[i][6], g[i][7])};
+            const u32x4 bp = {pack2(g[i][0], g[i][1]), pack2(g[i][2], g[i][3]), pack2(g[i][4], g[i][5]), pack2(g[i][6], g[i][7])};
             const bf16x8 b = __builtin_bit_cast(bf16x8, bp);
             const int x1 = 16 * (ct0 + i) + l15;                 // conv1 column: even -> even plane at x1 / 2, odd -> odd plane at (x1 + 1) / 2
             unsigned char* dst = row + (((x1 & 1) ? kStemPlane + (x1 + 1) / 2 : x1 / 2)) * kTSB + lq * 8;
@@ -674,14 +623,14 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
         }
     };
     conv1_rows(s0 - 1);
-    lds_sync();
+    lds_barrier();
     gather(2 * s0 + crow);
-    lds_sync();
+    lds_barrier();
     const int sl = tid >> 3, sp = tid & 7;                        // the thread's unit of an output row (56 pixels x 8 units of 16 bytes: threads 0 .. 447)
 #pragma unroll 1
     for (int Y = s0; Y < s1; ++Y) {
         conv1_rows(Y);
-        lds_sync();
+        lds_barrier();
         gather(2 * (Y + 1) + crow);                              // in flight under the 3x3 and the next barrier
         {
             // ---- conv2 row Y: tap row dy = conv1 row 2Y + dy - 1
@@ -689,9 +638,7 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) rb[dy] = ring + ((2 * Y + dy - 1 + 3) % 3) * (kStemRowSlots * kTSB) + l15 * kTSB + lq * 16;
             f32x4 acc[2] = {b2v, b2v};
-#ifdef GRNET_ABLATION
-            if (!(a.dbg & 2))
-#endif
+            if (!abl::bit(a.dbg, 2))
             conv3x3_row(acc, rb, wl, tp, [](int dx) { return dx == 1 ? 0 : (kStemPlane + (dx >> 1)) * kTSB; }, 16 * kTSB);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -699,10 +646,8 @@ __global__ __launch_bounds__(512) void conv_bf16_stem_pair(const RollArgs a) {
                 if (px < WO) *reinterpret_cast<u32x2*>(ostage + px * kTSB + (blk * 16 + lq * 4) * 2) = pack4_relu(acc[i]);
             }
         }
-        lds_sync();
-#ifdef GRNET_ABLATION
-        if (!(a.dbg & 8))
-#endif
+        lds_barrier();
+        if (!abl::bit(a.dbg, 8))
         if (wave < 7)                                             // (wave-uniform: 448 threads move the row; the next step's barrier orders these reads before the staging is rewritten)
             *reinterpret_cast<u32x4*>(outb + (size_t)(Y * WO + sl) * a.out_ctot + sp * 8) = *reinterpret_cast<const u32x4*>(ostage + sl * kTSB + sp * 16);
     }
@@ -748,12 +693,9 @@ hipError_t launch_conv_bf16_bneck(const void* in, int in_ctot, int in_coff, void
 #ifdef GRNET_ABLATION
         if (GRNET_AB_SET(ROLL_PHASES)) {
             a.dbg |= 32;
-            unsigned long long z[8] = {};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_roll_phase), z, sizeof(z));
             hipError_t e = launch_k(conv_bf16_bneck_dma, dim3(N * a.S), dim3(512), (size_t)kBneckDmaLds, s, a);
-            (void)hipStreamSynchronize(s);
             unsigned long long h[8] = {};
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_roll_phase), sizeof(h));
+            abl::take_counters(HIP_SYMBOL(g_roll_phase), h, s);
             const double wg = (double)N * a.S * 57.0 / a.S;      // per workgroup and row step (approximately: the warm-up steps have no output phases)
             fprintf(stderr, "[roll phases] ticks per step: wait-dma %.0f  barrier1 %.0f  reduce+barrier %.0f  request %.0f  3x3+barrier %.0f  expand+barrier %.0f  store %.0f  tail %.0f\n",
                     h[0] / wg, h[1] / wg, h[2] / wg, h[3] / wg, h[4] / wg, h[5] / wg, h[6] / wg, h[7] / wg);

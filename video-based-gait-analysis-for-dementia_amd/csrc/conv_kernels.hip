@@ -16,34 +16,21 @@
 // + up to 3 addends each optionally nearest-upsampled by 2^shift (the HR fuse layers),
 // ReLU, store into a channel slice of the destination buffer.
 #include "kernels.h"
+#include "device.h"
 
 #include <cstdlib>
 
 namespace grk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Phase-ablation switches of tools/conv_micro.py (skip MFMAs / re-staging / epilogue to see what a launch spends where).
-// They exist only in a diagnostic build (make ABLATION=1); in the product build the conditions fold to false.
-#ifdef GRNET_ABLATION
-#define GRK_DBG(a, bit) (((a).dbg & (bit)) != 0)
-#else
-#define GRK_DBG(a, bit) false
-#endif
+// (abl::bit(a.dbg, n): the phase-ablation switches of tools/conv_micro.py -- skip MFMAs / re-staging / epilogue to see what a launch spends where.
+// They exist only in a diagnostic build (make ABLATION=1); in the product build the conditions fold to false.)
 // Diagnostic build only: shader-clock ticks of the phases of a split-K workgroup, summed over workgroups (wave 0 reports):
 // [0] index math up to the first stage's DMA, [1] wait for it, [2] stage loop, [3] cross-wave reduction, [4] epilogue, [5] workgroups.
+// ([6], [7]: the first tile's share of the epilogue -- bias loads + partial sums, store_tile; [4] is the rest of it.)
 #ifdef GRNET_ABLATION
 __device__ unsigned long long g_phase_f32[8];
 __device__ unsigned long long g_phase_wk[8];    // whole-K: [0] index math up to the first chunk's DMA, [1] more math + wait for it, [2] chunk loop, [3] epilogue, [4] workgroups
-#define GRK_PHASE_WK(i, t0, t1) do { if (threadIdx.x == 0) atomicAdd(&g_phase_wk[i], (t1) - (t0)); } while (0)
-#define GRK_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#define GRK_PHASE(i, t0, t1) do { if (threadIdx.x == 0) atomicAdd(&g_phase_f32[i], (t1) - (t0)); } while (0)
-#else
-#define GRK_TICK(var) do { } while (0)
-#define GRK_PHASE(i, t0, t1) do { } while (0)
 #endif
-#define GRNET_GLOBAL_AS __attribute__((address_space(1)))
-#define GRNET_LDS_AS __attribute__((address_space(3)))
 
 #ifndef GRNET_PLAIN_STAGING
 // LDS-DMA: lane l's 4 (16) bytes land at lds_wave_base + 4*l (16*l); the source is per lane.
@@ -90,9 +77,6 @@ __device__ __forceinline__ bool xcd_block(const ConvArgs& a, int& bx, int& by) {
     bx = first + q;                                      // adjacent tiles share their halo rows in its L2
     return bx < (((x + 1) * a.gx) >> 3);
 }
-// q / d for 0 <= q < 2^20, 0 < d < 2^20 through one fp32 reciprocal-multiply (exact: the +0.5 keeps the quotient of an
-// exact multiple away from the rounding edge); an integer division by a run-time value costs ~20 VALU instructions
-__device__ __forceinline__ int fdiv(int q, float inv_d) { return (int)(((float)q + 0.5f) * inv_d); }
 
 struct EpiCtx { int y0, g0, HoWo, RW, qlimit; float inv_RW, inv_Wo; bool vec_ok, pre0; };
 __device__ __forceinline__ EpiCtx make_epi_ctx(const ConvArgs& a, int y0, int g0) {
@@ -202,7 +186,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_mfma_f32(const ConvArgs a) {
 
     int bx, by;
     if (!xcd_block(a, bx, by)) return;
-    GRK_TICK(t_start);
+    abl::Ticks<5> ticks(true);
     const int ty = bx % a.tiles_y, grp = bx / a.tiles_y;
     const int y0 = ty * a.R, g0 = grp * a.G, co0 = by * TC;
     const int HW = a.H * a.W, RW = a.R * a.Wo, RinWp = a.Rin * a.Wp;
@@ -294,7 +278,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_mfma_f32(const ConvArgs a) {
         for (int cs = 0; cs < CSW; ++cs) acc[ps][cs] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int nchunks = a.CinPad / CK;
-    GRK_TICK(t_issue);
+    ticks.mark(0);
     issue(0, 0);                                          // first chunk in flight while the lane offsets are computed
     const EpiCtx ec = make_epi_ctx(a, y0, g0);
     f32x4 pre[PSW][CSW];
@@ -334,18 +318,13 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_mfma_f32(const ConvArgs a) {
 #pragma unroll
     for (int cs = 0; cs < CSW; ++cs) bbase[cs] = lq * TC + (((wc * CSW + cs) * 16 + l15) ^ ((lq & 1) << 4));
 
-#ifdef GRNET_ABLATION
-    unsigned long long t_first = 0;
-#endif
     for (int ch = 0; ch < nchunks; ++ch) {
         const int buf = ch & 1;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of chunk ch has landed
         __syncthreads();                                     // ... and everybody else's; buf^1 is free
-#ifdef GRNET_ABLATION
-        if (ch == 0) t_first = __builtin_readcyclecounter();
-#endif
-        if (ch + 1 < nchunks && !GRK_DBG(a, 2)) issue(ch + 1, buf ^ 1);
-        if (GRK_DBG(a, 1)) continue;
+        if (ch == 0) ticks.mark(1);
+        if (ch + 1 < nchunks && !abl::bit(a.dbg, 2)) issue(ch + 1, buf ^ 1);
+        if (abl::bit(a.dbg, 1)) continue;
         const float* wi = w_lds + buf * WFLOATS;
         const float* xi = in_lds + buf * CK * a.PSTR;
         // k-steps of the chunk = (tap, channel group of 4); software pipeline: the LDS reads of step s+1
@@ -390,28 +369,21 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_mfma_f32(const ConvArgs a) {
     }
 
     // ---- epilogue.  D: column (lane&15) = cout, rows (lane>>4)*4 + r = 4 consecutive pixels.
-    if (GRK_DBG(a, 4)) return;
-    GRK_TICK(t_loop);
+    if (abl::bit(a.dbg, 4)) return;
+    ticks.mark(2);
 #pragma unroll
     for (int cs = 0; cs < CSW; ++cs) {
         const int co = co0 + (wc * CSW + cs) * 16 + l15;
 #pragma unroll
         for (int ps = 0; ps < PSW; ++ps) {
-            if (GRK_DBG(a, 8) && (ps & 1)) continue;       // ablation: half of the tile stores
-            if (GRK_DBG(a, 16)) { if (acc[ps][cs][0] == 12345.678f) a.out[0] = 1.f; continue; }   // ablation: no stores at all (results kept live)
+            if (abl::bit(a.dbg, 8) && (ps & 1)) continue;       // ablation: half of the tile stores
+            if (abl::bit(a.dbg, 16)) { if (acc[ps][cs][0] == 12345.678f) a.out[0] = 1.f; continue; }   // ablation: no stores at all (results kept live)
             store_tile(a, ec, acc[ps][cs], (wp * PSW + ps) * 16 + lq * 4, co, pre[ps][cs], biasv[cs]);
         }
     }
-#ifdef GRNET_ABLATION
-    {
-        GRK_TICK(t_end);
-        GRK_PHASE_WK(0, t_start, t_issue);
-        GRK_PHASE_WK(1, t_issue, t_first);
-        GRK_PHASE_WK(2, t_first, t_loop);
-        GRK_PHASE_WK(3, t_loop, t_end);
-        if (threadIdx.x == 0) atomicAdd(&g_phase_wk[4], 1ull);
-    }
-#endif
+    ticks.mark(3);
+    ticks.count(4);
+    ticks.flush(GRK_ABL_COUNTERS(g_phase_wk), threadIdx.x == 0);
 }
 
 
@@ -443,7 +415,7 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
     static_assert(!EDGEPTR || (MODE == 1 && KS == 3 && 2 * WPT + 3 <= kEdgeZeros), "edge pointers: rows mode, 3x3");
     const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
-    GRK_TICK(t_start);
+    abl::Ticks<8> ticks(true);
     const int stage_floats = WFL + 4 * a.PSTR + (ZBLOCK ? kEdgeZeros : 0);   // [weights TAPS*4 x TC | input 4 x PSTR | zeros], ONE stage per wave:
     int* tab = reinterpret_cast<int*>(smem + NW * stage_floats);   // the co-resident waves hide the DMA (a second stage per wave
     float* mine = smem + wave * stage_floats;                        // measured no faster), and a fixed buffer keeps LDS addresses loop-invariant
@@ -549,7 +521,7 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
     // One stage per wave at a time: issue -> wait -> MFMAs -> issue the next into the same buffer.
     const int ngroups = a.CinPad / 4;
     const int my_stages = ngroups > wave ? (ngroups - wave + NW - 1) / NW : 0;
-    GRK_TICK(t_issue);
+    ticks.mark(0);
     if (my_stages > 0) issue(wave, 0);
     const EpiCtx ec = make_epi_ctx(a, y0, g0);
     constexpr int MAXT = (NT + NW - 1) / NW;                 // output tiles this wave finishes after the reduction
@@ -643,15 +615,10 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
     }
 #pragma unroll
     for (int cs = 0; cs < CSW; ++cs) brow[cs] = mine + bbase[cs];
-#ifdef GRNET_ABLATION
-    unsigned long long t_first = 0;
-#endif
     for (int i = 0; i < my_stages; ++i) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's stage has landed
-#ifdef GRNET_ABLATION
-        if (i == 0) t_first = __builtin_readcyclecounter();
-#endif
-        if (!GRK_DBG(a, 1)) {
+        if (i == 0) ticks.mark(1);
+        if (!abl::bit(a.dbg, 1)) {
             // software pipeline over the filter taps: the LDS reads of tap t+1 are in flight under the
             // MFMAs of tap t (one exposed LDS latency per stage instead of one per tap)
             // LD = taps prefetched ahead: 2 when a tap is only 4 MFMAs (128 cycles < LDS latency), else 1
@@ -699,11 +666,11 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (i + 1 < my_stages && !GRK_DBG(a, 2)) issue(wave + (i + 1) * NW, 0);          // refill the buffer just consumed
+        if (i + 1 < my_stages && !abl::bit(a.dbg, 2)) issue(wave + (i + 1) * NW, 0);          // refill the buffer just consumed
     }
 
     // ---- cross-wave reduction (fixed order -> deterministic), then the shared epilogue
-    GRK_TICK(t_loop);
+    ticks.mark(2);
     __syncthreads();                                       // every wave is done with its staging buffers
     f32x4* red = reinterpret_cast<f32x4*>(smem);           // [NW][NT][64]
 #pragma unroll
@@ -711,8 +678,8 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
 #pragma unroll
         for (int cs = 0; cs < CSW; ++cs) red[(wave * NT + ps * CSW + cs) * 64 + lane] = acc[ps][cs];
     __syncthreads();
-    if (GRK_DBG(a, 4)) return;
-    GRK_TICK(t_red);
+    if (abl::bit(a.dbg, 4)) return;
+    ticks.mark(3);
 #pragma unroll
     for (int i2 = 0; i2 < MAXT; ++i2) {
         const int t = wave + i2 * NW;
@@ -721,26 +688,13 @@ __device__ __forceinline__ void splitk_body(const ConvArgs& a, const int bx, con
 #pragma unroll
         for (int w = 1; w < NW; ++w) v += red[(w * NT + t) * 64 + lane];
         const int ps = t / CSW, cs = t - ps * CSW;
-#ifdef GRNET_ABLATION
-        const unsigned long long t_v = __builtin_readcyclecounter();
-        if (i2 == 0) GRK_PHASE(6, t_red, t_v);                     // bias loads + partial sums of the first tile
-#endif
+        if (i2 == 0) ticks.mark(6);                                // bias loads + partial sums of the first tile
         store_tile(a, ec, v, ps * 16 + lq * 4, co0 + cs * 16 + l15, pre[i2], biasv[i2]);
-#ifdef GRNET_ABLATION
-        if (i2 == 0) { const unsigned long long t_s = __builtin_readcyclecounter(); GRK_PHASE(7, t_v, t_s); }   // first tile's store_tile
-#endif
+        if (i2 == 0) ticks.mark(7);                                // first tile's store_tile
     }
-#ifdef GRNET_ABLATION
-    {
-        GRK_TICK(t_end);
-        GRK_PHASE(0, t_start, t_issue);
-        GRK_PHASE(1, t_issue, t_first);
-        GRK_PHASE(2, t_first, t_loop);
-        GRK_PHASE(3, t_loop, t_red);
-        GRK_PHASE(4, t_red, t_end);
-        if (threadIdx.x == 0) atomicAdd(&g_phase_f32[5], 1ull);
-    }
-#endif
+    ticks.mark(4);
+    ticks.count(5);
+    ticks.flush(GRK_ABL_COUNTERS(g_phase_f32), threadIdx.x == 0);
 }
 
 template <int MODE, int KS, int S, int PSW, int CSW, int NW, int WPT = 0>
@@ -1025,24 +979,20 @@ hipError_t launch_conv(ConvArgs a, hipStream_t s, int tile_hint) {
 #ifdef GRNET_ABLATION
     static const bool phases = GRNET_AB_SET(F32_PHASES);
     if (phases && e == hipSuccess && best.family == 0) {
-        unsigned long long h[8] = {}, z[8] = {};
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase_wk), sizeof(h));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_phase_wk), z, sizeof(z));
+        unsigned long long h[8] = {};
+        abl::take_counters(HIP_SYMBOL(g_phase_wk), h, s);
         const double n = h[4] ? (double)h[4] : 1.0;
         fprintf(stderr, "[f32 whole-K phases] %d->%d k%d s%d %dx%d N%d tps %d tcs %d wgs %llu: per WG ticks  index math %.0f  first wait %.0f  chunk loop %.0f "
                 "(%d chunks)  epilogue %.0f\n", a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.N, best.tps, best.tcs, h[4], h[0] / n, h[1] / n, h[2] / n,
                 a.CinPad / (a.ks == 1 ? kConvCK1 : kConvCK), h[3] / n);
     }
     if (phases && e == hipSuccess && best.family == 1) {
-        unsigned long long h[8] = {}, z[8] = {};
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase_f32), sizeof(h));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_phase_f32), z, sizeof(z));
+        unsigned long long h[8] = {};
+        abl::take_counters(HIP_SYMBOL(g_phase_f32), h, s);
         const double n = h[5] ? (double)h[5] : 1.0;
         fprintf(stderr, "[f32 split-K phases] %d->%d k%d s%d %dx%d N%d psw %d csw %d nw %d wgs %llu: per WG ticks  index math %.0f  first wait %.0f  "
                 "stage loop %.0f  reduction %.0f  epilogue %.0f (first tile: sums %.0f, store_tile %.0f)\n", a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.N,
-                best.tps, best.tcs, best.nw, h[5], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[6] / n, h[7] / n);
+                best.tps, best.tcs, best.nw, h[5], h[0] / n, h[1] / n, h[2] / n, h[3] / n, (h[4] + h[6] + h[7]) / n, h[6] / n, h[7] / n);
     }
 #endif
     return e;

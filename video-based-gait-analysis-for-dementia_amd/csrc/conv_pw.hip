@@ -13,10 +13,9 @@
 //   D[row = 4 lq + r][col = l15]: four consecutive pixels of one output channel per lane -> bias, residual and ReLU on 16-byte
 //           vectors, one 16-byte store per channel block.  No LDS, no barrier.
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

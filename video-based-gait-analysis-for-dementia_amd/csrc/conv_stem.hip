@@ -9,10 +9,9 @@
 //   B[k = lq][col = l15] = folded weight of channel 16 nt + l15: 28 registers per lane, loaded once per wave (pack_stem_weights);
 //   D[row = 4 lq + r][col = l15]: four consecutive pixels of one output channel per lane -> one 16-byte store per channel block.
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

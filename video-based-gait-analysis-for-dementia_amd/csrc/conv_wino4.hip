@@ -13,22 +13,17 @@
 // with B, 18 LDS writes into V[point][channel][16 tiles]; 72 MFMAs per wave, A fragment = one LDS dword, the 4 B fragments = one
 // 16-byte load straight from L2, requested a chunk ahead.
 #include "kernels.h"
+#include "device.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace grk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define GRNET_LDS_AS __attribute__((address_space(3)))
-
 namespace {
 
 #ifdef GRNET_ABLATION
 __device__ unsigned long long g_w4phase[8];      // diagnostic build, dbg bit 3: ticks summed over workgroups (tools/wino_phases.py)
-#define W4_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define W4_TICK(var) do { } while (0)
 #endif
 
 constexpr int kCK = 8;                       // input channels per chunk
@@ -40,21 +35,6 @@ static_assert(sizeof(float) * 36 * 16 * kMrow <= kLdsB, "the epilogue tile reuse
 
 template <typename T>
 __device__ __forceinline__ void landed(T& x) { asm volatile("" : "+v"(x)); }
-
-// 1-D transforms.  B^T rows 0..2 / 3..5 of F(4,3) (Lavin & Gray):  [4 0 -5 0 1 0] [0 -4 -4 1 1 0] [0 4 -4 -1 1 0] /
-// [0 -2 -1 2 1 0] [0 2 -1 -2 1 0] [0 4 0 -5 0 1]
-__device__ __forceinline__ void bt_lo(const float* d, float& r0, float& r1, float& r2) {
-    const float t1 = fmaf(-4.f, d[2], d[4]), t2 = fmaf(-4.f, d[1], d[3]);
-    r0 = fmaf(4.f, d[0], fmaf(-5.f, d[2], d[4]));
-    r1 = t1 + t2;
-    r2 = t1 - t2;
-}
-__device__ __forceinline__ void bt_hi(const float* d, float& r3, float& r4, float& r5) {
-    const float u1 = d[4] - d[2], u2 = 2.f * (d[3] - d[1]);
-    r3 = u1 + u2;
-    r4 = u1 - u2;
-    r5 = fmaf(4.f, d[1], fmaf(-5.f, d[3], d[5]));
-}
 
 // NB: 16-channel blocks per workgroup: 4, or 2 = HALF a 64-channel block of the same packed weights (the half-size workgroups of a
 // layer's last round, ConvArgs::wsplit)
@@ -182,7 +162,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
 
     const int nchunks = a.CinPad / kCK;
     bfrag bq[NLD];                                       // B fragments of the 18 MFMA groups (PAIR: of the 9 points); each is re-requested for the next chunk behind its group
-    W4_TICK(t_start);
+    abl::Ticks<5> ticks(abl::bit(a.dbg, 8));          // [0] prologue, [1] first transform, [2] chunk loop, [3] epilogue, [4] workgroups
     issue_raw(0);
     if (nchunks > 1) issue_raw(1);
 #pragma unroll
@@ -190,7 +170,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     if constexpr (PAIR) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");   // the raw rows (requested before the weight loads) have landed
     else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
     __syncthreads();
-    W4_TICK(t_first);
+    ticks.mark(0);
     {
         Tf t;
         tf_read(t, raw + rpos);
@@ -198,7 +178,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
         tf_rows(t);
         tf_cols(t, V + vpos);
     }
-    W4_TICK(t_tf0);
+    ticks.mark(1);
     // ---- the chunk loop: three clusters of 24 MFMAs (three points x two k-steps x four channel blocks)
     float av[2][6];
     auto load_a = [&](int buf, int c, int set) {         // A fragments of cluster c: points 3c .. 3c+2 of this wave, both k-steps
@@ -278,7 +258,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     fetch_res(0);                                       // under the last chunk's MFMAs
     chunk((nchunks - 1) & 1, false, 0);
 
-    W4_TICK(t_loop);
+    ticks.mark(2);
     // ---- epilogue: inverse transform A^T M A (A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]), + bias, + residual, ReLU
     float* Mx = smem;                                    // [36 points][16 channels][20]
     for (int nt = 0; nt < NB; ++nt) {
@@ -323,13 +303,9 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
             }
         }
     }
-#ifdef GRNET_ABLATION
-    if ((a.dbg & 8) && tid == 0) {
-        W4_TICK(t_end);
-        atomicAdd(&g_w4phase[0], t_first - t_start); atomicAdd(&g_w4phase[1], t_tf0 - t_first); atomicAdd(&g_w4phase[2], t_loop - t_tf0);
-        atomicAdd(&g_w4phase[3], t_end - t_loop); atomicAdd(&g_w4phase[4], 1ull);
-    }
-#endif
+    ticks.mark(3);
+    ticks.count(4);
+    ticks.flush(GRK_ABL_COUNTERS(g_w4phase), tid == 0);
 }
 
 template <int NB, int WD = 56, int ABL = 0, bool WSPLIT = false>
@@ -728,10 +704,8 @@ hipError_t launch_conv_wino4(ConvArgs a, hipStream_t s, int* n_launches) {
     if (GRNET_AB_SET(W4_PHASES)) {
         a.dbg |= 8;
         const hipError_t e = a.W == 56 ? launch_wino4_w<56>(a, s, f, n_launches) : launch_wino4_w<28>(a, s, f, n_launches);
-        unsigned long long h[8] = {}, z[8] = {};
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(g_w4phase), sizeof(h));
-        hipMemcpyToSymbol(HIP_SYMBOL(g_w4phase), z, sizeof(z));
+        unsigned long long h[8] = {};
+        abl::take_counters(HIP_SYMBOL(g_w4phase), h, s);
         const double n = h[4] ? (double)h[4] : 1.0;
         fprintf(stderr, "[wino4 phases] %d->%d @%d N%d add %d nb %d wgs %llu: per WG ticks  prologue %.0f  first transform %.0f  chunk loop %.0f (%d chunks)  epilogue %.0f\n",
                 a.Cin, a.Cout, a.W, a.N, a.n_add, f.nb, h[4], h[0] / n, h[1] / n, h[2] / n, a.CinPad / kCK, h[3] / n);

@@ -19,30 +19,13 @@
 //     (16 channels x H x W are one contiguous run of the NCHW tensor per image); after one barrier the waves share the read-out:
 //     slot 0 + slot 1 + ... in that order (deterministic), + residual (requested before the inverse transform), ReLU, 16-byte stores.
 #include "kernels.h"
+#include "device.h"
 
 #include <type_traits>
 
 namespace grk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// B^T of F(4,3), rows 0..2 / 3..5 (Lavin & Gray; as in conv_wino4.hip)
-__device__ __forceinline__ void bt_lo(const float* d, float& r0, float& r1, float& r2) {
-    const float t1 = fmaf(-4.f, d[2], d[4]), t2 = fmaf(-4.f, d[1], d[3]);
-    r0 = fmaf(4.f, d[0], fmaf(-5.f, d[2], d[4]));
-    r1 = t1 + t2;
-    r2 = t1 - t2;
-}
-__device__ __forceinline__ void bt_hi(const float* d, float& r3, float& r4, float& r5) {
-    const float u1 = d[4] - d[2], u2 = 2.f * (d[3] - d[1]);
-    r3 = u1 + u2;
-    r4 = u1 - u2;
-    r5 = fmaf(4.f, d[1], fmaf(-5.f, d[3], d[5]));
-}
 
 template <int WD, int KS>
 struct GeoS {

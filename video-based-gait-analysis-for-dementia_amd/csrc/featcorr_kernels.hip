@@ -14,10 +14,9 @@
 //   out      = y + x                                                                         :150
 // Everything is fp32 byte work except the 1536 -> 3072 layer, which runs on the fp32 matrix cores (gemm_nt_bias_f32).
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
-
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
 
 // cam (M,3) [s,tx,ty], bbox (M,4) [cx,cy,w,h], cimg (M,2) -> cparams (M,3)
 __global__ __launch_bounds__(256) void gait_cparams_kernel(const float* __restrict__ cam, int cam_ld, const float* __restrict__ bbox,

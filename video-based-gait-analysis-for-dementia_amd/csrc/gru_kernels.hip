@@ -7,15 +7,11 @@
 //   4. layer 1 on concat(fwd,bwd) of layer 0 (steps 2-3 again)
 //   5. heads: speed/step MLPs on the final hidden states, phase MLP + tanh on the layer-1 outputs
 #include "kernels.h"
+#include "device.h"
 
 #include <cstdlib>
 
 namespace grk {
-
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // C[M][N] = A[M][K] . B[N][K]^T + bias[N]   (row-major, K contiguous, K % 4 == 0, 16-byte aligned rows)
 // 64x64 tile, K-chunk 32, 4 waves as 2x2, each 2x2 MFMA 16x16x4 tiles.  LDS row stride 34 floats:
@@ -334,7 +330,6 @@ __global__ __launch_bounds__(512) void gru_recurrent_split_kernel(const float* _
 //  * FAST: sigmoid as v_rcp(1 + v_exp(-x)), tanh as 2 sigmoid(2x) - 1 (1 ulp instructions; |error| < 3e-7 per gate) instead of expf /
 //    division / tanhf: 0.4 us of the step's serial tail.
 // Same arithmetic per element otherwise, except for the order of the 300-term sums (quarters, even/odd columns).
-typedef float f32x2v __attribute__((ext_vector_type(2)));
 constexpr int kGruQuadCols = 76, kGruWaveUnits = 5;              // 4 x 76 = 304 columns; 8 waves x 5 = 40 >= 38 units
 template <bool FAST>
 __device__ __forceinline__ float gru_sigmoid(float x) {
@@ -376,7 +371,7 @@ __global__ __launch_bounds__(512) void gru_recurrent_rows_kernel(const float* __
     const int j = wave * kGruWaveUnits + ul;                     // unit of this lane within the slice
     const bool row_ok = q < 3 * kGruWaveUnits && j < nu;
     const bool owner = row_ok && gate == 0 && cq == 0;           // applies the gate equations for unit u0 + j
-    f32x2v W[kGruQuadCols / 2];
+    f32x2 W[kGruQuadCols / 2];
 #pragma unroll
     for (int i = 0; i < kGruQuadCols / 4; ++i)
 #pragma unroll
@@ -422,12 +417,12 @@ __global__ __launch_bounds__(512) void gru_recurrent_rows_kernel(const float* __
             h[step & 1][tid] = arrived ? __uint_as_float((unsigned)v) : __builtin_nanf("");
         }
         __syncthreads();
-        f32x2v acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
+        f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < kGruQuadCols / 4; ++i) {
             const f32x4 hv = *reinterpret_cast<const f32x4*>(hb + 16 * i + 4 * cq);
-            acc0 = __builtin_elementwise_fma(W[2 * i], f32x2v{hv[0], hv[1]}, acc0);
-            acc1 = __builtin_elementwise_fma(W[2 * i + 1], f32x2v{hv[2], hv[3]}, acc1);
+            acc0 = __builtin_elementwise_fma(W[2 * i], f32x2{hv[0], hv[1]}, acc0);
+            acc1 = __builtin_elementwise_fma(W[2 * i + 1], f32x2{hv[2], hv[3]}, acc1);
         }
         float sum = (acc0[0] + acc1[0]) + (acc0[1] + acc1[1]);
         sum += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sum), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]

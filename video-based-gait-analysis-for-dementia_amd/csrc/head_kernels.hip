@@ -3,24 +3,9 @@
 // the camera projection.  All of it is HBM/L2-bound byte work (< 0.1 % of the FLOPs):
 // wavefront reductions, coalesced 16-byte accesses, one pass over each tensor.
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
-
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // HR-module fuse output 0: y = relu(x_0 + up2(t_1) + up4(t_2) + up8(t_3)), nearest upsampling

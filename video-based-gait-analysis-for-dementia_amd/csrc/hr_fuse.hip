@@ -16,11 +16,9 @@
 // 16 LW q + LW m + r -- any bijection between rows and pixels is a valid GEMM, and the tiles leave through LDS by pixel index anyway.
 // Waves split the 16-channel N tiles first and K with what is left of the four (C_i = 32: two N tiles x two K halves, reduced in phase 2).
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -235,13 +233,7 @@ hipError_t launch_hr_fuse_up(const FuseUpArgs& a, hipStream_t s) {
 //            before the barrier.
 namespace {
 
-typedef __bf16 bf16x8_f __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4_f __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_f __attribute__((ext_vector_type(2)));
-typedef unsigned short u16_f;
-typedef __bf16 bf16x2_f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack2_f(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2_f)); }
-__device__ __forceinline__ void add8_f(float (&acc)[8], u32x4_f v) {
+__device__ __forceinline__ void add8_f(float (&acc)[8], u32x4 v) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) { acc[2 * k] += __uint_as_float(v[k] << 16); acc[2 * k + 1] += __uint_as_float(v[k] & 0xffff0000u); }
 }
@@ -263,35 +255,35 @@ template <int NB, int I> struct TOffB<NB, I, 0> { static constexpr int v = 0; };
 
 // tiles t0, t0 + 4, ... of source S for this wave (t0 = the wave's first tile of this source, continuing the round-robin over all sources)
 template <int NB, int I, int S>
-__device__ __forceinline__ void src_tiles_bf16(const FuseUpSrc& src, int n, int band, int lane, int first, u16_f* T) {
+__device__ __forceinline__ void src_tiles_bf16(const FuseUpSrc& src, int n, int band, int lane, int first, u16* T) {
     typedef SrcGeomB<NB, I, S> Q;
     typedef OutGeomB<NB, I> G;
     const int l15 = lane & 15, lq = lane >> 4;
-    const u16_f* xb = reinterpret_cast<const u16_f*>(src.x) + (size_t)n * Q::WJ * Q::WJ * src.ctot + src.coff + (size_t)band * Q::PJ * src.ctot;
-    const u16_f* wb = reinterpret_cast<const u16_f*>(src.w);
-    u16_f* Ts = T + TOffB<NB, I, S>::v;
+    const u16* xb = reinterpret_cast<const u16*>(src.x) + (size_t)n * Q::WJ * Q::WJ * src.ctot + src.coff + (size_t)band * Q::PJ * src.ctot;
+    const u16* wb = reinterpret_cast<const u16*>(src.w);
+    u16* Ts = T + TOffB<NB, I, S>::v;
 #pragma unroll
     for (int t = 0; t < (Q::TILES + 3) / 4; ++t) {
         const int tile = first + 4 * t;
         if (tile >= Q::TILES) break;                           // wave-uniform
         const int pt = tile / G::NCB, cb = tile - pt * G::NCB, px = pt * 16 + l15;
-        const u16_f* xp = xb + (size_t)(px < Q::PJ ? px : 0) * src.ctot + lq * 8;      // columns past the band re-read pixel 0 and are never stored
-        const u16_f* wp = wb + ((size_t)cb * 16 + l15) * 32 + lq * 8;
-        bf16x8_f bq[Q::NK], aq[Q::NK];
+        const u16* xp = xb + (size_t)(px < Q::PJ ? px : 0) * src.ctot + lq * 8;      // columns past the band re-read pixel 0 and are never stored
+        const u16* wp = wb + ((size_t)cb * 16 + l15) * 32 + lq * 8;
+        bf16x8 bq[Q::NK], aq[Q::NK];
 #pragma unroll
         for (int k = 0; k < Q::NK; ++k) {
-            bq[k] = *reinterpret_cast<const bf16x8_f*>(xp + k * 32);
-            aq[k] = *reinterpret_cast<const bf16x8_f*>(wp + (size_t)k * G::CI * 32);
+            bq[k] = *reinterpret_cast<const bf16x8*>(xp + k * 32);
+            aq[k] = *reinterpret_cast<const bf16x8*>(wp + (size_t)k * G::CI * 32);
         }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < Q::NK; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[k], bq[k], acc, 0, 0, 0);
-        if (px < Q::PJ) *reinterpret_cast<u32x2_f*>(Ts + px * G::CI + cb * 16 + lq * 4) = u32x2_f{pack2_f(acc[0], acc[1]), pack2_f(acc[2], acc[3])};
+        if (px < Q::PJ) *reinterpret_cast<u32x2*>(Ts + px * G::CI + cb * 16 + lq * 4) = u32x2{pack2(acc[0], acc[1]), pack2(acc[2], acc[3])};
     }
 }
 
 template <int NB, int I>
-__device__ __forceinline__ void fuse_up_body_bf16(const FuseUpOut& o, int n, int band, u16_f* T) {
+__device__ __forceinline__ void fuse_up_body_bf16(const FuseUpOut& o, int n, int band, u16* T) {
     typedef OutGeomB<NB, I> G;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // the waves take the tiles of all sources round-robin: tile g of the concatenated list goes to wave g % 4
@@ -309,23 +301,23 @@ __device__ __forceinline__ void fuse_up_body_bf16(const FuseUpOut& o, int n, int
         }
     }
     // phase 2 operands that do not depend on phase 1: requested before the barrier
-    const u16_f* xb = reinterpret_cast<const u16_f*>(o.base) + (size_t)n * G::WI * G::WI * o.base_ctot + o.base_coff;
-    u32x4_f bv[G::NIT], e0[G::NIT], e1[G::NIT];
+    const u16* xb = reinterpret_cast<const u16*>(o.base) + (size_t)n * G::WI * G::WI * o.base_ctot + o.base_coff;
+    u32x4 bv[G::NIT], e0[G::NIT], e1[G::NIT];
 #pragma unroll
     for (int it = 0; it < G::NIT; ++it) {
         const int u = it * 256 + tid, px = u / G::UPP, part = u - px * G::UPP, yl = px / G::WI, x = px - yl * G::WI;
         const size_t pix = (size_t)(band * G::BR + yl) * G::WI + x;
-        bv[it] = e0[it] = e1[it] = u32x4_f{0u, 0u, 0u, 0u};
+        bv[it] = e0[it] = e1[it] = u32x4{0u, 0u, 0u, 0u};
         if (u < G::NU) {
-            bv[it] = *reinterpret_cast<const u32x4_f*>(xb + pix * o.base_ctot + part * 8);
+            bv[it] = *reinterpret_cast<const u32x4*>(xb + pix * o.base_ctot + part * 8);
             if constexpr (I >= 1) {
-                if (o.n_extra >= 1) e0[it] = *reinterpret_cast<const u32x4_f*>(reinterpret_cast<const u16_f*>(o.extra[0]) + ((size_t)n * G::WI * G::WI + pix) * o.extra_ctot[0] + o.extra_coff[0] + part * 8);
-                if constexpr (I >= 2) { if (o.n_extra >= 2) e1[it] = *reinterpret_cast<const u32x4_f*>(reinterpret_cast<const u16_f*>(o.extra[1]) + ((size_t)n * G::WI * G::WI + pix) * o.extra_ctot[1] + o.extra_coff[1] + part * 8); }
+                if (o.n_extra >= 1) e0[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(o.extra[0]) + ((size_t)n * G::WI * G::WI + pix) * o.extra_ctot[0] + o.extra_coff[0] + part * 8);
+                if constexpr (I >= 2) { if (o.n_extra >= 2) e1[it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const u16*>(o.extra[1]) + ((size_t)n * G::WI * G::WI + pix) * o.extra_ctot[1] + o.extra_coff[1] + part * 8); }
             }
         }
     }
     __syncthreads();
-    u16_f* ob = reinterpret_cast<u16_f*>(o.out) + (size_t)n * G::WI * G::WI * o.out_ctot + o.out_coff;
+    u16* ob = reinterpret_cast<u16*>(o.out) + (size_t)n * G::WI * G::WI * o.out_ctot + o.out_coff;
 #pragma unroll
     for (int it = 0; it < G::NIT; ++it) {
         const int u = it * 256 + tid, px = u / G::UPP, part = u - px * G::UPP, yl = px / G::WI, x = px - yl * G::WI;
@@ -335,15 +327,15 @@ __device__ __forceinline__ void fuse_up_body_bf16(const FuseUpOut& o, int n, int
         if constexpr (I >= 1) { add8_f(acc, e0[it]); if constexpr (I >= 2) add8_f(acc, e1[it]); }
         {
             typedef SrcGeomB<NB, I, 0> Q;
-            add8_f(acc, *reinterpret_cast<const u32x4_f*>(T + TOffB<NB, I, 0>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
+            add8_f(acc, *reinterpret_cast<const u32x4*>(T + TOffB<NB, I, 0>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
         }
         if constexpr (G::NSRC >= 2) {
             typedef SrcGeomB<NB, I, 1> Q;
-            add8_f(acc, *reinterpret_cast<const u32x4_f*>(T + TOffB<NB, I, 1>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
+            add8_f(acc, *reinterpret_cast<const u32x4*>(T + TOffB<NB, I, 1>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
         }
         if constexpr (G::NSRC >= 3) {
             typedef SrcGeomB<NB, I, 2> Q;
-            add8_f(acc, *reinterpret_cast<const u32x4_f*>(T + TOffB<NB, I, 2>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
+            add8_f(acc, *reinterpret_cast<const u32x4*>(T + TOffB<NB, I, 2>::v + ((yl >> Q::SH) * Q::WJ + (x >> Q::SH)) * G::CI + part * 8));
         }
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(o.bias + part * 8), b1 = *reinterpret_cast<const f32x4*>(o.bias + part * 8 + 4);
         float v[8];
@@ -353,8 +345,8 @@ __device__ __forceinline__ void fuse_up_body_bf16(const FuseUpOut& o, int n, int
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
         }
-        *reinterpret_cast<u32x4_f*>(ob + ((size_t)(band * G::BR + yl) * G::WI + x) * o.out_ctot + part * 8) =
-            u32x4_f{pack2_f(v[0], v[1]), pack2_f(v[2], v[3]), pack2_f(v[4], v[5]), pack2_f(v[6], v[7])};
+        *reinterpret_cast<u32x4*>(ob + ((size_t)(band * G::BR + yl) * G::WI + x) * o.out_ctot + part * 8) =
+            u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
     }
 }
 
@@ -368,7 +360,7 @@ template <int NB> constexpr int lds_elems_b_max() {
 
 template <int NB>
 __global__ __launch_bounds__(256) void hr_fuse_up_bf16(const FuseUpArgs a) {
-    __shared__ __align__(16) u16_f T[lds_elems_b_max<NB>()];
+    __shared__ __align__(16) u16 T[lds_elems_b_max<NB>()];
     const int per = a.N * 7, i = a.only >= 0 ? a.only : blockIdx.x / per, rem = a.only >= 0 ? blockIdx.x : blockIdx.x - i * per, n = rem / 7, band = rem - n * 7;
     if (i == 0) fuse_up_body_bf16<NB, 0>(a.o[0], n, band, T);
     if constexpr (NB >= 3) { if (i == 1) fuse_up_body_bf16<NB, 1>(a.o[1], n, band, T); }

@@ -11,12 +11,11 @@
 // whatever the number of frames in the call and wherever the frame sits in it: bit-identical across call sizes, no atomics.
 // The table is read once per frame chunk (blockIdx.y, at most kJregChunks per call), not once per frame.
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kVerts = 6890, kFrameFloats = kVerts * 3;
 constexpr int kPassFrames = 16, kPassCols = kPassFrames * 3;     // 48 columns = 3 MFMA column tiles

@@ -34,6 +34,9 @@
 #define GRNET_AB_STR(name) (static_cast<const char*>(nullptr))
 #endif
 
+// launchers: pass a failed HIP call's error on to the caller
+#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
 namespace grk {
 
 // One-time work per device (kernel attributes, device queries) that launchers used to cache in plain function-local statics: two host
@@ -385,7 +388,7 @@ hipError_t conv_bf16_init();
 hipError_t launch_conv_bf16(ConvArgs a, hipStream_t s, int tile_hint = 0);     // pointers in `a` address bf16 data (bias fp32)
 // A chain of BasicBlocks of one HR branch in ONE launch, the frame resident in LDS (conv_bf16_chain.hip): convolutions 2k, 2k+1 are conv1 / conv2 of
 // block k (hrnet.py:43-59), every one C -> C, 3x3, stride 1, ReLU; conv2 adds the block's input.  (C, W) in {(64,28), (128,14), (256,7)}: ONE launch;
-// (32,56): one launch per block, 19-row bands of a frame resident (conv_bf16_block_band).
+// (32,56): the whole chain as one pipeline of rows (conv_bf16_chain_pipe), or one launch per block, a workgroup walking the bands of a frame (conv_bf16_block_frame).
 constexpr int kMaxChain = 8;
 struct ChainArgs {
     const void* in; int in_ctot, in_coff;       // NHWC bf16 view (N, W, W, C)
@@ -393,18 +396,20 @@ struct ChainArgs {
     int N, nconv;
     const void* w[kMaxChain];                   // [C/32][9][C][32] bf16, BatchNorm folded
     const float* bias[kMaxChain];               // fp32 [C]
-    void* mid[kMaxChain / 2 - 1];               // (32, 56) only -- one band-resident launch per BasicBlock: the output of block k < nconv/2 - 1
+    void* mid[kMaxChain / 2 - 1];               // (32, 56) only -- one launch per BasicBlock: the output of block k < nconv/2 - 1
     int mid_ctot[kMaxChain / 2 - 1], mid_coff[kMaxChain / 2 - 1];
     int flags = 0;                                   // bit 0 (conv_bf16_block_frame): the block's output through the plane + 16-byte stores instead of straight from the accumulators (A/B)
 };
 int conv_bf16_chain_launches(int c, int w, int nconv);
-hipError_t conv_bf16_chain_init();
+hipError_t conv_bf16_chain_init();             // sets the dynamic LDS of the kernels of conv_bf16_chain.hip, then calls the two below
+hipError_t conv_bf16_wide_init();
+hipError_t conv_bf16_s2_init();
 bool conv_bf16_chain_eligible(int c, int w);
 hipError_t launch_conv_bf16_chain(const ChainArgs& a, int c, int w, hipStream_t s);
-// one wide 3x3 stride-1 convolution with a band of the input resident in LDS (conv_bf16_chain.hip: conv_bf16_wide_band); pointers as launch_conv_bf16
+// one wide 3x3 stride-1 convolution with a band of the input resident in LDS (conv_bf16_wide.hip: conv_bf16_wide_band, conv_bf16_wide_ring); pointers as launch_conv_bf16
 bool conv_bf16_wide_eligible(const ConvArgs& a);
 hipError_t launch_conv_bf16_wide(const ConvArgs& a, hipStream_t s);
-// one 3x3 stride-2 convolution with a band of the input resident in LDS, de-interleaved by row / column parity (conv_bf16_chain.hip: conv_bf16_s2_band)
+// one 3x3 stride-2 convolution with a band of the input resident in LDS, de-interleaved by row / column parity (conv_bf16_s2.hip: conv_bf16_s2_band, conv_bf16_s2_rows)
 bool conv_bf16_s2_eligible(const ConvArgs& a);
 hipError_t launch_conv_bf16_s2(const ConvArgs& a, hipStream_t s);
 hipError_t launch_nchw_f32_to_nhwc_bf16(const float* in, void* out, int N, int C, int H, int W, int Cp, hipStream_t s);

@@ -26,6 +26,7 @@
 // (49 SPIN joints, the 29 spin2 joints, or the 25 kinectv2 joints of those) written directly.  A row is summed by ONE wave: lane l takes
 // entries l, l+64, ... in order, then the xor butterfly -- a fixed order per frame, whatever the call size; no atomics.
 #include "kernels.h"
+#include "device.h"
 
 namespace grk {
 namespace {
@@ -35,11 +36,6 @@ constexpr int kBlockFloats = kOneEuroBlock * kCh;              // 2304
 constexpr int kUnits = kBlockFloats / 256;                     // floats per thread per block (9)
 static_assert(kBlockFloats % 256 == 0, "a block must be a whole number of floats per thread");
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // one_euro_filter.py:27-46 with t_e = 1: every line one float32 operation of the reference
 __device__ __forceinline__ float one_euro_step(float x, float& x_prev, float& dx_prev, const OneEuroCoef& c) {
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(256) void smpl_joints54_kernel(const float* __restr
             const float w = t.extra_w[k];
             a0 += w * vn[v * 3]; a1 += w * vn[v * 3 + 1]; a2 += w * vn[v * 3 + 2];
         }
-        a0 = wave_sum64(a0); a1 = wave_sum64(a1); a2 = wave_sum64(a2);
+        a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
         if (lane == 0) { sj[45 + r][0] = a0; sj[45 + r][1] = a1; sj[45 + r][2] = a2; }
     }
     __syncthreads();

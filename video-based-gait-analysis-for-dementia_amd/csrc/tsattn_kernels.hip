@@ -12,13 +12,12 @@
 //   6. X1 = LN1(X + Y);  out = LN2(JWFF(X1) + X1)   LN = the reference's own: unbiased std, (std + eps)
 // Everything is fp32; reductions run in a fixed order (deterministic).
 #include "kernels.h"
+#include "device.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace grk {
-
-#define GRK_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
 
 namespace {
 
@@ -95,7 +94,6 @@ constexpr int kFBufFloats = kFK * kFLd + kFK * kFLdV;
 constexpr int kFlashLdsFloats = 2 * kFBufFloats;
 constexpr int kFU = kFK * (kDh / 2), kFLoads = (kFU + 64 * kFW - 1) / (64 * kFW);       // float2 units of a K (or V) block; per thread
 constexpr int kFlashMaxParts = 8, kFlashMinPartKeys = 128;
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const float* __restrict__ qkv, float* __restrict__ xt, int n, int kparts,
                                                                          float* __restrict__ part_o, float* __restrict__ part_ml) {
     extern __shared__ float sm[];
@@ -104,7 +102,6 @@ __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const flo
     const float* base = qkv + (size_t)bi * n * 3 * kE;
     const int nblk = (n + kFK - 1) / kFK;
     const int kbeg = (int)((long)nblk * part / kparts) * kFK, kend = min(n, (int)((long)nblk * (part + 1) / kparts) * kFK);
-    typedef float f2 __attribute__((ext_vector_type(2)));
     // this lane's part of the wave's Q fragment: query 16 wave + l15, columns 4 j + lq (columns 250, 251: zero; queries past the clip: zero rows, never stored)
     float qf[63];
     {
@@ -125,14 +122,14 @@ __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const flo
     }
     // staging map of a K / V block: unit u = (row, float2 column); rows are 8-byte aligned (a head starts 1000 bytes into its row)
     // a block's K half is requested before the S^T phase and stored behind it, its V half before / behind the O^T phase: eight staging registers, not sixteen
-    f2 reg[kFLoads];
+    f32x2 reg[kFLoads];
     auto request = [&](int k0, int which) {                    // which: 1 keys, 2 values; keys past the clip's end: zero rows (their scores are masked below)
         const float* gb = base + (size_t)k0 * 3 * kE + (which * kH + h) * kDh;
 #pragma unroll
         for (int i = 0; i < kFLoads; ++i) {
             const int u = i * 64 * kFW + tid, r = u / (kDh / 2), c2 = u - r * (kDh / 2);      // (recomputed per block: eight registers matter here)
             const bool ok = u < kFU && k0 + r < n;
-            reg[i] = ok ? *reinterpret_cast<const f2*>(gb + r * 3 * kE + 2 * c2) : f2{0.f, 0.f};
+            reg[i] = ok ? *reinterpret_cast<const f32x2*>(gb + r * 3 * kE + 2 * c2) : f32x2{0.f, 0.f};
         }
     };
     auto deposit = [&](float* buf, int ld) {
@@ -140,13 +137,13 @@ __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const flo
         for (int i = 0; i < kFLoads; ++i)
             if (i * 64 * kFW + tid < kFU) {
                 const int u = i * 64 * kFW + tid, r = u / (kDh / 2), c2 = u - r * (kDh / 2);
-                *reinterpret_cast<f2*>(buf + r * ld + 2 * c2) = reg[i];
+                *reinterpret_cast<f32x2*>(buf + r * ld + 2 * c2) = reg[i];
             }
     };
     float m_run = -INFINITY, l_run = 0.f;                      // of query l15, over this lane's keys (4 lq + r, 16 + 4 lq + r of every block) for l
-    f32x4_t O[16];                                             // O^T: rows = features 16 dt + 4 lq + r, column = query l15
+    f32x4 O[16];                                             // O^T: rows = features 16 dt + 4 lq + r, column = query l15
 #pragma unroll
-    for (int dt = 0; dt < 16; ++dt) O[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < 16; ++dt) O[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     request(kbeg, 1);
     deposit(sm, kFLd);
     request(kbeg, 2);
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const flo
         float* nxt = sm + (cur ^ 1) * kFBufFloats;              // free since the barrier that ended the previous block
         if (more) request(k0 + kFK, 1);                        // the next block's keys: in flight under this block's S^T MFMAs
         // S^T (32 keys x 16 queries) = K Q^T: 63 k-steps of 4 (columns 250, 251 are zeros)
-        f32x4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
         const float* k0row = Ks + l15 * kFLd + lq;
         const float* k1row = Ks + (16 + l15) * kFLd + lq;
 #pragma unroll
@@ -218,18 +215,18 @@ __global__ __launch_bounds__(64 * kFW) void temporal_attn_flash_kernel(const flo
         float* orow = xt + ((size_t)bi * n + q) * kE + h * kDh + 4 * lq;
 #pragma unroll
         for (int dt = 0; dt < 16; ++dt) {
-            if (dt * 16 + 4 * lq < kDh) *reinterpret_cast<f2*>(orow + dt * 16) = f2{O[dt][0] * inv, O[dt][1] * inv};
-            if (dt * 16 + 4 * lq + 2 < kDh) *reinterpret_cast<f2*>(orow + dt * 16 + 2) = f2{O[dt][2] * inv, O[dt][3] * inv};
+            if (dt * 16 + 4 * lq < kDh) *reinterpret_cast<f32x2*>(orow + dt * 16) = f32x2{O[dt][0] * inv, O[dt][1] * inv};
+            if (dt * 16 + 4 * lq + 2 < kDh) *reinterpret_cast<f32x2*>(orow + dt * 16 + 2) = f32x2{O[dt][2] * inv, O[dt][3] * inv};
         }
     } else {                                                   // this part's share: part_o (part, row, 1000) unnormalised, part_ml (part, row, head, {m, l})
         const size_t rows = (size_t)gridDim.z / kparts * n, row = (size_t)bi * n + q;
         float* orow = part_o + ((size_t)part * rows + row) * kE + h * kDh + 4 * lq;
 #pragma unroll
         for (int dt = 0; dt < 16; ++dt) {
-            if (dt * 16 + 4 * lq < kDh) *reinterpret_cast<f2*>(orow + dt * 16) = f2{O[dt][0], O[dt][1]};
-            if (dt * 16 + 4 * lq + 2 < kDh) *reinterpret_cast<f2*>(orow + dt * 16 + 2) = f2{O[dt][2], O[dt][3]};
+            if (dt * 16 + 4 * lq < kDh) *reinterpret_cast<f32x2*>(orow + dt * 16) = f32x2{O[dt][0], O[dt][1]};
+            if (dt * 16 + 4 * lq + 2 < kDh) *reinterpret_cast<f32x2*>(orow + dt * 16 + 2) = f32x2{O[dt][2], O[dt][3]};
         }
-        if (lq == 0) *reinterpret_cast<f2*>(part_ml + (((size_t)part * rows + row) * kH + h) * 2) = f2{m_run, l_run};
+        if (lq == 0) *reinterpret_cast<f32x2*>(part_ml + (((size_t)part * rows + row) * kH + h) * 2) = f32x2{m_run, l_run};
     }
 }
 
