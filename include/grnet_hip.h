@@ -219,6 +219,12 @@ int grnet_set_tuning(grnet_t* h, int n_frames, const char* text);
 
 /* Introspection used by bench.py / tests. */
 int grnet_num_kernel_launches(grnet_t* h);      /* launches enqueued by one grnet_forward */
+/* The cross-lane hand-offs of the handle's lane schedule (csrc/lane_deps.h; what GRNET_TRACE prints as "dependencies:"): counts[GRNET_PLAN_OPS] ops of a forward,
+ * WAITS_ALL / RECORDS_ALL hipStreamWaitEvent calls / recorded events per eager forward if every cross-lane read-after-write edge waited,
+ * WAITS / RECORDS those the schedule keeps (an edge is dropped when its lane is already ordered behind the producer), LANES_ALL / LANES_JOINED
+ * side lanes in use / side lanes the caller's stream still joins at the end.  Indices: the GRNET_PLAN_* enumerators below. */
+enum { GRNET_PLAN_OPS = 0, GRNET_PLAN_WAITS_ALL, GRNET_PLAN_RECORDS_ALL, GRNET_PLAN_WAITS, GRNET_PLAN_RECORDS, GRNET_PLAN_LANES_ALL, GRNET_PLAN_LANES_JOINED, GRNET_PLAN_COUNTS };
+int grnet_plan_counts(grnet_t* h, int64_t* counts /* GRNET_PLAN_COUNTS */);
 int grnet_num_conv_launches(grnet_t* h);        /* convolution launches of one grnet_forward (incl. the grouped fuse-term launch of each HR module) */
 double grnet_conv_flops_per_frame(grnet_t* h);  /* 2 * MACs of all convolutions on the path */
 /* The same with the layers that run a Winograd F(4x4,3x3) kernel counted at the 1/4 of their multiplies it executes (x 256/196 on 14x14 and

@@ -16,6 +16,7 @@ PRECISION_F32, PRECISION_BF16 = 0, 1
 CREATE_COMPACT_ARENA = 1
 JOINT_REGRESSOR_MAX_ROWS = 64
 JOINTS_SPIN49, JOINTS_SPIN2, JOINTS_KINECTV2 = 0, 1, 2
+PLAN_COUNTS = ("ops", "waits_all", "records_all", "waits", "records", "lanes_all", "lanes_joined")     # the GRNET_PLAN_* enumerators, in order
 RASTER_MAX_DIM, RASTER_SLOTS = 4096, 16
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
@@ -56,6 +57,7 @@ EXPORTS = {
     "grnet_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "grnet_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p]),
     "grnet_num_kernel_launches": (C.c_int, [C.c_void_p]),
+    "grnet_plan_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "grnet_num_conv_launches": (C.c_int, [C.c_void_p]),
     "grnet_conv_flops_per_frame": (C.c_double, [C.c_void_p]),
     "grnet_conv_executed_flops_per_frame": (C.c_double, [C.c_void_p]),

@@ -366,6 +366,12 @@ int grnet_set_tuning(grnet_t* h, int n_frames, const char* text) {
 
 int grnet_num_kernel_launches(grnet_t* h) { return h ? h->launches_last : GRNET_EINVAL; }
 
+int grnet_plan_counts(grnet_t* h, int64_t* counts) {
+    if (!h || !counts) return GRNET_EINVAL;
+    std::copy(h->handoff_counts, h->handoff_counts + GRNET_PLAN_COUNTS, counts);
+    return 0;
+}
+
 int grnet_num_conv_launches(grnet_t* h) { return h ? (int)(h->convs.size() + h->fuse_ups.size()) : GRNET_EINVAL; }
 
 double grnet_conv_flops_per_frame(grnet_t* h) {

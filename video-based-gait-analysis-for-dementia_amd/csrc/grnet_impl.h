@@ -237,6 +237,8 @@ struct grnet {
     hipStream_t side[kLanes] = {};      // lanes 1.. (lane 0 = the caller's stream)
     hipEvent_t ev_fork = nullptr, ev_join[kLanes] = {};
     int lanes_used = 1;
+    bool join_lane[kLanes] = {};        // the caller's stream waits for this side lane after the op list: its last op is not already behind lane 0's (analyze_dependencies)
+    int64_t handoff_counts[GRNET_PLAN_COUNTS] = {};   // grnet_plan_counts, indexed by the GRNET_PLAN_* enumerators
     int launches_last = 0;
     int last_n = 16;                   // frame count of the latest forward (grnet_conv_executed_flops_per_frame reports for it)
     std::map<int, int> tuned_mode;     // n -> bit 0: measured per-shape configurations (else cost model), bit 2: eager launches on the lane streams even if graphs are enabled

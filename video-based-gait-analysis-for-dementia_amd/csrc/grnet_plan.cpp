@@ -10,6 +10,7 @@
 // independent of the number of frames in a call, so a plan built once serves any n <= max_frames.  grnet_create_ex(GRNET_CREATE_COMPACT_ARENA)
 // lets tensors whose lifetimes cannot overlap share memory instead (plan_arena: ~13.7 MB / frame, same launches, same bits).
 #include "grnet_impl.h"
+#include "lane_deps.h"
 
 // ------------------------------------------------------------------ plan construction
 View grnet::new_buffer(int c, int h, int w) {
@@ -872,18 +873,36 @@ void grnet::schedule_lanes(std::vector<Op>& list, int n) const {
     list.swap(out);
 }
 
+// Cross-lane read-after-write edges -> Op::waits / Op::record and the lanes the caller's stream joins (lane_deps.h).  Of the edges only
+// those stay that the lane is not ordered behind already: the happens-before order of the launches, and with it every output bit, is that
+// of the full edge set.  The graph recorder reads the same Op::waits, so a captured forward has the reduced edges too.
 void grnet::analyze_dependencies(std::vector<Op>& ops, std::vector<hipEvent_t>& op_events) {
     const std::vector<std::vector<int>> producers = raw_producers(ops);
-    for (int i = 0; i < (int)ops.size(); ++i)
-        for (int w : producers[i])
-            if (ops[w].lane != ops[i].lane) {
-                ops[i].waits.push_back(w);
-                ops[w].record = true;
-            }
-    op_events.assign(ops.size(), nullptr);
-    if (getenv("GRNET_TRACE")) {
-        size_t waits = 0, records = 0;
-        for (const Op& op : ops) { waits += op.waits.size(); records += op.record; }
-        fprintf(stderr, "[grnet] dependencies: %zu ops, %zu cross-lane waits, %zu recorded events\n", ops.size(), waits, records);
+    std::vector<int> lane_of(ops.size());
+    for (size_t i = 0; i < ops.size(); ++i) lane_of[i] = ops[i].lane;
+    static const int reduce_waits = GRNET_AB(WAIT_REDUCE, 1);   // 0: every cross-lane edge waits and every side lane is joined (the schedule until round 6)
+    const lane_deps::Handoffs all = lane_deps::all_cross_lane_waits(lane_of, producers);
+    const lane_deps::Handoffs kept = reduce_waits ? lane_deps::reduce_cross_lane_waits(lane_of, producers) : all;
+    for (size_t i = 0; i < ops.size(); ++i) {
+        ops[i].waits = kept.waits[i];
+        ops[i].record = kept.record[i] != 0;
     }
+    std::fill(join_lane, join_lane + kLanes, false);
+    int joins_all = 0, joins_kept = 0;
+    for (size_t l = 1; l < kept.join.size() && l < (size_t)kLanes; ++l) {
+        join_lane[l] = kept.join[l] != 0;
+        joins_all += all.join[l];
+        joins_kept += kept.join[l];
+    }
+    handoff_counts[GRNET_PLAN_OPS] = (int64_t)ops.size();
+    handoff_counts[GRNET_PLAN_WAITS_ALL] = (int64_t)all.n_waits;
+    handoff_counts[GRNET_PLAN_RECORDS_ALL] = (int64_t)all.n_records;
+    handoff_counts[GRNET_PLAN_WAITS] = (int64_t)kept.n_waits;
+    handoff_counts[GRNET_PLAN_RECORDS] = (int64_t)kept.n_records;
+    handoff_counts[GRNET_PLAN_LANES_ALL] = joins_all;
+    handoff_counts[GRNET_PLAN_LANES_JOINED] = joins_kept;
+    op_events.assign(ops.size(), nullptr);
+    if (getenv("GRNET_TRACE"))
+        fprintf(stderr, "[grnet] dependencies: %zu ops, cross-lane waits %zu -> %zu, recorded events %zu -> %zu, joined lanes %d -> %d\n", ops.size(), all.n_waits,
+                kept.n_waits, all.n_records, kept.n_records, joins_all, joins_kept);
 }

@@ -355,11 +355,14 @@ int grnet::enqueue(const float* frames, int n, const grnet_outputs_t& o, hipStre
     hipStream_t caller = s;
     for (size_t oi = 0; oi < ops.size(); ++oi) {
         const Op& op = ops[oi];
-        if (convs_only && op.kind != Op::CONV && op.kind != Op::FUSEUP) continue;
         s = lane_stream[op.lane];
         const int lane = multi_lane ? op.lane : 0;
         if (lanes)
             for (int w : op.waits) HIP_TRY(hipStreamWaitEvent(s, op_events[w], 0));
+        if (convs_only && op.kind != Op::CONV && op.kind != Op::FUSEUP) {   // a skipped op keeps its place in the order: later ops of its lane rely on its waits
+            if (lanes && op.record) HIP_TRY(hipEventRecord(op_events[oi], s));
+            continue;
+        }
         if (tl_start && !rec) HIP_TRY(hipEventRecord((*tl_start)[oi], s));
         if (rec) {                                            // dependencies: previous node of the lane + cross-lane producers
             rec->deps.clear();
@@ -444,7 +447,8 @@ int grnet::enqueue(const float* frames, int n, const grnet_outputs_t& o, hipStre
     }
     s = caller;
     if (lanes)
-        for (int l = 1; l < lanes_used; ++l) {                // join: the caller's stream continues after every lane
+        for (int l = 1; l < lanes_used; ++l) {                // join: the caller's stream continues after every lane -- a lane whose last op lane 0 is
+            if (!join_lane[l]) continue;                      // already behind through a kept wait needs no event
             HIP_TRY(hipEventRecord(ev_join[l], side[l]));
             HIP_TRY(hipStreamWaitEvent(s, ev_join[l], 0));
         }

@@ -429,6 +429,12 @@ class GRNet:
     def num_conv_launches(self):
         return self._lib.grnet_num_conv_launches(self._h)
 
+    def plan_counts(self):
+        """Cross-lane hand-offs of the lane schedule (grnet_plan_counts): waits / recorded events over all edges and the kept ones, lanes used / joined."""
+        c = (C.c_int64 * len(_lib.PLAN_COUNTS))()
+        _lib.check(self._lib, self._h, self._lib.grnet_plan_counts(self._h, c), "grnet_plan_counts")
+        return dict(zip(_lib.PLAN_COUNTS, (int(v) for v in c)))
+
     def conv_flops_per_frame(self):
         return self._lib.grnet_conv_flops_per_frame(self._h)
 
