@@ -5,7 +5,8 @@ demo.py (argparse :391-456, loop :126-231, pickle :254-267), with the model runn
 Out of scope here (rows 12, 17): ffmpeg video decoding and the YOLOv3+SORT tracker.  So this entry point takes what the
 reference takes once those steps are done: --img_folder (extracted frames) and --tracking_path (joblib {id: {'bbox','frames'}}).
 --mesh_render draws the overlay frames (demo.py:269-385) with the library's own rasteriser: OpenGL's geometry rules, a stated Lambert
-shading that is NOT pyrender's; --wireframe, --display and the matplotlib skeleton view stay refused.
+shading that is NOT pyrender's; with --wireframe the overlay is the meshes' edges as 1-pixel lines (GL's polygon mode GL_LINE,
+by the library's own line rule).  --display, the matplotlib skeleton view and --wireframe without --mesh_render stay refused.
 The reference's --cpu_only (demo.py:46-49,403) is accepted and refused with one line: there is deliberately no CPU fallback.
 """
 import argparse
@@ -69,8 +70,8 @@ def refusal(a):
     """One line for a flag this build parses and refuses, None otherwise."""
     if a.cpu_only:
         return CPU_ONLY_MESSAGE
-    if a.wireframe:
-        return "--wireframe needs OpenGL's line rasterisation, which the library's triangle rasteriser does not have: not implemented"
+    if a.wireframe and not a.mesh_render:
+        return "--wireframe draws the lines of the --mesh_render overlay and needs it: add --mesh_render"
     if a.display:
         return "--display opens a window (cv2.imshow / matplotlib) and is not implemented: the frames of --mesh_render are written to disk"
     return None
@@ -78,7 +79,7 @@ def refusal(a):
 
 def render_overlay(model, pipe, args, results, verts_dev, output_path, stem):
     """demo.py:269-385 with --mesh_render: every image of the folder is written as %06d.png -- the persons of the frame drawn far to near, each
-    in its random HSV colour, over the frame; with --sideview the same meshes turned by 270 degrees about y on black, appended to the right of
+    in its random HSV colour (--wireframe: only the edges of its front faces, as 1-pixel lines), over the frame; with --sideview the same meshes turned by 270 degrees about y on black, appended to the right of
     EVERY frame (the reference widens only frames with a person; frames of one size are what a video needs).  A frame without a person is its
     input.  --save_obj writes the turned mesh per person and frame, with or without --mesh_render."""
     import torch
@@ -114,11 +115,11 @@ def render_overlay(model, pipe, args, results, verts_dev, output_path, stem):
         imgs = torch.from_numpy(np.stack([np.asarray(Image.open(osp.join(args.img_folder, names[i])).convert("RGB")) for i in idxs])).to(model.device)
         verts = torch.stack(rows) if rows else None
         if rows:
-            model.render(imgs, verts, np.stack(cams), cols, where)
+            model.render(imgs, verts, np.stack(cams), cols, where, wireframe=args.wireframe)
         if args.sideview:
             side = torch.zeros_like(imgs)
             if rows:
-                model.render(side, verts, np.stack(cams), cols, where, M=model.SIDE_VIEW)
+                model.render(side, verts, np.stack(cams), cols, where, M=model.SIDE_VIEW, wireframe=args.wireframe)
             imgs = torch.cat([imgs, side], 2)
         out = imgs.cpu().numpy()
         for k, fi in enumerate(idxs):
@@ -232,7 +233,7 @@ def parser():
     p.add_argument("--grnet_batch_size", type=int, default=450)
     p.add_argument("--display", action="store_true", help="parsed, and refused: no window is opened")
     p.add_argument("--mesh_render", action="store_true", help="write the overlay frames (and the video, if ffmpeg is on PATH): the meshes drawn over the input frames on the GPU")
-    p.add_argument("--wireframe", action="store_true", help="parsed, and refused: needs line rasterisation")
+    p.add_argument("--wireframe", action="store_true", help="with --mesh_render: draw the meshes as wireframes (the edges of the front faces, 1-pixel lines) in the main and the side view")
     p.add_argument("--sideview", action="store_true", help="with --mesh_render: append the meshes seen from the side, on black, to the right of every frame")
     p.add_argument("--save_obj", action="store_true", help="write rendered/<person>/<frame>.obj, the mesh as the renderer turns it")
     p.add_argument("--smooth", action="store_true")

@@ -405,14 +405,30 @@ int grnet_load_faces(grnet_t* h, const int32_t* faces_host, int n_faces);
  * a bad size, or on a handle without faces, is still refused. */
 int grnet_render_meshes(grnet_t* h, const float* verts_dev, int n, const float* cams_dev, const float* colours_host, const int32_t* image_index_host,
                         const float* M_host, unsigned char* images_dev, int F, int H, int W, void* stream);
+/* grnet_render_meshes with flags: 0 is grnet_render_meshes exactly; a bit other than those below is GRNET_EINVAL (checked first, with a message).
+ * GRNET_RENDER_WIREFRAME draws demo.py --wireframe (the reference's RenderFlags.ALL_WIREFRAME, GL's polygon mode GL_LINE): nothing is filled; every
+ * face that survives the same cull (doubled area > 0) is drawn as its three edges k = 0: v0->v1, 1: v1->v2, 2: v2->v0, 1-pixel lines without
+ * anti-aliasing, so front faces on the far side show through.  The line rule, on the snapped integers: the edge is x-major if
+ * |dx| >= |dy|, else y-major (dx = dy = 0 draws nothing); P is the major and Q the minor coordinate, the end points are ordered P_lo < P_hi and all
+ * that follows is computed from (lo, hi) alone, so both draws of a shared edge are identical; major index m is covered iff
+ * P_lo <= 256 m + 128 < P_hi; the minor index is n = floor((Q_lo dP + (256 m + 128 - P_lo) dQ) / (256 dP)), exact in int64, dropped outside the
+ * viewport; t = (256 m + 128 - P_lo) / dP, z = z_lo + t (z_hi - z_lo), discarded outside [-1, 1]; GL_LESS as one 64-bit atomicMin on
+ * (ordered(z) << 32) | (3 face + k): at equal depth the lower 3 face + k wins.  Normal and position are interpolated between the two end points
+ * with the same t; shade, store, painter's order, launch groups and workspace are those of the fill. */
+#define GRNET_RENDER_WIREFRAME 1u
+int grnet_render_meshes_ex(grnet_t* h, const float* verts_dev, int n, const float* cams_dev, const float* colours_host, const int32_t* image_index_host,
+                           const float* M_host, unsigned char* images_dev, int F, int H, int W, unsigned flags, void* stream);
 /* The stages alone, on ANY small mesh: V vertices, F faces (faces_host (F,3) int32, validated against V), one camera cam_dev (4).
  * grnet_op_raster_setup: verts_dev (V,3) -> xy_dev (V,2) int32 snapped window coordinates, z_dev (V) z_ndc, normals_dev (V,3) unit vertex normals.
  * grnet_op_raster: xy_dev, z_dev as above -> winner_dev (H,W) int32 in image rows: the winning face per pixel, -1 where uncovered.
- * Both allocate temporaries and synchronise `stream` before they return (test hooks, like grnet_op_conv2d). */
+ * grnet_op_raster_lines: the same for the wireframe: 3 face + k of the winning edge per pixel, -1 where uncovered.
+ * All three allocate temporaries and synchronise `stream` before they return (test hooks, like grnet_op_conv2d). */
 int grnet_op_raster_setup(grnet_t* h, const float* verts_dev, int V, const int32_t* faces_host, int F, const float* cam_dev, const float* M_host,
                           int H, int W, int32_t* xy_dev, float* z_dev, float* normals_dev, void* stream);
 int grnet_op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W, int32_t* winner_dev,
                     void* stream);
+int grnet_op_raster_lines(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W,
+                          int32_t* winner_dev, void* stream);
 
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single

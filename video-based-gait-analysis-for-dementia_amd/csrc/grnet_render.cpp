@@ -1,5 +1,6 @@
 // The mesh overlay of demo.py --mesh_render behind the C ABI (lib/utils/renderer.py:78-126; kernels: render_kernels.hip, rules: DESIGN 4.5):
-// the face table of a handle, grnet_render_meshes, and the two hooks that run the stages alone on a small mesh.
+// the face table of a handle, grnet_render_meshes / grnet_render_meshes_ex (filled, or the wireframe), and the hooks that run the stages alone
+// on a small mesh.
 #include "grnet_impl.h"
 
 namespace {
@@ -65,6 +66,40 @@ struct DeviceBlock {                                        // freed when a hook
     ~DeviceBlock() { if (p) (void)hipFree(p); }
 };
 
+// grnet_op_raster (lines = false) and grnet_op_raster_lines: one validation, one synchronisation
+int op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W, int32_t* winner_dev, bool lines,
+              void* stream) {
+    const std::string op = lines ? "op_raster_lines" : "op_raster", name = "grnet_" + op;
+    if (!h) return GRNET_EINVAL;
+    if (!xy_dev || !z_dev || !faces_host || !winner_dev) return h->fail(GRNET_EINVAL, name + ": null pointer");
+    if (V < 1 || F < 1) return h->fail(GRNET_EINVAL, name + ": V and F must be >= 1");
+    if (!dims_ok(H, W)) return h->fail(GRNET_EINVAL, name + ": image outside [1, " + std::to_string(kRasterMaxDim) + "]");
+    DeviceGuard guard(h->device);
+    RasterMesh m{};
+    DeviceBlock table, ws;
+    std::string why;
+    if (int rc = build_raster_mesh(faces_host, F, V, &m, &table.p, &why)) return h->fail(rc, name + ": " + why);
+    const size_t words = raster_depth_words(H, W);
+    if (hipMalloc(&ws.p, words * 8 + 16) != hipSuccess) return h->fail(GRNET_ENOMEM, name + ": hipMalloc failed");
+    RasterWork work{};
+    work.depth = static_cast<unsigned long long*>(ws.p);
+    work.bbox = reinterpret_cast<int*>(work.depth + words);
+    work.xy = const_cast<int*>(xy_dev);                     // the cover kernels only read the vertex records
+    work.z = const_cast<float*>(z_dev);
+    const int whole[4] = {kRasterCoordLimit, kRasterCoordLimit, kRasterCoordLimit, kRasterCoordLimit};    // (-X, -Y, X, Y): the whole viewport is cleared
+    RasterChunk c{};
+    c.n = 1;
+    const RasterView view = raster_view(nullptr, H, W);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(work.bbox, whole, sizeof(whole), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = lines ? launch_raster_lines_cover(c, view, m, work, s) : launch_raster_cover(c, view, m, work, s);
+    if (e == hipSuccess) e = launch_raster_winner(view, work, winner_dev, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, op + ": " + hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 void grnet::faces_clear() {
@@ -94,7 +129,15 @@ int grnet_load_faces(grnet_t* h, const int32_t* faces_host, int n_faces) {
 
 int grnet_render_meshes(grnet_t* h, const float* verts_dev, int n, const float* cams_dev, const float* colours_host, const int32_t* image_index_host,
                         const float* M_host, unsigned char* images_dev, int F, int H, int W, void* stream) {
+    return grnet_render_meshes_ex(h, verts_dev, n, cams_dev, colours_host, image_index_host, M_host, images_dev, F, H, W, 0u, stream);
+}
+
+int grnet_render_meshes_ex(grnet_t* h, const float* verts_dev, int n, const float* cams_dev, const float* colours_host, const int32_t* image_index_host,
+                           const float* M_host, unsigned char* images_dev, int F, int H, int W, unsigned flags, void* stream) {
     if (!h) return GRNET_EINVAL;
+    if (flags & ~(unsigned)GRNET_RENDER_WIREFRAME)
+        return h->fail(GRNET_EINVAL, "grnet_render_meshes_ex: flags " + std::to_string(flags) + " has bits other than GRNET_RENDER_WIREFRAME (1)");
+    const bool lines = flags & GRNET_RENDER_WIREFRAME;
     if (n < 0) return h->fail(GRNET_EINVAL, "grnet_render_meshes: n " + std::to_string(n) + " < 0");
     if (!dims_ok(H, W))
         return h->fail(GRNET_EINVAL, "grnet_render_meshes: image " + std::to_string(H) + " x " + std::to_string(W) + " outside [1, " + std::to_string(kRasterMaxDim) + "]");
@@ -122,8 +165,8 @@ int grnet_render_meshes(grnet_t* h, const float* verts_dev, int n, const float* 
     auto flush = [&]() -> hipError_t {
         if (!c.n) return hipSuccess;
         hipError_t e = launch_raster_setup(verts_dev, cams_dev, c, view, h->rmesh, work, s);
-        if (e == hipSuccess) e = launch_raster_cover(c, view, h->rmesh, work, s);
-        if (e == hipSuccess) e = launch_raster_resolve(c, view, h->rmesh, work, images_dev, s);
+        if (e == hipSuccess) e = lines ? launch_raster_lines_cover(c, view, h->rmesh, work, s) : launch_raster_cover(c, view, h->rmesh, work, s);
+        if (e == hipSuccess) e = lines ? launch_raster_lines_resolve(c, view, h->rmesh, work, images_dev, s) : launch_raster_resolve(c, view, h->rmesh, work, images_dev, s);
         c.n = 0;
         return e;
     };
@@ -171,34 +214,12 @@ int grnet_op_raster_setup(grnet_t* h, const float* verts_dev, int V, const int32
 
 int grnet_op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W, int32_t* winner_dev,
                     void* stream) {
-    if (!h) return GRNET_EINVAL;
-    if (!xy_dev || !z_dev || !faces_host || !winner_dev) return h->fail(GRNET_EINVAL, "grnet_op_raster: null pointer");
-    if (V < 1 || F < 1) return h->fail(GRNET_EINVAL, "grnet_op_raster: V and F must be >= 1");
-    if (!dims_ok(H, W)) return h->fail(GRNET_EINVAL, "grnet_op_raster: image outside [1, " + std::to_string(kRasterMaxDim) + "]");
-    DeviceGuard guard(h->device);
-    RasterMesh m{};
-    DeviceBlock table, ws;
-    std::string why;
-    if (int rc = build_raster_mesh(faces_host, F, V, &m, &table.p, &why)) return h->fail(rc, "grnet_op_raster: " + why);
-    const size_t words = raster_depth_words(H, W);
-    if (hipMalloc(&ws.p, words * 8 + 16) != hipSuccess) return h->fail(GRNET_ENOMEM, "grnet_op_raster: hipMalloc failed");
-    RasterWork work{};
-    work.depth = static_cast<unsigned long long*>(ws.p);
-    work.bbox = reinterpret_cast<int*>(work.depth + words);
-    work.xy = const_cast<int*>(xy_dev);                     // the cover kernels only read the vertex records
-    work.z = const_cast<float*>(z_dev);
-    const int whole[4] = {kRasterCoordLimit, kRasterCoordLimit, kRasterCoordLimit, kRasterCoordLimit};    // (-X, -Y, X, Y): the whole viewport is cleared
-    RasterChunk c{};
-    c.n = 1;
-    const RasterView view = raster_view(nullptr, H, W);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(work.bbox, whole, sizeof(whole), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch_raster_cover(c, view, m, work, s);
-    if (e == hipSuccess) e = launch_raster_winner(view, work, winner_dev, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("op_raster: ") + hipGetErrorString(e));
-    return 0;
+    return op_raster(h, xy_dev, z_dev, V, faces_host, F, H, W, winner_dev, false, stream);
+}
+
+int grnet_op_raster_lines(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W,
+                          int32_t* winner_dev, void* stream) {
+    return op_raster(h, xy_dev, z_dev, V, faces_host, F, H, W, winner_dev, true, stream);
 }
 
 }  // extern "C"

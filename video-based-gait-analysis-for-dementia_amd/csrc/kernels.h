@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "raster_lines.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -323,7 +324,7 @@ hipError_t launch_joint_regress(const float* verts, const float* wpack, int jout
 // The mesh overlay of demo.py --mesh_render (lib/utils/renderer.py:78-126; csrc/render_kernels.hip) ----
 constexpr int kRasterSlots = 16;             // meshes per launch group: each has its own depth image and vertex records in the workspace
 constexpr int kRasterMaxDim = 4096;          // largest image side
-constexpr int kRasterSnapBits = 8;           // sub-pixel bits of the snapped window coordinates
+// kRasterSnapBits = 8, the sub-pixel bits of the snapped window coordinates: raster_lines.h
 constexpr int kRasterCoordLimit = 1 << 28;   // |X|, |Y| are clamped here: coordinate differences < 2^29 + 2^21, edge products < 2^59, their sums fit int64
 struct RasterView { float M[9]; int H, W; };                      // q = M (x, -y, -z); the viewport
 struct RasterMesh {                                               // the topology of one mesh, device pointers (grnet_load_faces)
@@ -355,6 +356,12 @@ hipError_t launch_raster_cover(const RasterChunk& c, const RasterView& v, const 
 hipError_t launch_raster_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s);
 // slot 0's winning face per pixel in IMAGE rows, -1 where uncovered: winner (H,W) int32, every element written
 hipError_t launch_raster_winner(const RasterView& v, RasterWork w, int* winner, hipStream_t s);
+// The wireframe (demo.py --mesh_render --wireframe): the three edges of every front face as 1-pixel lines; the low word of a depth key is
+// 3 face + k, k = 0: v0 -> v1, 1: v1 -> v2, 2: v2 -> v0.  Same two launches each as the filled pair above; the depth clear and the resolve
+// reach one pixel further than the fill's, to every pixel whose SQUARE meets the bounding box.
+constexpr int kRasterLineWaveSteps = 16;     // an edge of more major steps than this is walked by the whole wave (unmeasured: NOTES_rejected)
+hipError_t launch_raster_lines_cover(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s);
+hipError_t launch_raster_lines_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s);
 
 // GRU gait encoder (gait_feat_encoder.py:79-104) ------------------------------------------------
 struct GruWeights {

@@ -26,7 +26,21 @@
 //   interpolated unit normal and position, three point lights at (0,-1,1), (0,1,1), (1,1,2) in q space:
 //   shade = 0.3 + sum_l max(0, n.l) / (pi d_l^2), byte k of the pixel = floor(255 min(1, colour_k shade) + 0.5).  Only covered pixels are stored
 //   (three byte stores each: a person covers a few percent of a frame); the depth reads are 512 contiguous bytes per wave.
-// raster_winner_kernel -- the test hook's read-out: the face per pixel in image rows, -1 where uncovered.
+// raster_winner_kernel -- the test hook's read-out: the low word of the key per pixel in image rows, -1 where uncovered.
+//
+// The wireframe (--wireframe: GL_LINE polygon mode) replaces the cover and the resolve; setup, normals, clear and winner are shared:
+// raster_lines_cover_kernel -- the same 64 faces per wave and the same A2 cull, then the three edges k = 0: v0 -> v1, 1: v1 -> v2,
+//   2: v2 -> v0 of every front face.  An edge is x-major if |dx| >= |dy|, else y-major; P is the major coordinate, Q the minor one; the end
+//   points are ordered P_lo < P_hi and EVERYTHING after that is computed from (lo, hi), so the two draws of a shared edge are the same
+//   fragments with the same depths.  Major index m is covered iff P_lo <= 256 m + 128 < P_hi; there the minor index is
+//   n = floor((Q_lo dP + (256 m + 128 - P_lo) dQ) / (256 dP)) in int64: one division for the first m of a lane, then the remainder is stepped
+//   (add 256 dQ, carry against 256 dP), which gives the same integers.  An edge of at most kRasterLineWaveSteps major steps is its lane's own
+//   loop; a longer one is collected with __ballot and walked by the whole wave, 64 major steps an iteration.  t = (256 m + 128 - P_lo) / dP,
+//   z = fma(t, z_hi - z_lo, z_lo) + 0; outside [-1, 1] discarded; one atomicMin on (ordered(z) << 32) | (3 face + k).
+// raster_resolve_kernel<true> -- face and k from the key, the major axis, (lo, hi) and t again from the pixel, normal and position
+//   interpolated between the two end points with t, then the same shade and store.  A line's pixel is the one whose SQUARE holds the line, so
+//   its centre may lie up to half a pixel outside the mesh's bounding box: the clear and the resolve of a wireframe take the pixels whose
+//   squares meet the box (pixel_range_squares), a superset of the fill's.
 #include "kernels.h"
 
 namespace grk {
@@ -55,9 +69,21 @@ __device__ __forceinline__ void pixel_range(int lo, int hi, int n, int& first, i
     last = min(n - 1, (hi - kHalf) >> kRasterSnapBits);
 }
 
+// The pixels whose squares [256 i, 256 i + 256) meet [lo, hi]: where a line between lo and hi can put a fragment
+__device__ __forceinline__ void pixel_range_squares(int lo, int hi, int n, int& first, int& last) {
+    first = max(0, lo >> kRasterSnapBits);
+    last = min(n - 1, hi >> kRasterSnapBits);
+}
+
+template <bool kLines>
 __device__ __forceinline__ bool slot_box(const int* bbox, const RasterView& v, int& i0, int& i1, int& j0, int& j1) {
-    pixel_range(-bbox[0], bbox[2], v.W, i0, i1);
-    pixel_range(-bbox[1], bbox[3], v.H, j0, j1);
+    if constexpr (kLines) {
+        pixel_range_squares(-bbox[0], bbox[2], v.W, i0, i1);
+        pixel_range_squares(-bbox[1], bbox[3], v.H, j0, j1);
+    } else {
+        pixel_range(-bbox[0], bbox[2], v.W, i0, i1);
+        pixel_range(-bbox[1], bbox[3], v.H, j0, j1);
+    }
     return i0 <= i1 && j0 <= j1;
 }
 
@@ -134,10 +160,11 @@ __global__ __launch_bounds__(256) void raster_normals_kernel(RasterMesh m, Raste
     o[2] = nz * inv;
 }
 
+template <bool kLines>
 __global__ __launch_bounds__(256) void raster_clear_kernel(RasterView view, RasterWork w) {
     const int slot = blockIdx.z;
     int i0, i1, j0, j1;
-    if (!slot_box(w.bbox + slot * 4, view, i0, i1, j0, j1)) return;
+    if (!slot_box<kLines>(w.bbox + slot * 4, view, i0, i1, j0, j1)) return;
     const int i = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1)), j = blockIdx.y * kTileH + threadIdx.x / kTileW;
     if (i < i0 || i > i1 || j < j0 || j > j1) return;
     w.depth[(size_t)slot * view.H * view.W + (size_t)j * view.W + i] = kDepthClear;
@@ -190,32 +217,72 @@ __global__ __launch_bounds__(256) void raster_cover_kernel(RasterView view, Rast
     }
 }
 
-__global__ __launch_bounds__(256) void raster_resolve_kernel(RasterChunk c, RasterView view, RasterMesh m, RasterWork w, unsigned char* __restrict__ images) {
-    const int slot = blockIdx.z;
-    int i0, i1, j0, j1;
-    if (!slot_box(w.bbox + slot * 4, view, i0, i1, j0, j1)) return;
-    const int i = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1)), j = blockIdx.y * kTileH + threadIdx.x / kTileW;
-    if (i < i0 || i > i1 || j < j0 || j > j1) return;
-    const unsigned long long key = w.depth[(size_t)slot * view.H * view.W + (size_t)j * view.W + i];
-    if (key == kDepthClear) return;
-    const int* f = m.faces + (size_t)(unsigned)key * 3;
-    const size_t vo = (size_t)slot * m.n_verts;
-    const int* xa = w.xy + (vo + f[0]) * 2;
-    const int* xb = w.xy + (vo + f[1]) * 2;
-    const int* xc = w.xy + (vo + f[2]) * 2;
-    const int px = i * kSub + kHalf, py = j * kSub + kHalf;
-    const float inv_area = 1.f / (float)edge(xa[0], xa[1], xb[0], xb[1], xc[0], xc[1]);
-    const float b0 = (float)edge(xb[0], xb[1], xc[0], xc[1], px, py) * inv_area;
-    const float b1 = (float)edge(xc[0], xc[1], xa[0], xa[1], px, py) * inv_area;
-    const float b2 = (float)edge(xa[0], xa[1], xb[0], xb[1], px, py) * inv_area;
-    const float *na = w.nrm + (vo + f[0]) * 3, *nb = w.nrm + (vo + f[1]) * 3, *nc = w.nrm + (vo + f[2]) * 3;
-    const float *qa = w.q + (vo + f[0]) * 3, *qb = w.q + (vo + f[1]) * 3, *qc = w.q + (vo + f[2]) * 3;
-    float n[3], p[3];
+// The edge records and their integer arithmetic: raster_lines.h
+__device__ __forceinline__ float line_t(const LineRec& r, int m) { return (float)(m * kSub + kHalf - r.P0) / (float)(r.P1 - r.P0); }
+
+__device__ __forceinline__ void line_fragment(const LineRec& r, int m, long long n, unsigned id, const RasterView& view, unsigned long long* depth) {
+    if (n < 0 || n >= (r.xmajor ? view.H : view.W)) return;
+    const float z = fmaf(line_t(r, m), r.z1 - r.z0, r.z0) + 0.f;                   // + 0: -0 and +0 are one depth
+    if (!(z >= -1.f && z <= 1.f)) return;
+    const int i = r.xmajor ? m : (int)n, j = r.xmajor ? (int)n : m;
+    atomicMin(depth + (size_t)j * view.W + i, ((unsigned long long)ordered_bits(z) << 32) | id);
+}
+
+__global__ __launch_bounds__(256) void raster_lines_cover_kernel(RasterView view, RasterMesh m, RasterWork w) {
+    const int slot = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const int* xy = w.xy + (size_t)slot * m.n_verts * 2;
+    const float* zv = w.z + (size_t)slot * m.n_verts;
+    unsigned long long* depth = w.depth + (size_t)slot * view.H * view.W;
+    int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
+    float Z[3] = {0.f, 0.f, 0.f};
+    bool front = false;
+    if (f < m.n_faces) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int v = m.faces[(size_t)f * 3 + k];
+            X[k] = xy[2 * v], Y[k] = xy[2 * v + 1], Z[k] = zv[v];
+        }
+        front = edge(X[0], Y[0], X[1], Y[1], X[2], Y[2]) > 0;
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        n[k] = b0 * na[k] + b1 * nb[k] + b2 * nc[k];
-        p[k] = b0 * qa[k] + b1 * qb[k] + b2 * qc[k];
+        const int a = k, b = (k + 1) % 3;
+        LineRec r{};
+        r.m1 = -1;
+        bool flip = false;
+        if (front && line_order(X[a], Y[a], X[b], Y[b], r, flip)) {
+            r.z0 = flip ? Z[b] : Z[a], r.z1 = flip ? Z[a] : Z[b];
+            line_range(r, r.xmajor ? view.W : view.H);
+        }
+        const int steps = r.m1 - r.m0 + 1;
+        const bool wide = steps > kRasterLineWaveSteps;
+        if (steps > 0 && !wide) {                                                  // a short edge: this lane's own loop
+            const LineStride st = line_stride(r, 1);
+            long long n, rem;
+            line_minor(r, r.m0, n, rem);
+            for (int mm = r.m0; mm <= r.m1; ++mm, line_advance(st, n, rem)) line_fragment(r, mm, n, 3u * (unsigned)f + k, view, depth);
+        }
+        unsigned long long todo = __ballot(wide);
+        while (todo) {                                         // wave-uniform: a long edge is 64 lanes' work
+            const int t = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            LineRec e;
+            e.P0 = __shfl(r.P0, t, 64), e.Q0 = __shfl(r.Q0, t, 64), e.P1 = __shfl(r.P1, t, 64), e.Q1 = __shfl(r.Q1, t, 64);
+            e.z0 = __shfl(r.z0, t, 64), e.z1 = __shfl(r.z1, t, 64);
+            e.m0 = __shfl(r.m0, t, 64), e.m1 = __shfl(r.m1, t, 64), e.xmajor = __shfl(r.xmajor, t, 64);
+            const unsigned id = 3u * (unsigned)(f - lane + t) + k;
+            const LineStride st = line_stride(e, 64);          // wave-uniform
+            long long n, rem;
+            line_minor(e, e.m0 + lane, n, rem);               // m0 + lane <= 4095 + 63: the numerator stays far inside int64
+            for (int mm = e.m0 + lane; mm <= e.m1; mm += 64, line_advance(st, n, rem)) line_fragment(e, mm, n, id, view, depth);
+        }
     }
+}
+
+// bytes of a covered pixel from the interpolated normal n (any length) and position p, in q space
+__device__ __forceinline__ void shade_store(const float n[3], const float p[3], const float colour[3], unsigned char* out) {
     const float n2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
     const float ninv = n2 > 0.f ? 1.f / sqrtf(n2) : 0.f;
     const float lights[3][3] = {{0.f, -1.f, 1.f}, {0.f, 1.f, 1.f}, {1.f, 1.f, 2.f}};
@@ -227,10 +294,58 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(RasterChunk c, Rast
         const float cosine = (n[0] * dx + n[1] * dy + n[2] * dz) * ninv / sqrtf(d2);
         shade += fmaxf(0.f, cosine) / (3.14159265358979323846f * d2);
     }
-    unsigned char* out = images + (((size_t)c.image[slot] * view.H + (view.H - 1 - j)) * view.W + i) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-        out[k] = (unsigned char)floorf(255.f * fmaxf(0.f, fminf(1.f, c.colour[slot][k] * shade)) + 0.5f);
+        out[k] = (unsigned char)floorf(255.f * fmaxf(0.f, fminf(1.f, colour[k] * shade)) + 0.5f);
+}
+
+template <bool kLines>
+__global__ __launch_bounds__(256) void raster_resolve_kernel(RasterChunk c, RasterView view, RasterMesh m, RasterWork w, unsigned char* __restrict__ images) {
+    const int slot = blockIdx.z;
+    int i0, i1, j0, j1;
+    if (!slot_box<kLines>(w.bbox + slot * 4, view, i0, i1, j0, j1)) return;
+    const int i = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1)), j = blockIdx.y * kTileH + threadIdx.x / kTileW;
+    if (i < i0 || i > i1 || j < j0 || j > j1) return;
+    const unsigned long long key = w.depth[(size_t)slot * view.H * view.W + (size_t)j * view.W + i];
+    if (key == kDepthClear) return;
+    const size_t vo = (size_t)slot * m.n_verts;
+    float n[3], p[3];
+    if constexpr (kLines) {
+        const unsigned id = (unsigned)key;
+        const int* f = m.faces + (size_t)(id / 3) * 3;
+        int va = f[id % 3], vb = f[(id % 3 + 1) % 3];
+        const int* xa = w.xy + (vo + va) * 2;
+        const int* xb = w.xy + (vo + vb) * 2;
+        LineRec r{};
+        bool flip = false;
+        if (!line_order(xa[0], xa[1], xb[0], xb[1], r, flip)) return;             // never: a point draws no fragment
+        if (flip) { const int s = va; va = vb, vb = s; }
+        const float t = line_t(r, r.xmajor ? i : j);
+        const float *na = w.nrm + (vo + va) * 3, *nb = w.nrm + (vo + vb) * 3, *qa = w.q + (vo + va) * 3, *qb = w.q + (vo + vb) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            n[k] = na[k] + t * (nb[k] - na[k]);
+            p[k] = qa[k] + t * (qb[k] - qa[k]);
+        }
+    } else {
+        const int* f = m.faces + (size_t)(unsigned)key * 3;
+        const int* xa = w.xy + (vo + f[0]) * 2;
+        const int* xb = w.xy + (vo + f[1]) * 2;
+        const int* xc = w.xy + (vo + f[2]) * 2;
+        const int px = i * kSub + kHalf, py = j * kSub + kHalf;
+        const float inv_area = 1.f / (float)edge(xa[0], xa[1], xb[0], xb[1], xc[0], xc[1]);
+        const float b0 = (float)edge(xb[0], xb[1], xc[0], xc[1], px, py) * inv_area;
+        const float b1 = (float)edge(xc[0], xc[1], xa[0], xa[1], px, py) * inv_area;
+        const float b2 = (float)edge(xa[0], xa[1], xb[0], xb[1], px, py) * inv_area;
+        const float *na = w.nrm + (vo + f[0]) * 3, *nb = w.nrm + (vo + f[1]) * 3, *nc = w.nrm + (vo + f[2]) * 3;
+        const float *qa = w.q + (vo + f[0]) * 3, *qb = w.q + (vo + f[1]) * 3, *qc = w.q + (vo + f[2]) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            n[k] = b0 * na[k] + b1 * nb[k] + b2 * nc[k];
+            p[k] = b0 * qa[k] + b1 * qb[k] + b2 * qc[k];
+        }
+    }
+    shade_store(n, p, c.colour[slot], images + (((size_t)c.image[slot] * view.H + (view.H - 1 - j)) * view.W + i) * 3);
 }
 
 __global__ __launch_bounds__(256) void raster_winner_kernel(RasterView view, RasterWork w, int* __restrict__ winner) {
@@ -258,13 +373,24 @@ hipError_t launch_raster_setup(const float* verts, const float* cams, const Rast
 }
 
 hipError_t launch_raster_cover(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s) {
-    hipLaunchKernelGGL(raster_clear_kernel, pixel_grid(v, c.n), dim3(256), 0, s, v, w);
+    hipLaunchKernelGGL(raster_clear_kernel<false>, pixel_grid(v, c.n), dim3(256), 0, s, v, w);
     if (m.n_faces) hipLaunchKernelGGL(raster_cover_kernel, dim3((m.n_faces + 255) / 256, c.n), dim3(256), 0, s, v, m, w);
     return hipGetLastError();
 }
 
 hipError_t launch_raster_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s) {
-    hipLaunchKernelGGL(raster_resolve_kernel, pixel_grid(v, c.n), dim3(256), 0, s, c, v, m, w, images);
+    hipLaunchKernelGGL(raster_resolve_kernel<false>, pixel_grid(v, c.n), dim3(256), 0, s, c, v, m, w, images);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_lines_cover(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s) {
+    hipLaunchKernelGGL(raster_clear_kernel<true>, pixel_grid(v, c.n), dim3(256), 0, s, v, w);
+    if (m.n_faces) hipLaunchKernelGGL(raster_lines_cover_kernel, dim3((m.n_faces + 255) / 256, c.n), dim3(256), 0, s, v, m, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_lines_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s) {
+    hipLaunchKernelGGL(raster_resolve_kernel<true>, pixel_grid(v, c.n), dim3(256), 0, s, c, v, m, w, images);
     return hipGetLastError();
 }
 

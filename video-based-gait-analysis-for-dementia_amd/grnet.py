@@ -802,13 +802,16 @@ class GRNet:
     # ------------------------------------------------------------------ the mesh overlay (demo.py --mesh_render)
     SIDE_VIEW = (0.0, 0.0, -1.0, 0.0, 1.0, 0.0, 1.0, 0.0, 0.0)      # the reference's --sideview: rotation by 270 degrees about y (demo.py:351-352)
 
-    def render(self, images, verts, cams, colours, image_index, M=None, rgb=True):
-        """Draw n meshes into uint8 device images (F,H,W,3) IN PLACE and return them (grnet_render_meshes; the rules: DESIGN.md 4.5).  verts
+    RENDER_WIREFRAME = 1            # GRNET_RENDER_WIREFRAME
+
+    def render(self, images, verts, cams, colours, image_index, M=None, rgb=True, wireframe=False):
+        """Draw n meshes into uint8 device images (F,H,W,3) IN PLACE and return them (grnet_render_meshes_ex; the rules: DESIGN.md 4.5).  verts
         (n,6890,3) and cams (n,4) rows [sx,sy,tx,ty] -- host or device; colours (n,3): the (r,g,b) triples the reference hands to
         Renderer.render; image_index (n): the image each mesh is drawn into.  Meshes of one image are drawn in the order given, later over
         earlier.  M: 9 floats, None for the main view, GRNet.SIDE_VIEW for --sideview.  Nothing synchronises; n is not limited by max_frames.
         rgb: the reference writes its (r,g,b) triple into a BGR image (cv2) WITHOUT swapping, so what it shows is (b,g,r) of the triple.
-        pipeline keeps frames in RGB, so the triple goes down reversed to put the same colour on the screen; rgb=False: BGR frames, as is."""
+        pipeline keeps frames in RGB, so the triple goes down reversed to put the same colour on the screen; rgb=False: BGR frames, as is.
+        wireframe: the reference's --wireframe -- nothing filled, the three edges of every front face as 1-pixel lines, shaded alike."""
         if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda \
                 or not images.is_contiguous():
             raise ValueError("images must be a contiguous uint8 (F,H,W,3) tensor on the device")
@@ -824,9 +827,10 @@ class GRNet:
             raise ValueError(f"verts, cams, colours and image_index disagree on n: {n}, {c.shape[0]}, {col.shape[0]}, {idx.shape[0]}")
         Mh = None if M is None else np.ascontiguousarray(np.asarray(M, np.float32).reshape(9))
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_render_meshes(self._h, v.data_ptr(), n, c.data_ptr(), col.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
-                                           Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, images.data_ptr(), F, H, W, stream)
-        _lib.check(self._lib, self._h, rc, "grnet_render_meshes")
+        rc = self._lib.grnet_render_meshes_ex(self._h, v.data_ptr(), n, c.data_ptr(), col.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                              Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, images.data_ptr(), F, H, W,
+                                              self.RENDER_WIREFRAME if wireframe else 0, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_render_meshes_ex")
         return images
 
     def op_raster_setup(self, verts, faces, cam, H, W, M=None):
@@ -847,17 +851,24 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_raster_setup")
         return xy, z, nrm
 
-    def op_raster(self, xy, z, faces, H, W):
-        """Snapped vertices xy (V,2) int32 and z (V) -> the winning face per pixel (H,W) int32 in image rows, -1 where uncovered (grnet_op_raster)."""
+    def _op_raster(self, entry, xy, z, faces, H, W):
         xy = torch.as_tensor(xy).to(self.device, torch.int32).reshape(-1, 2).contiguous()
         z = torch.as_tensor(z).to(self.device, torch.float32).reshape(-1).contiguous()
         f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
         out = torch.empty(H, W, dtype=torch.int32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_op_raster(self._h, xy.data_ptr(), z.data_ptr(), xy.shape[0], f.ctypes.data_as(C.c_void_p), f.shape[0], H, W, out.data_ptr(),
+        rc = getattr(self._lib, entry)(self._h, xy.data_ptr(), z.data_ptr(), xy.shape[0], f.ctypes.data_as(C.c_void_p), f.shape[0], H, W, out.data_ptr(),
                                        stream)
-        _lib.check(self._lib, self._h, rc, "grnet_op_raster")
+        _lib.check(self._lib, self._h, rc, entry)
         return out
+
+    def op_raster(self, xy, z, faces, H, W):
+        """Snapped vertices xy (V,2) int32 and z (V) -> the winning face per pixel (H,W) int32 in image rows, -1 where uncovered (grnet_op_raster)."""
+        return self._op_raster("grnet_op_raster", xy, z, faces, H, W)
+
+    def op_raster_lines(self, xy, z, faces, H, W):
+        """op_raster for the wireframe: 3 face + k of the winning edge per pixel, k = 0: v0->v1, 1: v1->v2, 2: v2->v0 (grnet_op_raster_lines)."""
+        return self._op_raster("grnet_op_raster_lines", xy, z, faces, H, W)
 
     # single-op hooks for kernel parity tests
     def op_conv2d(self, x, w, bias=None, stride=1, relu=False, add=None, tile_hint=0):
