@@ -6,7 +6,10 @@ Out of scope here (rows 12, 17): ffmpeg video decoding and the YOLOv3+
 reference takes once those steps are done: --img_folder (extracted frames) and --tracking_path (joblib {id: {'bbox','frames'}}).
 --mesh_render draws the overlay frames (demo.py:269-385) with the library's own rasteriser: OpenGL's geometry rules, a stated Lambert
 shading that is NOT pyrender's; with --wireframe the overlay is the meshes' edges as 1-pixel lines (GL's polygon mode GL_LINE,
-by the library's own line rule).  --display, the matplotlib skeleton view and --wireframe without --mesh_render stay refused.
+by the library's own line rule).  --skeleton_view writes the reference's OTHER output (demo.py:288-290, 303-361 without --mesh_render): the input
+frame on the left and the 3D skeleton of every tracked person on the right, from matplotlib's viewpoint for the reference's settings, drawn on
+the GPU by the library's own wide-line rule (no pane fills, no tick labels or titles, no caps, no anti-aliasing, the panel as large
+as the input frame) -- NOT by matplotlib.  --display and --wireframe without --mesh_render stay refused.
 The reference's --cpu_only (demo.py:46-49,403) is accepted and refused with one line: there is deliberately no CPU fallback.
 """
 import argparse
@@ -64,6 +67,7 @@ def build_model(pkg, args, seqlen):
 
 
 RENDER_CHUNK = 16            # frames uploaded, drawn and downloaded together
+SKELETON_JOINT_TYPES = ("spin", "kinectv2")      # pipeline.skeleton_bones
 
 
 def refusal(a):
@@ -72,9 +76,78 @@ def refusal(a):
         return CPU_ONLY_MESSAGE
     if a.wireframe and not a.mesh_render:
         return "--wireframe draws the lines of the --mesh_render overlay and needs it: add --mesh_render"
+    if a.skeleton_view and a.mesh_render:
+        return "--skeleton_view and --mesh_render are the reference's two alternative outputs (demo.py:285-290): give one of them"
+    if a.skeleton_view and a.joint_type not in SKELETON_JOINT_TYPES:
+        return (f"--skeleton_view has no bone table for --joint_type {a.joint_type}: the skeletons the library emits as 3D joints are "
+                + " and ".join(SKELETON_JOINT_TYPES))
     if a.display:
         return "--display opens a window (cv2.imshow / matplotlib) and is not implemented: the frames of --mesh_render are written to disk"
     return None
+
+
+def save_video(args, folder, output_path, stem):
+    """demo.py:379-383, demo_utils.py:160-173: the frames of `folder` as <stem>.mp4, if ffmpeg is there and --save_vid has not switched it off."""
+    if args.save_vid and shutil.which("ffmpeg"):
+        save_name = osp.join(output_path, stem + ".mp4")
+        command = ["ffmpeg", "-y", "-threads", "16", "-start_number", "0", "-i", f"{folder}/%06d.png", "-profile:v", "baseline", "-level", "3.0",
+                   "-c:v", "libx264", "-pix_fmt", "yuv420p", "-an", "-v", "error", save_name]
+        print(f"Saving result video to {save_name}")
+        subprocess.call(command)
+    else:
+        print(f"The rendered frames are in {folder} (no video: {'--save_vid switches it off' if not args.save_vid else 'no ffmpeg on PATH'}).")
+
+
+def skeleton_widths(H, W):
+    """(bone, grid) line widths in pixels for an H x W panel: matplotlib's lw=2 pt is 2.78 px on its 225.45-px axes, its grid's 0.8 pt 1.11 px."""
+    S = min(H, W)
+    return max(2, int(round(S / 81))), max(1, int(round(S / 203)))
+
+
+def image_frames(args):
+    """The sorted .png / .jpg names of --img_folder for --skeleton_view; one line and out if the folder holds ready .npy crops (or nothing)."""
+    names = sorted(x for x in os.listdir(args.img_folder) if x.endswith((".png", ".jpg")))
+    every = sorted(x for x in os.listdir(args.img_folder) if x.endswith((".png", ".jpg", ".npy")))
+    if not names or names != every:
+        sys.exit("--skeleton_view puts the input frames (.png / .jpg) beside the skeletons: this folder holds ready .npy crops")
+    return names
+
+
+def render_skeleton_view(model, pipe, args, results, view_joints, rot, output_path, stem):
+    """demo.py:288-290, 303-361 without --mesh_render: every image of the folder is written as %06d.png, (H, 2W, 3) -- the input on the left, and
+    on the right an H x W panel: white, the grid of the three far panes, then the skeleton of every person of the frame in --joint_type's bones,
+    turned by the body rotation `rot`, all persons in ONE depth buffer.  view_joints: person -> (T,J,3) joints in --joint_type's skeleton."""
+    import torch
+    from PIL import Image
+    names = image_frames(args)
+    n_frames = len(names)
+    last = max((int(np.max(r["frame_ids"])) for r in results.values() if len(r["frame_ids"])), default=-1)
+    if last >= n_frames:
+        sys.exit(f"the tracking file names frame {last}, but {args.img_folder} holds {n_frames} frames")
+    frame_results = pipe.prepare_rendering_results(results, list(range(n_frames)))
+    bones, bone_colours = pipe.skeleton_bones(args.joint_type)
+    grid_points, grid_segments = pipe.skeleton_grid()
+    folder = osp.join(output_path, stem + "_output")
+    os.makedirs(folder, exist_ok=True)
+    print(f"Rendering output video, writing frames to {folder}.")
+    for s in range(0, n_frames, RENDER_CHUNK):
+        idxs = range(s, min(n_frames, s + RENDER_CHUNK))
+        imgs = torch.from_numpy(np.stack([np.asarray(Image.open(osp.join(args.img_folder, names[i])).convert("RGB")) for i in idxs])).to(model.device)
+        H, W = imgs.shape[1:3]
+        bone_width, grid_width = skeleton_widths(H, W)
+        panel = torch.full_like(imgs, 255)
+        # the grid is not turned with the body: a call of its own, one copy of it per frame, under the skeletons
+        model.render_segments(panel, np.repeat(grid_points[None], len(idxs), 0), grid_segments, [pipe.GRID_COLOUR] * len(grid_segments),
+                              [grid_width] * len(grid_segments), list(range(len(idxs))))
+        rows = [view_joints[pid][pd["row"]] for fi in idxs for pid, pd in frame_results[fi].items()]
+        where = [k for k, fi in enumerate(idxs) for _ in frame_results[fi]]
+        if rows:
+            model.render_segments(panel, np.stack(rows), bones, bone_colours, [bone_width] * len(bones), where, R=rot)
+        out = torch.cat([imgs, panel], 2).cpu().numpy()
+        for k, fi in enumerate(idxs):
+            Image.fromarray(out[k]).save(osp.join(folder, f"{fi:06d}.png"))
+    save_video(args, folder, output_path, stem)
+    return folder
 
 
 def render_overlay(model, pipe, args, results, verts_dev, output_path, stem):
@@ -126,14 +199,7 @@ def render_overlay(model, pipe, args, results, verts_dev, output_path, stem):
             Image.fromarray(out[k]).save(osp.join(folder, f"{fi:06d}.png"))
     if not args.mesh_render:
         return None
-    if args.save_vid and shutil.which("ffmpeg"):                                             # demo.py:379-383, demo_utils.py:160-173
-        save_name = osp.join(output_path, stem + ".mp4")
-        command = ["ffmpeg", "-y", "-threads", "16", "-start_number", "0", "-i", f"{folder}/%06d.png", "-profile:v", "baseline", "-level", "3.0",
-                   "-c:v", "libx264", "-pix_fmt", "yuv420p", "-an", "-v", "error", save_name]
-        print(f"Saving result video to {save_name}")
-        subprocess.call(command)
-    else:
-        print(f"The rendered frames are in {folder} (no video: {'--save_vid switches it off' if not args.save_vid else 'no ffmpeg on PATH'}).")
+    save_video(args, folder, output_path, stem)
     return folder
 
 
@@ -146,6 +212,8 @@ def main(args):
         sys.exit(f'Input image folder "{args.img_folder}" does not exist! (video decoding is out of scope: extract frames first)')
     if not args.tracking_path:
         sys.exit("--tracking_path is required (the YOLOv3+SORT tracker is a separate third-party model)")
+    if args.skeleton_view:
+        image_frames(args)                                    # refused before the model runs
     video_name = osp.basename(osp.normpath(args.vid_file)).split(".")[0] if args.vid_file else osp.basename(osp.normpath(args.img_folder))
     output_path = osp.join(args.output_folder, video_name, "normal" + time.strftime("-%m%d"))
     os.makedirs(output_path, exist_ok=True)
@@ -168,11 +236,13 @@ def main(args):
             smpl_tables = {"J_regressor_extra": np.load(osp.join(args.smpl_dir, "J_regressor_extra.npy"))}
     t0 = time.time()
     results, verts_dev, n_frames = {}, {}, 0
+    view_joints, view_rot = {}, None
     for pid, tr in tracking.items():
         bboxes, frames = np.asarray(tr["bbox"], np.float32).copy(), np.asarray(tr["frames"])
         ds = pipe.InferenceFrames(args.img_folder, frames, bboxes, scale=1.0)
         device_smooth = args.smooth and not args.smooth_on_host
-        on_device = device_smooth or args.mesh_render          # the overlay draws the vertices where the forward left them
+        # the overlay draws the vertices where the forward left them; the skeleton view forms the 49 joints from them
+        on_device = device_smooth or args.mesh_render or args.skeleton_view
         pred = pipe.run_tracklet(model, ds.batches(args.grnet_batch_size, model=model), on_device=on_device)
         w, h = ds.image_size()
         theta = pred.pop("theta", None)
@@ -192,6 +262,13 @@ def main(args):
         if args.mesh_render:
             import torch
             verts_dev[pid] = torch.as_tensor(pred["verts"]).to(model.device)
+        if args.skeleton_view:
+            # the view and its body rotation are defined on the 49 SPIN joints (demo.py:239-247, 359): --smooth has them, a plain forward
+            # emits the 29 spin2 joints, from which and from its vertices the device forms the 49; the pickle stays what it is
+            j49 = pred["joints3d"] if args.smooth else model.spin_joints(pred["joints3d"], pred["verts"], joints="spin49")
+            j49 = np.asarray(j49.cpu().numpy() if hasattr(j49, "cpu") else j49)
+            view_joints[pid] = j49 if args.joint_type == "spin" else pipe.convert_kps(j49, "spin", args.joint_type)
+            view_rot = pipe.body_rotation(j49[10])             # demo.py:241: frame 10 of the last person processed
         pred = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in pred.items()}
         results[pid] = pipe.make_demo_result(pred, ds.bboxes, ds.frames, w, h)
         if args.joint_type != "spin":                          # demo.py:224-229
@@ -218,6 +295,8 @@ def main(args):
     print(f'Saving output results to "{out}".')
     if args.mesh_render or args.save_obj:
         render_overlay(model, pipe, args, results, verts_dev, output_path, osp.basename(out)[:-len(".pkl")])
+    if args.skeleton_view:
+        render_skeleton_view(model, pipe, args, results, view_joints, view_rot, output_path, osp.basename(out)[:-len(".pkl")])
     return out
 
 
@@ -234,6 +313,8 @@ def parser():
     p.add_argument("--display", action="store_true", help="parsed, and refused: no window is opened")
     p.add_argument("--mesh_render", action="store_true", help="write the overlay frames (and the video, if ffmpeg is on PATH): the meshes drawn over the input frames on the GPU")
     p.add_argument("--wireframe", action="store_true", help="with --mesh_render: draw the meshes as wireframes (the edges of the front faces, 1-pixel lines) in the main and the side view")
+    p.add_argument("--skeleton_view", action="store_true", help="write the reference's other output (and the video): the input frame on the left, the 3D skeletons "
+                   "of the frame's persons on the right, from matplotlib's viewpoint, drawn on the GPU; not together with --mesh_render")
     p.add_argument("--sideview", action="store_true", help="with --mesh_render: append the meshes seen from the side, on black, to the right of every frame")
     p.add_argument("--save_obj", action="store_true", help="write rendered/<person>/<frame>.obj, the mesh as the renderer turns it")
     p.add_argument("--smooth", action="store_true")
@@ -265,6 +346,6 @@ if __name__ == "__main__":
         if getattr(a, flag) != getattr(d, flag):
             print(f"warning: --{flag} configures a step outside the per-frame path (the tracker, SURVEY 8f) and has no effect here")
     for flag in ("sideview", "save_vid"):
-        if getattr(a, flag) != getattr(d, flag) and not a.mesh_render:
+        if getattr(a, flag) != getattr(d, flag) and not a.mesh_render and not (a.skeleton_view and flag == "save_vid"):
             print(f"warning: --{flag} configures the output video and has no effect without --mesh_render")
     main(a)

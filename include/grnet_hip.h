@@ -430,6 +430,47 @@ int grnet_op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V
 int grnet_op_raster_lines(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W,
                           int32_t* winner_dev, void* stream);
 
+/* ---- the 3D skeleton view of demo.py --skeleton_view -- demo.py:303-361 without --mesh_render, lib/utils/vis.py:571-587 (csrc/skeleton_kernels.hip;
+ * the rules in full: DESIGN.md 4.6) -----------------------------------------------------------------------------------------------------------
+ * grnet_spin_joints: the joints of grnet_smooth_pose WITHOUT the filter and without an SMPL pass: kp29_dev (n,29,3) and verts_dev (n,6890,3) as a
+ * forward (or grnet_smpl_forward) leaves them -> joints_dev (n,49|29|25,3) for GRNET_JOINTS_SPIN49 / _SPIN2 / _KINECTV2, in chunks of max_frames,
+ * bit-identical to what grnet_smooth_pose writes for the same vertices and joints.  The forward emits the 29 'spin2' joints; the reference's
+ * skeleton view and its body rotation (joints 27, 28, 39, 40) are defined on the 49.  No host synchronisation, no allocation.  GRNET_EINVAL: n < 0,
+ * an unknown joints_kind, a null pointer; GRNET_ESTATE: no SMPL tables.  n == 0 is a no-op after those checks. */
+int grnet_spin_joints(grnet_t* h, const float* kp29_dev, const float* verts_dev, int n, int joints_kind, float* joints_dev, void* stream);
+/* Draws n skeletons of P points each as S wide line segments: points_dev (n,P,3) is a device pointer; segments_host (S,2) int32 point indices,
+ * colours_host (S,3) uint8 in the image's MEMORY order, widths_host (S) int32 pixels in [1, 16], image_index_host (n), R_host (9 floats, row-major,
+ * or NULL for the identity), proj_host (16 doubles, row-major) and window_host (4 doubles: x0, x1, y0, y1) are host pointers.  images_dev: uint8
+ * (F,H,W,3), in/out.  A point p becomes p' = R p, hw = proj[3] . (p',1), (xs, ys) = proj[0,1] . (p',1) / hw; the window maps onto the centred
+ * S x S square, S = min(H, W), in GL window coordinates (origin bottom-left): x_win = (W - S)/2 + S (xs - x0)/(x1 - x0), y likewise; snapped to 8
+ * sub-pixel bits; depth d = proj[3][0..2] . p'.  A point is invalid if p' is not finite, hw <= 0 or a window coordinate exceeds 2^20 pixels in
+ * magnitude; a segment with an invalid end draws nothing.  Lines follow OpenGL's rule for non-antialiased lines of width w on the snapped
+ * integers: ends ordered and major axis chosen as for the wireframe, major index m covered iff P0 <= 256 m + 128 < P1, the column
+ * n0 .. n0 + w - 1, n0 = floor((Q0 dP + (256 m + 128 - P0) dQ - (w - 1) 128 dP) / (256 dP)), inside the viewport, all at the depth interpolated at m;
+ * no caps, no joins, no anti-aliasing, no shading.  ALL skeletons aimed at an image share ONE depth image: GL_LESS on
+ * (ordered(d) << 32) | (r S + s), r the skeleton's rank in call order among those aimed at that image, s the segment: at equal depth the lower id
+ * wins.  The three bytes of a covered pixel become the segment's colour, EVERY other byte is left as it is; image row = H - 1 - GL row.
+ * Coverage and winner do not depend on execution order.  Everything is enqueued on `stream`; n is NOT limited by max_frames.  The workspace is
+ * grnet_render_meshes' (ONE allocation at the first call of either); a launch group is min(16, 4096 * 4096 / (H * W)) IMAGES, and the skeletons
+ * aimed at them go through in launches of up to 64, their records as kernel arguments.  No host synchronisation: the segment table is copied
+ * through pinned host memory the handle owns (a ring of 4 tables of 64 KiB, allocated at the first call; a call waits only if the copy made 4 calls
+ * earlier has not finished).  A group with more than 65 536 points goes through in passes over depth images cleared as a whole.  Calls on a
+ * handle must be ordered, as for grnet_render_meshes.  Does not need grnet_load_faces.
+ * GRNET_EINVAL (with a message): n < 0, P outside [1, 1024], S outside [0, 4096], H or W outside [1, 4096], F < 1 -- checked first, so an empty
+ * call with a bad size is still refused; n == 0 is then a no-op that reads no pointer -- a null pointer, a non-finite entry of R, proj or window,
+ * an empty window (x1 <= x0 or y1 <= y0), a segment index outside [0, P), a width outside [1, 16], an image_index outside [0, F), more skeletons
+ * aimed at one image than r S + s holds in 31 bits.  A refused call touches no image. */
+int grnet_render_segments(grnet_t* h, const float* points_dev, int n, int P, const int32_t* segments_host, int S, const unsigned char* colours_host,
+                          const int32_t* widths_host, const int32_t* image_index_host, const float* R_host, const double* proj_host,
+                          const double* window_host, unsigned char* images_dev, int F, int H, int W, void* stream);
+/* The two stages alone, for ONE skeleton (test hooks: they allocate temporaries and synchronise `stream` before they return).
+ * grnet_op_segments_setup: points_dev (P,3) -> xy_dev (P,2) int32 snapped window coordinates, INT32_MIN in both for an invalid point, and
+ * depth_dev (P).  grnet_op_raster_segments: those -> winner_dev (H,W) int32 in image rows: the winning segment per pixel, -1 where uncovered. */
+int grnet_op_segments_setup(grnet_t* h, const float* points_dev, int P, const float* R_host, const double* proj_host, const double* window_host, int H,
+                            int W, int32_t* xy_dev, float* depth_dev, void* stream);
+int grnet_op_raster_segments(grnet_t* h, const int32_t* xy_dev, const float* depth_dev, int P, const int32_t* segments_host, int S,
+                             const int32_t* widths_host, int H, int W, int32_t* winner_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

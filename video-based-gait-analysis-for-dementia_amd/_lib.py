@@ -18,6 +18,7 @@ JOINT_REGRESSOR_MAX_ROWS = 64
 JOINTS_SPIN49, JOINTS_SPIN2, JOINTS_KINECTV2 = 0, 1, 2
 PLAN_COUNTS = ("ops", "waits_all", "records_all", "waits", "records", "lanes_all", "lanes_joined")     # the GRNET_PLAN_* enumerators, in order
 RASTER_MAX_DIM, RASTER_SLOTS = 4096, 16
+SEG_MAX_POINTS, SEG_MAX_SEGMENTS, SEG_MAX_WIDTH = 1024, 4096, 16
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
 
@@ -106,6 +107,13 @@ EXPORTS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_op_raster": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "grnet_op_raster_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grnet_spin_joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grnet_render_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "grnet_op_segments_setup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "grnet_op_raster_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
     "grnet_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "grnet_comm_probe": (C.c_int, []),
     "grnet_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int]),

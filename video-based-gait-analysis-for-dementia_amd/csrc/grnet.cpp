@@ -25,6 +25,9 @@ grnet::~grnet() {
     jreg_clear();
     faces_clear();
     if (raster_ws) (void)hipFree(raster_ws);
+    if (seg_stage) (void)hipHostFree(seg_stage);
+    for (hipEvent_t e : seg_stage_done)
+        if (e) (void)hipEventDestroy(e);
     if (temporal_ws) (void)hipFree(temporal_ws);
     if (gru_fault) (void)hipHostFree(gru_fault);
     if (arena) (void)hipFree(arena);

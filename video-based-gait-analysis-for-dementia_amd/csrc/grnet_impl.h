@@ -3,7 +3,8 @@
 //   grnet_weights.cpp  the weight loader (reference state_dict keys -> BN-folded, kernel-layout weights) and its entry points
 //   grnet_run.cpp      allocation, kernel choice, the launch path, the graph cache, the tuner
 //   grnet_hooks.cpp    the single-op test and timing hooks
-//   grnet_render.cpp   the mesh overlay: the face table, grnet_render_meshes and its two stage hooks
+//   grnet_render.cpp   the mesh overlay: the face table, grnet_render_meshes and its stage hooks; the render workspace
+//   grnet_skeleton.cpp the 3D skeleton view: grnet_render_segments and its two stage hooks, grnet_spin_joints
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -151,6 +152,16 @@ struct DeviceGuard {
 // Offsets for n buffers of which some pairs may not overlap (grnet_arena_assign, plan_arena): grnet_plan.cpp
 void arena_first_fit(const std::vector<int64_t>& sizes, const std::vector<std::vector<int>>& adj, int64_t align, std::vector<int64_t>& off, int64_t* total);
 
+// The render workspace, shared by the mesh overlay and the skeleton view (grnet_render.cpp): [depth words | vertex records of kRasterSlots meshes]
+constexpr int kSmplVerts = 6890;
+constexpr size_t kRasterDepthWords = (size_t)kRasterMaxDim * kRasterMaxDim;   // the depth images of a launch group share ONE largest image: 128 MiB
+size_t raster_record_bytes(int slots, int V);
+bool raster_dims_ok(int H, int W);
+struct DeviceBlock {                                        // freed when a hook returns, whichever way
+    void* p = nullptr;
+    ~DeviceBlock() { if (p) (void)hipFree(p); }
+};
+
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
@@ -230,6 +241,12 @@ struct grnet {
     RasterMesh rmesh{};
     void* rmesh_block = nullptr;
     void* raster_ws = nullptr;
+    // grnet_render_segments: the segment table of a call goes to the device through pinned host memory, a ring of kSegStageSlots tables each with
+    // the event recorded behind its copy, so the call enqueues and returns (grnet_skeleton.cpp)
+    static constexpr int kSegStageSlots = 4;
+    void* seg_stage = nullptr;
+    hipEvent_t seg_stage_done[kSegStageSlots] = {};
+    unsigned seg_stage_next = 0;
 
     // ------------------------------------------------------------------ the schedule, the tuning tables and the graph cache (grnet_run.cpp)
     std::vector<Op> ops_flat;   // the same ops placed on the lane streams by schedule_lanes(): the enqueue order
@@ -374,6 +391,8 @@ struct grnet {
     int dev_alloc(float** p, size_t floats);
     void jreg_clear();
     void faces_clear();
+    int seg_stage_slot(void** slot, hipEvent_t* done);   // grnet_skeleton.cpp: the next table of the ring, free to be written
+    int raster_workspace(const char* who);   // grnet_render.cpp: raster_ws, allocated at the first call of grnet_render_meshes(_ex) or grnet_render_segments
     const Op* nth_conv_op(int pos) const;
     int gru_fault_check();
     int taps_begin(size_t need, const char* what);

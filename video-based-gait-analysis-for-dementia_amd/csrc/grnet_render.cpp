@@ -5,9 +5,6 @@
 
 namespace {
 
-constexpr int kSmplVerts = 6890;
-constexpr size_t kRasterDepthWords = (size_t)kRasterMaxDim * kRasterMaxDim;   // the depth images of a launch group share ONE largest image: 128 MiB
-
 // faces (F,3) host -> ONE device block [faces 3F | row offsets V+1 | faces at each vertex 3F], the vertex -> face rows in ascending face order.
 // 0, or GRNET_EINVAL (an index outside [0, V)) / GRNET_ENOMEM / GRNET_EHIP with *why set; *block is the caller's to hipFree.
 int build_raster_mesh(const int32_t* faces, int F, int V, RasterMesh* out, void** block, std::string* why) {
@@ -39,8 +36,6 @@ int build_raster_mesh(const int32_t* faces, int F, int V, RasterMesh* out, void*
     return 0;
 }
 
-size_t raster_record_bytes(int slots, int V) { return (size_t)slots * ((size_t)V * 9 * 4 + 16); }
-
 // [depth words | q | normals | z | xy | bounding boxes] from an 8-byte aligned base
 RasterWork raster_carve(void* base, size_t depth_words, int slots, int V) {
     RasterWork w;
@@ -59,13 +54,6 @@ RasterView raster_view(const float* M_host, int H, int W) {
     return v;
 }
 
-bool dims_ok(int H, int W) { return H >= 1 && H <= kRasterMaxDim && W >= 1 && W <= kRasterMaxDim; }
-
-struct DeviceBlock {                                        // freed when a hook returns, whichever way
-    void* p = nullptr;
-    ~DeviceBlock() { if (p) (void)hipFree(p); }
-};
-
 // grnet_op_raster (lines = false) and grnet_op_raster_lines: one validation, one synchronisation
 int op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, const int32_t* faces_host, int F, int H, int W, int32_t* winner_dev, bool lines,
               void* stream) {
@@ -73,7 +61,7 @@ int op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, cons
     if (!h) return GRNET_EINVAL;
     if (!xy_dev || !z_dev || !faces_host || !winner_dev) return h->fail(GRNET_EINVAL, name + ": null pointer");
     if (V < 1 || F < 1) return h->fail(GRNET_EINVAL, name + ": V and F must be >= 1");
-    if (!dims_ok(H, W)) return h->fail(GRNET_EINVAL, name + ": image outside [1, " + std::to_string(kRasterMaxDim) + "]");
+    if (!raster_dims_ok(H, W)) return h->fail(GRNET_EINVAL, name + ": image outside [1, " + std::to_string(kRasterMaxDim) + "]");
     DeviceGuard guard(h->device);
     RasterMesh m{};
     DeviceBlock table, ws;
@@ -101,6 +89,17 @@ int op_raster(grnet_t* h, const int32_t* xy_dev, const float* z_dev, int V, cons
 }
 
 }  // namespace
+
+namespace grnet_detail {
+size_t raster_record_bytes(int slots, int V) { return (size_t)slots * ((size_t)V * 9 * 4 + 16); }
+bool raster_dims_ok(int H, int W) { return H >= 1 && H <= kRasterMaxDim && W >= 1 && W <= kRasterMaxDim; }
+}  // namespace grnet_detail
+
+int grnet::raster_workspace(const char* who) {
+    if (!raster_ws && hipMalloc(&raster_ws, kRasterDepthWords * 8 + raster_record_bytes(kRasterSlots, kSmplVerts)) != hipSuccess)
+        return fail(GRNET_ENOMEM, std::string(who) + ": hipMalloc of the workspace failed");
+    return 0;
+}
 
 void grnet::faces_clear() {
     if (!rmesh_block) return;
@@ -139,7 +138,7 @@ int grnet_render_meshes_ex(grnet_t* h, const float* verts_dev, int n, const floa
         return h->fail(GRNET_EINVAL, "grnet_render_meshes_ex: flags " + std::to_string(flags) + " has bits other than GRNET_RENDER_WIREFRAME (1)");
     const bool lines = flags & GRNET_RENDER_WIREFRAME;
     if (n < 0) return h->fail(GRNET_EINVAL, "grnet_render_meshes: n " + std::to_string(n) + " < 0");
-    if (!dims_ok(H, W))
+    if (!raster_dims_ok(H, W))
         return h->fail(GRNET_EINVAL, "grnet_render_meshes: image " + std::to_string(H) + " x " + std::to_string(W) + " outside [1, " + std::to_string(kRasterMaxDim) + "]");
     if (F < 1) return h->fail(GRNET_EINVAL, "grnet_render_meshes: F " + std::to_string(F) + " < 1");
     if (!h->rmesh_block) return h->fail(GRNET_ESTATE, "grnet_render_meshes before grnet_load_faces");
@@ -149,8 +148,7 @@ int grnet_render_meshes_ex(grnet_t* h, const float* verts_dev, int n, const floa
         if (image_index_host[i] < 0 || image_index_host[i] >= F)
             return h->fail(GRNET_EINVAL, "grnet_render_meshes: image_index[" + std::to_string(i) + "] = " + std::to_string(image_index_host[i]) + " outside [0, " + std::to_string(F) + ")");
     DeviceGuard guard(h->device);
-    if (!h->raster_ws && hipMalloc(&h->raster_ws, kRasterDepthWords * 8 + raster_record_bytes(kRasterSlots, kSmplVerts)) != hipSuccess)
-        return h->fail(GRNET_ENOMEM, "grnet_render_meshes: hipMalloc of the workspace failed");
+    if (int rc = h->raster_workspace("grnet_render_meshes")) return rc;
     const RasterWork work = raster_carve(h->raster_ws, kRasterDepthWords, kRasterSlots, kSmplVerts);
     const RasterView view = raster_view(M_host, H, W);
     const int slots = (int)std::min<size_t>(kRasterSlots, kRasterDepthWords / raster_depth_words(H, W));
@@ -191,7 +189,7 @@ int grnet_op_raster_setup(grnet_t* h, const float* verts_dev, int V, const int32
     if (!h) return GRNET_EINVAL;
     if (!verts_dev || !faces_host || !cam_dev || !xy_dev || !z_dev || !normals_dev) return h->fail(GRNET_EINVAL, "grnet_op_raster_setup: null pointer (only M_host may be NULL)");
     if (V < 1 || F < 1) return h->fail(GRNET_EINVAL, "grnet_op_raster_setup: V and F must be >= 1");
-    if (!dims_ok(H, W)) return h->fail(GRNET_EINVAL, "grnet_op_raster_setup: image outside [1, " + std::to_string(kRasterMaxDim) + "]");
+    if (!raster_dims_ok(H, W)) return h->fail(GRNET_EINVAL, "grnet_op_raster_setup: image outside [1, " + std::to_string(kRasterMaxDim) + "]");
     DeviceGuard guard(h->device);
     RasterMesh m{};
     DeviceBlock table, ws;

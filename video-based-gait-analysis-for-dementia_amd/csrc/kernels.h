@@ -362,6 +362,38 @@ hipError_t launch_raster_winner(const RasterView& v, RasterWork w, int* winner, 
 constexpr int kRasterLineWaveSteps = 16;     // an edge of more major steps than this is walked by the whole wave (unmeasured: NOTES_rejected)
 hipError_t launch_raster_lines_cover(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, hipStream_t s);
 hipError_t launch_raster_lines_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s);
+// the wireframe's depth clear alone, over `slots` depth images and their bounding boxes: the skeleton view's clear
+hipError_t launch_raster_lines_clear(const RasterView& v, RasterWork w, int slots, hipStream_t s);
+
+// The 3D skeleton view of demo.py --skeleton_view (demo.py:303-361, lib/utils/vis.py:571-587; csrc/skeleton_kernels.hip) ----
+// Wide line segments between projected points, ALL skeletons aimed at an image in ONE depth image.  A launch group is up to kRasterSlots
+// IMAGES, slot s with its own depth image and bounding box in RasterWork (q and nrm unused); the skeletons aimed at them go through in batches
+// whose records are kernel arguments.
+constexpr int kSegMaxPoints = 1024, kSegMaxSegments = 4096, kSegMaxWidth = 16;
+constexpr int kSegBatchSkeletons = 64;       // skeletons per launch of the setup and of the cover: their records are a kernel argument (1 KiB)
+constexpr int kSegGroupPoints = 65536;       // projected points (xy, depth) the workspace's record area holds at a time: 64 skeletons of 1024 points
+constexpr int kSegWindowLimit = 1 << 20;     // a window coordinate beyond this many pixels makes a point invalid; snapped: kRasterCoordLimit
+struct SegView {
+    float R[9];                    // the body rotation, row-major, applied first
+    float X[4], Y[4], Wh[4];       // x_win = cx + X.(p,1) / hw, y_win = cy + Y.(p,1) / hw, hw = Wh.(p,1): projection and window folded on the host in double
+    float cx, cy;
+    int H, W;
+};
+struct SegSegment { int a, b, width, colour; };   // point indices, pixels, the three bytes in memory order (byte k: bits 8k..8k+7)
+struct SegSkeleton { int index, slot, rank, pad; };  // row of the call's points, the image's slot in the group, its rank among the skeletons of that image
+struct SegBatch {                                 // the skeletons of one launch
+    int n;                         // <= kSegBatchSkeletons
+    int base;                      // skeleton k's points are records (base + k) * P ... of w.xy / w.z
+    SegSkeleton rec[kSegBatchSkeletons];
+};
+struct SegGroup { int n; int image[kRasterSlots]; };
+struct SegTables { const SegSegment* seg; int S, P; };
+// points (n,P,3) -> w.xy / w.z of the batch's skeletons (INT_MIN in both coordinates: invalid) and the slots' bounding boxes grown by pad
+hipError_t launch_segments_setup(const float* points, const SegView& v, SegTables t, const SegBatch& b, int pad, RasterWork w, hipStream_t s);
+// one wave per (skeleton, segment): 64-bit atomicMin of (ordered(depth) << 32) | (rank S + segment) on every pixel of the wide line
+hipError_t launch_segments_cover(const SegView& v, SegTables t, const SegBatch& b, RasterWork w, hipStream_t s);
+// the colour of the winning segment into every covered pixel of the slots' bounding boxes: images (F,H,W,3) uint8, every other byte untouched
+hipError_t launch_segments_resolve(const SegView& v, const SegGroup& g, SegTables t, RasterWork w, unsigned char* images, hipStream_t s);
 
 // GRU gait encoder (gait_feat_encoder.py:79-104) ------------------------------------------------
 struct GruWeights {

@@ -7,6 +7,11 @@
 // |X|, |Y| <= 2^28: dP < 2^29 + 1, |Q0 dP| < 2^58, |(.) dQ| < 2^59, D = 256 dP < 2^38; everything fits int64.
 // One division gives n and the remainder at a lane's first m (line_minor); a stride of s major steps adds s * 256 dQ = sq D + sr to the
 // numerator, 0 <= sr < D (line_stride: s = 1 needs no division), so line_advance is an add and one carry and gives the same integers.
+//
+// Wide lines (the skeleton view; skeleton_kernels.hip): a line of width w pixels, 1 <= w <= 16, covers at major index m the w
+// minor indices n0 .. n0 + w - 1, n0 = floor((Q0 dP + (256 m + 128 - P0) dQ - (w - 1) 128 dP) / (256 dP)) -- OpenGL's rule for non-antialiased wide
+// lines: the column of w pixels starts (w - 1) / 2 pixels below the line.  The offset is constant along the line, so it goes into the numerator
+// once (line_minor_wide; |(w - 1) 128 dP| < 2^41) and the stepping above is unchanged.  w = 1 is line_minor.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -51,6 +56,16 @@ GRK_LINES_HD void line_minor(const LineRec& r, int m, long long& n, long long& r
     constexpr int sub = 1 << kRasterSnapBits, half = sub / 2;
     const long long dP = (long long)r.P1 - r.P0, dQ = (long long)r.Q1 - r.Q0, D = sub * dP;
     const long long num = (long long)r.Q0 * dP + ((long long)m * sub + half - r.P0) * dQ;
+    n = num / D;
+    rem = num - n * D;
+    if (rem < 0) rem += D, --n;
+}
+
+// n0 of a line of width w at major index m (w = 1: line_minor)
+GRK_LINES_HD void line_minor_wide(const LineRec& r, int m, int w, long long& n, long long& rem) {
+    constexpr int sub = 1 << kRasterSnapBits, half = sub / 2;
+    const long long dP = (long long)r.P1 - r.P0, dQ = (long long)r.Q1 - r.Q0, D = sub * dP;
+    const long long num = (long long)r.Q0 * dP + ((long long)m * sub + half - r.P0) * dQ - (long long)(w - 1) * half * dP;
     n = num / D;
     rem = num - n * D;
     if (rem < 0) rem += D, --n;

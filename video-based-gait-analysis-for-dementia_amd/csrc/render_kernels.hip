@@ -41,38 +41,15 @@
 //   interpolated between the two end points with t, then the same shade and store.  A line's pixel is the one whose SQUARE holds the line, so
 //   its centre may lie up to half a pixel outside the mesh's bounding box: the clear and the resolve of a wireframe take the pixels whose
 //   squares meet the box (pixel_range_squares), a superset of the fill's.
-#include "kernels.h"
+#include "raster_device.h"
 
 namespace grk {
 namespace {
-
-constexpr int kSub = 1 << kRasterSnapBits;
-constexpr int kHalf = kSub / 2;
-constexpr unsigned long long kDepthClear = ~0ull;
-constexpr int kTileW = 64, kTileH = 4;                        // pixels per 256-thread workgroup of the clear / resolve / winner kernels
-
-__device__ __forceinline__ int snap(float win) {
-    float v = floorf(win * (float)kSub + 0.5f);
-    v = fminf(fmaxf(v, -(float)kRasterCoordLimit), (float)kRasterCoordLimit);      // fmaxf(NaN, a) = a
-    return (int)v;
-}
-
-__device__ __forceinline__ int wave_max64(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // The pixels whose centres lie inside [lo, hi] (snapped units) on an axis of n pixels: first and last index, first > last if there is none
 __device__ __forceinline__ void pixel_range(int lo, int hi, int n, int& first, int& last) {
     first = max(0, (lo - kHalf + kSub - 1) >> kRasterSnapBits);
     last = min(n - 1, (hi - kHalf) >> kRasterSnapBits);
-}
-
-// The pixels whose squares [256 i, 256 i + 256) meet [lo, hi]: where a line between lo and hi can put a fragment
-__device__ __forceinline__ void pixel_range_squares(int lo, int hi, int n, int& first, int& last) {
-    first = max(0, lo >> kRasterSnapBits);
-    last = min(n - 1, hi >> kRasterSnapBits);
 }
 
 template <bool kLines>
@@ -93,11 +70,6 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
 
 // a top or a left edge in image space, for the edge a -> b of a triangle that is counter-clockwise in GL window space
 __device__ __forceinline__ bool top_left(int ax, int ay, int bx, int by) { return by < ay || (by == ay && bx < ax); }
-
-__device__ __forceinline__ unsigned ordered_bits(float z) {
-    const unsigned u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(256) void raster_setup_kernel(const float* __restrict__ verts, const float* __restrict__ cams, RasterChunk c, RasterView view,
                                                            int n_verts, RasterWork w) {
@@ -217,8 +189,7 @@ __global__ __launch_bounds__(256) void raster_cover_kernel(RasterView view, Rast
     }
 }
 
-// The edge records and their integer arithmetic: raster_lines.h
-__device__ __forceinline__ float line_t(const LineRec& r, int m) { return (float)(m * kSub + kHalf - r.P0) / (float)(r.P1 - r.P0); }
+// The edge records and their integer arithmetic: raster_lines.h; line_t: raster_device.h
 
 __device__ __forceinline__ void line_fragment(const LineRec& r, int m, long long n, unsigned id, const RasterView& view, unsigned long long* depth) {
     if (n < 0 || n >= (r.xmajor ? view.H : view.W)) return;
@@ -391,6 +362,11 @@ hipError_t launch_raster_lines_cover(const RasterChunk& c, const RasterView& v, 
 
 hipError_t launch_raster_lines_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s) {
     hipLaunchKernelGGL(raster_resolve_kernel<true>, pixel_grid(v, c.n), dim3(256), 0, s, c, v, m, w, images);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_lines_clear(const RasterView& v, RasterWork w, int slots, hipStream_t s) {
+    hipLaunchKernelGGL(raster_clear_kernel<true>, pixel_grid(v, slots), dim3(256), 0, s, v, w);
     return hipGetLastError();
 }
 

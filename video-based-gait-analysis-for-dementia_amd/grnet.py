@@ -870,6 +870,104 @@ class GRNet:
         """op_raster for the wireframe: 3 face + k of the winning edge per pixel, k = 0: v0->v1, 1: v1->v2, 2: v2->v0 (grnet_op_raster_lines)."""
         return self._op_raster("grnet_op_raster_lines", xy, z, faces, H, W)
 
+    # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
+    def spin_joints(self, joints29, verts, joints="spin49"):
+        """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a
+        forward returns them, host or device -> (n,49|29|25,3) device tensor, bit-identical to smooth_pose's joints for the same vertices.
+        n is not limited by max_frames; nothing synchronises."""
+        if joints not in self._JOINT_KINDS:
+            raise ValueError(f"joints must be one of {sorted(self._JOINT_KINDS)}, got {joints!r}")
+        kind, nj = self._JOINT_KINDS[joints]
+        kp = torch.as_tensor(joints29).to(self.device, torch.float32).contiguous()
+        v = torch.as_tensor(verts).to(self.device, torch.float32).contiguous()
+        if kp.dim() != 3 or tuple(kp.shape[1:]) != (29, 3) or v.dim() != 3 or tuple(v.shape[1:]) != (6890, 3) or kp.shape[0] != v.shape[0]:
+            raise ValueError(f"joints29 must be (n,29,3) and verts (n,6890,3), got {tuple(kp.shape)} and {tuple(v.shape)}")
+        out = torch.empty(kp.shape[0], nj, 3, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_spin_joints(self._h, kp.data_ptr(), v.data_ptr(), kp.shape[0], kind, out.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_spin_joints")
+        return out
+
+    @staticmethod
+    def _segment_view(view, R):
+        """(proj (16) float64, window (4) float64, R (9) float32 or None), contiguous, for the C ABI; view=None: pipeline.skeleton_view()."""
+        if view is None:
+            from . import pipeline
+            view = pipeline.skeleton_view()
+        proj = np.ascontiguousarray(np.asarray(view[0], np.float64).reshape(16))
+        window = np.ascontiguousarray(np.asarray(view[1], np.float64).reshape(4))
+        Rh = None if R is None else np.ascontiguousarray(np.asarray(R, np.float32).reshape(9))
+        return proj, window, Rh
+
+    @staticmethod
+    def _segment_table(segments, widths):
+        seg = np.ascontiguousarray(np.asarray(segments, np.int64).reshape(-1, 2).clip(-1, 2**31 - 1), dtype=np.int32)
+        wid = np.ascontiguousarray(np.asarray(widths, np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
+        if wid.shape[0] != seg.shape[0]:
+            raise ValueError(f"segments and widths disagree on S: {seg.shape[0]}, {wid.shape[0]}")
+        return seg, wid
+
+    def render_segments(self, images, points, segments, colours, widths, image_index, R=None, view=None, rgb=True):
+        """Draw n skeletons as wide line segments into uint8 device images (F,H,W,3) IN PLACE and return them (grnet_render_segments; the rules:
+        DESIGN.md 4.6).  points (n,P,3), host or device; segments (S,2) point indices, colours (S,3) uint8 (r,g,b), widths (S) pixels in [1,16];
+        image_index (n): the image each skeleton is drawn into -- all skeletons of an image share ONE depth buffer, the nearer segment wins,
+        at equal depth the one drawn first.  R: the 3x3 body rotation applied to the points first (None: identity); view: (P 4x4, window
+        (x0,x1,y0,y1)), None for pipeline.skeleton_view().  rgb: the images are RGB (pipeline's frames) and a pixel gets (r,g,b) as given;
+        rgb=False: BGR images, the triple goes down reversed so that the screen shows the same colour.  The C call only enqueues (the host-side
+        tables given as numpy arrays are read before it returns); n is not limited by max_frames."""
+        if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda \
+                or not images.is_contiguous():
+            raise ValueError("images must be a contiguous uint8 (F,H,W,3) tensor on the device")
+        F, H, W = images.shape[:3]
+        p = torch.as_tensor(points).to(self.device, torch.float32).contiguous()
+        if p.dim() != 3 or p.shape[2] != 3:
+            raise ValueError(f"points must be (n,P,3), got {tuple(p.shape)}")
+        n, P = p.shape[:2]
+        seg, wid = self._segment_table(segments, widths)
+        col = np.asarray(colours).reshape(-1, 3)
+        if col.shape[0] != seg.shape[0] or col.size and (col.min() < 0 or col.max() > 255):
+            raise ValueError(f"colours must be (S,3) bytes with S = {seg.shape[0]}, got {col.shape} in [{col.min() if col.size else 0}, {col.max() if col.size else 0}]")
+        col = np.ascontiguousarray(col if rgb else col[:, ::-1], dtype=np.uint8)
+        idx = np.ascontiguousarray(np.asarray(image_index, np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
+        if idx.shape[0] != n:
+            raise ValueError(f"points and image_index disagree on n: {n}, {idx.shape[0]}")
+        proj, window, Rh = self._segment_view(view, R)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_render_segments(self._h, p.data_ptr(), n, P, ptr(seg), seg.shape[0], ptr(col), ptr(wid), ptr(idx),
+                                             ptr(Rh) if Rh is not None else None, ptr(proj), ptr(window), images.data_ptr(), F, H, W, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_render_segments")
+        return images
+
+    def op_segments_setup(self, points, H, W, R=None, view=None):
+        """points (P,3) -> (xy (P,2) int32 snapped window coordinates, INT32_MIN in both for an invalid point; depth (P)) on the device
+        (grnet_op_segments_setup)."""
+        p = torch.as_tensor(points).to(self.device, torch.float32).reshape(-1, 3).contiguous()
+        proj, window, Rh = self._segment_view(view, R)
+        P = p.shape[0]
+        xy = torch.empty(P, 2, dtype=torch.int32, device=self.device)
+        d = torch.empty(P, dtype=torch.float32, device=self.device)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_segments_setup(self._h, p.data_ptr(), P, ptr(Rh) if Rh is not None else None, ptr(proj), ptr(window), H, W,
+                                               xy.data_ptr(), d.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_segments_setup")
+        return xy, d
+
+    def op_raster_segments(self, xy, depth, segments, widths, H, W):
+        """Snapped points xy (P,2) int32 and depth (P) -> the winning segment per pixel (H,W) int32 in image rows, -1 where uncovered
+        (grnet_op_raster_segments)."""
+        xy = torch.as_tensor(xy).to(self.device, torch.int32).reshape(-1, 2).contiguous()
+        d = torch.as_tensor(depth).to(self.device, torch.float32).reshape(-1).contiguous()
+        seg, wid = self._segment_table(segments, widths)
+        out = torch.empty(H, W, dtype=torch.int32, device=self.device)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_raster_segments(self._h, xy.data_ptr(), d.data_ptr(), xy.shape[0], ptr(seg), seg.shape[0], ptr(wid), H, W,
+                                                out.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_raster_segments")
+        return out
+
     # single-op hooks for kernel parity tests
     def op_conv2d(self, x, w, bias=None, stride=1, relu=False, add=None, tile_hint=0):
         n, cin, h, wd = x.shape

@@ -401,6 +401,94 @@ def prepare_rendering_results(results, nframes):
     return frame_results
 
 
+# ----------------------------------------------------------------------------- the 3D skeleton view (demo.py:238-247, 303-361; vis.py:571-587)
+SKELETON_ELEV, SKELETON_AZIM = 200.0, -27.0                   # demo.py:311 view_init
+SKELETON_LIMITS = ((-0.6, 0.6), (-1.0, 1.0), (-1.0, 1.0))     # demo.py:312-314
+SKELETON_TICKS = (7, 11, 11)                                  # demo.py:315-319: linspace over the limits
+SKELETON_WINDOW = (-0.095, 0.09, -0.095, 0.09)                # what matplotlib's 3D axes show of the projected plane: (x0, x1, y0, y1)
+BONE_COLOURS = ((215, 48, 39), (69, 117, 180))                # vis.py:575-585: even bones, odd bones (RGB)
+GRID_COLOUR = (176, 176, 176)                                 # matplotlib's grid colour, #b0b0b0
+# Bones as pairs of joint indices, in the order the reference draws them (the order decides the colour and, at equal depth, the winner).
+# 'spin': over the 49 SPIN joints, whose first 25 are OpenPose's BODY_25 -- head and trunk, arms, legs, face, feet, and nose -> headtop (38).
+# 'kinectv2': over the 25 Kinect v2 joints -- spine, arms from the thorax (20), hands, legs.  tests/golden/skeleton_view.npz pins both.
+_BONES = {
+    "spin": ((0, 1), (1, 2), (1, 5), (2, 3), (5, 6), (3, 4), (6, 7), (1, 8), (8, 12), (8, 9), (12, 13), (9, 10), (13, 14), (10, 11), (0, 16), (0, 15),
+             (16, 18), (15, 17), (21, 20), (24, 23), (19, 20), (22, 23), (19, 21), (22, 24), (14, 21), (11, 24), (0, 38)),
+    "kinectv2": ((0, 1), (20, 2), (1, 20), (2, 3), (20, 4), (20, 8), (4, 5), (8, 9), (5, 6), (9, 10), (6, 7), (10, 11), (7, 21), (11, 23), (6, 22),
+                 (10, 24), (0, 12), (0, 16), (12, 13), (16, 17), (13, 14), (17, 18), (14, 15), (18, 19)),
+}
+
+
+def skeleton_view():
+    """(P (4,4) float64, window (x0, x1, y0, y1)): matplotlib's Axes3D.get_proj() for the reference's axes -- view_init(elev=200, azim=-27), the
+    limits above, and matplotlib's defaults: box aspect 4:4:3 (times 25/21), eye distance 10, focal length 1, roll 0, vertical axis z -- by closed
+    formula; matplotlib is not imported.  Projected coordinates are (P p)[0,1] / (P p)[3]; the axes show the window of them."""
+    e, a = np.deg2rad(SKELETON_ELEV), np.deg2rad(SKELETON_AZIM)
+    lim = np.array(SKELETON_LIMITS)
+    aspect = np.array([4.0, 4.0, 3.0])
+    aspect *= 1.8294640721620434 * 25 / 24 / np.linalg.norm(aspect)        # matplotlib's set_box_aspect: (4, 4, 3) * 25/84 to 1e-9, i.e. x and y 25/21
+    dist, focal = 10.0, 1.0
+    world = np.eye(4)                                          # the limits -> the box [0, aspect]
+    world[[0, 1, 2], [0, 1, 2]] = aspect / (lim[:, 1] - lim[:, 0])
+    world[:3, 3] = -lim[:, 0] * aspect / (lim[:, 1] - lim[:, 0])
+    w = np.array([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)])      # unit, from the box's centre to the eye
+    eye = aspect / 2 + dist * focal * w
+    norm_elev = (SKELETON_ELEV + 180.0) % 360.0 - 180.0       # beyond +-90 degrees the axes stand on their head
+    up = np.array([0.0, 0.0, -1.0 if abs(norm_elev) > 90.0 else 1.0])
+    u = np.cross(up, w)
+    u /= np.linalg.norm(u)
+    v = np.cross(w, u)
+    look = np.eye(4)
+    look[:3, :3] = np.stack([u, v, w])
+    look[:3, 3] = -np.stack([u, v, w]) @ eye
+    zfront, zback = -dist, dist
+    persp = np.array([[focal, 0, 0, 0], [0, focal, 0, 0], [0, 0, (zfront + zback) / (zfront - zback), -2 * zfront * zback / (zfront - zback)], [0, 0, -1, 0]])
+    return persp @ look @ world, SKELETON_WINDOW
+
+
+def skeleton_bones(name):
+    """(bones (B,2) int64, colours (B,3) uint8 RGB) of the skeleton the view draws for --joint_type ``name``: 'spin' (the 49 joints) or
+    'kinectv2' (25), the two skeletons the library emits as 3D joints; the colours alternate (vis.py:585).  Any other name raises NameError,
+    as convert_kps does."""
+    if name not in _BONES:
+        raise NameError(f"name 'get_{name}_skeleton' is not defined")
+    bones = np.array(_BONES[name], np.int64)
+    return bones, np.array([BONE_COLOURS[i % 2] for i in range(len(bones))], np.uint8)
+
+
+def skeleton_grid():
+    """(points (N,3) float64, segments (N/2,2) int64): the grid lines on the three FAR panes of the view's box, at the reference's ticks.  Of
+    the two panes of an axis the far one is that whose centre has the larger homogeneous coordinate P[3] . (c, 1)."""
+    P, _ = skeleton_view()
+    lim = np.array(SKELETON_LIMITS)
+    ticks = [np.linspace(lo, hi, k) for (lo, hi), k in zip(SKELETON_LIMITS, SKELETON_TICKS)]
+    pts = []
+    for axis in range(3):
+        far = lim[axis, 1] if P[3, axis] * lim[axis, 1] > P[3, axis] * lim[axis, 0] else lim[axis, 0]
+        b, c = [k for k in range(3) if k != axis]
+        for along, across in ((b, c), (c, b)):                 # lines at the ticks of `along`, spanning `across`
+            for t in ticks[along]:
+                for end in lim[across]:
+                    p = np.zeros(3)
+                    p[axis], p[along], p[across] = far, t, end
+                    pts.append(p)
+    pts = np.array(pts)
+    return pts, np.arange(len(pts), dtype=np.int64).reshape(-1, 2)
+
+
+def body_rotation(j49):
+    """demo.py:239-247: the rotation that turns the body towards the view's x axis, from ONE frame of the 49 SPIN joints (49,3): h = lhip - rhip
+    (joints 28, 27), v = thorax - hip (40, 39), both normalised; R = orthogonal_procrustes([[1,0,0]], cross(h, v)) by scipy's formula.  The input
+    has rank 1: only the first row, e_x R = cross(h, v) / |cross(h, v)|, is determined; the rest is what LAPACK's SVD returns, in the
+    reference as here.  Points are drawn as R p (demo.py:325)."""
+    j = np.asarray(j49, np.float64).reshape(49, 3)
+    h, v = j[28] - j[27], j[40] - j[39]
+    h, v = h / np.linalg.norm(h), v / np.linalg.norm(v)
+    A, B = np.array([[1.0, 0.0, 0.0]]), np.cross(h, v).reshape(1, 3)
+    u, _, vt = np.linalg.svd((B.T @ A).T)
+    return u @ vt
+
+
 def write_obj(path, verts, faces):
     """The mesh renderer.py:82-86 exports per person and frame: the vertices turned by 180 degrees about x, (x, -y, -z), and the faces, 1-based."""
     v = np.asarray(verts, np.float64) * np.array([1.0, -1.0, -1.0])
