@@ -18,7 +18,8 @@
 //
 // Roles (as conv_bf16.hip): A[cout l&15][k = 8(l>>4)+j] = W[tap][cout][cin], B[k][pixel l&15] = slot[pixel + tap][cin], D[cout 4(l>>4)+r][pixel l&15].
 // Wave (cb, pg) owns CS x 16 output channels x PS column tiles; per k-step (one tap x 32 input channels): CS weight fragments (global, 16 B
-// per lane, prefetched two steps ahead in a ring of three register sets), PS pixel fragments (ds_read_b128), CS x PS MFMAs.
+// per lane, prefetched two steps ahead in a ring of three register sets), PS pixel fragments (ds_read_b128), CS x PS MFMAs.  The tile geometry and that
+// k-loop (plane_kloop) are defined once for this file, conv_bf16_wide.hip and conv_bf16_s2.hip: conv_bf16_plane.h.
 //
 // In place: a convolution's outputs are all held in accumulators until every wave has finished READING the plane (barrier), then written
 // over it (bias, ReLU, bf16, 8 bytes per lane and tile), barrier, next convolution.  The residual of a BasicBlock costs no registers: when
@@ -29,6 +30,7 @@
 // path up to fp32 summation order (output-rounding ties); tests/test_gpu_conv_bf16.py compares both and the fp32 oracle on bf16-rounded operands.
 #include "kernels.h"
 #include "device.h"
+#include "conv_bf16_plane.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -41,76 +43,14 @@ namespace {
 // frame 0, W + 1: zero, W + 2 .. 2 W + 1: frame 1), so a workgroup's weight stream -- 9.4 MB per chain from L2, the bound of that chain: two single-frame workgroups
 // per CU pulled 46 B/clk of the CU's 64 -- serves two frames.  The separator row is never written (the column mask below), so it stays the zero padding of both.
 template <int C, int W, int F = 1>
-struct ChainGeom {
-    static constexpr int P = W + 1;                         // row pitch in slots
-    static constexpr int SB = 2 * C + 32;                   // slot stride, bytes
-    static constexpr int O0 = P + 1;                        // slot of pixel (0, 0) = first output column
+struct ChainGeom : PlaneGeom<C, C, W, F * W + F - 1, F * W> {
+    typedef PlaneGeom<C, C, W, F * W + F - 1, F * W> B;
     static constexpr int H = F * W + F - 1;                 // plane rows that carry outputs (the separator rows included)
-    static constexpr int NOUT = H * P - 1;                  // output columns o0 .. slot of pixel (W-1, W-1) of the last frame
-    static constexpr int CS = 2;                            // 16-channel blocks per wave
-    static constexpr int WCB = C / (16 * CS);               // waves along the output channels
-    static constexpr int WPG = 8 / WCB;                     // waves along the pixels
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG;      // column tiles per wave
-    static constexpr int NT = WPG * PS;                     // column tiles
-    static constexpr int NSLOT = O0 + NT * 16 + P + 2;      // highest slot a tap reads: O0 + 16 NT - 1 + P + 1; + one spare slot (the read-ahead of a convolution's last step)
-    static constexpr int LDS = NSLOT * SB;
-    static constexpr int NS = 9 * (C / 32);                 // k-steps per convolution
-    static constexpr int UPP = C / 8;                       // 16-byte units per pixel
-    static constexpr int NU = (F * W * W * UPP + 511) / 512;    // units per thread of the plane
-    static_assert(C % 32 == 0 && WCB >= 1 && WCB <= 8 && 8 % WCB == 0, "wave grid");
-    static_assert((SB / 16) % 2 == 0 && ((SB / 32) % 2) == 1, "slot stride must be 32 * odd bytes (conflict-free b128 reads)");
-    static_assert(NS % 3 == 0, "the weight ring has three register sets");
+    static constexpr int LDS = B::NSLOT * B::SB;
+    static constexpr int NU = B::NUO;                       // units per thread of the plane: all of it arrives and leaves
     static_assert(LDS <= 160 * 1024, "the plane must fit the LDS");
-    static_assert(F > 1 || (PS - 1) * 16 * SB + (2 * P + 2) * SB + (C / 32) * 64 < 65536, "ds_read immediates");      // (F = 2: 70 KB of plane, hipcc keeps a second base register)
+    static_assert(F > 1 || B::IMM16, "ds_read immediates");      // (F = 2: 70 KB of plane, hipcc keeps a second base register)
 };
-
-// One convolution's k-loop over the LDS plane of the frame-resident chain.
-// Per k-step (tap x 32-channel chunk): CS weight fragments requested two steps ahead (ring of three register sets), and per column tile
-// one pixel fragment: tile ps of step s + 1 is requested right behind the MFMAs of tile ps of step s, into the register set they have
-// just read -- a read has PS - 1 MFMA pairs (and the SIMD's other wave) to land.  Left to itself hipcc sinks every read and every
-// weight load to its first use (one register set, lgkmcnt(0) in front of every MFMA pair, vmcnt(0) per step: the loop ran at LDS
-// latency); the sched_barrier behind every group pins the order written here.  The chunk loop stays a loop (9 taps unrolled: the
-// ring positions are static, 9 = 3 x 3), so every address is a per-chunk base + immediates.
-// bread: B operand of tap (0,0), chunk 0, tile 0 of this lane; wc / wn: the weights of this / the next convolution (UNIFORM pointers: with the
-// lane's share kept apart as the 32-bit byte offset wlb every weight load is `global_load v, v_off, s[base]` -- a 64-bit per-lane pointer per
-// k-step cost two registers each, which hipcc hoisted out of the band loop of the frame kernel and spilled); wr[0], wr[1] hold steps 0, 1 on
-// entry and the next convolution's on exit.
-// RING: register sets of the weight ring = prefetch distance + 1.  3 (two k-steps ahead) where a k-step is >= 14 MFMAs; 9 (eight ahead) for the
-// 256-channel 7x7 chain, whose k-steps are 8 MFMAs = 128 cycles: two steps did not cover an L2 round trip (SQ_WAIT_ANY 0.73 of its wave cycles).
-// RING must divide the 9 taps of a chunk (the ring positions are static in the unrolled tap loop).
-template <int C, int P, int SB, int CS, int PS, int RING = 3>
-__device__ __forceinline__ void chain_kloop(f32x4 (&acc)[CS][PS], bf16x8 (&wr)[RING][CS], const unsigned char* bread, const u16* wc, const u16* wn, unsigned wlb) {
-    constexpr int NCH = C / 32, D = RING - 1;
-    static_assert(9 % RING == 0, "the ring must divide the taps");
-    bf16x8 bfr[PS];
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB);
-#pragma unroll 1
-    for (int chunk = 0; chunk < NCH; ++chunk) {
-        const unsigned char* bch = bread + chunk * 64;
-        const u16* wch = wc + (size_t)chunk * 9 * C * 32;
-        const bool lastc = chunk == NCH - 1;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            {                                                             // weights of step s + D (taps 9 .. = the next chunk's / the next convolution's first ones)
-                const u16* src = wch + (size_t)(tap + D) * C * 32;
-                if (tap + D >= 9) src = lastc ? wn + (size_t)(tap + D - 9) * C * 32 : src;
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) wr[(tap + D) % RING][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(src + cs * 16 * 32) + wlb);
-            }
-            // the next step's pixel fragments: tap + 1 of this chunk, or tap 0 of the next (the last step of a convolution reads ahead into
-            // the slot padding / the spare slot: nobody uses those values)
-            const int noff = tap < 8 ? (((tap + 1) / 3) * P + ((tap + 1) % 3)) * SB : 64;
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[tap % RING][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(bch + ps * 16 * SB + noff);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
 
 // Registers: the 256-channel 7x7 chain (L2-bound on its weight stream, MFMA-busy 0.41) is held to 96 (five waves per SIMD; 32 bytes of scratch): two of its workgroups fit
 // a CU -- 158 -> 147 us per chain alone at 256 frames -- and one fits BESIDE a workgroup of the 128-channel 14x14 chain (2 x 96 + 2 x 160 registers, 45 + 74 KB of LDS), which
@@ -189,7 +129,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 256 &&
         const u16* wc = reinterpret_cast<const u16*>(a.w[ci]);
         const int cn = ci + 1 < a.nconv ? ci + 1 : ci;                        // the last convolution re-requests itself (nobody waits for it)
         const u16* wn = reinterpret_cast<const u16*>(a.w[cn]);
-        chain_kloop<C, P, SB, CS, PS, RING>(acc, wr, bread, wc, wn, wlb);
+        plane_kloop<G, CS, PS, RING>(acc, wr, bread, wc, wn, (size_t)C * 32, C / 32, true, wlb);
         // ---- in-place epilogue
         const bool first = (ci & 1) == 0;                                     // conv1 of a BasicBlock: the plane still holds the block's input x
         f32x4 bnext[CS];
@@ -203,8 +143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 256 &&
                 unsigned char* pos = owrite + ps * 16 * SB + cs * 32;
                 u32x2 r = u32x2{0u, 0u};
                 if (first) r = *reinterpret_cast<const u32x2*>(pos);
-                const f32x4 v = acc[cs][ps];
-                const u32x2 pk = u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))};
+                const u32x2 pk = pack4_relu(acc[cs][ps]);
                 if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(pos) = pk;
                 f32x4 nx = bnext[cs];
                 if (first) { nx[0] += bf_lo(r[0]); nx[1] += bf_hi(r[0]); nx[2] += bf_lo(r[1]); nx[3] += bf_hi(r[1]); }
@@ -232,20 +171,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(C == 256 &&
 // reads them; rows y0 .. y0 + R - 1 -> HBM.  (A kernel with the workgroup = one band, one or two per CU, measured 51-53 us per block against 43 for the
 // frame-persistent kernel below: NOTES_rejected.md.)
 template <int C, int W, int R>
-struct BandGeom {
-    static constexpr int P = W + 1, SB = 2 * C + 32;
+struct BandGeom : PlaneGeom<C, C, W, R + 2, R> {            // outputs on plane rows 1 .. R + 2 (conv1's)
+    typedef PlaneGeom<C, C, W, R + 2, R> B;
     static constexpr int ROWS = R + 4;                      // plane rows: image rows y0 - 2 .. y0 + R + 1
-    static constexpr int O0 = P + 1;                        // plane row 1, x = 0
-    static constexpr int NOUT = (R + 2) * P - 1;            // plane rows 1 .. R + 2
-    static constexpr int CS = 2, WCB = C / 32, WPG = 8 / WCB;
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int NSLOT = O0 + NT * 16 + P + 2;
-    static constexpr int LDS = NSLOT * SB;
-    static constexpr int UPP = C / 8;
-    static constexpr int NUI = (ROWS * W * UPP + 511) / 512, NUO = (R * W * UPP + 511) / 512;
-    static constexpr int NB = (W + R - 1) / R;              // bands per frame
-    static_assert(((SB / 32) % 2) == 1 && LDS <= 160 * 1024 && PS <= 32 && NSLOT >= ROWS * P + 1, "band geometry");
-    static_assert((PS - 1) * 16 * SB + (2 * P + 2) * SB + (C / 32) * 64 < 65536, "ds_read immediates");
+    static constexpr int LDS = B::NSLOT * B::SB;
+    static_assert(LDS <= 160 * 1024 && B::NSLOT >= ROWS * B::P + 1, "band geometry");
+    static_assert(B::IMM16, "ds_read immediates");
 };
 
 // ---- The same block with the WORKGROUP = ONE FRAME walking its NB = 56 / R bands, the next band arriving by LDS-DMA under the current band's MFMAs.
@@ -265,7 +196,7 @@ struct BandGeom {
 
 
 // k-loop of one 32 -> 32 convolution with the weights in LDS: per tap CS weight fragments (one tap ahead, two register sets) and PS pixel fragments
-// (ring as in chain_kloop); no vector-memory operation.  wl: this lane's fragment of tap 0, block 0 (swizzled part); 2 KB per tap, 1 KB per block.
+// (ring as in plane_kloop); no vector-memory operation.  wl: this lane's fragment of tap 0, block 0 (swizzled part); 2 KB per tap, 1 KB per block.
 template <int P, int SB, int CS, int PS>
 __device__ __forceinline__ void chain_kloop_ldsw(f32x4 (&acc)[CS][PS], const unsigned char* bread, const unsigned char* wl) {
     bf16x8 bfr[PS], wr[2][CS];

@@ -29,8 +29,6 @@ namespace grk {
 
 namespace {
 
-__device__ __forceinline__ u32x2 pack4_relu(const f32x4 v) { return u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))}; }
-
 constexpr int kW2Bytes = 2 * 9 * 64 * 64;                     // the 64 -> 64 3x3 weights: [chunk 2][tap 9][cout 64][32 k] bf16, 64-byte rows
 constexpr int kTSB = 160;                                     // slot stride of a 64-channel pixel in LDS: 128 + 32 bytes = 32 x odd (conflict-free b128 reads of 16 consecutive slots)
 

@@ -1,5 +1,6 @@
-// bf16 path: the 3x3 stride-2 layers with a band (or a ring of rows) of the input resident in LDS.  The flattened, padded LDS plane, the MFMA roles and the
-// weight ring are those of the frame-resident chain kernels (conv_bf16_chain.hip: its header describes them) and of conv_bf16_wide.hip.
+// bf16 path: the 3x3 stride-2 layers with a band (or a ring of rows) of the input resident in LDS.  The flattened, padded LDS plane and the MFMA roles are
+// those of the frame-resident chain kernels (conv_bf16_chain.hip: its header describes them); the tile geometry and the k-loop with its weight ring are the
+// LDS-plane family's one definition (conv_bf16_plane.h).
 //
 // ---- ONE 3x3 STRIDE-2 convolution (fuse layers' down paths hrnet.py:213-241, transitions hrnet.py:348-387, the stem's second convolution hrnet.py:470-475) with a
 // band of the input resident in LDS.  conv_bf16_nhwc runs these layers at 0.05-0.16 of the matrix peak and 2-3 x their HBM time: 112-pixel tiles of ~60
@@ -9,66 +10,34 @@
 // sub(py, px) at (Y + oy, X + ox) with py = (dy != 1), oy = -(dy == 0) and likewise for x, and inside its sub-plane every tap IS a constant offset again.
 // The LDS-DMA does the de-interleaving for free: its source address is per lane.  Each sub-plane is flattened with pitch Wo + 1 (column X' = -1 is the shared
 // zero column, row Y' = y0 - 1 the zero / halo row), R + 1 rows; output column o = (Y - y0)(Wo + 1) + X.  Everything else -- CP input channels per pass,
-// weight ring, MFMA roles, in-place tile through LDS -- is conv_bf16_wide_band's; the epilogue adds the layer's fused addends (nearest-upsampled terms of
+// weight ring, MFMA roles, in-place tile through LDS -- is as in conv_bf16_wide_band (the k-loop IS the same one: plane_kloop with this geometry's tap
+// offsets); the epilogue adds the layer's fused addends (nearest-upsampled terms of
 // the fuse sum, hrnet.py:258-265) before the ReLU.
 #include "kernels.h"
 #include "device.h"
+#include "conv_bf16_plane.h"
 
 namespace grk {
 
 namespace {
 
 template <int CP, int CT, int WO, int R>
-struct S2Geom {
-    static constexpr int P = WO + 1, SB = 2 * CP + 32, UPS = SB / 16, OSB = 2 * CT + 32;
-    static constexpr int NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
+struct S2Geom : PlaneGeom<CP, CT, WO, R, R> {             // the plane geometry of the OUTPUT (pitch Wo + 1) for each of the four sub-planes
+    typedef PlaneGeom<CP, CT, WO, R, R> B;
+    using B::P; using B::SB; using B::NT;
+    static constexpr int UPS = SB / 16, OSB = 2 * CT + 32;
     static constexpr int SUBROWS = R + 1;
     static constexpr int SUB = (SUBROWS * P > NT * 16 + P + 1 ? SUBROWS * P : NT * 16 + P + 1);      // slots per sub-plane: its rows, or what the farthest tap of the last column tile reaches
     static constexpr int FILL_UNITS = (4 * SUB * UPS + 63) / 64 * 64;
     static constexpr int NFILL = (FILL_UNITS / 64 + 7) / 8;
     static constexpr int LDS = (4 * SUB * SB + SB > FILL_UNITS * 16 ? 4 * SUB * SB + SB : FILL_UNITS * 16);
-    static constexpr int UPP = CT / 8, NUO = (R * WO * UPP + 511) / 512;
-    static constexpr int NB = (WO + R - 1) / R;
-    static_assert(((SB / 32) % 2) == 1 && LDS <= 160 * 1024 && PS <= 32 && NT * 16 * OSB <= LDS && CT % 32 == 0 && 8 % (CT / 32) == 0, "stride-2 band geometry");
-    // byte offset of tap (dy, dx) from the lane's base (sub-plane (0,0), row 0, column slot 0)
+    static_assert(LDS <= 160 * 1024 && NT * 16 * OSB <= LDS, "stride-2 band geometry");
+    // byte offset of tap (dy, dx) from the lane's base (sub-plane (0,0), row 0, column slot 0); replaces the stride-1 offsets of PlaneGeom
     static constexpr int toff(int tap) {
         const int dy = tap / 3, dx = tap % 3, py = dy != 1, px = dx != 1, oy = dy == 0 ? -1 : 0, ox = dx == 0 ? -1 : 0;
         return ((py * 2 + px) * SUB + (oy + 1) * P + (ox + 1)) * SB;
     }
 };
-
-template <typename G, int CS, int PS>
-__device__ __forceinline__ void s2_kloop(f32x4 (&acc)[CS][PS], bf16x8 (&wr)[3][CS], const unsigned char* bread, const u16* wc, size_t wtap, int nch, bool last, unsigned wlb) {
-    constexpr int SB = G::SB;
-    bf16x8 bfr[PS];
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB + G::toff(0));
-#pragma unroll 1
-    for (int chunk = 0; chunk < nch; ++chunk) {
-        const unsigned char* bch = bread + chunk * 64;
-        const u16* wch = wc + (size_t)chunk * 9 * wtap;
-        const bool lastc = last && chunk == nch - 1;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            {
-                const u16* src = wch + (size_t)(tap + 2) * wtap;
-                if (tap >= 7) src = lastc ? wc + (size_t)(tap - 7) * wtap : src;
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) wr[(tap + 2) % 3][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(src + cs * 16 * 32) + wlb);
-            }
-            const int noff = tap < 8 ? G::toff(tap + 1) : G::toff(0) + 64;      // the next chunk's first tap; behind the last chunk it reads ahead into padding / the spare slot
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[tap % 3][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(bch + ps * 16 * SB + noff);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
 
 template <int CP, int CT, int WO, int R>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(S2Geom<CP, CT, WO, R>::LDS <= 80 * 1024 ? 4 : 2))) void conv_bf16_s2_band(const ConvArgs a) {
@@ -126,7 +95,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(S2Geom<CP, 
         fill(c0, cw);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        s2_kloop<G, CS, PS>(acc, wr, bread, wg + (size_t)(c0 / 32) * 9 * wtap, wtap, cw / 32, pass == npass - 1, wlb);
+        const u16* wpass = wg + (size_t)(c0 / 32) * 9 * wtap;       // the pass's first k-step; behind the layer's last one the stream ends: its own first steps again
+        plane_kloop<G>(acc, wr, bread, wpass, wpass, wtap, cw / 32, pass == npass - 1, wlb);
     }
     // ---- epilogue: + fused addends (nearest-upsampled by 2^shift), ReLU, bf16; through LDS as whole channel rows
     const int Ho = WO;
@@ -165,11 +135,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(S2Geom<CP, 
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps)
 #pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_bits(v[0]); v[1] = relu_bits(v[1]); v[2] = relu_bits(v[2]); v[3] = relu_bits(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
-        }
+        for (int cs = 0; cs < CS; ++cs)
+            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = pack4_relu_if(acc[cs][ps], a.relu);
     __syncthreads();
     u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * Ho * WO * a.out_ctot + a.out_coff + cbo * CT;
     const int cstore = a.Cout - cbo * CT;

@@ -1,5 +1,6 @@
-// bf16 path: the wide 3x3 stride-1 layers with a band of the input resident in LDS.  The flattened, padded LDS plane, the MFMA roles and the weight ring are
-// those of the frame-resident chain kernels (conv_bf16_chain.hip: its header describes them).
+// bf16 path: the wide 3x3 stride-1 layers with a band of the input resident in LDS.  The flattened, padded LDS plane and the MFMA roles are those of the
+// frame-resident chain kernels (conv_bf16_chain.hip: its header describes them); the tile geometry and the k-loop with its weight ring are the LDS-plane
+// family's one definition (conv_bf16_plane.h).
 //
 // ---- ONE wide 3x3 stride-1 convolution (upsample heads hrnet.py:440-453, PARE head pare.py:377-400, layer1's 3x3 hrnet.py:80-100) with a band of
 // the input resident in LDS.  conv_bf16_nhwc runs these layers at 0.25-0.45 of the matrix peak: 224-pixel x 64-channel tiles, 32 input
@@ -12,60 +13,24 @@
 // The tile leaves through the plane (in place, as in the chain kernel) as whole channel rows.
 #include "kernels.h"
 #include "device.h"
+#include "conv_bf16_plane.h"
 
 namespace grk {
 
 namespace {
 
+// CT output channels per workgroup (CT <= CP: the tile leaves through the first 2 CT bytes of the plane's slots)
 template <int CP, int CT, int W, int R>
-struct WideGeom {
-    static constexpr int P = W + 1, SB = 2 * CP + 32, UPS = SB / 16;
+struct WideGeom : PlaneGeom<CP, CT, W, R, R> {
+    typedef PlaneGeom<CP, CT, W, R, R> B;
+    static constexpr int UPS = B::SB / 16;
     static constexpr int ROWS = R + 2;                      // plane rows: image rows y0 - 1 .. y0 + R
-    static constexpr int O0 = P + 1, NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;    // CT output channels per workgroup (CT <= CP: the tile leaves through the first 2 CT bytes of the plane's slots)
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int NSLOT = O0 + NT * 16 + P + 2;
-    static constexpr int LDS = NSLOT * SB;
-    static constexpr int FILL_UNITS = ((ROWS * P + 1) * UPS + 63) / 64 * 64;      // slots 0 .. ROWS * P (the last one: the right halo of the last row), whole wave-instructions
+    static constexpr int LDS = B::NSLOT * B::SB;
+    static constexpr int FILL_UNITS = ((ROWS * B::P + 1) * UPS + 63) / 64 * 64;    // slots 0 .. ROWS * P (the last one: the right halo of the last row), whole wave-instructions
     static constexpr int NFILL = (FILL_UNITS / 64 + 7) / 8;                        // wave-instructions per wave
-    static constexpr int UPP = CT / 8, NUO = (R * W * UPP + 511) / 512;
-    static constexpr int NB = (W + R - 1) / R;
-    static_assert(((SB / 32) % 2) == 1 && LDS <= 160 * 1024 && PS <= 32 && FILL_UNITS * 16 <= LDS && CT <= CP && CT % 32 == 0 && 8 % (CT / 32) == 0, "wide-band geometry");
+    static_assert(LDS <= 160 * 1024 && FILL_UNITS * 16 <= LDS && CT <= CP, "wide-band geometry");
     // (with CP = 128 the farthest pixel fragment lies 89 KB behind the lane's base: past the 16-bit ds_read immediate, hipcc keeps a second base register)
 };
-
-// chain_kloop with a run-time chunk count and weight stride (the output-channel padding of the layer): wc = the pass's first k-step, wtap = elements
-// per k-step (CoutPad x 32); the ring's two leading steps of the NEXT pass are simply the next two k-steps of the stream -- except behind the very
-// last chunk of the layer (last), where the stream ends: the pass's own first steps are re-requested (nobody waits for them).
-template <int P, int SB, int CS, int PS>
-__device__ __forceinline__ void wide_kloop(f32x4 (&acc)[CS][PS], bf16x8 (&wr)[3][CS], const unsigned char* bread, const u16* wc, size_t wtap, int nch, bool last, unsigned wlb) {
-    bf16x8 bfr[PS];
-#pragma unroll
-    for (int ps = 0; ps < PS; ++ps) bfr[ps] = *reinterpret_cast<const bf16x8*>(bread + ps * 16 * SB);
-#pragma unroll 1
-    for (int chunk = 0; chunk < nch; ++chunk) {
-        const unsigned char* bch = bread + chunk * 64;
-        const u16* wch = wc + (size_t)chunk * 9 * wtap;
-        const bool lastc = last && chunk == nch - 1;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            {
-                const u16* src = wch + (size_t)(tap + 2) * wtap;
-                if (tap >= 7) src = lastc ? wc + (size_t)(tap - 7) * wtap : src;
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) wr[(tap + 2) % 3][cs] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(src + cs * 16 * 32) + wlb);
-            }
-            const int noff = tap < 8 ? (((tap + 1) / 3) * P + ((tap + 1) % 3)) * SB : 64;
-#pragma unroll
-            for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-                for (int cs = 0; cs < CS; ++cs) acc[cs][ps] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[tap % 3][cs], bfr[ps], acc[cs][ps], 0, 0, 0);
-                bfr[ps] = *reinterpret_cast<const bf16x8*>(bch + ps * 16 * SB + noff);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
 
 template <int CP, int CT, int W, int R>
 __global__ __launch_bounds__(512) void conv_bf16_wide_band(const ConvArgs a) {
@@ -76,10 +41,8 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_band(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wcb = wave % G::WCB, pg = wave / G::WCB;
     const int ncb = a.CoutPad / CT;                            // output-channel tiles of the layer
-    // workgroups go to the 8 XCDs round-robin by blockIdx: with a.xcd the ids are re-dealt so that CONSECUTIVE tiles -- the ncb output-channel tiles of a band,
-    // then the frame's next band (which shares two halo rows) -- run on ONE XCD at about the same time and meet in its L2
     int bid = blockIdx.x;
-    if (a.xcd && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    if (a.xcd) bid = xcd_redeal(bid);
     const int cbo = bid % ncb, nb = bid / ncb, n = nb / G::NB, band = nb - n * G::NB;
     if (n >= a.N) return;
     const int y0 = band * R;
@@ -137,19 +100,17 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_band(const ConvArgs a) {
         fill(c0, cw);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        const u16* wpass = wg + (size_t)(c0 / 32) * 9 * wtap;       // the pass's first k-step; behind the layer's last one the stream ends: its own first steps again
         if (!abl::bit(a.dbg, 2))
-        wide_kloop<P, SB, CS, PS>(acc, wr, bread, wg + (size_t)(c0 / 32) * 9 * wtap, wtap, cw / 32, pass == npass - 1, wlb);
+        plane_kloop<G>(acc, wr, bread, wpass, wpass, wtap, cw / 32, pass == npass - 1, wlb);
     }
     // ---- the tile: bias is in the accumulators; ReLU, bf16, in place through the plane, rows y0 .. y0 + R - 1 -> HBM as whole channel rows
     __syncthreads();
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps)
 #pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_bits(v[0]); v[1] = relu_bits(v[1]); v[2] = relu_bits(v[2]); v[3] = relu_bits(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 32) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
-        }
+        for (int cs = 0; cs < CS; ++cs)
+            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * SB + cs * 32) = pack4_relu_if(acc[cs][ps], a.relu);
     __syncthreads();
     u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff + cbo * CT;
     const int cstore = a.Cout - cbo * CT;                      // real channels of this tile (CoutPad may exceed Cout)
@@ -179,23 +140,19 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_band(const ConvArgs a) {
 // (tap 8 and taps 0 .. NFILL-2: every wave issues the same count -- a wave without an own last piece re-requests the plane's last one, and behind the
 // last chunk the pieces fetch zeros into the plane nobody reads any more).
 template <int CT, int W, int R, bool DIRECT = false>
-struct RingGeom {
-    static constexpr int P = W + 1, SB = 96, UPS = SB / 16;
+struct RingGeom : PlaneGeom<32, CT, W, R, R> {                                      // a plane holds ONE 32-channel chunk: slot stride 96 bytes
+    typedef PlaneGeom<32, CT, W, R, R> B;
+    static constexpr int UPS = B::SB / 16;
     static constexpr int ROWS = R + 2;
-    static constexpr int O0 = P + 1, NOUT = R * P - 1;
-    static constexpr int CS = 2, WCB = CT / 32, WPG = 8 / WCB;
-    static constexpr int PS = ((NOUT + 15) / 16 + WPG - 1) / WPG, NT = WPG * PS;
-    static constexpr int NPIECE = ((ROWS * P + 1) * UPS + 63) / 64;                 // one-KiB DMA pieces of a plane: slots 0 .. ROWS * P
+    static constexpr int NPIECE = ((ROWS * B::P + 1) * UPS + 63) / 64;              // one-KiB DMA pieces of a plane: slots 0 .. ROWS * P
     static constexpr int PB = NPIECE * 1024;                                        // plane stride, bytes
     static constexpr int NFILL = (NPIECE + 7) / 8;                                  // pieces per wave and chunk
     static constexpr int WRING = 2 * PB;                                            // the waves' weight rings: 8 x 3 slots x 2 KiB (a plane's dead columns read into them: garbage, never stored)
     static constexpr int OSB = 2 * CT + 32;                                         // slot stride of the output tile (staged over everything)
     static constexpr int LDS = WRING + 8 * 3 * 2048;
-    static constexpr int UPP = CT / 8, NUO = (R * W * UPP + 511) / 512;
-    static constexpr int NB = (W + R - 1) / R;
     static constexpr bool piece_at(int tap) { return tap == 8 || tap < NFILL - 1; }
-    static_assert(LDS <= 160 * 1024 && NFILL >= 2 && NFILL <= 7 && PS <= 32 && (DIRECT || (O0 + NT * 16) * OSB <= LDS) && CT % 32 == 0 && 8 % (CT / 32) == 0, "ring geometry");
-    static_assert((PS - 1) * 16 * SB + (2 * P + 2) * SB + 64 < 65536 && (O0 + NT * 16 + P + 2) * SB + 64 <= LDS - PB, "ds_read immediates / the farthest dead read stays inside the allocation");
+    static_assert(LDS <= 160 * 1024 && NFILL >= 2 && NFILL <= 7 && (DIRECT || (B::O0 + B::NT * 16) * OSB <= LDS), "ring geometry");
+    static_assert(B::IMM16 && B::NSLOT * B::SB + 64 <= LDS - PB, "ds_read immediates / the farthest dead read stays inside the allocation");
 };
 
 template <int CT, int W, int R, bool DIRECT = false>
@@ -207,8 +164,8 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_ring(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wcb = wave % G::WCB, pg = wave / G::WCB;
     const int ncb = a.CoutPad / CT;
-    int bid = blockIdx.x;                                                           // a.xcd: consecutive tiles on ONE XCD (see conv_bf16_wide_band)
-    if (a.xcd && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    int bid = blockIdx.x;
+    if (a.xcd) bid = xcd_redeal(bid);
     const int cbo = bid % ncb, nb = bid / ncb, n = nb / G::NB, band = nb - n * G::NB;
     if (n >= a.N) return;
     const int y0 = band * R;
@@ -337,11 +294,8 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_ring(const ConvArgs a) {
             const int o = o_first + ps * 16, r = o / P, x = o - r * P - 1;
             u16* op = outw + ((size_t)(y0 + r - 1) * W + x) * a.out_ctot;
 #pragma unroll
-            for (int cs = 0; cs < CS; ++cs) {
-                f32x4 v = acc[cs][ps];
-                if (a.relu) { v[0] = relu_bits(v[0]); v[1] = relu_bits(v[1]); v[2] = relu_bits(v[2]); v[3] = relu_bits(v[3]); }
-                if ((valid & (1u << ps)) && wcb * CS * 16 + cs * 16 + lq * 4 < cstore) *reinterpret_cast<u32x2*>(op + cs * 16) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
-            }
+            for (int cs = 0; cs < CS; ++cs)
+                if ((valid & (1u << ps)) && wcb * CS * 16 + cs * 16 + lq * 4 < cstore) *reinterpret_cast<u32x2*>(op + cs * 16) = pack4_relu_if(acc[cs][ps], a.relu);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // no piece may land in an LDS that already belongs to somebody else
         return;
@@ -353,11 +307,8 @@ __global__ __launch_bounds__(512) void conv_bf16_wide_ring(const ConvArgs a) {
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps)
 #pragma unroll
-        for (int cs = 0; cs < CS; ++cs) {
-            f32x4 v = acc[cs][ps];
-            if (a.relu) { v[0] = relu_bits(v[0]); v[1] = relu_bits(v[1]); v[2] = relu_bits(v[2]); v[3] = relu_bits(v[3]); }
-            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
-        }
+        for (int cs = 0; cs < CS; ++cs)
+            if (valid & (1u << ps)) *reinterpret_cast<u32x2*>(owrite + ps * 16 * OSB + cs * 32) = pack4_relu_if(acc[cs][ps], a.relu);
     __syncthreads();
     u16* outb = reinterpret_cast<u16*>(a.out) + (size_t)n * W * W * a.out_ctot + a.out_coff + cbo * CT;
     const int cstore = a.Cout - cbo * CT;

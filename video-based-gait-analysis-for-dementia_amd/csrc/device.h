@@ -29,6 +29,12 @@ __device__ __forceinline__ unsigned relu_pk(unsigned v) {      // max(x, 0) on t
     const s16x2 a = __builtin_bit_cast(s16x2, v);
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, s16x2{0, 0}));
 }
+// an accumulator's four values -> ReLU -> four bf16 (8 bytes); the second form applies the ReLU where the layer has one (relu: wave-uniform)
+__device__ __forceinline__ u32x2 pack4_relu(const f32x4 v) { return u32x2{pack2(relu_bits(v[0]), relu_bits(v[1])), pack2(relu_bits(v[2]), relu_bits(v[3]))}; }
+__device__ __forceinline__ u32x2 pack4_relu_if(f32x4 v, int relu) {
+    if (relu) { v[0] = relu_bits(v[0]); v[1] = relu_bits(v[1]); v[2] = relu_bits(v[2]); v[3] = relu_bits(v[3]); }
+    return u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+}
 __device__ __forceinline__ float bf_lo(unsigned v) { return __uint_as_float(v << 16); }
 __device__ __forceinline__ float bf_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
 // q / d for 0 <= q < 2^20, 0 < d < 2^20 through one fp32 reciprocal multiply (exact: the +0.5 keeps the quotient of an exact multiple away from the
