@@ -1,7 +1,8 @@
-"""The transform matrices the Winograd kernels are built on (csrc/conv_wino.hip: F(2x2,3x3); csrc/conv_wino4.hip: F(4x4,3x3)),
-checked on the CPU: A^T [ (G g G^T) . (B^T d B) ] A equals the 3x3 correlation of the patch exactly (fp64), summed over channels
-like the kernels do, and in fp32 stays within the error the per-layer GPU tests allow.  The same constants appear in the kernels'
-1-D transform helpers (bt_lo / bt_hi, the epilogue's A^T rows) and in pack_wino*_weights (G)."""
+"""The transform matrices the Winograd kernels are built on (F(4x4,3x3): csrc/conv_wino4.hip with conv_wino4_tile.h, csrc/conv_wino4s.hip;
+F(2x2,3x3): the round-2 kernel, kept in the history only), checked on the CPU: A^T [ (G g G^T) . (B^T d B) ] A equals the 3x3 correlation of
+the patch exactly (fp64), summed over channels like the kernels do, and in fp32 stays within the error the per-layer GPU tests allow.  The
+same constants appear in the kernels' 1-D transform helpers -- bt_lo / bt_hi (B^T) and at_f43 (A^T) in csrc/device.h, used for both passes of
+every F(4x4,3x3) kernel -- and in wino4_transform_filter (G; csrc/conv_wino4.hip), which every weight packer calls."""
 import numpy as np
 import pytest
 

@@ -14,6 +14,7 @@
 // 16-byte load straight from L2, requested a chunk ahead.
 #include "kernels.h"
 #include "device.h"
+#include "conv_wino4_tile.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -27,19 +28,14 @@ __device__ unsigned long long g_w4phase[8];      // diagnostic build, dbg bit 3:
 #endif
 
 constexpr int kCK = 8;                       // input channels per chunk
-constexpr int kRaw = 6 * 56;                 // raw floats per channel: 6 input rows
-constexpr int kV = 36 * kCK * 16;            // V[point][channel][16 tile slots]
-constexpr int kMrow = 20;                    // epilogue: [point][channel][16 MFMA rows + 4]
-constexpr size_t kLdsB = sizeof(float) * (2 * kCK * kRaw + 2 * kV);     // 58 368 B
-static_assert(sizeof(float) * 36 * 16 * kMrow <= kLdsB, "the epilogue tile reuses the staging area");
+constexpr size_t kLdsB = Wino4Geom<56, kCK, 256>::lds_bytes;      // 58 368 B (56-wide maps; 28-wide ones need less and take the same)
 
 template <typename T>
 __device__ __forceinline__ void landed(T& x) { asm volatile("" : "+v"(x)); }
 
 // NB: 16-channel blocks per workgroup: 4, or 2 = HALF a 64-channel block of the same packed weights (the half-size workgroups of a
 // layer's last round, ConvArgs::wsplit)
-// WD: map width, 56 or 28.  A workgroup's 14 tiles are one tile row of a 56-wide map (6 input rows) or two tile rows of 7 of a 28-wide
-// one (10 input rows; 7 tile rows per image = 3.5 groups: the last group's lower half reads zeros and stores nothing).
+// WD: map width, 56 or 28 (Wino4Geom).
 // WSPLIT: the 32-channel kernel on HALF a 64-channel block of weights packed for the 64-channel kernel (last-round workgroups).  The
 // standalone 32-channel layers (NB = 2, !WSPLIT) have their own packing with the two k-steps of a chunk interleaved (pack_wino4_weights):
 // one 16-byte load brings a point's B fragments of BOTH k-steps, 9 weight loads per chunk and wave instead of 18.
@@ -47,35 +43,24 @@ template <int NB, int WD, int ABL, bool WSPLIT>
 __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     constexpr bool PAIR = NB == 2 && !WSPLIT;
     constexpr int NLD = PAIR ? 9 : 18;                   // weight loads per chunk and wave
-    constexpr int TPR = WD / 4, TRG = 14 / TPR, kRawW = (4 * TRG + 2) * WD, UPC = kRawW / 4;   // tiles per tile row, tile rows per workgroup, raw floats / units per channel
-    static_assert(WD == 56 || WD == 28, "tile geometry");
+    typedef Wino4Geom<WD, kCK, 256> G;
+    constexpr int TPR = G::TPR, TRG = G::TRG, kRawW = G::RAWW, UPC = G::UPC, kV = G::V, kMrow = G::MROW;
     extern __shared__ __align__(16) float smem[];
-    float* raw = smem;                                  // [2][8][kRawW]
-    float* V = raw + 2 * kCK * kRaw;                    // [2][36][8][16]
+    float* raw = smem;                                  // [2][8][RAWW]
+    float* V = raw + G::VOFF;                           // [2][36][8][16]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
 
     const int id = a.blk0 + (WSPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x), nb0 = WSPLIT ? 2 * (int)(blockIdx.x & 1) : 0;
-    int bx, by;
-    if (a.xcd) {
-        const int j = id >> 3, x = id & 7, q = j / a.gy;
-        by = j - q * a.gy;
-        bx = x * (a.gx >> 3) + q;
-    } else {
-        bx = id / a.gy;
-        by = id - bx * a.gy;
-    }
-    const int groups = ((a.H >> 2) + TRG - 1) / TRG;     // tile-row groups per image (14 or 4)
-    const int img = bx / groups, r = bx - img * groups;
+    int img, r, by;
+    G::decode(a, id, img, r, by);
     const int co0 = WSPLIT ? by * 64 : by * (NB * 16);      // first channel of the weight block; channel n*16 + l sits at l*cstr + n
     constexpr int cstr = WSPLIT ? 4 : NB;
-    if (a.prio == 1) __builtin_amdgcn_s_setprio(1);         // critical-chain layers
-    else if (a.prio >= 2) __builtin_amdgcn_s_setprio(3);
+    set_wave_prio(a.prio);
     const int HW = a.H * a.W;
     const float* inb = a.in + ((size_t)img * a.in_ctot + a.in_coff) * HW;
     const int g0 = (4 * TRG * r - 1) * WD;               // plane index of raw[.][0]
 
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, 36 * a.CinPad * a.CoutPad * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)inb, (short)0, a.Cin * HW * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t u_rsrc = buffer_rsrc(a.w, 36 * a.CinPad * a.CoutPad * 4), r_rsrc = buffer_rsrc(inb, a.Cin * HW * 4);
     typedef float bfrag __attribute__((ext_vector_type(PAIR ? 4 : NB)));   // PAIR: {k-step 0: n0 n1, k-step 1: n0 n1}
     const int nchunks_u = a.CinPad / kCK;
     // byte offsets: a lane's part (VGPR) + point / chunk part (scalar)
@@ -88,10 +73,10 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
         if constexpr (PAIR || NB == 4) return __builtin_bit_cast(bfrag, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ub, soff, 0));
         else return __builtin_bit_cast(bfrag, __builtin_amdgcn_raw_buffer_load_b64(u_rsrc, ub, soff, 0));
     };
-    int roff[3];                                         // raw rows: 672 units per chunk; -1 = no unit or a row outside the image
+    int roff[G::NRU];                                    // raw rows: 672 units per chunk; -1 = no unit or a row outside the image
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int u = i * 256 + tid, ch = u / UPC, k = u - ch * UPC, gi = g0 + 4 * k;
+    for (int i = 0; i < G::NRU; ++i) {
+        const int u = i * G::NT + tid, ch = u / UPC, k = u - ch * UPC, gi = g0 + 4 * k;
         const bool unit = u < kCK * UPC, inside = gi >= 0 && gi < HW;
         roff[i] = unit && inside ? (ch * HW + gi) * 4 : -1;
         if (unit && !inside) {                           // rows above / below the image: zero once in both buffers, the DMA never writes there
@@ -99,19 +84,10 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
             *reinterpret_cast<f32x4*>(raw + kCK * kRawW + u * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    auto issue_raw = [&](int chunk) {
-        const int soff = chunk * (kCK * 4) * HW;
-        float* dst = raw + (chunk & 1) * (kCK * kRawW);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (roff[i] >= 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_rsrc, (GRNET_LDS_AS void*)(dst + (i * 256 + wave * 64) * 4), 16, roff[i], soff, 0, 0);
-        asm volatile("" ::: "memory");                   // later loads stay behind these requests: the vmcnt waits below count on the order
-    };
+    auto issue_raw = [&](int chunk) { G::issue_raw(roff, r_rsrc, raw, chunk, wave, HW); };
 
-    // ---- input transform.  16 rows of 16 lanes: row = (channel 0..7, half 0..1), lane = tile 0..13 (lanes 14, 15 idle: their zeros are the
-    // right neighbour of tile 13 and they write into the two padding tile slots).  A thread reads all 6 rows of its tile's 6x6 patch (own
-    // columns 4t .. 4t+3 as one 16-byte read per row, 4t-1 / 4t+4 from the neighbour lanes by DPP, whose out-of-row zero is the image's
-    // left padding) and produces rows 3*half .. 3*half+2 of B^T d B.
+    // ---- input transform (Wino4Patch).  16 rows of 16 lanes: row = (channel 0..7, half 0..1), lane = tile 0..13 (lanes 14, 15 idle: their
+    // zeros are the right neighbour of tile 13 and they write into the two padding tile slots)
     const int row16 = tid >> 4, px = tid & 15, chn = row16 & 7;
     const int half = __builtin_amdgcn_readfirstlane(row16 >> 3);                         // wave-uniform: waves 0, 1 / 2, 3
     // WD = 28: the 16 lanes are two tile rows of 7 tiles + 1 idle lane each; idle lanes supply the zero on BOTH sides there
@@ -120,39 +96,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     const int rpos = chn * kRawW + (4 * trl) * WD + 4 * (real ? pc : TPR - 1);
     const int slot = real ? trl * TPR + pc : 14 + (WD == 56 ? px - 14 : trl);            // tile slot in V (14, 15: padding)
     const int vpos = (half * 18) * (kCK * 16) + chn * 16 + slot;                         // + (rr * 6 + c) * 128 for row rr of the half, column c
-    struct Tf { float d[6][6]; float e[3][6]; };
-    auto tf_read = [&](Tf& t, const float* rp) {        // 6 LDS reads
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rp + i * WD);
-            t.d[i][1] = v[0]; t.d[i][2] = v[1]; t.d[i][3] = v[2]; t.d[i][4] = v[3];
-        }
-    };
-    auto tf_halo = [&](Tf& t) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            t.d[i][0] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(WD == 56 || real ? t.d[i][4] : 0.f), 0x111, 0xf, 0xf, true));   // row_shr:1
-            t.d[i][5] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(real ? t.d[i][1] : 0.f), 0x101, 0xf, 0xf, true));    // row_shl:1
-        }
-    };
-    auto tf_rows = [&](Tf& t) {                         // three rows of B^T d, per column
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const float col[6] = {t.d[0][j], t.d[1][j], t.d[2][j], t.d[3][j], t.d[4][j], t.d[5][j]};
-            if (half == 0) bt_lo(col, t.e[0][j], t.e[1][j], t.e[2][j]);
-            else bt_hi(col, t.e[0][j], t.e[1][j], t.e[2][j]);
-        }
-    };
-    auto tf_cols = [&](Tf& t, float* vp) {              // (B^T d) B: all 6 columns of the three rows, 18 LDS writes
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-            float o[6];
-            bt_lo(t.e[rr], o[0], o[1], o[2]);
-            bt_hi(t.e[rr], o[3], o[4], o[5]);
-#pragma unroll
-            for (int c = 0; c < 6; ++c) vp[(rr * 6 + c) * (kCK * 16)] = o[c];
-        }
-    };
+    typedef Wino4Patch<G> Tf;
 
     f32x4 acc[9][NB];                                    // [point of this wave][channel block]
 #pragma unroll
@@ -173,10 +117,10 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     ticks.mark(0);
     {
         Tf t;
-        tf_read(t, raw + rpos);
-        tf_halo(t);
-        tf_rows(t);
-        tf_cols(t, V + vpos);
+        t.read(raw + rpos);
+        t.halo(real);
+        t.rows(half);
+        t.cols(V + vpos);
     }
     ticks.mark(1);
     // ---- the chunk loop: three clusters of 24 MFMAs (three points x two k-steps x four channel blocks)
@@ -200,8 +144,8 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) landed(av[c & 1][k]);
             if (with_transform && ABL != 2) {
-                if (c == 1) { tf_halo(t); tf_rows(t); }
-                if (c == 2) tf_cols(t, vp);
+                if (c == 1) { t.halo(real); t.rows(half); }
+                if (c == 2) t.cols(vp);
             }
             __builtin_amdgcn_sched_barrier(0);
             // (2) requests: the next cluster's A fragments, the next chunk's B fragments of the previous cluster, the next chunk's input rows
@@ -210,7 +154,7 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
 #pragma unroll
                 for (int k = 0; k < NLD / 3; ++k) bq[(NLD / 3) * (c - 1) + k] = load_u(next, (NLD / 3) * (c - 1) + k);
             }
-            if (with_transform && ABL != 2 && c == 0) tf_read(t, rp);
+            if (with_transform && ABL != 2 && c == 0) t.read(rp);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 6; ++k)
@@ -244,16 +188,12 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
     // thread (channel c of the pass's 16, tile t): 4 output rows of 4 pixels.  The residual rows of a pass are requested a pass ahead
     // (pass 0's before the accumulators go to LDS): their round trip used to sit between the inverse transform and the stores of every
     // pass -- twice per launch of the 32-channel branch layers, which are the longest dependency chain of stages 2-4.
-    const int ec = tid / 14, et = tid - ec * 14, etro = et / TPR, etx = et - etro * TPR, eorow = 4 * (TRG * r + etro);
-    const bool ethread = tid < 14 * 16 && eorow < a.H;
+    typename G::Epi ep;
+    G::epi(tid, r, a.H, ep);
     f32x4 radd[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     auto fetch_res = [&](int nt) {
-        const int co = co0 + (nb0 + nt) * 16 + ec;
-        if (has_add && ethread && co < a.Cout) {
-            const float* ap = a.add[0] + ((size_t)img * a.add_ctot[0] + a.add_coff[0] + co) * HW + eorow * WD + 4 * etx;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) radd[i] = *reinterpret_cast<const f32x4*>(ap + i * WD);
-        }
+        const int co = co0 + (nb0 + nt) * 16 + ep.ec;
+        if (has_add && ep.on && co < a.Cout) G::fetch_res(radd, a, ep, img, co, HW);
     };
     fetch_res(0);                                       // under the last chunk's MFMAs
     chunk((nchunks - 1) & 1, false, 0);
@@ -273,29 +213,24 @@ __device__ __forceinline__ void conv_wino4_body(const ConvArgs& a) {
         __syncthreads();
         const f32x4 rcur[4] = {radd[0], radd[1], radd[2], radd[3]};
         if (nt + 1 < NB) fetch_res(nt + 1);
-        if (ethread) {
-            const int c = ec, t = et, tx = etx;
-            const int co = co0 + (nb0 + nt) * 16 + c, orow = eorow;
+        if (ep.on) {
+            const int co = co0 + (nb0 + nt) * 16 + ep.ec;
             if (co < a.Cout) {
                 float s[4][6];                           // A^T M: rows of the 4x6 intermediate
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
                     float m[6];
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) m[i] = Mx[((i * 6 + j) * 16 + c) * kMrow + t];
-                    const float p12 = m[1] + m[2], m12 = m[1] - m[2], p34 = m[3] + m[4], m34 = m[3] - m[4];
-                    s[0][j] = m[0] + p12 + p34;
-                    s[1][j] = fmaf(2.f, m34, m12);
-                    s[2][j] = fmaf(4.f, p34, p12);
-                    s[3][j] = fmaf(8.f, m34, m12) + m[5];
+                    for (int i = 0; i < 6; ++i) m[i] = Mx[((i * 6 + j) * 16 + ep.ec) * kMrow + ep.et];
+                    at_f43(m, s[0][j], s[1][j], s[2][j], s[3][j]);
                 }
                 const float b = a.bias[co];
-                const size_t obase = ((size_t)img * a.out_ctot + a.out_coff + co) * HW + orow * WD + 4 * tx;
+                const size_t obase = ((size_t)img * a.out_ctot + a.out_coff + co) * HW + ep.eorow * WD + 4 * ep.etx;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float* q = s[i];
-                    const float p12 = q[1] + q[2], m12 = q[1] - q[2], p34 = q[3] + q[4], m34 = q[3] - q[4];
-                    f32x4 y = f32x4{q[0] + p12 + p34 + b, fmaf(2.f, m34, m12) + b, fmaf(4.f, p34, p12) + b, fmaf(8.f, m34, m12) + q[5] + b};
+                    float y0, y1, y2, y3;
+                    at_f43<true>(s[i], y0, y1, y2, y3, b);
+                    f32x4 y = f32x4{y0, y1, y2, y3};
                     if (has_add) y += rcur[i];
                     if (a.relu) { y[0] = fmaxf(y[0], 0.f); y[1] = fmaxf(y[1], 0.f); y[2] = fmaxf(y[2], 0.f); y[3] = fmaxf(y[3], 0.f); }
                     *reinterpret_cast<f32x4*>(a.out + obase + i * WD) = y;
@@ -327,9 +262,7 @@ __global__ __launch_bounds__(256) void conv_wino4_f32(const ConvArgs a) { conv_w
 // Wave w: points 9 (w & 3) .. + 8, output channels 64 (w >> 2) .. + 63 of the workgroup's 128 (4 accumulator tiles per point).
 // LDS: raw rows [2][16][336] + V [2][36][16][16] = 116.7 KB (one workgroup per CU); the epilogue's [2 halves][36][16][20] reuses it.
 constexpr int kCKW = 16;                              // input channels per chunk
-constexpr int kVW = 36 * kCKW * 16;                   // V[point][channel][16 tile slots]
-constexpr size_t kLdsW = sizeof(float) * (2 * kCKW * kRaw + 2 * kVW);      // 116 736 B (56-wide maps; 28-wide ones need less and take the same)
-static_assert(sizeof(float) * 2 * 36 * 16 * kMrow <= kLdsW, "the epilogue tiles reuse the staging area");
+constexpr size_t kLdsW = Wino4Geom<56, kCKW, 512>::lds_bytes;      // 116 736 B
 
 // WD: map width, 56 (one tile row of 14 tiles) or 28 (two tile rows of 7, as in the 4-wave kernel).  NPW: 16-channel blocks per wave:
 // 4 = 128 output channels per workgroup, 2 = 64 (the 64 -> 64 layers: HR branch 1 on 28x28 maps -- until round 4 two 32-channel
@@ -337,39 +270,29 @@ static_assert(sizeof(float) * 2 * 36 * 16 * kMrow <= kLdsW, "the epilogue tiles 
 // 4-wave kernel's 64-channel blocks: a lane's 16 bytes hold its channel of the four 16-channel blocks; with NPW = 2 a wave reads its 8.
 template <int WD, int NPW>
 __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
-    constexpr int TPR = WD / 4, TRG = 14 / TPR, kRawW = (4 * TRG + 2) * WD, UPC = kRawW / 4;   // tiles per tile row, tile rows per workgroup, raw floats / units per channel
+    typedef Wino4Geom<WD, kCKW, 512> G;
+    constexpr int TPR = G::TPR, TRG = G::TRG, kRawW = G::RAWW, UPC = G::UPC, kVW = G::V, kMrow = G::MROW;
     constexpr int COUTW = 2 * NPW * 16;                  // output channels per workgroup
-    static_assert((WD == 56 || WD == 28) && (NPW == 4 || NPW == 2), "geometry");
+    static_assert(NPW == 4 || NPW == 2, "geometry");
     typedef float bfrag __attribute__((ext_vector_type(NPW)));
     extern __shared__ __align__(16) float smem[];
-    float* raw = smem;                                  // [2][16][kRawW]
-    float* V = raw + 2 * kCKW * kRaw;                   // [2][36][16][16]
+    float* raw = smem;                                  // [2][16][RAWW]
+    float* V = raw + G::VOFF;                           // [2][36][16][16]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, lq = lane >> 4;
     const int pg = wave & 3, hf = wave >> 2;            // point group; half of the workgroup's output channels = half of the patch it transforms
 
     const int id = blockIdx.x;
-    int bx, by;
-    if (a.xcd) {
-        const int j = id >> 3, x = id & 7, q = j / a.gy;
-        by = j - q * a.gy;
-        bx = x * (a.gx >> 3) + q;
-    } else {
-        bx = id / a.gy;
-        by = id - bx * a.gy;
-    }
-    const int groups = ((a.H >> 2) + TRG - 1) / TRG;     // tile-row groups per image (14 or 4)
-    const int img = bx / groups, r = bx - img * groups;
+    int img, r, by;
+    G::decode(a, id, img, r, by);
     // first output channel of this wave and where it sits in the packed weights: channel n*16 + l of a 64-block is at l*4 + n
     const int co0 = by * COUTW + hf * (NPW * 16);
     const int wpos = NPW == 4 ? co0 : (co0 & ~63) + ((co0 >> 5) & 1) * 2;
-    if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (a.prio >= 2) __builtin_amdgcn_s_setprio(3);
+    set_wave_prio(a.prio);
     const int HW = a.H * a.W;
     const float* inb = a.in + ((size_t)img * a.in_ctot + a.in_coff) * HW;
     const int g0 = (4 * TRG * r - 1) * WD;               // plane index of raw[.][0]
 
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, 36 * a.CinPad * a.CoutPad * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)inb, (short)0, a.Cin * HW * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t u_rsrc = buffer_rsrc(a.w, 36 * a.CinPad * a.CoutPad * 4), r_rsrc = buffer_rsrc(inb, a.Cin * HW * 4);
     const int ub = ((pg * 9 * a.CinPad + lq) * a.CoutPad + wpos + l15 * 4) * 4;       // a lane's part of a B-fragment address (bytes)
     const int u_point = a.CinPad * a.CoutPad * 4, u_kstep = 4 * a.CoutPad * 4, u_chunk = kCKW * a.CoutPad * 4;
     // B fragments of cluster q of a chunk: q = 2 * (point third t) + (k-step pair kp); entry e = 2 * (point in third) + (k-step in pair)
@@ -378,11 +301,10 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
         if constexpr (NPW == 4) return __builtin_bit_cast(bfrag, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ub, soff, 0));
         else return __builtin_bit_cast(bfrag, __builtin_amdgcn_raw_buffer_load_b64(u_rsrc, ub, soff, 0));
     };
-    constexpr int NRU = (kCKW * UPC + 511) / 512;        // 16-byte units of a chunk's raw rows per thread (3)
-    int roff[NRU];                                       // -1 = no unit or a row outside the image
+    int roff[G::NRU];                                    // -1 = no unit or a row outside the image
 #pragma unroll
-    for (int i = 0; i < NRU; ++i) {
-        const int u = i * 512 + tid, ch = u / UPC, k = u - ch * UPC, gi = g0 + 4 * k;
+    for (int i = 0; i < G::NRU; ++i) {
+        const int u = i * G::NT + tid, ch = u / UPC, k = u - ch * UPC, gi = g0 + 4 * k;
         const bool unit = u < kCKW * UPC, inside = gi >= 0 && gi < HW;
         roff[i] = unit && inside ? (ch * HW + gi) * 4 : -1;
         if (unit && !inside) {                           // rows above / below the image: zero once in both buffers, the DMA never writes there
@@ -390,14 +312,7 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
             *reinterpret_cast<f32x4*>(raw + kCKW * kRawW + u * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    auto issue_raw = [&](int chunk) {
-        const int soff = chunk * (kCKW * 4) * HW;
-        float* dst = raw + (chunk & 1) * (kCKW * kRawW);
-#pragma unroll
-        for (int i = 0; i < NRU; ++i)
-            if (roff[i] >= 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_rsrc, (GRNET_LDS_AS void*)(dst + (i * 512 + wave * 64) * 4), 16, roff[i], soff, 0, 0);
-        asm volatile("" ::: "memory");
-    };
+    auto issue_raw = [&](int chunk) { G::issue_raw(roff, r_rsrc, raw, chunk, wave, HW); };
 
     // ---- input transform: thread = (channel 0..15, tile slot 0..15, half), as in the 4-wave kernel (WD = 28: the 16 lanes are two tile rows of
     // 7 tiles + 1 idle lane each; idle lanes supply the zero on both sides there)
@@ -408,32 +323,11 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
     const int slot = real ? trl * TPR + pc : 14 + (WD == 56 ? px - 14 : trl);
     const int vpos = (hf * 18) * (kCKW * 16) + chn * 16 + slot;            // + (rr * 6 + c) * 256 for row rr of the half, column c
     auto transform = [&](const float* rp, float* vp) {
-        float e[3][6];
-        float d[6][6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rp + i * WD);
-            d[i][1] = v[0]; d[i][2] = v[1]; d[i][3] = v[2]; d[i][4] = v[3];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            d[i][0] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(WD == 56 || real ? d[i][4] : 0.f), 0x111, 0xf, 0xf, true));   // row_shr:1
-            d[i][5] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(real ? d[i][1] : 0.f), 0x101, 0xf, 0xf, true));               // row_shl:1
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const float col[6] = {d[0][j], d[1][j], d[2][j], d[3][j], d[4][j], d[5][j]};
-            if (hf == 0) bt_lo(col, e[0][j], e[1][j], e[2][j]);
-            else bt_hi(col, e[0][j], e[1][j], e[2][j]);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) {
-            float o[6];
-            bt_lo(e[rr], o[0], o[1], o[2]);
-            bt_hi(e[rr], o[3], o[4], o[5]);
-#pragma unroll
-            for (int c = 0; c < 6; ++c) vp[(rr * 6 + c) * (kCKW * 16)] = o[c];
-        }
+        Wino4Patch<G> t;
+        t.read(rp);
+        t.halo(real);
+        t.rows(hf);
+        t.cols(vp);
     };
 
     f32x4 acc[9][NPW];                                   // [point of this wave][16-channel block of its half]
@@ -479,16 +373,13 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
 
     // thread (half h, channel c of the pass's 16, tile t) of the epilogue: 4 output rows of 4 pixels; the residual rows of a pass are requested a pass ahead
     const bool has_add = a.n_add == 1;
-    const int eh = tid >> 8, et2 = tid & 255, ec = et2 / 14, et = et2 - ec * 14, etro = et / TPR, etx = et - etro * TPR, eorow = 4 * (TRG * r + etro);
-    const bool ethread = et2 < 14 * 16 && eorow < a.H;
+    const int eh = tid >> 8;
+    typename G::Epi ep;
+    G::epi(tid & 255, r, a.H, ep);
     f32x4 radd[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     auto fetch_res = [&](int nt) {
-        const int co = by * COUTW + eh * (NPW * 16) + nt * 16 + ec;
-        if (has_add && ethread && co < a.Cout) {
-            const float* ap = a.add[0] + ((size_t)img * a.add_ctot[0] + a.add_coff[0] + co) * HW + eorow * WD + 4 * etx;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) radd[i] = *reinterpret_cast<const f32x4*>(ap + i * WD);
-        }
+        const int co = by * COUTW + eh * (NPW * 16) + nt * 16 + ep.ec;
+        if (has_add && ep.on && co < a.Cout) G::fetch_res(radd, a, ep, img, co, HW);
     };
 
     issue_raw(0);
@@ -524,8 +415,8 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
     }
 
     // ---- epilogue: inverse transform A^T M A, + bias, + residual, ReLU; both halves go through LDS together, 16 channels each per pass
-    float* Mx = smem + hf * (36 * 16 * kMrow);           // this wave's half: [36 points][16 channels][20]
-    const float* Mr = smem + eh * (36 * 16 * kMrow);     // the half this thread reads
+    float* Mx = smem + hf * G::MTILE;                    // this wave's half: [36 points][16 channels][20]
+    const float* Mr = smem + eh * G::MTILE;              // the half this thread reads
     for (int nt = 0; nt < NPW; ++nt) {
         __syncthreads();
 #pragma unroll
@@ -538,28 +429,24 @@ __device__ __forceinline__ void conv_wino4w_body(const ConvArgs& a) {
         __syncthreads();
         const f32x4 rcur[4] = {radd[0], radd[1], radd[2], radd[3]};
         if (nt + 1 < NPW) fetch_res(nt + 1);
-        if (ethread) {
-            const int co = by * COUTW + eh * (NPW * 16) + nt * 16 + ec;
+        if (ep.on) {
+            const int co = by * COUTW + eh * (NPW * 16) + nt * 16 + ep.ec;
             if (co < a.Cout) {
                 float s4[4][6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
                     float m[6];
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) m[i] = Mr[((i * 6 + j) * 16 + ec) * kMrow + et];
-                    const float p12 = m[1] + m[2], m12 = m[1] - m[2], p34 = m[3] + m[4], m34 = m[3] - m[4];
-                    s4[0][j] = m[0] + p12 + p34;
-                    s4[1][j] = fmaf(2.f, m34, m12);
-                    s4[2][j] = fmaf(4.f, p34, p12);
-                    s4[3][j] = fmaf(8.f, m34, m12) + m[5];
+                    for (int i = 0; i < 6; ++i) m[i] = Mr[((i * 6 + j) * 16 + ep.ec) * kMrow + ep.et];
+                    at_f43(m, s4[0][j], s4[1][j], s4[2][j], s4[3][j]);
                 }
                 const float b = a.bias[co];
-                const size_t obase = ((size_t)img * a.out_ctot + a.out_coff + co) * HW + eorow * WD + 4 * etx;
+                const size_t obase = ((size_t)img * a.out_ctot + a.out_coff + co) * HW + ep.eorow * WD + 4 * ep.etx;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float* q = s4[i];
-                    const float p12 = q[1] + q[2], m12 = q[1] - q[2], p34 = q[3] + q[4], m34 = q[3] - q[4];
-                    f32x4 y = f32x4{q[0] + p12 + p34 + b, fmaf(2.f, m34, m12) + b, fmaf(4.f, p34, p12) + b, fmaf(8.f, m34, m12) + q[5] + b};
+                    float y0, y1, y2, y3;
+                    at_f43<true>(s4[i], y0, y1, y2, y3, b);
+                    f32x4 y = f32x4{y0, y1, y2, y3};
                     if (has_add) y += rcur[i];
                     if (a.relu) { y[0] = fmaxf(y[0], 0.f); y[1] = fmaxf(y[1], 0.f); y[2] = fmaxf(y[2], 0.f); y[3] = fmaxf(y[3], 0.f); }
                     *reinterpret_cast<f32x4*>(a.out + obase + i * WD) = y;
@@ -611,24 +498,16 @@ hipError_t conv_wino4_form(const ConvArgs& a, Wino4Form* f) {
     if (!conv_wino4_eligible(a.Cin, a.Cout, a.ks, a.stride, a.H, a.W, a.n_add) || a.CinPad % kCK != 0 || a.CoutPad % (f->nb * 16) != 0) return hipErrorInvalidValue;
     if (a.n_add == 1 && a.add_shift[0] != 0) return hipErrorInvalidValue;
     const int npw = conv_wino4_wide(a.Cout, a.W);
-    if (npw && a.CinPad % kCKW == 0 && a.CoutPad % (npw * 32) == 0 && !(a.dbg & 32)) {
-        const int trg = a.W == 56 ? 1 : 2;
-        f->waves = 8;
-        f->npw = npw;
-        f->gx = a.N * (((a.H >> 2) + trg - 1) / trg);
-        f->gy = a.CoutPad / (npw * 32);
-        f->xcd = f->gx % 8 == 0 && f->gx >= 16 ? 1 : 0;
-        f->full = f->gx * f->gy;
-        return hipSuccess;
-    }
-    const int trg = 14 / (a.W / 4);
-    f->waves = 4;
+    const bool wide = npw && a.CinPad % kCKW == 0 && a.CoutPad % (npw * 32) == 0 && !(a.dbg & 32);
+    const int trg = wino4_tile_rows(a.W);                // both kernels: a workgroup is one group of 14 tiles
+    f->waves = wide ? 8 : 4;
+    f->npw = wide ? npw : 0;
     f->gx = a.N * (((a.H >> 2) + trg - 1) / trg);
-    f->gy = a.CoutPad / (f->nb * 16);
+    f->gy = a.CoutPad / (wide ? npw * 32 : f->nb * 16);
     f->xcd = f->gx % 8 == 0 && f->gx >= 16 ? 1 : 0;
     const int total = f->gx * f->gy;
     f->full = total;
-    if (f->nb == 2) return hipSuccess;
+    if (wide || f->nb == 2) return hipSuccess;
     static const int split_env = GRNET_AB(WINO_SPLIT, 1);
     int kCUs = 0;                                        // workgroups per round = CUs of this device (one workgroup fits a CU)
     if (hipError_t e = device_cu_count(&kCUs); e != hipSuccess) return e;
@@ -641,15 +520,20 @@ hipError_t conv_wino4_form(const ConvArgs& a, Wino4Form* f) {
     return hipSuccess;
 }
 
-template <int WD>
-static hipError_t launch_wino4_w(ConvArgs a, hipStream_t s, const Wino4Form& f, int* n_launches) {
-    const size_t kLdsB = wino4_lds();
+// the grid of form f in the kernel arguments: one launch, unless the caller adds the half-size last round
+static void apply_form(ConvArgs& a, const Wino4Form& f, int* n_launches) {
     a.gx = f.gx;
     a.gy = f.gy;
     a.xcd = f.xcd;
     a.blk0 = 0;
     a.wsplit = 0;
     if (n_launches) *n_launches = 1;
+}
+
+template <int WD>
+static hipError_t launch_wino4_w(ConvArgs a, hipStream_t s, const Wino4Form& f, int* n_launches) {
+    const size_t kLdsB = wino4_lds();
+    apply_form(a, f, n_launches);
     const int total = a.gx * a.gy;
 #ifdef GRNET_ABLATION
     if constexpr (WD == 56) {
@@ -680,22 +564,17 @@ hipError_t launch_conv_wino4(ConvArgs a, hipStream_t s, int* n_launches) {
     if (hipError_t e = current_device(&dev); e != hipSuccess) return e;
     if (hipError_t e = once_per_device(attr, dev, [](int*) {
             hipError_t e = hipSuccess;
-            auto set = [&](auto kern) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino4_lds()); };
-            set(conv_wino4_f32<4, 56>); set(conv_wino4_f32<2, 56>); set(conv_wino4_f32<4, 28>); set(conv_wino4_f32<2, 28>);
-            set(conv_wino4_f32<2, 56, 0, true>); set(conv_wino4_f32<2, 28, 0, true>);
-            auto setw = [&](auto kern) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsW); };
-            setw(conv_wino4w_f32<56, 4>); setw(conv_wino4w_f32<56, 2>); setw(conv_wino4w_f32<28, 4>); setw(conv_wino4w_f32<28, 2>);
+            const size_t l4 = wino4_lds();
+            auto set = [&](auto kern, size_t lds) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); };
+            set(conv_wino4_f32<4, 56>, l4); set(conv_wino4_f32<2, 56>, l4); set(conv_wino4_f32<4, 28>, l4); set(conv_wino4_f32<2, 28>, l4);
+            set(conv_wino4_f32<2, 56, 0, true>, l4); set(conv_wino4_f32<2, 28, 0, true>, l4);
+            set(conv_wino4w_f32<56, 4>, kLdsW); set(conv_wino4w_f32<56, 2>, kLdsW); set(conv_wino4w_f32<28, 4>, kLdsW); set(conv_wino4w_f32<28, 2>, kLdsW);
             return e;
         }); e != hipSuccess) return e;
     Wino4Form f;
     if (hipError_t e = conv_wino4_form(a, &f); e != hipSuccess) return e;
     if (f.waves == 8) {
-        a.gx = f.gx;
-        a.gy = f.gy;
-        a.xcd = f.xcd;
-        a.blk0 = 0;
-        a.wsplit = 0;
-        if (n_launches) *n_launches = 1;
+        apply_form(a, f, n_launches);
         const dim3 grid(a.gx * a.gy);
         if (a.W == 56) return f.npw == 4 ? launch_k(conv_wino4w_f32<56, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<56, 2>, grid, dim3(512), kLdsW, s, a);
         return f.npw == 4 ? launch_k(conv_wino4w_f32<28, 4>, grid, dim3(512), kLdsW, s, a) : launch_k(conv_wino4w_f32<28, 2>, grid, dim3(512), kLdsW, s, a);
@@ -728,28 +607,21 @@ void wino4_transform_filter(const double* g, double* u) {
 
 // U = G g G^T per (cout, cin) in fp64 -> [36][cin_pad][cout_pad] fp32; w: (cout, cin, 3, 3) folded weights (double)
 void pack_wino4_weights(const double* w, int cout, int cin, int cin_pad, int cout_pad, float* out, int wid) {
-    static const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     const int nb = conv_wino4_blocks(cout, wid), tc = nb * 16;              // the kernel variant launch_conv_wino4 picks for this layer
     for (size_t i = 0; i < (size_t)36 * cin_pad * cout_pad; ++i) out[i] = 0.f;
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci) {
             // within a workgroup's tc channels, channel n*16 + l sits at l*nb + n: lane l's nb MFMA B fragments are one load
             const int cpos = (co / tc) * tc + (co % 16) * nb + (co % tc) / 16;
-            const double* g = w + ((size_t)co * cin + ci) * 9;
-            double t[6][3];
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 3; ++j) t[i][j] = G[i][0] * g[j] + G[i][1] * g[3 + j] + G[i][2] * g[6 + j];
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 6; ++j) {
-                    const double u = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];
-                    const int p = i * 6 + j;
-                    if (nb == 4) out[((size_t)p * cin_pad + ci) * cout_pad + cpos] = (float)u;
-                    else {                               // 32-channel layers: [point][chunk][k % 4][32-channel block][channel l][k-step][n]
-                        const int chunk = ci / kCK, ks = (ci % kCK) / 4, kq = ci % 4;
-                        out[(((size_t)p * (cin_pad / kCK) + chunk) * 4 + kq) * ((size_t)cout_pad * 2) + (co / 32) * 64 + (co % 16) * 4 + ks * 2 + (co % 32) / 16] = (float)u;
-                    }
+            double u[36];
+            wino4_transform_filter(w + ((size_t)co * cin + ci) * 9, u);
+            for (int p = 0; p < 36; ++p) {
+                if (nb == 4) out[((size_t)p * cin_pad + ci) * cout_pad + cpos] = (float)u[p];
+                else {                                   // 32-channel layers: [point][chunk][k % 4][32-channel block][channel l][k-step][n]
+                    const int chunk = ci / kCK, ks = (ci % kCK) / 4, kq = ci % 4;
+                    out[(((size_t)p * (cin_pad / kCK) + chunk) * 4 + kq) * ((size_t)cout_pad * 2) + (co / 32) * 64 + (co % 16) * 4 + ks * 2 + (co % 32) / 16] = (float)u[p];
                 }
+            }
         }
 }
 

@@ -54,15 +54,13 @@ __global__ __launch_bounds__(64 * KS) void conv_wino4s_f32(const ConvArgs a) {
     const int id = blockIdx.x, jd = id >> 3;
     const int nb = (id & 7) + 8 * (jd % (NBK / 8)), grp = jd / (NBK / 8);
     const int img0 = grp * IPW;
-    if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (a.prio >= 2) __builtin_amdgcn_s_setprio(3);
+    set_wave_prio(a.prio);
 
     // tile of this lane as A-operand row: x-major, so that the x neighbours are SH lanes away inside the 16-lane row
     const int tx = WD == 14 ? (l15 >> 2) : (l15 >> 3), ty = WD == 14 ? (l15 & 3) : (l15 & 1), ii = WD == 14 ? 0 : ((l15 >> 1) & 3);
     const bool img_ok = img0 + ii < a.N;
     const float* inb = a.in + ((size_t)img0 * a.in_ctot + a.in_coff) * HW;
-    const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)inb, (short)0, (((IPW - 1) * a.in_ctot + C) * HW + 4) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, 36 * C * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_rsrc = buffer_rsrc(inb, (((IPW - 1) * a.in_ctot + C) * HW + 4) * 4), u_rsrc = buffer_rsrc(a.w, 36 * C * C * 4);
     int voff[6], voff2[WD == 14 ? 6 : 1];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(64 * KS) void conv_wino4s_f32(const ConvArgs a) {
 
     // ---- epilogue.  The residual of this wave's share of the read-out is requested now.
     const size_t slab0 = ((size_t)img0 * a.out_ctot + a.out_coff + nb * 16) * HW;          // first float of image img0's slab
-    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + slab0), (short)0, ((IPW - 1) * a.out_ctot * HW + G::SLAB) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t o_rsrc = buffer_rsrc(a.out + slab0, ((IPW - 1) * a.out_ctot * HW + G::SLAB) * 4);
     const bool has_add = a.n_add == 1;
     int uoff[G::ITERS], goff[G::ITERS];                  // LDS float offset inside a slot / global byte offset from image img0's slab
     f32x4 res[G::ITERS];
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(64 * KS) void conv_wino4s_f32(const ConvArgs a) {
     }
     if (has_add) {
         const size_t aslab0 = ((size_t)img0 * a.add_ctot[0] + a.add_coff[0] + nb * 16) * HW;
-        const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.add[0] + aslab0), (short)0, ((IPW - 1) * a.add_ctot[0] * HW + G::SLAB) * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t a_rsrc = buffer_rsrc(a.add[0] + aslab0, ((IPW - 1) * a.add_ctot[0] * HW + G::SLAB) * 4);
 #pragma unroll
         for (int it = 0; it < G::ITERS; ++it) {
             const int u = it * (64 * KS) + kw * 64 + lane;
@@ -187,21 +185,16 @@ __global__ __launch_bounds__(64 * KS) void conv_wino4s_f32(const ConvArgs a) {
         float s[4][6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            const float m0 = acc[j][i], m1 = acc[6 + j][i], m2 = acc[12 + j][i], m3 = acc[18 + j][i], m4 = acc[24 + j][i], m5 = acc[30 + j][i];
-            const float p12 = m1 + m2, m12 = m1 - m2, p34 = m3 + m4, m34 = m3 - m4;
-            s[0][j] = m0 + p12 + p34;
-            s[1][j] = fmaf(2.f, m34, m12);
-            s[2][j] = fmaf(4.f, p34, p12);
-            s[3][j] = fmaf(8.f, m34, m12) + m5;
+            const float m[6] = {acc[j][i], acc[6 + j][i], acc[12 + j][i], acc[18 + j][i], acc[24 + j][i], acc[30 + j][i]};
+            at_f43(m, s[0][j], s[1][j], s[2][j], s[3][j]);
         }
         const int slot = 4 * lq + i;
         const int stx = WD == 14 ? (slot >> 2) : (slot >> 3), sty = WD == 14 ? (slot & 3) : (slot & 1), sii = WD == 14 ? 0 : ((slot >> 1) & 3);
         float* op = Ow + sii * G::SLABP + l15 * HW + (4 * sty) * WD + 4 * stx;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float* q = s[r];
-            const float p12 = q[1] + q[2], m12 = q[1] - q[2], p34 = q[3] + q[4], m34 = q[3] - q[4];
-            const float y0 = q[0] + p12 + p34 + bias, y1 = fmaf(2.f, m34, m12) + bias, y2 = fmaf(4.f, p34, p12) + bias, y3 = fmaf(8.f, m34, m12) + q[5] + bias;
+            float y0, y1, y2, y3;
+            at_f43<true>(s[r], y0, y1, y2, y3, bias);
             if (4 * sty + r < WD) {
                 if constexpr (WD == 14) {
                     *reinterpret_cast<f32x2*>(op + r * WD) = f32x2{y0, y1};

@@ -1,5 +1,5 @@
-// Device-side helpers shared by the kernels: vector types, bf16 packing, the LDS-only barrier, wave reductions, the LDS-DMA forms, and the
-// timing-only hooks of the diagnostic build.  Included by the .hip files after kernels.h; the .cpp files do not include it.
+// Device-side helpers shared by the kernels: vector types, bf16 packing, the LDS-only barrier, wave reductions, the 1-D transforms of Winograd F(4,3),
+// wave priority and buffer resources, the LDS-DMA forms, and the timing-only hooks of the diagnostic build.  Included by the .hip files after kernels.h; the .cpp files do not include it.
 #pragma once
 #include "kernels.h"
 
@@ -74,6 +74,27 @@ __device__ __forceinline__ void bt_hi(const float* d, float& r3, float& r4, floa
     r3 = u1 + u2;
     r4 = u1 - u2;
     r5 = fmaf(4.f, d[1], fmaf(-5.f, d[3], d[5]));
+}
+// the 1-D output transform: A^T = [1 1 1 1 1 0] [0 1 -1 2 -2 0] [0 1 1 4 4 0] [0 1 -1 8 -8 1]; rows, then columns of A^T M A go through it.  ADD: + add
+// behind each result (the column pass adds the bias there; written into the same expressions, the epilogues compile as they did with the sums spelled out)
+template <bool ADD = false>
+__device__ __forceinline__ void at_f43(const float* m, float& s0, float& s1, float& s2, float& s3, float add = 0.f) {
+    const float p12 = m[1] + m[2], m12 = m[1] - m[2], p34 = m[3] + m[4], m34 = m[3] - m[4];
+    auto out = [&](float v) { return ADD ? v + add : v; };
+    s0 = out(m[0] + p12 + p34);
+    s1 = out(fmaf(2.f, m34, m12));
+    s2 = out(fmaf(4.f, p34, p12));
+    s3 = out(fmaf(8.f, m34, m12) + m[5]);
+}
+
+// wave priority of a layer (ConvArgs::prio): 1 = on the critical chain, >= 2 = the pole of it
+__device__ __forceinline__ void set_wave_prio(int prio) {
+    if (prio == 1) __builtin_amdgcn_s_setprio(1);
+    else if (prio >= 2) __builtin_amdgcn_s_setprio(3);
+}
+// raw buffer resource over `bytes` bytes from p: offsets past the end load zeros and store nothing
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* p, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
 }
 
 // ---- LDS-DMA: lane l's 16 bytes land at the wave's LDS base + 16 l; the source address is per lane.  Four forms.
