@@ -4,6 +4,9 @@ precomputed bounding boxes, writing the reference's joblib "json" database
 {'vid_name': (F,), 'bbox': (F,4) f32, 'joints3D': (F,25,3) f32 kinectv2} every 50 videos
 (reference: batch_generation.py:180-287 prepare_data, :289-371 run_grnet_on_frame, argparse :373-387).
 
+The boxes come from --bbox_path (a joblib file, as the reference's prepare_data wants it) or are made here from a folder of OpenPose .mat
+files (--openpose_folder: the reference's load_openpose_anno, batch_generation.py:39-178, with the K-medoids centre on the GPU).
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -43,9 +46,31 @@ def flush_windows(n_videos, max_vid):
     return [(a, b) for a, b in zip(cuts, cuts[1:]) if b > a]
 
 
+def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_factory=None):
+    """load_openpose_anno (batch_generation.py:95-178): {vid_name: (T,4) float64 boxes} from a folder of OpenPose .mat files, by
+    pipeline.openpose_boxes -- on the GPU through a GRNet handle without weights (model_factory(local_rank) -> an object with
+    bbox_from_joints2d: the seam of the CPU tests), or on the host (on_host).  The call is deterministic, so under several ranks every
+    rank computes the same boxes; rank 0 writes them to bbox_out with joblib.dump, and the bad files' names to bbox_out + '.bad'."""
+    pkg = importlib.import_module(PKG)
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    model = None
+    if not on_host:
+        model = model_factory(local_rank) if model_factory is not None else pkg.GRNet(max_frames=1, device_id=local_rank)
+    boxes, bad = pkg.pipeline.openpose_boxes(openpose_folder, model=model)
+    if model is not None and hasattr(model, "close"):
+        model.close()
+    if bbox_out and int(os.environ.get("RANK", "0")) == 0:
+        import joblib
+        joblib.dump(boxes, bbox_out)
+        joblib.dump(bad, bbox_out + ".bad")
+        print(f"Save {len(boxes)} boxes to {bbox_out} ({len(bad)} files without usable 2D joints: {bbox_out}.bad).")
+    return boxes
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
-                 model_factory=None, backend="nccl", exchange="torch", full_arena=False):
-    """model_factory(local_rank) -> model and backend="gloo" are the seam of the CPU tests (tests/test_host_cpu.py): the window / plan /
+                 model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None):
+    """annos: the boxes themselves ({vid_name: (T,4)}, boxes_from_openpose) instead of the joblib file fv.
+    model_factory(local_rank) -> model and backend="gloo" are the seam of the CPU tests (tests/test_host_cpu.py): the window / plan /
     run / gather / flush logic below then runs under two gloo ranks with a stand-in model and tensors on the CPU.
     exchange: "torch" = the window's all-gather through the launcher's process group; "capi" = through the C ABI's own RCCL communicator
     (harness.RcclComm: grnet_comm_create + grnet_allgather; needs one GPU per rank)."""
@@ -54,8 +79,9 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     pkg = importlib.import_module(PKG)
     pipe = importlib.import_module(PKG + ".pipeline")
     harness = pkg.harness
-    assert osp.isfile(fv), fv
-    annos = joblib.load(fv)
+    if annos is None:
+        assert osp.isfile(fv), fv
+        annos = joblib.load(fv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
@@ -143,10 +169,14 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     return db.written if rank == 0 else []
 
 
-if __name__ == "__main__":
+def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--vid_folder", type=str, default="", help="folder containing one frame folder per video.")
     p.add_argument("--bbox_path", type=str, default="", help="joblib file with the precomputed bbox per video.")
+    p.add_argument("--openpose_folder", type=str, default="", help="folder of OpenPose .mat files ('skeleton': (P,T,25,3), normalised): the boxes are made from them "
+                   "(the reference's load_openpose_anno) instead of read from --bbox_path; without --vid_folder the script writes --bbox_out and exits")
+    p.add_argument("--bbox_out", type=str, default="", help="with --openpose_folder: joblib file that receives the boxes (the files without usable joints: FILE.bad)")
+    p.add_argument("--bbox_on_host", action="store_true", help="with --openpose_folder: the numpy float64 statement of the box instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -156,6 +186,19 @@ if __name__ == "__main__":
     p.add_argument("--full_arena", action="store_true", help="one buffer per intermediate tensor (the library's default layout: 41 GB at 400 frames in f32 "
                    "against 5.5 GB); this script never reads intermediates, so it shares buffers by liveness -- same launches, bit-identical outputs")
     p.add_argument("--exchange", choices=("torch", "capi"), default="torch", help="multi-GPU: the all-gather through torch.distributed or through the C ABI's grnet_allgather")
-    a = p.parse_args()
+    a = p.parse_args(argv)
+    if a.bbox_path and a.openpose_folder:
+        sys.exit("batch_generation.py: --bbox_path and --openpose_folder both name the source of the boxes: give one of them")
+    if (a.bbox_out or a.bbox_on_host) and not a.openpose_folder:
+        sys.exit("batch_generation.py: --bbox_out and --bbox_on_host belong to --openpose_folder, which was not given")
+    if a.openpose_folder and not a.vid_folder and not a.bbox_out:
+        sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
+    annos = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host) if a.openpose_folder else None
+    if a.openpose_folder and not a.vid_folder:
+        return
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
-                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena)
+                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos)
+
+
+if __name__ == "__main__":
+    main()

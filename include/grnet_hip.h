@@ -471,6 +471,27 @@ int grnet_op_segments_setup(grnet_t* h, const float* points_dev, int P, const fl
 int grnet_op_raster_segments(grnet_t* h, const int32_t* xy_dev, const float* depth_dev, int P, const int32_t* segments_host, int S,
                              const int32_t* widths_host, int H, int W, int32_t* winner_dev, void* stream);
 
+/* ---- one box per sequence from 2D joints -- batch_generation.py:39-93, get_bbox_from_joints2d(smooth=False) (csrc/bbox_kernels.hip) ----
+ * joints_dev: float64 (sum T, K, 3) rows (x, y, score) in pixels, n_seq sequences lying back to back; frame_offsets_host: n_seq + 1 frame offsets,
+ * the first 0.  Per frame, joints whose score is below `threshold` take the three components of the joint with the highest score (the first of equal
+ * ones), and h = lr_y - ul_y after ul_y -= (lr_y - ul_y) 0.10.  Per sequence, the centre is the exact 1-medoid of its T K float32 points (x, y, score):
+ * the point whose summed distance to all the others is smallest, the lowest index among equal sums -- the fixed point of the reference's K-medoids
+ * with k = 1 -- and nw = nh = median(h) 1.1, times 1.8 if that is below 500.  bbox_dev (n_seq,4) float64 = [cx, cy, nw, nh], cx and cy float32 values
+ * widened; medoid_dev (n_seq) int32 or NULL: the medoid's index into its sequence's T K points.  Distances are formed in float32 and summed in float64
+ * in a fixed order with no atomics: the float64 cost of the chosen point is within (1 + 1e-6) of the minimum, and the result does not depend on
+ * scheduling.  The input must be finite.  Needs no weights: works on a handle straight from grnet_create.  No host synchronisation; the only allocation
+ * is a scratch buffer owned by the handle, outside the activation arena, that grows (synchronising the device) when a call is larger than any before.
+ * GRNET_EINVAL (with a message, nothing is launched): K outside [1, 64], n_seq < 1, a null pointer, a non-finite threshold, frame_offsets[0] != 0, an
+ * empty sequence or offsets that do not increase, a sequence of more than 4096 frames (the n x n matrix of the reference itself would be 42 GB there).
+ *
+ * grnet_op_medoid: the 1-medoid alone.  points_dev (n,4) float32 rows (x, y, s, pad), 16-byte aligned; point_offsets_host: n_seq + 1 point offsets,
+ * the first 0, a sequence of 1 .. 262144 points; splits: column splits of the row sums, 1 .. 64, or 0 for the library's choice.  index_dev (n_seq)
+ * int32 and cost_dev (n_seq) float64: the chosen row of each sequence and its summed distance.  Same refusals. */
+int grnet_bbox_from_joints2d(grnet_t* h, const double* joints_dev, int K, const int32_t* frame_offsets_host, int n_seq, double threshold,
+                             double* bbox_dev, int32_t* medoid_dev, void* stream);
+int grnet_op_medoid(grnet_t* h, const float* points_dev, const int32_t* point_offsets_host, int n_seq, int splits, int32_t* index_dev, double* cost_dev,
+                    void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -29,6 +29,7 @@ grnet::~grnet() {
     for (hipEvent_t e : seg_stage_done)
         if (e) (void)hipEventDestroy(e);
     if (temporal_ws) (void)hipFree(temporal_ws);
+    if (bbox_ws) (void)hipFree(bbox_ws);
     if (gru_fault) (void)hipHostFree(gru_fault);
     if (arena) (void)hipFree(arena);
 }

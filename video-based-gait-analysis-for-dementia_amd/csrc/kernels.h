@@ -311,6 +311,27 @@ int smooth_joint_count(int kind);  // 49 / 29 / 25 for GRNET_JOINTS_SPIN49 / _SP
 // kp29 (n,29,3) as launch_smpl wrote it (rows 0..23 are read), verts (n,6890,3) -> joints (n,smooth_joint_count(kind),3)
 hipError_t launch_smpl_joints54(const float* kp29, const float* verts, SmplTables t, int kind, float* joints, int n, hipStream_t s);
 
+// One box per sequence from 2D joints (batch_generation.py:39-93; csrc/bbox_kernels.hip, compiled without fma contraction) ----
+constexpr int kBboxMaxJoints = 64;     // joints per frame: one wave lane each
+constexpr int kBboxMaxFrames = 4096;   // frames per sequence: the heights of one sequence fit the LDS of the median's workgroup
+constexpr double kBboxMinPixel = 500., kBboxSmallScale = 1.8;   // batch_generation.py:27-28 (MIN_PIXEL, BS)
+constexpr int kMedoidRows = 256;       // rows per workgroup of the row-sum kernel, one per thread
+constexpr int kMedoidTile = 1024;      // columns staged in LDS at a time (16 KiB)
+constexpr int kMedoidMaxSplits = 64;   // column splits of one row tile
+constexpr int kMedoidBatch = 128;      // sequences per launch: their offsets travel as a kernel argument
+struct MedoidBatch { int n; int off[kMedoidBatch + 1]; };       // point offsets of n sequences lying back to back, from the start of the points
+// columns of one split: the n columns in `splits` equal runs, rounded up to the row-sum kernel's unroll; split s covers [s c, min(n, (s + 1) c))
+__host__ __device__ inline int medoid_split_columns(int n, int splits) { return ((n + splits - 1) / splits + 7) & ~7; }
+// joints (frames,K,3) float64 -> points (frames K,4) float32 (x, y, s, 0) after the score rule, hgt (frames) float64
+hipError_t launch_bbox_prepare(const double* joints, int K, int frames, double threshold, float* points, double* hgt, hipStream_t s);
+// partial [splits][n] float64 per sequence, sequence q at partial + splits * off[q]: the sums of row i over the columns of each split
+hipError_t launch_medoid_rowsum(const float* points, const MedoidBatch& b, int splits, double* partial, hipStream_t s);
+// per sequence q of the batch (entry seq0 + q of the outputs; each may be NULL): the row of least cost, that cost, its (x, y)
+hipError_t launch_medoid_argmin(const float* points, const MedoidBatch& b, int seq0, int splits, const double* partial, int* index, double* cost,
+                                float* centre, hipStream_t s);
+// off / K are frame offsets into hgt; bbox (n_seq,4) float64 = [cx, cy, nw, nh]
+hipError_t launch_bbox_assemble(const double* hgt, const MedoidBatch& b, int seq0, int K, const float* centre, double* bbox, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

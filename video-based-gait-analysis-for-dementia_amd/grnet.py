@@ -870,6 +870,58 @@ class GRNet:
         """op_raster for the wireframe: 3 face + k of the winning edge per pixel, k = 0: v0->v1, 1: v1->v2, 2: v2->v0 (grnet_op_raster_lines)."""
         return self._op_raster("grnet_op_raster_lines", xy, z, faces, H, W)
 
+    # ------------------------------------------------------------------ boxes from 2D joints (batch_generation.py:39-93)
+    @staticmethod
+    def _sequence_offsets(rows, lengths, what):
+        """n_seq + 1 int32 offsets of sequences of `lengths` rows lying back to back (None: one sequence of all rows).  Which lengths the
+        device takes is the C ABI's to say."""
+        lengths = [int(rows)] if lengths is None else [int(v) for v in lengths]
+        if sum(lengths) != rows or sum(lengths) > 2**31 - 1:
+            raise ValueError(f"lengths sum to {sum(lengths)}, {what} has {rows} rows")
+        off = np.zeros(len(lengths) + 1, np.int32)
+        off[1:] = np.cumsum(np.asarray(lengths, np.int64))
+        return off
+
+    def bbox_from_joints2d(self, joints2d, lengths=None, threshold=0.1, return_index=False):
+        """One box per sequence from 2D joints, get_bbox_from_joints2d(smooth=False) on the device (grnet_bbox_from_joints2d).
+        joints2d (T,K,3) rows (x, y, score) in pixels, or (sum T,K,3) with the sequences' `lengths` -- numpy or torch, taken as float64.
+        Returns a float64 device tensor (n_seq,4) = [cx, cy, nw, nh]; return_index: also the medoids' indices (n_seq,) int32 into their
+        sequences' T K points.  Works before finalize(): no weight is read.  ValueError on non-finite input."""
+        j = torch.as_tensor(joints2d)
+        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
+            raise ValueError(f"joints2d must be (T,K,3) with T >= 1, got {tuple(j.shape)}")
+        if not bool(torch.isfinite(j).all()):
+            raise ValueError("joints2d has a non-finite entry")
+        j = j.to(self.device, torch.float64).contiguous()
+        off = self._sequence_offsets(j.shape[0], lengths, "joints2d")
+        n_seq = len(off) - 1
+        box = torch.empty(n_seq, 4, dtype=torch.float64, device=self.device)
+        index = torch.empty(n_seq, dtype=torch.int32, device=self.device) if return_index else None
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_bbox_from_joints2d(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, float(threshold),
+                                                box.data_ptr(), index.data_ptr() if return_index else None, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_bbox_from_joints2d")
+        return (box, index) if return_index else box
+
+    def op_medoid(self, points, lengths=None, splits=0):
+        """The exact 1-medoid alone (grnet_op_medoid): points (n,3) or (n,4) float32 rows (x, y, s[, pad]), one sequence or `lengths` of them;
+        splits: column splits of the row sums, 0 = the library's choice.  Returns (index (n_seq,) int32, cost (n_seq,) float64) on the device:
+        each sequence's row of least summed distance, lowest index on ties, and that sum."""
+        p = torch.as_tensor(points).to(self.device, torch.float32)
+        if p.dim() != 2 or p.shape[1] not in (3, 4) or p.shape[0] < 1:
+            raise ValueError(f"points must be (n,3) or (n,4) with n >= 1, got {tuple(p.shape)}")
+        p4 = torch.zeros(p.shape[0], 4, dtype=torch.float32, device=self.device)
+        p4[:, :3] = p[:, :3]
+        off = self._sequence_offsets(p.shape[0], lengths, "points")
+        n_seq = len(off) - 1
+        index = torch.empty(n_seq, dtype=torch.int32, device=self.device)
+        cost = torch.empty(n_seq, dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_medoid(self._h, p4.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, int(splits), index.data_ptr(),
+                                       cost.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_medoid")
+        return index, cost
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

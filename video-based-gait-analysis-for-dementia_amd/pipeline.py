@@ -4,6 +4,7 @@ output formats, restated for the HIP model (numpy on the host, no kernels here).
 Reference counterparts:
   * demo model loop + result dict     demo.py:126-231  -> run_tracklet(), make_demo_result()
   * batch 3D-joint generation         batch_generation.py:289-371, 222-284 -> run_on_frames(), BatchDb
+  * boxes from OpenPose 2D joints     batch_generation.py:39-93, 95-178 -> bbox_from_joints2d(), openpose_boxes()
   * crop-cam / crop-coords -> image   lib/utils/demo_utils.py:176-209
   * spin2 -> kinectv2 joints          lib/data_utils/kp_utils.py:26-36 with the tables :211-242, :904-931
   * crop + normalise of a frame       lib/dataset/inference.py:71-87, lib/data_utils/img_utils.py:252-285,355-363
@@ -495,6 +496,106 @@ def write_obj(path, verts, faces):
     with open(path, "w") as f:
         f.write("".join(f"v {x:.8f} {y:.8f} {z:.8f}\n" for x, y, z in v))
         f.write("".join(f"f {a} {b} {c}\n" for a, b, c in np.asarray(faces, np.int64) + 1))
+
+
+# ----------------------------------------------------------------------------- boxes from 2D joints
+BBOX_MIN_PIXEL, BBOX_SMALL_SCALE = 500, 1.8                   # batch_generation.py:27-28 (MIN_PIXEL, BS)
+OPENPOSE_INTERACTIONS = (44, 45, 46, 47, 48)                  # :99, actions with two people
+OPENPOSE_MIN_CREDIBLE, OPENPOSE_MIN_SDIFF, OPENPOSE_MAX_THRESH = 3, 0.01, 0.3      # :30-32 (M, MIN_sdiff, MAX_THRESH)
+
+
+def medoid_index(points, block=256):
+    """The exact 1-medoid of float32 points: argmin_i sum_j |p_i - p_j| with the distances and sums in float64, lowest index on ties.  Row
+    blocks, so no n x n array is formed."""
+    cols = np.ascontiguousarray(np.asarray(points, np.float32).astype(np.float64).T)
+    best, at = np.inf, 0
+    for a in range(0, cols.shape[1], block):
+        d2 = sum((c[a:a + block, None] - c[None, :]) ** 2 for c in cols)
+        c = np.sqrt(d2).sum(axis=1)
+        k = int(np.argmin(c))
+        if c[k] < best:
+            best, at = c[k], a + k
+    return at
+
+
+def bbox_from_joints2d(kp_2d, threshold=0.1):
+    """get_bbox_from_joints2d(kp_2d, smooth=False, threshold) of batch_generation.py:39-93 in numpy float64, the host statement of
+    GRNet.bbox_from_joints2d: kp_2d (T,K,3) rows (x, y, score) in pixels -> (T,4) float64, the one box [cx, cy, nw, nh] repeated.  Joints
+    whose score is below the threshold take the frame's first joint of highest score; the centre is the exact 1-medoid of the T K float32
+    points over ALL THREE columns (the reference hands x, y and the score to euclidean_distances), which is the fixed point of its
+    kmedoids.fasterpam with one medoid; nw = nh = median(h) * 1.1, times 1.8 below 500 (the median of w is computed there and dropped)."""
+    kp = np.array(kp_2d, dtype=np.float64)
+    if kp.ndim != 3 or kp.shape[2] != 3 or kp.shape[0] < 1 or kp.shape[1] < 1:
+        raise ValueError(f"kp_2d must be (T,K,3) with T, K >= 1, got {kp.shape}")
+    if not np.isfinite(kp).all():
+        raise ValueError("kp_2d has a non-finite entry")
+    T, K = kp.shape[:2]
+    invalid = kp[:, :, 2] < threshold
+    ref = np.repeat(kp[np.arange(T), np.argmax(kp[:, :, 2], axis=-1)][:, None, :], K, axis=1)
+    kp[invalid] = ref[invalid]
+    ul_y, lr_y = kp[:, :, 1].min(axis=1), kp[:, :, 1].max(axis=1)
+    ul_y -= (lr_y - ul_y) * 0.10                               # prevent cutting the head
+    h = lr_y - ul_y
+    points = kp.reshape(-1, 3).astype(np.float32)
+    c_xy = points[medoid_index(points), :2]
+    nh = np.median(h) * 1.1
+    if nh < BBOX_MIN_PIXEL:
+        nh = nh * BBOX_SMALL_SCALE
+    return np.repeat(np.array([c_xy[0], c_xy[1], nh, nh], np.float64)[None, :], T, axis=0)
+
+
+def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080):
+    """load_openpose_anno of batch_generation.py:95-178 without its vis branches: one box per OpenPose .mat file of anno_folder ->
+    (boxes {vid_name: (T,4) float64, or None where no candidate's box has a positive size}, bad [file names]).  Every rule is the
+    reference's as written: files are 'A<action>_...' and the interaction actions 44-48 are skipped; 'skeleton' is (P,T,25,3), normalised;
+    an empty array, no person with more than 3 joints of positive score in every frame (:114), or no person passing the :120 test is a
+    bad file -- :120 indexes the 4-D array as joints2d[:,:,2], so it looks at the three components of JOINT 2 only; of several persons those
+    within 0.01 of the best mean score stay; x and y are scaled to pixels; the candidate with the strictly largest box wins, the first of
+    equal ones.  np.bool (:126) no longer exists in numpy: it is bool here.  Files are visited in sorted order (the reference: os.listdir
+    order), and a 'skeleton' of another dtype is widened to float64 first.
+    model=None: pipeline.bbox_from_joints2d per candidate.  With a GRNet, EVERY candidate of every file goes into ONE
+    model.bbox_from_joints2d call and the choice runs on the returned boxes."""
+    import scipy.io as sio
+    assert osp.isdir(anno_folder), anno_folder
+    boxes, bad, cands = {}, [], []                             # cands: (vid_name, [scaled (T,25,3) candidates])
+    for name in sorted(os.listdir(anno_folder)):
+        if int(name.split("_")[0][1:]) in OPENPOSE_INTERACTIONS:
+            continue
+        joints2d = np.asarray(sio.loadmat(osp.join(anno_folder, name))["skeleton"], dtype=np.float64)
+        if joints2d.size == 0:
+            bad.append(name)
+            continue
+        if not np.logical_and.reduce((joints2d[:, :, :, 2] > 0).sum(-1) > OPENPOSE_MIN_CREDIBLE, axis=-1).sum():
+            bad.append(name)
+            continue
+        seqlen = joints2d.shape[1]
+        valid = np.logical_and.reduce(np.logical_or.reduce(joints2d[:, :, 2] > OPENPOSE_MAX_THRESH, axis=-1), axis=-1)
+        if valid.sum() == 0:
+            bad.append(name)
+            continue
+        joints2d = joints2d[valid].reshape(-1, seqlen, 25, 3)
+        mask = np.array([True]).astype(bool)
+        if joints2d.shape[0] > 1:
+            scores = joints2d[:, :, :, 2].mean(-1).mean(-1)
+            mask = (scores.max() - scores) < OPENPOSE_MIN_SDIFF
+        j2ds = joints2d[mask].reshape(-1, seqlen, 25, 3)
+        j2ds[:, :, :, 0] *= img_w
+        j2ds[:, :, :, 1] *= img_h
+        cands.append((name.split(".")[0], list(j2ds)))
+    flat = [j for _, js in cands for j in js]
+    if model is None or not flat:
+        rows = [bbox_from_joints2d(j)[0] for j in flat]
+    else:
+        rows = list(model.bbox_from_joints2d(np.concatenate(flat, 0), lengths=[j.shape[0] for j in flat]).cpu().numpy())
+    k = 0
+    for vid_name, js in cands:
+        area, chosen = 0, None
+        for j in js:
+            if rows[k][2] > area:
+                area, chosen = rows[k][2], np.repeat(rows[k][None, :], j.shape[0], axis=0)
+            k += 1
+        boxes[vid_name] = chosen
+    return boxes, bad
 
 
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
