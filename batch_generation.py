@@ -7,6 +7,9 @@ precomputed bounding boxes, writing the reference's joblib "json" database
 The boxes come from --bbox_path (a joblib file, as the reference's prepare_data wants it) or are made here from a folder of OpenPose .mat
 files (--openpose_folder: the reference's load_openpose_anno, batch_generation.py:39-178, with the K-medoids centre on the GPU).
 
+--gt_path FILE (opt-in) compares the joints with ground truth in this script's own output schema and reports MPJPE, PA-MPJPE, acceleration and
+acceleration error per video in millimetres (GRNet.pose_metrics on the device; the reference has no evaluation code).
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -67,9 +70,82 @@ def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_fac
     return boxes
 
 
+def load_ground_truth(gt_path):
+    """{vid_name: (T,25,3) kinectv2 joints} from a joblib database in this script's own output schema: 'vid_name' (F,) and 'joints3D' (F,25,3),
+    the frames of a video in order."""
+    import joblib
+    db = joblib.load(gt_path)
+    names, joints = np.asarray(db["vid_name"]), np.asarray(db["joints3D"])
+    if joints.ndim != 3 or joints.shape[1:] != (25, 3) or names.shape[0] != joints.shape[0]:
+        raise ValueError(f"{gt_path}: 'vid_name' (F,) and 'joints3D' (F,25,3) expected, got {names.shape} and {joints.shape}")
+    rows = {}
+    for i, name in enumerate(names):
+        rows.setdefault(str(name), []).append(i)
+    return {name: joints[idx] for name, idx in rows.items()}
+
+
+METRIC_NAMES = ("mpjpe", "pa_mpjpe", "pve", "accel", "accel_err")     # the columns of pose_metrics; no vertices here, so pve is not reported
+
+
+class WindowMetrics:
+    """--gt_path: one pose_metrics call per database window on rank 0, one sequence per video, on the joints the gather left on the device
+    (model.pose_metrics; on_host, or a model without the method: pipeline.pose_metrics after a download).  root: kinectv2 joint 0; select: the
+    kinectv2 joints that spin2 fills (kps_tables.json, entries >= 0) -- convert_kps leaves the others at zero.  Millimetres."""
+
+    def __init__(self, gt, pipe, model, on_host):
+        self.gt, self.pipe = gt, pipe
+        self.device_call = None if on_host or not hasattr(model, "pose_metrics") else model.pose_metrics
+        table = pipe._kps_tables()["from_spin2"]["kinectv2"]
+        self.select = [k for k, i in enumerate(table) if i >= 0]
+        self.videos = {}
+        self.sums, self.counts = np.zeros(5), np.zeros(5, np.int64)
+
+    def add_window(self, keys, per_video):
+        """keys[vi], per_video[vi] (T,75): the videos of one window; a video the ground truth lacks, or of another length, is skipped."""
+        import torch
+        pred, truth, lengths, names = [], [], [], []
+        for vi, key in enumerate(keys):
+            kp = per_video[vi]
+            frames = int(kp.shape[0])
+            if key not in self.gt:
+                print(f"Metrics: skip video {key}, the ground truth has no such video.")
+            elif self.gt[key].shape[0] != frames:
+                print(f"Metrics: skip video {key}, {frames} frames here and {self.gt[key].shape[0]} in the ground truth.")
+            else:
+                pred.append(kp.reshape(frames, 25, 3))
+                truth.append(self.gt[key])
+                lengths.append(frames)
+                names.append(key)
+        if not names:
+            return
+        pred, truth = torch.cat(pred, 0), np.concatenate(truth, 0)
+        kw = dict(lengths=lengths, root=[0], select=self.select, unit=1000.0)
+        if self.device_call is not None:
+            per_seq = self.device_call(pred, truth, **kw)["per_sequence"].cpu().numpy()
+        else:
+            per_seq = self.pipe.pose_metrics(pred.cpu().numpy(), truth, **kw)["per_sequence"]
+        for name, T, row in zip(names, lengths, per_seq):
+            count = np.array([T, T, 0, max(T - 2, 0), max(T - 2, 0)], np.int64)
+            self.videos[name] = {"frames": T, **{m: (float(row[c]) if count[c] else None) for c, m in enumerate(METRIC_NAMES) if m != "pve"}}
+            self.sums += np.where(count > 0, row * count, 0.0)
+            self.counts += count
+
+    def write(self, path):
+        import json
+        total = {"frames": int(self.counts[0]), **{m: (float(self.sums[c] / self.counts[c]) if self.counts[c] else None)
+                                                   for c, m in enumerate(METRIC_NAMES) if m != "pve"}}
+        with open(path, "w") as f:
+            json.dump({**self.videos, "total": total}, f, indent=1, allow_nan=False)
+        shown = ", ".join(f"{m} {total[m]:.2f}" for m in total if m != "frames" and total[m] is not None)
+        print(f"Save metrics of {len(self.videos)} videos ({total['frames']} frames; mm: {shown}) to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
-                 model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None):
-    """annos: the boxes themselves ({vid_name: (T,4)}, boxes_from_openpose) instead of the joblib file fv.
+                 model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
+                 metrics_on_host=False):
+    """gt_path: also compare the joints with that ground truth (WindowMetrics) and write metrics_out (default: outpath with _metrics.json).
+    annos: the boxes themselves ({vid_name: (T,4)}, boxes_from_openpose) instead of the joblib file fv.
     model_factory(local_rank) -> model and backend="gloo" are the seam of the CPU tests (tests/test_host_cpu.py): the window / plan /
     run / gather / flush logic below then runs under two gloo ranks with a stand-in model and tensors on the CPU.
     exchange: "torch" = the window's all-gather through the launcher's process group; "capi" = through the C ABI's own RCCL communicator
@@ -117,6 +193,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             raise ValueError("exchange='capi' needs the nccl backend (one GPU per rank)")
         comm = harness.RcclComm(world, rank, dev, dist=dist)
     db = pipe.BatchDb(outpath) if rank == 0 else None
+    metrics = WindowMetrics(load_ground_truth(gt_path), pipe, model, metrics_on_host) if gt_path and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -146,6 +223,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             mine.append(kp.reshape(hi - lo, 75))
         local = torch.cat(mine, 0) if mine else torch.zeros(0, 75, device=dev)
         per_video = harness.gather_work_items(items, local, 75, world, rank, dist, dev, comm=comm)
+        if metrics is not None:
+            metrics.add_window([v[0] for v in vids], per_video)
         if rank == 0:
             for vi, (key, _, bboxes) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -158,6 +237,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     if rank == 0:
         print(f"=====>>> Generation frame rate: {n_done / max(time.time() - start, 1e-9):.1f}")
         print(f"Save database to {db.flush()}.")
+    if metrics is not None:
+        metrics.write(metrics_out or osp.splitext(outpath)[0] + "_metrics.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -177,6 +258,10 @@ def main(argv=None):
                    "(the reference's load_openpose_anno) instead of read from --bbox_path; without --vid_folder the script writes --bbox_out and exits")
     p.add_argument("--bbox_out", type=str, default="", help="with --openpose_folder: joblib file that receives the boxes (the files without usable joints: FILE.bad)")
     p.add_argument("--bbox_on_host", action="store_true", help="with --openpose_folder: the numpy float64 statement of the box instead of the GPU kernels")
+    p.add_argument("--gt_path", type=str, default="", help="joblib database in this script's output schema ('vid_name' (F,), 'joints3D' (F,25,3) kinectv2): report MPJPE, "
+                   "PA-MPJPE, acceleration and acceleration error per video against it (millimetres); a video it lacks, or of another length, is skipped")
+    p.add_argument("--metrics_out", type=str, default="", help="with --gt_path: the JSON file of the metrics (default: --outpath with _metrics.json)")
+    p.add_argument("--metrics_on_host", action="store_true", help="with --gt_path: the numpy float64 statement of the metrics instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -191,13 +276,16 @@ def main(argv=None):
         sys.exit("batch_generation.py: --bbox_path and --openpose_folder both name the source of the boxes: give one of them")
     if (a.bbox_out or a.bbox_on_host) and not a.openpose_folder:
         sys.exit("batch_generation.py: --bbox_out and --bbox_on_host belong to --openpose_folder, which was not given")
+    if (a.metrics_out or a.metrics_on_host) and not a.gt_path:
+        sys.exit("batch_generation.py: --metrics_out and --metrics_on_host belong to --gt_path, which was not given")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host) if a.openpose_folder else None
     if a.openpose_folder and not a.vid_folder:
         return
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
-                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos)
+                 synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
+                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host)
 
 
 if __name__ == "__main__":

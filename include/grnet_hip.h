@@ -492,6 +492,38 @@ int grnet_bbox_from_joints2d(grnet_t* h, const double* joints_dev, int K, const 
 int grnet_op_medoid(grnet_t* h, const float* points_dev, const int32_t* point_offsets_host, int n_seq, int splits, int32_t* index_dev, double* cost_dev,
                     void* stream);
 
+/* ---- pose metrics: MPJPE, PA-MPJPE, PVE, acceleration and acceleration error (csrc/metric_kernels.hip) ---------------------------
+ * The reference has no evaluation code; DESIGN.md 4.8 is the specification.  pred_dev, gt_dev: float32 (sum T, J, 3), n_seq sequences lying back
+ * to back; frame_offsets_host: n_seq + 1 frame offsets, the first 0.  Every input is widened to float64 and all arithmetic is float64.
+ * select_host: n_select indices into the J joints that enter the metrics (NULL with n_select 0: all J, in order); root_host: n_root indices into
+ * the J joints (select does not apply to them) whose mean is subtracted from every joint of the frame, for pred and for gt each with its own mean
+ * (NULL with n_root 0: nothing is subtracted).  P, G (m, 3): the selected joints of a frame after that.
+ *   mpjpe     mean_j |P_j - G_j|
+ *   pa_mpjpe  mean_j |s R P_j + t - G_j| for the similarity that minimises sum_j |s R P_j + t - G_j|^2: mu1, mu2 the joint means, X1 = (P - mu1)^T,
+ *             X2 = (G - mu2)^T, var1 = sum X1^2, K = X1 X2^T, R the proper rotation that maximises trace(R K) (one-sided Jacobi, csrc/procrustes3.h),
+ *             s = trace(R K) / var1, t = mu2 - s R mu1.  var1 == 0 (all selected pred joints equal): s = 0, R = I.
+ *   pve       mean_v |pred_verts_v - gt_verts_v|: pred_verts_dev, gt_verts_dev float32 (sum T, V, 3), both or neither; not aligned in any way
+ *   accel     mean_j |P[f-1]_j - 2 P[f]_j + P[f+1]_j|; accel_err: the same of P - G.  Interior frames of a sequence only.
+ * per_frame_dev (sum T, 5) float64 = [mpjpe, pa_mpjpe, pve, accel, accel_err], each times `unit` (1000: metres -> millimetres).  Entries undefined
+ * by structure are NaN: the two accelerations at the first and last frame of a sequence, pve without vertices.  per_seq_dev (n_seq, 5) and total_dev
+ * (5): the means over the structurally defined entries, NaN where there are none; the total is formed from the sequences' sums and counts.
+ * transform_dev (sum T, 13) = [s, R row-major (9), t (3)] in the inputs' own units (`unit` does not enter).  Any of the four may be NULL.
+ * Fixed summation orders, no atomics: a frame's row has the same bits whatever the call's size and the frame's position in it, a sequence's means
+ * the same bits whether it travels alone or with others.  The input must be finite.  Needs no weights: works on a handle straight from grnet_create.
+ * No host synchronisation; the only allocation is a scratch buffer owned by the handle, outside the activation arena, that grows (synchronising
+ * the device) when a call is larger than any before.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): J outside [1, 64], n_seq < 1, a null pred_dev, gt_dev or
+ * frame_offsets_host, n_select or n_root outside [1, 64] with its pointer or not 0 without it, an index outside [0, J), one vertex pointer without
+ * the other, V < 1 with vertices, a non-finite unit, frame_offsets[0] != 0, an empty sequence or offsets that do not increase.
+ *
+ * grnet_op_procrustes: the rotation alone (test hook).  K_dev (k,9) float64 row-major -> R_dev (k,9) the proper rotation maximising trace(R K),
+ * sigma_dev (k,3) the singular values of K, s1 >= s2 >= s3 >= 0.  K = 0 gives R = I.  GRNET_EINVAL: k < 1, a null pointer. */
+int grnet_pose_metrics(grnet_t* h, const float* pred_dev, const float* gt_dev, int J, const int32_t* frame_offsets_host, int n_seq,
+                       const int32_t* select_host, int n_select, const int32_t* root_host, int n_root, const float* pred_verts_dev,
+                       const float* gt_verts_dev, int V, double unit, double* per_frame_dev, double* per_seq_dev, double* total_dev, double* transform_dev,
+                       void* stream);
+int grnet_op_procrustes(grnet_t* h, const double* K_dev, int k, double* R_dev, double* sigma_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

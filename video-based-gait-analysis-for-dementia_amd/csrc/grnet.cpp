@@ -30,6 +30,7 @@ grnet::~grnet() {
         if (e) (void)hipEventDestroy(e);
     if (temporal_ws) (void)hipFree(temporal_ws);
     if (bbox_ws) (void)hipFree(bbox_ws);
+    if (metric_ws) (void)hipFree(metric_ws);
     if (gru_fault) (void)hipHostFree(gru_fault);
     if (arena) (void)hipFree(arena);
 }

@@ -6,6 +6,7 @@
 //   grnet_render.cpp   the mesh overlay: the face table, grnet_render_meshes and its stage hooks; the render workspace
 //   grnet_skeleton.cpp the 3D skeleton view: grnet_render_segments and its two stage hooks, grnet_spin_joints
 //   grnet_bbox.cpp     boxes from 2D joints: grnet_bbox_from_joints2d, its 1-medoid hook and their scratch
+//   grnet_metrics.cpp  pose metrics: grnet_pose_metrics, the Procrustes hook and their scratch
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -253,6 +254,11 @@ struct grnet {
     void* bbox_ws = nullptr;
     size_t bbox_ws_bytes = 0;
 
+    // grnet_pose_metrics: the sequences' sums and counts (and the per-frame rows when the caller takes none), grown on demand, outside the arena
+    // (grnet_metrics.cpp)
+    void* metric_ws = nullptr;
+    size_t metric_ws_bytes = 0;
+
     // ------------------------------------------------------------------ the schedule, the tuning tables and the graph cache (grnet_run.cpp)
     std::vector<Op> ops_flat;   // the same ops placed on the lane streams by schedule_lanes(): the enqueue order
     std::vector<hipEvent_t> op_events_flat;
@@ -398,6 +404,7 @@ struct grnet {
     void faces_clear();
     int seg_stage_slot(void** slot, hipEvent_t* done);   // grnet_skeleton.cpp: the next table of the ring, free to be written
     int bbox_scratch(size_t bytes, char** out);   // grnet_bbox.cpp: bbox_ws of at least this size
+    int metric_scratch(size_t bytes, char** out); // grnet_metrics.cpp: metric_ws of at least this size
     int raster_workspace(const char* who);   // grnet_render.cpp: raster_ws, allocated at the first call of grnet_render_meshes(_ex) or grnet_render_segments
     const Op* nth_conv_op(int pos) const;
     int gru_fault_check();

@@ -332,6 +332,25 @@ hipError_t launch_medoid_argmin(const float* points, const MedoidBatch& b, int s
 // off / K are frame offsets into hgt; bbox (n_seq,4) float64 = [cx, cy, nw, nh]
 hipError_t launch_bbox_assemble(const double* hgt, const MedoidBatch& b, int seq0, int K, const float* centre, double* bbox, hipStream_t s);
 
+// Pose metrics: MPJPE, PA-MPJPE, PVE, acceleration and acceleration error (csrc/metric_kernels.hip, compiled without fma contraction) ----
+constexpr int kMetricMaxJoints = 64;   // joints per frame, selected joints and root joints: one wave lane each
+constexpr int kMetricBatch = 128;      // sequences per launch: their offsets travel as a kernel argument
+struct MetricBatch { int n; int off[kMetricBatch + 1]; };       // frame offsets of n sequences lying back to back, from the start of the call
+struct MetricJoints { int n_select, n_root; unsigned char select[kMetricMaxJoints], root[kMetricMaxJoints]; };   // indices into the J joints
+// per_frame (frames,5) float64 = [mpjpe, pa_mpjpe, pve, accel, accel_err] x unit: the joints launch writes columns 0, 1 and NaN into 3, 4 (and 2
+// without vertices), the vertices launch column 2, the acceleration launch columns 3, 4 of the interior frames; transform (frames,13) or NULL
+hipError_t launch_metric_joints(const float* pred, const float* gt, int J, int frames, const MetricJoints& mj, double unit, int has_verts, double* per_frame,
+                                double* transform, hipStream_t s);
+hipError_t launch_metric_accel(const float* pred, const float* gt, int J, const MetricBatch& b, const MetricJoints& mj, double unit, double* per_frame,
+                               hipStream_t s);
+hipError_t launch_metric_verts(const float* pred, const float* gt, int V, int frames, double unit, double* per_frame, hipStream_t s);
+// seq_sum / seq_cnt (n_seq,5): the sums and counts of the structurally defined entries of sequence seq0 + q; per_seq (n_seq,5) or NULL: their means
+hipError_t launch_metric_seq_means(const double* per_frame, const MetricBatch& b, int seq0, int has_verts, double* seq_sum, long long* seq_cnt,
+                                   double* per_seq, hipStream_t s);
+hipError_t launch_metric_total(const double* seq_sum, const long long* seq_cnt, int n_seq, double* total, hipStream_t s);
+// K (k,9) float64 -> R (k,9), sigma (k,3): procrustes3() of procrustes3.h, one thread per matrix
+hipError_t launch_procrustes(const double* K, int k, double* R, double* sigma, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

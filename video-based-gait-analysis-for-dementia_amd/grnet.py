@@ -922,6 +922,78 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_medoid")
         return index, cost
 
+    # ------------------------------------------------------------------ pose metrics
+    def _metric_input(self, x, what, width=None):
+        """A finite (n,width,3) float32 device tensor of `x` (numpy or torch)."""
+        t = torch.as_tensor(x)
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1 or (width is not None and t.shape[1] != width):
+            raise ValueError(f"{what} must be (n,{'J' if width is None else width},3) with n >= 1, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{what} has a non-finite entry")
+        return t.to(self.device, torch.float32).contiguous()
+
+    def pose_metrics(self, pred_joints, gt_joints, lengths=None, root=None, select=None, pred_verts=None, gt_verts=None, unit=1000.0,
+                     return_transform=False):
+        """MPJPE, PA-MPJPE, PVE, acceleration and acceleration error on the device (grnet_pose_metrics; the definitions: DESIGN 4.8).
+        pred_joints, gt_joints (n,J,3), J <= 64, one sequence or `lengths` of them lying back to back -- numpy or torch, taken as float32 and
+        widened to float64 on the device.  root: joint indices whose mean is subtracted per frame (H36M-14: [2, 3]; kinectv2: [0]; None:
+        nothing); select: the joint indices that enter the metrics (None: all); pred_verts, gt_verts (n,V,3): both or neither; unit multiplies
+        every metric (1000: metres -> millimetres).  Returns a dict of float64 device tensors: per_frame (n,5) = [mpjpe, pa_mpjpe, pve, accel,
+        accel_err] with NaN where an entry is undefined by structure (the accelerations at a sequence's ends, pve without vertices),
+        per_sequence (n_seq,5) and total (5,): the means over the defined entries; return_transform: also transform (n,13) = [s, R row-major,
+        t] of the Procrustes alignment, in the inputs' units.  Works before finalize(): no weight is read.  Nothing synchronises.  ValueError
+        on non-finite input."""
+        p = self._metric_input(pred_joints, "pred_joints")
+        g = self._metric_input(gt_joints, "gt_joints")
+        if p.shape != g.shape:
+            raise ValueError(f"pred_joints and gt_joints differ in shape: {tuple(p.shape)}, {tuple(g.shape)}")
+        if (pred_verts is None) != (gt_verts is None):
+            raise ValueError("pred_verts and gt_verts go together")
+        n, J = p.shape[:2]
+        pv = gv = None
+        V = 0
+        if pred_verts is not None:
+            pv = self._metric_input(pred_verts, "pred_verts")
+            gv = self._metric_input(gt_verts, "gt_verts")
+            if pv.shape != gv.shape or pv.shape[0] != n:
+                raise ValueError(f"pred_verts and gt_verts must both be ({n},V,3), got {tuple(pv.shape)} and {tuple(gv.shape)}")
+            V = pv.shape[1]
+        off = self._sequence_offsets(n, lengths, "pred_joints")
+        n_seq = len(off) - 1
+
+        def indices(v):                                       # int32 for the C ABI, which says which indices it takes
+            return np.ascontiguousarray(np.asarray(v, np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
+        sel_keep = None if select is None else indices(select)
+        root_keep = None if root is None or len(root) == 0 else indices(root)
+        i32p = C.POINTER(C.c_int32)
+        out = {"per_frame": torch.empty(n, 5, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 5, dtype=torch.float64, device=self.device),
+               "total": torch.empty(5, dtype=torch.float64, device=self.device)}
+        if return_transform:
+            out["transform"] = torch.empty(n, 13, dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_pose_metrics(self._h, p.data_ptr(), g.data_ptr(), J, off.ctypes.data_as(i32p), n_seq,
+                                          sel_keep.ctypes.data_as(i32p) if sel_keep is not None else None, 0 if sel_keep is None else sel_keep.shape[0],
+                                          root_keep.ctypes.data_as(i32p) if root_keep is not None else None, 0 if root_keep is None else root_keep.shape[0],
+                                          pv.data_ptr() if pv is not None else None, gv.data_ptr() if gv is not None else None, V, float(unit),
+                                          out["per_frame"].data_ptr(), out["per_sequence"].data_ptr(), out["total"].data_ptr(),
+                                          out["transform"].data_ptr() if return_transform else None, stream)
+        _lib.check(self._lib, self._h, rc, "grnet_pose_metrics")
+        return out
+
+    def op_procrustes(self, K):
+        """The Procrustes rotation alone (grnet_op_procrustes): K (k,3,3) or (3,3) float64 -> (R (k,3,3) the proper rotation that maximises
+        trace(R K), sigma (k,3) the singular values of K, descending) on the device."""
+        k = torch.as_tensor(K).to(self.device, torch.float64).reshape(-1, 9).contiguous()
+        if k.shape[0] < 1:
+            raise ValueError("K must hold at least one 3x3 matrix")
+        R = torch.empty(k.shape[0], 9, dtype=torch.float64, device=self.device)
+        sigma = torch.empty(k.shape[0], 3, dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_op_procrustes(self._h, k.data_ptr(), k.shape[0], R.data_ptr(), sigma.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_procrustes")
+        return R.reshape(-1, 3, 3), sigma
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

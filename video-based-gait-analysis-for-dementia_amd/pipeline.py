@@ -5,6 +5,7 @@ Reference counterparts:
   * demo model loop + result dict     demo.py:126-231  -> run_tracklet(), make_demo_result()
   * batch 3D-joint generation         batch_generation.py:289-371, 222-284 -> run_on_frames(), BatchDb
   * boxes from OpenPose 2D joints     batch_generation.py:39-93, 95-178 -> bbox_from_joints2d(), openpose_boxes()
+  * pose metrics (no counterpart)     DESIGN 4.8 -> pose_metrics()
   * crop-cam / crop-coords -> image   lib/utils/demo_utils.py:176-209
   * spin2 -> kinectv2 joints          lib/data_utils/kp_utils.py:26-36 with the tables :211-242, :904-931
   * crop + normalise of a frame       lib/dataset/inference.py:71-87, lib/data_utils/img_utils.py:252-285,355-363
@@ -596,6 +597,90 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080):
             k += 1
         boxes[vid_name] = chosen
     return boxes, bad
+
+
+def pose_metrics(pred_joints, gt_joints, lengths=None, root=None, select=None, pred_verts=None, gt_verts=None, unit=1000.0, return_transform=False):
+    """MPJPE, PA-MPJPE, PVE, acceleration and acceleration error in numpy float64 with np.linalg.svd: the host statement of
+    GRNet.pose_metrics, same arguments, a dict of numpy arrays.  The inputs are taken as float32 and widened, as the device takes them.
+    per_frame (n,5) = [mpjpe, pa_mpjpe, pve, accel, accel_err] times unit, NaN where undefined by structure; per_sequence (n_seq,5) and
+    total (5,): means over the defined entries (the total from the sequences' sums and counts); transform (n,13) = [s, R row-major, t]."""
+    def widened(x, what):
+        a = np.asarray(x)
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"{what} must be (n,J,3) with n >= 1, got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{what} has a non-finite entry")
+        return a.astype(np.float32).astype(np.float64)
+    p, g = widened(pred_joints, "pred_joints"), widened(gt_joints, "gt_joints")
+    if p.shape != g.shape:
+        raise ValueError(f"pred_joints and gt_joints differ in shape: {p.shape}, {g.shape}")
+    if (pred_verts is None) != (gt_verts is None):
+        raise ValueError("pred_verts and gt_verts go together")
+    n, J = p.shape[:2]
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    sel = np.arange(J) if select is None else np.asarray(select, np.int64).reshape(-1)
+    rt = np.zeros(0, np.int64) if root is None else np.asarray(root, np.int64).reshape(-1)
+    for idx, what in ((sel, "select"), (rt, "root")):
+        if idx.size > 64 or (what == "select" and idx.size < 1) or (idx.size and (idx.min() < 0 or idx.max() >= J)):
+            raise ValueError(f"{what} must hold at most 64 indices into the {J} joints")
+    if J > 64:
+        raise ValueError(f"J {J} > 64")
+    if not np.isfinite(unit):
+        raise ValueError("unit must be finite")
+    if rt.size:
+        p = p - p[:, rt].mean(axis=1, keepdims=True)
+        g = g - g[:, rt].mean(axis=1, keepdims=True)
+    P, G = p[:, sel], g[:, sel]
+    per_frame = np.full((n, 5), np.nan)
+    per_frame[:, 0] = np.linalg.norm(P - G, axis=2).mean(axis=1)
+    mu1, mu2 = P.mean(axis=1, keepdims=True), G.mean(axis=1, keepdims=True)
+    X1, X2 = P - mu1, G - mu2
+    var1 = (X1 ** 2).sum(axis=(1, 2))
+    K = np.einsum("nja,njb->nab", X1, X2)
+    U, S, Vt = np.linalg.svd(K)
+    d = np.sign(np.linalg.det(np.einsum("nab,nbc->nac", U, Vt)))
+    d[d == 0] = 1.0
+    Z = np.tile(np.eye(3), (n, 1, 1))
+    Z[:, 2, 2] = d
+    R = np.einsum("nba,nbc,ndc->nad", Vt, Z, U)                 # V Z U^T
+    degenerate = var1 == 0                                     # all selected pred joints equal: s = 0, R = I
+    R[degenerate] = np.eye(3)
+    s = np.where(degenerate, 0.0, np.einsum("nab,nba->n", R, K) / np.where(degenerate, 1.0, var1))
+    t = mu2[:, 0] - s[:, None] * np.einsum("nab,nb->na", R, mu1[:, 0])
+    aligned = s[:, None, None] * np.einsum("nab,njb->nja", R, P) + t[:, None, :]
+    per_frame[:, 1] = np.linalg.norm(aligned - G, axis=2).mean(axis=1)
+    if pred_verts is not None:
+        pv, gv = widened(pred_verts, "pred_verts"), widened(gt_verts, "gt_verts")
+        if pv.shape != gv.shape or pv.shape[0] != n:
+            raise ValueError(f"pred_verts and gt_verts must both be ({n},V,3), got {pv.shape} and {gv.shape}")
+        per_frame[:, 2] = np.linalg.norm(pv - gv, axis=2).mean(axis=1)
+    sums, counts = np.zeros((len(lengths), 5)), np.zeros((len(lengths), 5), np.int64)
+    a = 0
+    for q, T in enumerate(lengths):
+        if T >= 3:
+            acc = P[a:a + T - 2] - 2.0 * P[a + 1:a + T - 1] + P[a + 2:a + T]
+            E = P[a:a + T] - G[a:a + T]
+            err = E[:-2] - 2.0 * E[1:-1] + E[2:]
+            per_frame[a + 1:a + T - 1, 3] = np.linalg.norm(acc, axis=2).mean(axis=1)
+            per_frame[a + 1:a + T - 1, 4] = np.linalg.norm(err, axis=2).mean(axis=1)
+        a += T
+    per_frame *= float(unit)
+    a = 0
+    for q, T in enumerate(lengths):
+        rows = per_frame[a:a + T]
+        defined = ~np.isnan(rows)                              # NaN here is structural: the input is finite
+        counts[q] = defined.sum(axis=0)
+        sums[q] = np.where(defined, rows, 0.0).sum(axis=0)
+        a += T
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_seq = np.where(counts > 0, sums / np.maximum(counts, 1), np.nan)
+        total = np.where(counts.sum(axis=0) > 0, sums.sum(axis=0) / np.maximum(counts.sum(axis=0), 1), np.nan)
+    out = {"per_frame": per_frame, "per_sequence": per_seq, "total": total}
+    if return_transform:
+        out["transform"] = np.concatenate([s[:, None], R.reshape(n, 9), t], axis=1)
+    return out
 
 
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
