@@ -10,6 +10,10 @@ files (--openpose_folder: the reference's load_openpose_anno, batch_generation.p
 --gt_path FILE (opt-in) compares the joints with ground truth in this script's own output schema and reports MPJPE, PA-MPJPE, acceleration and
 acceleration error per video in millimetres (GRNet.pose_metrics on the device; the reference has no evaluation code).
 
+--trajectory (opt-in, with --openpose_folder and --vid_folder) fits the camera-space translation of every frame to the OpenPose 2D joints the
+boxes were made from (GRNet.fit_translation on the device, DESIGN 4.9: SPIN's weighted least squares, the reference's estimate_translation_np) and
+adds 'trans', 'trans_status' and 'reproj' to the database; the camera is an assumption, see --focal_length.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -32,6 +36,7 @@ ROOT = osp.dirname(osp.abspath(__file__))
 sys.path.insert(0, ROOT)
 PKG = "video-based-gait-analysis-for-dementia_amd"
 MIN_FDIFF = 10            # batch_generation.py:35
+IMG_W, IMG_H = 1920, 1080  # batch_generation.py:25-26: the frame the OpenPose joints are scaled to
 BBOX_SCALE = 1.1          # batch_generation.py:296 (Inference(scale=1.1))
 
 
@@ -49,17 +54,18 @@ def flush_windows(n_videos, max_vid):
     return [(a, b) for a, b in zip(cuts, cuts[1:]) if b > a]
 
 
-def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_factory=None):
+def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_factory=None, return_joints=False):
     """load_openpose_anno (batch_generation.py:95-178): {vid_name: (T,4) float64 boxes} from a folder of OpenPose .mat files, by
     pipeline.openpose_boxes -- on the GPU through a GRNet handle without weights (model_factory(local_rank) -> an object with
     bbox_from_joints2d: the seam of the CPU tests), or on the host (on_host).  The call is deterministic, so under several ranks every
-    rank computes the same boxes; rank 0 writes them to bbox_out with joblib.dump, and the bad files' names to bbox_out + '.bad'."""
+    rank computes the same boxes; rank 0 writes them to bbox_out with joblib.dump, and the bad files' names to bbox_out + '.bad'.
+    return_joints: (boxes, {vid_name: the (T,25,3) pixel joints of the candidate whose box won}) -- what --trajectory fits to."""
     pkg = importlib.import_module(PKG)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     model = None
     if not on_host:
         model = model_factory(local_rank) if model_factory is not None else pkg.GRNet(max_frames=1, device_id=local_rank)
-    boxes, bad = pkg.pipeline.openpose_boxes(openpose_folder, model=model)
+    boxes, bad, joints2d = pkg.pipeline.openpose_boxes(openpose_folder, model=model, img_w=IMG_W, img_h=IMG_H, return_joints=True)
     if model is not None and hasattr(model, "close"):
         model.close()
     if bbox_out and int(os.environ.get("RANK", "0")) == 0:
@@ -67,7 +73,7 @@ def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_fac
         joblib.dump(boxes, bbox_out)
         joblib.dump(bad, bbox_out + ".bad")
         print(f"Save {len(boxes)} boxes to {bbox_out} ({len(bad)} files without usable 2D joints: {bbox_out}.bad).")
-    return boxes
+    return (boxes, joints2d) if return_joints else boxes
 
 
 def load_ground_truth(gt_path):
@@ -141,10 +147,59 @@ class WindowMetrics:
         return path
 
 
+class WindowTrajectory:
+    """--trajectory: one fit_translation call per database window on rank 0, one sequence per video, on the kinectv2 joints the gather left on the
+    device and the window's OpenPose joints, uploaded once (model.fit_translation; on_host, or a model without the method:
+    pipeline.fit_translation after a download).  The pairs are pipeline.BODY25_FROM_KINECTV2, the centre the middle of the IMG_W x IMG_H frame, the
+    focal length an assumption (--focal_length).  A video whose frame count differs from its OpenPose length has no detections to pair with its
+    frames -- its boxes were repeated for the same reason -- and gets NaN rows with status 1."""
+
+    def __init__(self, joints2d, pipe, model, on_host, focal_length=None):
+        self.joints2d, self.pipe = joints2d, pipe
+        self.device_call = None if on_host or not hasattr(model, "fit_translation") else model.fit_translation
+        self.focal_length = float(focal_length) if focal_length else float(np.hypot(IMG_W, IMG_H))
+        self.centre = (IMG_W / 2.0, IMG_H / 2.0)
+
+    def add_window(self, keys, per_video):
+        """keys[vi], per_video[vi] (T,75) -> per video (trans (T,3) float32, trans_status (T,) uint8, reproj (T,) float32)."""
+        import torch
+        rows = [None] * len(keys)
+        j3, j2, lengths, which = [], [], [], []
+        for vi, key in enumerate(keys):
+            frames = int(per_video[vi].shape[0])
+            found = self.joints2d.get(key)
+            if found is None or found.shape[0] != frames:
+                print(f"Trajectory: skip video {key}, {frames} frames here and {'no' if found is None else found.shape[0]} frames of 2D joints.")
+                rows[vi] = (np.full((frames, 3), np.nan, np.float32), np.full(frames, self.pipe.TRANS_TOO_FEW, np.uint8), np.full(frames, np.nan, np.float32))
+                continue
+            j3.append(per_video[vi].reshape(frames, 25, 3))
+            j2.append(np.asarray(found, np.float32))
+            lengths.append(frames)
+            which.append(vi)
+        if not which:
+            return rows
+        j3, j2 = torch.cat(j3, 0), np.concatenate(j2, 0)
+        kw = dict(lengths=lengths, focal_length=self.focal_length, centre=self.centre)
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, j2, self.pipe.BODY25_FROM_KINECTV2, **kw).items()}
+        else:
+            out = self.pipe.fit_translation(j3.cpu().numpy(), j2, self.pipe.BODY25_FROM_KINECTV2, **kw)
+        a = 0
+        for vi, T, seq in zip(which, lengths, out["per_sequence"]):
+            r = out["per_frame"][a:a + T]
+            rows[vi] = (r[:, :3].astype(np.float32), r[:, 5].astype(np.uint8), r[:, 3].astype(np.float32))
+            mean = "none" if np.isnan(seq[2]) else f"{seq[2]:.2f} px"
+            print(f"Trajectory: video {keys[vi]}, {int(seq[0])} frames fitted, {int(seq[1])} filled, mean reprojection error {mean}, path length {seq[3]:.3f} m.")
+            a += T
+        return rows
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False):
-    """gt_path: also compare the joints with that ground truth (WindowMetrics) and write metrics_out (default: outpath with _metrics.json).
+                 metrics_on_host=False, trajectory=None):
+    """trajectory: {'joints2d': {vid_name: (T,25,3) pixel joints}, 'focal_length': F or None, 'on_host': bool} -- also fit the camera-space
+    translation of every frame (WindowTrajectory) and add 'trans' (N,3) float32, 'trans_status' (N,) uint8 and 'reproj' (N,) float32 to the database.
+    gt_path: also compare the joints with that ground truth (WindowMetrics) and write metrics_out (default: outpath with _metrics.json).
     annos: the boxes themselves ({vid_name: (T,4)}, boxes_from_openpose) instead of the joblib file fv.
     model_factory(local_rank) -> model and backend="gloo" are the seam of the CPU tests (tests/test_host_cpu.py): the window / plan /
     run / gather / flush logic below then runs under two gloo ranks with a stand-in model and tensors on the CPU.
@@ -194,6 +249,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         comm = harness.RcclComm(world, rank, dev, dist=dist)
     db = pipe.BatchDb(outpath) if rank == 0 else None
     metrics = WindowMetrics(load_ground_truth(gt_path), pipe, model, metrics_on_host) if gt_path and rank == 0 else None
+    traj = WindowTrajectory(trajectory["joints2d"], pipe, model, trajectory.get("on_host", False), trajectory.get("focal_length")) \
+        if trajectory is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -225,12 +282,14 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         per_video = harness.gather_work_items(items, local, 75, world, rank, dist, dev, comm=comm)
         if metrics is not None:
             metrics.add_window([v[0] for v in vids], per_video)
+        fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
         if rank == 0:
             for vi, (key, _, bboxes) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
                 # appends the very array the dataset modified)
                 bboxes[:, 2:] *= BBOX_SCALE
-                db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3))
+                extra = dict(zip(("trans", "trans_status", "reproj"), fitted[vi])) if fitted is not None else {}
+                db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
                 print(f"Save database to {db.flush()}.")
@@ -262,6 +321,13 @@ def main(argv=None):
                    "PA-MPJPE, acceleration and acceleration error per video against it (millimetres); a video it lacks, or of another length, is skipped")
     p.add_argument("--metrics_out", type=str, default="", help="with --gt_path: the JSON file of the metrics (default: --outpath with _metrics.json)")
     p.add_argument("--metrics_on_host", action="store_true", help="with --gt_path: the numpy float64 statement of the metrics instead of the GPU kernels")
+    p.add_argument("--trajectory", action="store_true", help="with --openpose_folder and --vid_folder: fit the camera-space translation of every frame to the 2D joints "
+                   "of the person the box was made from and add 'trans' (N,3), 'trans_status' (N,) (0 fitted, 1 too few joints, 2 degenerate, 3 filled) and "
+                   "'reproj' (N,) pixels to the database; one line per video")
+    p.add_argument("--focal_length", type=float, default=0.0, help="with --trajectory: the focal length in pixels.  The data carries no calibration: the default "
+                   f"sqrt({IMG_W}^2 + {IMG_H}^2) (a 53 degree diagonal field of view) and the centre ({IMG_W // 2}, {IMG_H // 2}) are ASSUMPTIONS, and depth "
+                   "scales with the focal length")
+    p.add_argument("--trajectory_on_host", action="store_true", help="with --trajectory: the numpy float64 statement of the fit instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -278,14 +344,27 @@ def main(argv=None):
         sys.exit("batch_generation.py: --bbox_out and --bbox_on_host belong to --openpose_folder, which was not given")
     if (a.metrics_out or a.metrics_on_host) and not a.gt_path:
         sys.exit("batch_generation.py: --metrics_out and --metrics_on_host belong to --gt_path, which was not given")
+    if (a.focal_length or a.trajectory_on_host) and not a.trajectory:
+        sys.exit("batch_generation.py: --focal_length and --trajectory_on_host belong to --trajectory, which was not given")
+    if a.trajectory and a.bbox_path:
+        sys.exit("batch_generation.py: --trajectory fits to the 2D joints of --openpose_folder; --bbox_path carries none")
+    if a.trajectory and not (a.openpose_folder and a.vid_folder):
+        sys.exit("batch_generation.py: --trajectory needs --openpose_folder (the 2D joints) and --vid_folder (the frames)")
+    if a.trajectory and not (np.isfinite(a.focal_length) and a.focal_length >= 0):
+        sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
-    annos = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host) if a.openpose_folder else None
+    annos = trajectory = None
+    if a.trajectory:
+        annos, joints2d = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host, return_joints=True)
+        trajectory = {"joints2d": joints2d, "focal_length": a.focal_length or None, "on_host": a.trajectory_on_host}
+    elif a.openpose_folder:
+        annos = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host)
     if a.openpose_folder and not a.vid_folder:
         return
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
-                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host)
+                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory)
 
 
 if __name__ == "__main__":

@@ -524,6 +524,33 @@ int grnet_pose_metrics(grnet_t* h, const float* pred_dev, const float* gt_dev, i
                        void* stream);
 int grnet_op_procrustes(grnet_t* h, const double* K_dev, int k, double* R_dev, double* sigma_dev, void* stream);
 
+/* ---- camera-space trajectory: the translation fitted to 2D joints (csrc/translation_kernels.hip, csrc/translation3.h) -------------
+ * estimate_translation_np -- lib/utils/geometry.py:296-337 (SPIN's weighted least squares), per frame, with per-sequence intrinsics, a status,
+ * the reprojection error, a fill of the unfitted frames and a per-sequence summary, none of which the reference has.
+ * joints3d_dev float32 (frames, K3, 3) and joints2d_dev float32 (frames, K2, 3) = (x, y, confidence) in pixels: n_seq sequences lying back to back;
+ * frame_offsets_host: n_seq + 1 frame offsets, the first 0, the last `frames`.  pairs_host (n_pairs, 2) int32 = (3D joint, 2D joint);
+ * camera_host (n_seq, 3) float64 = (f, cx, cy) of each sequence.  Every input is widened to float64 and all arithmetic is float64.
+ *   fit     a pair is used where its confidence is finite and > conf_threshold, with weight w = confidence.  u = x - cx, v = y - cy, ex = u Z - f X,
+ *           ey = v Z - f Y; A = [[f^2 Sw, 0, -f Swu], [0, f^2 Sw, -f Swv], [-f Swu, -f Swv, Sw(u^2 + v^2)]], b = [f Sw ex, f Sw ey, -Sw(u ex + v ey)],
+ *           the sums over the used pairs in table order; A t = b by elimination with partial pivoting
+ *   reproj  the weighted mean over the used pairs of |f (X + tx, Y + ty) / (Z + tz) + (cx, cy) - (x, y)|, pixels
+ *   status  0 fitted; 1 fewer than min_joints used pairs; 2 a zero pivot, a non-finite result or a used joint with Z + tz <= 0 (the reference raises
+ *           LinAlgError or returns garbage); 3 filled.  t and reproj are NaN for 1 and 2
+ *   fill    (fill != 0) a run of unfitted frames between two fitted ones takes numpy.linspace(prev, next, gap + 2)[1:-1] bit for bit; a run before
+ *           the first or after the last fitted frame holds the nearest fitted t; a sequence without a fitted frame stays as it is.  Filled frames get
+ *           status 3 and keep a NaN reproj
+ * per_frame_dev (frames, 6) float64 = [tx, ty, tz, reproj, n_used, status]; per_seq_dev (n_seq, 4) float64 = [frames fitted, frames filled, mean
+ * reproj over the fitted frames (NaN without one), path length sum |(J_root + t)[i+1] - (J_root + t)[i]| over consecutive frames whose t are both
+ * finite]; root: a 3D joint index.  Fixed summation orders, no atomics: a frame's fit has the same bits whatever the call, a sequence's rows and
+ * summary the same bits whether it travels alone or with others.  Non-finite coordinates need no check: they end in status 2.  Needs no weights:
+ * works on a handle straight from grnet_create.  No host synchronisation and no allocation: everything is enqueued on `stream`.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer, K3 or K2 < 1, n_pairs outside [1, 64], a pair index
+ * outside K3 or K2, n_seq or frames < 1, frame_offsets[0] != 0, an empty sequence or offsets that do not ascend or do not end at `frames`, a
+ * non-finite or non-positive f, a non-finite centre, a non-finite or negative conf_threshold, min_joints < 2, root outside [0, K3). */
+int grnet_fit_translation(grnet_t* h, const float* joints3d_dev, int K3, const float* joints2d_dev, int K2, int frames, const int32_t* frame_offsets_host,
+                          int n_seq, const int32_t* pairs_host, int n_pairs, const double* camera_host, double conf_threshold, int min_joints, int root,
+                          int fill, double* per_frame_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

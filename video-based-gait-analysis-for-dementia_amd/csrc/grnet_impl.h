@@ -7,6 +7,7 @@
 //   grnet_skeleton.cpp the 3D skeleton view: grnet_render_segments and its two stage hooks, grnet_spin_joints
 //   grnet_bbox.cpp     boxes from 2D joints: grnet_bbox_from_joints2d, its 1-medoid hook and their scratch
 //   grnet_metrics.cpp  pose metrics: grnet_pose_metrics, the Procrustes hook and their scratch
+//   grnet_translation.cpp  the camera-space trajectory: grnet_fit_translation
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

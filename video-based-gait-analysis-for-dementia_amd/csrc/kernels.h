@@ -351,6 +351,20 @@ hipError_t launch_metric_total(const double* seq_sum, const long long* seq_cnt, 
 // K (k,9) float64 -> R (k,9), sigma (k,3): procrustes3() of procrustes3.h, one thread per matrix
 hipError_t launch_procrustes(const double* K, int k, double* R, double* sigma, hipStream_t s);
 
+// Camera-space trajectory: the translation fitted to 2D joints per frame, filled and summed up per sequence (csrc/translation_kernels.hip, compiled
+// without fma contraction; the arithmetic: csrc/translation3.h) ----
+constexpr int kTransMaxPairs = 64;     // (3D joint, 2D joint) pairs of the table
+constexpr int kTransBatch = 64;        // sequences per launch: their offsets and intrinsics travel as a kernel argument
+struct TransPairs { int n; int p3[kTransMaxPairs], p2[kTransMaxPairs]; };
+struct TransBatch { int n; int off[kTransBatch + 1]; double cam[kTransBatch][3]; };      // frame offsets from the start of the call; (f, cx, cy) per sequence
+// per_frame (frames,6) float64 = [tx, ty, tz, reproj_px, n_used, status]: one lane per frame
+hipError_t launch_translation_fit(const float* joints3d, const float* joints2d, int K3, int K2, const TransPairs& pairs, const TransBatch& b, double threshold,
+                                  int min_joints, double* per_frame, hipStream_t s);
+// one workgroup per sequence: fills the unfitted rows of per_frame (fill != 0) and writes per_seq (n_seq,4) = [fitted, filled, mean reproj, path length]
+// of sequence seq0 + q
+hipError_t launch_translation_seq(const float* joints3d, int K3, int root, const TransBatch& b, int seq0, int fill, double* per_frame, double* per_seq,
+                                  hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -994,6 +994,49 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_procrustes")
         return R.reshape(-1, 3, 3), sigma
 
+    # ------------------------------------------------------------------ the camera-space trajectory
+    def fit_translation(self, joints3d, joints2d, pairs, lengths=None, focal_length=5000.0, centre=(112.0, 112.0), conf_threshold=0.1, min_joints=4,
+                        root=0, fill=True):
+        """The translation that makes the 3D joints project onto the 2D detections, per frame, on the device (grnet_fit_translation: SPIN's
+        weighted least squares, the reference's estimate_translation_np; the rules: DESIGN 4.9).  joints3d (n,K3,3) and joints2d (n,K2,3) =
+        (x, y, confidence) in pixels, one sequence or `lengths` of them lying back to back -- numpy or torch, taken as float32 and widened to
+        float64 on the device; pairs (P,2), P <= 64, of (3D index, 2D index); focal_length: one number or one per sequence; centre: (cx, cy) or
+        (n_seq,2).  Returns a dict of float64 device tensors: per_frame (n,6) = [tx, ty, tz, reproj_px, n_used, status] with status 0 fitted,
+        1 fewer than min_joints pairs above conf_threshold, 2 degenerate (t and reproj NaN for 1 and 2), 3 filled (fill: linear between fitted
+        frames, the nearest fitted t outside them); per_sequence (n_seq,4) = [fitted, filled, mean reproj, path length of joint `root`].
+        Non-finite values are not refused: a dead confidence drops the pair, anything else ends in status 2.  Works before finalize(): no
+        weight is read.  Nothing synchronises."""
+        def joints(x, what):
+            t = torch.as_tensor(x)
+            if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"{what} must be (n,K,3) with n, K >= 1, got {tuple(t.shape)}")
+            return t.to(self.device, torch.float32).contiguous()
+        j3, j2 = joints(joints3d, "joints3d"), joints(joints2d, "joints2d")
+        n = j3.shape[0]
+        if j2.shape[0] != n:
+            raise ValueError(f"joints3d has {n} frames and joints2d {j2.shape[0]}")
+        off = self._sequence_offsets(n, lengths, "joints3d")
+        n_seq = len(off) - 1
+        table = np.asarray(pairs, np.int64)
+        if table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError(f"pairs must be (P,2) of (3D index, 2D index), got {table.shape}")
+        table = np.ascontiguousarray(table.clip(-1, 2**31 - 1), dtype=np.int32)       # which indices and how many the device takes is the C ABI's to say
+        cam = np.empty((n_seq, 3), np.float64)
+        try:
+            cam[:, 0] = np.asarray(focal_length, np.float64)
+            cam[:, 1:] = np.asarray(centre, np.float64)
+        except ValueError:
+            raise ValueError(f"focal_length must be one number or {n_seq} of them, centre (cx, cy) or ({n_seq},2)") from None
+        out = {"per_frame": torch.empty(n, 6, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, dtype=torch.float64, device=self.device)}
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_fit_translation(self._h, j3.data_ptr(), j3.shape[1], j2.data_ptr(), j2.shape[1], n, off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq,
+                                             table.ctypes.data_as(C.POINTER(C.c_int32)), table.shape[0], cam.ctypes.data_as(C.POINTER(C.c_double)),
+                                             float(conf_threshold), int(min_joints), int(root), int(bool(fill)), out["per_frame"].data_ptr(),
+                                             out["per_sequence"].data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_fit_translation")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

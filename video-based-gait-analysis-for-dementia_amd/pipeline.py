@@ -545,7 +545,7 @@ def bbox_from_joints2d(kp_2d, threshold=0.1):
     return np.repeat(np.array([c_xy[0], c_xy[1], nh, nh], np.float64)[None, :], T, axis=0)
 
 
-def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080):
+def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joints=False):
     """load_openpose_anno of batch_generation.py:95-178 without its vis branches: one box per OpenPose .mat file of anno_folder ->
     (boxes {vid_name: (T,4) float64, or None where no candidate's box has a positive size}, bad [file names]).  Every rule is the
     reference's as written: files are 'A<action>_...' and the interaction actions 44-48 are skipped; 'skeleton' is (P,T,25,3), normalised;
@@ -555,7 +555,9 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080):
     equal ones.  np.bool (:126) no longer exists in numpy: it is bool here.  Files are visited in sorted order (the reference: os.listdir
     order), and a 'skeleton' of another dtype is widened to float64 first.
     model=None: pipeline.bbox_from_joints2d per candidate.  With a GRNet, EVERY candidate of every file goes into ONE
-    model.bbox_from_joints2d call and the choice runs on the returned boxes."""
+    model.bbox_from_joints2d call and the choice runs on the returned boxes.
+    return_joints: a third value, {vid_name: the scaled (T,25,3) float64 joints (x, y in pixels, score) of the candidate whose box won, or None}
+    -- what fit_translation needs beside the 3D joints."""
     import scipy.io as sio
     assert osp.isdir(anno_folder), anno_folder
     boxes, bad, cands = {}, [], []                             # cands: (vid_name, [scaled (T,25,3) candidates])
@@ -589,13 +591,17 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080):
     else:
         rows = list(model.bbox_from_joints2d(np.concatenate(flat, 0), lengths=[j.shape[0] for j in flat]).cpu().numpy())
     k = 0
+    winners = {}
     for vid_name, js in cands:
-        area, chosen = 0, None
+        area, chosen, winner = 0, None, None
         for j in js:
             if rows[k][2] > area:
-                area, chosen = rows[k][2], np.repeat(rows[k][None, :], j.shape[0], axis=0)
+                area, chosen, winner = rows[k][2], np.repeat(rows[k][None, :], j.shape[0], axis=0), j
             k += 1
         boxes[vid_name] = chosen
+        winners[vid_name] = winner
+    if return_joints:
+        return boxes, bad, winners
     return boxes, bad
 
 
@@ -683,6 +689,128 @@ def pose_metrics(pred_joints, gt_joints, lengths=None, root=None, select=None, p
     return out
 
 
+# ----------------------------------------------------------------------------- the camera-space trajectory
+# (kinectv2 index, BODY_25 index) of the joints both lists of kp_utils.py name alike; Thorax / Neck and the feet are defined differently and left out
+BODY25_FROM_KINECTV2 = ((0, 8), (4, 5), (5, 6), (6, 7), (8, 2), (9, 3), (10, 4), (12, 12), (13, 13), (14, 14), (16, 9), (17, 10), (18, 11))
+TRANS_FITTED, TRANS_TOO_FEW, TRANS_DEGENERATE, TRANS_FILLED = 0, 1, 2, 3
+
+
+def _solve3(A, b):
+    """x of the 3x3 system A x = b by elimination with partial pivoting (the first of equal pivots), one float64 rounding per operation; None at a
+    zero or NaN pivot."""
+    A, b = [[float(v) for v in row] for row in A], [float(v) for v in b]
+    for k in range(3):
+        p, best = k, abs(A[k][k])
+        for r in range(k + 1, 3):
+            if abs(A[r][k]) > best:
+                p, best = r, abs(A[r][k])
+        if not best > 0.0:
+            return None
+        A[k], A[p], b[k], b[p] = A[p], A[k], b[p], b[k]
+        for r in range(k + 1, 3):
+            m = A[r][k] / A[k][k]
+            for c in range(k + 1, 3):
+                A[r][c] = A[r][c] - m * A[k][c]
+            b[r] = b[r] - m * b[k]
+    x2 = b[2] / A[2][2]
+    x1 = (b[1] - A[1][2] * x2) / A[1][1]
+    x0 = ((b[0] - A[0][1] * x1) - A[0][2] * x2) / A[0][0]
+    return x0, x1, x2
+
+
+def fit_translation(joints3d, joints2d, pairs, lengths=None, focal_length=5000.0, centre=(112.0, 112.0), conf_threshold=0.1, min_joints=4, root=0, fill=True):
+    """estimate_translation_np (lib/utils/geometry.py:296-337) per frame in numpy float64 with the statuses, the fill and the summary of DESIGN 4.9:
+    the host statement of GRNet.fit_translation, same arguments, a dict of numpy arrays.  The inputs are taken as float32 and widened, as the device
+    takes them.  per_frame (n,6) = [tx, ty, tz, reproj_px, n_used, status], per_sequence (n_seq,4) = [fitted, filled, mean reproj, path length]."""
+    def widened(x, what):
+        a = np.asarray(x)
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"{what} must be (n,K,3) with n, K >= 1, got {a.shape}")
+        return a.astype(np.float32).astype(np.float64)
+    j3, j2 = widened(joints3d, "joints3d"), widened(joints2d, "joints2d")
+    n = j3.shape[0]
+    if j2.shape[0] != n:
+        raise ValueError(f"joints3d has {n} frames and joints2d {j2.shape[0]}")
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    table = np.asarray(pairs, np.int64)
+    if table.ndim != 2 or table.shape[1] != 2 or not 1 <= table.shape[0] <= 64:
+        raise ValueError(f"pairs must be (P,2) of (3D index, 2D index) with 1 <= P <= 64, got {table.shape}")
+    if table.min() < 0 or table[:, 0].max() >= j3.shape[1] or table[:, 1].max() >= j2.shape[1]:
+        raise ValueError(f"a pair index lies outside the {j3.shape[1]} 3D joints or the {j2.shape[1]} 2D joints")
+    n_seq = len(lengths)
+    cam = np.empty((n_seq, 3), np.float64)
+    try:
+        cam[:, 0] = np.asarray(focal_length, np.float64)
+        cam[:, 1:] = np.asarray(centre, np.float64)
+    except ValueError:
+        raise ValueError(f"focal_length must be one number or {n_seq} of them, centre (cx, cy) or ({n_seq},2)") from None
+    if not np.isfinite(cam).all() or (cam[:, 0] <= 0).any():
+        raise ValueError("focal_length must be finite and positive, centre finite")
+    if not np.isfinite(conf_threshold) or conf_threshold < 0:
+        raise ValueError("conf_threshold must be finite and not negative")
+    if min_joints < 2:
+        raise ValueError(f"min_joints {min_joints} < 2")
+    if not 0 <= root < j3.shape[1]:
+        raise ValueError(f"root {root} outside the {j3.shape[1]} 3D joints")
+    per_frame = np.full((n, 6), np.nan)
+    per_seq = np.zeros((n_seq, 4))
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            f, cx, cy = (float(v) for v in cam[q])
+            rows = per_frame[a:a + T]
+            for i in range(T):
+                S, D = j3[a + i, table[:, 0]], j2[a + i, table[:, 1]]
+                used = np.flatnonzero((D[:, 2] > conf_threshold) & np.isfinite(D[:, 2]))
+                rows[i, 4], rows[i, 5] = used.size, TRANS_TOO_FEW
+                if used.size < min_joints:
+                    continue
+                rows[i, 5] = TRANS_DEGENERATE
+                sw = swu = swv = swr = sbx = sby = sbz = 0.0
+                for j in used:                                   # table order, one rounding per operation
+                    X, Y, Z, w = float(S[j, 0]), float(S[j, 1]), float(S[j, 2]), float(D[j, 2])
+                    u, v = float(D[j, 0]) - cx, float(D[j, 1]) - cy
+                    ex, ey = u * Z - f * X, v * Z - f * Y
+                    sw, swu, swv, swr = sw + w, swu + w * u, swv + w * v, swr + w * (u * u + v * v)
+                    sbx, sby, sbz = sbx + w * ex, sby + w * ey, sbz + w * (u * ex + v * ey)
+                d0, ax, ay = (f * f) * sw, -(f * swu), -(f * swv)
+                t = _solve3([[d0, 0.0, ax], [0.0, d0, ay], [ax, ay, swr]], [f * sbx, f * sby, -sbz])
+                if t is None or not np.isfinite(t).all():
+                    continue
+                depth = S[used, 2] + t[2]
+                if not (depth > 0).all():
+                    continue
+                px = ((f * (S[used, 0] + t[0])) / depth + cx) - D[used, 0]
+                py = ((f * (S[used, 1] + t[1])) / depth + cy) - D[used, 1]
+                acc = 0.0
+                for e in D[used, 2] * np.sqrt(px * px + py * py):
+                    acc = acc + float(e)
+                if not np.isfinite(acc / sw):
+                    continue
+                rows[i] = (t[0], t[1], t[2], acc / sw, used.size, TRANS_FITTED)
+            fitted = np.flatnonzero(rows[:, 5] == TRANS_FITTED)
+            if fill and fitted.size:
+                todo = rows[:, 5] != TRANS_FITTED
+                rows[:fitted[0], :3], rows[fitted[-1] + 1:, :3] = rows[fitted[0], :3], rows[fitted[-1], :3]
+                for lo, hi in zip(fitted[:-1], fitted[1:]):
+                    if hi - lo > 1:
+                        rows[lo + 1:hi, :3] = np.linspace(rows[lo, :3], rows[hi, :3], hi - lo + 1)[1:-1]
+                rows[todo, 3], rows[todo, 5] = np.nan, TRANS_FILLED
+            pos = j3[a:a + T, root] + rows[:, :3]
+            steps = np.sqrt((np.diff(pos, axis=0) ** 2).sum(axis=1))
+            path = 0.0
+            for s in steps[np.isfinite(steps)]:                  # a step is finite exactly where both t are
+                path = path + float(s)
+            acc = 0.0
+            for e in rows[fitted, 3]:
+                acc = acc + float(e)
+            per_seq[q] = (fitted.size, (rows[:, 5] == TRANS_FILLED).sum(), acc / fitted.size if fitted.size else np.nan, path)
+            a += T
+    return {"per_frame": per_frame, "per_sequence": per_seq}
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
@@ -713,18 +841,24 @@ class BatchDb:
             raise AssertionError("outpath must end with .json (batch_generation.py:236)")
         self.outpath, self.out_ind, self.db, self.written = outpath, 0, defaultdict(list), []
 
-    def add(self, vid_name, bboxes, joints3d):
+    def add(self, vid_name, bboxes, joints3d, **extra):
+        """extra: further per-frame arrays of n rows (batch_generation.py --trajectory: trans, trans_status, reproj), every video or none."""
         n = bboxes.shape[0]
         self.db["vid_name"].extend([vid_name] * n)
         self.db["bbox"].append(np.asarray(bboxes).reshape(n, 4))
         self.db["joints3D"].append(np.asarray(joints3d).reshape(n, 25, 3))
+        for name, rows in extra.items():
+            assert np.asarray(rows).shape[0] == n, (name, np.asarray(rows).shape, n)
+            self.db[name].append(np.asarray(rows))
 
     def flush(self):
         import joblib
         if not len(self.db):
             return None
-        db = {k: (np.concatenate(v, 0).astype(np.float32) if isinstance(v[0], np.ndarray) else np.array(v))
-              for k, v in self.db.items()}
+        def stacked(v):                                        # floats as float32, as the reference stores them; integer columns keep their type
+            a = np.concatenate(v, 0)
+            return a if a.dtype.kind in "iu" else a.astype(np.float32)
+        db = {k: (stacked(v) if isinstance(v[0], np.ndarray) else np.array(v)) for k, v in self.db.items()}
         outfp = self.outpath[:-5] + f"_{self.out_ind}.json"
         joblib.dump(db, outfp)
         self.written.append(outfp)
