@@ -99,7 +99,8 @@ def _q(t):
 # float64 mode: the teacher-forced stage tests of the fp32 path (tests/test_gpu_f32_stages.py) compare ONE launch with a reference on the
 # launch's own fp32 input; computed in float64, the reference's own rounding stays far below the kernels' (~1e-7 against 1e-6 .. 1e-5 of a
 # tensor's scale).  Under float64(): conv2d, batchnorm, conv_bn, basic_block, bottleneck, hr_fuse, upsample_nearest, upsample_bilinear2x,
-# keypoint_attention and head_tail take float32 inputs and return float64; geometry and SMPL stay float32.  Outside it nothing changes.
+# keypoint_attention, head_tail, rot6d_to_rotmat, project, smpl_lbs and smpl_joints29 take float32 inputs and return float64; the quaternion /
+# axis-angle geometry stays float32.  Outside it nothing changes.
 # The temporal modules follow the same rule (tests/test_gpu_temporal_stages.py): layer_normalization, _softmax, _gelu, multi_attention, joint_wise_ffn,
 # ts_attn_block, gru_direction, _mlp, gru_forward, gait_cparams and feat_corrector return float64 under float64(); each is then the composition of the
 # per-launch stage functions at the end of this file (ts_stage_* / gru_stage_* / fc_stage_*: one function per GPU launch, float64 output from that launch's
@@ -308,14 +309,14 @@ def head_tail(plf, csf, sd, p="head."):
 # ----------------------------------------------------------------------------- geometry
 def rot6d_to_rotmat(x):
     """geometry.py:395-410.  x (...,6) viewed (3,2): a1 = elements 0,2,4; a2 = 1,3,5."""
-    x = np.asarray(x, np.float32).reshape(-1, 3, 2)
+    x = np.asarray(x, _dt()).reshape(-1, 3, 2)
     a1, a2 = x[:, :, 0], x[:, :, 1]
     b1 = a1 / np.maximum(np.linalg.norm(a1, axis=1, keepdims=True), 1e-6)
     d = (b1 * a2).sum(1, keepdims=True)
     u = a2 - d * b1
     b2 = u / np.maximum(np.linalg.norm(u, axis=1, keepdims=True), 1e-6)
     b3 = np.cross(b1, b2)
-    return np.stack([b1, b2, b3], -1).astype(np.float32)                    # columns b1 b2 b3
+    return np.stack([b1, b2, b3], -1).astype(_dt())                         # columns b1 b2 b3
 
 
 def rotmat_to_quat(R, eps=1e-6):
@@ -366,13 +367,14 @@ def rotmat_to_aa(R):
 def project(joints, cam):
     """convert_weak_perspective_to_perspective + perspective_projection + /112
     (geometry.py:427-479, smpl.py:172-186)."""
-    joints = np.asarray(joints, np.float32)
-    cam = np.asarray(cam, np.float32)
+    dt = _dt()
+    joints = np.asarray(joints, dt)
+    cam = np.asarray(cam, dt)
     t = np.stack([cam[:, 1], cam[:, 2],
-                  np.float32(2 * FOCAL) / (np.float32(IMG_RES) * cam[:, 0] + np.float32(1e-9))], -1)
+                  dt(2 * FOCAL) / (dt(IMG_RES) * cam[:, 0] + dt(1e-9))], -1)
     p = joints + t[:, None, :]
     p = p / p[:, :, 2:3]
-    return (np.float32(FOCAL) * p[:, :, :2] / np.float32(IMG_RES / 2.0)).astype(np.float32)
+    return (dt(FOCAL) * p[:, :, :2] / dt(IMG_RES / 2.0)).astype(dt)
 
 
 # ----------------------------------------------------------------------------- SMPL
@@ -381,25 +383,30 @@ def smpl_lbs(betas, rotmat, smpl):
 
     Per-frame, per-joint loops (a deliberately different formulation from the batched one the
     golden generator's stand-in uses).  Returns verts (N,6890,3), posed joints (N,24,3).
+    The kinematic tree is smpl["parents"] where the tables carry one, the SMPL tree otherwise.  Under float64() the fp32 inputs
+    and tables are widened and everything is computed and returned in float64.
     """
-    betas = np.asarray(betas, np.float32)
-    R = np.asarray(rotmat, np.float32).reshape(-1, 24, 3, 3)
-    vt, sdirs, pdirs = smpl["v_template"], smpl["shapedirs"], smpl["posedirs"]
-    Jr, W = smpl["J_regressor"], smpl["lbs_weights"]
+    dt = _dt()
+    betas = np.asarray(betas, dt)
+    R = np.asarray(rotmat, dt).reshape(-1, 24, 3, 3)
+    wide = (lambda a: np.asarray(a, np.float64)) if _F64 else (lambda a: a)
+    vt, sdirs, pdirs = wide(smpl["v_template"]), wide(smpl["shapedirs"]), wide(smpl["posedirs"])
+    Jr, W = wide(smpl["J_regressor"]), wide(smpl["lbs_weights"])
+    parents = [int(p) for p in smpl["parents"]] if "parents" in smpl else PARENTS
     N = betas.shape[0]
-    verts = np.empty((N, vt.shape[0], 3), np.float32)
-    joints = np.empty((N, 24, 3), np.float32)
+    verts = np.empty((N, vt.shape[0], 3), dt)
+    joints = np.empty((N, 24, 3), dt)
     for n in range(N):
         v_shaped = vt + sdirs @ betas[n]                                   # (V,3)
         J = Jr @ v_shaped                                                   # (24,3)
-        pose_feat = (R[n, 1:] - np.eye(3, dtype=np.float32)).reshape(207)
+        pose_feat = (R[n, 1:] - np.eye(3, dtype=dt)).reshape(207)
         v_posed = v_shaped + (pose_feat @ pdirs).reshape(-1, 3)
-        G = np.zeros((24, 4, 4), np.float32)
+        G = np.zeros((24, 4, 4), dt)
         for i in range(24):
-            T = np.eye(4, dtype=np.float32)
+            T = np.eye(4, dtype=dt)
             T[:3, :3] = R[n, i]
-            T[:3, 3] = J[i] - (J[PARENTS[i]] if i > 0 else 0)
-            G[i] = T if i == 0 else G[PARENTS[i]] @ T
+            T[:3, 3] = J[i] - (J[parents[i]] if i > 0 else 0)
+            G[i] = T if i == 0 else G[parents[i]] @ T
         joints[n] = G[:, :3, 3]
         A = G.copy()
         for i in range(24):
@@ -412,8 +419,8 @@ def smpl_lbs(betas, rotmat, smpl):
 def smpl_joints29(verts, joints24, smpl):
     """The reference wrapper's 29 'spin2' joints (smpl.py:113-118)."""
     j45 = np.concatenate([joints24, verts[:, EXTRA_VERT_IDS]], 1)
-    extra = np.einsum("jv,nvk->njk", smpl["J_regressor_extra"], verts)
-    return np.concatenate([j45[:, :24], j45[:, [35, 37]], j45[:, [40, 42]], extra[:, 5:6]], 1).astype(np.float32)
+    extra = np.einsum("jv,nvk->njk", np.asarray(smpl["J_regressor_extra"], np.float64) if _F64 else smpl["J_regressor_extra"], verts)
+    return np.concatenate([j45[:, :24], j45[:, [35, 37]], j45[:, [40, 42]], extra[:, 5:6]], 1).astype(_dt())
 
 
 # ----------------------------------------------------------------------------- whole path
