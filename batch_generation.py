@@ -14,6 +14,11 @@ acceleration error per video in millimetres (GRNet.pose_metrics on the device, D
 boxes were made from (GRNet.fit_translation on the device, DESIGN 4.9: SPIN's weighted least squares, the reference's estimate_translation_np) and
 adds 'trans', 'trans_status' and 'reproj' to the database; the camera is an assumption, see --focal_length.
 
+--bbox_track (opt-in, with --openpose_folder) makes one box PER FRAME for the chosen person of each video instead of the one fixed box, as the
+reference's Inference(joints2d=...) does (lib/utils/smooth_bbox.py; GRNet.track_boxes on the device): the gaps without a detection
+are interpolated, the frames before the first and after the last detection are dropped, --bbox_smooth adds the median and the Gaussian, and the
+database gains 'bbox_status'.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -54,26 +59,61 @@ def flush_windows(n_videos, max_vid):
     return [(a, b) for a, b in zip(cuts, cuts[1:]) if b > a]
 
 
-def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_factory=None, return_joints=False):
+def boxes_from_openpose(openpose_folder, bbox_out=None, on_host=False, model_factory=None, return_joints=False, track=None):
     """load_openpose_anno (batch_generation.py:95-178): {vid_name: (T,4) float64 boxes} from a folder of OpenPose .mat files, by
     pipeline.openpose_boxes -- on the GPU through a GRNet handle without weights (model_factory(local_rank) -> an object with
     bbox_from_joints2d: the seam of the CPU tests), or on the host (on_host).  The call is deterministic, so under several ranks every
     rank computes the same boxes; rank 0 writes them to bbox_out with joblib.dump, and the bad files' names to bbox_out + '.bad'.
-    return_joints: (boxes, {vid_name: the (T,25,3) pixel joints of the candidate whose box won}) -- what --trajectory fits to."""
+    return_joints: (boxes, {vid_name: the (T,25,3) pixel joints of the candidate whose box won}) -- what --trajectory fits to.
+    track: {'kernel_size', 'sigma', 'pad'} -- --bbox_track: per-frame boxes of the frames [start, end) of each video (pipeline.openpose_boxes
+    with track=; model.track_boxes, or pipeline.track_boxes with on_host), and a further last value, the tracks {vid_name: {'range', 'frames',
+    'status'}} that prepare_data wants.  A video without any detection is dropped with one line (and keeps a None there); a frame inside a track whose smoothed scale is
+    not positive (status 3: the zero padding of scipy's median near the ends of a track) stops the script."""
     pkg = importlib.import_module(PKG)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     model = None
     if not on_host:
         model = model_factory(local_rank) if model_factory is not None else pkg.GRNet(max_frames=1, device_id=local_rank)
-    boxes, bad, joints2d = pkg.pipeline.openpose_boxes(openpose_folder, model=model, img_w=IMG_W, img_h=IMG_H, return_joints=True)
+    found = pkg.pipeline.openpose_boxes(openpose_folder, model=model, img_w=IMG_W, img_h=IMG_H, return_joints=True, **({} if track is None else {"track": track}))
+    boxes, bad, joints2d = found[:3]
     if model is not None and hasattr(model, "close"):
         model.close()
+    tracks = None
+    if track is not None:
+        tracks = found[3]
+        for key in sorted(tracks):
+            if tracks[key] is None:
+                if int(os.environ.get("RANK", "0")) == 0:
+                    print(f"Track: skip video {key}, no frame of its 2D joints has a detection.")
+                del boxes[key], joints2d[key]                   # tracks[key] stays None: prepare_data has nothing more to say about it
+            elif (tracks[key]["status"] == pkg.pipeline.TRACK_BAD_SCALE).any():
+                start = tracks[key]["range"][0]
+                at = [int(i) + start for i in np.flatnonzero(tracks[key]["status"] == pkg.pipeline.TRACK_BAD_SCALE)]
+                sys.exit(f"batch_generation.py: video {key}: the smoothed box scale of {len(at)} frame(s) (the first: {at[0]}) is not positive -- near the ends of a "
+                         "track more than half of the median's window is zero padding (scipy's, the reference's own result); try --bbox_pad edge")
     if bbox_out and int(os.environ.get("RANK", "0")) == 0:
         import joblib
         joblib.dump(boxes, bbox_out)
         joblib.dump(bad, bbox_out + ".bad")
         print(f"Save {len(boxes)} boxes to {bbox_out} ({len(bad)} files without usable 2D joints: {bbox_out}.bad).")
+    if track is not None:
+        return (boxes, joints2d, tracks) if return_joints else (boxes, tracks)
     return (boxes, joints2d) if return_joints else boxes
+
+
+def align_track(bboxes, status, start, end, T, n_files):
+    """--bbox_track where a video has n_files extracted frames and its 2D joints T (within MIN_FDIFF): the fixed-box rule -- repeat box 0 -- would
+    throw the track away.  Fewer files: the track is truncated to the frames that exist.  More files, and the track reaches the last frame of
+    the 2D joints: the last box is held over the further frames (status 1).  Returns (bboxes, status, stop): the frames [start, stop)."""
+    stop = end
+    if n_files < end:
+        stop = max(n_files, start)
+        bboxes, status = bboxes[:stop - start], status[:stop - start]
+    elif n_files > T and end == T:
+        stop = n_files
+        bboxes = np.concatenate([bboxes, np.repeat(bboxes[-1:], n_files - T, axis=0)], 0)
+        status = np.concatenate([status, np.ones(n_files - T, status.dtype)], 0)
+    return bboxes, status, stop
 
 
 def load_ground_truth(gt_path):
@@ -196,8 +236,11 @@ class WindowTrajectory:
 
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None):
-    """trajectory: {'joints2d': {vid_name: (T,25,3) pixel joints}, 'focal_length': F or None, 'on_host': bool} -- also fit the camera-space
+                 metrics_on_host=False, trajectory=None, tracks=None):
+    """tracks: {vid_name: {'range': (start, end), 'frames': T, 'status': (end - start,) uint8}} of boxes_from_openpose(track=...) -- annos holds one
+    box per frame of [start, end) of each video: only those frames are generated, the 2D joints of `trajectory` are taken as sliced alike, and the
+    database gains 'bbox_status' (N,) uint8 (0 detected, 1 interpolated or held).
+    trajectory: {'joints2d': {vid_name: (T,25,3) pixel joints}, 'focal_length': F or None, 'on_host': bool} -- also fit the camera-space
     translation of every frame (WindowTrajectory) and add 'trans' (N,3) float32, 'trans_status' (N,) uint8 and 'reproj' (N,) float32 to the database.
     gt_path: also compare the joints with that ground truth (WindowMetrics) and write metrics_out (default: outpath with _metrics.json).
     annos: the boxes themselves ({vid_name: (T,4)}, boxes_from_openpose) instead of the joblib file fv.
@@ -258,16 +301,33 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         for vid_name in vidnames[wa:wb]:
             key = vid_name.split(".")[0]
             if key not in annos:
-                if rank == 0:
+                if rank == 0 and not (tracks is not None and key in tracks and tracks[key] is None):
                     print(f"Skip video {vid_name}, no precomputed 2D joints!")
                 continue
             img_dir = osp.join(vid_folder, vid_name)
             files = sorted(x for x in os.listdir(img_dir) if x.endswith(("png", "jpg", "npy")))
             bboxes = np.array(annos[key])                      # a copy in the annotation's own dtype
-            assert abs(len(files) - bboxes.shape[0]) < MIN_FDIFF
-            if len(files) != bboxes.shape[0]:                  # align frame number (batch_generation.py:258-261)
-                bboxes = np.repeat(bboxes[0, None, :], len(files), axis=0)
-            vids.append((key, img_dir, bboxes))
+            first, status = 0, None
+            if tracks is not None and tracks.get(key) is not None:
+                (first, end), T, status = tracks[key]["range"], tracks[key]["frames"], tracks[key]["status"]
+                assert abs(len(files) - T) < MIN_FDIFF
+                if len(files) != T:
+                    bboxes, status, stop = align_track(bboxes, status, first, end, T, len(files))
+                    if rank == 0:
+                        print(f"Track: video {key} has {len(files)} frames and {T} frames of 2D joints: the track [{first}, {end}) is "
+                              f"{'held' if stop > end else 'cut'} to [{first}, {stop}).")
+                    if traj is not None:                        # the 2D joints alike; a held frame has no detection to fit to (score 0: filled)
+                        j2 = traj.joints2d[key][:stop - first]
+                        traj.joints2d[key] = np.concatenate([j2, np.zeros((stop - first - j2.shape[0],) + j2.shape[1:], j2.dtype)], 0)
+                    if stop <= first:
+                        if rank == 0:
+                            print(f"Skip video {vid_name}, its track begins behind its last frame!")
+                        continue
+            else:
+                assert abs(len(files) - bboxes.shape[0]) < MIN_FDIFF
+                if len(files) != bboxes.shape[0]:              # align frame number (batch_generation.py:258-261)
+                    bboxes = np.repeat(bboxes[0, None, :], len(files), axis=0)
+            vids.append((key, img_dir, bboxes, first, status))
         items = harness.plan_work_items([v[2].shape[0] for v in vids], world, chunk)
         mine = []
         for vi, lo, hi, r in items:
@@ -276,7 +336,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             # run_on_frames scales the boxes it is given by 1.1 in place (as Inference.__init__ does, inference.py:48):
             # hand it a copy of the UNSCALED rows; the database rows are scaled once below, on every rank alike
             # the joints stay on the device: no host synchronisation per work item, one all-gather per window
-            kp = pipe.run_on_frames(model, vids[vi][1], np.arange(lo, hi), vids[vi][2][lo:hi].copy(), device=dev, batch_size=chunk, on_device=True)["kp_3d"]
+            kp = pipe.run_on_frames(model, vids[vi][1], np.arange(lo, hi) + vids[vi][3], vids[vi][2][lo:hi].copy(), device=dev, batch_size=chunk, on_device=True)["kp_3d"]
             mine.append(kp.reshape(hi - lo, 75))
         local = torch.cat(mine, 0) if mine else torch.zeros(0, 75, device=dev)
         per_video = harness.gather_work_items(items, local, 75, world, rank, dist, dev, comm=comm)
@@ -284,11 +344,13 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             metrics.add_window([v[0] for v in vids], per_video)
         fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
         if rank == 0:
-            for vi, (key, _, bboxes) in enumerate(vids):
+            for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
                 # appends the very array the dataset modified)
                 bboxes[:, 2:] *= BBOX_SCALE
                 extra = dict(zip(("trans", "trans_status", "reproj"), fitted[vi])) if fitted is not None else {}
+                if status is not None:
+                    extra["bbox_status"] = status
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -317,6 +379,14 @@ def main(argv=None):
                    "(the reference's load_openpose_anno) instead of read from --bbox_path; without --vid_folder the script writes --bbox_out and exits")
     p.add_argument("--bbox_out", type=str, default="", help="with --openpose_folder: joblib file that receives the boxes (the files without usable joints: FILE.bad)")
     p.add_argument("--bbox_on_host", action="store_true", help="with --openpose_folder: the numpy float64 statement of the box instead of the GPU kernels")
+    p.add_argument("--bbox_track", action="store_true", help="with --openpose_folder: one box PER FRAME for the chosen person of each video instead of the one fixed "
+                   "box (the reference's lib/utils/smooth_bbox.py, as its Inference(joints2d=...) uses it): gaps without a detection are interpolated, frames before "
+                   "the first and after the last detection are dropped, the database gains 'bbox_status' (N,) (0 detected, 1 interpolated)")
+    p.add_argument("--bbox_smooth", action="store_true", help="with --bbox_track: the median and the Gaussian of smooth_bbox_params over the track")
+    p.add_argument("--bbox_kernel", type=int, default=None, help="with --bbox_smooth: the median's window, odd, 1 to 31 (default 11)")
+    p.add_argument("--bbox_sigma", type=float, default=None, help="with --bbox_smooth: the Gaussian's sigma in frames, 0 (none) to 16 (default 3)")
+    p.add_argument("--bbox_pad", choices=("zero", "edge"), default=None, help="with --bbox_smooth: what the median's window holds outside the track: zeros (scipy's "
+                   "medfilt, the reference; the first and last frames of a track then lose their box and the script stops) or the first / last value (default zero)")
     p.add_argument("--gt_path", type=str, default="", help="joblib database in this script's output schema ('vid_name' (F,), 'joints3D' (F,25,3) kinectv2): report MPJPE, "
                    "PA-MPJPE, acceleration and acceleration error per video against it (millimetres); a video it lacks, or of another length, is skipped")
     p.add_argument("--metrics_out", type=str, default="", help="with --gt_path: the JSON file of the metrics (default: --outpath with _metrics.json)")
@@ -342,6 +412,16 @@ def main(argv=None):
         sys.exit("batch_generation.py: --bbox_path and --openpose_folder both name the source of the boxes: give one of them")
     if (a.bbox_out or a.bbox_on_host) and not a.openpose_folder:
         sys.exit("batch_generation.py: --bbox_out and --bbox_on_host belong to --openpose_folder, which was not given")
+    if (a.bbox_track or a.bbox_smooth) and not a.openpose_folder:
+        sys.exit("batch_generation.py: --bbox_track and --bbox_smooth belong to --openpose_folder, which was not given")
+    if a.bbox_smooth and not a.bbox_track:
+        sys.exit("batch_generation.py: --bbox_smooth belongs to --bbox_track, which was not given")
+    if (a.bbox_kernel is not None or a.bbox_sigma is not None or a.bbox_pad is not None) and not a.bbox_smooth:
+        sys.exit("batch_generation.py: --bbox_kernel, --bbox_sigma and --bbox_pad belong to --bbox_smooth, which was not given")
+    if a.bbox_kernel is not None and not (1 <= a.bbox_kernel <= 31 and a.bbox_kernel % 2 == 1):
+        sys.exit("batch_generation.py: --bbox_kernel must be odd and within 1 to 31")
+    if a.bbox_sigma is not None and not (np.isfinite(a.bbox_sigma) and 0 <= a.bbox_sigma <= 16):
+        sys.exit("batch_generation.py: --bbox_sigma must be within 0 to 16")
     if (a.metrics_out or a.metrics_on_host) and not a.gt_path:
         sys.exit("batch_generation.py: --metrics_out and --metrics_on_host belong to --gt_path, which was not given")
     if (a.focal_length or a.trajectory_on_host) and not a.trajectory:
@@ -354,17 +434,22 @@ def main(argv=None):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
-    annos = trajectory = None
+    annos = trajectory = tracks = None
+    track = None
+    if a.bbox_track:
+        track = {"kernel_size": 11 if a.bbox_kernel is None else a.bbox_kernel, "sigma": 3.0 if a.bbox_sigma is None else a.bbox_sigma,
+                 "pad": a.bbox_pad or "zero"} if a.bbox_smooth else {}
+    if a.openpose_folder:
+        found = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host, return_joints=True, track=track)
+        annos, joints2d = found[:2]
+        tracks = found[2] if track is not None else None
     if a.trajectory:
-        annos, joints2d = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host, return_joints=True)
         trajectory = {"joints2d": joints2d, "focal_length": a.focal_length or None, "on_host": a.trajectory_on_host}
-    elif a.openpose_folder:
-        annos = boxes_from_openpose(a.openpose_folder, a.bbox_out, on_host=a.bbox_on_host)
     if a.openpose_folder and not a.vid_folder:
         return
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
-                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory)
+                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks)
 
 
 if __name__ == "__main__":

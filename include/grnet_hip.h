@@ -551,6 +551,42 @@ int grnet_fit_translation(grnet_t* h, const float* joints3d_dev, int K3, const f
                           int n_seq, const int32_t* pairs_host, int n_pairs, const double* camera_host, double conf_threshold, int min_joints, int root,
                           int fill, double* per_frame_dev, double* per_seq_dev, void* stream);
 
+/* ---- per-frame boxes from 2D joints: tracked, gaps filled, smoothed (csrc/track_kernels.hip, csrc/track_boxes.h) -----------------
+ * lib/utils/smooth_bbox.py (kp_to_bbox_param squared=True, get_all_bbox_params, smooth_bbox_params) and the box of lib/dataset/inference.py:57-66.
+ * joints_dev float64 (sum T, K, 3) rows (x, y, score) in pixels: n_seq sequences lying back to back; frame_offsets_host: n_seq + 1 frame offsets,
+ * the first 0.  1 <= K <= 64, 1 <= n_seq <= 8192.  Everything is float64, one rounding per operation.
+ *   frame    a joint counts where score > vis_thresh, strictly; min and max of x and of y over those joints, height = sqrt(dx^2 + dy^2); the frame
+ *            has a detection where a joint counts and height >= 0.5; then centre = (min + max) / 2, scale = 150 / height.  Non-finite joints are
+ *            not refused: every test is a comparison that is false for NaN, so a frame whose min, max or height is not finite has no detection
+ *   fill     start = the first detected frame, end = the last + 1; a frame between them without a detection takes, per column,
+ *            numpy.linspace(prev, next, gap + 2)[1:-1] of the detected frames on either side, bit for bit (the statement of grnet_fit_translation's
+ *            fill); the neighbours are found in a bitmask of 64 frames a word, by word
+ *   median   (kernel_size > 1; odd, <= 31) scipy.signal.medfilt over [start, end) of each column: the window padded with zeros (pad =
+ *            GRNET_TRACK_PAD_ZERO, scipy's) or with the first / last value (GRNET_TRACK_PAD_EDGE); by selection, so exact
+ *   gauss    (sigma > 0; <= 16) scipy.ndimage.gaussian_filter1d with its defaults: radius r = int(4 sigma + 0.5), weights exp(-0.5 x^2 / sigma^2)
+ *            over their sum (made on the host once a call), mode reflect with period 2 (end - start) however short the track; the centre term
+ *            first, then the pairs (x[l - i] + x[l + i]) w[i] from i = r down to 1 (scipy's own order)
+ *   box      [cx, cy, 150 / scale, 150 / scale]
+ * With kernel_size = 1 and sigma = 0 the call is get_all_bbox_params alone.
+ * boxes_dev (sum T, 4) float64; status_dev (sum T) int32: 0 detected, 1 interpolated, 2 outside [start, end) (box all zeros, as
+ * get_smooth_bbox_params pads), 3 inside, but the smoothed scale is not a positive finite number (box all zeros) -- with GRNET_TRACK_PAD_ZERO that
+ * is the reference's own result near the ends of a track, where more than half of the median's window is padding and the median is 0;
+ * range_dev (n_seq, 2) int32 = [start, end), [-1, 0) for a sequence without a detection, as the reference returns.
+ * No window, fill or reflection crosses a sequence; fixed orders, no atomics: a sequence's rows have the same bits whether it travels alone or with
+ * others.  Needs no weights: works on a handle straight from grnet_create.  Two launches behind one small copy from pinned memory, whatever n_seq
+ * and T; no host synchronisation; the scratch is the box calls' (grown on demand, outside the arena).
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): K or n_seq out of range, a null pointer, frame_offsets[0] != 0,
+ * offsets that do not increase, an even kernel_size or one outside [1, 31], a negative, non-finite or too large sigma, a non-finite vis_thresh,
+ * an unknown pad.
+ * grnet_op_median1d / grnet_op_gauss1d: one stage alone (test hooks) on x_dev float64, n_seq columns lying back to back with their n_seq + 1
+ * offsets, into out_dev (not x_dev); sigma > 0. */
+#define GRNET_TRACK_PAD_ZERO 0
+#define GRNET_TRACK_PAD_EDGE 1
+int grnet_track_boxes(grnet_t* h, const double* joints_dev, int K, const int32_t* frame_offsets_host, int n_seq, double vis_thresh, int kernel_size,
+                      double sigma, int pad, double* boxes_dev, int32_t* status_dev, int32_t* range_dev, void* stream);
+int grnet_op_median1d(grnet_t* h, const double* x_dev, const int32_t* offsets_host, int n_seq, int kernel_size, int pad, double* out_dev, void* stream);
+int grnet_op_gauss1d(grnet_t* h, const double* x_dev, const int32_t* offsets_host, int n_seq, double sigma, double* out_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -8,6 +8,7 @@
 //   grnet_bbox.cpp     boxes from 2D joints: grnet_bbox_from_joints2d, its 1-medoid hook and their scratch
 //   grnet_metrics.cpp  pose metrics: grnet_pose_metrics, the Procrustes hook and their scratch
 //   grnet_translation.cpp  the camera-space trajectory: grnet_fit_translation
+//   grnet_track.cpp    per-frame boxes from 2D joints: grnet_track_boxes and its two stage hooks
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

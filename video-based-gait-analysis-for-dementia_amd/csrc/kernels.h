@@ -365,6 +365,25 @@ hipError_t launch_translation_fit(const float* joints3d, const float* joints2d, 
 hipError_t launch_translation_seq(const float* joints3d, int K3, int root, const TransBatch& b, int seq0, int fill, double* per_frame, double* per_seq,
                                   hipStream_t s);
 
+// Per-frame boxes from 2D joints: tracked, gaps filled, smoothed (csrc/track_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/track_boxes.h) ----
+constexpr int kTrackMaxJoints = 64;        // joints per frame
+constexpr int kTrackMaxKernel = 31;        // the median's window, odd
+constexpr double kTrackMaxSigma = 16.;     // the Gaussian's width: radius int(4 sigma + 0.5) <= 64, 129 weights
+constexpr int kTrackMaxRadius = 64;
+constexpr int kTrackMaxSeqs = 8192;        // sequences per call: their offsets and the weights travel through one pinned table
+constexpr int kTrackThreads = 1024;        // threads of the sequence kernel's workgroup
+constexpr int kTrackLdsFrames = 1024;      // frames of [start, end) whose median and Gaussian run in LDS (two buffers of three columns)
+// params (frames,3) = [cx, cy, scale] of the detected frames (the others stay as they are); words: bit f & 63 of word f >> 6 = frame f detected,
+// 4 * ceil(frames / 256) words
+hipError_t launch_track_frames(const double* joints, int K, int frames, double vis_thresh, double* params, unsigned long long* words, hipStream_t s);
+// one workgroup per sequence; off: n_seq + 1 frame offsets ON THE DEVICE; weights[0 .. radius] (radius < 0: no Gaussian), ksize 1: no median;
+// work (frames,6); boxes (frames,4), status (frames), range (n_seq,2)
+hipError_t launch_track_sequences(const int* off, int n_seq, const double* weights, int radius, int ksize, int pad, const double* params,
+                                  const unsigned long long* words, double* work, double* boxes, int* status, int* range, hipStream_t s);
+// the median (radius < 0) or the Gaussian alone on x, per sequence, into out (not x)
+hipError_t launch_track_filter(const int* off, int n_seq, const double* x, const double* weights, int radius, int ksize, int pad, double* out, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1037,6 +1037,55 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_fit_translation")
         return out
 
+    # ------------------------------------------------------------------ per-frame boxes from 2D joints
+    def track_boxes(self, joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0, pad="zero"):
+        """One box per frame from 2D joints on the device (grnet_track_boxes: the reference's lib/utils/smooth_bbox.py and the box of
+        lib/dataset/inference.py:57-66; the rules: DESIGN 4.10).  joints2d (T,K,3) rows (x, y, score) in pixels, or (sum T,K,3) with the sequences'
+        `lengths` -- numpy or torch, taken as float64; a joint counts where score > vis_thresh.  kernel_size (odd, 1 .. 31; 1: none) and sigma
+        (0: none, else <= 16) are the median and the Gaussian of smooth_bbox_params (the reference: 11 and 3 or 8); pad "zero" (scipy's) or
+        "edge".  Returns a dict of device tensors: boxes (n,4) float64 [cx, cy, h, h]; status (n,) int32 -- 0 detected, 1 interpolated,
+        2 outside [start, end), 3 inside but without a positive finite smoothed scale (2 and 3: a box of zeros); range (n_seq,2) int32
+        [start, end), [-1, 0) without any detection.  Non-finite joints are not refused: their frame counts as undetected.  Works before
+        finalize(): no weight is read.  Nothing synchronises."""
+        j = torch.as_tensor(joints2d)
+        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
+            raise ValueError(f"joints2d must be (T,K,3) with T >= 1, got {tuple(j.shape)}")
+        if pad not in _lib.TRACK_PAD:
+            raise ValueError(f"pad must be 'zero' or 'edge', got {pad!r}")
+        j = j.to(self.device, torch.float64).contiguous()
+        n = j.shape[0]
+        off = self._sequence_offsets(n, lengths, "joints2d")
+        n_seq = len(off) - 1
+        out = {"boxes": torch.empty(n, 4, dtype=torch.float64, device=self.device), "status": torch.empty(n, dtype=torch.int32, device=self.device),
+               "range": torch.empty(n_seq, 2, dtype=torch.int32, device=self.device)}
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_track_boxes(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, float(vis_thresh), int(kernel_size),
+                                         float(sigma), _lib.TRACK_PAD[pad], out["boxes"].data_ptr(), out["status"].data_ptr(), out["range"].data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_track_boxes")
+        return out
+
+    def _op_filter1d(self, x, lengths):
+        x = torch.as_tensor(x).to(self.device, torch.float64).contiguous()
+        if x.dim() != 1 or x.shape[0] < 1:
+            raise ValueError(f"x must be (n,) with n >= 1, got {tuple(x.shape)}")
+        off = self._sequence_offsets(x.shape[0], lengths, "x")
+        return x, off, torch.empty_like(x), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def op_median1d(self, x, lengths=None, kernel_size=11, pad="zero"):
+        """The median of track_boxes alone (grnet_op_median1d): x (n,) float64, one column or `lengths` of them lying back to back -> (n,) on the device."""
+        x, off, out, stream = self._op_filter1d(x, lengths)
+        rc = self._lib.grnet_op_median1d(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, int(kernel_size), _lib.TRACK_PAD[pad],
+                                         out.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_median1d")
+        return out
+
+    def op_gauss1d(self, x, lengths=None, sigma=3.0):
+        """The Gaussian of track_boxes alone (grnet_op_gauss1d): x (n,) float64, one column or `lengths` of them lying back to back -> (n,) on the device."""
+        x, off, out, stream = self._op_filter1d(x, lengths)
+        rc = self._lib.grnet_op_gauss1d(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, float(sigma), out.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_gauss1d")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

@@ -545,7 +545,7 @@ def bbox_from_joints2d(kp_2d, threshold=0.1):
     return np.repeat(np.array([c_xy[0], c_xy[1], nh, nh], np.float64)[None, :], T, axis=0)
 
 
-def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joints=False):
+def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joints=False, track=None):
     """load_openpose_anno of batch_generation.py:95-178 without its vis branches: one box per OpenPose .mat file of anno_folder ->
     (boxes {vid_name: (T,4) float64, or None where no candidate's box has a positive size}, bad [file names]).  Every rule is the
     reference's as written: files are 'A<action>_...' and the interaction actions 44-48 are skipped; 'skeleton' is (P,T,25,3), normalised;
@@ -557,7 +557,13 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joint
     model=None: pipeline.bbox_from_joints2d per candidate.  With a GRNet, EVERY candidate of every file goes into ONE
     model.bbox_from_joints2d call and the choice runs on the returned boxes.
     return_joints: a third value, {vid_name: the scaled (T,25,3) float64 joints (x, y in pixels, score) of the candidate whose box won, or None}
-    -- what fit_translation needs beside the 3D joints."""
+    -- what fit_translation needs beside the 3D joints.
+    track: {'kernel_size', 'sigma', 'pad', 'vis_thresh'} (each optional: 1, 0, 'zero', 0.3) -- per-frame boxes instead of the one fixed box
+    (DESIGN 4.10).  The person is chosen exactly as above, by the fixed box; then the winners of ALL files go into ONE track_boxes call
+    (model.track_boxes, or pipeline.track_boxes with model=None) and a video keeps the frames [start, end) from its first to its last
+    detection, as the reference's Inference does (lib/dataset/inference.py:64-66): boxes[vid_name] is (end - start, 4), the returned joints
+    are sliced the same way, and a further last value {vid_name: {'range': (start, end), 'frames': T, 'status': (end - start,) uint8}} says
+    which frames they were.  A video without any detection has None for all three."""
     import scipy.io as sio
     assert osp.isdir(anno_folder), anno_folder
     boxes, bad, cands = {}, [], []                             # cands: (vid_name, [scaled (T,25,3) candidates])
@@ -600,9 +606,32 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joint
             k += 1
         boxes[vid_name] = chosen
         winners[vid_name] = winner
-    if return_joints:
-        return boxes, bad, winners
-    return boxes, bad
+    tracks = {}
+    if track is not None:
+        names = [v for v, _ in cands if winners[v] is not None]
+        for v, _ in cands:
+            if winners[v] is None:
+                boxes[v], tracks[v] = None, None
+        if names:
+            kw = dict(lengths=[winners[v].shape[0] for v in names], vis_thresh=track.get("vis_thresh", 0.3), kernel_size=track.get("kernel_size", 1),
+                      sigma=track.get("sigma", 0.0), pad=track.get("pad", "zero"))
+            joints = np.concatenate([winners[v] for v in names], 0)
+            if model is None:
+                out = track_boxes(joints, **kw)
+            else:
+                out = {k: t.cpu().numpy() for k, t in model.track_boxes(joints, **kw).items()}
+            a = 0
+            for v, (start, end) in zip(names, out["range"]):
+                T = winners[v].shape[0]
+                if start < 0:
+                    boxes[v] = winners[v] = tracks[v] = None
+                else:
+                    boxes[v] = out["boxes"][a + start:a + end].copy()
+                    tracks[v] = {"range": (int(start), int(end)), "frames": T, "status": out["status"][a + start:a + end].astype(np.uint8)}
+                    winners[v] = winners[v][start:end]
+                a += T
+    result = (boxes, bad) + ((winners,) if return_joints else ()) + ((tracks,) if track is not None else ())
+    return result
 
 
 def pose_metrics(pred_joints, gt_joints, lengths=None, root=None, select=None, pred_verts=None, gt_verts=None, unit=1000.0, return_transform=False):
@@ -809,6 +838,125 @@ def fit_translation(joints3d, joints2d, pairs, lengths=None, focal_length=5000.0
             per_seq[q] = (fitted.size, (rows[:, 5] == TRANS_FILLED).sum(), acc / fitted.size if fitted.size else np.nan, path)
             a += T
     return {"per_frame": per_frame, "per_sequence": per_seq}
+
+
+# ----------------------------------------------------------------------------- per-frame boxes from 2D joints
+TRACK_DETECTED, TRACK_INTERPOLATED, TRACK_OUTSIDE, TRACK_BAD_SCALE = 0, 1, 2, 3
+TRACK_MIN_HEIGHT, TRACK_PERSON_PIXELS = 0.5, 150.0             # lib/utils/smooth_bbox.py:60,64
+
+
+def track_reflect(j, n):
+    """Index into [0, n) of position j of scipy.ndimage's mode 'reflect' (d c b a | a b c d | d c b a): period 2n, any integer j (arrays too)."""
+    m = np.mod(j, 2 * n)
+    return np.where(m < n, m, 2 * n - 1 - m)
+
+
+def median_filter1d(x, kernel_size=11, pad="zero"):
+    """scipy.signal.medfilt(x, kernel_size) of a float64 column by sorting every window; pad 'zero' (scipy's) or 'edge' (the first / last value)."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or x.size < 1:
+        raise ValueError(f"x must be (n,) with n >= 1, got {x.shape}")
+    if kernel_size < 1 or kernel_size > 31 or kernel_size % 2 == 0:
+        raise ValueError(f"kernel_size {kernel_size} must be odd and within [1, 31]")
+    if pad not in ("zero", "edge"):
+        raise ValueError(f"pad must be 'zero' or 'edge', got {pad!r}")
+    half = kernel_size // 2
+    ext = np.pad(x, half, mode="constant" if pad == "zero" else "edge")
+    windows = np.lib.stride_tricks.sliding_window_view(ext, kernel_size)
+    return np.sort(windows, axis=1)[:, half].copy()
+
+
+def gauss_weights(sigma):
+    """The 2r + 1 weights of scipy.ndimage.gaussian_filter1d(sigma) with its defaults (order 0, truncate 4): r = int(4 sigma + 0.5)."""
+    r = int(4.0 * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return phi / phi.sum()
+
+
+def gauss_filter1d(x, sigma=3.0):
+    """scipy.ndimage.gaussian_filter1d(x, sigma) of a float64 column: np.dot of the weights against the reflected extension, however short x is."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or x.size < 1:
+        raise ValueError(f"x must be (n,) with n >= 1, got {x.shape}")
+    if not np.isfinite(sigma) or not 0 < sigma <= 16:
+        raise ValueError("sigma must be within (0, 16]")
+    w = gauss_weights(sigma)
+    r, n = w.size // 2, x.size
+    ext = x[track_reflect(np.arange(-r, n + r), n)]
+    return np.array([np.dot(ext[l:l + 2 * r + 1], w) for l in range(n)])
+
+
+def track_boxes(joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0, pad="zero", return_params=False):
+    """One box per frame from 2D joints in numpy float64: the reference's lib/utils/smooth_bbox.py (kp_to_bbox_param squared=True,
+    get_all_bbox_params, smooth_bbox_params) and the box of lib/dataset/inference.py:57-66 -- the host statement of GRNet.track_boxes, same
+    arguments, a dict of numpy arrays (the rules: DESIGN 4.10).  Per frame: min and max of x and y over the joints with score > vis_thresh,
+    height = sqrt(dx^2 + dy^2), a detection where height >= 0.5 (and everything is finite), centre = (min + max) / 2, scale = 150 / height.
+    Per sequence: [start, end) from the first to the last detection, np.linspace across the frames without one, then per column the median
+    (kernel_size > 1) and the Gaussian (sigma > 0) over [start, end), and box = [cx, cy, 150 / scale, 150 / scale].  boxes (n,4); status (n,)
+    int32: 0 detected, 1 interpolated, 2 outside [start, end), 3 no positive finite smoothed scale (2 and 3: zeros); range (n_seq,2) int32,
+    [-1, 0) without any detection.  return_params: also params (n,3) = the smoothed [cx, cy, scale], zeros outside [start, end)."""
+    kp = np.asarray(joints2d, np.float64)
+    if kp.ndim != 3 or kp.shape[2] != 3 or kp.shape[0] < 1 or not 1 <= kp.shape[1] <= 64:
+        raise ValueError(f"joints2d must be (T,K,3) with T >= 1 and 1 <= K <= 64, got {kp.shape}")
+    n = kp.shape[0]
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    if not np.isfinite(vis_thresh):
+        raise ValueError("vis_thresh must be finite")
+    if kernel_size < 1 or kernel_size > 31 or kernel_size % 2 == 0:
+        raise ValueError(f"kernel_size {kernel_size} must be odd and within [1, 31]")
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    if pad not in ("zero", "edge"):
+        raise ValueError(f"pad must be 'zero' or 'edge', got {pad!r}")
+    boxes, status = np.zeros((n, 4)), np.full(n, TRACK_OUTSIDE, np.int32)
+    params, rng = np.zeros((n, 3)), np.empty((len(lengths), 2), np.int32)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            rows = np.zeros((T, 3))
+            detected = np.zeros(T, bool)
+            for i in range(T):
+                vis = kp[a + i, :, 2] > vis_thresh
+                if not vis.any():
+                    continue
+                lo, hi = kp[a + i, vis, :2].min(axis=0), kp[a + i, vis, :2].max(axis=0)
+                d = hi - lo
+                height = np.sqrt(d[0] * d[0] + d[1] * d[1])
+                if not (np.isfinite(kp[a + i, vis, :2]).all() and height >= TRACK_MIN_HEIGHT and np.isfinite(height)):
+                    continue
+                rows[i, :2], rows[i, 2] = (lo + hi) / 2.0, TRACK_PERSON_PIXELS / height
+                detected[i] = True
+            found = np.flatnonzero(detected)
+            if not found.size:
+                rng[q] = (-1, 0)
+                a += T
+                continue
+            start, end = int(found[0]), int(found[-1]) + 1
+            rng[q] = (start, end)
+            for lo, hi in zip(found[:-1], found[1:]):
+                if hi - lo > 1:                                  # column by column, on scalars, as the reference calls np.linspace
+                    for c in range(3):
+                        rows[lo + 1:hi, c] = np.linspace(rows[lo, c], rows[hi, c], hi - lo + 1)[1:-1]
+            cols = rows[start:end].copy()
+            for c in range(3):
+                if kernel_size > 1:
+                    cols[:, c] = median_filter1d(cols[:, c], kernel_size, pad)
+                if sigma > 0:
+                    cols[:, c] = gauss_filter1d(cols[:, c], sigma)
+            good = (cols[:, 2] > 0) & np.isfinite(cols[:, 2])
+            side = TRACK_PERSON_PIXELS / np.where(good, cols[:, 2], 1.0)
+            inside = np.stack([cols[:, 0], cols[:, 1], side, side], axis=1)
+            boxes[a + start:a + end] = np.where(good[:, None], inside, 0.0)
+            status[a + start:a + end] = np.where(good, np.where(detected[start:end], TRACK_DETECTED, TRACK_INTERPOLATED), TRACK_BAD_SCALE)
+            params[a + start:a + end] = cols
+            a += T
+    out = {"boxes": boxes, "status": status, "range": rng}
+    if return_params:
+        out["params"] = params
+    return out
 
 
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
