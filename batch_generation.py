@@ -19,6 +19,11 @@ reference's Inference(joints2d=...) does (lib/utils/smooth_bbox.py; GRNet.track_
 are interpolated, the frames before the first and after the last detection are dropped, --bbox_smooth adds the median and the Gaussian, and the
 database gains 'bbox_status'.
 
+--gait (opt-in, with --vid_folder) reads heel strikes, toe-offs and the gait parameters of every video off its 3D joints -- cadence, step and stride
+time with their variability, step length and width, stance share, walking speed (GRNet.gait_parameters on the device, DESIGN 4.11: the
+coordinate-based events of Zeni, Richards and Higginson 2008) -- writes them to <outpath>_gait.json and adds 'gait_events' to the database; with
+--trajectory the speed along the fitted trajectory as well.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -234,10 +239,58 @@ class WindowTrajectory:
         return rows
 
 
+class WindowGait:
+    """--gait: one gait_parameters call per database window on rank 0, one sequence per video, on the kinectv2 joints the gather left on the device
+    (model.gait_parameters; on_host, or a model without the method: pipeline.gait_parameters after a download), with the window's translations
+    where --trajectory made them -- as the database stores them, float32, so the file can be made again from the database.  The joints are
+    pipeline.GAIT_JOINTS_KINECTV2."""
+
+    def __init__(self, pipe, model, on_host, fps=20.0, sigma=2.0, window=5, min_excursion=0.05):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_parameters") else model.gait_parameters
+        self.kw = dict(fps=float(fps), sigma=float(sigma), window=int(window), min_excursion=float(min_excursion))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None -> per video the events (T,) uint8."""
+        import torch
+        if not keys:
+            return []
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, **self.kw).items()}
+        else:
+            out = self.pipe.gait_parameters(j3.cpu().numpy(), lengths=lengths, trans=trans, **self.kw)
+        events, a = [], 0
+        for key, T, row in zip(keys, lengths, out["per_sequence"]):
+            events.append(out["events"][a:a + T].astype(np.uint8))
+            self.videos[key] = {name: (None if np.isnan(v) else float(v)) for name, v in zip(self.pipe.GAIT_COLUMNS, row)}
+            shown = self.videos[key]
+            speed = "none" if shown["speed"] is None else f"{shown['speed']:.3f} m/s"
+            if shown["trajectory_speed"] is not None:
+                speed += f" ({shown['trajectory_speed']:.3f} m/s along the trajectory)"
+            print(f"Gait: video {key}, {int(row[4])} steps, cadence {'none' if shown['cadence'] is None else format(shown['cadence'], '.1f') + ' steps/min'}, "
+                  f"stride-time CV {'none' if shown['stride_time_cv'] is None else format(shown['stride_time_cv'], '.2f') + ' %'}, speed {speed}.")
+            a += T
+        return events
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait parameters of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None):
-    """tracks: {vid_name: {'range': (start, end), 'frames': T, 'status': (end - start,) uint8}} of boxes_from_openpose(track=...) -- annos holds one
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None):
+    """gait: {'fps', 'sigma', 'window', 'min_excursion', 'on_host', 'out'} (each optional) -- also read the gait events and parameters of every video
+    off its joints (WindowGait), add 'gait_events' (N,) uint8 to the database (bit 0 heel strike left, 1 heel strike right, 2 toe-off left, 3 toe-off
+    right) and write the parameters to gait['out'] (default: outpath with _gait.json).
+    tracks: {vid_name: {'range': (start, end), 'frames': T, 'status': (end - start,) uint8}} of boxes_from_openpose(track=...) -- annos holds one
     box per frame of [start, end) of each video: only those frames are generated, the 2D joints of `trajectory` are taken as sliced alike, and the
     database gains 'bbox_status' (N,) uint8 (0 detected, 1 interpolated or held).
     trajectory: {'joints2d': {vid_name: (T,25,3) pixel joints}, 'focal_length': F or None, 'on_host': bool} -- also fit the camera-space
@@ -294,6 +347,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     metrics = WindowMetrics(load_ground_truth(gt_path), pipe, model, metrics_on_host) if gt_path and rank == 0 else None
     traj = WindowTrajectory(trajectory["joints2d"], pipe, model, trajectory.get("on_host", False), trajectory.get("focal_length")) \
         if trajectory is not None and rank == 0 else None
+    walk = WindowGait(pipe, model, gait.get("on_host", False), **{k: gait[k] for k in ("fps", "sigma", "window", "min_excursion") if gait.get(k) is not None}) \
+        if gait is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -343,6 +398,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         if metrics is not None:
             metrics.add_window([v[0] for v in vids], per_video)
         fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
+        gait_events = walk.add_window([v[0] for v in vids], per_video, fitted) if walk is not None else None
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -351,6 +407,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                 extra = dict(zip(("trans", "trans_status", "reproj"), fitted[vi])) if fitted is not None else {}
                 if status is not None:
                     extra["bbox_status"] = status
+                if gait_events is not None:
+                    extra["gait_events"] = gait_events[vi]
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -360,6 +418,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         print(f"Save database to {db.flush()}.")
     if metrics is not None:
         metrics.write(metrics_out or osp.splitext(outpath)[0] + "_metrics.json")
+    if walk is not None:
+        walk.write(gait.get("out") or osp.splitext(outpath)[0] + "_gait.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -398,6 +458,15 @@ def main(argv=None):
                    f"sqrt({IMG_W}^2 + {IMG_H}^2) (a 53 degree diagonal field of view) and the centre ({IMG_W // 2}, {IMG_H // 2}) are ASSUMPTIONS, and depth "
                    "scales with the focal length")
     p.add_argument("--trajectory_on_host", action="store_true", help="with --trajectory: the numpy float64 statement of the fit instead of the GPU kernels")
+    p.add_argument("--gait", action="store_true", help="with --vid_folder: heel strikes, toe-offs and the gait parameters of every video from its 3D joints (cadence, step "
+                   "and stride time with their variability, step length and width, stance share, speed; with --trajectory the speed along the fitted trajectory too): "
+                   "'gait_events' (N,) in the database, the parameters in <outpath>_gait.json, one line per video")
+    p.add_argument("--gait_out", type=str, default="", help="with --gait: the JSON file of the parameters (default: --outpath with _gait.json)")
+    p.add_argument("--gait_fps", type=float, default=None, help="with --gait: frames a second of the extracted frames (default 20, what the reference extracts at)")
+    p.add_argument("--gait_sigma", type=float, default=None, help="with --gait: sigma in frames of the Gaussian over the ankle and foot signals, 0 (none) to 16 (default 2)")
+    p.add_argument("--gait_window", type=int, default=None, help="with --gait: an event is the extreme of this many frames on either side, 1 to 32 (default 5)")
+    p.add_argument("--gait_min_excursion", type=float, default=None, help="with --gait: metres a signal must rise or fall within the window for an event (default 0.05)")
+    p.add_argument("--gait_on_host", action="store_true", help="with --gait: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -432,6 +501,20 @@ def main(argv=None):
         sys.exit("batch_generation.py: --trajectory needs --openpose_folder (the 2D joints) and --vid_folder (the frames)")
     if a.trajectory and not (np.isfinite(a.focal_length) and a.focal_length >= 0):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
+    for flag, given in (("--gait_out", bool(a.gait_out)), ("--gait_fps", a.gait_fps is not None), ("--gait_sigma", a.gait_sigma is not None),
+                        ("--gait_window", a.gait_window is not None), ("--gait_min_excursion", a.gait_min_excursion is not None), ("--gait_on_host", a.gait_on_host)):
+        if given and not a.gait:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait, which was not given")
+    if a.gait and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait needs --vid_folder (the frames whose joints it reads)")
+    if a.gait_fps is not None and not (np.isfinite(a.gait_fps) and a.gait_fps > 0):
+        sys.exit("batch_generation.py: --gait_fps must be a positive number of frames a second")
+    if a.gait_sigma is not None and not (np.isfinite(a.gait_sigma) and 0 <= a.gait_sigma <= 16):
+        sys.exit("batch_generation.py: --gait_sigma must be within 0 to 16")
+    if a.gait_window is not None and not 1 <= a.gait_window <= 32:
+        sys.exit("batch_generation.py: --gait_window must be within 1 to 32")
+    if a.gait_min_excursion is not None and not (np.isfinite(a.gait_min_excursion) and a.gait_min_excursion >= 0):
+        sys.exit("batch_generation.py: --gait_min_excursion must be a number of metres, not negative")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -447,9 +530,11 @@ def main(argv=None):
         trajectory = {"joints2d": joints2d, "focal_length": a.focal_length or None, "on_host": a.trajectory_on_host}
     if a.openpose_folder and not a.vid_folder:
         return
+    gait = {"fps": a.gait_fps, "sigma": a.gait_sigma, "window": a.gait_window, "min_excursion": a.gait_min_excursion, "on_host": a.gait_on_host,
+            "out": a.gait_out or None} if a.gait else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
-                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks)
+                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait)
 
 
 if __name__ == "__main__":

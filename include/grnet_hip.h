@@ -587,6 +587,45 @@ int grnet_track_boxes(grnet_t* h, const double* joints_dev, int K, const int32_t
 int grnet_op_median1d(grnet_t* h, const double* x_dev, const int32_t* offsets_host, int n_seq, int kernel_size, int pad, double* out_dev, void* stream);
 int grnet_op_gauss1d(grnet_t* h, const double* x_dev, const int32_t* offsets_host, int n_seq, double sigma, double* out_dev, void* stream);
 
+/* ---- gait events and parameters from the 3D joints (csrc/gait_kernels.hip, csrc/gait_events.h) -------------------------------------
+ * The coordinate-based events of Zeni, Richards and Higginson (Gait & Posture 27, 2008) and what a gait lab reads from them.  The reference has no
+ * gait code: DESIGN.md 4.11 is the specification.
+ * joints3d_dev float32 (sum T, J, 3), camera frame of the SMPL stage (x right, y down, z away), metres: n_seq sequences lying back to back;
+ * frame_offsets_host: n_seq + 1 frame offsets, the first 0; joints_host: 8 indices into the J joints -- pelvis, spine-shoulder, left hip, right hip,
+ * left ankle, right ankle, left foot, right foot; trans_dev: null, or float64 (sum T, 3), the camera-space translation of every frame (NaN rows
+ * allowed: grnet_fit_translation's per_frame[:, :3]).  Everything is float64, one rounding per operation.
+ *   axes     per frame l = lhip - rhip, u = spine_shoulder - pelvis, f = (l x u) / |l x u| (where the body faces), n = l / |l|; a frame where
+ *            |l x u| or |l| is not a positive finite number is invalid: its signals are NaN, and every later test is a comparison, false for NaN
+ *   signals  hL, hR = (ankle - pelvis) . f; tL, tR = (foot - pelvis) . f; wd = |(lankle - rankle) . n|; products summed x, y, z
+ *   smooth   (sigma > 0; <= 16) grnet_track_boxes' Gaussian over hL, hR, tL, tR inside each sequence; a NaN spreads as far as the kernel reaches
+ *   events   frame t with all of [t - window, t + window] inside its sequence: a heel strike where h(t) > 0, h(t) > h(t - i) and h(t) >= h(t + i) for
+ *            i = 1 .. window, and h(t) - min over the window >= min_excursion; a toe-off where t(t) < 0, t(t) < t(t - i), t(t) <= t(t + i) and
+ *            max over the window - t(t) >= min_excursion
+ * events_dev (sum T) int32: bit 0 heel strike left, 1 heel strike right, 2 toe-off left, 3 toe-off right.
+ * per_frame_dev (sum T, 7) float64 = [hL, hR, tL, tR (as smoothed), wd, step_length, step_width]: at a heel strike of foot X step_length =
+ * h_X(t) - h_other(t) and step_width = wd(t) (of the left foot where both strike), elsewhere NaN.
+ * per_seq_dev (n_seq, 18) float64: [0..3] the four counts in the order of the bits; [4] steps = pairs of consecutive heel strikes in time order
+ * (a frame with both: left first) that are of opposite feet; [5, 6] step time mean and SD in seconds, (t2 - t1) / fps; [7] cadence = 60 / [5];
+ * [8, 9, 10] stride time mean, SD and 100 SD / mean over consecutive heel strikes of the same foot, the left foot's strides first; [11, 12] step
+ * length mean and SD at the second strike of each step, h_X - h_other of the striking foot X; [13, 14] step width mean and SD at the same frames;
+ * [15] stance share in per cent: the mean, over the strides of a foot whose first toe-off after the opening strike lies before the closing strike, of
+ * 100 (t_TO - t_HS) / (t_HS' - t_HS); [16] speed = [11] * [7] / 60; [17] speed along the trajectory = |P(t_b) - P(t_a)| / ((t_b - t_a) / fps) with
+ * P = pelvis + trans and t_a, t_b the first and last heel-strike frames whose trans is finite.  Means are S / n with the sums in time order,
+ * standard deviations two-pass with ddof = 0.  A column is NaN where its count is 0, [17] also where trans_dev is null or t_a = t_b.
+ * No window, filter or search crosses a sequence; fixed orders, no atomics: a sequence's rows have the same bits whether it travels alone or with
+ * others.  Needs no weights.  At most three launches (two with sigma = 0) behind one small copy from pinned memory, whatever n_seq and T; no host
+ * synchronisation; the scratch is the box calls' (grown on demand, outside the arena).
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J),
+ * n_seq outside [1, 8192] (the upper end is grnet_track_boxes': the offsets travel through the same slot of the pinned ring), frame_offsets[0] != 0,
+ * offsets that do not increase, fps not positive and finite, a negative, non-finite or too large
+ * sigma, window outside [1, 32], a negative or non-finite min_excursion.
+ * grnet_op_gait_events: the events rule alone (test hook) on signals_dev float64 (sum T, 4) = [hL, hR, tL, tR] into events_dev. */
+int grnet_gait_parameters(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                          const double* trans_dev, double fps, double sigma, int window, double min_excursion, double* per_frame_dev, int32_t* events_dev,
+                          double* per_seq_dev, void* stream);
+int grnet_op_gait_events(grnet_t* h, const double* signals_dev, const int32_t* frame_offsets_host, int n_seq, int window, double min_excursion,
+                         int32_t* events_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -9,6 +9,7 @@
 //   grnet_metrics.cpp  pose metrics: grnet_pose_metrics, the Procrustes hook and their scratch
 //   grnet_translation.cpp  the camera-space trajectory: grnet_fit_translation
 //   grnet_track.cpp    per-frame boxes from 2D joints: grnet_track_boxes and its two stage hooks
+//   grnet_gait.cpp     gait events and parameters from the 3D joints: grnet_gait_parameters and its events hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -416,3 +417,12 @@ struct grnet {
     GruWorkspace gru_carve(float* p, size_t rows, int b, float** xc) const;
     int clip_limit(int n, const char* tail);
 };
+
+// grnet_track.cpp, shared with grnet_gait.cpp: the first kTrackFront bytes of such a call's scratch hold its table -- the Gaussian's weights
+// (host-made, scipy's), then the n_seq + 1 frame offsets -- uploaded through one slot of the pinned ring, so the copy is enqueued like a kernel.
+constexpr size_t kTrackOffsetsAt = ((size_t)(kTrackMaxRadius + 1) * sizeof(double) + 255) & ~(size_t)255;      // the weights lie in front: the copy ends with the offsets
+constexpr size_t kTrackFront = (kTrackOffsetsAt + (size_t)(kTrackMaxSeqs + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
+struct TrackTable { const int* off; const double* weights; int radius; };      // radius < 0: sigma == 0, no Gaussian
+// "" or what is wrong with n_seq + 1 offsets of sequences of at least one row lying back to back, `unit` values a row
+std::string track_offsets_error(const int32_t* off, int n_seq, long long unit);
+int track_upload_table(grnet* h, const std::string& name, const int32_t* off, int n_seq, double sigma, char* ws, hipStream_t s, TrackTable* t);

@@ -4,17 +4,8 @@
 // slot of the handle's pinned ring, so the copy is enqueued like a kernel and the call returns without waiting for the device.
 #include "grnet_impl.h"
 
-namespace {
-
-constexpr size_t kTrackTableBytes = (size_t)kSegMaxSegments * sizeof(SegSegment);      // one slot of the pinned ring
-constexpr size_t kTrackOffsetsAt = ((size_t)(kTrackMaxRadius + 1) * sizeof(double) + 255) & ~(size_t)255;      // the weights lie in front: the copy ends with the offsets
-constexpr size_t kTrackFront = (kTrackOffsetsAt + (size_t)(kTrackMaxSeqs + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
-static_assert(kTrackFront <= kTrackTableBytes, "the weights and the offsets fit one slot of the pinned ring");
-
-size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// "" or what is wrong with n_seq + 1 offsets of sequences of at least one row lying back to back
-std::string offsets_error(const int32_t* off, int n_seq, long long unit) {
+// The table of a call -- the Gaussian's weights, then the sequences' offsets -- and the offsets' rules: declared in grnet_impl.h, shared with grnet_gait.cpp
+std::string track_offsets_error(const int32_t* off, int n_seq, long long unit) {
     if (off[0] != 0) return "offsets[0] = " + std::to_string(off[0]) + ", not 0";
     for (int q = 0; q < n_seq; ++q)
         if (off[q + 1] <= off[q])
@@ -22,6 +13,13 @@ std::string offsets_error(const int32_t* off, int n_seq, long long unit) {
     if ((long long)off[n_seq] * unit > 0x7fffffffLL) return std::to_string((long long)off[n_seq] * unit) + " values in one call no longer fit 31 bits";
     return "";
 }
+
+namespace {
+
+constexpr size_t kTrackTableBytes = (size_t)kSegMaxSegments * sizeof(SegSegment);      // one slot of the pinned ring
+static_assert(kTrackFront <= kTrackTableBytes, "the weights and the offsets fit one slot of the pinned ring");
+
+size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 std::string filter_error(int kernel_size, double sigma, int pad) {
     if (kernel_size < 1 || kernel_size > kTrackMaxKernel || kernel_size % 2 == 0)
@@ -45,10 +43,10 @@ int gauss_weights(double sigma, double* w) {
     return r;
 }
 
-struct TrackTable { const int* off; const double* weights; int radius; };
+}  // namespace
 
 // The call's table -- weights and offsets -- into the first kTrackFront bytes of the scratch `ws`, through the pinned ring
-int upload_table(grnet* h, const int32_t* off, int n_seq, double sigma, char* ws, hipStream_t s, TrackTable* t) {
+int track_upload_table(grnet* h, const std::string& name, const int32_t* off, int n_seq, double sigma, char* ws, hipStream_t s, TrackTable* t) {
     void* stage = nullptr;
     hipEvent_t staged = nullptr;
     if (int rc = h->seg_stage_slot(&stage, &staged)) return rc;
@@ -56,11 +54,13 @@ int upload_table(grnet* h, const int32_t* off, int n_seq, double sigma, char* ws
     memcpy(static_cast<char*>(stage) + kTrackOffsetsAt, off, (size_t)(n_seq + 1) * sizeof(int32_t));
     hipError_t e = hipMemcpyAsync(ws, stage, kTrackOffsetsAt + (size_t)(n_seq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipEventRecord(staged, s);
-    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("track_boxes: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, name + hipGetErrorString(e));
     t->off = reinterpret_cast<const int*>(ws + kTrackOffsetsAt);
     t->weights = reinterpret_cast<const double*>(ws);
     return 0;
 }
+
+namespace {
 
 int op_filter(grnet_t* h, const std::string& name, const double* x_dev, const int32_t* offsets_host, int n_seq, int kernel_size, double sigma, int pad,
               double* out_dev, void* stream) {
@@ -68,14 +68,14 @@ int op_filter(grnet_t* h, const std::string& name, const double* x_dev, const in
     if (!x_dev || !offsets_host || !out_dev) return h->fail(GRNET_EINVAL, name + "null pointer");
     if (x_dev == out_dev) return h->fail(GRNET_EINVAL, name + "out_dev must not be x_dev");
     std::string why = filter_error(kernel_size, sigma, pad);
-    if (why.empty()) why = offsets_error(offsets_host, n_seq, 1);
+    if (why.empty()) why = track_offsets_error(offsets_host, n_seq, 1);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     DeviceGuard guard(h->device);
     char* ws = nullptr;
     if (int rc = h->bbox_scratch(kTrackFront, &ws)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrackTable t{};
-    if (int rc = upload_table(h, offsets_host, n_seq, sigma, ws, s, &t)) return rc;
+    if (int rc = track_upload_table(h, name, offsets_host, n_seq, sigma, ws, s, &t)) return rc;
     const hipError_t e = launch_track_filter(t.off, n_seq, x_dev, t.weights, t.radius, kernel_size, pad, out_dev, s);
     if (e != hipSuccess) return h->fail(GRNET_EHIP, name + hipGetErrorString(e));
     return 0;
@@ -95,7 +95,7 @@ int grnet_track_boxes(grnet_t* h, const double* joints_dev, int K, const int32_t
         return h->fail(GRNET_EINVAL, name + "null pointer (joints_dev, frame_offsets_host, boxes_dev, status_dev and range_dev are all needed)");
     if (!std::isfinite(vis_thresh)) return h->fail(GRNET_EINVAL, name + "vis_thresh must be finite");
     std::string why = filter_error(kernel_size, sigma, pad);
-    if (why.empty()) why = offsets_error(frame_offsets_host, n_seq, (long long)K * 3);
+    if (why.empty()) why = track_offsets_error(frame_offsets_host, n_seq, (long long)K * 3);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     const int frames = frame_offsets_host[n_seq];
     const size_t b_words = align256((size_t)((frames + 255) / 256) * 4 * sizeof(unsigned long long)), b_params = align256((size_t)frames * 3 * sizeof(double)),
@@ -108,7 +108,7 @@ int grnet_track_boxes(grnet_t* h, const double* joints_dev, int K, const int32_t
     double* work = reinterpret_cast<double*>(ws + kTrackFront + b_words + b_params);
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrackTable t{};
-    if (int rc = upload_table(h, frame_offsets_host, n_seq, sigma, ws, s, &t)) return rc;
+    if (int rc = track_upload_table(h, name, frame_offsets_host, n_seq, sigma, ws, s, &t)) return rc;
     hipError_t e = launch_track_frames(joints_dev, K, frames, vis_thresh, params, words, s);
     if (e == hipSuccess) e = launch_track_sequences(t.off, n_seq, t.weights, t.radius, kernel_size, pad, params, words, work, boxes_dev, status_dev, range_dev, s);
     if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("track_boxes: ") + hipGetErrorString(e));

@@ -384,6 +384,24 @@ hipError_t launch_track_sequences(const int* off, int n_seq, const double* weigh
 // the median (radius < 0) or the Gaussian alone on x, per sequence, into out (not x)
 hipError_t launch_track_filter(const int* off, int n_seq, const double* x, const double* weights, int radius, int ksize, int pad, double* out, hipStream_t s);
 
+// Gait events and parameters from the 3D joints (csrc/gait_kernels.hip, compiled without fma contraction; the arithmetic: csrc/gait_events.h;
+// DESIGN 4.11) ----
+constexpr int kGaitMaxWindow = 32;         // frames on either side of an event
+constexpr int kGaitThreads = 256;          // threads of the sequence kernel's workgroup: four waves, each a word of the event bitmasks at a time
+constexpr int kGaitLdsWords = 64;          // words of each event bitmask a sequence keeps in LDS: 4096 frames (longer ones: the call's scratch)
+struct GaitTable { int j[8]; };            // pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot
+// words of ONE of the four event bitmasks of a call: sequence q owns words (f0 >> 6) + q onwards
+inline size_t gait_mask_words(int frames, int n_seq) { return (size_t)(frames >> 6) + (size_t)n_seq + 1; }
+// per_frame (frames,7): column 4 (the width) always; columns 0 .. 3 (the signals) where raw is null, else raw (4,frames) gets them, a column each
+hipError_t launch_gait_frames(const float* joints, int J, int frames, const GaitTable& tab, double* raw, double* per_frame, hipStream_t s);
+// sigma > 0: columns 0 .. 3 of per_frame = the Gaussian of raw's columns inside each sequence; off: n_seq + 1 frame offsets ON THE DEVICE
+hipError_t launch_gait_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
+// one workgroup per sequence: events (frames), columns 5 and 6 of per_frame, per_seq (n_seq,18); words: 4 * mask_words; trans (frames,3) or null
+hipError_t launch_gait_sequences(const int* off, int n_seq, int J, int pelvis, const float* joints, const double* trans, double fps, int window,
+                                 double min_excursion, unsigned long long* words, size_t mask_words, double* per_frame, int* events, double* per_seq, hipStream_t s);
+// the events rule alone on signals (frames,4) = [hL, hR, tL, tR]
+hipError_t launch_gait_events(const int* off, int n_seq, const double* signals, int window, double min_excursion, int* events, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1086,6 +1086,57 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gauss1d")
         return out
 
+    # ------------------------------------------------------------------ gait events and parameters from the 3D joints
+    def gait_parameters(self, joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, window=5, min_excursion=0.05, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Heel strikes, toe-offs and the gait parameters of every sequence on the device (grnet_gait_parameters; the rules and the columns: DESIGN
+        4.11, pipeline.GAIT_COLUMNS).  joints3d (T,J,3) in the camera frame of the SMPL stage, metres, or (sum T,J,3) with the sequences' `lengths` --
+        numpy or torch, taken as float32; joints: the 8 indices pelvis, spine-shoulder, left and right hip, ankle, foot (default: kinectv2,
+        pipeline.GAIT_JOINTS_KINECTV2); trans (sum T,3): the camera-space translation of every frame (fit_translation's per_frame[:, :3]; NaN rows
+        allowed), taken as float64.  sigma (frames; 0: none, <= 16) smooths the four signals, window (1 .. 32 frames) and min_excursion (metres) rule the
+        events.  Returns a dict of device tensors: per_frame (n,7) float64 [hL, hR, tL, tR, wd, step_length, step_width]; events (n,) int32, bit 0 heel
+        strike left, 1 heel strike right, 2 toe-off left, 3 toe-off right; per_sequence (n_seq,18) float64.  Nothing is refused on the data: a
+        degenerate frame has NaN signals and no events near it.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = torch.as_tensor(joints3d)
+        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
+            raise ValueError(f"joints3d must be (T,J,3) with T >= 1, got {tuple(j.shape)}")
+        j = j.to(self.device, torch.float32).contiguous()
+        n = j.shape[0]
+        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
+        if table.size != 8:
+            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        t = None
+        if trans is not None:
+            t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
+            if tuple(t.shape) != (n, 3):
+                raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
+        if int(window) != window:
+            raise ValueError(f"window {window} must be a whole number of frames")
+        off = self._sequence_offsets(n, lengths, "joints3d")
+        n_seq = len(off) - 1
+        out = {"per_frame": torch.empty(n, 7, dtype=torch.float64, device=self.device), "events": torch.empty(n, dtype=torch.int32, device=self.device),
+               "per_sequence": torch.empty(n_seq, 18, dtype=torch.float64, device=self.device)}
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_gait_parameters(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, table.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             None if t is None else t.data_ptr(), float(fps), float(sigma), int(window), float(min_excursion),
+                                             out["per_frame"].data_ptr(), out["events"].data_ptr(), out["per_sequence"].data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_gait_parameters")
+        return out
+
+    def op_gait_events(self, signals, lengths=None, window=5, min_excursion=0.05):
+        """The events rule of gait_parameters alone (grnet_op_gait_events): signals (n,4) float64 [hL, hR, tL, tR], one sequence or `lengths` of them
+        lying back to back -> (n,) int32 events on the device."""
+        x = torch.as_tensor(signals).to(self.device, torch.float64).contiguous()
+        if x.dim() != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+            raise ValueError(f"signals must be (n,4) with n >= 1, got {tuple(x.shape)}")
+        if int(window) != window:
+            raise ValueError(f"window {window} must be a whole number of frames")
+        off = self._sequence_offsets(x.shape[0], lengths, "signals")
+        out = torch.empty(x.shape[0], dtype=torch.int32, device=self.device)
+        rc = self._lib.grnet_op_gait_events(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, int(window), float(min_excursion),
+                                            out.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_events")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

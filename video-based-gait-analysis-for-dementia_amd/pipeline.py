@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import netspec
+from ._lib import GAIT_JOINTS_KINECTV2
 
 IMAGENET_MEAN = np.array([0.485, 0.456, 0.406], np.float32)
 IMAGENET_STD = np.array([0.229, 0.224, 0.225], np.float32)
@@ -957,6 +958,145 @@ def track_boxes(joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0
     if return_params:
         out["params"] = params
     return out
+
+
+# ----------------------------------------------------------------------------- gait events and parameters from the 3D joints
+# GAIT_JOINTS_KINECTV2 (imported above) = (0, 20, 12, 16, 14, 18, 15, 19): pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot
+GAIT_HEEL_L, GAIT_HEEL_R, GAIT_TOE_L, GAIT_TOE_R = 1, 2, 4, 8   # the bits of an events entry
+GAIT_COLUMNS = ("heel_strikes_left", "heel_strikes_right", "toe_offs_left", "toe_offs_right", "steps", "step_time_mean", "step_time_sd", "cadence",
+                "stride_time_mean", "stride_time_sd", "stride_time_cv", "step_length_mean", "step_length_sd", "step_width_mean", "step_width_sd",
+                "stance_share", "speed", "trajectory_speed")
+
+
+def gait_events(signals, window=5, min_excursion=0.05):
+    """The events rule of DESIGN 4.11 on ONE sequence: signals (T,4) float64 [hL, hR, tL, tR] -> (T,) int32.  Frame t with all of
+    [t - window, t + window] inside: a heel strike where h(t) > 0, h(t) > every earlier and >= every later value of the window, and h(t) - the
+    window's minimum >= min_excursion; a toe-off where t(t) < 0, < before, <= after, and the window's maximum - t(t) >= min_excursion.  Every test
+    is a comparison, false for NaN."""
+    s = np.asarray(signals, np.float64)
+    if s.ndim != 2 or s.shape[1] != 4 or s.shape[0] < 1:
+        raise ValueError(f"signals must be (T,4) with T >= 1, got {s.shape}")
+    T, w = s.shape[0], int(window)
+    ev = np.zeros(T, np.int32)
+    if T < 2 * w + 1:
+        return ev
+    with np.errstate(invalid="ignore"):
+        for k in range(4):
+            x = s[:, k] if k < 2 else -s[:, k]                 # a toe-off is a heel strike of the negated signal: negation is exact
+            win = np.lib.stride_tricks.sliding_window_view(x, 2 * w + 1)     # row i: frames i .. i + 2w, its centre t = i + w
+            v = win[:, w]
+            hit = (v > 0) & (v[:, None] > win[:, :w]).all(axis=1) & (v[:, None] >= win[:, w + 1:]).all(axis=1) & (v - win.min(axis=1) >= min_excursion)
+            ev[w:T - w] |= np.where(hit, 1 << k, 0).astype(np.int32)
+    return ev
+
+
+def _gait_sum(values):
+    """The sum in the order given, one rounding per addition (np.sum adds pairwise)."""
+    return float(np.cumsum(np.asarray(values, np.float64))[-1])
+
+
+def _gait_mean_sd(values):
+    """(S / n, sqrt(sum((x - mean)^2) / n)) with both sums in the order given; (nan, nan) of nothing."""
+    x = np.asarray(values, np.float64)
+    if x.size == 0:
+        return np.nan, np.nan
+    mean = _gait_sum(x) / x.size
+    d = x - mean
+    return mean, float(np.sqrt(_gait_sum(d * d) / x.size))
+
+
+def gait_parameters(joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, window=5, min_excursion=0.05, joints=GAIT_JOINTS_KINECTV2):
+    """Heel strikes, toe-offs and gait parameters from 3D joints in numpy float64 (the coordinate-based events of Zeni, Richards and Higginson 2008;
+    the rules: DESIGN 4.11): the host statement of GRNet.gait_parameters, same arguments, a dict of numpy arrays -- the same operations in the same
+    order, every sum a cumulative sum.  joints3d (n,J,3) in the camera frame of the SMPL stage (x right, y down, z away), taken as float32 and
+    widened; joints: the indices of pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot; trans (n,3) float64
+    or None.  per_frame (n,7) = [hL, hR, tL, tR (as smoothed), wd, step_length, step_width]; events (n,) int32 (GAIT_HEEL_L, GAIT_HEEL_R,
+    GAIT_TOE_L, GAIT_TOE_R); per_sequence (n_seq,18), columns GAIT_COLUMNS."""
+    a3 = np.asarray(joints3d)
+    if a3.ndim != 3 or a3.shape[2] != 3 or a3.shape[0] < 1 or a3.shape[1] < 1:
+        raise ValueError(f"joints3d must be (n,J,3) with n, J >= 1, got {a3.shape}")
+    j3 = a3.astype(np.float32).astype(np.float64)
+    n, J = j3.shape[:2]
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    if not 1 <= int(window) <= 32 or int(window) != window:
+        raise ValueError(f"window {window} outside [1, 32]")
+    if not np.isfinite(min_excursion) or min_excursion < 0:
+        raise ValueError("min_excursion must be finite and not negative")
+    tr = None
+    if trans is not None:
+        tr = np.asarray(trans, np.float64)
+        if tr.shape != (n, 3):
+            raise ValueError(f"trans must be ({n},3), got {tr.shape}")
+    fps, w = float(fps), int(window)
+
+    def dot(a, b):
+        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+    pelvis, spine, lhip, rhip, lank, rank_, lfoot, rfoot = (j3[:, i] for i in tab)
+    per_frame = np.full((n, 7), np.nan)
+    with np.errstate(all="ignore"):
+        l, u = lhip - rhip, spine - pelvis
+        c = np.stack([l[:, 1] * u[:, 2] - l[:, 2] * u[:, 1], l[:, 2] * u[:, 0] - l[:, 0] * u[:, 2], l[:, 0] * u[:, 1] - l[:, 1] * u[:, 0]], axis=1)
+        nc, nl = np.sqrt(dot(c, c)), np.sqrt(dot(l, l))
+        valid = (nc > 0) & np.isfinite(nc) & (nl > 0) & np.isfinite(nl)
+        f, side = c / nc[:, None], l / nl[:, None]
+        for k, joint in enumerate((lank, rank_, lfoot, rfoot)):
+            per_frame[:, k] = np.where(valid, dot(joint - pelvis, f), np.nan)
+        per_frame[:, 4] = np.where(valid, np.abs(dot(lank - rank_, side)), np.nan)
+    events = np.zeros(n, np.int32)
+    per_seq = np.full((len(lengths), 18), np.nan)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            rows = per_frame[a:a + T]
+            if sigma > 0:
+                for k in range(4):
+                    rows[:, k] = gauss_filter1d(rows[:, k].copy(), sigma)
+            ev = events[a:a + T]
+            ev[:] = gait_events(rows[:, :4], w, min_excursion)
+            heel = [np.flatnonzero(ev & GAIT_HEEL_L), np.flatnonzero(ev & GAIT_HEEL_R)]
+            toe = [np.flatnonzero(ev & GAIT_TOE_L), np.flatnonzero(ev & GAIT_TOE_R)]
+            for foot in (1, 0):                                  # the left foot's values where both strike in one frame
+                rows[heel[foot], 5] = rows[heel[foot], foot] - rows[heel[foot], 1 - foot]
+                rows[heel[foot], 6] = rows[heel[foot], 4]
+            out = per_seq[q]
+            out[:4] = heel[0].size, heel[1].size, toe[0].size, toe[1].size
+            strikes = sorted([(int(t), 0) for t in heel[0]] + [(int(t), 1) for t in heel[1]])      # time order, the left foot first within a frame
+            steps = [(t1, t2, f2) for (t1, f1), (t2, f2) in zip(strikes[:-1], strikes[1:]) if f1 != f2]
+            out[4] = len(steps)
+            if steps:
+                out[5], out[6] = _gait_mean_sd([float(t2 - t1) / fps for t1, t2, _ in steps])
+                out[7] = 60.0 / out[5]
+                out[11], out[12] = _gait_mean_sd([rows[t2, f2] - rows[t2, 1 - f2] for _, t2, f2 in steps])
+                out[13], out[14] = _gait_mean_sd([rows[t2, 4] for _, t2, _ in steps])
+                out[16] = (out[11] * out[7]) / 60.0
+            strides = [(int(t1), int(t2), foot) for foot in (0, 1) for t1, t2 in zip(heel[foot][:-1], heel[foot][1:])]     # the left foot's first
+            if strides:
+                out[8], out[9] = _gait_mean_sd([float(t2 - t1) / fps for t1, t2, _ in strides])
+                out[10] = (100.0 * out[9]) / out[8]
+            stance = []
+            for t1, t2, foot in strides:
+                off = toe[foot][(toe[foot] > t1) & (toe[foot] < t2)]
+                if off.size:
+                    stance.append((100.0 * float(off[0] - t1)) / float(t2 - t1))
+            if stance:
+                out[15] = _gait_sum(stance) / len(stance)
+            if tr is not None:
+                seen = [t for t, _ in strikes if np.isfinite(tr[a + t]).all()]
+                if seen and seen[0] != seen[-1]:
+                    ta, tb = seen[0], seen[-1]
+                    d = (pelvis[a + tb] + tr[a + tb]) - (pelvis[a + ta] + tr[a + ta])
+                    out[17] = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) / (float(tb - ta) / fps)
+            a += T
+    return {"per_frame": per_frame, "events": events, "per_sequence": per_seq}
 
 
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
