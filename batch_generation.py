@@ -24,6 +24,11 @@ time with their variability, step length and width, stance share, walking speed 
 coordinate-based events of Zeni, Richards and Higginson 2008) -- writes them to <outpath>_gait.json and adds 'gait_events' to the database; with
 --trajectory the speed along the fitted trajectory as well.
 
+--gait_kinematics (opt-in, with --gait) adds the other half of what a gait lab reads off a walk: hip, knee, ankle, shoulder and elbow angles and the
+trunk's inclination, cut at the heel strikes --gait found, put on 0 to 100 % of the gait cycle and averaged over the strides, with each joint's range
+of motion and its left / right symmetry (GRNet.gait_kinematics on the device) -- in <outpath>_kinematics.json.  The numbers are
+reported, never judged; the trunk's inclination assumes a level camera.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -260,9 +265,11 @@ class WindowGait:
         j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
         trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
         if self.device_call is not None:
-            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, **self.kw).items()}
+            made = self.device_call(j3, lengths=lengths, trans=trans, **self.kw)
+            out = {k: v.cpu().numpy() for k, v in made.items()}
         else:
-            out = self.pipe.gait_parameters(j3.cpu().numpy(), lengths=lengths, trans=trans, **self.kw)
+            made = out = self.pipe.gait_parameters(j3.cpu().numpy(), lengths=lengths, trans=trans, **self.kw)
+        self.window = (j3, lengths, made["events"])            # for WindowKinematics: the joints and the events as this call returned them
         events, a = [], 0
         for key, T, row in zip(keys, lengths, out["per_sequence"]):
             events.append(out["events"][a:a + T].astype(np.uint8))
@@ -284,10 +291,62 @@ class WindowGait:
         return path
 
 
+class WindowKinematics:
+    """--gait_kinematics: one gait_kinematics call per database window on rank 0, directly after WindowGait's, on the same joints and on the events
+    that call returned (model.gait_kinematics; on_host, or a model without the method: pipeline.gait_kinematics after a download).  Per video and
+    channel (pipeline.KINEMATICS_CHANNELS) the six columns of pipeline.KINEMATICS_COLUMNS plus curve_mean and curve_sd, 101 numbers each.  The joints
+    are pipeline.KINEMATICS_JOINTS_KINECTV2.  The database gains nothing: the per-frame angles can be made again from its joints and events."""
+
+    def __init__(self, pipe, model, on_host, sigma=2.0, min_stride=8, max_stride=60):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_kinematics") else model.gait_kinematics
+        self.kw = dict(sigma=float(sigma), min_stride=int(min_stride), max_stride=int(max_stride))
+        self.videos = {}
+
+    def add_window(self, keys, j3, lengths, events):
+        """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths and the events (sum T,)."""
+        if not keys:
+            return
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, lengths=lengths, **self.kw).items()}
+        else:
+            ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
+            out = self.pipe.gait_kinematics(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, unit=" deg"):
+            return "none" if v is None else f"{v:.1f}{unit}"
+        a = 0
+        for key, T, rows, curves in zip(keys, lengths, out["per_sequence"], out["curves"]):
+            video = {}
+            for c, name in enumerate(self.pipe.KINEMATICS_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.KINEMATICS_COLUMNS, rows[c])}
+                video[name]["curve_mean"] = [number(v) for v in curves[c, :, 0]]
+                video[name]["curve_sd"] = [number(v) for v in curves[c, :, 1]]
+            self.videos[key] = video
+            trunk = out["per_frame"][a:a + T, 12]
+            trunk = None if not np.isfinite(trunk).any() else float(np.nanmean(trunk))
+            print(f"Kinematics: video {key}, knee ROM {shown(video['knee_flexion_left']['rom_mean'])} / {shown(video['knee_flexion_right']['rom_mean'])}, "
+                  f"arm swing ROM {shown(video['shoulder_flexion_left']['rom_mean'])} / {shown(video['shoulder_flexion_right']['rom_mean'])} "
+                  f"(symmetry index {shown(video['shoulder_flexion_left']['symmetry_index'], ' %')}), mean trunk inclination {shown(trunk)}.")
+            a += T
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait kinematics of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None, gait=None):
-    """gait: {'fps', 'sigma', 'window', 'min_excursion', 'on_host', 'out'} (each optional) -- also read the gait events and parameters of every video
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None):
+    """kinematics: {'sigma', 'min_stride', 'max_stride', 'on_host', 'out'} (each optional; needs gait) -- also the joint angles per gait cycle of every
+    video (WindowKinematics), written to kinematics['out'] (default: outpath with _kinematics.json); the database gains nothing.
+    gait: {'fps', 'sigma', 'window', 'min_excursion', 'on_host', 'out'} (each optional) -- also read the gait events and parameters of every video
     off its joints (WindowGait), add 'gait_events' (N,) uint8 to the database (bit 0 heel strike left, 1 heel strike right, 2 toe-off left, 3 toe-off
     right) and write the parameters to gait['out'] (default: outpath with _gait.json).
     tracks: {vid_name: {'range': (start, end), 'frames': T, 'status': (end - start,) uint8}} of boxes_from_openpose(track=...) -- annos holds one
@@ -349,6 +408,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         if trajectory is not None and rank == 0 else None
     walk = WindowGait(pipe, model, gait.get("on_host", False), **{k: gait[k] for k in ("fps", "sigma", "window", "min_excursion") if gait.get(k) is not None}) \
         if gait is not None and rank == 0 else None
+    if kinematics is not None and gait is None:
+        raise ValueError("kinematics needs gait: the cycles are cut at the heel strikes it finds")
+    angles = WindowKinematics(pipe, model, kinematics.get("on_host", False),
+                              **{k: kinematics[k] for k in ("sigma", "min_stride", "max_stride") if kinematics.get(k) is not None}) \
+        if kinematics is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -399,6 +463,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             metrics.add_window([v[0] for v in vids], per_video)
         fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
         gait_events = walk.add_window([v[0] for v in vids], per_video, fitted) if walk is not None else None
+        if angles is not None and vids:
+            angles.add_window([v[0] for v in vids], *walk.window)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -420,6 +486,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         metrics.write(metrics_out or osp.splitext(outpath)[0] + "_metrics.json")
     if walk is not None:
         walk.write(gait.get("out") or osp.splitext(outpath)[0] + "_gait.json")
+    if angles is not None:
+        angles.write(kinematics.get("out") or osp.splitext(outpath)[0] + "_kinematics.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -467,6 +535,13 @@ def main(argv=None):
     p.add_argument("--gait_window", type=int, default=None, help="with --gait: an event is the extreme of this many frames on either side, 1 to 32 (default 5)")
     p.add_argument("--gait_min_excursion", type=float, default=None, help="with --gait: metres a signal must rise or fall within the window for an event (default 0.05)")
     p.add_argument("--gait_on_host", action="store_true", help="with --gait: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_kinematics", action="store_true", help="with --gait: hip, knee, ankle, shoulder and elbow angles and the trunk's inclination per gait cycle "
+                   "(101 points, mean and SD over the strides), each joint's range of motion and left / right symmetry, in <outpath>_kinematics.json, one line per video")
+    p.add_argument("--kinematics_out", type=str, default="", help="with --gait_kinematics: the JSON file (default: --outpath with _kinematics.json)")
+    p.add_argument("--kinematics_sigma", type=float, default=None, help="with --gait_kinematics: sigma in frames of the Gaussian over the angles, 0 (none) to 16 (default 2)")
+    p.add_argument("--kinematics_min_stride", type=int, default=None, help="with --gait_kinematics: the shortest stride that is used, in frames (default 8: 0.4 s at 20 fps)")
+    p.add_argument("--kinematics_max_stride", type=int, default=None, help="with --gait_kinematics: the longest stride that is used, in frames, at most 4096 (default 60: 3 s)")
+    p.add_argument("--kinematics_on_host", action="store_true", help="with --gait_kinematics: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -515,6 +590,18 @@ def main(argv=None):
         sys.exit("batch_generation.py: --gait_window must be within 1 to 32")
     if a.gait_min_excursion is not None and not (np.isfinite(a.gait_min_excursion) and a.gait_min_excursion >= 0):
         sys.exit("batch_generation.py: --gait_min_excursion must be a number of metres, not negative")
+    if a.gait_kinematics and not a.gait:
+        sys.exit("batch_generation.py: --gait_kinematics belongs to --gait, which was not given (the cycles are cut at the heel strikes it finds)")
+    for flag, given in (("--kinematics_out", bool(a.kinematics_out)), ("--kinematics_sigma", a.kinematics_sigma is not None),
+                        ("--kinematics_min_stride", a.kinematics_min_stride is not None), ("--kinematics_max_stride", a.kinematics_max_stride is not None),
+                        ("--kinematics_on_host", a.kinematics_on_host)):
+        if given and not a.gait_kinematics:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_kinematics, which was not given")
+    if a.kinematics_sigma is not None and not (np.isfinite(a.kinematics_sigma) and 0 <= a.kinematics_sigma <= 16):
+        sys.exit("batch_generation.py: --kinematics_sigma must be within 0 to 16")
+    lo, hi = 8 if a.kinematics_min_stride is None else a.kinematics_min_stride, 60 if a.kinematics_max_stride is None else a.kinematics_max_stride
+    if a.gait_kinematics and not 1 <= lo <= hi <= 4096:
+        sys.exit("batch_generation.py: --kinematics_min_stride and --kinematics_max_stride must be frames with 1 <= min <= max <= 4096")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -532,9 +619,12 @@ def main(argv=None):
         return
     gait = {"fps": a.gait_fps, "sigma": a.gait_sigma, "window": a.gait_window, "min_excursion": a.gait_min_excursion, "on_host": a.gait_on_host,
             "out": a.gait_out or None} if a.gait else None
+    kinematics = {"sigma": a.kinematics_sigma, "min_stride": a.kinematics_min_stride, "max_stride": a.kinematics_max_stride, "on_host": a.kinematics_on_host,
+                  "out": a.kinematics_out or None} if a.gait_kinematics else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
-                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait)
+                 gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
+                 **({"kinematics": kinematics} if kinematics is not None else {}))
 
 
 if __name__ == "__main__":

@@ -626,6 +626,41 @@ int grnet_gait_parameters(grnet_t* h, const float* joints3d_dev, int J, const in
 int grnet_op_gait_events(grnet_t* h, const double* signals_dev, const int32_t* frame_offsets_host, int n_seq, int window, double min_excursion,
                          int32_t* events_dev, void* stream);
 
+/* ---- joint-angle kinematics per gait cycle (csrc/gait_kinematics_kernels.hip, csrc/gait_angles.h) --------------------------------
+ * Hip, knee, ankle, shoulder and elbow angles and the trunk's inclination over time, cut at the heel strikes grnet_gait_parameters found, put on
+ * 0 .. 100 % of the gait cycle and averaged over the strides.  The reference has no such code: DESIGN.md 4.12 is the specification.
+ * joints3d_dev float32 (sum T, J, 3), frame_offsets_host as for grnet_gait_parameters; events_dev int32 (sum T): its events (bits 0 and 1, the heel
+ * strikes, are read); joints_host: 16 indices into the J joints -- pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder,
+ * elbow, wrist.  Everything is float64, one rounding per operation; the arctangent is made of + - * / and sqrt alone (csrc/gait_angles.h), so the
+ * numpy statement and the kernels agree in every bit.
+ *   axes     l, u, f, n as grnet_gait_parameters makes them, and w = f x n, the body's up; an invalid frame has NaN in the channels that use the axes
+ *            (0 .. 3, 8, 9, 12) and numbers in the others
+ *   channels in degrees: 0, 1 hip flexion left, right atan2(d . f, -(d . w)) with d = knee - hip; 2, 3 hip abduction atan2(+-(d . n), -(d . w));
+ *            4, 5 knee flexion atan2(|d x s|, d . s) with s = ankle - knee; 6, 7 ankle dorsiflexion atan2(|s x g|, s . g) - 90 with g = foot - ankle;
+ *            8, 9 shoulder flexion atan2(a . f, -(a . w)) with a = elbow - shoulder; 10, 11 elbow flexion atan2(|a x b|, a . b) with
+ *            b = wrist - elbow; 12 trunk inclination atan2(|u x e|, u . e) from e = (0, -1, 0), the vertical of a LEVEL camera
+ *   smooth   (sigma > 0; <= 16) grnet_track_boxes' Gaussian over each of the 13 columns inside each sequence
+ *   strides  pairs of consecutive heel strikes t0 < t1 of the left foot (even channels and 12) or the right (odd ones); used for a channel where
+ *            min_stride <= t1 - t0 <= max_stride and the channel is finite on all of [t0, t1]
+ *   cycle    point p = 0 .. 100 of a stride of L frames: q = p L div 100, r = p L mod 100, x[t0 + q] + (x[t0 + q + 1] - x[t0 + q]) (r / 100.0)
+ * per_frame_dev (sum T, 13) float64: the channels as smoothed.  curves_dev (n_seq, 13, 101, 2) float64: mean and SD of every cycle point over the
+ * used strides.  per_seq_dev (n_seq, 13, 6) float64: [0] strides used; [1], [2] the mean over strides of the stride's maximum and minimum; [3], [4]
+ * mean and SD of the stride's range of motion max - min; [5] the symmetry index 100 |ROM_L - ROM_R| / (0.5 (ROM_L + ROM_R)) of the pair's [3], the
+ * same in both channels, NaN for channel 12, where either count is 0 or the denominator is not positive.  Means are S / n with the sums in time
+ * order from +0.0, standard deviations two-pass with ddof = 0; NaN where no stride is used.
+ * No filter or search crosses a sequence; fixed orders, no atomics: a sequence's outputs have the same bits whether it travels alone or with others.
+ * Needs no weights.  At most three launches (two with sigma = 0) behind one small copy from pinned memory, whatever n_seq and T; no host
+ * synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer, J < 1, a table index outside [0, J), n_seq outside
+ * [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a negative, non-finite or too large sigma, min_stride < 1, max_stride < min_stride,
+ * max_stride > 4096.
+ * grnet_op_gait_cycles: the strides, cycle curves and rows alone (test hook) on angles_dev float64 (sum T, 13) and events_dev. */
+int grnet_gait_kinematics(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                          const int32_t* events_dev, double sigma, int min_stride, int max_stride, double* per_frame_dev, double* curves_dev,
+                          double* per_seq_dev, void* stream);
+int grnet_op_gait_cycles(grnet_t* h, const double* angles_dev, const int32_t* events_dev, const int32_t* frame_offsets_host, int n_seq, int min_stride,
+                         int max_stride, double* curves_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

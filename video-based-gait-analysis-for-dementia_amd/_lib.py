@@ -24,6 +24,8 @@ METRIC_MAX_JOINTS = 64
 TRANS_MAX_PAIRS = 64
 TRACK_PAD = {"zero": 0, "edge": 1}
 GAIT_JOINTS_KINECTV2 = (0, 20, 12, 16, 14, 18, 15, 19)         # pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot
+# pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist
+KINEMATICS_JOINTS_KINECTV2 = (0, 20, 12, 16, 13, 17, 14, 18, 15, 19, 4, 8, 5, 9, 6, 10)
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
 
@@ -133,6 +135,9 @@ EXPORTS = {
     "grnet_gait_parameters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_double, C.c_double,
                                         C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_op_gait_events": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "grnet_gait_kinematics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_double, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grnet_op_gait_cycles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_op_procrustes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "grnet_comm_probe": (C.c_int, []),

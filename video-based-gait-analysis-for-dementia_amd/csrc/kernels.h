@@ -402,6 +402,21 @@ hipError_t launch_gait_sequences(const int* off, int n_seq, int J, int pelvis, c
 // the events rule alone on signals (frames,4) = [hL, hR, tL, tR]
 hipError_t launch_gait_events(const int* off, int n_seq, const double* signals, int window, double min_excursion, int* events, hipStream_t s);
 
+// Joint-angle kinematics per gait cycle (csrc/gait_kinematics_kernels.hip, compiled without fma contraction; the arithmetic: csrc/gait_angles.h;
+// DESIGN 4.12) ----
+constexpr int kKinMaxStride = 4096;        // frames between the two heel strikes of a stride
+constexpr int kKinThreads = 256;           // threads of the cycle kernel's workgroup: four waves; threads 0 .. 100 own a cycle point each
+constexpr int kKinLdsWords = 16;           // words of each heel-strike bitmask a sequence keeps in LDS: 1024 frames (longer ones: the call's scratch)
+constexpr int kKinMaskSets = 26;           // bitmasks of a call in the scratch: left and right for each of the 13 channels' workgroups
+struct KinTable { int j[16]; };            // pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist
+// per_frame (frames,13) where raw is null, else raw (13,frames) gets the angles, a column each
+hipError_t launch_kin_frames(const float* joints, int J, int frames, const KinTable& tab, double* raw, double* per_frame, hipStream_t s);
+// sigma > 0: per_frame = the Gaussian of raw's columns inside each sequence; off: n_seq + 1 frame offsets ON THE DEVICE
+hipError_t launch_kin_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
+// one workgroup per (sequence, channel): curves (n_seq,13,101,2), per_seq (n_seq,13,6); words: kKinMaskSets * mask_words (gait_mask_words)
+hipError_t launch_kin_cycles(const int* off, int n_seq, const int* events, const double* per_frame, int min_stride, int max_stride, unsigned long long* words,
+                             size_t mask_words, double* curves, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1137,6 +1137,61 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_events")
         return out
 
+    # ------------------------------------------------------------------ joint-angle kinematics per gait cycle
+    def gait_kinematics(self, joints3d, events, lengths=None, sigma=2.0, min_stride=8, max_stride=60, joints=_lib.KINEMATICS_JOINTS_KINECTV2):
+        """Joint angles over time and per gait cycle of every sequence on the device (grnet_gait_kinematics; the rules, channels and columns: DESIGN
+        4.12, pipeline.KINEMATICS_CHANNELS, pipeline.KINEMATICS_COLUMNS).  joints3d (T,J,3) in the camera frame of the SMPL stage, metres, or
+        (sum T,J,3) with the sequences' `lengths` -- numpy or torch, taken as float32; events (sum T,): what gait_parameters returned, taken as int32;
+        joints: the 16 indices pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist (default: kinectv2,
+        pipeline.KINEMATICS_JOINTS_KINECTV2).  sigma (frames; 0: none, <= 16) smooths the 13 angle columns; a stride of min_stride .. max_stride frames
+        (1 <= min <= max <= 4096) on which a channel is finite is used for it.  Returns a dict of device tensors: per_frame (n,13) float64 degrees;
+        curves (n_seq,13,101,2) float64, mean and SD of the cycle curve; per_sequence (n_seq,13,6) float64.  Channel 12 assumes a level camera.
+        Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = torch.as_tensor(joints3d)
+        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
+            raise ValueError(f"joints3d must be (T,J,3) with T >= 1, got {tuple(j.shape)}")
+        j = j.to(self.device, torch.float32).contiguous()
+        n = j.shape[0]
+        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
+        if tuple(ev.shape) != (n,):
+            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        table = np.asarray(_lib.KINEMATICS_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
+        if table.size != 16:
+            raise ValueError(f"joints must name 16 joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist), got {table.size}")
+        if int(min_stride) != min_stride or int(max_stride) != max_stride:
+            raise ValueError("min_stride and max_stride must be whole numbers of frames")
+        off = self._sequence_offsets(n, lengths, "joints3d")
+        n_seq = len(off) - 1
+        out = {"per_frame": torch.empty(n, 13, dtype=torch.float64, device=self.device),
+               "curves": torch.empty(n_seq, 13, 101, 2, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 13, 6, dtype=torch.float64, device=self.device)}
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.grnet_gait_kinematics(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, table.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             ev.data_ptr(), float(sigma), int(min_stride), int(max_stride), out["per_frame"].data_ptr(), out["curves"].data_ptr(),
+                                             out["per_sequence"].data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_gait_kinematics")
+        return out
+
+    def op_gait_cycles(self, angles, events, lengths=None, min_stride=8, max_stride=60):
+        """The cycle stage of gait_kinematics alone (grnet_op_gait_cycles): angles (n,13) float64 and events (n,) int32, one sequence or `lengths` of
+        them lying back to back -> {curves (n_seq,13,101,2), per_sequence (n_seq,13,6)} on the device."""
+        x = torch.as_tensor(angles).to(self.device, torch.float64).contiguous()
+        if x.dim() != 2 or x.shape[1] != 13 or x.shape[0] < 1:
+            raise ValueError(f"angles must be (n,13) with n >= 1, got {tuple(x.shape)}")
+        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
+        if tuple(ev.shape) != (x.shape[0],):
+            raise ValueError(f"events must be ({x.shape[0]},), got {tuple(ev.shape)}")
+        if int(min_stride) != min_stride or int(max_stride) != max_stride:
+            raise ValueError("min_stride and max_stride must be whole numbers of frames")
+        off = self._sequence_offsets(x.shape[0], lengths, "angles")
+        n_seq = len(off) - 1
+        out = {"curves": torch.empty(n_seq, 13, 101, 2, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 13, 6, dtype=torch.float64, device=self.device)}
+        rc = self._lib.grnet_op_gait_cycles(self._h, x.data_ptr(), ev.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, int(min_stride), int(max_stride),
+                                            out["curves"].data_ptr(), out["per_sequence"].data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_cycles")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

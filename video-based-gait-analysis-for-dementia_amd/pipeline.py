@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import netspec
-from ._lib import GAIT_JOINTS_KINECTV2
+from ._lib import GAIT_JOINTS_KINECTV2, KINEMATICS_JOINTS_KINECTV2
 
 IMAGENET_MEAN = np.array([0.485, 0.456, 0.406], np.float32)
 IMAGENET_STD = np.array([0.229, 0.224, 0.225], np.float32)
@@ -1097,6 +1097,180 @@ def gait_parameters(joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, win
                     out[17] = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) / (float(tb - ta) / fps)
             a += T
     return {"per_frame": per_frame, "events": events, "per_sequence": per_seq}
+
+
+# ----------------------------------------------------------------------------- joint-angle kinematics per gait cycle
+# KINEMATICS_JOINTS_KINECTV2 (imported above) = (0, 20, 12, 16, 13, 17, 14, 18, 15, 19, 4, 8, 5, 9, 6, 10): pelvis, spine-shoulder, then left and right
+# hip, knee, ankle, foot, shoulder, elbow, wrist
+KINEMATICS_CHANNELS = ("hip_flexion_left", "hip_flexion_right", "hip_abduction_left", "hip_abduction_right", "knee_flexion_left", "knee_flexion_right",
+                       "ankle_dorsiflexion_left", "ankle_dorsiflexion_right", "shoulder_flexion_left", "shoulder_flexion_right", "elbow_flexion_left",
+                       "elbow_flexion_right", "trunk_inclination")
+KINEMATICS_COLUMNS = ("strides", "max_mean", "min_mean", "rom_mean", "rom_sd", "symmetry_index")
+KINEMATICS_POINTS = 101
+KINEMATICS_DEGREES = 57.29577951308232
+_KIN_ATAN_COEFFS = tuple((-1.0 if k % 2 else 1.0) * (1.0 / (2 * k + 1)) for k in range(12))       # 1, -1/3, 1/5, ... -1/23
+
+
+def gait_atan2(y, x):
+    """atan2 out of + - * / and sqrt alone, elementwise in float64 (csrc/gait_angles.h states the same operations in the same order, so the kernels
+    give the same bits): t = min(|y|, |x|) / max(|y|, |x|); twice t <- t / (1 + sqrt(1 + t t)); the 12 terms of atan's Taylor series by Horner; times
+    4; then pi / 2 - a where |y| > |x|, pi - a where x < 0, -a where y < 0.  NaN where both arguments are zero or either is not finite."""
+    y, x = np.broadcast_arrays(np.asarray(y, np.float64), np.asarray(x, np.float64))
+    with np.errstate(all="ignore"):
+        bad = ~np.isfinite(y) | ~np.isfinite(x) | ((y == 0) & (x == 0))
+        ay, ax = np.abs(y), np.abs(x)
+        steep = ay > ax
+        t = np.where(steep, ax, ay) / np.where(bad, 1.0, np.where(steep, ay, ax))
+        t = t / (1.0 + np.sqrt(1.0 + t * t))
+        t = t / (1.0 + np.sqrt(1.0 + t * t))
+        z = t * t
+        p = np.full(z.shape, _KIN_ATAN_COEFFS[11])
+        for c in _KIN_ATAN_COEFFS[10::-1]:
+            p = p * z + c
+        a = 4.0 * (t * p)
+        a = np.where(steep, 1.5707963267948966 - a, a)
+        a = np.where(x < 0, 3.141592653589793 - a, a)
+        a = np.where(y < 0, -a, a) + 0.0
+        return np.where(bad, np.nan, a)
+
+
+def _kin_dot(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def _kin_cross(a, b):
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+
+
+def _kin_bend(a, b):
+    """The angle between the rows of a and b in degrees: atan2(|a x b|, a . b)."""
+    c = _kin_cross(a, b)
+    return gait_atan2(np.sqrt(_kin_dot(c, c)), _kin_dot(a, b)) * KINEMATICS_DEGREES
+
+
+def _kin_sum(values):
+    """The sum along axis 0 in the order given from +0.0, one rounding per addition."""
+    v = np.asarray(values, np.float64)
+    return np.cumsum(np.concatenate([np.zeros((1,) + v.shape[1:]), v]), axis=0)[-1]
+
+
+def _kin_strides_check(min_stride, max_stride):
+    if int(min_stride) != min_stride or int(max_stride) != max_stride:
+        raise ValueError("min_stride and max_stride must be whole numbers of frames")
+    if min_stride < 1:
+        raise ValueError(f"min_stride {min_stride} < 1")
+    if max_stride < min_stride or max_stride > 4096:
+        raise ValueError(f"max_stride {max_stride} outside [min_stride, 4096]")
+    return int(min_stride), int(max_stride)
+
+
+def gait_cycles(angles, events, lengths=None, min_stride=8, max_stride=60):
+    """Rules 5 to 7 of DESIGN 4.12 on given angle columns: the host statement of GRNet.op_gait_cycles.  angles (n,13) float64, events (n,) with the
+    bits of gait_parameters; a stride of a channel's foot -- two consecutive heel strikes t0 < t1 -- is used where min_stride <= t1 - t0 <=
+    max_stride and the channel is finite on all of [t0, t1].  Returns {'curves': (n_seq,13,101,2) mean and SD of every cycle point over the used
+    strides, 'per_sequence': (n_seq,13,6), columns KINEMATICS_COLUMNS}."""
+    x = np.asarray(angles, np.float64)
+    if x.ndim != 2 or x.shape[1] != 13 or x.shape[0] < 1:
+        raise ValueError(f"angles must be (n,13) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64)
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lo, hi = _kin_strides_check(min_stride, max_stride)
+    curves = np.full((len(lengths), 13, KINEMATICS_POINTS, 2), np.nan)
+    rows = np.full((len(lengths), 13, 6), np.nan)
+    points = np.arange(KINEMATICS_POINTS)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            heel = [np.flatnonzero(ev[a:a + T] & GAIT_HEEL_L), np.flatnonzero(ev[a:a + T] & GAIT_HEEL_R)]
+            for c in range(13):
+                col = x[a:a + T, c]
+                hs = heel[0 if c == 12 else c & 1]
+                used = [(int(t0), int(t1 - t0)) for t0, t1 in zip(hs[:-1], hs[1:]) if lo <= t1 - t0 <= hi and np.isfinite(col[t0:t1 + 1]).all()]
+                k = len(used)
+                rows[q, c, 0] = k
+                if not k:
+                    continue
+                top = np.array([col[t0:t0 + L + 1].max() for t0, L in used]) + 0.0         # a zero has the sign +, whatever order the maximum took
+                low = np.array([col[t0:t0 + L + 1].min() for t0, L in used]) + 0.0
+                rom = top - low
+                pts = np.empty((k, KINEMATICS_POINTS))
+                for i, (t0, L) in enumerate(used):
+                    at, r = t0 + (points * L) // 100, (points * L) % 100
+                    v = col[at]
+                    pts[i] = np.where(r == 0, v, v + (col[np.minimum(at + 1, t0 + L)] - v) * (r / 100.0))
+                mean = _kin_sum(pts) / k
+                d = pts - mean
+                curves[q, c, :, 0], curves[q, c, :, 1] = mean, np.sqrt(_kin_sum(d * d) / k)
+                m_rom = _kin_sum(rom) / k
+                e = rom - m_rom
+                rows[q, c, 1:5] = _kin_sum(top) / k, _kin_sum(low) / k, m_rom, np.sqrt(_kin_sum(e * e) / k)
+            for c in range(0, 12, 2):
+                l, r = rows[q, c], rows[q, c + 1]
+                den = 0.5 * (l[3] + r[3])
+                if l[0] > 0 and r[0] > 0 and den > 0:
+                    rows[q, c, 5] = rows[q, c + 1, 5] = (100.0 * abs(l[3] - r[3])) / den
+            a += T
+    return {"curves": curves, "per_sequence": rows}
+
+
+def gait_kinematics(joints3d, events, lengths=None, sigma=2.0, min_stride=8, max_stride=60, joints=KINEMATICS_JOINTS_KINECTV2):
+    """Joint angles over time and per gait cycle from 3D joints in numpy float64 (the rules: DESIGN 4.12): the host statement of
+    GRNet.gait_kinematics, same arguments, a dict of numpy arrays -- the same operations in the same order, every sum a cumulative sum.  joints3d
+    (n,J,3) in the camera frame of the SMPL stage (x right, y down, z away), taken as float32 and widened; events (n,): what gait_parameters
+    returned; joints: the 16 indices of pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist.  per_frame
+    (n,13): the channels KINEMATICS_CHANNELS in degrees, as smoothed; curves (n_seq,13,101,2); per_sequence (n_seq,13,6), columns
+    KINEMATICS_COLUMNS.  Channel 12, the trunk's inclination, is measured from the camera's vertical: it assumes a level camera."""
+    a3 = np.asarray(joints3d)
+    if a3.ndim != 3 or a3.shape[2] != 3 or a3.shape[0] < 1 or a3.shape[1] < 1:
+        raise ValueError(f"joints3d must be (n,J,3) with n, J >= 1, got {a3.shape}")
+    j3 = a3.astype(np.float32).astype(np.float64)
+    n, J = j3.shape[:2]
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != 16 or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be 16 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist)")
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _kin_strides_check(min_stride, max_stride)
+    if np.asarray(events).shape != (n,):
+        raise ValueError(f"events must be ({n},), got {np.asarray(events).shape}")
+    p = [j3[:, i] for i in tab]
+    per_frame = np.full((n, 13), np.nan)
+    with np.errstate(all="ignore"):
+        l, u = p[2] - p[3], p[1] - p[0]
+        c = _kin_cross(l, u)
+        nc, nl = np.sqrt(_kin_dot(c, c)), np.sqrt(_kin_dot(l, l))
+        valid = (nc > 0) & np.isfinite(nc) & (nl > 0) & np.isfinite(nl)
+        f, side = c / np.where(valid, nc, 1.0)[:, None], l / np.where(valid, nl, 1.0)[:, None]
+        w = _kin_cross(f, side)
+        for s in (0, 1):
+            d, sh, g = p[4 + s] - p[2 + s], p[6 + s] - p[4 + s], p[8 + s] - p[6 + s]
+            arm, fore = p[12 + s] - p[10 + s], p[14 + s] - p[12 + s]
+            down, out_d = -_kin_dot(d, w), _kin_dot(d, side)
+            per_frame[:, 0 + s] = np.where(valid, gait_atan2(_kin_dot(d, f), down) * KINEMATICS_DEGREES, np.nan)
+            per_frame[:, 2 + s] = np.where(valid, gait_atan2(-out_d if s else out_d, down) * KINEMATICS_DEGREES, np.nan)
+            per_frame[:, 4 + s] = _kin_bend(d, sh)
+            per_frame[:, 6 + s] = _kin_bend(sh, g) - 90.0
+            per_frame[:, 8 + s] = np.where(valid, gait_atan2(_kin_dot(arm, f), -_kin_dot(arm, w)) * KINEMATICS_DEGREES, np.nan)
+            per_frame[:, 10 + s] = _kin_bend(arm, fore)
+        per_frame[:, 12] = np.where(valid, _kin_bend(u, np.broadcast_to(np.array([0.0, -1.0, 0.0]), u.shape)), np.nan)
+        if sigma > 0:
+            a = 0
+            for T in lengths:
+                for k in range(13):
+                    per_frame[a:a + T, k] = gauss_filter1d(per_frame[a:a + T, k].copy(), sigma)
+                a += T
+    out = gait_cycles(per_frame, events, lengths, min_stride, max_stride)
+    out["per_frame"] = per_frame
+    return out
 
 
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
