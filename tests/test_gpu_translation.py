@@ -209,7 +209,7 @@ def test_refusals_leave_the_outputs_untouched(model, pkg):
     nan, inf = float("nan"), float("inf")
     for kw, word in ((dict(n_pairs=0), b"n_pairs 0"), (dict(pairs=[0, 0] * 65), b"n_pairs 65"), (dict(pairs=[25, 0]), b"pairs[0][0] = 25"),
                      (dict(pairs=[0, 0, 3, 25]), b"pairs[1][1] = 25"), (dict(pairs=[-1, 0]), b"pairs[0][0] = -1"), (dict(K3=18), b"outside [0, K3 = 18)"),
-                     (dict(offsets=(0, 5, 3)), b"ascend"), (dict(offsets=(0, 4, 4)), b"empty"), (dict(offsets=(1, 8)), b"not 0"), (dict(offsets=(0, 3, 7)), b"end at 7"),
+                     (dict(offsets=(0, 5, 3)), b"increase"), (dict(offsets=(0, 4, 4)), b"empty"), (dict(offsets=(1, 8)), b"not 0"), (dict(offsets=(0, 3, 7)), b"end at 7"),
                      (dict(frames=9), b"end at 8"), (dict(n_seq=0), b"n_seq 0"), (dict(cam=(0.0, 1.0, 1.0, 1.0, 1.0, 1.0)), b"focal length of sequence 0"),
                      (dict(cam=(1.0, 1.0, 1.0, -2.0, 1.0, 1.0)), b"focal length of sequence 1"), (dict(cam=(nan, 1.0, 1.0, 1.0, 1.0, 1.0)), b"focal length"),
                      (dict(cam=(inf, 1.0, 1.0, 1.0, 1.0, 1.0)), b"focal length"), (dict(cam=(1.0, nan, 1.0, 1.0, 1.0, 1.0)), b"centre of sequence 0"),

@@ -1,24 +1,10 @@
 // Boxes from 2D joints behind the C ABI (batch_generation.py:39-93, get_bbox_from_joints2d; kernels: bbox_kernels.hip, rules: DESIGN 4.7):
-// grnet_bbox_from_joints2d, the hook that runs the 1-medoid alone, and the scratch both keep on the handle.  Neither reads a weight or the arena.
+// grnet_bbox_from_joints2d and the hook that runs the 1-medoid alone.  Neither reads a weight or the arena; their scratch is bbox_ws (grow_scratch).
 #include "grnet_impl.h"
 
 namespace {
 
 constexpr int kMedoidMaxPoints = kBboxMaxFrames * kBboxMaxJoints;      // points of one sequence
-
-size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// "" or what is wrong with n_seq + 1 offsets of sequences lying back to back, each of 1 .. longest units
-std::string offsets_error(const int32_t* off, int n_seq, int longest, int unit, const char* what) {
-    if (off[0] != 0) return std::string(what) + "[0] = " + std::to_string(off[0]) + ", not 0";
-    for (int q = 0; q < n_seq; ++q) {
-        const long long len = (long long)off[q + 1] - off[q];
-        if (len < 1) return "sequence " + std::to_string(q) + " is empty or its offsets do not increase (" + std::to_string(off[q]) + ", " + std::to_string(off[q + 1]) + ")";
-        if (len > longest) return "sequence " + std::to_string(q) + " has " + std::to_string(len) + " entries, more than " + std::to_string(longest);
-    }
-    if ((long long)off[n_seq] * unit > 0x7fffffffLL) return std::to_string((long long)off[n_seq] * unit) + " points in one call no longer fit 31 bits";
-    return "";
-}
 
 // Column splits of a call: enough workgroups for four per CU (one 400-frame sequence is 40 row tiles), a split keeping at least one row tile's worth of columns
 int choose_splits(const std::vector<int>& point_off) {
@@ -51,18 +37,6 @@ hipError_t run_medoid(const float* points, const std::vector<int>& point_off, in
 
 }  // namespace
 
-// Scratch of the box calls, grown on demand and kept: a call of a size seen before allocates nothing.  Growing synchronises the device.
-int grnet::bbox_scratch(size_t bytes, char** out) {
-    if (bytes > bbox_ws_bytes) {
-        if (bbox_ws) { (void)hipDeviceSynchronize(); (void)hipFree(bbox_ws); bbox_ws = nullptr; bbox_ws_bytes = 0; }
-        const size_t want = bytes + bytes / 4;
-        if (hipMalloc(&bbox_ws, want) != hipSuccess) { bbox_ws = nullptr; return fail(GRNET_ENOMEM, "box workspace (" + std::to_string(want >> 20) + " MiB)"); }
-        bbox_ws_bytes = want;
-    }
-    *out = static_cast<char*>(bbox_ws);
-    return 0;
-}
-
 extern "C" {
 
 int grnet_bbox_from_joints2d(grnet_t* h, const double* joints_dev, int K, const int32_t* frame_offsets_host, int n_seq, double threshold,
@@ -73,7 +47,7 @@ int grnet_bbox_from_joints2d(grnet_t* h, const double* joints_dev, int K, const 
     if (n_seq < 1) return h->fail(GRNET_EINVAL, name + "n_seq " + std::to_string(n_seq) + " < 1");
     if (!joints_dev || !frame_offsets_host || !bbox_dev) return h->fail(GRNET_EINVAL, name + "null pointer (only medoid_dev may be NULL)");
     if (!std::isfinite(threshold)) return h->fail(GRNET_EINVAL, name + "threshold must be finite");
-    const std::string why = offsets_error(frame_offsets_host, n_seq, kBboxMaxFrames, K, "frame_offsets");
+    const std::string why = offsets_error(frame_offsets_host, n_seq, "frame_offsets", kBboxMaxFrames, K);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why + " (a sequence has 1 .. " + std::to_string(kBboxMaxFrames) + " frames)");
     std::vector<int> point_off(n_seq + 1);
     for (int q = 0; q <= n_seq; ++q) point_off[q] = frame_offsets_host[q] * K;
@@ -102,7 +76,7 @@ int grnet_op_medoid(grnet_t* h, const float* points_dev, const int32_t* point_of
     if (splits < 0 || splits > kMedoidMaxSplits) return h->fail(GRNET_EINVAL, name + "splits " + std::to_string(splits) + " outside [0, " + std::to_string(kMedoidMaxSplits) + "]");
     if (!points_dev || !point_offsets_host || !index_dev || !cost_dev) return h->fail(GRNET_EINVAL, name + "null pointer");
     if (reinterpret_cast<uintptr_t>(points_dev) & 15) return h->fail(GRNET_EINVAL, name + "points_dev must be 16-byte aligned");
-    const std::string why = offsets_error(point_offsets_host, n_seq, kMedoidMaxPoints, 1, "point_offsets");
+    const std::string why = offsets_error(point_offsets_host, n_seq, "point_offsets", kMedoidMaxPoints, 1);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     const std::vector<int> point_off(point_offsets_host, point_offsets_host + n_seq + 1);
     if (!splits) splits = choose_splits(point_off);

@@ -5,8 +5,9 @@
 //   grnet_hooks.cpp    the single-op test and timing hooks
 //   grnet_render.cpp   the mesh overlay: the face table, grnet_render_meshes and its stage hooks; the render workspace
 //   grnet_skeleton.cpp the 3D skeleton view: grnet_render_segments and its two stage hooks, grnet_spin_joints
-//   grnet_bbox.cpp     boxes from 2D joints: grnet_bbox_from_joints2d, its 1-medoid hook and their scratch
-//   grnet_metrics.cpp  pose metrics: grnet_pose_metrics, the Procrustes hook and their scratch
+//   grnet_seq.cpp      shared by the calls over sequences lying back to back: the scratch grower, the entry of the calls that upload a table (seq_call)
+//   grnet_bbox.cpp     boxes from 2D joints: grnet_bbox_from_joints2d and its 1-medoid hook
+//   grnet_metrics.cpp  pose metrics: grnet_pose_metrics and the Procrustes hook
 //   grnet_translation.cpp  the camera-space trajectory: grnet_fit_translation
 //   grnet_track.cpp    per-frame boxes from 2D joints: grnet_track_boxes and its two stage hooks
 //   grnet_gait.cpp     gait events and parameters from the 3D joints: grnet_gait_parameters and its events hook
@@ -24,12 +25,14 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <unordered_map>
 #include <vector>
 
 #include "kernels.h"
+#include "seq_args.h"
 
 namespace grnet_detail {
 using namespace grk;
@@ -178,6 +181,7 @@ struct DeviceBlock {                                        // freed when a hook
 
 using namespace grk;
 using namespace grnet_detail;
+using namespace seq_args;
 
 struct grnet {
     // ------------------------------------------------------------------ the handle: what it was created for, its state, its options
@@ -254,12 +258,13 @@ struct grnet {
     hipEvent_t seg_stage_done[kSegStageSlots] = {};
     unsigned seg_stage_next = 0;
 
-    // grnet_bbox_from_joints2d / grnet_op_medoid: points, heights and the row sums' partials, grown on demand, outside the arena (grnet_bbox.cpp)
+    // grnet_bbox_from_joints2d / grnet_op_medoid: points, heights and the row sums' partials; the calls of seq_call: their table and what lies
+    // behind it.  Grown on demand, outside the arena (grow_scratch)
     void* bbox_ws = nullptr;
     size_t bbox_ws_bytes = 0;
 
-    // grnet_pose_metrics: the sequences' sums and counts (and the per-frame rows when the caller takes none), grown on demand, outside the arena
-    // (grnet_metrics.cpp)
+    // grnet_pose_metrics: the sequences' sums and counts (and the per-frame rows when the caller takes none), grown on demand, outside the arena.
+    // A buffer of its own: a metrics call and a box call on two streams never meet in one
     void* metric_ws = nullptr;
     size_t metric_ws_bytes = 0;
 
@@ -407,8 +412,9 @@ struct grnet {
     void jreg_clear();
     void faces_clear();
     int seg_stage_slot(void** slot, hipEvent_t* done);   // grnet_skeleton.cpp: the next table of the ring, free to be written
-    int bbox_scratch(size_t bytes, char** out);   // grnet_bbox.cpp: bbox_ws of at least this size
-    int metric_scratch(size_t bytes, char** out); // grnet_metrics.cpp: metric_ws of at least this size
+    int grow_scratch(void*& ws, size_t& have, size_t bytes, const char* what, char** out);   // grnet_seq.cpp: ws of at least this size
+    int bbox_scratch(size_t bytes, char** out) { return grow_scratch(bbox_ws, bbox_ws_bytes, bytes, "box workspace", out); }
+    int metric_scratch(size_t bytes, char** out) { return grow_scratch(metric_ws, metric_ws_bytes, bytes, "metric workspace", out); }
     int raster_workspace(const char* who);   // grnet_render.cpp: raster_ws, allocated at the first call of grnet_render_meshes(_ex) or grnet_render_segments
     const Op* nth_conv_op(int pos) const;
     int gru_fault_check();
@@ -419,11 +425,26 @@ struct grnet {
     int clip_limit(int n, const char* tail);
 };
 
-// grnet_track.cpp, shared with grnet_gait.cpp: the first kTrackFront bytes of such a call's scratch hold its table -- the Gaussian's weights
-// (host-made, scipy's), then the n_seq + 1 frame offsets -- uploaded through one slot of the pinned ring, so the copy is enqueued like a kernel.
-constexpr size_t kTrackOffsetsAt = ((size_t)(kTrackMaxRadius + 1) * sizeof(double) + 255) & ~(size_t)255;      // the weights lie in front: the copy ends with the offsets
-constexpr size_t kTrackFront = (kTrackOffsetsAt + (size_t)(kTrackMaxSeqs + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
-struct TrackTable { const int* off; const double* weights; int radius; };      // radius < 0: sigma == 0, no Gaussian
-// "" or what is wrong with n_seq + 1 offsets of sequences of at least one row lying back to back, `unit` values a row
-std::string track_offsets_error(const int32_t* off, int n_seq, long long unit);
-int track_upload_table(grnet* h, const std::string& name, const int32_t* off, int n_seq, double sigma, char* ws, hipStream_t s, TrackTable* t);
+// grnet_seq.cpp: the calls whose kernels read the sequences' offsets and the Gaussian's weights from the device (per-frame boxes, gait, kinematics
+// and their hooks).  The first kSeqFront bytes of such a call's scratch (bbox_ws) hold its table -- the weights (host-made, scipy's), then the
+// n_seq + 1 frame offsets -- uploaded through one slot of the pinned ring, so the copy is enqueued like a kernel.
+constexpr size_t kSeqOffsetsAt = align256((size_t)(kTrackMaxRadius + 1) * sizeof(double));      // the weights lie in front: the copy ends with the offsets
+constexpr size_t kSeqFront = align256(kSeqOffsetsAt + (size_t)(kTrackMaxSeqs + 1) * sizeof(int32_t));
+struct SeqCall {
+    std::optional<DeviceGuard> guard;      // held until the call's launches are enqueued
+    const int* off = nullptr;              // on the device
+    const double* weights = nullptr;       // on the device
+    int radius = -1;                       // < 0: sigma == 0, no Gaussian
+    char* behind = nullptr;                // the call's `extra` bytes of scratch, behind the table
+};
+int seq_call_check(grnet* h, const std::string& name, const int32_t* off, int n_seq, long long unit);      // the two halves of seq_call
+int seq_call_upload(grnet* h, const std::string& name, const int32_t* off, int n_seq, double sigma, size_t extra, hipStream_t s, SeqCall* c);
+inline size_t seq_no_extra(int) { return 0; }      // the `extra` of a call that keeps nothing behind its table
+// The entry of such a call, after its own argument checks: n_seq within [1, kTrackMaxSeqs] and the offsets' rules (seq_args.h, `unit` values per
+// frame), then the device guard, kSeqFront + extra(frames) bytes of scratch and the table, staged and enqueued on `s`.  `extra` is asked for
+// the sizes only once the offsets hold, so it may trust its frame count.
+template <class Extra>
+int seq_call(grnet* h, const std::string& name, const int32_t* off, int n_seq, long long unit, double sigma, hipStream_t s, SeqCall* c, Extra extra) {
+    if (int rc = seq_call_check(h, name, off, n_seq, unit)) return rc;
+    return seq_call_upload(h, name, off, n_seq, sigma, extra(off[n_seq]), s, c);
+}

@@ -1,10 +1,8 @@
-// Pose metrics behind the C ABI (kernels: metric_kernels.hip, rules: DESIGN 4.8): grnet_pose_metrics, the hook that runs the Procrustes rotation
-// alone, and the scratch the handle keeps for them.  Neither reads a weight or the arena.
+// Pose metrics behind the C ABI (kernels: metric_kernels.hip, rules: DESIGN 4.8): grnet_pose_metrics and the hook that runs the Procrustes rotation
+// alone.  Neither reads a weight or the arena; the scratch is metric_ws (grow_scratch).
 #include "grnet_impl.h"
 
 namespace {
-
-size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // "" or what is wrong with `count` indices into J joints
 std::string indices_error(const int32_t* idx, int count, int J, const char* what) {
@@ -14,18 +12,6 @@ std::string indices_error(const int32_t* idx, int count, int J, const char* what
 }
 
 }  // namespace
-
-// Scratch of the metric calls, grown on demand and kept: a call of a size seen before allocates nothing.  Growing synchronises the device.
-int grnet::metric_scratch(size_t bytes, char** out) {
-    if (bytes > metric_ws_bytes) {
-        if (metric_ws) { (void)hipDeviceSynchronize(); (void)hipFree(metric_ws); metric_ws = nullptr; metric_ws_bytes = 0; }
-        const size_t want = bytes + bytes / 4;
-        if (hipMalloc(&metric_ws, want) != hipSuccess) { metric_ws = nullptr; return fail(GRNET_ENOMEM, "metric workspace (" + std::to_string(want >> 20) + " MiB)"); }
-        metric_ws_bytes = want;
-    }
-    *out = static_cast<char*>(metric_ws);
-    return 0;
-}
 
 extern "C" {
 
@@ -48,12 +34,8 @@ int grnet_pose_metrics(grnet_t* h, const float* pred_dev, const float* gt_dev, i
     if (has_verts && V < 1) return h->fail(GRNET_EINVAL, name + "V " + std::to_string(V) + " < 1");
     if (has_verts && 3LL * V > 0x7fffffffLL) return h->fail(GRNET_EINVAL, name + "V " + std::to_string(V) + ": 3 V no longer fits 31 bits");
     if (!std::isfinite(unit)) return h->fail(GRNET_EINVAL, name + "unit must be finite");
-    if (frame_offsets_host[0] != 0) return h->fail(GRNET_EINVAL, name + "frame_offsets[0] = " + std::to_string(frame_offsets_host[0]) + ", not 0");
-    for (int q = 0; q < n_seq; ++q)
-        if (frame_offsets_host[q + 1] <= frame_offsets_host[q])
-            return h->fail(GRNET_EINVAL, name + "sequence " + std::to_string(q) + " is empty or its offsets do not increase (" + std::to_string(frame_offsets_host[q]) +
-                                             ", " + std::to_string(frame_offsets_host[q + 1]) + ")");
-    std::string why = select_host ? indices_error(select_host, n_select, J, "select") : "";
+    std::string why = offsets_error(frame_offsets_host, n_seq, "frame_offsets", 0, 0);      // no 31-bit rule: the kernels index with size_t
+    if (why.empty() && select_host) why = indices_error(select_host, n_select, J, "select");
     if (why.empty() && root_host) why = indices_error(root_host, n_root, J, "root");
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
 

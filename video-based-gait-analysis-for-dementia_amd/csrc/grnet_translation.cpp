@@ -23,11 +23,8 @@ int grnet_fit_translation(grnet_t* h, const float* joints3d_dev, int K3, const f
     }
     if (n_seq < 1) return h->fail(GRNET_EINVAL, name + "n_seq " + num(n_seq) + " < 1");
     if (frames < 1) return h->fail(GRNET_EINVAL, name + "frames " + num(frames) + " < 1");
-    if (frame_offsets_host[0] != 0) return h->fail(GRNET_EINVAL, name + "frame_offsets[0] = " + num(frame_offsets_host[0]) + ", not 0");
-    for (int q = 0; q < n_seq; ++q)
-        if (frame_offsets_host[q + 1] <= frame_offsets_host[q])
-            return h->fail(GRNET_EINVAL, name + "sequence " + num(q) + " is empty or its offsets do not ascend (" + num(frame_offsets_host[q]) + ", " +
-                                             num(frame_offsets_host[q + 1]) + ")");
+    const std::string why = offsets_error(frame_offsets_host, n_seq, "frame_offsets", 0, 0);      // no 31-bit rule: the kernels index with size_t
+    if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     if (frame_offsets_host[n_seq] != frames)
         return h->fail(GRNET_EINVAL, name + "the offsets end at " + num(frame_offsets_host[n_seq]) + ", not at the " + num(frames) + " frames");
     for (int q = 0; q < n_seq; ++q) {

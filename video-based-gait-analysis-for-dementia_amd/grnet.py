@@ -34,6 +34,11 @@ _TOLERATED_SMPL_KEYS = ("vertex_joint_selector.extra_joints_idxs", "betas", "glo
                         "body_pose", "transl")
 
 
+def _i32p(a):
+    """The int32 numpy array `a` as the C ABI takes a `const int32_t*`."""
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 def _np32(t):
     if torch.is_tensor(t):
         t = t.detach().cpu().numpy()
@@ -145,6 +150,12 @@ class GRNet:
         self.focal_length = focal_length
         if pretrained_pare:
             self.load_pare_dict(pretrained_pare)
+
+    def _stream(self, device=None):
+        """The current stream of `device` (None: the handle's) as the C ABI takes it."""
+        if device is None:
+            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
     # ------------------------------------------------------------------ weights
     def _load_tensor(self, key, value):
@@ -297,7 +308,7 @@ class GRNet:
         n = v.shape[0]
         jout = max(self.joint_regressor_rows(), 0)
         out = torch.empty(n, jout, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         for s in range(0, max(n, 1), self.max_frames):
             m = min(self.max_frames, n - s)
             rc = self._lib.grnet_regress_joints(self._h, v[s:s + m].data_ptr(), m, out[s:s + m].data_ptr() if jout else None, stream)
@@ -340,7 +351,7 @@ class GRNet:
                   "features": (480, 56, 56), "part_attn": (25, 56, 56), "smpl_feats": (128, 56, 56)}
         for k in extras:
             out[k] = new(n, *shapes[k])
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = self._stream(dev)
         for s in range(0, n, self.max_frames):
             m = min(self.max_frames, n - s)
             o = _lib.Outputs()
@@ -386,7 +397,7 @@ class GRNet:
             setattr(o, k, v.data_ptr())
         for k, v in gait.items():
             setattr(g, k, v.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = self._stream(dev)
         rc = self._lib.grnet_gait_correct(self._h, plf.data_ptr(), csf.data_ptr(), cam.data_ptr(), cam.shape[1], bb.data_ptr(), ci.data_ptr(),
                                           b, t, C.byref(o), C.byref(g), stream)
         _lib.check(self._lib, self._h, rc, "grnet_gait_correct")
@@ -404,7 +415,7 @@ class GRNet:
                 rc = self._lib.grnet_set_tuning(self._h, int(n_frames), f.read().encode())
             if rc == 0:
                 return self
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_tune(self._h, int(n_frames), stream, int(level)), "grnet_tune")
         if cache:
             buf = C.create_string_buffer(1 << 16)
@@ -451,7 +462,7 @@ class GRNet:
         shape measured ALONE (grnet_time_conv: HIP events around `reps` back-to-back launches), algorithmic and executed FLOPs.
         Returns a list of dicts sorted by total time: name, launches, total_us, avg_us, gflop (algorithmic, per step), executed_gflop."""
         self.finalize()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         convs = self.describe_convs()
         timed, rows = {}, {}
         for pos, c in enumerate(convs):
@@ -525,7 +536,7 @@ class GRNet:
         self.finalize()
         x = frames.to(self.device, torch.float32).contiguous()
         buf = C.create_string_buffer(1 << 18)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_op_timeline(self._h, x.data_ptr(), x.shape[0], stream, buf, len(buf))
         if rc < 0:
             _lib.check(self._lib, self._h, rc, "grnet_op_timeline")
@@ -537,7 +548,7 @@ class GRNet:
 
     def time_convs(self, n_frames):
         ms = C.c_float()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_time_convs(self._h, n_frames, stream, C.byref(ms)), "grnet_time_convs")
         return ms.value
 
@@ -555,7 +566,7 @@ class GRNet:
         verts = torch.empty(n, 6890, 3, dtype=torch.float32, device=dev)
         kp3d = torch.empty(n, 29, 3, dtype=torch.float32, device=dev)
         kp2d = torch.empty(n, 29, 2, dtype=torch.float32, device=dev) if cam is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = self._stream(dev)
         for s0 in range(0, n, self.max_frames):
             m = min(self.max_frames, n - s0)
             rc = self._lib.grnet_smpl_forward(self._h, b[s0:].data_ptr(), r[s0:].data_ptr(), c[s0:].data_ptr() if c is not None else None,
@@ -582,7 +593,7 @@ class GRNet:
             raise ValueError("bboxes must be (n,4) and match the number of frames")
         hgt, wid = images.shape[-3], images.shape[-2]
         out = torch.empty(n, 3, 224, 224, dtype=torch.float32, device=images.device)
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        stream = self._stream(images.device)
         if mode == "cv2":
             from .pipeline import cv_crop_maps
             maps = torch.from_numpy(cv_crop_maps(bb_host, scale)).to(images.device, non_blocking=True)
@@ -601,7 +612,7 @@ class GRNet:
     def debug_tensor(self, name, n_frames):
         """Named intermediate of the last forward as an (n,C,H,W) tensor (see grnet_debug_tensor)."""
         shp = (C.c_int64 * 3)()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_debug_tensor(self._h, name.encode(), n_frames, None, shp, stream),
                    "grnet_debug_tensor")
         out = torch.empty(n_frames, shp[0], shp[1], shp[2], dtype=torch.float32, device=self.device)
@@ -617,7 +628,7 @@ class GRNet:
 
     def arena_fill(self, pattern):
         """Diagnostic: fill the arena behind its zero block with a 32-bit pattern on the current stream (grnet_arena_fill)."""
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_arena_fill(self._h, int(pattern) & 0xffffffff, stream), "grnet_arena_fill")
 
     def tsattn_plan(self, n):
@@ -676,7 +687,7 @@ class GRNet:
         y = torch.empty(b, 3, dtype=torch.float32, device=x.device)
         ph = torch.empty(b, t, 4, dtype=torch.float32, device=x.device)
         xc = torch.empty(b, t, 3072, dtype=torch.float32, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_gru_forward(self._h, x.data_ptr(), cp.data_ptr(), b, t, y.data_ptr(), ph.data_ptr(),
                                          xc.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_gru_forward")
@@ -692,7 +703,7 @@ class GRNet:
         x = x.to(torch.float32).contiguous()
         xs = xs.to(torch.float32).contiguous()
         y = torch.empty(b, n, 3072, dtype=torch.float32, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_tsattn_forward(self._h, x.data_ptr(), xs.data_ptr(), b, n, y.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_tsattn_forward")
         return y
@@ -710,7 +721,7 @@ class GRNet:
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         out = {"theta": new(n, 85), "verts": new(n, 6890, 3), "kp_2d": new(n, 29, 2), "kp_3d": new(n, 29, 3),
                "rotmat": new(n, 24, 3, 3), "pred_rot6d": new(n, 24, 6)}
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = self._stream(dev)
         for s0 in range(0, n, self.max_frames):
             m = min(self.max_frames, n - s0)
             o = _lib.Outputs()
@@ -723,7 +734,7 @@ class GRNet:
     def op_rot6d_to_rotmat(self, x):
         x = x.to(self.device, torch.float32).reshape(-1, 6).contiguous()
         out = torch.empty(x.shape[0], 3, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_op_rot6d_to_rotmat(self._h, x.data_ptr(), x.shape[0], out.data_ptr(), stream),
                    "grnet_op_rot6d_to_rotmat")
         return out
@@ -731,7 +742,7 @@ class GRNet:
     def op_rotmat_to_aa(self, R):
         R = R.to(self.device, torch.float32).reshape(-1, 9).contiguous()
         out = torch.empty(R.shape[0], 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_op_rotmat_to_aa(self._h, R.data_ptr(), R.shape[0], out.data_ptr(), stream),
                    "grnet_op_rotmat_to_aa")
         return out
@@ -760,7 +771,7 @@ class GRNet:
         in place -> (T,72) device tensor, bit-identical to the reference's float32 numpy arithmetic."""
         x, ptr, ld = self._pose_rows(x, "x")
         out = torch.empty(x.shape[0], 72, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_op_one_euro(self._h, ptr, ld, x.shape[0], min_cutoff, beta, d_cutoff, out.data_ptr(), stream),
                    "grnet_op_one_euro")
         return out
@@ -769,7 +780,7 @@ class GRNet:
         """Axis-angle (...,3) -> (m,3,3), smplx's batch_rodrigues (grnet_op_aa_to_rotmat)."""
         aa = torch.as_tensor(aa).to(self.device, torch.float32).reshape(-1, 3).contiguous()
         out = torch.empty(aa.shape[0], 3, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         _lib.check(self._lib, self._h, self._lib.grnet_op_aa_to_rotmat(self._h, aa.data_ptr(), aa.shape[0], out.data_ptr(), stream),
                    "grnet_op_aa_to_rotmat")
         return out
@@ -793,7 +804,7 @@ class GRNet:
         pose_hat = torch.empty(T, 72, dtype=torch.float32, device=self.device)
         verts = torch.empty(T, 6890, 3, dtype=torch.float32, device=self.device) if return_verts else None
         out = torch.empty(T, nj, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_smooth_pose(self._h, ptr, ld, b0.data_ptr(), T, min_cutoff, beta, kind, pose_hat.data_ptr(),
                                          verts.data_ptr() if return_verts else None, out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_smooth_pose")
@@ -826,7 +837,7 @@ class GRNet:
         if not (c.shape[0] == col.shape[0] == idx.shape[0] == n):
             raise ValueError(f"verts, cams, colours and image_index disagree on n: {n}, {c.shape[0]}, {col.shape[0]}, {idx.shape[0]}")
         Mh = None if M is None else np.ascontiguousarray(np.asarray(M, np.float32).reshape(9))
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_render_meshes_ex(self._h, v.data_ptr(), n, c.data_ptr(), col.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
                                               Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, images.data_ptr(), F, H, W,
                                               self.RENDER_WIREFRAME if wireframe else 0, stream)
@@ -844,7 +855,7 @@ class GRNet:
         xy = torch.empty(V, 2, dtype=torch.int32, device=self.device)
         z = torch.empty(V, dtype=torch.float32, device=self.device)
         nrm = torch.empty(V, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_op_raster_setup(self._h, v.data_ptr(), V, f.ctypes.data_as(C.c_void_p), f.shape[0], c.data_ptr(),
                                              Mh.ctypes.data_as(C.c_void_p) if Mh is not None else None, H, W, xy.data_ptr(), z.data_ptr(), nrm.data_ptr(),
                                              stream)
@@ -856,7 +867,7 @@ class GRNet:
         z = torch.as_tensor(z).to(self.device, torch.float32).reshape(-1).contiguous()
         f = np.ascontiguousarray(np.asarray(faces).reshape(-1, 3), dtype=np.int32)
         out = torch.empty(H, W, dtype=torch.int32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = getattr(self._lib, entry)(self._h, xy.data_ptr(), z.data_ptr(), xy.shape[0], f.ctypes.data_as(C.c_void_p), f.shape[0], H, W, out.data_ptr(),
                                        stream)
         _lib.check(self._lib, self._h, rc, entry)
@@ -882,23 +893,36 @@ class GRNet:
         off[1:] = np.cumsum(np.asarray(lengths, np.int64))
         return off
 
+    def _rows_input(self, x, what, trailing, dtype, finite=False):
+        """`x` (numpy or torch) as a contiguous device tensor of `dtype` and shape (n,) + trailing with n >= 1; a None in `trailing` stands for any
+        size >= 1 (how many joints a call takes is the C ABI's to say).  finite: ValueError on a NaN or an infinity."""
+        t = torch.as_tensor(x)
+        if t.dim() != 1 + len(trailing) or t.shape[0] < 1 or any(have < 1 if want is None else have != want for have, want in zip(t.shape[1:], trailing)):
+            shape = ",".join(["n"] + ["K" if want is None else str(want) for want in trailing])
+            raise ValueError(f"{what} must be ({shape}{',' if not trailing else ''}) with n >= 1, got {tuple(t.shape)}")
+        if finite and not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{what} has a non-finite entry")
+        return t.to(self.device, dtype).contiguous()
+
+    @staticmethod
+    def _whole_frames(**values):
+        """ValueError unless every named value (window, min_stride, max_stride) is a whole number of frames."""
+        for name, v in values.items():
+            if int(v) != v:
+                raise ValueError(f"{name} {v} must be a whole number of frames")
+
     def bbox_from_joints2d(self, joints2d, lengths=None, threshold=0.1, return_index=False):
         """One box per sequence from 2D joints, get_bbox_from_joints2d(smooth=False) on the device (grnet_bbox_from_joints2d).
         joints2d (T,K,3) rows (x, y, score) in pixels, or (sum T,K,3) with the sequences' `lengths` -- numpy or torch, taken as float64.
         Returns a float64 device tensor (n_seq,4) = [cx, cy, nw, nh]; return_index: also the medoids' indices (n_seq,) int32 into their
         sequences' T K points.  Works before finalize(): no weight is read.  ValueError on non-finite input."""
-        j = torch.as_tensor(joints2d)
-        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
-            raise ValueError(f"joints2d must be (T,K,3) with T >= 1, got {tuple(j.shape)}")
-        if not bool(torch.isfinite(j).all()):
-            raise ValueError("joints2d has a non-finite entry")
-        j = j.to(self.device, torch.float64).contiguous()
+        j = self._rows_input(joints2d, "joints2d", (None, 3), torch.float64, finite=True)
         off = self._sequence_offsets(j.shape[0], lengths, "joints2d")
         n_seq = len(off) - 1
         box = torch.empty(n_seq, 4, dtype=torch.float64, device=self.device)
         index = torch.empty(n_seq, dtype=torch.int32, device=self.device) if return_index else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_bbox_from_joints2d(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, float(threshold),
+        stream = self._stream()
+        rc = self._lib.grnet_bbox_from_joints2d(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, float(threshold),
                                                 box.data_ptr(), index.data_ptr() if return_index else None, stream)
         _lib.check(self._lib, self._h, rc, "grnet_bbox_from_joints2d")
         return (box, index) if return_index else box
@@ -916,22 +940,13 @@ class GRNet:
         n_seq = len(off) - 1
         index = torch.empty(n_seq, dtype=torch.int32, device=self.device)
         cost = torch.empty(n_seq, dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_op_medoid(self._h, p4.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, int(splits), index.data_ptr(),
+        stream = self._stream()
+        rc = self._lib.grnet_op_medoid(self._h, p4.data_ptr(), _i32p(off), n_seq, int(splits), index.data_ptr(),
                                        cost.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_medoid")
         return index, cost
 
     # ------------------------------------------------------------------ pose metrics
-    def _metric_input(self, x, what, width=None):
-        """A finite (n,width,3) float32 device tensor of `x` (numpy or torch)."""
-        t = torch.as_tensor(x)
-        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1 or (width is not None and t.shape[1] != width):
-            raise ValueError(f"{what} must be (n,{'J' if width is None else width},3) with n >= 1, got {tuple(t.shape)}")
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{what} has a non-finite entry")
-        return t.to(self.device, torch.float32).contiguous()
-
     def pose_metrics(self, pred_joints, gt_joints, lengths=None, root=None, select=None, pred_verts=None, gt_verts=None, unit=1000.0,
                      return_transform=False):
         """MPJPE, PA-MPJPE, PVE, acceleration and acceleration error on the device (grnet_pose_metrics; the definitions: DESIGN 4.8).
@@ -943,8 +958,8 @@ class GRNet:
         per_sequence (n_seq,5) and total (5,): the means over the defined entries; return_transform: also transform (n,13) = [s, R row-major,
         t] of the Procrustes alignment, in the inputs' units.  Works before finalize(): no weight is read.  Nothing synchronises.  ValueError
         on non-finite input."""
-        p = self._metric_input(pred_joints, "pred_joints")
-        g = self._metric_input(gt_joints, "gt_joints")
+        p = self._rows_input(pred_joints, "pred_joints", (None, 3), torch.float32, finite=True)
+        g = self._rows_input(gt_joints, "gt_joints", (None, 3), torch.float32, finite=True)
         if p.shape != g.shape:
             raise ValueError(f"pred_joints and gt_joints differ in shape: {tuple(p.shape)}, {tuple(g.shape)}")
         if (pred_verts is None) != (gt_verts is None):
@@ -953,8 +968,8 @@ class GRNet:
         pv = gv = None
         V = 0
         if pred_verts is not None:
-            pv = self._metric_input(pred_verts, "pred_verts")
-            gv = self._metric_input(gt_verts, "gt_verts")
+            pv = self._rows_input(pred_verts, "pred_verts", (None, 3), torch.float32, finite=True)
+            gv = self._rows_input(gt_verts, "gt_verts", (None, 3), torch.float32, finite=True)
             if pv.shape != gv.shape or pv.shape[0] != n:
                 raise ValueError(f"pred_verts and gt_verts must both be ({n},V,3), got {tuple(pv.shape)} and {tuple(gv.shape)}")
             V = pv.shape[1]
@@ -965,16 +980,15 @@ class GRNet:
             return np.ascontiguousarray(np.asarray(v, np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
         sel_keep = None if select is None else indices(select)
         root_keep = None if root is None or len(root) == 0 else indices(root)
-        i32p = C.POINTER(C.c_int32)
         out = {"per_frame": torch.empty(n, 5, dtype=torch.float64, device=self.device),
                "per_sequence": torch.empty(n_seq, 5, dtype=torch.float64, device=self.device),
                "total": torch.empty(5, dtype=torch.float64, device=self.device)}
         if return_transform:
             out["transform"] = torch.empty(n, 13, dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_pose_metrics(self._h, p.data_ptr(), g.data_ptr(), J, off.ctypes.data_as(i32p), n_seq,
-                                          sel_keep.ctypes.data_as(i32p) if sel_keep is not None else None, 0 if sel_keep is None else sel_keep.shape[0],
-                                          root_keep.ctypes.data_as(i32p) if root_keep is not None else None, 0 if root_keep is None else root_keep.shape[0],
+        stream = self._stream()
+        rc = self._lib.grnet_pose_metrics(self._h, p.data_ptr(), g.data_ptr(), J, _i32p(off), n_seq,
+                                          _i32p(sel_keep) if sel_keep is not None else None, 0 if sel_keep is None else sel_keep.shape[0],
+                                          _i32p(root_keep) if root_keep is not None else None, 0 if root_keep is None else root_keep.shape[0],
                                           pv.data_ptr() if pv is not None else None, gv.data_ptr() if gv is not None else None, V, float(unit),
                                           out["per_frame"].data_ptr(), out["per_sequence"].data_ptr(), out["total"].data_ptr(),
                                           out["transform"].data_ptr() if return_transform else None, stream)
@@ -989,7 +1003,7 @@ class GRNet:
             raise ValueError("K must hold at least one 3x3 matrix")
         R = torch.empty(k.shape[0], 9, dtype=torch.float64, device=self.device)
         sigma = torch.empty(k.shape[0], 3, dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_op_procrustes(self._h, k.data_ptr(), k.shape[0], R.data_ptr(), sigma.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_procrustes")
         return R.reshape(-1, 3, 3), sigma
@@ -1006,12 +1020,8 @@ class GRNet:
         frames, the nearest fitted t outside them); per_sequence (n_seq,4) = [fitted, filled, mean reproj, path length of joint `root`].
         Non-finite values are not refused: a dead confidence drops the pair, anything else ends in status 2.  Works before finalize(): no
         weight is read.  Nothing synchronises."""
-        def joints(x, what):
-            t = torch.as_tensor(x)
-            if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-                raise ValueError(f"{what} must be (n,K,3) with n, K >= 1, got {tuple(t.shape)}")
-            return t.to(self.device, torch.float32).contiguous()
-        j3, j2 = joints(joints3d, "joints3d"), joints(joints2d, "joints2d")
+        j3 = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        j2 = self._rows_input(joints2d, "joints2d", (None, 3), torch.float32)
         n = j3.shape[0]
         if j2.shape[0] != n:
             raise ValueError(f"joints3d has {n} frames and joints2d {j2.shape[0]}")
@@ -1029,9 +1039,9 @@ class GRNet:
             raise ValueError(f"focal_length must be one number or {n_seq} of them, centre (cx, cy) or ({n_seq},2)") from None
         out = {"per_frame": torch.empty(n, 6, dtype=torch.float64, device=self.device),
                "per_sequence": torch.empty(n_seq, 4, dtype=torch.float64, device=self.device)}
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_fit_translation(self._h, j3.data_ptr(), j3.shape[1], j2.data_ptr(), j2.shape[1], n, off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq,
-                                             table.ctypes.data_as(C.POINTER(C.c_int32)), table.shape[0], cam.ctypes.data_as(C.POINTER(C.c_double)),
+        stream = self._stream()
+        rc = self._lib.grnet_fit_translation(self._h, j3.data_ptr(), j3.shape[1], j2.data_ptr(), j2.shape[1], n, _i32p(off), n_seq,
+                                             _i32p(table), table.shape[0], cam.ctypes.data_as(C.POINTER(C.c_double)),
                                              float(conf_threshold), int(min_joints), int(root), int(bool(fill)), out["per_frame"].data_ptr(),
                                              out["per_sequence"].data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_fit_translation")
@@ -1047,34 +1057,29 @@ class GRNet:
         2 outside [start, end), 3 inside but without a positive finite smoothed scale (2 and 3: a box of zeros); range (n_seq,2) int32
         [start, end), [-1, 0) without any detection.  Non-finite joints are not refused: their frame counts as undetected.  Works before
         finalize(): no weight is read.  Nothing synchronises."""
-        j = torch.as_tensor(joints2d)
-        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
-            raise ValueError(f"joints2d must be (T,K,3) with T >= 1, got {tuple(j.shape)}")
+        j = self._rows_input(joints2d, "joints2d", (None, 3), torch.float64)
         if pad not in _lib.TRACK_PAD:
             raise ValueError(f"pad must be 'zero' or 'edge', got {pad!r}")
-        j = j.to(self.device, torch.float64).contiguous()
         n = j.shape[0]
         off = self._sequence_offsets(n, lengths, "joints2d")
         n_seq = len(off) - 1
         out = {"boxes": torch.empty(n, 4, dtype=torch.float64, device=self.device), "status": torch.empty(n, dtype=torch.int32, device=self.device),
                "range": torch.empty(n_seq, 2, dtype=torch.int32, device=self.device)}
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_track_boxes(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, float(vis_thresh), int(kernel_size),
+        stream = self._stream()
+        rc = self._lib.grnet_track_boxes(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, float(vis_thresh), int(kernel_size),
                                          float(sigma), _lib.TRACK_PAD[pad], out["boxes"].data_ptr(), out["status"].data_ptr(), out["range"].data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_track_boxes")
         return out
 
     def _op_filter1d(self, x, lengths):
-        x = torch.as_tensor(x).to(self.device, torch.float64).contiguous()
-        if x.dim() != 1 or x.shape[0] < 1:
-            raise ValueError(f"x must be (n,) with n >= 1, got {tuple(x.shape)}")
+        x = self._rows_input(x, "x", (), torch.float64)
         off = self._sequence_offsets(x.shape[0], lengths, "x")
-        return x, off, torch.empty_like(x), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return x, off, torch.empty_like(x), self._stream()
 
     def op_median1d(self, x, lengths=None, kernel_size=11, pad="zero"):
         """The median of track_boxes alone (grnet_op_median1d): x (n,) float64, one column or `lengths` of them lying back to back -> (n,) on the device."""
         x, off, out, stream = self._op_filter1d(x, lengths)
-        rc = self._lib.grnet_op_median1d(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, int(kernel_size), _lib.TRACK_PAD[pad],
+        rc = self._lib.grnet_op_median1d(self._h, x.data_ptr(), _i32p(off), len(off) - 1, int(kernel_size), _lib.TRACK_PAD[pad],
                                          out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_median1d")
         return out
@@ -1082,7 +1087,7 @@ class GRNet:
     def op_gauss1d(self, x, lengths=None, sigma=3.0):
         """The Gaussian of track_boxes alone (grnet_op_gauss1d): x (n,) float64, one column or `lengths` of them lying back to back -> (n,) on the device."""
         x, off, out, stream = self._op_filter1d(x, lengths)
-        rc = self._lib.grnet_op_gauss1d(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, float(sigma), out.data_ptr(), stream)
+        rc = self._lib.grnet_op_gauss1d(self._h, x.data_ptr(), _i32p(off), len(off) - 1, float(sigma), out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_gauss1d")
         return out
 
@@ -1096,10 +1101,7 @@ class GRNet:
         events.  Returns a dict of device tensors: per_frame (n,7) float64 [hL, hR, tL, tR, wd, step_length, step_width]; events (n,) int32, bit 0 heel
         strike left, 1 heel strike right, 2 toe-off left, 3 toe-off right; per_sequence (n_seq,18) float64.  Nothing is refused on the data: a
         degenerate frame has NaN signals and no events near it.  Works before finalize(): no weight is read.  Nothing synchronises."""
-        j = torch.as_tensor(joints3d)
-        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
-            raise ValueError(f"joints3d must be (T,J,3) with T >= 1, got {tuple(j.shape)}")
-        j = j.to(self.device, torch.float32).contiguous()
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
         table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
         if table.size != 8:
@@ -1109,14 +1111,13 @@ class GRNet:
             t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
             if tuple(t.shape) != (n, 3):
                 raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
-        if int(window) != window:
-            raise ValueError(f"window {window} must be a whole number of frames")
+        self._whole_frames(window=window)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
         out = {"per_frame": torch.empty(n, 7, dtype=torch.float64, device=self.device), "events": torch.empty(n, dtype=torch.int32, device=self.device),
                "per_sequence": torch.empty(n_seq, 18, dtype=torch.float64, device=self.device)}
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_gait_parameters(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, table.ctypes.data_as(C.POINTER(C.c_int32)),
+        stream = self._stream()
+        rc = self._lib.grnet_gait_parameters(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, _i32p(table),
                                              None if t is None else t.data_ptr(), float(fps), float(sigma), int(window), float(min_excursion),
                                              out["per_frame"].data_ptr(), out["events"].data_ptr(), out["per_sequence"].data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_gait_parameters")
@@ -1125,15 +1126,12 @@ class GRNet:
     def op_gait_events(self, signals, lengths=None, window=5, min_excursion=0.05):
         """The events rule of gait_parameters alone (grnet_op_gait_events): signals (n,4) float64 [hL, hR, tL, tR], one sequence or `lengths` of them
         lying back to back -> (n,) int32 events on the device."""
-        x = torch.as_tensor(signals).to(self.device, torch.float64).contiguous()
-        if x.dim() != 2 or x.shape[1] != 4 or x.shape[0] < 1:
-            raise ValueError(f"signals must be (n,4) with n >= 1, got {tuple(x.shape)}")
-        if int(window) != window:
-            raise ValueError(f"window {window} must be a whole number of frames")
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        self._whole_frames(window=window)
         off = self._sequence_offsets(x.shape[0], lengths, "signals")
         out = torch.empty(x.shape[0], dtype=torch.int32, device=self.device)
-        rc = self._lib.grnet_op_gait_events(self._h, x.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), len(off) - 1, int(window), float(min_excursion),
-                                            out.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        rc = self._lib.grnet_op_gait_events(self._h, x.data_ptr(), _i32p(off), len(off) - 1, int(window), float(min_excursion),
+                                            out.data_ptr(), self._stream())
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_events")
         return out
 
@@ -1147,10 +1145,7 @@ class GRNet:
         (1 <= min <= max <= 4096) on which a channel is finite is used for it.  Returns a dict of device tensors: per_frame (n,13) float64 degrees;
         curves (n_seq,13,101,2) float64, mean and SD of the cycle curve; per_sequence (n_seq,13,6) float64.  Channel 12 assumes a level camera.
         Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
-        j = torch.as_tensor(joints3d)
-        if j.dim() != 3 or j.shape[2] != 3 or j.shape[0] < 1:
-            raise ValueError(f"joints3d must be (T,J,3) with T >= 1, got {tuple(j.shape)}")
-        j = j.to(self.device, torch.float32).contiguous()
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
         ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
         if tuple(ev.shape) != (n,):
@@ -1158,15 +1153,14 @@ class GRNet:
         table = np.asarray(_lib.KINEMATICS_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
         if table.size != 16:
             raise ValueError(f"joints must name 16 joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist), got {table.size}")
-        if int(min_stride) != min_stride or int(max_stride) != max_stride:
-            raise ValueError("min_stride and max_stride must be whole numbers of frames")
+        self._whole_frames(min_stride=min_stride, max_stride=max_stride)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
         out = {"per_frame": torch.empty(n, 13, dtype=torch.float64, device=self.device),
                "curves": torch.empty(n_seq, 13, 101, 2, dtype=torch.float64, device=self.device),
                "per_sequence": torch.empty(n_seq, 13, 6, dtype=torch.float64, device=self.device)}
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.grnet_gait_kinematics(self._h, j.data_ptr(), j.shape[1], off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, table.ctypes.data_as(C.POINTER(C.c_int32)),
+        stream = self._stream()
+        rc = self._lib.grnet_gait_kinematics(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, _i32p(table),
                                              ev.data_ptr(), float(sigma), int(min_stride), int(max_stride), out["per_frame"].data_ptr(), out["curves"].data_ptr(),
                                              out["per_sequence"].data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_gait_kinematics")
@@ -1175,20 +1169,17 @@ class GRNet:
     def op_gait_cycles(self, angles, events, lengths=None, min_stride=8, max_stride=60):
         """The cycle stage of gait_kinematics alone (grnet_op_gait_cycles): angles (n,13) float64 and events (n,) int32, one sequence or `lengths` of
         them lying back to back -> {curves (n_seq,13,101,2), per_sequence (n_seq,13,6)} on the device."""
-        x = torch.as_tensor(angles).to(self.device, torch.float64).contiguous()
-        if x.dim() != 2 or x.shape[1] != 13 or x.shape[0] < 1:
-            raise ValueError(f"angles must be (n,13) with n >= 1, got {tuple(x.shape)}")
+        x = self._rows_input(angles, "angles", (13,), torch.float64)
         ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
         if tuple(ev.shape) != (x.shape[0],):
             raise ValueError(f"events must be ({x.shape[0]},), got {tuple(ev.shape)}")
-        if int(min_stride) != min_stride or int(max_stride) != max_stride:
-            raise ValueError("min_stride and max_stride must be whole numbers of frames")
+        self._whole_frames(min_stride=min_stride, max_stride=max_stride)
         off = self._sequence_offsets(x.shape[0], lengths, "angles")
         n_seq = len(off) - 1
         out = {"curves": torch.empty(n_seq, 13, 101, 2, dtype=torch.float64, device=self.device),
                "per_sequence": torch.empty(n_seq, 13, 6, dtype=torch.float64, device=self.device)}
-        rc = self._lib.grnet_op_gait_cycles(self._h, x.data_ptr(), ev.data_ptr(), off.ctypes.data_as(C.POINTER(C.c_int32)), n_seq, int(min_stride), int(max_stride),
-                                            out["curves"].data_ptr(), out["per_sequence"].data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        rc = self._lib.grnet_op_gait_cycles(self._h, x.data_ptr(), ev.data_ptr(), _i32p(off), n_seq, int(min_stride), int(max_stride),
+                                            out["curves"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_cycles")
         return out
 
@@ -1205,7 +1196,7 @@ class GRNet:
         if kp.dim() != 3 or tuple(kp.shape[1:]) != (29, 3) or v.dim() != 3 or tuple(v.shape[1:]) != (6890, 3) or kp.shape[0] != v.shape[0]:
             raise ValueError(f"joints29 must be (n,29,3) and verts (n,6890,3), got {tuple(kp.shape)} and {tuple(v.shape)}")
         out = torch.empty(kp.shape[0], nj, 3, dtype=torch.float32, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_spin_joints(self._h, kp.data_ptr(), v.data_ptr(), kp.shape[0], kind, out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_spin_joints")
         return out
@@ -1255,7 +1246,7 @@ class GRNet:
             raise ValueError(f"points and image_index disagree on n: {n}, {idx.shape[0]}")
         proj, window, Rh = self._segment_view(view, R)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_render_segments(self._h, p.data_ptr(), n, P, ptr(seg), seg.shape[0], ptr(col), ptr(wid), ptr(idx),
                                              ptr(Rh) if Rh is not None else None, ptr(proj), ptr(window), images.data_ptr(), F, H, W, stream)
         _lib.check(self._lib, self._h, rc, "grnet_render_segments")
@@ -1270,7 +1261,7 @@ class GRNet:
         xy = torch.empty(P, 2, dtype=torch.int32, device=self.device)
         d = torch.empty(P, dtype=torch.float32, device=self.device)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_op_segments_setup(self._h, p.data_ptr(), P, ptr(Rh) if Rh is not None else None, ptr(proj), ptr(window), H, W,
                                                xy.data_ptr(), d.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_segments_setup")
@@ -1284,7 +1275,7 @@ class GRNet:
         seg, wid = self._segment_table(segments, widths)
         out = torch.empty(H, W, dtype=torch.int32, device=self.device)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         rc = self._lib.grnet_op_raster_segments(self._h, xy.data_ptr(), d.data_ptr(), xy.shape[0], ptr(seg), seg.shape[0], ptr(wid), H, W,
                                                 out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_raster_segments")
@@ -1299,7 +1290,7 @@ class GRNet:
         out = torch.empty(n, cout, ho, wo, dtype=torch.float32, device=x.device)
         wn = _np32(w)
         bn = _np32(bias) if bias is not None else None
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_op_conv2d(self._h, x.data_ptr(), n, cin, h, wd, wn.ctypes.data_as(C.c_void_p),
                                        bn.ctypes.data_as(C.c_void_p) if bn is not None else None, cout, ks, stride,
                                        int(relu), add.data_ptr() if add is not None else None, out.data_ptr(),
@@ -1323,7 +1314,7 @@ class GRNet:
         ctot = (C.c_int * max(k, 1))(*[t.shape[1] for t in tens])
         coff = (C.c_int * max(k, 1))(*[int(a[1]) for a in adds])
         shift = (C.c_int * max(k, 1))(*[int(a[2]) for a in adds])
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_op_conv2d_adds(self._h, x.data_ptr(), n, cin, h, wd, wn.ctypes.data_as(C.c_void_p),
                                             bn.ctypes.data_as(C.c_void_p) if bn is not None else None, cout, ks, stride, int(relu), k, ptrs, ctot, coff,
                                             shift, out.data_ptr(), tile_hint, stream)
@@ -1338,7 +1329,7 @@ class GRNet:
         wn = np.ascontiguousarray(np.stack([_np32(w) for w in ws]))
         bn = np.ascontiguousarray(np.stack([_np32(b) for b in bs]))
         us = C.c_float(0.0)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_op_conv_chain(self._h, x.data_ptr(), n, c, wd, len(ws), wn.ctypes.data_as(C.c_void_p), bn.ctypes.data_as(C.c_void_p),
                                            out.data_ptr(), int(reps), C.byref(us), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_conv_chain")
@@ -1347,7 +1338,7 @@ class GRNet:
     def op_bilinear2x(self, x):
         n, c, h, w = x.shape
         out = torch.empty(n, c, 2 * h, 2 * w, dtype=torch.float32, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = self._stream(x.device)
         rc = self._lib.grnet_op_bilinear2x(self._h, x.data_ptr(), n, c, h, w, out.data_ptr(), stream)
         _lib.check(self._lib, self._h, rc, "grnet_op_bilinear2x")
         return out

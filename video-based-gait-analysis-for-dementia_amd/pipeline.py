@@ -635,27 +635,36 @@ def openpose_boxes(anno_folder, model=None, img_w=1920, img_h=1080, return_joint
     return result
 
 
+def _sequence_lengths(n, lengths):
+    """The lengths of the sequences that cut n frames lying back to back, as a list (None: one sequence of them all); each has at least one frame."""
+    lengths = [n] if lengths is None else [int(v) for v in lengths]
+    if sum(lengths) != n or min(lengths) < 1:
+        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    return lengths
+
+
+def _widened(x, what, finite=False):
+    """x (n,K,3) with n, K >= 1 as the device takes it: rounded to float32, then widened to float64.  finite: ValueError on a NaN or an infinity."""
+    a = np.asarray(x)
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"{what} must be (n,K,3) with n, K >= 1, got {a.shape}")
+    if finite and not np.isfinite(a).all():
+        raise ValueError(f"{what} has a non-finite entry")
+    return a.astype(np.float32).astype(np.float64)
+
+
 def pose_metrics(pred_joints, gt_joints, lengths=None, root=None, select=None, pred_verts=None, gt_verts=None, unit=1000.0, return_transform=False):
     """MPJPE, PA-MPJPE, PVE, acceleration and acceleration error in numpy float64 with np.linalg.svd: the host statement of
     GRNet.pose_metrics, same arguments, a dict of numpy arrays.  The inputs are taken as float32 and widened, as the device takes them.
     per_frame (n,5) = [mpjpe, pa_mpjpe, pve, accel, accel_err] times unit, NaN where undefined by structure; per_sequence (n_seq,5) and
     total (5,): means over the defined entries (the total from the sequences' sums and counts); transform (n,13) = [s, R row-major, t]."""
-    def widened(x, what):
-        a = np.asarray(x)
-        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-            raise ValueError(f"{what} must be (n,J,3) with n >= 1, got {a.shape}")
-        if not np.isfinite(a).all():
-            raise ValueError(f"{what} has a non-finite entry")
-        return a.astype(np.float32).astype(np.float64)
-    p, g = widened(pred_joints, "pred_joints"), widened(gt_joints, "gt_joints")
+    p, g = _widened(pred_joints, "pred_joints", finite=True), _widened(gt_joints, "gt_joints", finite=True)
     if p.shape != g.shape:
         raise ValueError(f"pred_joints and gt_joints differ in shape: {p.shape}, {g.shape}")
     if (pred_verts is None) != (gt_verts is None):
         raise ValueError("pred_verts and gt_verts go together")
     n, J = p.shape[:2]
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     sel = np.arange(J) if select is None else np.asarray(select, np.int64).reshape(-1)
     rt = np.zeros(0, np.int64) if root is None else np.asarray(root, np.int64).reshape(-1)
     for idx, what in ((sel, "select"), (rt, "root")):
@@ -688,7 +697,7 @@ def pose_metrics(pred_joints, gt_joints, lengths=None, root=None, select=None, p
     aligned = s[:, None, None] * np.einsum("nab,njb->nja", R, P) + t[:, None, :]
     per_frame[:, 1] = np.linalg.norm(aligned - G, axis=2).mean(axis=1)
     if pred_verts is not None:
-        pv, gv = widened(pred_verts, "pred_verts"), widened(gt_verts, "gt_verts")
+        pv, gv = _widened(pred_verts, "pred_verts", finite=True), _widened(gt_verts, "gt_verts", finite=True)
         if pv.shape != gv.shape or pv.shape[0] != n:
             raise ValueError(f"pred_verts and gt_verts must both be ({n},V,3), got {pv.shape} and {gv.shape}")
         per_frame[:, 2] = np.linalg.norm(pv - gv, axis=2).mean(axis=1)
@@ -752,18 +761,11 @@ def fit_translation(joints3d, joints2d, pairs, lengths=None, focal_length=5000.0
     """estimate_translation_np (lib/utils/geometry.py:296-337) per frame in numpy float64 with the statuses, the fill and the summary of DESIGN 4.9:
     the host statement of GRNet.fit_translation, same arguments, a dict of numpy arrays.  The inputs are taken as float32 and widened, as the device
     takes them.  per_frame (n,6) = [tx, ty, tz, reproj_px, n_used, status], per_sequence (n_seq,4) = [fitted, filled, mean reproj, path length]."""
-    def widened(x, what):
-        a = np.asarray(x)
-        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-            raise ValueError(f"{what} must be (n,K,3) with n, K >= 1, got {a.shape}")
-        return a.astype(np.float32).astype(np.float64)
-    j3, j2 = widened(joints3d, "joints3d"), widened(joints2d, "joints2d")
+    j3, j2 = _widened(joints3d, "joints3d"), _widened(joints2d, "joints2d")
     n = j3.shape[0]
     if j2.shape[0] != n:
         raise ValueError(f"joints3d has {n} frames and joints2d {j2.shape[0]}")
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     table = np.asarray(pairs, np.int64)
     if table.ndim != 2 or table.shape[1] != 2 or not 1 <= table.shape[0] <= 64:
         raise ValueError(f"pairs must be (P,2) of (3D index, 2D index) with 1 <= P <= 64, got {table.shape}")
@@ -901,9 +903,7 @@ def track_boxes(joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0
     if kp.ndim != 3 or kp.shape[2] != 3 or kp.shape[0] < 1 or not 1 <= kp.shape[1] <= 64:
         raise ValueError(f"joints2d must be (T,K,3) with T >= 1 and 1 <= K <= 64, got {kp.shape}")
     n = kp.shape[0]
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     if not np.isfinite(vis_thresh):
         raise ValueError("vis_thresh must be finite")
     if kernel_size < 1 or kernel_size > 31 or kernel_size % 2 == 0:
@@ -1012,14 +1012,9 @@ def gait_parameters(joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, win
     widened; joints: the indices of pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot; trans (n,3) float64
     or None.  per_frame (n,7) = [hL, hR, tL, tR (as smoothed), wd, step_length, step_width]; events (n,) int32 (GAIT_HEEL_L, GAIT_HEEL_R,
     GAIT_TOE_L, GAIT_TOE_R); per_sequence (n_seq,18), columns GAIT_COLUMNS."""
-    a3 = np.asarray(joints3d)
-    if a3.ndim != 3 or a3.shape[2] != 3 or a3.shape[0] < 1 or a3.shape[1] < 1:
-        raise ValueError(f"joints3d must be (n,J,3) with n, J >= 1, got {a3.shape}")
-    j3 = a3.astype(np.float32).astype(np.float64)
+    j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     tab = np.asarray(joints, np.int64).reshape(-1)
     if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
         raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
@@ -1177,9 +1172,7 @@ def gait_cycles(angles, events, lengths=None, min_stride=8, max_stride=60):
     if ev.shape != (n,):
         raise ValueError(f"events must be ({n},), got {ev.shape}")
     ev = ev.astype(np.int64)
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     lo, hi = _kin_strides_check(min_stride, max_stride)
     curves = np.full((len(lengths), 13, KINEMATICS_POINTS, 2), np.nan)
     rows = np.full((len(lengths), 13, 6), np.nan)
@@ -1226,14 +1219,9 @@ def gait_kinematics(joints3d, events, lengths=None, sigma=2.0, min_stride=8, max
     returned; joints: the 16 indices of pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist.  per_frame
     (n,13): the channels KINEMATICS_CHANNELS in degrees, as smoothed; curves (n_seq,13,101,2); per_sequence (n_seq,13,6), columns
     KINEMATICS_COLUMNS.  Channel 12, the trunk's inclination, is measured from the camera's vertical: it assumes a level camera."""
-    a3 = np.asarray(joints3d)
-    if a3.ndim != 3 or a3.shape[2] != 3 or a3.shape[0] < 1 or a3.shape[1] < 1:
-        raise ValueError(f"joints3d must be (n,J,3) with n, J >= 1, got {a3.shape}")
-    j3 = a3.astype(np.float32).astype(np.float64)
+    j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
-    lengths = [n] if lengths is None else [int(v) for v in lengths]
-    if sum(lengths) != n or min(lengths) < 1:
-        raise ValueError(f"lengths {lengths if len(lengths) < 8 else len(lengths)} do not cut {n} frames into sequences of at least one frame")
+    lengths = _sequence_lengths(n, lengths)
     tab = np.asarray(joints, np.int64).reshape(-1)
     if tab.size != 16 or tab.min() < 0 or tab.max() >= J:
         raise ValueError(f"joints must be 16 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist)")
