@@ -29,6 +29,11 @@ trunk's inclination, cut at the heel strikes --gait found, put on 0 to 100 % of 
 of motion and its left / right symmetry (GRNet.gait_kinematics on the device) -- in <outpath>_kinematics.json.  The numbers are
 reported, never judged; the trunk's inclination assumes a level camera.
 
+--gait_turns (opt-in, with --gait) finds where the subject turns round -- runs of the pelvis' yaw rate in the camera's horizontal plane that are fast,
+long and wide enough (GRNet.gait_turns on the device; the thresholds follow El-Gohary et al. 2014 and are unvalidated on the model's
+output) -- and makes the step and stride columns of --gait again over the intervals that are wholly straight walking: <outpath>_turns.json, and
+'gait_phase' in the database.  Reported, never judged; the heading assumes a level camera.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -270,6 +275,7 @@ class WindowGait:
         else:
             made = out = self.pipe.gait_parameters(j3.cpu().numpy(), lengths=lengths, trans=trans, **self.kw)
         self.window = (j3, lengths, made["events"])            # for WindowKinematics: the joints and the events as this call returned them
+        self.rows = made["per_frame"]                          # for WindowTurns: the per-frame rows as this call returned them
         events, a = [], 0
         for key, T, row in zip(keys, lengths, out["per_sequence"]):
             events.append(out["events"][a:a + T].astype(np.uint8))
@@ -341,10 +347,63 @@ class WindowKinematics:
         return path
 
 
+class WindowTurns:
+    """--gait_turns: one gait_turns call per database window on rank 0, directly after WindowGait's, on the same joints and on the events and per-frame
+    rows that call returned (model.gait_turns; on_host, or a model without the method: pipeline.gait_turns after a download).  Per video the columns
+    of pipeline.TURN_COLUMNS plus 'turns', the list of its stored turns keyed by pipeline.TURN_TABLE_COLUMNS.  The joints are
+    pipeline.GAIT_JOINTS_KINECTV2, fps is WindowGait's.  The thresholds are unvalidated on the model's output; nothing is judged."""
+
+    def __init__(self, pipe, model, on_host, fps=20.0, sigma=8.0, edge_rate=5.0, peak_rate=15.0, min_angle=45.0, min_frames=10, max_frames=200):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_turns") else model.gait_turns
+        self.kw = dict(fps=float(fps), sigma=float(sigma), edge_rate=float(edge_rate), peak_rate=float(peak_rate), min_angle=float(min_angle),
+                       min_frames=int(min_frames), max_frames=int(max_frames))
+        self.videos = {}
+
+    def add_window(self, keys, j3, lengths, events, gait_rows, whole):
+        """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths, the events (sum T,) and the per-frame
+        rows (sum T,7); whole[key]: its row of the whole clip, for the line -> per video the phase (T,) uint8."""
+        if not keys:
+            return []
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, gait_rows, lengths=lengths, **self.kw).items()}
+        else:
+            ev, rows = (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in (events, gait_rows))
+            out = self.pipe.gait_turns(j3.cpu().numpy(), ev, rows, lengths=lengths, **self.kw)
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit):
+            return "none" if v is None else format(v, form) + unit
+        phases, a = [], 0
+        for key, T, row, table in zip(keys, lengths, out["per_sequence"], out["turns"]):
+            phases.append(out["phase"][a:a + T].astype(np.uint8))
+            video = {name: number(v) for name, v in zip(self.pipe.TURN_COLUMNS, row)}
+            video["turns"] = [{name: number(v) for name, v in zip(self.pipe.TURN_TABLE_COLUMNS, turn)} for turn in table if not np.isnan(turn[0])]
+            self.videos[key] = video
+            clip = whole[key]
+            print(f"Turns: video {key}, {int(row[0])} turns, mean turn time {shown(video['turn_duration_mean'], '.2f', ' s')}, stride-time CV "
+                  f"{shown(clip['stride_time_cv'], '.2f', ' %')} over the whole clip against {shown(video['straight_stride_time_cv'], '.2f', ' %')} straight, "
+                  f"speed {shown(clip['speed'], '.3f', ' m/s')} against {shown(video['straight_speed'], '.3f', ' m/s')}.")
+            a += T
+        return phases
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save turns of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None):
-    """kinematics: {'sigma', 'min_stride', 'max_stride', 'on_host', 'out'} (each optional; needs gait) -- also the joint angles per gait cycle of every
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None):
+    """turns: {'sigma', 'edge_rate', 'peak_rate', 'min_angle', 'min_frames', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
+    takes) -- also the turns of every video and its gait parameters over straight walking alone (WindowTurns), written to turns['out'] (default:
+    outpath with _turns.json); the database gains 'gait_phase' (N,) uint8 (0 straight, 1 left turn, 2 right turn, 3 unknown).
+    kinematics: {'sigma', 'min_stride', 'max_stride', 'on_host', 'out'} (each optional; needs gait) -- also the joint angles per gait cycle of every
     video (WindowKinematics), written to kinematics['out'] (default: outpath with _kinematics.json); the database gains nothing.
     gait: {'fps', 'sigma', 'window', 'min_excursion', 'on_host', 'out'} (each optional) -- also read the gait events and parameters of every video
     off its joints (WindowGait), add 'gait_events' (N,) uint8 to the database (bit 0 heel strike left, 1 heel strike right, 2 toe-off left, 3 toe-off
@@ -413,6 +472,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     angles = WindowKinematics(pipe, model, kinematics.get("on_host", False),
                               **{k: kinematics[k] for k in ("sigma", "min_stride", "max_stride") if kinematics.get(k) is not None}) \
         if kinematics is not None and rank == 0 else None
+    if turns is not None and gait is None:
+        raise ValueError("turns needs gait: it runs on the events and rows of that call")
+    rounds = WindowTurns(pipe, model, turns.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
+                         **{k: turns[k] for k in ("sigma", "edge_rate", "peak_rate", "min_angle", "min_frames", "max_frames") if turns.get(k) is not None}) \
+        if turns is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -465,6 +529,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         gait_events = walk.add_window([v[0] for v in vids], per_video, fitted) if walk is not None else None
         if angles is not None and vids:
             angles.add_window([v[0] for v in vids], *walk.window)
+        gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -475,6 +540,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                     extra["bbox_status"] = status
                 if gait_events is not None:
                     extra["gait_events"] = gait_events[vi]
+                if gait_phase is not None:
+                    extra["gait_phase"] = gait_phase[vi]
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -488,6 +555,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         walk.write(gait.get("out") or osp.splitext(outpath)[0] + "_gait.json")
     if angles is not None:
         angles.write(kinematics.get("out") or osp.splitext(outpath)[0] + "_kinematics.json")
+    if rounds is not None:
+        rounds.write(turns.get("out") or osp.splitext(outpath)[0] + "_turns.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -542,6 +611,17 @@ def main(argv=None):
     p.add_argument("--kinematics_min_stride", type=int, default=None, help="with --gait_kinematics: the shortest stride that is used, in frames (default 8: 0.4 s at 20 fps)")
     p.add_argument("--kinematics_max_stride", type=int, default=None, help="with --gait_kinematics: the longest stride that is used, in frames, at most 4096 (default 60: 3 s)")
     p.add_argument("--kinematics_on_host", action="store_true", help="with --gait_kinematics: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_turns", action="store_true", help="with --gait: where the subject turns round (yaw rate of the pelvis in the camera's horizontal plane) and the "
+                   "step and stride columns of --gait over straight walking alone: 'gait_phase' (N,) in the database, <outpath>_turns.json, one line per video; the "
+                   "default thresholds follow El-Gohary et al. 2014 and are unvalidated on the model's output")
+    p.add_argument("--turns_out", type=str, default="", help="with --gait_turns: the JSON file (default: --outpath with _turns.json)")
+    p.add_argument("--turns_sigma", type=float, default=None, help="with --gait_turns: sigma in frames of the Gaussian over the yaw rate, 0 (none) to 16 (default 8)")
+    p.add_argument("--turns_edge_rate", type=float, default=None, help="with --gait_turns: a turn is a run of yaw rate beyond this many degrees a second (default 5)")
+    p.add_argument("--turns_peak_rate", type=float, default=None, help="with --gait_turns: ... that peaks at this many degrees a second or more (default 15)")
+    p.add_argument("--turns_min_angle", type=float, default=None, help="with --gait_turns: ... and covers this many degrees or more (default 45)")
+    p.add_argument("--turns_min_duration", type=float, default=None, help="with --gait_turns: the shortest turn in seconds, made frames through --gait_fps (default 0.5)")
+    p.add_argument("--turns_max_duration", type=float, default=None, help="with --gait_turns: the longest turn in seconds, made frames through --gait_fps (default 10)")
+    p.add_argument("--turns_on_host", action="store_true", help="with --gait_turns: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -602,6 +682,28 @@ def main(argv=None):
     lo, hi = 8 if a.kinematics_min_stride is None else a.kinematics_min_stride, 60 if a.kinematics_max_stride is None else a.kinematics_max_stride
     if a.gait_kinematics and not 1 <= lo <= hi <= 4096:
         sys.exit("batch_generation.py: --kinematics_min_stride and --kinematics_max_stride must be frames with 1 <= min <= max <= 4096")
+    if a.gait_turns and not a.gait:
+        sys.exit("batch_generation.py: --gait_turns belongs to --gait, which was not given (it runs on the events and rows of that call)")
+    for flag, given in (("--turns_out", bool(a.turns_out)), ("--turns_sigma", a.turns_sigma is not None), ("--turns_edge_rate", a.turns_edge_rate is not None),
+                        ("--turns_peak_rate", a.turns_peak_rate is not None), ("--turns_min_angle", a.turns_min_angle is not None),
+                        ("--turns_min_duration", a.turns_min_duration is not None), ("--turns_max_duration", a.turns_max_duration is not None),
+                        ("--turns_on_host", a.turns_on_host)):
+        if given and not a.gait_turns:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_turns, which was not given")
+    if a.turns_sigma is not None and not (np.isfinite(a.turns_sigma) and 0 <= a.turns_sigma <= 16):
+        sys.exit("batch_generation.py: --turns_sigma must be within 0 to 16")
+    edge, peak = 5.0 if a.turns_edge_rate is None else a.turns_edge_rate, 15.0 if a.turns_peak_rate is None else a.turns_peak_rate
+    if a.gait_turns and not (np.isfinite(edge) and np.isfinite(peak) and 0 <= edge <= peak):
+        sys.exit("batch_generation.py: --turns_edge_rate and --turns_peak_rate must be degrees a second with 0 <= edge <= peak")
+    if a.turns_min_angle is not None and not (np.isfinite(a.turns_min_angle) and a.turns_min_angle >= 0):
+        sys.exit("batch_generation.py: --turns_min_angle must be a number of degrees, not negative")
+    turn_frames = None
+    if a.gait_turns:
+        lo, hi = 0.5 if a.turns_min_duration is None else a.turns_min_duration, 10.0 if a.turns_max_duration is None else a.turns_max_duration
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+            sys.exit("batch_generation.py: --turns_min_duration and --turns_max_duration must be seconds with 0 < min <= max")
+        fps = 20.0 if a.gait_fps is None else a.gait_fps
+        turn_frames = (max(1, int(round(lo * fps))), max(1, int(round(hi * fps))))       # whole frames, the nearest
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -621,10 +723,12 @@ def main(argv=None):
             "out": a.gait_out or None} if a.gait else None
     kinematics = {"sigma": a.kinematics_sigma, "min_stride": a.kinematics_min_stride, "max_stride": a.kinematics_max_stride, "on_host": a.kinematics_on_host,
                   "out": a.kinematics_out or None} if a.gait_kinematics else None
+    turns = {"sigma": a.turns_sigma, "edge_rate": a.turns_edge_rate, "peak_rate": a.turns_peak_rate, "min_angle": a.turns_min_angle, "min_frames": turn_frames[0],
+             "max_frames": turn_frames[1], "on_host": a.turns_on_host, "out": a.turns_out or None} if a.gait_turns else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
-                 **({"kinematics": kinematics} if kinematics is not None else {}))
+                 **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}))
 
 
 if __name__ == "__main__":

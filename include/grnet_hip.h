@@ -661,6 +661,44 @@ int grnet_gait_kinematics(grnet_t* h, const float* joints3d_dev, int J, const in
 int grnet_op_gait_cycles(grnet_t* h, const double* angles_dev, const int32_t* events_dev, const int32_t* frame_offsets_host, int n_seq, int min_stride,
                          int max_stride, double* curves_dev, double* per_seq_dev, void* stream);
 
+/* ---- turns and straight-walking gait parameters (csrc/gait_turns_kernels.hip, csrc/gait_turns.h) ---------------------------------
+ * Where the subject turns round, and the gait row's step and stride columns over the intervals that are wholly straight walking.  Called directly
+ * after grnet_gait_parameters on the same joints and on what it returned.  The reference has no such code: DESIGN.md 4.13 is the specification.  The
+ * default thresholds follow the inertial-sensor turn rule of El-Gohary et al. (Sensors 14, 2014) and are UNVALIDATED on the model's output.
+ * joints3d_dev float32 (sum T, J, 3), frame_offsets_host and joints_host as for grnet_gait_parameters (the first four indices are read: pelvis,
+ * spine-shoulder, left hip, right hip); events_dev int32 (sum T): its events; gait_rows_dev float64 (sum T, 7): its per_frame (columns 0, 1 and 4
+ * are read).  Everything is float64, one rounding per operation; every test is a comparison, false for NaN.
+ *   heading  g = (f_x, f_z) of grnet_gait_parameters' f: its part in the horizontal plane of a LEVEL camera; NaN of an invalid frame
+ *   step     D(0) = +0; D(t) = atan2(g_x(t-1) g_z(t) - g_z(t-1) g_x(t), g_x(t-1) g_x(t) + g_z(t-1) g_z(t)) in degrees (csrc/gait_angles.h's
+ *            arctangent), positive towards the subject's left; NaN where either frame is invalid or a horizontal part vanishes
+ *   rate     w = D fps, then (sigma > 0; <= 16) grnet_track_boxes' Gaussian inside each sequence; a NaN spreads as far as the kernel reaches
+ *   runs     maximal runs of w > edge_rate (left) and of w < -edge_rate (right); a run is a TURN where max |w| >= peak_rate, |sum D| over it (raw
+ *            steps in time order from +0.0) >= min_angle and min_frames <= its length <= max_frames
+ * per_frame_dev (sum T, 2) float64 = [D, w as smoothed].  phase_dev (sum T) int32: 1 a frame of a left turn, 2 of a right turn, 3 w is NaN, 0 straight
+ * (a run that is no turn included).  turns_dev (n_seq, max_turns, 7) float64, in time order: [first frame, last frame (inclusive, counted inside the
+ * sequence), +1 left / -1 right, sum D, (last - first + 1) / fps, max |w|, heel strikes of either foot inside the turn (a frame where both strike
+ * counts two)]; rows past the count are NaN, turns past max_turns are counted but not stored.
+ * per_seq_dev (n_seq, 24) float64: [0, 1, 2] turns, left, right; [3] turn frames; [4] unknown frames; [5] straight bouts (maximal runs of phase 0);
+ * [6] straight frames; [7 .. 10] the means over ALL turns of duration, |angle|, peak and steps in turn (NaN without a turn); [11 .. 23] the gait
+ * row's columns 4 .. 16 in that order over the intervals that are wholly straight: a step (t1, t2), a stride (t0, t1) and the stance share's stride
+ * count where no frame of the closed interval has phase != 0; consecutive still means consecutive among ALL strikes.  With no frame of phase != 0,
+ * [11 .. 23] equal grnet_gait_parameters' [4 .. 16] in every bit.
+ * No filter or search crosses a sequence; fixed orders, no atomics: a sequence's outputs have the same bits whether it travels alone or with others.
+ * Needs no weights.  Two launches behind one small copy from pinned memory, whatever n_seq and T; no host synchronisation; the scratch is the box
+ * calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer, J < 1, a table index outside [0, J) (all 8 are
+ * checked), n_seq outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, fps not positive and finite, a negative, non-finite or too
+ * large sigma, a negative or non-finite edge_rate, peak_rate < edge_rate (or not finite), a negative or non-finite min_angle, min_frames < 1,
+ * max_frames < min_frames, max_turns outside [1, 64].
+ * grnet_op_gait_turn_runs: runs, phases, the turn table and the row alone (test hook) on rates_dev float64 (sum T, 2) = [D, w]. */
+int grnet_gait_turns(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                     const int32_t* events_dev, const double* gait_rows_dev, double fps, double sigma, double edge_rate, double peak_rate, double min_angle,
+                     int min_frames, int max_frames, int max_turns, double* per_frame_dev, int32_t* phase_dev, double* turns_dev, double* per_seq_dev,
+                     void* stream);
+int grnet_op_gait_turn_runs(grnet_t* h, const double* rates_dev, const int32_t* events_dev, const double* gait_rows_dev, const int32_t* frame_offsets_host,
+                            int n_seq, double fps, double edge_rate, double peak_rate, double min_angle, int min_frames, int max_frames, int max_turns,
+                            int32_t* phase_dev, double* turns_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -417,6 +417,18 @@ hipError_t launch_kin_smooth(const int* off, int n_seq, const double* weights, i
 hipError_t launch_kin_cycles(const int* off, int n_seq, const int* events, const double* per_frame, int min_stride, int max_stride, unsigned long long* words,
                              size_t mask_words, double* curves, double* per_seq, hipStream_t s);
 
+// Turns and straight-walking gait parameters (csrc/gait_turns_kernels.hip, compiled without fma contraction; the arithmetic: csrc/gait_turns.h;
+// DESIGN 4.13) ----
+struct TurnRule;                           // gait_turns.h: fps and the thresholds of rule 4
+// one workgroup per sequence: per_frame (frames,2) = [yaw step, yaw rate]; radius < 0: no Gaussian and raw is not used, else raw (frames) gets the raw
+// rates; off: n_seq + 1 frame offsets ON THE DEVICE; tab: its first four joints are read
+hipError_t launch_turn_rates(const int* off, int n_seq, const double* weights, int radius, int J, const GaitTable& tab, const float* joints, double fps,
+                             double* raw, double* per_frame, hipStream_t s);
+// one workgroup per sequence on per_frame (frames,2), the gait call's events (frames) and rows (frames,7): phase (frames), turns
+// (n_seq,max_turns,7), per_seq (n_seq,24); words: kTurnMaskSets (gait_turns.h) * mask_words (gait_mask_words)
+hipError_t launch_turn_sequences(const int* off, int n_seq, const TurnRule& rule, const double* per_frame, const int* events, const double* gait_rows,
+                                 unsigned long long* words, size_t mask_words, int* phase, double* turns, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

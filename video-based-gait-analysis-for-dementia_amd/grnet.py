@@ -1183,6 +1183,67 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_cycles")
         return out
 
+    # ------------------------------------------------------------------ turns and straight-walking gait parameters
+    def _turn_inputs(self, n, events, gait_rows, min_frames, max_frames, max_turns):
+        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
+        if tuple(ev.shape) != (n,):
+            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        rows = torch.as_tensor(gait_rows).to(self.device, torch.float64).contiguous()
+        if tuple(rows.shape) != (n, 7):
+            raise ValueError(f"gait_rows must be ({n},7), got {tuple(rows.shape)}")
+        self._whole_frames(min_frames=min_frames, max_frames=max_frames, max_turns=max_turns)
+        if not 1 <= int(max_turns) <= 64:
+            raise ValueError(f"max_turns {max_turns} outside [1, 64]")      # the turn table is allocated here: a size the C ABI would refuse is refused first
+        return ev, rows
+
+    def _turn_outputs(self, n, n_seq, max_turns):
+        return {"phase": torch.empty(n, dtype=torch.int32, device=self.device),
+                "turns": torch.empty(n_seq, int(max_turns), 7, dtype=torch.float64, device=self.device),
+                "per_sequence": torch.empty(n_seq, 24, dtype=torch.float64, device=self.device)}
+
+    def gait_turns(self, joints3d, events, gait_rows, lengths=None, fps=20.0, sigma=8.0, edge_rate=5.0, peak_rate=15.0, min_angle=45.0, min_frames=10,
+                   max_frames=200, max_turns=8, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Turns and the gait parameters of straight walking of every sequence on the device (grnet_gait_turns; the rules and the columns: DESIGN 4.13,
+        pipeline.TURN_COLUMNS).  Called after gait_parameters on the same joints3d, lengths and joints, with its `events` (taken as int32) and its
+        `per_frame` as gait_rows (sum T,7), taken as float64.  The yaw rate (degrees a second, positive towards the subject's left) is smoothed by sigma
+        frames (0: none, <= 16); a run of it beyond +-edge_rate is a turn where it peaks at peak_rate or more, covers min_angle degrees or more and
+        lasts min_frames .. max_frames frames.  The defaults follow El-Gohary et al. 2014 and are unvalidated on the model's output; the heading
+        assumes a level camera.  Returns a dict of device tensors: per_frame (n,2) float64 [yaw step, yaw rate]; phase (n,) int32 -- 0 straight, 1 left
+        turn, 2 right turn, 3 unknown; turns (n_seq,max_turns,7) float64; per_sequence (n_seq,24) float64.  Works before finalize(): no weight is read.
+        Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
+        if table.size != 8:
+            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        ev, rows = self._turn_inputs(n, events, gait_rows, min_frames, max_frames, max_turns)
+        off = self._sequence_offsets(n, lengths, "joints3d")
+        n_seq = len(off) - 1
+        out = self._turn_outputs(n, n_seq, max_turns)
+        out["per_frame"] = torch.empty(n, 2, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_turns(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, _i32p(table), ev.data_ptr(), rows.data_ptr(), float(fps),
+                                        float(sigma), float(edge_rate), float(peak_rate), float(min_angle), int(min_frames), int(max_frames), int(max_turns),
+                                        out["per_frame"].data_ptr(), out["phase"].data_ptr(), out["turns"].data_ptr(), out["per_sequence"].data_ptr(),
+                                        self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_turns")
+        return out
+
+    def op_gait_turn_runs(self, rates, events, gait_rows, lengths=None, fps=20.0, edge_rate=5.0, peak_rate=15.0, min_angle=45.0, min_frames=10, max_frames=200,
+                          max_turns=8):
+        """Rules 4 to 7 of gait_turns alone (grnet_op_gait_turn_runs): rates (n,2) float64 [yaw step, yaw rate], events (n,) and gait_rows (n,7), one
+        sequence or `lengths` of them lying back to back -> {phase, turns, per_sequence} on the device."""
+        x = self._rows_input(rates, "rates", (2,), torch.float64)
+        n = x.shape[0]
+        ev, rows = self._turn_inputs(n, events, gait_rows, min_frames, max_frames, max_turns)
+        off = self._sequence_offsets(n, lengths, "rates")
+        n_seq = len(off) - 1
+        out = self._turn_outputs(n, n_seq, max_turns)
+        rc = self._lib.grnet_op_gait_turn_runs(self._h, x.data_ptr(), ev.data_ptr(), rows.data_ptr(), _i32p(off), n_seq, float(fps), float(edge_rate),
+                                               float(peak_rate), float(min_angle), int(min_frames), int(max_frames), int(max_turns), out["phase"].data_ptr(),
+                                               out["turns"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_turn_runs")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

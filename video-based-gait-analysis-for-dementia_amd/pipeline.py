@@ -1261,6 +1261,154 @@ def gait_kinematics(joints3d, events, lengths=None, sigma=2.0, min_stride=8, max
     return out
 
 
+# ----------------------------------------------------------------------------- turns and straight-walking gait parameters (DESIGN 4.13)
+TURN_STRAIGHT, TURN_LEFT, TURN_RIGHT, TURN_UNKNOWN = 0, 1, 2, 3          # a frame's phase
+TURN_COLUMNS = ("n_turns", "n_turns_left", "n_turns_right", "turn_frames", "unknown_frames", "straight_bouts", "straight_frames", "turn_duration_mean",
+                "turn_angle_mean", "turn_peak_rate_mean", "turn_steps_mean") + tuple("straight_" + name for name in GAIT_COLUMNS[4:17])
+TURN_TABLE_COLUMNS = ("first_frame", "last_frame", "direction", "angle", "duration", "peak_rate", "steps")
+
+
+def _turn_rule_check(fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns):
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if not np.isfinite(edge_rate) or edge_rate < 0:
+        raise ValueError("edge_rate must be finite and not negative")
+    if not np.isfinite(peak_rate) or peak_rate < edge_rate:
+        raise ValueError("peak_rate must be finite and not below edge_rate")
+    if not np.isfinite(min_angle) or min_angle < 0:
+        raise ValueError("min_angle must be finite and not negative")
+    if int(min_frames) != min_frames or int(max_frames) != max_frames or int(max_turns) != max_turns:
+        raise ValueError("min_frames, max_frames and max_turns must be whole numbers")
+    if min_frames < 1:
+        raise ValueError(f"min_frames {min_frames} < 1")
+    if max_frames < min_frames:
+        raise ValueError(f"max_frames {max_frames} < min_frames {min_frames}")
+    if not 1 <= max_turns <= 64:
+        raise ValueError(f"max_turns {max_turns} outside [1, 64]")
+
+
+def _turn_runs_of(mask):
+    """[(first, behind)] of the maximal runs of True in a boolean column, in time order."""
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], mask.astype(np.int8), [0]])))
+    return [(int(a), int(b)) for a, b in zip(edges[::2], edges[1::2])]
+
+
+def gait_turn_runs(rates, events, gait_rows, lengths=None, fps=20.0, edge_rate=5.0, peak_rate=15.0, min_angle=45.0, min_frames=10, max_frames=200, max_turns=8):
+    """Rules 4 to 7 of DESIGN 4.13 on given rates: the host statement of GRNet.op_gait_turn_runs.  rates (n,2) float64 [yaw step in degrees, yaw rate
+    in degrees a second], events (n,) and gait_rows (n,7) as gait_parameters returned them.  A maximal run of rate > edge_rate (left) or
+    < -edge_rate (right) is a turn where max |rate| >= peak_rate, |sum of its steps| >= min_angle and min_frames <= its length <= max_frames.  Returns
+    {'phase': (n,) int32, 'turns': (n_seq,max_turns,7), columns TURN_TABLE_COLUMNS, 'per_sequence': (n_seq,24), columns TURN_COLUMNS}; every sum in
+    time order from +0.0, every comparison false for NaN."""
+    x = np.asarray(rates, np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or x.shape[0] < 1:
+        raise ValueError(f"rates must be (n,2) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64)
+    g = np.asarray(gait_rows, np.float64)
+    if g.shape != (n, 7):
+        raise ValueError(f"gait_rows must be ({n},7), got {g.shape}")
+    lengths = _sequence_lengths(n, lengths)
+    _turn_rule_check(fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns)
+    fps, max_turns = float(fps), int(max_turns)
+    phase = np.zeros(n, np.int32)
+    turns = np.full((len(lengths), max_turns, 7), np.nan)
+    per_seq = np.full((len(lengths), 24), np.nan)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            step, rate, e, rows, ph = x[a:a + T, 0], x[a:a + T, 1], ev[a:a + T], g[a:a + T], phase[a:a + T]
+            strike = ((e & GAIT_HEEL_L) != 0).astype(np.int64) + ((e & GAIT_HEEL_R) != 0).astype(np.int64)
+            ph[np.isnan(rate)] = TURN_UNKNOWN
+            found = []
+            for sign, mask in ((1, rate > edge_rate), (-1, rate < -edge_rate)):
+                for first, behind in _turn_runs_of(mask):
+                    peak = float(np.abs(rate[first:behind]).max())
+                    angle = float(_kin_sum(step[first:behind]))
+                    if peak >= peak_rate and abs(angle) >= min_angle and min_frames <= behind - first <= max_frames:
+                        found.append([float(first), float(behind - 1), float(sign), angle, float(behind - first) / fps, peak, float(strike[first:behind].sum())])
+                        ph[first:behind] = TURN_LEFT if sign > 0 else TURN_RIGHT
+            found.sort()                                       # by the first frame: time order
+            for i, row in enumerate(found[:max_turns]):
+                turns[q, i] = row
+            out = per_seq[q]
+            out[0], out[1], out[2] = len(found), sum(r[2] > 0 for r in found), sum(r[2] < 0 for r in found)
+            out[3], out[4] = np.count_nonzero((ph == TURN_LEFT) | (ph == TURN_RIGHT)), np.count_nonzero(ph == TURN_UNKNOWN)
+            out[5], out[6] = len(_turn_runs_of(ph == TURN_STRAIGHT)), np.count_nonzero(ph == TURN_STRAIGHT)
+            if found:
+                for k, values in enumerate(([r[4] for r in found], [abs(r[3]) for r in found], [r[5] for r in found], [r[6] for r in found])):
+                    out[7 + k] = float(_kin_sum(values)) / len(found)
+            busy = np.concatenate([[0], np.cumsum(ph != TURN_STRAIGHT)])
+
+            def straight(t1, t2):
+                return busy[t2 + 1] == busy[t1]
+
+            # columns 11 .. 23: gait_parameters' 4 .. 16 with one test more per link
+            heel = [np.flatnonzero(e & GAIT_HEEL_L), np.flatnonzero(e & GAIT_HEEL_R)]
+            toe = [np.flatnonzero(e & GAIT_TOE_L), np.flatnonzero(e & GAIT_TOE_R)]
+            strikes = sorted([(int(t), 0) for t in heel[0]] + [(int(t), 1) for t in heel[1]])
+            steps = [(t1, t2, f2) for (t1, f1), (t2, f2) in zip(strikes[:-1], strikes[1:]) if f1 != f2 and straight(t1, t2)]
+            out[11] = len(steps)
+            if steps:
+                out[12], out[13] = _gait_mean_sd([float(t2 - t1) / fps for t1, t2, _ in steps])
+                out[14] = 60.0 / out[12]
+                out[18], out[19] = _gait_mean_sd([rows[t2, f2] - rows[t2, 1 - f2] for _, t2, f2 in steps])
+                out[20], out[21] = _gait_mean_sd([rows[t2, 4] for _, t2, _ in steps])
+                out[23] = (out[18] * out[14]) / 60.0
+            strides = [(int(t1), int(t2), foot) for foot in (0, 1) for t1, t2 in zip(heel[foot][:-1], heel[foot][1:]) if straight(int(t1), int(t2))]
+            if strides:
+                out[15], out[16] = _gait_mean_sd([float(t2 - t1) / fps for t1, t2, _ in strides])
+                out[17] = (100.0 * out[16]) / out[15]
+            stance = []
+            for t1, t2, foot in strides:
+                off = toe[foot][(toe[foot] > t1) & (toe[foot] < t2)]
+                if off.size:
+                    stance.append((100.0 * float(off[0] - t1)) / float(t2 - t1))
+            if stance:
+                out[22] = _gait_sum(stance) / len(stance)
+            a += T
+    return {"phase": phase, "turns": turns, "per_sequence": per_seq}
+
+
+def gait_turns(joints3d, events, gait_rows, lengths=None, fps=20.0, sigma=8.0, edge_rate=5.0, peak_rate=15.0, min_angle=45.0, min_frames=10, max_frames=200,
+               max_turns=8, joints=GAIT_JOINTS_KINECTV2):
+    """Turns and the gait parameters of straight walking from 3D joints in numpy float64 (the rules: DESIGN 4.13; the thresholds after El-Gohary et al.
+    2014, unvalidated on the model's output): the host statement of GRNet.gait_turns, same arguments, a dict of numpy arrays -- the same operations in
+    the same order.  joints3d (n,J,3) as gait_parameters takes them; events and gait_rows: its events and per_frame; joints: its table, of which
+    pelvis, spine-shoulder, left hip and right hip are read.  The ground heading g = (f_x, f_z) assumes a level camera.  per_frame (n,2) = [yaw step
+    in degrees, positive towards the subject's left; yaw rate in degrees a second as smoothed]; phase, turns, per_sequence: gait_turn_runs'."""
+    j3 = _widened(joints3d, "joints3d")
+    n, J = j3.shape[:2]
+    lengths = _sequence_lengths(n, lengths)
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    _turn_rule_check(fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns)
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    pelvis, spine, lhip, rhip = (j3[:, i] for i in tab[:4])
+    per_frame = np.zeros((n, 2))
+    with np.errstate(all="ignore"):
+        l, u = lhip - rhip, spine - pelvis
+        c = _kin_cross(l, u)
+        nc, nl = np.sqrt(_kin_dot(c, c)), np.sqrt(_kin_dot(l, l))
+        valid = (nc > 0) & np.isfinite(nc) & (nl > 0) & np.isfinite(nl)
+        gx, gz = np.where(valid, c[:, 0] / nc, np.nan), np.where(valid, c[:, 2] / nc, np.nan)
+        a = 0
+        for T in lengths:
+            x, z = gx[a:a + T], gz[a:a + T]
+            step = per_frame[a:a + T, 0]
+            step[1:] = gait_atan2(x[:-1] * z[1:] - z[:-1] * x[1:], x[:-1] * x[1:] + z[:-1] * z[1:]) * KINEMATICS_DEGREES
+            raw = step * float(fps)
+            per_frame[a:a + T, 1] = gauss_filter1d(raw, sigma) if sigma > 0 else raw
+            a += T
+    out = gait_turn_runs(per_frame, events, gait_rows, lengths, fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
