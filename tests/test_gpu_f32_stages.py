@@ -6,7 +6,8 @@ Teacher forcing: each launch's reference is the float64 oracle (oracle.float64()
 distinct frames tiled (frame k is frame k % 8): every copy of a frame must give the same bits in every tap and every output, and the references run
 on the 8 distinct frames.  Before the checked forward the handle runs a forward of the same size on other frames, so a consumer that reads a buffer
 before its producer has written it reads different numbers and fails.  Which kernel and launch form each size takes is asserted first
-(grnet_conv_kernel_info, grnet_conv_launch_form), so that a plan change cannot quietly move a check onto another kernel."""
+(grnet_conv_kernel_info, grnet_conv_launch_form), so that a plan change cannot quietly move a check onto another kernel.  At 16 frames every convolution launch is also held, element by element,
+to the rule of tests/test_gpu_conv_elements.py on its own tapped input (Checker.conv; tests/helpers/conv_checks.py forward_check)."""
 import ctypes as C
 import hashlib
 
@@ -15,6 +16,7 @@ import pytest
 import torch
 
 from .conftest import rel_err
+from .helpers import conv_checks as cc
 from .helpers import smpl_checks as sc
 
 pytestmark = pytest.mark.gpu
@@ -135,8 +137,11 @@ def _seams(fam, form, h):
 
 
 class Checker:
-    def __init__(self, by_key):
-        self.by_key, self.worst = by_key, {}
+    """elements > 0 (with the state dict): conv() also takes the per-element ratio of the launch on the first `elements` distinct frames of its own
+    tapped input (tests/helpers/conv_checks.py forward_check), given `own` = dict(x, bn | bias, stride, relu, residual, keys, bns)."""
+
+    def __init__(self, by_key, sd=None, elements=0):
+        self.by_key, self.worst, self.sd, self.elements = by_key, {}, sd, elements
 
     def __call__(self, fam, name, g, r, form=None):
         r = _np(r)
@@ -151,31 +156,57 @@ class Checker:
                 self.worst[fam] = max(self.worst[fam], es / bar)
                 assert es <= bar, (name, fam, "border / seam", sl, es, bar)
 
-    def conv(self, key, name, g, r):
+    def conv(self, key, name, g, r, own=None):
         _, form, _ = self.by_key[key]
         self(form["family"], name, g, r, form)
+        if self.elements and own is not None:
+            self._elements(key, name, g, form, **own)
+
+    def _elements(self, key, name, g, form, x, bn=None, bias=None, stride=1, relu=False, residual=None, keys=None, bns=None):
+        """|got - float64| per element in roundings of the element's magnitude, from |x|, |BatchNorm-folded weights|, |shift|, |residual|; the bar
+        is the family's yardstick on the same tapped input (FACTOR x its ratio, at least FACTOR).  keys / bns: the layers one launch computes."""
+        sd, f, fam = self.sd, slice(0, self.elements), form["family"]
+        ws, shifts = [], []
+        for k, b in zip(keys or [key], bns or [bn]):
+            if b is not None:
+                w64, sh = cc.fold_bn(sd[k], *(sd[b + s] for s in (".weight", ".bias", ".running_mean", ".running_var")))
+            else:
+                w64, sh = cc.widen(sd[k]), cc.widen(sd[bias]) if bias else np.zeros(len(sd[k]))
+            ws.append(w64)
+            shifts.append(sh)
+        res = None if residual is None else _np(residual)[f]
+        ratio, at, y, yname, bar = cc.forward_check(fam, g[f], _np(x)[f], np.concatenate(ws), np.concatenate(shifts), stride, res, relu)
+        print(f"conv_bounds family={fam} case=forward16:{name} data=forward form={'bias' + '_relu' * relu + '_res' * (res is not None)} gpu={ratio:.3f} "
+              f"at={at} where={cc.where(at, fam, form, g.shape[2])} yardstick={yname}:{y:.3f} accepted={bar:.3f}")
+        k = fam + " elements"
+        self.worst[k] = max(self.worst.get(k, 0.0), ratio / bar)
+        assert ratio <= bar, (name, fam, ratio, at, bar)
 
 
 def _check_direct_stages(ck, oracle, sd, got, base):
     """The stages that hold a direct-kernel launch: stem_conv2, layer1's convolutions, the transitions, the fuse layers and head.cam_shape."""
     T = lambda name: _t(got[name])
     with oracle.float64():
-        ck.conv(B + "conv2.weight", "stem_conv2", got["stem_conv2"], oracle.conv_bn(T("stem_conv1"), sd, B + "conv2.weight", B + "bn2", stride=2, relu=True))
+        ck.conv(B + "conv2.weight", "stem_conv2", got["stem_conv2"], oracle.conv_bn(T("stem_conv1"), sd, B + "conv2.weight", B + "bn2", stride=2, relu=True),
+                own=dict(x=got["stem_conv1"], bn=B + "bn2", stride=2, relu=True))
         q = B + "layer1.0."
         ck.conv(q + "downsample.0.weight", "layer1.0.downsample", got["layer1.0.downsample"],
-                oracle.conv_bn(T("stem_conv2"), sd, q + "downsample.0.weight", q + "downsample.1"))
+                oracle.conv_bn(T("stem_conv2"), sd, q + "downsample.0.weight", q + "downsample.1"), own=dict(x=got["stem_conv2"], bn=q + "downsample.1"))
         for k in range(4):
             q, x_in = f"{B}layer1.{k}.", "stem_conv2" if k == 0 else f"layer1.{k - 1}"
             res = T("layer1.0.downsample") if k == 0 else T(x_in)
-            ck.conv(q + "conv1.weight", f"layer1.{k}.conv1", got[f"layer1.{k}.conv1"], oracle.conv_bn(T(x_in), sd, q + "conv1.weight", q + "bn1", relu=True))
+            ck.conv(q + "conv1.weight", f"layer1.{k}.conv1", got[f"layer1.{k}.conv1"], oracle.conv_bn(T(x_in), sd, q + "conv1.weight", q + "bn1", relu=True),
+                    own=dict(x=got[x_in], bn=q + "bn1", relu=True))
             ck.conv(q + "conv2.weight", f"layer1.{k}.conv2", got[f"layer1.{k}.conv2"],
-                    oracle.conv_bn(T(f"layer1.{k}.conv1"), sd, q + "conv2.weight", q + "bn2", relu=True))
+                    oracle.conv_bn(T(f"layer1.{k}.conv1"), sd, q + "conv2.weight", q + "bn2", relu=True), own=dict(x=got[f"layer1.{k}.conv1"], bn=q + "bn2", relu=True))
             ck.conv(q + "conv3.weight", f"layer1.{k}", got[f"layer1.{k}"],
-                    oracle.conv_bn(T(f"layer1.{k}.conv2"), sd, q + "conv3.weight", q + "bn3", relu=True, residual=res))
+                    oracle.conv_bn(T(f"layer1.{k}.conv2"), sd, q + "conv3.weight", q + "bn3", relu=True, residual=res),
+                    own=dict(x=got[f"layer1.{k}.conv2"], bn=q + "bn3", relu=True, residual=res))
         for name, src, stride in (("transition1.0", "layer1.3", 1), ("transition1.1", "layer1.3", 2), ("transition2.2", "stage2.0.y1", 2),
                                   ("transition3.3", "stage3.3.y2", 2)):
             w = B + name + (".0.weight" if name == "transition1.0" else ".0.0.weight")
-            ck.conv(w, name, got[name], oracle.conv_bn(T(src), sd, w, w[:-len("0.weight")] + "1", stride=stride, relu=True))
+            ck.conv(w, name, got[name], oracle.conv_bn(T(src), sd, w, w[:-len("0.weight")] + "1", stride=stride, relu=True),
+                    own=dict(x=got[src], bn=w[:-len("0.weight")] + "1", stride=stride, relu=True))
         for stage, mi, nb in MODULES:
             tag = f"{stage}.{mi}"
             ys = oracle.hr_fuse([T(f"{tag}.x{b}") for b in range(nb)], sd, f"{B}{tag}.")
@@ -183,22 +214,26 @@ def _check_direct_stages(ck, oracle, sd, got, base):
                 ck("fuse", f"{tag}.y{i}", got[f"{tag}.y{i}"], ys[i])
         hd = "head."
         ck.conv(hd + "smpl_final_layer.weight", "head.cam_shape", got["head.cam_shape"],
-                oracle.conv2d(T("head.smpl_feats"), sd[hd + "smpl_final_layer.weight"], bias=sd[hd + "smpl_final_layer.bias"]))
+                oracle.conv2d(T("head.smpl_feats"), sd[hd + "smpl_final_layer.weight"], bias=sd[hd + "smpl_final_layer.bias"]),
+                own=dict(x=got["head.smpl_feats"], bias=hd + "smpl_final_layer.bias"))
 
 
 def _check_all_stages(ck, oracle, sd, smpl, got, base):
     T = lambda name: _t(got[name])
     _check_direct_stages(ck, oracle, sd, got, base)
     with oracle.float64():
-        ck.conv(B + "conv1.weight", "stem_conv1", got["stem_conv1"], oracle.conv_bn(_t(base), sd, B + "conv1.weight", B + "bn1", stride=2, relu=True))
+        ck.conv(B + "conv1.weight", "stem_conv1", got["stem_conv1"], oracle.conv_bn(_t(base), sd, B + "conv1.weight", B + "bn1", stride=2, relu=True),
+                own=dict(x=base, bn=B + "bn1", stride=2, relu=True))
         # the four BasicBlocks of every branch: each convolution from its own tapped input (and the block's tapped input as the residual)
         for stage, mi, nb in MODULES:
             for b in range(nb):
                 for k in range(4):
                     x_in, c1, out = _block_io(stage, mi, b, k, nb)
                     q = f"{B}{stage}.{mi}.branches.{b}.{k}."
-                    ck.conv(q + "conv1.weight", c1, got[c1], oracle.conv_bn(T(x_in), sd, q + "conv1.weight", q + "bn1", relu=True))
-                    ck.conv(q + "conv2.weight", out, got[out], oracle.conv_bn(T(c1), sd, q + "conv2.weight", q + "bn2", relu=True, residual=T(x_in)))
+                    ck.conv(q + "conv1.weight", c1, got[c1], oracle.conv_bn(T(x_in), sd, q + "conv1.weight", q + "bn1", relu=True),
+                            own=dict(x=got[x_in], bn=q + "bn1", relu=True))
+                    ck.conv(q + "conv2.weight", out, got[out], oracle.conv_bn(T(c1), sd, q + "conv2.weight", q + "bn2", relu=True, residual=T(x_in)),
+                            own=dict(x=got[c1], bn=q + "bn2", relu=True, residual=got[x_in]))
         # upsample heads: bilinear x2 from the previous tap, the 3x3 from the bilinear tap
         for idx, layers, br in HEADS:
             prev = f"stage4.2.y{br}"
@@ -206,7 +241,8 @@ def _check_all_stages(ck, oracle, sd, smpl, got, base):
                 nm, q = f"up{idx}.{l}", f"{B}upsample_stage_{idx}."
                 ck("bilinear", nm + ".bilinear", got[nm + ".bilinear"], oracle.upsample_bilinear2x(T(prev)))
                 ck.conv(q + f"{4 * l + 1}.weight", nm + ".conv", got[nm + ".conv"],
-                        oracle.conv_bn(T(nm + ".bilinear"), sd, q + f"{4 * l + 1}.weight", q + f"{4 * l + 2}", relu=True))
+                        oracle.conv_bn(T(nm + ".bilinear"), sd, q + f"{4 * l + 1}.weight", q + f"{4 * l + 2}", relu=True),
+                        own=dict(x=got[nm + ".bilinear"], bn=q + f"{4 * l + 2}", relu=True))
                 prev = nm + ".conv"
         # cat: the four slices ARE the taps (stage4.2's y0 is written into it, the heads' last convolutions too)
         parts = ["stage4.2.y0", "up2.0.conv", "up3.1.conv", "up4.2.conv"]
@@ -215,13 +251,18 @@ def _check_all_stages(ck, oracle, sd, smpl, got, base):
         hd = "head."
         ref_first = np.concatenate([_np(oracle.conv_bn(T("cat"), sd, hd + f"{b}.0.weight", hd + f"{b}.1", relu=True))
                                     for b in ("keypoint_deconv_layers", "smpl_deconv_layers")], 1)
-        ck.conv(hd + "keypoint_deconv_layers.0.weight", "head.first", got["head.first"], ref_first)
+        ck.conv(hd + "keypoint_deconv_layers.0.weight", "head.first", got["head.first"], ref_first,
+                own=dict(x=got["cat"], relu=True, keys=[hd + f"{b}.0.weight" for b in ("keypoint_deconv_layers", "smpl_deconv_layers")],
+                         bns=[hd + f"{b}.1" for b in ("keypoint_deconv_layers", "smpl_deconv_layers")]))
         ck.conv(hd + "keypoint_deconv_layers.3.weight", "head.part_feats", got["head.part_feats"],
-                oracle.conv_bn(_t(got["head.first"][:, :128]), sd, hd + "keypoint_deconv_layers.3.weight", hd + "keypoint_deconv_layers.4", relu=True))
+                oracle.conv_bn(_t(got["head.first"][:, :128]), sd, hd + "keypoint_deconv_layers.3.weight", hd + "keypoint_deconv_layers.4", relu=True),
+                own=dict(x=got["head.first"][:, :128], bn=hd + "keypoint_deconv_layers.4", relu=True))
         ck.conv(hd + "smpl_deconv_layers.3.weight", "head.smpl_feats", got["head.smpl_feats"],
-                oracle.conv_bn(_t(got["head.first"][:, 128:]), sd, hd + "smpl_deconv_layers.3.weight", hd + "smpl_deconv_layers.4", relu=True))
+                oracle.conv_bn(_t(got["head.first"][:, 128:]), sd, hd + "smpl_deconv_layers.3.weight", hd + "smpl_deconv_layers.4", relu=True),
+                own=dict(x=got["head.first"][:, 128:], bn=hd + "smpl_deconv_layers.4", relu=True))
         ck.conv(hd + "keypoint_final_layer.weight", "head.heat", got["head.heat"],
-                oracle.conv2d(T("head.part_feats"), sd[hd + "keypoint_final_layer.weight"], bias=sd[hd + "keypoint_final_layer.bias"]))
+                oracle.conv2d(T("head.part_feats"), sd[hd + "keypoint_final_layer.weight"], bias=sd[hd + "keypoint_final_layer.bias"]),
+                own=dict(x=got["head.part_feats"], bias=hd + "keypoint_final_layer.bias"))
         # attention pooling from the tapped heat / feature maps
         attn = got["head.heat"][:, 1:]
         for k, feat in (("point_local_feat", "head.smpl_feats"), ("cam_shape_feats", "head.cam_shape")):
@@ -326,7 +367,7 @@ def test_every_fp32_launch_matches_float64_oracle_on_its_own_input(pkg, oracle, 
     assert not differ, f"copies of a frame differ at {n} frames: {differ}"
     by_key = _forms_by_key(forms)
     _assert_forms(n, by_key)
-    ck = Checker(by_key)
+    ck = Checker(by_key, synth_weights, elements=2 if n == 16 else 0)       # the first two of the eight distinct frames, every convolution launch
     _check_all_stages(ck, oracle, synth_weights, synth_smpl, got, base)
     _end_to_end(oracle, synth_weights, synth_smpl, got, base)
     print(f"n={n} worst err / bound per family: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(ck.worst.items())))

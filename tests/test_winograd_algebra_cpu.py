@@ -6,16 +6,7 @@ every F(4x4,3x3) kernel -- and in wino4_transform_filter (G; csrc/conv_wino4.hip
 import numpy as np
 import pytest
 
-F23 = dict(
-    BT=np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64),
-    G=np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64),
-    AT=np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64), m=2)
-F43 = dict(
-    BT=np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0],
-                 [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]], np.float64),
-    G=np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6],
-                [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], np.float64),
-    AT=np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], np.float64), m=4)
+from .helpers.conv_checks import F23, F43                 # the matrices live with the yardstick of the convolutions
 
 
 def direct(d, g):
