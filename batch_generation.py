@@ -34,6 +34,12 @@ long and wide enough (GRNet.gait_turns on the device; the threshold
 output) -- and makes the step and stride columns of --gait again over the intervals that are wholly straight walking: <outpath>_turns.json, and
 'gait_phase' in the database.  Reported, never judged; the heading assumes a level camera.
 
+--gait_contacts (opt-in, with --gait) finds when both feet are on the ground -- low runs of the speed of the vector from one ankle to the other, which
+does not depend on the root and stands still while both feet do, their edges placed between frames, each run led by the foot whose heel strike --gait
+found beside it (GRNet.gait_contacts on the device; the thresholds are unvalidated on the model's output, and smoothing shortens the
+runs) -- and from them double-support, single-support, swing and stance time: <outpath>_contacts.json, and 'gait_support' in the database.
+Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -397,10 +403,61 @@ class WindowTurns:
         return path
 
 
+class WindowContacts:
+    """--gait_contacts: one gait_contacts call per database window on rank 0, directly after WindowGait's, on the same joints and on the events that
+    call returned (model.gait_contacts; on_host, or a model without the method: pipeline.gait_contacts after a download).  Per video the columns of
+    pipeline.CONTACT_COLUMNS plus 'runs', the list of its stored attributed runs keyed by pipeline.CONTACT_RUN_COLUMNS.  The joints are
+    pipeline.GAIT_JOINTS_KINECTV2, fps is WindowGait's.  The thresholds are unvalidated on the model's output; nothing is judged."""
+
+    def __init__(self, pipe, model, on_host, fps=20.0, sigma=0.0, fraction=0.25, speed=0.0, reach=2, max_frames=20):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_contacts") else model.gait_contacts
+        self.kw = dict(fps=float(fps), sigma=float(sigma), fraction=float(fraction), speed=float(speed), reach=int(reach), max_frames=int(max_frames))
+        self.videos = {}
+
+    def add_window(self, keys, j3, lengths, events):
+        """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths and the events (sum T,) -> per video the
+        phases (T,) uint8."""
+        if not keys:
+            return []
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, lengths=lengths, **self.kw).items()}
+        else:
+            ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
+            out = self.pipe.gait_contacts(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit):
+            return "none" if v is None else format(v, form) + unit
+        phases, a = [], 0
+        for key, T, row, table in zip(keys, lengths, out["per_sequence"], out["runs"]):
+            phases.append(out["phase"][a:a + T].astype(np.uint8))
+            video = {name: number(v) for name, v in zip(self.pipe.CONTACT_COLUMNS, row)}
+            video["runs"] = [{name: number(v) for name, v in zip(self.pipe.CONTACT_RUN_COLUMNS, run)} for run in table if run[2] == 1 or run[2] == -1]
+            self.videos[key] = video
+            print(f"Contacts: video {key}, {int(row[3] + row[4])} double supports, double-support time {shown(video['double_support_time_mean'], '.3f', ' s')} "
+                  f"({shown(video['double_support_share_mean'], '.1f', ' %')} of the stride), single-support time "
+                  f"{shown(video['single_support_time_mean'], '.3f', ' s')}, left / right asymmetry {shown(video['double_support_asymmetry'], '.1f', ' %')}.")
+            a += T
+        return phases
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save contacts of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None):
-    """turns: {'sigma', 'edge_rate', 'peak_rate', 'min_angle', 'min_frames', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None):
+    """contacts: {'sigma', 'fraction', 'speed', 'reach', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the
+    double supports of every video and its support, swing and stance times (WindowContacts), written to contacts['out'] (default: outpath with
+    _contacts.json); the database gains 'gait_support' (N,) uint8 (0 moving, 1 left-led double support, 2 right-led, 3 static and unattributed, 4 unknown).
+    turns: {'sigma', 'edge_rate', 'peak_rate', 'min_angle', 'min_frames', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
     takes) -- also the turns of every video and its gait parameters over straight walking alone (WindowTurns), written to turns['out'] (default:
     outpath with _turns.json); the database gains 'gait_phase' (N,) uint8 (0 straight, 1 left turn, 2 right turn, 3 unknown).
     kinematics: {'sigma', 'min_stride', 'max_stride', 'on_host', 'out'} (each optional; needs gait) -- also the joint angles per gait cycle of every
@@ -477,6 +534,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     rounds = WindowTurns(pipe, model, turns.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                          **{k: turns[k] for k in ("sigma", "edge_rate", "peak_rate", "min_angle", "min_frames", "max_frames") if turns.get(k) is not None}) \
         if turns is not None and rank == 0 else None
+    if contacts is not None and gait is None:
+        raise ValueError("contacts needs gait: it runs on the events of that call")
+    stands = WindowContacts(pipe, model, contacts.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
+                            **{k: contacts[k] for k in ("sigma", "fraction", "speed", "reach", "max_frames") if contacts.get(k) is not None}) \
+        if contacts is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -530,6 +592,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         if angles is not None and vids:
             angles.add_window([v[0] for v in vids], *walk.window)
         gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
+        gait_support = stands.add_window([v[0] for v in vids], *walk.window) if stands is not None and vids else None
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -542,6 +605,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                     extra["gait_events"] = gait_events[vi]
                 if gait_phase is not None:
                     extra["gait_phase"] = gait_phase[vi]
+                if gait_support is not None:
+                    extra["gait_support"] = gait_support[vi]
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -557,6 +622,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         angles.write(kinematics.get("out") or osp.splitext(outpath)[0] + "_kinematics.json")
     if rounds is not None:
         rounds.write(turns.get("out") or osp.splitext(outpath)[0] + "_turns.json")
+    if stands is not None:
+        stands.write(contacts.get("out") or osp.splitext(outpath)[0] + "_contacts.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -622,6 +689,18 @@ def main(argv=None):
     p.add_argument("--turns_min_duration", type=float, default=None, help="with --gait_turns: the shortest turn in seconds, made frames through --gait_fps (default 0.5)")
     p.add_argument("--turns_max_duration", type=float, default=None, help="with --gait_turns: the longest turn in seconds, made frames through --gait_fps (default 10)")
     p.add_argument("--turns_on_host", action="store_true", help="with --gait_turns: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_contacts", action="store_true", help="with --gait: when both feet are on the ground (low runs of the speed of the vector from one ankle to the "
+                   "other, led by the heel strikes of --gait) and double-support, single-support, swing and stance time: 'gait_support' (N,) in the database, "
+                   "<outpath>_contacts.json, one line per video; the thresholds are unvalidated on the model's output")
+    p.add_argument("--contacts_out", type=str, default="", help="with --gait_contacts: the JSON file (default: --outpath with _contacts.json)")
+    p.add_argument("--contacts_sigma", type=float, default=None, help="with --gait_contacts: sigma in frames of the Gaussian over the inter-foot vector, 0 (none) to 16 "
+                   "(default 0: smoothing shortens the runs)")
+    p.add_argument("--contacts_fraction", type=float, default=None, help="with --gait_contacts: static is below this share of the mean inter-foot speed (default 0.25)")
+    p.add_argument("--contacts_speed", type=float, default=None, help="with --gait_contacts: above 0, static is below this many metres a second instead (default 0)")
+    p.add_argument("--contacts_reach", type=int, default=None, help="with --gait_contacts: a heel strike leads a run within this many frames of it, 0 to 8 (default 2)")
+    p.add_argument("--contacts_max_duration", type=float, default=None, help="with --gait_contacts: the longest double support in seconds, made frames through --gait_fps "
+                   "(default 1.0); a longer run is standing")
+    p.add_argument("--contacts_on_host", action="store_true", help="with --gait_contacts: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -704,6 +783,26 @@ def main(argv=None):
             sys.exit("batch_generation.py: --turns_min_duration and --turns_max_duration must be seconds with 0 < min <= max")
         fps = 20.0 if a.gait_fps is None else a.gait_fps
         turn_frames = (max(1, int(round(lo * fps))), max(1, int(round(hi * fps))))       # whole frames, the nearest
+    if a.gait_contacts and not a.gait:
+        sys.exit("batch_generation.py: --gait_contacts belongs to --gait, which was not given (it runs on the events of that call)")
+    for flag, given in (("--contacts_out", bool(a.contacts_out)), ("--contacts_sigma", a.contacts_sigma is not None), ("--contacts_fraction", a.contacts_fraction is not None),
+                        ("--contacts_speed", a.contacts_speed is not None), ("--contacts_reach", a.contacts_reach is not None),
+                        ("--contacts_max_duration", a.contacts_max_duration is not None), ("--contacts_on_host", a.contacts_on_host)):
+        if given and not a.gait_contacts:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_contacts, which was not given")
+    if a.contacts_sigma is not None and not (np.isfinite(a.contacts_sigma) and 0 <= a.contacts_sigma <= 16):
+        sys.exit("batch_generation.py: --contacts_sigma must be within 0 to 16")
+    share, fixed = 0.25 if a.contacts_fraction is None else a.contacts_fraction, 0.0 if a.contacts_speed is None else a.contacts_speed
+    if a.gait_contacts and not (np.isfinite(share) and np.isfinite(fixed) and share >= 0 and fixed >= 0 and (share > 0 or fixed > 0)):
+        sys.exit("batch_generation.py: --contacts_fraction and --contacts_speed must not be negative, and not both zero")
+    if a.contacts_reach is not None and not 0 <= a.contacts_reach <= 8:
+        sys.exit("batch_generation.py: --contacts_reach must be within 0 to 8 frames")
+    contact_frames = None
+    if a.gait_contacts:
+        longest = 1.0 if a.contacts_max_duration is None else a.contacts_max_duration
+        if not (np.isfinite(longest) and longest > 0):
+            sys.exit("batch_generation.py: --contacts_max_duration must be a positive number of seconds")
+        contact_frames = max(1, int(round(longest * (20.0 if a.gait_fps is None else a.gait_fps))))       # whole frames, the nearest
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -725,10 +824,13 @@ def main(argv=None):
                   "out": a.kinematics_out or None} if a.gait_kinematics else None
     turns = {"sigma": a.turns_sigma, "edge_rate": a.turns_edge_rate, "peak_rate": a.turns_peak_rate, "min_angle": a.turns_min_angle, "min_frames": turn_frames[0],
              "max_frames": turn_frames[1], "on_host": a.turns_on_host, "out": a.turns_out or None} if a.gait_turns else None
+    contacts = {"sigma": a.contacts_sigma, "fraction": a.contacts_fraction, "speed": a.contacts_speed, "reach": a.contacts_reach, "max_frames": contact_frames,
+                "on_host": a.contacts_on_host, "out": a.contacts_out or None} if a.gait_contacts else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
-                 **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}))
+                 **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
+                 **({"contacts": contacts} if contacts is not None else {}))
 
 
 if __name__ == "__main__":

@@ -699,6 +699,55 @@ int grnet_op_gait_turn_runs(grnet_t* h, const double* rates_dev, const int32_t* 
                             int n_seq, double fps, double edge_rate, double peak_rate, double min_angle, int min_frames, int max_frames, int max_turns,
                             int32_t* phase_dev, double* turns_dev, double* per_seq_dev, void* stream);
 
+/* ---- foot contact phases and double support (csrc/gait_contacts_kernels.hip, csrc/gait_contacts.h) ---------------------------------
+ * When both feet are on the ground, and from that double-support, single-support, swing and stance time.  Called directly after
+ * grnet_gait_parameters on the same joints and on its events.  The reference has no such code: DESIGN.md 4.14 is the specification.  The joints are
+ * root-relative, so no foot's speed in the world is known; the vector from one ankle to the other does not depend on the root and stands still
+ * while both feet do.  The thresholds are UNVALIDATED on the model's output, and smoothing SHORTENS the runs (DESIGN.md 4.14 has the figures), which
+ * is why sigma defaults to 0 in the Python layers.
+ * joints3d_dev float32 (sum T, J, 3), frame_offsets_host and joints_host as for grnet_gait_parameters (all 8 indices are checked; entries 4 and 5,
+ * the ankles, are read); events_dev int32 (sum T): its events, of which bits 0 and 1, the heel strikes, are read.  Everything is float64, one
+ * rounding per operation; every test is a comparison, false for NaN.  An INTERVAL k of a sequence lies between its frames k and k + 1, 0 <= k <= T-2.
+ *   vector    d(t) = left ankle - right ankle; then (sigma > 0; <= 16) grnet_track_boxes' Gaussian over each of its three columns inside the
+ *             sequence; a NaN spreads as far as the kernel reaches
+ *   speed     s(k) = sqrt((dx^2 + dy^2) + dz^2) fps of d(k+1) - d(k), in metres a second, sitting at time k + 1/2; row T-1 of a sequence is NaN
+ *   threshold thr = speed where speed > 0, else fraction * (S / n): n the number of finite s of the sequence, S their sum in a FIXED SHAPE --
+ *             blocks of 64 consecutive intervals aligned to the sequence, inside a block a balanced tree over adjacent pairs (0+1, 2+3, ..., then
+ *             pairs of those), a non-finite or missing entry +0.0, the block sums added in time order from +0.0; n = 0: NaN, and no run
+ *   runs      an interval is static where s(k) < thr; a run is a maximal stretch [a, b] of static intervals; it is CLOSED where a >= 1, b <= T-3 and
+ *             s(a-1) and s(b+1) are finite, and then t_start = (a - 0.5) + (s(a-1) - thr) / (s(a-1) - s(a)) and
+ *             t_end = (b + 0.5) + (thr - s(b)) / (s(b+1) - s(b)), in frames
+ *   lead      a closed run of at most max_frames intervals is a double support LED by foot X where some frame of [a - reach, b + 1 + reach], cut to
+ *             the sequence, holds a heel strike of X and none holds one of the other foot; the earliest such strike is recorded.  Every other run
+ *             is unattributed: open, too long (standing), struck by both feet or by neither.
+ * per_frame_dev (sum T, 4) float64 = [s, d_x, d_y, d_z as smoothed].  phase_dev (sum T) int32, of the interval that begins at the frame: 0 moving, 1
+ * static and left-led, 2 static and right-led, 3 static and unattributed, 4 s is NaN (the last row of every sequence).  runs_dev (n_seq, max_runs, 6)
+ * float64, ALL static runs in time order: [t_start, t_end, +1 left / -1 right / 0 unattributed, heel-strike frame, (t_end - t_start) / fps, min s over
+ * the run]; of an open run columns 0, 1 and 4 are NaN, of an unattributed one column 3; rows past the count are NaN, runs past max_runs are counted
+ * and used in the row but not stored.
+ * per_seq_dev (n_seq, 20) float64: [0] thr; [1] S / n, about twice the walking speed; [2] static runs; [3, 4] left-led and right-led double
+ * supports; [5] unattributed runs; [6, 7] double-support time in seconds, mean and SD over the attributed runs in time order; [8, 9] its mean
+ * left-led and right-led; [10] 100 |L - R| / (0.5 (L + R)); then over the STRIDES -- three consecutive static runs R0, R', R1 led by X, the other
+ * foot, X (an unattributed run between breaks the chain), the left foot's first -- [11] their number; [12, 13] stride time (start R1 - start R0) mean
+ * and SD; [14, 15, 16] the means of stance (end R' - start R0), swing (start R1 - end R') and single support (start R' - end R0), all in seconds;
+ * [17] the mean of 100 stance / stride; [18] the mean of 100 (|R0| + |R'|) / stride; [19] 100 [13] / [12].  Means are sums in the stated order over
+ * the count, SDs two-pass with ddof = 0; a column is NaN where its count is 0.
+ * No filter or search crosses a sequence; fixed orders, no atomics: a sequence's outputs have the same bits whether it travels alone or with others.
+ * Needs no weights.  At most three launches (two with sigma = 0) behind one small copy from pinned memory, whatever n_seq and T; no host
+ * synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer, J < 1, a table index outside [0, J) (all 8 are
+ * checked), n_seq outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, fps not positive and finite, a negative, non-finite or too
+ * large sigma, a negative or non-finite fraction or speed, fraction and speed both zero, reach outside [0, 8], max_frames < 1, max_runs outside
+ * [1, 512].
+ * grnet_op_gait_contact_runs: the threshold, runs, phases, the run table and the row alone (test hook) on speeds_dev float64 (sum T), whose last
+ * entry of every sequence is not read. */
+int grnet_gait_contacts(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                        const int32_t* events_dev, double fps, double sigma, double fraction, double speed, int reach, int max_frames, int max_runs,
+                        double* per_frame_dev, int32_t* phase_dev, double* runs_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_contact_runs(grnet_t* h, const double* speeds_dev, const int32_t* events_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                               double fraction, double speed, int reach, int max_frames, int max_runs, int32_t* phase_dev, double* runs_dev,
+                               double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -429,6 +429,21 @@ hipError_t launch_turn_rates(const int* off, int n_seq, const double* weights, i
 hipError_t launch_turn_sequences(const int* off, int n_seq, const TurnRule& rule, const double* per_frame, const int* events, const double* gait_rows,
                                  unsigned long long* words, size_t mask_words, int* phase, double* turns, double* per_seq, hipStream_t s);
 
+// Foot contact phases and double support (csrc/gait_contacts_kernels.hip, compiled without fma contraction; the arithmetic: csrc/gait_contacts.h;
+// DESIGN 4.14) ----
+struct ContactRule;                        // gait_contacts.h: fps, the threshold's fraction or speed, the attribution's reach and limits
+// one lane per frame: per_frame (frames,4) = [s, d_x, d_y, d_z]; raw null: no Gaussian follows and s is made here, else raw (3,frames) gets the
+// vectors and per_frame is not written; off: n_seq + 1 frame offsets ON THE DEVICE; tab: its ankles (entries 4 and 5) are read
+hipError_t launch_contact_frames(const int* off, int n_seq, const float* joints, int J, int frames, const GaitTable& tab, double fps, double* raw,
+                                 double* per_frame, hipStream_t s);
+// a workgroup per (sequence, column): the Gaussian of raw (3,frames) into columns 1 .. 3 of per_frame
+hipError_t launch_contact_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
+// one workgroup per sequence on per_frame (frames,4) -- make_s: s is made from its smoothed vectors first -- or, per_frame null, on speeds (frames), and
+// on the gait call's events (frames): phase (frames), runs (n_seq,max_runs,6), per_seq (n_seq,20); words: (kContactMaskSets + 1) (gait_contacts.h) *
+// mask_words (gait_mask_words), the last set holding the block sums
+hipError_t launch_contact_sequences(const int* off, int n_seq, const ContactRule& rule, double* per_frame, const double* speeds, bool make_s, const int* events,
+                                    unsigned long long* words, size_t mask_words, int* phase, double* runs, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1244,6 +1244,63 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_turn_runs")
         return out
 
+    # ------------------------------------------------------------------ foot contact phases and double support
+    def _contact_inputs(self, n, events, reach, max_frames, max_runs):
+        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
+        if tuple(ev.shape) != (n,):
+            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        self._whole_frames(reach=reach, max_frames=max_frames, max_runs=max_runs)
+        if not 1 <= int(max_runs) <= 512:
+            raise ValueError(f"max_runs {max_runs} outside [1, 512]")      # the run table is allocated here: a size the C ABI would refuse is refused first
+        return ev
+
+    def _contact_outputs(self, n, n_seq, max_runs):
+        return {"phase": torch.empty(n, dtype=torch.int32, device=self.device),
+                "runs": torch.empty(n_seq, int(max_runs), 6, dtype=torch.float64, device=self.device),
+                "per_sequence": torch.empty(n_seq, 20, dtype=torch.float64, device=self.device)}
+
+    def gait_contacts(self, joints3d, events, lengths=None, fps=20.0, sigma=0.0, fraction=0.25, speed=0.0, reach=2, max_frames=20, max_runs=128,
+                      joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Foot contact phases and double support of every sequence on the device (grnet_gait_contacts; the rules and the columns: DESIGN 4.14,
+        pipeline.CONTACT_COLUMNS).  Called after gait_parameters on the same joints3d, lengths and joints, with its `events` (taken as int32).  The
+        speed s of the vector from the right ankle to the left one (metres a second; its three columns smoothed by sigma frames first, 0: none,
+        <= 16) is about zero while both feet stand; an interval is static where s < fraction * mean s (or < speed, where speed > 0), a maximal run
+        of static intervals whose edges lie inside the sequence is closed, and a closed run of at most max_frames intervals is a double support led
+        by the foot whose heel strike alone lies within reach frames of it.  The thresholds are unvalidated on the model's output; smoothing
+        shortens the runs.  Returns a dict of device tensors: per_frame (n,4) float64 [s, d_x, d_y, d_z]; phase (n,) int32 -- 0 moving, 1 left-led,
+        2 right-led, 3 static and unattributed, 4 s is NaN; runs (n_seq,max_runs,6) float64; per_sequence (n_seq,20) float64.  Works before
+        finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
+        if table.size != 8:
+            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        ev = self._contact_inputs(n, events, reach, max_frames, max_runs)
+        off = self._sequence_offsets(n, lengths, "joints3d")
+        n_seq = len(off) - 1
+        out = self._contact_outputs(n, n_seq, max_runs)
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_contacts(self._h, j.data_ptr(), j.shape[1], _i32p(off), n_seq, _i32p(table), ev.data_ptr(), float(fps), float(sigma),
+                                           float(fraction), float(speed), int(reach), int(max_frames), int(max_runs), out["per_frame"].data_ptr(),
+                                           out["phase"].data_ptr(), out["runs"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_contacts")
+        return out
+
+    def op_gait_contact_runs(self, speeds, events, lengths=None, fps=20.0, fraction=0.25, speed=0.0, reach=2, max_frames=20, max_runs=128):
+        """Rules 3 to 9 of gait_contacts alone (grnet_op_gait_contact_runs): speeds (n,) float64 (the last entry of every sequence is not read) and
+        events (n,), one sequence or `lengths` of them lying back to back -> {phase, runs, per_sequence} on the device."""
+        x = self._rows_input(speeds, "speeds", (), torch.float64)
+        n = x.shape[0]
+        ev = self._contact_inputs(n, events, reach, max_frames, max_runs)
+        off = self._sequence_offsets(n, lengths, "speeds")
+        n_seq = len(off) - 1
+        out = self._contact_outputs(n, n_seq, max_runs)
+        rc = self._lib.grnet_op_gait_contact_runs(self._h, x.data_ptr(), ev.data_ptr(), _i32p(off), n_seq, float(fps), float(fraction), float(speed), int(reach),
+                                                  int(max_frames), int(max_runs), out["phase"].data_ptr(), out["runs"].data_ptr(),
+                                                  out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_contact_runs")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

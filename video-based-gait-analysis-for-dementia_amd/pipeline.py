@@ -1409,6 +1409,157 @@ def gait_turns(joints3d, events, gait_rows, lengths=None, fps=20.0, sigma=8.0, e
     return out
 
 
+# ----------------------------------------------------------------------------- foot contact phases and double support
+CONTACT_MOVING, CONTACT_LEFT, CONTACT_RIGHT, CONTACT_UNATTRIBUTED, CONTACT_NAN = 0, 1, 2, 3, 4          # an interval's phase, held by its first frame
+CONTACT_COLUMNS = ("threshold", "interfoot_speed_mean", "static_runs", "double_supports_left", "double_supports_right", "unattributed_runs",
+                   "double_support_time_mean", "double_support_time_sd", "double_support_time_left", "double_support_time_right",
+                   "double_support_asymmetry", "strides", "stride_time_mean", "stride_time_sd", "stance_time_mean", "swing_time_mean",
+                   "single_support_time_mean", "stance_share_mean", "double_support_share_mean", "stride_time_cv")
+CONTACT_RUN_COLUMNS = ("t_start", "t_end", "lead", "heel_strike_frame", "duration", "speed_min")
+
+
+def _contact_rule_check(fps, fraction, speed, reach, max_frames, max_runs):
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if not np.isfinite(fraction) or fraction < 0:
+        raise ValueError("fraction must be finite and not negative")
+    if not np.isfinite(speed) or speed < 0:
+        raise ValueError("speed must be finite and not negative")
+    if fraction == 0 and speed == 0:
+        raise ValueError("fraction and speed are both zero: no threshold")
+    if int(reach) != reach or int(max_frames) != max_frames or int(max_runs) != max_runs:
+        raise ValueError("reach, max_frames and max_runs must be whole numbers")
+    if not 0 <= reach <= 8:
+        raise ValueError(f"reach {reach} outside [0, 8]")
+    if max_frames < 1:
+        raise ValueError(f"max_frames {max_frames} < 1")
+    if not 1 <= max_runs <= 512:
+        raise ValueError(f"max_runs {max_runs} outside [1, 512]")
+
+
+def contact_tree_sum(s):
+    """Rule 3's sum of the finite entries of s (n,) in its fixed shape, as reshapes: blocks of 64 consecutive entries, inside a block adjacent pairs
+    (0+1, 2+3, ...), then pairs of those, a non-finite or missing entry +0.0; the block sums added in time order from +0.0 -> (S, count)."""
+    s = np.asarray(s, np.float64)
+    fin = np.isfinite(s)
+    x = np.concatenate([np.where(fin, s, 0.0), np.zeros((-s.size) % 64)]).reshape(-1, 64)
+    while x.shape[1] > 1:
+        x = x[:, 0::2] + x[:, 1::2]
+    return float(_kin_sum(x[:, 0])), int(np.count_nonzero(fin))
+
+
+def gait_contact_runs(speeds, events, lengths=None, fps=20.0, fraction=0.25, speed=0.0, reach=2, max_frames=20, max_runs=128):
+    """Rules 3 to 9 of DESIGN 4.14 on given speeds: the host statement of GRNet.op_gait_contact_runs.  speeds (n,) float64: entry k of a sequence is the
+    inter-foot speed of the interval between its frames k and k + 1 (the last entry of every sequence is not read); events (n,) as gait_parameters
+    returned them.  Returns {'phase': (n,) int32, 'runs': (n_seq,max_runs,6), columns CONTACT_RUN_COLUMNS, 'per_sequence': (n_seq,20), columns
+    CONTACT_COLUMNS}; every sum in the stated order, every comparison false for NaN."""
+    x = np.asarray(speeds, np.float64)
+    if x.ndim != 1 or x.shape[0] < 1:
+        raise ValueError(f"speeds must be (n,) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64)
+    lengths = _sequence_lengths(n, lengths)
+    _contact_rule_check(fps, fraction, speed, reach, max_frames, max_runs)
+    fps, fraction, speed, reach, max_frames, max_runs = float(fps), float(fraction), float(speed), int(reach), int(max_frames), int(max_runs)
+    phase = np.zeros(n, np.int32)
+    runs = np.full((len(lengths), max_runs, 6), np.nan)
+    per_seq = np.full((len(lengths), 20), np.nan)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            s, e, ph = x[f0:f0 + T - 1], ev[f0:f0 + T], phase[f0:f0 + T]
+            S, count = contact_tree_sum(s)
+            mean = S / count if count else np.nan
+            thr = speed if speed > 0 else fraction * mean
+            ph[T - 1] = CONTACT_NAN
+            ph[:T - 1][np.isnan(s)] = CONTACT_NAN
+            heel = [np.flatnonzero(e & GAIT_HEEL_L), np.flatnonzero(e & GAIT_HEEL_R)]
+            found = []                                         # (lead, t_start, t_end) of every static run in time order
+            for a, behind in _turn_runs_of(s < thr):
+                b = behind - 1
+                closed = a >= 1 and b <= T - 3 and bool(np.isfinite(s[a - 1])) and bool(np.isfinite(s[b + 1]))
+                t0 = t1 = strike = np.nan
+                lead = 0
+                if closed:
+                    t0 = (a - 0.5) + (s[a - 1] - thr) / (s[a - 1] - s[a])
+                    t1 = (b + 0.5) + (thr - s[b]) / (s[b + 1] - s[b])
+                    if b - a + 1 <= max_frames:
+                        lo, hi = max(a - reach, 0), min(b + 1 + reach, T - 1)
+                        hit = [h[(h >= lo) & (h <= hi)] for h in heel]
+                        if (hit[0].size > 0) != (hit[1].size > 0):
+                            lead = 1 if hit[0].size else -1
+                            strike = float(hit[0][0] if hit[0].size else hit[1][0])
+                ph[a:b + 1] = CONTACT_LEFT if lead > 0 else CONTACT_RIGHT if lead < 0 else CONTACT_UNATTRIBUTED
+                if len(found) < max_runs:
+                    runs[q, len(found)] = [t0, t1, float(lead), strike, (t1 - t0) / fps, s[a:b + 1].min()]
+                found.append((lead, t0, t1))
+            out = per_seq[q]
+            out[0], out[1], out[2] = thr, mean, len(found)
+            out[3], out[4] = sum(r[0] > 0 for r in found), sum(r[0] < 0 for r in found)
+            out[5] = out[2] - out[3] - out[4]
+            support = [(lead, (t1 - t0) / fps) for lead, t0, t1 in found if lead]
+            if support:
+                out[6], out[7] = _gait_mean_sd([d for _, d in support])
+                for col, sign in ((8, 1), (9, -1)):
+                    side = [d for lead, d in support if lead == sign]
+                    if side:
+                        out[col] = _gait_sum(side) / len(side)
+                if not np.isnan(out[8]) and not np.isnan(out[9]):
+                    out[10] = (100.0 * abs(out[8] - out[9])) / (0.5 * (out[8] + out[9]))
+            strides = []
+            for X in (1, -1):                                  # the left foot's strides first
+                for (l0, a0, b0), (l1, a1, b1), (l2, a2, _) in zip(found[:-2], found[1:-1], found[2:]):
+                    if l0 == X and l1 == -X and l2 == X:
+                        length = a2 - a0
+                        strides.append((length / fps, (b1 - a0) / fps, (a2 - b1) / fps, (a1 - b0) / fps, (100.0 * (b1 - a0)) / length,
+                                        (100.0 * ((b0 - a0) + (b1 - a1))) / length))
+            out[11] = len(strides)
+            if strides:
+                cols = list(zip(*strides))
+                out[12], out[13] = _gait_mean_sd(cols[0])
+                for col, values in zip((14, 15, 16, 17, 18), cols[1:]):
+                    out[col] = _gait_sum(values) / len(values)
+                out[19] = (100.0 * out[13]) / out[12]
+            f0 += T
+    return {"phase": phase, "runs": runs, "per_sequence": per_seq}
+
+
+def gait_contacts(joints3d, events, lengths=None, fps=20.0, sigma=0.0, fraction=0.25, speed=0.0, reach=2, max_frames=20, max_runs=128,
+                  joints=GAIT_JOINTS_KINECTV2):
+    """Foot contact phases and double support from 3D joints in numpy float64 (the rules: DESIGN 4.14; the thresholds are unvalidated on the model's
+    output): the host statement of GRNet.gait_contacts, same arguments, a dict of numpy arrays -- the same operations in the same order.  joints3d
+    (n,J,3) as gait_parameters takes them; events: its events; joints: its table, of which the two ankles are read.  per_frame (n,4) = [s, d_x, d_y,
+    d_z]: d = left ankle - right ankle, smoothed by sigma frames per column inside each sequence; s(k) = |d(k + 1) - d(k)| fps, NaN in the last row of
+    every sequence.  phase, runs, per_sequence: gait_contact_runs'."""
+    j3 = _widened(joints3d, "joints3d")
+    n, J = j3.shape[:2]
+    lengths = _sequence_lengths(n, lengths)
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    _contact_rule_check(fps, fraction, speed, reach, max_frames, max_runs)
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    per_frame = np.full((n, 4), np.nan)
+    with np.errstate(all="ignore"):
+        d = j3[:, tab[4]] - j3[:, tab[5]]
+        a = 0
+        for T in lengths:
+            seq = d[a:a + T]
+            if sigma > 0:
+                seq = np.stack([gauss_filter1d(seq[:, k], sigma) for k in range(3)], axis=1)
+            per_frame[a:a + T, 1:] = seq
+            step = seq[1:] - seq[:-1]
+            per_frame[a:a + T - 1, 0] = np.sqrt((step[:, 0] * step[:, 0] + step[:, 1] * step[:, 1]) + step[:, 2] * step[:, 2]) * float(fps)
+            a += T
+    out = gait_contact_runs(per_frame[:, 0], events, lengths, fps, fraction, speed, reach, max_frames, max_runs)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
