@@ -40,6 +40,12 @@ found beside it (GRNet.gait_contacts on the device; the thresholds 
 runs) -- and from them double-support, single-support, swing and stance time: <outpath>_contacts.json, and 'gait_support' in the database.
 Reported, never judged.
 
+--gait_regularity (opt-in, needs no --gait) reads step and stride regularity, their ratio -- a symmetry figure -- and a cadence off the autocorrelation of
+four body signals (the ankles' separation along the facing and along the trunk, the trunk's lean, the pelvis' height), with no events at all
+(GRNet.gait_regularity on the device; Moe-Nilssen and Helbostad 2004 on trunk accelerations; the defaults are unvalidated on the model's
+output): <outpath>_regularity.json.  The line prints its cadence beside --gait's: where the two disagree, the event rule failed on that video or the
+walk is not periodic.  With --gait_turns only straight walking counts.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -451,10 +457,72 @@ class WindowContacts:
         return path
 
 
+class WindowRegularity:
+    """--gait_regularity: one gait_regularity call per database window on rank 0, one sequence per video, on the joints the window's gather left on
+    the device (model.gait_regularity; on_host, or a model without the method: pipeline.gait_regularity after a download) -- with the window's
+    translations where --trajectory made them, and with --gait_turns' phase as `exclude`, so that only straight walking counts (straight_only).  It
+    needs no events and so no --gait.  Per video and channel (pipeline.REGULARITY_CHANNELS) the ten columns of pipeline.REGULARITY_COLUMNS, step_time
+    and stride_time in seconds, and the acf list.  The joints are pipeline.GAIT_JOINTS_KINECTV2.  The defaults are unvalidated on the model's output;
+    the results are reported and never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, max_lag=60, min_lag=4, min_peak=0.25, min_pairs=20):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_regularity") else model.gait_regularity
+        self.straight_only = bool(straight_only)
+        self.kw = dict(fps=float(fps), sigma=float(sigma), max_lag=int(max_lag), min_lag=int(min_lag), min_peak=float(min_peak), min_pairs=int(min_pairs))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None, whole=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None;
+        whole: WindowGait's videos, for the event cadence in the line, or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_regularity(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw)
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        fps = self.kw["fps"]
+        for key, rows, acf in zip(keys, out["per_sequence"], out["acf"]):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.REGULARITY_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.REGULARITY_COLUMNS, rows[c])}
+                video[name]["step_time"] = number(rows[c][3] / fps)
+                video[name]["stride_time"] = number(rows[c][6] / fps)
+                video[name]["acf"] = [number(v) for v in acf[c]]
+            self.videos[key] = video
+            sep = video["sep"]
+            events = "" if whole is None or key not in whole else f" (events: {shown(whole[key]['cadence'], '.1f', ' steps/min')})"
+            print(f"Regularity: video {key}, cadence {shown(sep['cadence'], '.1f', ' steps/min')} from the autocorrelation{events}, step regularity "
+                  f"{shown(sep['step_regularity'], '.3f')}, stride regularity {shown(sep['stride_regularity'], '.3f')}, symmetry {shown(sep['symmetry'], '.3f')}"
+                  f"{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait regularity of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None):
-    """contacts: {'sigma', 'fraction', 'speed', 'reach', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None):
+    """regularity: {'sigma', 'max_lag', 'min_lag', 'min_peak', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional, with 'fps'; needs no gait, whose
+    fps it takes where it has none) -- also the step and stride regularity, the symmetry and the autocorrelation cadence of every video (WindowRegularity), written to
+    regularity['out'] (default: outpath with _regularity.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
+    contacts: {'sigma', 'fraction', 'speed', 'reach', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the
     double supports of every video and its support, swing and stance times (WindowContacts), written to contacts['out'] (default: outpath with
     _contacts.json); the database gains 'gait_support' (N,) uint8 (0 moving, 1 left-led double support, 2 right-led, 3 static and unattributed, 4 unknown).
     turns: {'sigma', 'edge_rate', 'peak_rate', 'min_angle', 'min_frames', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
@@ -539,6 +607,10 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     stands = WindowContacts(pipe, model, contacts.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                             **{k: contacts[k] for k in ("sigma", "fraction", "speed", "reach", "max_frames") if contacts.get(k) is not None}) \
         if contacts is not None and rank == 0 else None
+    steady = WindowRegularity(pipe, model, regularity.get("on_host", False), not regularity.get("all_frames", False),
+                              **({"fps": gait["fps"]} if regularity.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
+                              **{k: regularity[k] for k in ("fps", "sigma", "max_lag", "min_lag", "min_peak", "min_pairs") if regularity.get(k) is not None}) \
+        if regularity is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -593,6 +665,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             angles.add_window([v[0] for v in vids], *walk.window)
         gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
         gait_support = stands.add_window([v[0] for v in vids], *walk.window) if stands is not None and vids else None
+        if steady is not None and vids:
+            steady.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -624,6 +698,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         rounds.write(turns.get("out") or osp.splitext(outpath)[0] + "_turns.json")
     if stands is not None:
         stands.write(contacts.get("out") or osp.splitext(outpath)[0] + "_contacts.json")
+    if steady is not None:
+        steady.write(regularity.get("out") or osp.splitext(outpath)[0] + "_regularity.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -701,6 +777,17 @@ def main(argv=None):
     p.add_argument("--contacts_max_duration", type=float, default=None, help="with --gait_contacts: the longest double support in seconds, made frames through --gait_fps "
                    "(default 1.0); a longer run is standing")
     p.add_argument("--contacts_on_host", action="store_true", help="with --gait_contacts: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_regularity", action="store_true", help="with --vid_folder (no --gait needed): step and stride regularity, symmetry and a cadence WITHOUT events, "
+                   "from the autocorrelation of four body signals (Moe-Nilssen and Helbostad 2004): <outpath>_regularity.json, one line per video; takes "
+                   "--gait_fps where given; with --gait_turns only straight walking counts; the defaults are unvalidated on the model's output")
+    p.add_argument("--regularity_out", type=str, default="", help="with --gait_regularity: the JSON file (default: --outpath with _regularity.json)")
+    p.add_argument("--regularity_sigma", type=float, default=None, help="with --gait_regularity: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--regularity_max_lag", type=int, default=None, help="with --gait_regularity: the largest lag in frames, 8 to 255 (default 60)")
+    p.add_argument("--regularity_min_lag", type=int, default=None, help="with --gait_regularity: the first peak is looked for from this lag on, 2 to the largest lag - 2 (default 4)")
+    p.add_argument("--regularity_min_peak", type=float, default=None, help="with --gait_regularity: the first peak is at least this high, above 0 up to 1 (default 0.25)")
+    p.add_argument("--regularity_min_pairs", type=int, default=None, help="with --gait_regularity: a lag with fewer pairs of frames is undefined, 2 to 2^20 (default 20)")
+    p.add_argument("--regularity_all_frames", action="store_true", help="with --gait_regularity and --gait_turns: count the frames of the turns too")
+    p.add_argument("--regularity_on_host", action="store_true", help="with --gait_regularity: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -737,7 +824,7 @@ def main(argv=None):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     for flag, given in (("--gait_out", bool(a.gait_out)), ("--gait_fps", a.gait_fps is not None), ("--gait_sigma", a.gait_sigma is not None),
                         ("--gait_window", a.gait_window is not None), ("--gait_min_excursion", a.gait_min_excursion is not None), ("--gait_on_host", a.gait_on_host)):
-        if given and not a.gait:
+        if given and not a.gait and not (flag == "--gait_fps" and a.gait_regularity):
             sys.exit(f"batch_generation.py: {flag} belongs to --gait, which was not given")
     if a.gait and not a.vid_folder:
         sys.exit("batch_generation.py: --gait needs --vid_folder (the frames whose joints it reads)")
@@ -803,6 +890,24 @@ def main(argv=None):
         if not (np.isfinite(longest) and longest > 0):
             sys.exit("batch_generation.py: --contacts_max_duration must be a positive number of seconds")
         contact_frames = max(1, int(round(longest * (20.0 if a.gait_fps is None else a.gait_fps))))       # whole frames, the nearest
+    for flag, given in (("--regularity_out", bool(a.regularity_out)), ("--regularity_sigma", a.regularity_sigma is not None),
+                        ("--regularity_max_lag", a.regularity_max_lag is not None), ("--regularity_min_lag", a.regularity_min_lag is not None),
+                        ("--regularity_min_peak", a.regularity_min_peak is not None), ("--regularity_min_pairs", a.regularity_min_pairs is not None),
+                        ("--regularity_all_frames", a.regularity_all_frames), ("--regularity_on_host", a.regularity_on_host)):
+        if given and not a.gait_regularity:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_regularity, which was not given")
+    if a.gait_regularity and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_regularity needs --vid_folder (the frames whose joints it reads)")
+    if a.regularity_sigma is not None and not (np.isfinite(a.regularity_sigma) and 0 <= a.regularity_sigma <= 16):
+        sys.exit("batch_generation.py: --regularity_sigma must be within 0 to 16")
+    if a.regularity_max_lag is not None and not 8 <= a.regularity_max_lag <= 255:
+        sys.exit("batch_generation.py: --regularity_max_lag must be within 8 to 255 frames")
+    if a.regularity_min_lag is not None and not 2 <= a.regularity_min_lag <= (60 if a.regularity_max_lag is None else a.regularity_max_lag) - 2:
+        sys.exit("batch_generation.py: --regularity_min_lag must be within 2 to --regularity_max_lag - 2 frames")
+    if a.regularity_min_peak is not None and not 0 < a.regularity_min_peak <= 1:
+        sys.exit("batch_generation.py: --regularity_min_peak must be above 0 and at most 1")
+    if a.regularity_min_pairs is not None and not 2 <= a.regularity_min_pairs <= 2 ** 20:
+        sys.exit("batch_generation.py: --regularity_min_pairs must be within 2 to 2^20")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -826,11 +931,14 @@ def main(argv=None):
              "max_frames": turn_frames[1], "on_host": a.turns_on_host, "out": a.turns_out or None} if a.gait_turns else None
     contacts = {"sigma": a.contacts_sigma, "fraction": a.contacts_fraction, "speed": a.contacts_speed, "reach": a.contacts_reach, "max_frames": contact_frames,
                 "on_host": a.contacts_on_host, "out": a.contacts_out or None} if a.gait_contacts else None
+    regularity = {"fps": a.gait_fps, "sigma": a.regularity_sigma, "max_lag": a.regularity_max_lag, "min_lag": a.regularity_min_lag, "min_peak": a.regularity_min_peak,
+                  "min_pairs": a.regularity_min_pairs, "all_frames": a.regularity_all_frames, "on_host": a.regularity_on_host,
+                  "out": a.regularity_out or None} if a.gait_regularity else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
                  **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
-                 **({"contacts": contacts} if contacts is not None else {}))
+                 **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}))
 
 
 if __name__ == "__main__":

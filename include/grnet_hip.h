@@ -748,6 +748,44 @@ int grnet_op_gait_contact_runs(grnet_t* h, const double* speeds_dev, const int32
                                double fraction, double speed, int reach, int max_frames, int max_runs, int32_t* phase_dev, double* runs_dev,
                                double* per_seq_dev, void* stream);
 
+/* Gait regularity and symmetry WITHOUT EVENTS, from the autocorrelation of four body signals (Moe-Nilssen and Helbostad 2004, who measure trunk
+ * accelerations with a sensor; these signals are joint positions of a pose model and the defaults are unvalidated on its output): step and stride
+ * time as the first two dominant lags, step and stride regularity as the coefficients there, their ratio as symmetry, and a cadence that is
+ * independent of the events of grnet_gait_parameters (which is the specification).  joints3d_dev (sum T, J, 3) float32, the n_seq
+ * sequences back to back, frame_offsets_host (n_seq + 1) and joints_host (8) as grnet_gait_parameters takes them (the two foot entries are checked
+ * but not read); trans_dev (sum T, 3) float64 or NULL; exclude_dev (sum T) int32 or NULL: a frame whose entry is not 0 does not count (the phase of
+ * grnet_gait_turns: only straight walking counts).  Float64, one rounding per operation:
+ *   signals  per frame, with the axes l, u, f, n of grnet_gait_parameters and u^ = u / |u|, a dot product ((x + y) + z):
+ *            [0] sep = (lankle - rankle) . f; [1] lift = (lankle - rankle) . u^; [2] sway = u^ . n; [3] bob = -(pelvis_y + trans_y).  0 .. 2 are NaN in
+ *            a frame without valid axes, 3 without trans or where the trans row is not finite.  0 .. 2 are ODD (a step is half a stride with the sign
+ *            turned), 3 is EVEN (it repeats every step).  sigma > 0 (<= 16): scipy's Gaussian over each channel inside its sequence; a NaN spreads.
+ *   validity a frame counts for a channel where its signal is finite and its exclude entry is 0; run(t) = the frames before t that do not count; a
+ *            pair (t, t + m) counts where both frames count and run(t) = run(t + m): no frame between them fails.
+ *   rho      n = the frames that count, mu = S / n with S their values added in time order from +0.0, d = x - mu; for m = 0 .. max_lag: N(m) = the
+ *            counting pairs, A(m) = (the sum of d(t) d(t + m) over them in time order from +0.0) / N(m), rho(m) = A(m) / A(0) -- NaN where
+ *            N(m) < min_pairs, N(0) < min_pairs or A(0) is not positive.  The unbiased estimator: it can pass 1 and is never clipped.
+ *   peaks    m is a local maximum where rho(m-1), rho(m), rho(m+1) are defined (1 <= m <= max_lag - 1), rho(m) > rho(m-1) and rho(m) >= rho(m+1); a
+ *            local minimum is one of -rho.  FIRST PEAK: the least m in [min_lag, max_lag - 1] that is a local maximum with rho(m) >= min_peak.
+ *            Odd channel: the first peak is the stride lag d2; the step lag d1 is the local minimum of least rho in [d2 - (3 d2)/4, d2 - d2/4]
+ *            (integer divisions; of a tie the earliest); step regularity -rho(d1).  Even channel: the first peak is d1; d2 is the local maximum of
+ *            largest rho in [2 d1 - d1/2, 2 d1 + d1/2] cut to [1, max_lag - 1]; step regularity rho(d1).  A lag not found is -1.
+ *   refined  lag m + 0.5 (a - c) / ((a - 2 b) + c) with a, b, c = rho(m-1), rho(m), rho(m+1); m where that denominator is 0.
+ * per_frame_dev (sum T, 4) float64: the signals as smoothed.  acf_dev (n_seq, 4, max_lag + 1) float64.  per_seq_dev (n_seq, 4, 10) float64: [0] n;
+ * [1] A(0); [2] d1; [3] d1 refined; [4] step regularity; [5] d2; [6] d2 refined; [7] stride regularity rho(d2); [8] symmetry [4] / [7] (NaN where [7] <=
+ * 0); [9] cadence 120 fps / [6], steps a minute.  Where rho(0) is not defined everything but [0] is NaN; what hangs on a lag not found is NaN.
+ * A workgroup per (sequence, channel), a lane per lag; fixed orders, no atomics: a sequence's outputs have the same bits alone or among others.
+ * Needs no weights.  At most three launches (two with sigma = 0) behind one small copy from pinned memory; no host synchronisation; the scratch is
+ * the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, fps not positive and finite, sigma outside [0, 16], max_lag outside [8, 255],
+ * min_lag outside [2, max_lag - 2], min_peak outside (0, 1], min_pairs outside [2, 2^20].  Nothing is refused on the data.
+ * grnet_op_gait_autocorr: validity, rho, peaks and the rows alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_regularity(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                          const double* trans_dev, const int32_t* exclude_dev, double fps, double sigma, int max_lag, int min_lag, double min_peak,
+                          int min_pairs, double* per_frame_dev, double* acf_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_autocorr(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                           int max_lag, int min_lag, double min_peak, int min_pairs, double* acf_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -444,6 +444,19 @@ hipError_t launch_contact_smooth(const int* off, int n_seq, const double* weight
 hipError_t launch_contact_sequences(const int* off, int n_seq, const ContactRule& rule, double* per_frame, const double* speeds, bool make_s, const int* events,
                                     unsigned long long* words, size_t mask_words, int* phase, double* runs, double* per_seq, hipStream_t s);
 
+// Gait regularity and symmetry from the autocorrelation of four body signals (csrc/gait_regularity_kernels.hip, compiled without fma contraction; the
+// arithmetic: csrc/gait_regularity.h) ----
+struct RegRule;                            // gait_regularity.h: fps, max_lag, min_lag, min_peak, min_pairs
+constexpr int kRegLdsFrames = 64 * kGaitLdsWords;      // frames of a sequence whose centred signal and run numbers the sequence kernel keeps in LDS: 4096
+// one lane per frame: the four signals into per_frame (frames,4), or, raw not null (a Gaussian follows), into raw (4,frames); trans (frames,3) or null
+hipError_t launch_reg_frames(const float* joints, int J, int frames, const GaitTable& tab, const double* trans, double* raw, double* per_frame, hipStream_t s);
+// a workgroup per (sequence, channel): the Gaussian of raw (4,frames) into per_frame
+hipError_t launch_reg_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
+// a workgroup per (sequence, channel) on rows (frames,4) and exclude (frames) or null: acf (n_seq,4,max_lag+1), per_seq (n_seq,4,10).  Where a sequence
+// has more than kRegLdsFrames frames: long_d (4,frames) float64, long_key (4,frames) int32 and words: 8 * mask_words (gait_mask_words); else null
+hipError_t launch_reg_sequences(const int* off, int n_seq, const RegRule& rule, const double* rows, const int* exclude, int frames, double* long_d, int* long_key,
+                                unsigned long long* words, size_t mask_words, double* acf, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1301,6 +1301,63 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_contact_runs")
         return out
 
+    # ------------------------------------------------------------------ gait regularity and symmetry from the autocorrelation
+    def _regularity_call(self, n, lengths, exclude, max_lag, min_lag, min_pairs, what):
+        """(exclude on the device or None, offsets, the acf and per_sequence tensors) of gait_regularity and its hook."""
+        self._whole_frames(max_lag=max_lag, min_lag=min_lag, min_pairs=min_pairs)
+        if not 8 <= int(max_lag) <= 255:                           # the size of acf is made of it here
+            raise ValueError(f"max_lag {max_lag} outside [8, 255]")
+        ex = None
+        if exclude is not None:
+            ex = torch.as_tensor(exclude).to(self.device, torch.int32).contiguous()
+            if tuple(ex.shape) != (n,):
+                raise ValueError(f"exclude must be ({n},), got {tuple(ex.shape)}")
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"acf": torch.empty(n_seq, 4, int(max_lag) + 1, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, 10, dtype=torch.float64, device=self.device)}
+        return ex, off, out
+
+    def gait_regularity(self, joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, max_lag=60, min_lag=4, min_peak=0.25, min_pairs=20,
+                        joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Gait regularity and symmetry of every sequence WITHOUT EVENTS, on the device (grnet_gait_regularity; the rules, channels and columns: DESIGN
+        4.15, pipeline.REGULARITY_CHANNELS, pipeline.REGULARITY_COLUMNS).  joints3d, lengths, trans and joints as gait_parameters takes them (the
+        foot entries are not read).  Four signals per frame -- the ankles' separation along the facing (sep) and along the trunk (lift), the trunk's
+        lean against the hip line (sway), the pelvis' height in the camera frame (bob, with trans alone) -- each smoothed by sigma frames (0: none,
+        <= 16), then per (sequence, channel) the unbiased autocorrelation over the lags 0 .. max_lag (8 .. 255) of the frames that count: those
+        whose signal is finite and whose `exclude` entry (sum T, taken as int32; gait_turns' phase: only straight walking counts) is 0, in pairs
+        that no other frame lies between.  The first local maximum of at least min_peak from min_lag on is the stride (odd channels) or the step
+        (bob); a lag with fewer than min_pairs pairs is undefined.  Returns a dict of device tensors: per_frame (n,4) float64; acf
+        (n_seq,4,max_lag+1) float64; per_sequence (n_seq,4,10) float64.  The defaults are unvalidated on the model's output.  Nothing is refused
+        on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
+        if table.size != 8:
+            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        t = None
+        if trans is not None:
+            t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
+            if tuple(t.shape) != (n, 3):
+                raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
+        ex, off, out = self._regularity_call(n, lengths, exclude, max_lag, min_lag, min_pairs, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_regularity(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                             None if ex is None else ex.data_ptr(), float(fps), float(sigma), int(max_lag), int(min_lag), float(min_peak),
+                                             int(min_pairs), out["per_frame"].data_ptr(), out["acf"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_regularity")
+        return out
+
+    def op_gait_autocorr(self, signals, lengths=None, exclude=None, fps=20.0, max_lag=60, min_lag=4, min_peak=0.25, min_pairs=20):
+        """Rules 4 to 8 of gait_regularity alone (grnet_op_gait_autocorr): signals (n,4) float64 and exclude (n,) or None, one sequence or `lengths`
+        of them lying back to back -> {acf, per_sequence} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, out = self._regularity_call(x.shape[0], lengths, exclude, max_lag, min_lag, min_pairs, "signals")
+        rc = self._lib.grnet_op_gait_autocorr(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps), int(max_lag),
+                                              int(min_lag), float(min_peak), int(min_pairs), out["acf"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_autocorr")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

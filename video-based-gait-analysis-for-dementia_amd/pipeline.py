@@ -1560,6 +1560,169 @@ def gait_contacts(joints3d, events, lengths=None, fps=20.0, sigma=0.0, fraction=
     return out
 
 
+# ----------------------------------------------------------------------------- gait regularity and symmetry from the autocorrelation
+REGULARITY_CHANNELS = ("sep", "lift", "sway", "bob")           # 0 .. 2 odd (a step is half a stride with the sign turned), 3 even (it repeats every step)
+REGULARITY_COLUMNS = ("n", "variance", "step_lag", "step_lag_refined", "step_regularity", "stride_lag", "stride_lag_refined", "stride_regularity",
+                      "symmetry", "cadence")
+
+
+def _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs):
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if int(max_lag) != max_lag or int(min_lag) != min_lag or int(min_pairs) != min_pairs:
+        raise ValueError("max_lag, min_lag and min_pairs must be whole numbers")
+    if not 8 <= max_lag <= 255:
+        raise ValueError(f"max_lag {max_lag} outside [8, 255]")
+    if not 2 <= min_lag <= max_lag - 2:
+        raise ValueError(f"min_lag {min_lag} outside [2, max_lag - 2]")
+    if not 0 < min_peak <= 1:
+        raise ValueError("min_peak outside (0, 1]")
+    if not 2 <= min_pairs <= 2 ** 20:
+        raise ValueError(f"min_pairs {min_pairs} outside [2, 2^20]")
+
+
+def _regularity_sum(values):
+    """The sum in the order given from +0.0, one rounding per addition."""
+    return float(np.cumsum(np.concatenate([[0.0], np.asarray(values, np.float64)]))[-1])
+
+
+def _regularity_refine(rho, m):
+    a, b, c = rho[m - 1], rho[m], rho[m + 1]
+    den = (a - 2.0 * b) + c
+    return float(m) if den == 0 else m + (0.5 * (a - c)) / den
+
+
+def gait_autocorr(signals, lengths=None, exclude=None, fps=20.0, max_lag=60, min_lag=4, min_peak=0.25, min_pairs=20, return_pairs=False):
+    """Rules 4 to 8 of DESIGN 4.15 on given signals: the host statement of GRNet.op_gait_autocorr.  signals (n,4) float64, columns
+    REGULARITY_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count.  Returns {'acf': (n_seq,4,max_lag+1), 'per_sequence':
+    (n_seq,4,10), columns REGULARITY_COLUMNS}; every sum in time order from +0.0, every comparison false for NaN.  return_pairs: also 'pairs'
+    (n_seq,4,max_lag+1) int64, the N(m) of rule 5."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs)
+    fps, L, min_lag, min_peak, min_pairs = float(fps), int(max_lag), int(min_lag), float(min_peak), int(min_pairs)
+    acf = np.full((len(lengths), 4, L + 1), np.nan)
+    per_seq = np.full((len(lengths), 4, 10), np.nan)
+    pairs = np.zeros((len(lengths), 4, L + 1), np.int64)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                run = np.cumsum(~valid) - (~valid)                 # the invalid frames before t
+                count = int(valid.sum())
+                out, rho = per_seq[q, ch], acf[q, ch]
+                out[0] = count
+                if count == 0:
+                    continue
+                d = s - _regularity_sum(s[valid]) / count
+                sums, N = np.zeros(L + 1), np.zeros(L + 1, np.int64)
+                for m in range(min(L, T - 1) + 1):
+                    pair = valid[:T - m] & valid[m:] & (run[:T - m] == run[m:])
+                    N[m] = int(pair.sum())
+                    sums[m] = _regularity_sum(d[:T - m][pair] * d[m:][pair])
+                pairs[q, ch] = N
+                if N[0] < min_pairs or not sums[0] / N[0] > 0:
+                    continue
+                A0 = sums[0] / N[0]
+                ok = N >= min_pairs
+                rho[ok] = (sums[ok] / N[ok]) / A0
+                out[1] = A0
+                inner = np.arange(1, L)
+                is_max, is_min = np.zeros(L + 1, bool), np.zeros(L + 1, bool)
+                is_max[inner] = (rho[inner] > rho[inner - 1]) & (rho[inner] >= rho[inner + 1])
+                is_min[inner] = (-rho[inner] > -rho[inner - 1]) & (-rho[inner] >= -rho[inner + 1])
+                lag = np.arange(L + 1)
+                first = np.flatnonzero(is_max & (rho >= min_peak) & (lag >= min_lag) & (lag <= L - 1))
+                first = int(first[0]) if first.size else -1
+                d1 = d2 = -1
+                odd = ch < 3
+                if odd:
+                    d2 = first
+                    if d2 >= 0:
+                        cand = np.flatnonzero(is_min & (lag >= d2 - 3 * d2 // 4) & (lag <= d2 - d2 // 4))
+                        if cand.size:
+                            d1 = int(cand[np.argmin(rho[cand])])   # argmin and argmax take the earliest of a tie
+                else:
+                    d1 = first
+                    if d1 >= 0:
+                        cand = np.flatnonzero(is_max & (lag >= max(2 * d1 - d1 // 2, 1)) & (lag <= min(2 * d1 + d1 // 2, L - 1)))
+                        if cand.size:
+                            d2 = int(cand[np.argmax(rho[cand])])
+                out[2], out[5] = d1, d2
+                if d1 >= 0:
+                    out[3], out[4] = _regularity_refine(rho, d1), (-rho[d1] if odd else rho[d1])
+                if d2 >= 0:
+                    out[6], out[7] = _regularity_refine(rho, d2), rho[d2]
+                    out[9] = (120.0 * fps) / out[6]
+                    if d1 >= 0 and out[7] > 0:
+                        out[8] = out[4] / out[7]
+            f0 += T
+    out = {"acf": acf, "per_sequence": per_seq}
+    if return_pairs:
+        out["pairs"] = pairs
+    return out
+
+
+def gait_regularity(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, max_lag=60, min_lag=4, min_peak=0.25, min_pairs=20,
+                    joints=GAIT_JOINTS_KINECTV2):
+    """Gait regularity and symmetry without events, from the autocorrelation of four body signals in numpy float64 (Moe-Nilssen and Helbostad 2004, on
+    trunk accelerations; the rules: DESIGN 4.15; the defaults are unvalidated on the model's output): the host statement of GRNet.gait_regularity,
+    same arguments, a dict of numpy arrays -- the same operations in the same order, every sum a cumulative sum.  joints3d (n,J,3) and joints as
+    gait_parameters takes them (the foot entries are not read); trans (n,3) or None; exclude (n,) or None.  per_frame (n,4) = [sep, lift, sway, bob]
+    as smoothed by sigma frames; acf and per_sequence: gait_autocorr's."""
+    j3 = _widened(joints3d, "joints3d")
+    n, J = j3.shape[:2]
+    lengths = _sequence_lengths(n, lengths)
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs)
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    tr = None
+    if trans is not None:
+        tr = np.asarray(trans, np.float64)
+        if tr.shape != (n, 3):
+            raise ValueError(f"trans must be ({n},3), got {tr.shape}")
+
+    def dot(a, b):
+        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+    pelvis, spine, lhip, rhip, lank, rank_ = (j3[:, i] for i in tab[:6])
+    per_frame = np.full((n, 4), np.nan)
+    with np.errstate(all="ignore"):
+        l, u = lhip - rhip, spine - pelvis
+        c = np.stack([l[:, 1] * u[:, 2] - l[:, 2] * u[:, 1], l[:, 2] * u[:, 0] - l[:, 0] * u[:, 2], l[:, 0] * u[:, 1] - l[:, 1] * u[:, 0]], axis=1)
+        nc, nl, nu = np.sqrt(dot(c, c)), np.sqrt(dot(l, l)), np.sqrt(dot(u, u))
+        valid = (nc > 0) & np.isfinite(nc) & (nl > 0) & np.isfinite(nl)
+        f, side, up, d = c / nc[:, None], l / nl[:, None], u / nu[:, None], lank - rank_
+        per_frame[:, 0] = np.where(valid, dot(d, f), np.nan)
+        per_frame[:, 1] = np.where(valid, dot(d, up), np.nan)
+        per_frame[:, 2] = np.where(valid, dot(up, side), np.nan)
+        if tr is not None:
+            per_frame[:, 3] = np.where(np.isfinite(tr).all(axis=1), -(pelvis[:, 1] + tr[:, 1]), np.nan)
+        if sigma > 0:
+            a = 0
+            for T in lengths:
+                for k in range(4):
+                    per_frame[a:a + T, k] = gauss_filter1d(per_frame[a:a + T, k].copy(), sigma)
+                a += T
+    out = gait_autocorr(per_frame, lengths, exclude, fps, max_lag, min_lag, min_peak, min_pairs)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
