@@ -84,6 +84,24 @@ int main() {
     why = joint_table_error(table + 3, 1, 25);
     expect(has(why, "joint index -1 (entry 0)"), "a negative index is refused", why);
 
+    // the opening of the gait calls: J < 1 first, then the table's words; the table is copied only where it is good
+    int taken[4] = {7, 7, 7, 7};
+    expect(joint_table_take(table, 2, 25, taken).empty() && taken[0] == 0 && taken[1] == 24 && taken[2] == 7, "a good table is copied, `count` entries of it", "");
+    why = joint_table_take(table, 3, 25, taken);
+    expect(why == joint_table_error(table, 3, 25) && taken[1] == 24 && taken[2] == 7, "a bad table is refused in joint_table_error's words and not copied", why);
+    why = joint_table_take(table, 3, 0, taken);
+    expect(why == "J 0 < 1", "J = 0 is refused before the table is read", why);
+    why = joint_table_take(nullptr, 3, -2, taken);
+    expect(why == "J -2 < 1" && taken[0] == 0, "a negative J too, and no index is read", why);
+
+    // the raw columns: none without a Gaussian (0, negative or NaN sigma: the entry refuses the last two before it asks), else whole 256-byte steps
+    expect(raw_bytes(0., 13, 400) == 0 && raw_bytes(-1., 13, 400) == 0 && raw_bytes(nan, 13, 400) == 0, "no Gaussian, no raw columns", "");
+    expect(raw_bytes(2., 1, 1) == 256 && raw_bytes(2., 4, 8) == 256 && raw_bytes(16., 3, 11) == 512, "cols * frames doubles, rounded up to 256 bytes", "");
+    expect(raw_bytes(0.5, 13, 2147483647u / 75) == align256((size_t)13 * (2147483647u / 75) * 8), "13 columns of the most frames a call of J = 25 takes", "");
+
+    // the rule checks of the gait headers answer with a literal or null
+    expect(rule_text(nullptr).empty() && rule_text("max_lag outside [8, 255]") == "max_lag outside [8, 255]", "null is no refusal, a literal is its own text", "");
+
     if (failures) {
         std::printf("%d failed\n", failures);
         return 1;

@@ -59,6 +59,47 @@ def run(model, x, alone):
     return r
 
 
+GAUSS_LENGTHS = [1, 2, 5, 64, 65, 257, 300]     # shorter than any radius; the wave's edge and one past it; a second pass of the 256 threads; 694 in all
+# call -> (its smoothed columns of per_frame, how many of them the walker moves: its ankles and feet alone swing, every other joint is rigid)
+GAUSS_COLUMNS = {"gait": (range(0, 4), 4), "kinematics": (range(0, 13), 4), "contacts": (range(1, 4), 2), "regularity": (range(0, 4), 1)}
+
+
+def test_the_smoothing_of_every_gait_call_is_op_gauss1d(pkg):
+    """What the one Gaussian launch of gait_parameters, gait_kinematics, gait_contacts and gait_regularity (seq_gauss_columns_kernel) relies on: a
+    call's smoothed column IS op_gauss1d of its unsmoothed column, inside each sequence.  Expected: equal bytes, which is derived and no tolerance --
+    both run track_gauss of track_boxes.h on the same values with the same weights in the same order, in a file compiled without contraction.
+    Seven sequences of one walker, so that a wrong offset, row width or first column lands in a neighbour; sigma 16 has radius 64, more than
+    most of these sequences have frames.  The bytes are compared, so a NaN must be the same NaN in the same place."""
+    joints, trans = gc.walker(sum(GAUSS_LENGTHS), theta=0.37)
+    assert joints.shape == (694, 25, 3)
+
+    def same(a, b):
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+    model = pkg.GRNet(max_frames=1)
+    try:
+        events = model.gait_parameters(joints, lengths=GAUSS_LENGTHS, trans=trans, sigma=0.0)["events"]
+        calls = {"gait": lambda s: model.gait_parameters(joints, lengths=GAUSS_LENGTHS, trans=trans, sigma=s),
+                 "kinematics": lambda s: model.gait_kinematics(joints, events, lengths=GAUSS_LENGTHS, sigma=s),
+                 "contacts": lambda s: model.gait_contacts(joints, events, lengths=GAUSS_LENGTHS, sigma=s),
+                 "regularity": lambda s: model.gait_regularity(joints, lengths=GAUSS_LENGTHS, trans=trans, sigma=s)}
+        for name, call in calls.items():
+            columns, moving = GAUSS_COLUMNS[name]
+            raw = call(0.0)["per_frame"]
+            assert raw.dtype == torch.float64 and raw.shape[0] == 694
+            varies = [k for k in columns if float(raw[:, k].max() - raw[:, k].min()) > 1e-3]
+            assert len(varies) >= moving, (name, varies)          # the columns are not constant: a Gaussian of a constant would prove little
+            for sigma in (0.5, 2.0, 16.0):
+                got = call(sigma)["per_frame"]
+                for k in columns:
+                    assert same(got[:, k], model.op_gauss1d(raw[:, k], lengths=GAUSS_LENGTHS, sigma=sigma)), (name, sigma, k)
+                assert not any(same(got[:, k], raw[:, k]) for k in varies), (name, sigma)       # and the Gaussian did something
+                if name == "gait":
+                    assert same(got[:, 4], raw[:, 4]), sigma       # the width, which no Gaussian touches
+    finally:
+        model.close()
+
+
 def test_calls_in_flight_together_equal_the_same_calls_alone(pkg):
     x = inputs()
     together, alone = pkg.GRNet(max_frames=1), pkg.GRNet(max_frames=1)

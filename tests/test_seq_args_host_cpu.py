@@ -1,5 +1,5 @@
-"""csrc/seq_args.h, the argument rules of the calls that take sequences lying back to back -- the offsets' validator, align256, the sigma rule and
-the joint table's -- through tests/helpers/seq_args_check.cpp: a stand-alone program (its own main, no HIP) built with AddressSanitizer and UBSan and
+"""csrc/seq_args.h, the argument rules of the calls that take sequences lying back to back -- the offsets' validator, align256, the sigma rule, the joint
+table's and the opening the five gait calls share -- through tests/helpers/seq_args_check.cpp: a stand-alone program (its own main, no HIP) built with AddressSanitizer and UBSan and
 run directly.  It reaches what a GPU test would need gigabytes for: offsets at the 31-bit edge, the longest sequence at its edge, 8192 sequences."""
 import os
 import shutil

@@ -10,14 +10,14 @@
 // Without a Gaussian the lane makes the vector of the next frame too and with it s of its interval; whether its frame is the last of a sequence,
 // whose s is NaN, it finds by bisection in the offsets.  With one the three columns go to the call's scratch.
 //
-// contact_smooth_kernel -- sigma > 0 alone: a workgroup per (sequence, column), thread per frame, track_gauss from the scratch column into the rows.
+// sigma > 0 alone      -- seq_gauss_columns_kernel (track_kernels.hip) on the three columns: columns 1 .. 3 of the rows, which are 4 wide.
 //
 // contact_seq_kernel    -- one workgroup of four waves per sequence.  (0) after a Gaussian the lanes make s from the smoothed vectors, then a
 // barrier (a workgroup's own global writes are visible to it there).  (a) a wave takes 64 consecutive intervals, a lane an interval: an xor
 // butterfly over the lanes (1, 2, 4, ... 32) adds adjacent pairs, then pairs of those -- contact_block_sum's tree, and since a + b and b + a have
 // the same bits every lane ends with the block's sum; __ballot of "s is finite" and of the two heel-strike bits ARE words of three masks, aligned
-// to the sequence, in LDS where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch (sequence q owning words
-// (f0 >> 6) + q onwards of each).  Behind a barrier one lane adds the blocks in time order and makes the threshold.  (b) behind a barrier
+// to the sequence, in LDS where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch (gait_mask_at
+// of each).  Behind a barrier one lane adds the blocks in time order and makes the threshold.  (b) behind a barrier
 // __ballot(s < thr) is a word of the static mask.  (c) behind a barrier a lane whose interval is not static writes its phase; the lane at a run's
 // first interval finds the run's end by word, walks ITS run (contact_run: closed, edges, attribution from the heel-strike masks by word, least s),
 // writes the phases of its intervals and the run's row, whose index is the number of runs that begin below it, and keeps lead, edges and end of
@@ -61,16 +61,6 @@ __global__ __launch_bounds__(256) void contact_frame_kernel(const int* __restric
         s = contact_speed(d0, d1, fps);
     }
     row[0] = s;
-}
-
-__global__ __launch_bounds__(256) void contact_smooth_kernel(const int* __restrict__ off, const double* __restrict__ weights, int radius, int frames,
-                                                             const double* __restrict__ raw, double* __restrict__ per_frame) {
-    __shared__ double w_lds[kTrackMaxRadius + 1];
-    const int f0 = off[blockIdx.x], T = off[blockIdx.x + 1] - f0, k = blockIdx.y;
-    if ((int)threadIdx.x <= radius) w_lds[threadIdx.x] = weights[threadIdx.x];
-    __syncthreads();
-    const double* x = raw + (size_t)k * frames + f0;
-    for (int i = threadIdx.x; i < T; i += 256) per_frame[((size_t)f0 + i) * kContactFrameCols + 1 + k] = track_gauss(x, T, i, w_lds, radius);
 }
 
 // Stages (a) to (d) of one sequence on its masks and block sums: called once with the LDS arrays and once with the call's scratch, so that in each
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(kGaitThreads) void contact_seq_kernel(const int* __
         const ContactMasks m{lds[0], lds[1], lds[2], lds[3], lds[4], lds[5]};
         contact_sequence_stages(m, lds_blocks, shared, kept_rows, tid, T, r, s, stride, events + f0, phase + f0, table, out);
     } else {
-        unsigned long long* g = words + (size_t)(f0 >> 6) + q;
+        unsigned long long* g = gait_mask_at(words, f0, q);
         const size_t n = mask_words;
         const ContactMasks m{g, g + n, g + 2 * n, g + 3 * n, g + 4 * n, g + 5 * n};
         contact_sequence_stages(m, reinterpret_cast<double*>(g + kContactMaskSets * n), shared, kept_rows, tid, T, r, s, stride, events + f0, phase + f0, table, out);
@@ -179,10 +169,6 @@ __global__ __launch_bounds__(kGaitThreads) void contact_seq_kernel(const int* __
 hipError_t launch_contact_frames(const int* off, int n_seq, const float* joints, int J, int frames, const GaitTable& tab, double fps, double* raw,
                                  double* per_frame, hipStream_t s) {
     return launch_k(contact_frame_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, off, n_seq, joints, J, frames, tab, fps, raw, per_frame);
-}
-
-hipError_t launch_contact_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s) {
-    return launch_k(contact_smooth_kernel, dim3(n_seq, 3), dim3(256), 0, s, off, weights, radius, frames, raw, per_frame);
 }
 
 hipError_t launch_contact_sequences(const int* off, int n_seq, const ContactRule& rule, double* per_frame, const double* speeds, bool make_s, const int* events,

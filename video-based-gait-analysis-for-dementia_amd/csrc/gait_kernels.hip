@@ -9,13 +9,13 @@
 // roots and five dot products, far too little for a wave (the reasons of track_frame_kernel).  The four signals go to the call's scratch, one
 // column each, where a Gaussian follows, else straight into the per-frame rows; the width goes into its row either way.
 //
-// gait_smooth_kernel -- sigma > 0 alone: a workgroup per (sequence, signal), thread per frame, track_gauss from the scratch column into the rows.
+// sigma > 0 alone    -- seq_gauss_columns_kernel (track_kernels.hip) on the four columns: columns 0 .. 3 of the rows, which are 7 wide.
 //
 // gait_seq_kernel    -- one workgroup of four waves per sequence.  (a) events: a wave takes 64 consecutive frames of the sequence, a lane a frame;
 // the lane's four tests read the 2w + 1 rows around it, and __ballot of each kind IS one word of that kind's bitmask -- the words are aligned
-// to the sequence and lie in LDS where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch, sequence q owning words
-// (f0 >> 6) + q onwards of each of the four masks there, which never overlap the next sequence's.  The lane writes its events entry and the step
-// length and width of its row.  (b) behind one barrier (a workgroup's own global writes are visible to it there) wave 0 makes the
+// to the sequence and lie in LDS where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch (gait_mask_at of each of the
+// four masks there).  The lane writes its events entry and the step length and width of its row.
+// (b) behind one barrier (a workgroup's own global writes are visible to it there) wave 0 makes the
 // per-sequence row: lanes 0 to 3 the counts, lane 4 the steps, 5 the strides, 6 the stance share, 7 the speed along the trajectory -- each
 // walks the masks by word and adds in time order on its own, so no sum depends on the launch.  No atomics anywhere.
 //
@@ -39,16 +39,6 @@ __global__ __launch_bounds__(256) void gait_frame_kernel(const float* __restrict
         else row[k] = sig[k];
     }
     row[4] = sig[4];
-}
-
-__global__ __launch_bounds__(256) void gait_smooth_kernel(const int* __restrict__ off, const double* __restrict__ weights, int radius, int frames,
-                                                          const double* __restrict__ raw, double* __restrict__ per_frame) {
-    __shared__ double w_lds[kTrackMaxRadius + 1];
-    const int f0 = off[blockIdx.x], T = off[blockIdx.x + 1] - f0, k = blockIdx.y;
-    if ((int)threadIdx.x <= radius) w_lds[threadIdx.x] = weights[threadIdx.x];
-    __syncthreads();
-    const double* x = raw + (size_t)k * frames + f0;
-    for (int i = threadIdx.x; i < T; i += 256) per_frame[((size_t)f0 + i) * kGaitFrameCols + k] = track_gauss(x, T, i, w_lds, radius);
 }
 
 // Stages (a) and (b) of one sequence on its four bitmasks m[k][0, ceil(T / 64)): called once with the LDS array and once with the call's scratch, so that
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(kGaitThreads) void gait_seq_kernel(const int* __res
     if (((T - 1) >> 6) < kGaitLdsWords) {
         gait_sequence_stages(lds[0], lds[1], lds[2], lds[3], tid, T, J, pelvis, j, tr, fps, window, min_excursion, rows, events + f0, out);
     } else {
-        unsigned long long* g = words + (size_t)(f0 >> 6) + q;
+        unsigned long long* g = gait_mask_at(words, f0, q);
         gait_sequence_stages(g, g + mask_words, g + 2 * mask_words, g + 3 * mask_words, tid, T, J, pelvis, j, tr, fps, window, min_excursion, rows, events + f0, out);
     }
 }
@@ -114,10 +104,6 @@ __global__ __launch_bounds__(256) void gait_events_kernel(const int* __restrict_
 
 hipError_t launch_gait_frames(const float* joints, int J, int frames, const GaitTable& tab, double* raw, double* per_frame, hipStream_t s) {
     return launch_k(gait_frame_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, joints, J, frames, tab, raw, per_frame);
-}
-
-hipError_t launch_gait_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s) {
-    return launch_k(gait_smooth_kernel, dim3(n_seq, 4), dim3(256), 0, s, off, weights, radius, frames, raw, per_frame);
 }
 
 hipError_t launch_gait_sequences(const int* off, int n_seq, int J, int pelvis, const float* joints, const double* trans, double fps, int window,

@@ -9,12 +9,12 @@
 // sixty operations without a branch that depends on more than the octant (the reasons of track_frame_kernel).  The 13 angles go to the call's scratch,
 // one column each, where a Gaussian follows, else straight into the per-frame rows.
 //
-// kin_smooth_kernel -- sigma > 0 alone: a workgroup per (sequence, channel), thread per frame, track_gauss from the scratch column into the rows.
+// sigma > 0 alone  -- seq_gauss_columns_kernel (track_kernels.hip) on the 13 columns: all of the rows, which are 13 wide.
 //
 // kin_cycle_kernel  -- one workgroup of four waves per (sequence, channel).  (a) a wave takes 64 consecutive frames of the sequence's events, a lane a
 // frame: __ballot of the left and of the right heel strike IS one word of that foot's bitmask -- the words are aligned to the sequence and lie in LDS
-// where the sequence has at most 64 * kKinLdsWords frames, else in the call's scratch, where every (channel, foot) has a mask of its own and sequence q
-// owns words (f0 >> 6) + q onwards of it, which never overlap the next sequence's.  (b) behind one barrier EVERY thread walks the channel's foot's
+// where the sequence has at most 64 * kKinLdsWords frames, else in the call's scratch, where every (channel, foot) has a mask of its own
+// (gait_mask_at of it).  (b) behind one barrier EVERY thread walks the channel's foot's
 // mask by word (kin_channel): the walk is the same in all of them, so nothing diverges; a stride's finiteness, maximum and minimum are one reduction of
 // the workgroup (shuffles inside a wave, twelve doubles of LDS across the four: comparisons and a logical and, exact whatever the order); threads
 // 0 .. 100 each add their own cycle point over the used strides in time order, every thread holds the same sums of the row, and thread 0 writes it.
@@ -38,16 +38,6 @@ __global__ __launch_bounds__(256) void kin_frame_kernel(const float* __restrict_
         if (raw) raw[(size_t)k * frames + f] = ang[k];
         else per_frame[(size_t)f * kKinChannels + k] = ang[k];
     }
-}
-
-__global__ __launch_bounds__(256) void kin_smooth_kernel(const int* __restrict__ off, const double* __restrict__ weights, int radius, int frames,
-                                                         const double* __restrict__ raw, double* __restrict__ per_frame) {
-    __shared__ double w_lds[kTrackMaxRadius + 1];
-    const int f0 = off[blockIdx.x], T = off[blockIdx.x + 1] - f0, k = blockIdx.y;
-    if ((int)threadIdx.x <= radius) w_lds[threadIdx.x] = weights[threadIdx.x];
-    __syncthreads();
-    const double* x = raw + (size_t)k * frames + f0;
-    for (int i = threadIdx.x; i < T; i += 256) per_frame[((size_t)f0 + i) * kKinChannels + k] = track_gauss(x, T, i, w_lds, radius);
 }
 
 // Whether column x (frame i at x[i * kKinChannels]) is finite on all of [t0, t0 + L], and its maximum and minimum there: every thread of the workgroup
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(kKinThreads) void kin_cycle_kernel(const int* __res
     if (((T - 1) >> 6) < kKinLdsWords) {
         kin_cycle_stages(lds[0], lds[1], tid, T, c, events + f0, rows, min_stride, max_stride, red, curve, row);
     } else {
-        unsigned long long* g = words + (size_t)(2 * c) * mask_words + (size_t)(f0 >> 6) + q;
+        unsigned long long* g = gait_mask_at(words + (size_t)(2 * c) * mask_words, f0, q);
         kin_cycle_stages(g, g + mask_words, tid, T, c, events + f0, rows, min_stride, max_stride, red, curve, row);
     }
 }
@@ -136,10 +126,6 @@ __global__ __launch_bounds__(kKinThreads) void kin_cycle_kernel(const int* __res
 
 hipError_t launch_kin_frames(const float* joints, int J, int frames, const KinTable& tab, double* raw, double* per_frame, hipStream_t s) {
     return launch_k(kin_frame_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, joints, J, frames, tab, raw, per_frame);
-}
-
-hipError_t launch_kin_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s) {
-    return launch_k(kin_smooth_kernel, dim3(n_seq, kKinChannels), dim3(256), 0, s, off, weights, radius, frames, raw, per_frame);
 }
 
 hipError_t launch_kin_cycles(const int* off, int n_seq, const int* events, const double* per_frame, int min_stride, int max_stride, unsigned long long* words,

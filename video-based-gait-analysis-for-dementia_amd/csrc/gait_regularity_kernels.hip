@@ -9,7 +9,7 @@
 // reg_frame_kernel  -- ONE LANE PER FRAME over all frames of the call (the reasons of gait_frame_kernel): six joints, one cross product, three square
 // roots, three dot products.  The four signals go to the call's scratch, one column each, where a Gaussian follows, else into the per-frame rows.
 //
-// reg_smooth_kernel -- sigma > 0 alone: a workgroup per (sequence, channel), thread per frame, track_gauss from the scratch column into the rows.
+// sigma > 0 alone  -- seq_gauss_columns_kernel (track_kernels.hip) on the four columns: all of the rows, which are 4 wide.
 //
 // reg_seq_kernel    -- the grid is (n_seq, 4): one workgroup of four waves per (sequence, channel).  The signal and the run numbers of the sequence
 // lie in LDS where it has at most kRegLdsFrames frames, else in the call's scratch, through the same code.  (a) a wave takes 64 consecutive frames,
@@ -42,16 +42,6 @@ __global__ __launch_bounds__(256) void reg_frame_kernel(const float* __restrict_
         if (raw) raw[(size_t)k * frames + f] = sig[k];
         else per_frame[(size_t)f * kRegChannels + k] = sig[k];
     }
-}
-
-__global__ __launch_bounds__(256) void reg_smooth_kernel(const int* __restrict__ off, const double* __restrict__ weights, int radius, int frames,
-                                                         const double* __restrict__ raw, double* __restrict__ per_frame) {
-    __shared__ double w_lds[kTrackMaxRadius + 1];
-    const int f0 = off[blockIdx.x], T = off[blockIdx.x + 1] - f0, k = blockIdx.y;
-    if ((int)threadIdx.x <= radius) w_lds[threadIdx.x] = weights[threadIdx.x];
-    __syncthreads();
-    const double* x = raw + (size_t)k * frames + f0;
-    for (int i = threadIdx.x; i < T; i += 256) per_frame[((size_t)f0 + i) * kRegChannels + k] = track_gauss(x, T, i, w_lds, radius);
 }
 
 struct RegShared { double mu, sum_0; long long n, N_0; };
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(kGaitThreads) void reg_seq_kernel(const int* __rest
         reg_sequence_stages(lds_d, lds_key, lds_valid, lds_prefix, rho, lags, &shared, tid, T, r, reg_odd(ch), x, ex, a, out);
     } else {                                                   // the host gave the scratch: a sequence of the call is longer than the LDS arrays
         const size_t at = (size_t)ch * frames + f0;
-        unsigned long long* g = words + (size_t)ch * 2 * mask_words + (size_t)(f0 >> 6) + q;
+        unsigned long long* g = gait_mask_at(words + (size_t)ch * 2 * mask_words, f0, q);
         reg_sequence_stages(long_d + at, long_key + at, g, reinterpret_cast<long long*>(g + mask_words), rho, lags, &shared, tid, T, r, reg_odd(ch), x, ex, a, out);
     }
 }
@@ -138,10 +128,6 @@ __global__ __launch_bounds__(kGaitThreads) void reg_seq_kernel(const int* __rest
 
 hipError_t launch_reg_frames(const float* joints, int J, int frames, const GaitTable& tab, const double* trans, double* raw, double* per_frame, hipStream_t s) {
     return launch_k(reg_frame_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, joints, J, frames, tab, trans, raw, per_frame);
-}
-
-hipError_t launch_reg_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s) {
-    return launch_k(reg_smooth_kernel, dim3(n_seq, kRegChannels), dim3(256), 0, s, off, weights, radius, frames, raw, per_frame);
 }
 
 hipError_t launch_reg_sequences(const int* off, int n_seq, const RegRule& rule, const double* rows, const int* exclude, int frames, double* long_d, int* long_key,

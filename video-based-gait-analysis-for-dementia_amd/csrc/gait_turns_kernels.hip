@@ -14,7 +14,7 @@
 //
 // turn_seq_kernel  -- one workgroup of four waves per sequence, as gait_seq_kernel.  (a) a wave takes 64 consecutive frames, a lane a frame:
 // __ballot of rate > edge, of rate < -edge, of rate != rate and of the four event bits ARE words of seven bitmasks, aligned to the sequence, in LDS
-// where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch (sequence q owning words (f0 >> 6) + q onwards of each).
+// where the sequence has at most 64 * kGaitLdsWords frames, else in the call's scratch (gait_mask_at of each).
 // (b) behind a barrier the lane at the first frame of a run walks ITS run (turn_run: maximum, sum in time order, length); runs are disjoint, so the
 // walks run side by side; the verdicts are balloted into the accept mask at the runs' first frames.  (c) behind a barrier every lane finds the
 // first frame of the run it lies in (turn_last_clear) and with it its phase; ballots of the phases are the words of the left-turn, right-turn and
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kGaitThreads) void turn_seq_kernel(const int* __res
         const TurnMasks m{lds[0], lds[1], lds[2], lds[3], lds[4], lds[5], lds[6], lds[7], lds[8], lds[9], lds[10]};
         turn_sequence_stages(m, kept, tid, T, r, rows, events + f0, gait, phase + f0, table, out);
     } else {
-        unsigned long long* g = words + (size_t)(f0 >> 6) + q;
+        unsigned long long* g = gait_mask_at(words, f0, q);
         const size_t s = mask_words;
         const TurnMasks m{g, g + s, g + 2 * s, g + 3 * s, g + 4 * s, g + 5 * s, g + 6 * s, g + 7 * s, g + 8 * s, g + 9 * s, g + 10 * s};
         turn_sequence_stages(m, kept, tid, T, r, rows, events + f0, gait, phase + f0, table, out);

@@ -22,21 +22,19 @@ int grnet_gait_parameters(grnet_t* h, const float* joints3d_dev, int J, const in
     const std::string name = "grnet_gait_parameters: ";
     if (!joints3d_dev || !frame_offsets_host || !joints_host || !per_frame_dev || !events_dev || !per_seq_dev)
         return h->fail(GRNET_EINVAL, name + "null pointer (joints3d_dev, frame_offsets_host, joints_host, per_frame_dev, events_dev and per_seq_dev are all needed)");
-    if (J < 1) return h->fail(GRNET_EINVAL, name + "J " + std::to_string(J) + " < 1");
-    std::string why = joint_table_error(joints_host, 8, J);
+    GaitTable tab{};
+    std::string why = joint_table_take(joints_host, 8, J, tab.j);
     if (why.empty() && (!std::isfinite(fps) || !(fps > 0.))) why = "fps must be positive and finite";
     if (why.empty()) why = sigma_error(sigma, kTrackMaxSigma);
     if (why.empty()) why = events_error(window, min_excursion);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
-    GaitTable tab{};
-    std::copy(joints_host, joints_host + 8, tab.j);
     size_t mask_words = 0, b_words = 0, b_raw = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SeqCall c;
     if (int rc = seq_call(h, name, frame_offsets_host, n_seq, 3LL * J, sigma, s, &c, [&](int frames) {
             mask_words = gait_mask_words(frames, n_seq);
-            b_words = align256(4 * mask_words * sizeof(unsigned long long));
-            b_raw = sigma > 0. ? align256((size_t)frames * 4 * sizeof(double)) : 0;
+            b_words = gait_mask_bytes(4, mask_words);
+            b_raw = raw_bytes(sigma, 4, frames);
             return b_words + b_raw;
         }))
         return rc;
@@ -44,7 +42,7 @@ int grnet_gait_parameters(grnet_t* h, const float* joints3d_dev, int J, const in
     unsigned long long* words = reinterpret_cast<unsigned long long*>(c.behind);
     double* raw = b_raw ? reinterpret_cast<double*>(c.behind + b_words) : nullptr;
     hipError_t e = launch_gait_frames(joints3d_dev, J, frames, tab, raw, per_frame_dev, s);
-    if (e == hipSuccess && raw) e = launch_gait_smooth(c.off, n_seq, c.weights, c.radius, frames, raw, per_frame_dev, s);
+    if (e == hipSuccess && raw) e = launch_seq_gauss_columns(c.off, n_seq, 4, c.weights, c.radius, frames, raw, per_frame_dev, 7, 0, s);
     if (e == hipSuccess)
         e = launch_gait_sequences(c.off, n_seq, J, tab.j[0], joints3d_dev, trans_dev, fps, window, min_excursion, words, mask_words, per_frame_dev, events_dev,
                                   per_seq_dev, s);

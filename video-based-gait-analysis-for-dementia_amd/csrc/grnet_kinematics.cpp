@@ -12,9 +12,6 @@ std::string strides_error(int min_stride, int max_stride) {
     return "";
 }
 
-// the event bitmasks of a call's cycle stage, behind its table
-size_t cycle_mask_bytes(size_t mask_words) { return align256(kKinMaskSets * mask_words * sizeof(unsigned long long)); }
-
 }  // namespace
 
 extern "C" {
@@ -26,20 +23,18 @@ int grnet_gait_kinematics(grnet_t* h, const float* joints3d_dev, int J, const in
     const std::string name = "grnet_gait_kinematics: ";
     if (!joints3d_dev || !frame_offsets_host || !joints_host || !events_dev || !per_frame_dev || !curves_dev || !per_seq_dev)
         return h->fail(GRNET_EINVAL, name + "null pointer (joints3d_dev, frame_offsets_host, joints_host, events_dev, per_frame_dev, curves_dev and per_seq_dev are all needed)");
-    if (J < 1) return h->fail(GRNET_EINVAL, name + "J " + std::to_string(J) + " < 1");
-    std::string why = joint_table_error(joints_host, 16, J);
+    KinTable tab{};
+    std::string why = joint_table_take(joints_host, 16, J, tab.j);
     if (why.empty()) why = sigma_error(sigma, kTrackMaxSigma);
     if (why.empty()) why = strides_error(min_stride, max_stride);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
-    KinTable tab{};
-    std::copy(joints_host, joints_host + 16, tab.j);
     size_t mask_words = 0, b_words = 0, b_raw = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SeqCall c;
     if (int rc = seq_call(h, name, frame_offsets_host, n_seq, std::max(3LL * J, 13LL), sigma, s, &c, [&](int frames) {      // 13 angle columns a frame
             mask_words = gait_mask_words(frames, n_seq);
-            b_words = cycle_mask_bytes(mask_words);
-            b_raw = sigma > 0. ? align256((size_t)frames * 13 * sizeof(double)) : 0;
+            b_words = gait_mask_bytes(kKinMaskSets, mask_words);
+            b_raw = raw_bytes(sigma, 13, frames);
             return b_words + b_raw;
         }))
         return rc;
@@ -47,7 +42,7 @@ int grnet_gait_kinematics(grnet_t* h, const float* joints3d_dev, int J, const in
     unsigned long long* words = reinterpret_cast<unsigned long long*>(c.behind);
     double* raw = b_raw ? reinterpret_cast<double*>(c.behind + b_words) : nullptr;
     hipError_t e = launch_kin_frames(joints3d_dev, J, frames, tab, raw, per_frame_dev, s);
-    if (e == hipSuccess && raw) e = launch_kin_smooth(c.off, n_seq, c.weights, c.radius, frames, raw, per_frame_dev, s);
+    if (e == hipSuccess && raw) e = launch_seq_gauss_columns(c.off, n_seq, 13, c.weights, c.radius, frames, raw, per_frame_dev, 13, 0, s);
     if (e == hipSuccess) e = launch_kin_cycles(c.off, n_seq, events_dev, per_frame_dev, min_stride, max_stride, words, mask_words, curves_dev, per_seq_dev, s);
     if (e != hipSuccess) return h->fail(GRNET_EHIP, name + hipGetErrorString(e));
     return 0;
@@ -65,7 +60,7 @@ int grnet_op_gait_cycles(grnet_t* h, const double* angles_dev, const int32_t* ev
     SeqCall c;
     if (int rc = seq_call(h, name, frame_offsets_host, n_seq, 13, 0., s, &c, [&](int frames) {
             mask_words = gait_mask_words(frames, n_seq);
-            return cycle_mask_bytes(mask_words);
+            return gait_mask_bytes(kKinMaskSets, mask_words);
         }))
         return rc;
     const hipError_t e = launch_kin_cycles(c.off, n_seq, events_dev, angles_dev, min_stride, max_stride, reinterpret_cast<unsigned long long*>(c.behind), mask_words,

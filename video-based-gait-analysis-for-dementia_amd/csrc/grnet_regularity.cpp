@@ -6,12 +6,6 @@
 
 namespace {
 
-// the rule's own refusals are gait_regularity.h's, which the stand-alone checker runs too
-std::string rule_error(const RegRule& rule) {
-    const char* why = reg_rule_error(rule);
-    return why ? why : "";
-}
-
 // What the sequence kernel keeps in the call's scratch where a sequence has more frames than its LDS arrays hold (else nothing): per channel the
 // centred signal and the run numbers of every frame, and two sets of mask words (the validity and the counts before each word).
 struct RegLong {
@@ -25,7 +19,7 @@ struct RegLong {
         mask_words = gait_mask_words(off[n_seq], n_seq);
         b_d = align256(kRegChannels * frames * sizeof(double));
         b_key = align256(kRegChannels * frames * sizeof(int));
-        b_words = align256(kRegChannels * 2 * mask_words * sizeof(unsigned long long));
+        b_words = gait_mask_bytes(kRegChannels * 2, mask_words);
     }
 };
 
@@ -48,28 +42,26 @@ int grnet_gait_regularity(grnet_t* h, const float* joints3d_dev, int J, const in
     const std::string name = "grnet_gait_regularity: ";
     if (!joints3d_dev || !frame_offsets_host || !joints_host || !per_frame_dev || !acf_dev || !per_seq_dev)
         return h->fail(GRNET_EINVAL, name + "null pointer (joints3d_dev, frame_offsets_host, joints_host, per_frame_dev, acf_dev and per_seq_dev are all needed)");
-    if (J < 1) return h->fail(GRNET_EINVAL, name + "J " + std::to_string(J) + " < 1");
-    std::string why = joint_table_error(joints_host, 8, J);
+    GaitTable tab{};
+    std::string why = joint_table_take(joints_host, 8, J, tab.j);
     const RegRule rule{fps, max_lag, min_lag, min_peak, min_pairs};
-    if (why.empty()) why = rule_error(rule);
+    if (why.empty()) why = rule_text(reg_rule_error(rule));      // gait_regularity.h's refusals, which the stand-alone checker runs too
     if (why.empty()) why = sigma_error(sigma, kTrackMaxSigma);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
-    GaitTable tab{};
-    std::copy(joints_host, joints_host + 8, tab.j);
     RegLong lg;
     size_t b_raw = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SeqCall c;
     if (int rc = seq_call(h, name, frame_offsets_host, n_seq, std::max(3LL * J, (long long)kRegChannels), sigma, s, &c, [&](int frames) {
             lg.size(frame_offsets_host, n_seq);
-            b_raw = sigma > 0. ? align256(kRegChannels * (size_t)frames * sizeof(double)) : 0;
+            b_raw = raw_bytes(sigma, kRegChannels, frames);
             return b_raw + lg.bytes();
         }))
         return rc;
     const int frames = frame_offsets_host[n_seq];
     double* raw = b_raw ? reinterpret_cast<double*>(c.behind) : nullptr;
     hipError_t e = launch_reg_frames(joints3d_dev, J, frames, tab, trans_dev, raw, per_frame_dev, s);
-    if (e == hipSuccess && raw) e = launch_reg_smooth(c.off, n_seq, c.weights, c.radius, frames, raw, per_frame_dev, s);
+    if (e == hipSuccess && raw) e = launch_seq_gauss_columns(c.off, n_seq, kRegChannels, c.weights, c.radius, frames, raw, per_frame_dev, kRegChannels, 0, s);
     if (e == hipSuccess) e = sequences(c, c.behind + b_raw, lg, n_seq, frames, rule, per_frame_dev, exclude_dev, acf_dev, per_seq_dev, s);
     if (e != hipSuccess) return h->fail(GRNET_EHIP, name + hipGetErrorString(e));
     return 0;
@@ -81,7 +73,7 @@ int grnet_op_gait_autocorr(grnet_t* h, const double* signals_dev, const int32_t*
     const std::string name = "grnet_op_gait_autocorr: ";
     if (!signals_dev || !frame_offsets_host || !acf_dev || !per_seq_dev) return h->fail(GRNET_EINVAL, name + "null pointer");
     const RegRule rule{fps, max_lag, min_lag, min_peak, min_pairs};
-    const std::string why = rule_error(rule);
+    const std::string why = rule_text(reg_rule_error(rule));
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     RegLong lg;
     hipStream_t s = static_cast<hipStream_t>(stream);

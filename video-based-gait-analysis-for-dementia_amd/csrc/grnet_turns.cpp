@@ -6,13 +6,7 @@
 
 namespace {
 
-// the rule's own refusals are gait_turns.h's, which the stand-alone checker runs too
-std::string rule_error(const TurnRule& rule) {
-    const char* why = turn_rule_error(rule);
-    return why ? why : "";
-}
-
-size_t turn_mask_bytes(size_t mask_words) { return align256(kTurnMaskSets * mask_words * sizeof(unsigned long long)); }
+size_t turn_mask_bytes(size_t mask_words) { return gait_mask_bytes(kTurnMaskSets, mask_words); }
 
 }  // namespace
 
@@ -27,21 +21,19 @@ int grnet_gait_turns(grnet_t* h, const float* joints3d_dev, int J, const int32_t
     if (!joints3d_dev || !frame_offsets_host || !joints_host || !events_dev || !gait_rows_dev || !per_frame_dev || !phase_dev || !turns_dev || !per_seq_dev)
         return h->fail(GRNET_EINVAL, name + "null pointer (joints3d_dev, frame_offsets_host, joints_host, events_dev, gait_rows_dev, per_frame_dev, phase_dev, "
                                             "turns_dev and per_seq_dev are all needed)");
-    if (J < 1) return h->fail(GRNET_EINVAL, name + "J " + std::to_string(J) + " < 1");
-    std::string why = joint_table_error(joints_host, 8, J);
+    GaitTable tab{};
+    std::string why = joint_table_take(joints_host, 8, J, tab.j);
     const TurnRule rule{fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns};
-    if (why.empty()) why = rule_error(rule);
+    if (why.empty()) why = rule_text(turn_rule_error(rule));      // gait_turns.h's refusals, which the stand-alone checker runs too
     if (why.empty()) why = sigma_error(sigma, kTrackMaxSigma);
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
-    GaitTable tab{};
-    std::copy(joints_host, joints_host + 8, tab.j);
     size_t mask_words = 0, b_words = 0, b_raw = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SeqCall c;
     if (int rc = seq_call(h, name, frame_offsets_host, n_seq, std::max(3LL * J, 7LL), sigma, s, &c, [&](int frames) {      // 7 gait columns a frame
             mask_words = gait_mask_words(frames, n_seq);
             b_words = turn_mask_bytes(mask_words);
-            b_raw = sigma > 0. ? align256((size_t)frames * sizeof(double)) : 0;
+            b_raw = raw_bytes(sigma, 1, frames);
             return b_words + b_raw;
         }))
         return rc;
@@ -61,7 +53,7 @@ int grnet_op_gait_turn_runs(grnet_t* h, const double* rates_dev, const int32_t* 
     const std::string name = "grnet_op_gait_turn_runs: ";
     if (!rates_dev || !events_dev || !gait_rows_dev || !frame_offsets_host || !phase_dev || !turns_dev || !per_seq_dev) return h->fail(GRNET_EINVAL, name + "null pointer");
     const TurnRule rule{fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns};
-    const std::string why = rule_error(rule);
+    const std::string why = rule_text(turn_rule_error(rule));
     if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
     size_t mask_words = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);

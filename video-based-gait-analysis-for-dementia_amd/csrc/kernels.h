@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "raster_lines.h"
+#include "seq_args.h"
 
 #include <initializer_list>
 #include <mutex>
@@ -383,6 +384,10 @@ hipError_t launch_track_sequences(const int* off, int n_seq, const double* weigh
                                   const unsigned long long* words, double* work, double* boxes, int* status, int* range, hipStream_t s);
 // the median (radius < 0) or the Gaussian alone on x, per sequence, into out (not x)
 hipError_t launch_track_filter(const int* off, int n_seq, const double* x, const double* weights, int radius, int ksize, int pad, double* out, hipStream_t s);
+// The Gaussian of the gait calls (sigma > 0 alone), a workgroup per (sequence, channel): column k of raw (channels,frames) inside each sequence into
+// out[f * cols + col0 + k], the per-frame rows of the call (gait: cols 7, kinematics 13, contacts 4 from col0 1, regularity 4)
+hipError_t launch_seq_gauss_columns(const int* off, int n_seq, int channels, const double* weights, int radius, int frames, const double* raw, double* out,
+                                    int cols, int col0, hipStream_t s);
 
 // Gait events and parameters from the 3D joints (csrc/gait_kernels.hip, compiled without fma contraction; the arithmetic: csrc/gait_events.h;
 // DESIGN 4.11) ----
@@ -390,13 +395,16 @@ constexpr int kGaitMaxWindow = 32;         // frames on either side of an event
 constexpr int kGaitThreads = 256;          // threads of the sequence kernel's workgroup: four waves, each a word of the event bitmasks at a time
 constexpr int kGaitLdsWords = 64;          // words of each event bitmask a sequence keeps in LDS: 4096 frames (longer ones: the call's scratch)
 struct GaitTable { int j[8]; };            // pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot
-// words of ONE of the four event bitmasks of a call: sequence q owns words (f0 >> 6) + q onwards
+// words of ONE bitmask of a call in its scratch, for the sequences too long for the LDS; a set of them is one mask over all sequences
 inline size_t gait_mask_words(int frames, int n_seq) { return (size_t)(frames >> 6) + (size_t)n_seq + 1; }
+inline size_t gait_mask_bytes(size_t sets, size_t mask_words) { return seq_args::align256(sets * mask_words * sizeof(unsigned long long)); }
+// Where sequence q (frames f0 onwards) begins in a set of `words`.  Its ceil(T / 64) words end at or before (f1 >> 6) + q + 1, where the next sequence's
+// begin: ceil(T / 64) <= (f1 >> 6) - (f0 >> 6) + 1.  So no two sequences overlap, and the last ends inside gait_mask_words.
+__device__ __forceinline__ unsigned long long* gait_mask_at(unsigned long long* words, int f0, int q) { return words + (size_t)(f0 >> 6) + q; }
 // per_frame (frames,7): column 4 (the width) always; columns 0 .. 3 (the signals) where raw is null, else raw (4,frames) gets them, a column each
 hipError_t launch_gait_frames(const float* joints, int J, int frames, const GaitTable& tab, double* raw, double* per_frame, hipStream_t s);
-// sigma > 0: columns 0 .. 3 of per_frame = the Gaussian of raw's columns inside each sequence; off: n_seq + 1 frame offsets ON THE DEVICE
-hipError_t launch_gait_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
-// one workgroup per sequence: events (frames), columns 5 and 6 of per_frame, per_seq (n_seq,18); words: 4 * mask_words; trans (frames,3) or null
+// one workgroup per sequence, off: n_seq + 1 frame offsets ON THE DEVICE: events (frames), columns 5 and 6 of per_frame, per_seq (n_seq,18); words:
+// 4 * mask_words; trans (frames,3) or null
 hipError_t launch_gait_sequences(const int* off, int n_seq, int J, int pelvis, const float* joints, const double* trans, double fps, int window,
                                  double min_excursion, unsigned long long* words, size_t mask_words, double* per_frame, int* events, double* per_seq, hipStream_t s);
 // the events rule alone on signals (frames,4) = [hL, hR, tL, tR]
@@ -411,8 +419,6 @@ constexpr int kKinMaskSets = 26;           // bitmasks of a call in the scratch:
 struct KinTable { int j[16]; };            // pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist
 // per_frame (frames,13) where raw is null, else raw (13,frames) gets the angles, a column each
 hipError_t launch_kin_frames(const float* joints, int J, int frames, const KinTable& tab, double* raw, double* per_frame, hipStream_t s);
-// sigma > 0: per_frame = the Gaussian of raw's columns inside each sequence; off: n_seq + 1 frame offsets ON THE DEVICE
-hipError_t launch_kin_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
 // one workgroup per (sequence, channel): curves (n_seq,13,101,2), per_seq (n_seq,13,6); words: kKinMaskSets * mask_words (gait_mask_words)
 hipError_t launch_kin_cycles(const int* off, int n_seq, const int* events, const double* per_frame, int min_stride, int max_stride, unsigned long long* words,
                              size_t mask_words, double* curves, double* per_seq, hipStream_t s);
@@ -436,8 +442,6 @@ struct ContactRule;                        // gait_contacts.h: fps, the threshol
 // vectors and per_frame is not written; off: n_seq + 1 frame offsets ON THE DEVICE; tab: its ankles (entries 4 and 5) are read
 hipError_t launch_contact_frames(const int* off, int n_seq, const float* joints, int J, int frames, const GaitTable& tab, double fps, double* raw,
                                  double* per_frame, hipStream_t s);
-// a workgroup per (sequence, column): the Gaussian of raw (3,frames) into columns 1 .. 3 of per_frame
-hipError_t launch_contact_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
 // one workgroup per sequence on per_frame (frames,4) -- make_s: s is made from its smoothed vectors first -- or, per_frame null, on speeds (frames), and
 // on the gait call's events (frames): phase (frames), runs (n_seq,max_runs,6), per_seq (n_seq,20); words: (kContactMaskSets + 1) (gait_contacts.h) *
 // mask_words (gait_mask_words), the last set holding the block sums
@@ -450,8 +454,6 @@ struct RegRule;                            // gait_regularity.h: fps, max_lag, m
 constexpr int kRegLdsFrames = 64 * kGaitLdsWords;      // frames of a sequence whose centred signal and run numbers the sequence kernel keeps in LDS: 4096
 // one lane per frame: the four signals into per_frame (frames,4), or, raw not null (a Gaussian follows), into raw (4,frames); trans (frames,3) or null
 hipError_t launch_reg_frames(const float* joints, int J, int frames, const GaitTable& tab, const double* trans, double* raw, double* per_frame, hipStream_t s);
-// a workgroup per (sequence, channel): the Gaussian of raw (4,frames) into per_frame
-hipError_t launch_reg_smooth(const int* off, int n_seq, const double* weights, int radius, int frames, const double* raw, double* per_frame, hipStream_t s);
 // a workgroup per (sequence, channel) on rows (frames,4) and exclude (frames) or null: acf (n_seq,4,max_lag+1), per_seq (n_seq,4,10).  Where a sequence
 // has more than kRegLdsFrames frames: long_d (4,frames) float64, long_key (4,frames) int32 and words: 8 * mask_words (gait_mask_words); else null
 hipError_t launch_reg_sequences(const int* off, int n_seq, const RegRule& rule, const double* rows, const int* exclude, int frames, double* long_d, int* long_key,

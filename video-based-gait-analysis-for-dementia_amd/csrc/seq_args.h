@@ -1,4 +1,4 @@
-// The argument rules of the calls that take sequences lying back to back (boxes, metrics, trajectory, per-frame boxes, gait, kinematics and their
+// The argument rules of the calls that take sequences lying back to back (boxes, metrics, trajectory, per-frame boxes, the five gait calls and their
 // hooks): one statement each, in plain C++17 without a HIP header, so that a stand-alone program can run them (tests/helpers/seq_args_check.cpp).
 #pragma once
 #include <cstdint>
@@ -37,5 +37,20 @@ inline std::string joint_table_error(const int32_t* idx, int count, int J) {
         if (idx[k] < 0 || idx[k] >= J) return "joint index " + std::to_string(idx[k]) + " (entry " + std::to_string(k) + ") outside [0, " + std::to_string(J) + ")";
     return "";
 }
+
+// The opening of the five gait calls: "" and `table` = the call's `count` joint indices, or why not -- J < 1, else joint_table_error's words
+inline std::string joint_table_take(const int32_t* idx, int count, int J, int* table) {
+    if (J < 1) return "J " + std::to_string(J) + " < 1";
+    std::string why = joint_table_error(idx, count, J);
+    if (why.empty())
+        for (int k = 0; k < count; ++k) table[k] = idx[k];
+    return why;
+}
+
+// bytes of the (cols, frames) float64 columns that a call's frame kernel leaves for the Gaussian: none without one
+inline size_t raw_bytes(double sigma, size_t cols, size_t frames) { return sigma > 0. ? align256(cols * frames * sizeof(double)) : 0; }
+
+// a *_rule_error of the gait headers answers with a literal or null
+inline std::string rule_text(const char* why) { return why ? why : ""; }
 
 }  // namespace seq_args

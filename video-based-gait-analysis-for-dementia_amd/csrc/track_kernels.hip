@@ -22,6 +22,10 @@
 // reflection indexes [0, n) of its own sequence alone, and a sequence's rows have the same bits whatever else is in the call.
 //
 // track_filter_kernel -- the hooks grnet_op_median1d / grnet_op_gauss1d: stage (c) or (d) alone on a caller's columns, global to global.
+//
+// seq_gauss_columns_kernel -- the Gaussian of the gait calls (gait, kinematics, contacts, regularity; sigma > 0 alone): a workgroup per (sequence,
+// channel), thread per frame, the weights in LDS, track_gauss from the channel's column of the call's scratch into column col0 + channel of the
+// call's per-frame rows, `cols` values wide.  Width and first column are arguments: one multiply beside a chain of up to 129 dependent additions.
 #include "kernels.h"
 #include "device.h"
 #include "track_boxes.h"
@@ -132,6 +136,16 @@ __global__ __launch_bounds__(256) void track_filter_kernel(const int* __restrict
         out[(size_t)f0 + i] = radius >= 0 ? track_gauss(x + f0, n, i, weights, radius) : track_median(x + f0, n, i, ksize, pad);
 }
 
+__global__ __launch_bounds__(256) void seq_gauss_columns_kernel(const int* __restrict__ off, const double* __restrict__ weights, int radius, int frames,
+                                                                const double* __restrict__ raw, double* __restrict__ out, int cols, int col0) {
+    __shared__ double w_lds[kTrackMaxRadius + 1];
+    const int f0 = off[blockIdx.x], T = off[blockIdx.x + 1] - f0, k = blockIdx.y;
+    if ((int)threadIdx.x <= radius) w_lds[threadIdx.x] = weights[threadIdx.x];
+    __syncthreads();
+    const double* x = raw + (size_t)k * frames + f0;
+    for (int i = threadIdx.x; i < T; i += 256) out[((size_t)f0 + i) * cols + col0 + k] = track_gauss(x, T, i, w_lds, radius);
+}
+
 }  // namespace
 
 hipError_t launch_track_frames(const double* joints, int K, int frames, double vis_thresh, double* params, unsigned long long* words, hipStream_t s) {
@@ -145,6 +159,11 @@ hipError_t launch_track_sequences(const int* off, int n_seq, const double* weigh
 
 hipError_t launch_track_filter(const int* off, int n_seq, const double* x, const double* weights, int radius, int ksize, int pad, double* out, hipStream_t s) {
     return launch_k(track_filter_kernel, dim3(n_seq), dim3(256), 0, s, off, x, weights, radius, ksize, pad, out);
+}
+
+hipError_t launch_seq_gauss_columns(const int* off, int n_seq, int channels, const double* weights, int radius, int frames, const double* raw, double* out,
+                                    int cols, int col0, hipStream_t s) {
+    return launch_k(seq_gauss_columns_kernel, dim3(n_seq, channels), dim3(256), 0, s, off, weights, radius, frames, raw, out, cols, col0);
 }
 
 }  // namespace grk

@@ -75,6 +75,8 @@ def resolve_joint_regressor(J, select="reference"):
     return W, sel
 
 
+_GAIT_JOINT_NAMES = "pelvis, spine-shoulder, left / right hip, ankle, foot"
+_KIN_JOINT_NAMES = "pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist"
 _ARENA_FIELDS = ("bytes", "full_bytes", "lower_bound_bytes", "tensors", "shared_tensors")
 
 
@@ -1091,6 +1093,28 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gauss1d")
         return out
 
+    # ------------------------------------------------------------------ what the gait calls take alike: the joint table, events, trans
+    @staticmethod
+    def _joint_table(joints, default, names):
+        table = np.asarray(default if joints is None else joints, np.int32).reshape(-1)
+        if table.size != len(default):
+            raise ValueError(f"joints must name {len(default)} joints ({names}), got {table.size}")
+        return table
+
+    def _events_input(self, n, events):
+        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
+        if tuple(ev.shape) != (n,):
+            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        return ev
+
+    def _trans_input(self, n, trans):
+        if trans is None:
+            return None
+        t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
+        if tuple(t.shape) != (n, 3):
+            raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
+        return t
+
     # ------------------------------------------------------------------ gait events and parameters from the 3D joints
     def gait_parameters(self, joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, window=5, min_excursion=0.05, joints=_lib.GAIT_JOINTS_KINECTV2):
         """Heel strikes, toe-offs and the gait parameters of every sequence on the device (grnet_gait_parameters; the rules and the columns: DESIGN
@@ -1103,14 +1127,8 @@ class GRNet:
         degenerate frame has NaN signals and no events near it.  Works before finalize(): no weight is read.  Nothing synchronises."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
-        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
-        if table.size != 8:
-            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
-        t = None
-        if trans is not None:
-            t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
-            if tuple(t.shape) != (n, 3):
-                raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
         self._whole_frames(window=window)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
@@ -1147,12 +1165,8 @@ class GRNet:
         Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
-        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
-        if tuple(ev.shape) != (n,):
-            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
-        table = np.asarray(_lib.KINEMATICS_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
-        if table.size != 16:
-            raise ValueError(f"joints must name 16 joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist), got {table.size}")
+        ev = self._events_input(n, events)
+        table = self._joint_table(joints, _lib.KINEMATICS_JOINTS_KINECTV2, _KIN_JOINT_NAMES)
         self._whole_frames(min_stride=min_stride, max_stride=max_stride)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
@@ -1170,9 +1184,7 @@ class GRNet:
         """The cycle stage of gait_kinematics alone (grnet_op_gait_cycles): angles (n,13) float64 and events (n,) int32, one sequence or `lengths` of
         them lying back to back -> {curves (n_seq,13,101,2), per_sequence (n_seq,13,6)} on the device."""
         x = self._rows_input(angles, "angles", (13,), torch.float64)
-        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
-        if tuple(ev.shape) != (x.shape[0],):
-            raise ValueError(f"events must be ({x.shape[0]},), got {tuple(ev.shape)}")
+        ev = self._events_input(x.shape[0], events)
         self._whole_frames(min_stride=min_stride, max_stride=max_stride)
         off = self._sequence_offsets(x.shape[0], lengths, "angles")
         n_seq = len(off) - 1
@@ -1185,9 +1197,7 @@ class GRNet:
 
     # ------------------------------------------------------------------ turns and straight-walking gait parameters
     def _turn_inputs(self, n, events, gait_rows, min_frames, max_frames, max_turns):
-        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
-        if tuple(ev.shape) != (n,):
-            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        ev = self._events_input(n, events)
         rows = torch.as_tensor(gait_rows).to(self.device, torch.float64).contiguous()
         if tuple(rows.shape) != (n, 7):
             raise ValueError(f"gait_rows must be ({n},7), got {tuple(rows.shape)}")
@@ -1213,9 +1223,7 @@ class GRNet:
         Nothing synchronises."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
-        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
-        if table.size != 8:
-            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
         ev, rows = self._turn_inputs(n, events, gait_rows, min_frames, max_frames, max_turns)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
@@ -1246,9 +1254,7 @@ class GRNet:
 
     # ------------------------------------------------------------------ foot contact phases and double support
     def _contact_inputs(self, n, events, reach, max_frames, max_runs):
-        ev = torch.as_tensor(events).to(self.device, torch.int32).contiguous()
-        if tuple(ev.shape) != (n,):
-            raise ValueError(f"events must be ({n},), got {tuple(ev.shape)}")
+        ev = self._events_input(n, events)
         self._whole_frames(reach=reach, max_frames=max_frames, max_runs=max_runs)
         if not 1 <= int(max_runs) <= 512:
             raise ValueError(f"max_runs {max_runs} outside [1, 512]")      # the run table is allocated here: a size the C ABI would refuse is refused first
@@ -1272,9 +1278,7 @@ class GRNet:
         finalize(): no weight is read.  Nothing synchronises."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
-        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
-        if table.size != 8:
-            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
         ev = self._contact_inputs(n, events, reach, max_frames, max_runs)
         off = self._sequence_offsets(n, lengths, "joints3d")
         n_seq = len(off) - 1
@@ -1332,14 +1336,8 @@ class GRNet:
         on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
-        table = np.asarray(_lib.GAIT_JOINTS_KINECTV2 if joints is None else joints, np.int32).reshape(-1)
-        if table.size != 8:
-            raise ValueError(f"joints must name 8 joints (pelvis, spine-shoulder, left / right hip, ankle, foot), got {table.size}")
-        t = None
-        if trans is not None:
-            t = torch.as_tensor(trans).to(self.device, torch.float64).contiguous()
-            if tuple(t.shape) != (n, 3):
-                raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
         ex, off, out = self._regularity_call(n, lengths, exclude, max_lag, min_lag, min_pairs, "joints3d")
         out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
         rc = self._lib.grnet_gait_regularity(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),

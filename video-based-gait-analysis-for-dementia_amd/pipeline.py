@@ -890,6 +890,23 @@ def gauss_filter1d(x, sigma=3.0):
     return np.array([np.dot(ext[l:l + 2 * r + 1], w) for l in range(n)])
 
 
+_GAIT_JOINT_NAMES = "pelvis, spine-shoulder, left / right hip, ankle, foot"
+_KIN_JOINT_NAMES = "pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist"
+
+
+def _joint_table(joints, count, J, names):
+    """The `count` joint indices of a gait statement as int64, each within [0, J); `names` says in the message which joints they are."""
+    tab = np.asarray(joints, np.int64).reshape(-1)
+    if tab.size != count or tab.min() < 0 or tab.max() >= J:
+        raise ValueError(f"joints must be {count} indices into the {J} joints ({names})")
+    return tab
+
+
+def _sigma_check(sigma):
+    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
+        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+
+
 def track_boxes(joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0, pad="zero", return_params=False):
     """One box per frame from 2D joints in numpy float64: the reference's lib/utils/smooth_bbox.py (kp_to_bbox_param squared=True,
     get_all_bbox_params, smooth_bbox_params) and the box of lib/dataset/inference.py:57-66 -- the host statement of GRNet.track_boxes, same
@@ -908,8 +925,7 @@ def track_boxes(joints2d, lengths=None, vis_thresh=0.3, kernel_size=1, sigma=0.0
         raise ValueError("vis_thresh must be finite")
     if kernel_size < 1 or kernel_size > 31 or kernel_size % 2 == 0:
         raise ValueError(f"kernel_size {kernel_size} must be odd and within [1, 31]")
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _sigma_check(sigma)
     if pad not in ("zero", "edge"):
         raise ValueError(f"pad must be 'zero' or 'edge', got {pad!r}")
     boxes, status = np.zeros((n, 4)), np.full(n, TRACK_OUTSIDE, np.int32)
@@ -1015,13 +1031,10 @@ def gait_parameters(joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, win
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
-    tab = np.asarray(joints, np.int64).reshape(-1)
-    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
-        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
     if not np.isfinite(fps) or not fps > 0:
         raise ValueError("fps must be positive and finite")
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _sigma_check(sigma)
     if not 1 <= int(window) <= 32 or int(window) != window:
         raise ValueError(f"window {window} outside [1, 32]")
     if not np.isfinite(min_excursion) or min_excursion < 0:
@@ -1222,11 +1235,8 @@ def gait_kinematics(joints3d, events, lengths=None, sigma=2.0, min_stride=8, max
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
-    tab = np.asarray(joints, np.int64).reshape(-1)
-    if tab.size != 16 or tab.min() < 0 or tab.max() >= J:
-        raise ValueError(f"joints must be 16 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, knee, ankle, foot, shoulder, elbow, wrist)")
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    tab = _joint_table(joints, 16, J, _KIN_JOINT_NAMES)
+    _sigma_check(sigma)
     _kin_strides_check(min_stride, max_stride)
     if np.asarray(events).shape != (n,):
         raise ValueError(f"events must be ({n},), got {np.asarray(events).shape}")
@@ -1382,12 +1392,9 @@ def gait_turns(joints3d, events, gait_rows, lengths=None, fps=20.0, sigma=8.0, e
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
-    tab = np.asarray(joints, np.int64).reshape(-1)
-    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
-        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
     _turn_rule_check(fps, edge_rate, peak_rate, min_angle, min_frames, max_frames, max_turns)
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _sigma_check(sigma)
     pelvis, spine, lhip, rhip = (j3[:, i] for i in tab[:4])
     per_frame = np.zeros((n, 2))
     with np.errstate(all="ignore"):
@@ -1537,12 +1544,9 @@ def gait_contacts(joints3d, events, lengths=None, fps=20.0, sigma=0.0, fraction=
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
-    tab = np.asarray(joints, np.int64).reshape(-1)
-    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
-        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
     _contact_rule_check(fps, fraction, speed, reach, max_frames, max_runs)
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _sigma_check(sigma)
     per_frame = np.full((n, 4), np.nan)
     with np.errstate(all="ignore"):
         d = j3[:, tab[4]] - j3[:, tab[5]]
@@ -1685,12 +1689,9 @@ def gait_regularity(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, 
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
-    tab = np.asarray(joints, np.int64).reshape(-1)
-    if tab.size != 8 or tab.min() < 0 or tab.max() >= J:
-        raise ValueError(f"joints must be 8 indices into the {J} joints (pelvis, spine-shoulder, left / right hip, ankle, foot)")
+    tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
     _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs)
-    if not np.isfinite(sigma) or not 0 <= sigma <= 16:
-        raise ValueError("sigma must be 0 (no Gaussian) or within (0, 16]")
+    _sigma_check(sigma)
     tr = None
     if trans is not None:
         tr = np.asarray(trans, np.float64)
