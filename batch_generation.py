@@ -46,6 +46,12 @@ four body signals (the ankles' separation along the facing and along the trunk, 
 output): <outpath>_regularity.json.  The line prints its cadence beside --gait's: where the two disagree, the event rule failed on that video or the
 walk is not periodic.  With --gait_turns only straight walking counts.  Reported, never judged.
 
+--gait_harmonics (opt-in, with --gait) cuts the same four body signals at the heel strikes --gait found and reports the harmonic ratio of every
+stride -- the sum of the odd harmonics of its DFT over the sum of the even ones, or the inverse for the pelvis' height, which repeats every step --
+and its bounded form in percent (GRNet.gait_harmonics on the device; Smidt et al. 1971, Menz et al. 2003 and Bellanca et al. 2013 on
+trunk accelerations; the defaults are unvalidated on the model's output): <outpath>_harmonics.json.  With --gait_turns only straight strides count.
+Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -516,10 +522,69 @@ class WindowRegularity:
         return path
 
 
+class WindowHarmonics:
+    """--gait_harmonics: one gait_harmonics call per database window on rank 0, directly after WindowGait's, on the same joints and on the events that
+    call returned (model.gait_harmonics; on_host, or a model without the method: pipeline.gait_harmonics after a download) -- with the window's
+    translations where --trajectory made them, and with --gait_turns' phase as `exclude`, so that only straight strides count (straight_only).  Per
+    video and channel (pipeline.HARMONICS_CHANNELS) the twelve columns of pipeline.HARMONICS_COLUMNS, 'spectrum' (mean and SD of every harmonic's
+    amplitude) and 'strides', the stored strides keyed by pipeline.HARMONICS_STRIDE_COLUMNS.  The joints are pipeline.GAIT_JOINTS_KINECTV2, fps is
+    WindowGait's.  The defaults are unvalidated on the model's output; the results are reported and never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, n_harmonics=20, derivative=2, min_stride=8, max_stride=60):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_harmonics") else model.gait_harmonics
+        self.straight_only = bool(straight_only)
+        self.kw = dict(fps=float(fps), sigma=float(sigma), n_harmonics=int(n_harmonics), derivative=int(derivative), min_stride=int(min_stride), max_stride=int(max_stride))
+        self.videos = {}
+
+    def add_window(self, keys, j3, lengths, events, fitted=None, gait_phase=None):
+        """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths and the events (sum T,); fitted[vi] =
+        (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None."""
+        if not keys:
+            return
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
+            out = self.pipe.gait_harmonics(j3.cpu().numpy(), ev, lengths=lengths, trans=trans, exclude=exclude, **self.kw)
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        for key, rows, spectrum, strides in zip(keys, out["per_sequence"], out["spectrum"], out["strides"]):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.HARMONICS_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.HARMONICS_COLUMNS, rows[c])}
+                video[name]["spectrum"] = [{"mean": number(m), "sd": number(sd)} for m, sd in spectrum[c]]
+                video[name]["strides"] = [{col: number(v) for col, v in zip(self.pipe.HARMONICS_STRIDE_COLUMNS, stride)} for stride in strides[c] if not np.isnan(stride[0])]
+            self.videos[key] = video
+            sep, bob = video["sep"], video["bob"]
+            pelvis = f", of the pelvis' height {shown(bob['hr_mean'], '.3f')} ({shown(bob['ihr_mean'], '.1f', ' %')})" if trans is not None else ""
+            print(f"Harmonics: video {key}, {int(rows[0][1])} of {int(rows[0][0])} strides used, harmonic ratio of the ankles' separation {shown(sep['hr_mean'], '.3f')} "
+                  f"({shown(sep['ihr_mean'], '.1f', ' %')}){pelvis}, left / right index {shown(sep['hr_left_right_index'], '.1f', ' %')}"
+                  f"{', straight strides only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait harmonics of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
-                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None):
-    """regularity: {'sigma', 'max_lag', 'min_lag', 'min_peak', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional, with 'fps'; needs no gait, whose
+                 metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
+                 harmonics=None):
+    """harmonics: {'sigma', 'n_harmonics', 'derivative', 'min_stride', 'max_stride', 'all_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
+    takes) -- also the harmonic ratios per stride of every video (WindowHarmonics), written to harmonics['out'] (default: outpath with _harmonics.json);
+    with turns only straight strides count unless 'all_frames'; the database gains nothing.
+    regularity: {'sigma', 'max_lag', 'min_lag', 'min_peak', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional, with 'fps'; needs no gait, whose
     fps it takes where it has none) -- also the step and stride regularity, the symmetry and the autocorrelation cadence of every video (WindowRegularity), written to
     regularity['out'] (default: outpath with _regularity.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
     contacts: {'sigma', 'fraction', 'speed', 'reach', 'max_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the
@@ -611,6 +676,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                               **({"fps": gait["fps"]} if regularity.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
                               **{k: regularity[k] for k in ("fps", "sigma", "max_lag", "min_lag", "min_peak", "min_pairs") if regularity.get(k) is not None}) \
         if regularity is not None and rank == 0 else None
+    if harmonics is not None and gait is None:
+        raise ValueError("harmonics needs gait: the strides are cut at the heel strikes it finds")
+    smooth = WindowHarmonics(pipe, model, harmonics.get("on_host", False), not harmonics.get("all_frames", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
+                             **{k: harmonics[k] for k in ("sigma", "n_harmonics", "derivative", "min_stride", "max_stride") if harmonics.get(k) is not None}) \
+        if harmonics is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -667,6 +737,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         gait_support = stands.add_window([v[0] for v in vids], *walk.window) if stands is not None and vids else None
         if steady is not None and vids:
             steady.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None)
+        if smooth is not None and vids:
+            smooth.add_window([v[0] for v in vids], *walk.window, fitted, gait_phase)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -700,6 +772,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         stands.write(contacts.get("out") or osp.splitext(outpath)[0] + "_contacts.json")
     if steady is not None:
         steady.write(regularity.get("out") or osp.splitext(outpath)[0] + "_regularity.json")
+    if smooth is not None:
+        smooth.write(harmonics.get("out") or osp.splitext(outpath)[0] + "_harmonics.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -788,6 +862,18 @@ def main(argv=None):
     p.add_argument("--regularity_min_pairs", type=int, default=None, help="with --gait_regularity: a lag with fewer pairs of frames is undefined, 2 to 2^20 (default 20)")
     p.add_argument("--regularity_all_frames", action="store_true", help="with --gait_regularity and --gait_turns: count the frames of the turns too")
     p.add_argument("--regularity_on_host", action="store_true", help="with --gait_regularity: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_harmonics", action="store_true", help="with --gait: the harmonic ratio of every stride between two heel strikes of one foot, of four body "
+                   "signals (Smidt et al. 1971, Menz et al. 2003, Bellanca et al. 2013): <outpath>_harmonics.json, one line per video; the defaults are unvalidated on the "
+                   "model's output")
+    p.add_argument("--harmonics_out", type=str, default="", help="with --gait_harmonics: the JSON file (default: --outpath with _harmonics.json)")
+    p.add_argument("--harmonics_sigma", type=float, default=None, help="with --gait_harmonics: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0: "
+                   "a Gaussian damps the harmonics)")
+    p.add_argument("--harmonics_count", type=int, default=None, help="with --gait_harmonics: the harmonics of a stride, even, 2 to 32 (default 20)")
+    p.add_argument("--harmonics_derivative", type=int, default=None, help="with --gait_harmonics: 0 the signal, 1 its velocity, 2 its acceleration (default 2)")
+    p.add_argument("--harmonics_min_stride", type=int, default=None, help="with --gait_harmonics: the shortest stride in frames, 6 to the longest (default 8)")
+    p.add_argument("--harmonics_max_stride", type=int, default=None, help="with --gait_harmonics: the longest stride in frames, up to 255 (default 60)")
+    p.add_argument("--harmonics_all_frames", action="store_true", help="with --gait_harmonics and --gait_turns: count the strides of the turns too")
+    p.add_argument("--harmonics_on_host", action="store_true", help="with --gait_harmonics: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -908,6 +994,26 @@ def main(argv=None):
         sys.exit("batch_generation.py: --regularity_min_peak must be above 0 and at most 1")
     if a.regularity_min_pairs is not None and not 2 <= a.regularity_min_pairs <= 2 ** 20:
         sys.exit("batch_generation.py: --regularity_min_pairs must be within 2 to 2^20")
+    for flag, given in (("--harmonics_out", bool(a.harmonics_out)), ("--harmonics_sigma", a.harmonics_sigma is not None), ("--harmonics_count", a.harmonics_count is not None),
+                        ("--harmonics_derivative", a.harmonics_derivative is not None), ("--harmonics_min_stride", a.harmonics_min_stride is not None),
+                        ("--harmonics_max_stride", a.harmonics_max_stride is not None), ("--harmonics_all_frames", a.harmonics_all_frames),
+                        ("--harmonics_on_host", a.harmonics_on_host)):
+        if given and not a.gait_harmonics:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_harmonics, which was not given")
+    if a.gait_harmonics and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_harmonics needs --vid_folder (the frames whose joints it reads)")
+    if a.gait_harmonics and not a.gait:
+        sys.exit("batch_generation.py: --gait_harmonics needs --gait (the heel strikes its strides are cut at)")
+    if a.harmonics_sigma is not None and not (np.isfinite(a.harmonics_sigma) and 0 <= a.harmonics_sigma <= 16):
+        sys.exit("batch_generation.py: --harmonics_sigma must be within 0 to 16")
+    if a.harmonics_count is not None and not (2 <= a.harmonics_count <= 32 and a.harmonics_count % 2 == 0):
+        sys.exit("batch_generation.py: --harmonics_count must be even and within 2 to 32")
+    if a.harmonics_derivative is not None and not 0 <= a.harmonics_derivative <= 2:
+        sys.exit("batch_generation.py: --harmonics_derivative must be 0, 1 or 2")
+    if a.harmonics_max_stride is not None and not 6 <= a.harmonics_max_stride <= 255:
+        sys.exit("batch_generation.py: --harmonics_max_stride must be within 6 to 255 frames")
+    if not 6 <= (8 if a.harmonics_min_stride is None else a.harmonics_min_stride) <= (60 if a.harmonics_max_stride is None else a.harmonics_max_stride):
+        sys.exit("batch_generation.py: --harmonics_min_stride must be within 6 to --harmonics_max_stride frames")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -934,11 +1040,15 @@ def main(argv=None):
     regularity = {"fps": a.gait_fps, "sigma": a.regularity_sigma, "max_lag": a.regularity_max_lag, "min_lag": a.regularity_min_lag, "min_peak": a.regularity_min_peak,
                   "min_pairs": a.regularity_min_pairs, "all_frames": a.regularity_all_frames, "on_host": a.regularity_on_host,
                   "out": a.regularity_out or None} if a.gait_regularity else None
+    harmonics = {"sigma": a.harmonics_sigma, "n_harmonics": a.harmonics_count, "derivative": a.harmonics_derivative, "min_stride": a.harmonics_min_stride,
+                 "max_stride": a.harmonics_max_stride, "all_frames": a.harmonics_all_frames, "on_host": a.harmonics_on_host,
+                 "out": a.harmonics_out or None} if a.gait_harmonics else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
                  **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
-                 **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}))
+                 **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
+                 **({"harmonics": harmonics} if harmonics is not None else {}))
 
 
 if __name__ == "__main__":

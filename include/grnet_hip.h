@@ -786,6 +786,46 @@ int grnet_gait_regularity(grnet_t* h, const float* joints3d_dev, int J, const in
 int grnet_op_gait_autocorr(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
                            int max_lag, int min_lag, double min_peak, int min_pairs, double* acf_dev, double* per_seq_dev, void* stream);
 
+/* Harmonic ratios per stride of the same four body signals (Smidt et al. 1971, Menz et al. 2003, Bellanca et al. 2013, who measure trunk accelerations
+ * with a sensor; these signals are joint positions of a pose model and the defaults are unvalidated on its output): over each stride between two
+ * heel strikes of one foot, the amplitudes of the first harmonics of the detrended signal, the ratio of their even and odd sums, and its bounded form
+ * (which is the specification).  joints3d_dev, frame_offsets_host, joints_host, trans_dev and exclude_dev as grnet_gait_regularity takes
+ * them; events_dev (sum T) int32 is the `events` output of grnet_gait_parameters, of which bits 0 and 1 (the heel strikes) are read.  Float64, one
+ * rounding per operation:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma: sep, lift, sway ODD, bob EVEN.  sigma > 0 (<= 16) damps the higher harmonics.
+ *   strides  per sequence the pairs t0 < t1 of consecutive heel strikes of the left foot in time order, then those of the right; L = t1 - t0.  A
+ *            candidate is USED for a channel where min_stride <= L <= max_stride, the channel is finite and exclude is 0 on all of [t0, t1], and
+ *            neither sum E, O below fails to be positive and finite.
+ *   detrend  y(i) = (x(t0 + i) - x(t0)) - (x(t1) - x(t0)) ((double)i / (double)L), i = 0 .. L - 1.
+ *   twiddle  (sin, cos)(2 pi j / L) without libm: r = 4j, q = r div L, m = r mod L, swapped where 2m > L with m' = L - m, phi = (1.5707963267948966 m') /
+ *            L, z = phi phi, s = phi P(z), c = Q(z) by Horner with the doubles nearest to (-1)^k / (2k+1)!, k = 8 .. 0, and (-1)^k / (2k)!, k = 9 .. 0;
+ *            then selection and negation alone by q and swap.  Within 2^-51 of the true value for every 6 <= L <= 255.
+ *   DFT      H = min(n_harmonics, (L - 1) div 2), less one if odd; C_k = sum y(i) cos_j, S_k = sum y(i) sin_j, j = (k i) mod L, over i in time order from
+ *            +0.0; a_k = sqrt(C_k C_k + S_k S_k) (2.0 / L).
+ *   ratios   w_k = a_k g_k, g_k = 1, k or k k for derivative 0, 1, 2; E, O = the sums of w_k over the even and the odd k in rising k from +0.0, PE, PO
+ *            those of w_k w_k.  Odd channel: HR = O / E, iHR = (100 PO) / (PE + PO); even channel: HR = E / O, iHR = (100 PE) / (PE + PO).
+ * per_frame_dev (sum T, 4) float64.  strides_dev (n_seq, 4, max_strides, 6) float64: every candidate in order, [t0, t1 (inside the sequence), +1 left /
+ * -1 right, H if used else 0, HR, iHR (NaN unless used)]; rows past the count NaN; candidates past max_strides are counted and used, not stored.
+ * spectrum_dev (n_seq, 4, n_harmonics, 2) float64: mean and SD of a_k over the used strides whose H >= k, NaN where none.  per_seq_dev (n_seq, 4, 12)
+ * float64: [0] candidates; [1] used; [2, 3] HR mean, SD; [4, 5] HR mean of the left, of the right strides; [6] (100 |[4] - [5]|) / (0.5 ([4] + [5]));
+ * [7, 8] iHR mean, SD; [9] mean L of the used strides; [10] fps / [9]; [11] the least H used.  Means S / n in the candidates' order from +0.0, SDs
+ * two-pass with ddof 0, NaN where the count is 0.
+ * A workgroup per (sequence, channel), a wave per stride, a lane per (harmonic, cosine | sine); fixed orders, no atomics: a sequence's outputs have
+ * the same bits alone or among others, and its length is not limited.  Needs no weights.  At most three launches (two with sigma = 0) behind one small
+ * copy from pinned memory; no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, fps not positive and finite, sigma outside [0, 16], n_harmonics odd or outside
+ * [2, 32], derivative outside [0, 2], max_stride above 255, min_stride outside [6, max_stride], max_strides outside [1, 512].  Nothing is refused on
+ * the data.
+ * grnet_op_gait_stride_dft: the strides, spectra and rows alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_harmonics(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                         const double* trans_dev, const int32_t* events_dev, const int32_t* exclude_dev, double fps, double sigma, int n_harmonics,
+                         int derivative, int min_stride, int max_stride, int max_strides, double* per_frame_dev, double* strides_dev,
+                         double* spectrum_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_stride_dft(grnet_t* h, const double* signals_dev, const int32_t* events_dev, const int32_t* exclude_dev,
+                             const int32_t* frame_offsets_host, int n_seq, double fps, int n_harmonics, int derivative, int min_stride, int max_stride,
+                             int max_strides, double* strides_dev, double* spectrum_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

@@ -459,6 +459,15 @@ hipError_t launch_reg_frames(const float* joints, int J, int frames, const GaitT
 hipError_t launch_reg_sequences(const int* off, int n_seq, const RegRule& rule, const double* rows, const int* exclude, int frames, double* long_d, int* long_key,
                                 unsigned long long* words, size_t mask_words, double* acf, double* per_seq, hipStream_t s);
 
+// Harmonic ratios per stride of the same four signals (csrc/gait_harmonics_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_harmonics.h).  The frame kernel is launch_reg_frames ----
+struct HarRule;                            // gait_harmonics.h: fps, n_harmonics, derivative, min_stride, max_stride, max_strides
+// a workgroup per (sequence, channel) on rows (frames,4), the gait call's events (frames) and exclude (frames) or null: strides
+// (n_seq,4,max_strides,6), spectrum (n_seq,4,n_harmonics,2), per_seq (n_seq,4,12).  slots: 4 * har_slots(frames, n_seq) of n_harmonics + 4 float64.
+// Where a sequence has more than 64 * kGaitLdsWords frames: words: 8 * mask_words (gait_mask_words); else null
+hipError_t launch_har_sequences(const int* off, int n_seq, const HarRule& rule, const double* rows, const int* events, const int* exclude, int frames,
+                                unsigned long long* words, size_t mask_words, double* slots, double* strides, double* spectrum, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1115,6 +1115,14 @@ class GRNet:
             raise ValueError(f"trans must be ({n},3), got {tuple(t.shape)}")
         return t
 
+    def _exclude_input(self, n, exclude):
+        if exclude is None:
+            return None
+        ex = torch.as_tensor(exclude).to(self.device, torch.int32).contiguous()
+        if tuple(ex.shape) != (n,):
+            raise ValueError(f"exclude must be ({n},), got {tuple(ex.shape)}")
+        return ex
+
     # ------------------------------------------------------------------ gait events and parameters from the 3D joints
     def gait_parameters(self, joints3d, lengths=None, trans=None, fps=20.0, sigma=2.0, window=5, min_excursion=0.05, joints=_lib.GAIT_JOINTS_KINECTV2):
         """Heel strikes, toe-offs and the gait parameters of every sequence on the device (grnet_gait_parameters; the rules and the columns: DESIGN
@@ -1311,11 +1319,7 @@ class GRNet:
         self._whole_frames(max_lag=max_lag, min_lag=min_lag, min_pairs=min_pairs)
         if not 8 <= int(max_lag) <= 255:                           # the size of acf is made of it here
             raise ValueError(f"max_lag {max_lag} outside [8, 255]")
-        ex = None
-        if exclude is not None:
-            ex = torch.as_tensor(exclude).to(self.device, torch.int32).contiguous()
-            if tuple(ex.shape) != (n,):
-                raise ValueError(f"exclude must be ({n},), got {tuple(ex.shape)}")
+        ex = self._exclude_input(n, exclude)
         off = self._sequence_offsets(n, lengths, what)
         n_seq = len(off) - 1
         out = {"acf": torch.empty(n_seq, 4, int(max_lag) + 1, dtype=torch.float64, device=self.device),
@@ -1354,6 +1358,60 @@ class GRNet:
         rc = self._lib.grnet_op_gait_autocorr(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps), int(max_lag),
                                               int(min_lag), float(min_peak), int(min_pairs), out["acf"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_autocorr")
+        return out
+
+    # ------------------------------------------------------------------ harmonic ratios per stride
+    def _harmonics_call(self, n, events, lengths, exclude, n_harmonics, derivative, min_stride, max_stride, max_strides, what):
+        """(events and exclude on the device, offsets, the strides, spectrum and per_sequence tensors) of gait_harmonics and its hook."""
+        ev = self._events_input(n, events)
+        self._whole_frames(n_harmonics=n_harmonics, derivative=derivative, min_stride=min_stride, max_stride=max_stride, max_strides=max_strides)
+        if not 2 <= int(n_harmonics) <= 32 or int(n_harmonics) % 2:        # the sizes of spectrum and strides are made of these here
+            raise ValueError(f"n_harmonics {n_harmonics} must be even and within [2, 32]")
+        if not 1 <= int(max_strides) <= 512:
+            raise ValueError(f"max_strides {max_strides} outside [1, 512]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"strides": torch.empty(n_seq, 4, int(max_strides), 6, dtype=torch.float64, device=self.device),
+               "spectrum": torch.empty(n_seq, 4, int(n_harmonics), 2, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, 12, dtype=torch.float64, device=self.device)}
+        return ev, ex, off, out
+
+    def gait_harmonics(self, joints3d, events, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, n_harmonics=20, derivative=2, min_stride=8,
+                       max_stride=60, max_strides=128, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Harmonic ratios per stride of every sequence on the device (grnet_gait_harmonics; the rules, channels and columns: DESIGN 4.16,
+        pipeline.HARMONICS_CHANNELS, HARMONICS_COLUMNS, HARMONICS_STRIDE_COLUMNS).  Called after gait_parameters on the same joints3d, lengths, trans and
+        joints, with its `events` (taken as int32); exclude as gait_regularity takes it.  The four signals of gait_regularity, smoothed by sigma
+        frames (0: none, the default, since a Gaussian damps the harmonics it is about to report; <= 16), are cut at consecutive heel strikes of one
+        foot; a stride of min_stride .. max_stride (6 .. 255) frames that is finite and not excluded throughout is detrended, its first H <=
+        n_harmonics (even, 2 .. 32) harmonics below Nyquist are weighted by k^derivative (2: the acceleration the papers measure) and summed over the
+        even and the odd k.  HR is odd / even on sep, lift and sway and even / odd on bob; iHR its bounded form in percent.  Returns a dict of device
+        tensors: per_frame (n,4) float64; strides (n_seq,4,max_strides,6); spectrum (n_seq,4,n_harmonics,2); per_sequence (n_seq,4,12).  The
+        defaults are unvalidated on the model's output.  Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing
+        synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ev, ex, off, out = self._harmonics_call(n, events, lengths, exclude, n_harmonics, derivative, min_stride, max_stride, max_strides, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_harmonics(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                            ev.data_ptr(), None if ex is None else ex.data_ptr(), float(fps), float(sigma), int(n_harmonics), int(derivative),
+                                            int(min_stride), int(max_stride), int(max_strides), out["per_frame"].data_ptr(), out["strides"].data_ptr(),
+                                            out["spectrum"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_harmonics")
+        return out
+
+    def op_gait_stride_dft(self, signals, events, lengths=None, exclude=None, fps=20.0, n_harmonics=20, derivative=2, min_stride=8, max_stride=60,
+                           max_strides=128):
+        """Rules 3 to 8 of gait_harmonics alone (grnet_op_gait_stride_dft): signals (n,4) float64, events (n,) and exclude (n,) or None, one sequence or
+        `lengths` of them lying back to back -> {strides, spectrum, per_sequence} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ev, ex, off, out = self._harmonics_call(x.shape[0], events, lengths, exclude, n_harmonics, derivative, min_stride, max_stride, max_strides, "signals")
+        rc = self._lib.grnet_op_gait_stride_dft(self._h, x.data_ptr(), ev.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps),
+                                                int(n_harmonics), int(derivative), int(min_stride), int(max_stride), int(max_strides), out["strides"].data_ptr(),
+                                                out["spectrum"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_stride_dft")
         return out
 
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)

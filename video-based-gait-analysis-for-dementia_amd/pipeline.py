@@ -12,6 +12,7 @@ Reference counterparts:
     (SURVEY 8f-1 "next": OpenCV's warpAffine is third-party and absent offline -- parity UNPINNED; the
     PIL bilinear crop below follows the same geometry: box centre/size * scale -> 224x224, border 0)
 """
+import math
 import os
 import os.path as osp
 from collections import defaultdict
@@ -1686,11 +1687,20 @@ def gait_regularity(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, 
     same arguments, a dict of numpy arrays -- the same operations in the same order, every sum a cumulative sum.  joints3d (n,J,3) and joints as
     gait_parameters takes them (the foot entries are not read); trans (n,3) or None; exclude (n,) or None.  per_frame (n,4) = [sep, lift, sway, bob]
     as smoothed by sigma frames; acf and per_sequence: gait_autocorr's."""
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, lambda: _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs))
+    out = gait_autocorr(per_frame, lengths, exclude, fps, max_lag, min_lag, min_peak, min_pairs)
+    out["per_frame"] = per_frame
+    return out
+
+
+def _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check):
+    """(the sequences' lengths, per_frame (n,4)) of gait_regularity and gait_harmonics: rules 1 to 3 of DESIGN 4.15.  rule_check() refuses the caller's
+    own scalars, behind the joint table and before sigma, as the C ABI does."""
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
     tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
-    _regularity_rule_check(fps, max_lag, min_lag, min_peak, min_pairs)
+    rule_check()
     _sigma_check(sigma)
     tr = None
     if trans is not None:
@@ -1719,7 +1729,165 @@ def gait_regularity(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, 
                 for k in range(4):
                     per_frame[a:a + T, k] = gauss_filter1d(per_frame[a:a + T, k].copy(), sigma)
                 a += T
-    out = gait_autocorr(per_frame, lengths, exclude, fps, max_lag, min_lag, min_peak, min_pairs)
+    return lengths, per_frame
+
+
+# ----------------------------------------------------------------------------- harmonic ratios per stride
+HARMONICS_CHANNELS = REGULARITY_CHANNELS
+HARMONICS_COLUMNS = ("candidates", "used", "hr_mean", "hr_sd", "hr_left", "hr_right", "hr_left_right_index", "ihr_mean", "ihr_sd", "stride_frames",
+                     "strides_per_second", "least_harmonics")
+HARMONICS_STRIDE_COLUMNS = ("t0", "t1", "side", "harmonics", "hr", "ihr")
+_HARMONICS_SIN = tuple((-1.0) ** k / math.factorial(2 * k + 1) for k in range(9))      # every factorial here is a double: the division rounds once
+_HARMONICS_COS = tuple((-1.0) ** k / math.factorial(2 * k) for k in range(10))
+
+
+def _harmonics_rule_check(fps, n_harmonics, derivative, min_stride, max_stride, max_strides):
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if any(int(v) != v for v in (n_harmonics, derivative, min_stride, max_stride, max_strides)):
+        raise ValueError("n_harmonics, derivative, min_stride, max_stride and max_strides must be whole numbers")
+    if not 2 <= n_harmonics <= 32 or n_harmonics % 2:
+        raise ValueError(f"n_harmonics {n_harmonics} must be even and within [2, 32]")
+    if not 0 <= derivative <= 2:
+        raise ValueError(f"derivative {derivative} outside [0, 2]")
+    if max_stride > 255:
+        raise ValueError(f"max_stride {max_stride} above 255")
+    if not 6 <= min_stride <= max_stride:
+        raise ValueError(f"min_stride {min_stride} outside [6, max_stride]")
+    if not 1 <= max_strides <= 512:
+        raise ValueError(f"max_strides {max_strides} outside [1, 512]")
+
+
+def harmonics_twiddles(L):
+    """Rule 5 of DESIGN 4.16: (sin, cos) of 2 pi j / L for j = 0 .. L - 1 without libm -- the reduction in integers, two Horner polynomials on [0, pi/4],
+    then selection and negation alone.  The device and the host checker make the same bits."""
+    j = np.arange(int(L), dtype=np.int64)
+    r = 4 * j
+    q, m = r // L, r % L
+    swap = 2 * m > L
+    phi = (1.5707963267948966 * np.where(swap, L - m, m).astype(np.float64)) / float(L)
+    z = phi * phi
+    p = np.full(z.shape, _HARMONICS_SIN[-1])
+    for coef in _HARMONICS_SIN[-2::-1]:
+        p = p * z + coef
+    s = phi * p
+    c = np.full(z.shape, _HARMONICS_COS[-1])
+    for coef in _HARMONICS_COS[-2::-1]:
+        c = c * z + coef
+    a, b = np.where(swap, c, s), np.where(swap, s, c)
+    return np.choose(q, [a, b, -a, -b]), np.choose(q, [b, -a, -b, a])
+
+
+def _harmonics_moments(values):
+    """(S / n, the two-pass SD with ddof 0) of the values in the order given, or (NaN, NaN) of none."""
+    v = np.asarray(values, np.float64)
+    if v.size == 0:
+        return np.nan, np.nan
+    m = _regularity_sum(v) / v.size
+    d = v - m
+    return m, float(np.sqrt(_regularity_sum(d * d) / v.size))
+
+
+def gait_stride_dft(signals, events, lengths=None, exclude=None, fps=20.0, n_harmonics=20, derivative=2, min_stride=8, max_stride=60, max_strides=128,
+                    return_sums=False):
+    """Rules 3 to 8 of DESIGN 4.16 on given signals: the host statement of GRNet.op_gait_stride_dft.  signals (n,4) float64, columns
+    HARMONICS_CHANNELS; events (n,) as gait_parameters returns them (bits 0 and 1 are read); exclude (n,) or None.  Returns {'strides':
+    (n_seq,4,max_strides,6), columns HARMONICS_STRIDE_COLUMNS, 'spectrum': (n_seq,4,n_harmonics,2), 'per_sequence': (n_seq,4,12), columns
+    HARMONICS_COLUMNS}; every sum in the order of the rules from +0.0, every comparison false for NaN.  return_sums: also 'sums', a list of
+    (sequence, channel, t0, t1, y, C, S) of every used stride, in order."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64)
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    _harmonics_rule_check(fps, n_harmonics, derivative, min_stride, max_stride, max_strides)
+    fps, n_h, d, max_strides = float(fps), int(n_harmonics), int(derivative), int(max_strides)
+    strides = np.full((len(lengths), 4, max_strides, 6), np.nan)
+    spectrum = np.full((len(lengths), 4, n_h, 2), np.nan)
+    per_seq = np.full((len(lengths), 4, 12), np.nan)
+    tables, sums = {}, []
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            e = ev[f0:f0 + T]
+            cand = []
+            for bit, side in ((1, 1.0), (2, -1.0)):
+                at = np.flatnonzero(e & bit)
+                cand += [(int(t0), int(t1), side) for t0, t1 in zip(at[:-1], at[1:])]
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                used = []                                         # (side, L, H, HR, iHR, amplitudes)
+                for c, (t0, t1, side) in enumerate(cand):
+                    L = t1 - t0
+                    H, HR, iHR = 0, np.nan, np.nan
+                    if min_stride <= L <= max_stride and valid[t0:t1 + 1].all():
+                        i = np.arange(L)
+                        y = (s[t0:t1] - s[t0]) - (s[t1] - s[t0]) * (i.astype(np.float64) / float(L))
+                        if L not in tables:
+                            tables[L] = harmonics_twiddles(L)
+                        sn, cs = tables[L]
+                        H = min(n_h, (L - 1) // 2) & ~1
+                        C, S = np.zeros(H), np.zeros(H)
+                        for k in range(1, H + 1):
+                            j = (k * i) % L
+                            C[k - 1], S[k - 1] = _regularity_sum(y * cs[j]), _regularity_sum(y * sn[j])
+                        a = np.sqrt(C * C + S * S) * (2.0 / float(L))
+                        k = np.arange(1, H + 1)
+                        kf = k.astype(np.float64)
+                        w = a * (1.0 if d == 0 else kf if d == 1 else kf * kf)
+                        E, O = _regularity_sum(w[1::2]), _regularity_sum(w[0::2])
+                        PE, PO = _regularity_sum(w[1::2] * w[1::2]), _regularity_sum(w[0::2] * w[0::2])
+                        if E > 0 and np.isfinite(E) and O > 0 and np.isfinite(O):
+                            odd = ch < 3
+                            HR = O / E if odd else E / O
+                            iHR = (100.0 * (PO if odd else PE)) / (PE + PO)
+                            used.append((side, L, H, HR, iHR, a))
+                            if return_sums:
+                                sums.append((q, ch, t0, t1, y, C, S))
+                        else:
+                            H = 0
+                    if c < max_strides:
+                        strides[q, ch, c] = (t0, t1, side, H, HR, iHR)
+                out = per_seq[q, ch]
+                out[0], out[1] = len(cand), len(used)
+                out[2], out[3] = _harmonics_moments([u[3] for u in used])
+                out[4] = _harmonics_moments([u[3] for u in used if u[0] > 0])[0]
+                out[5] = _harmonics_moments([u[3] for u in used if u[0] < 0])[0]
+                out[6] = (100.0 * np.abs(out[4] - out[5])) / (0.5 * (out[4] + out[5]))
+                out[7], out[8] = _harmonics_moments([u[4] for u in used])
+                out[9] = _harmonics_moments([float(u[1]) for u in used])[0]
+                out[10] = fps / out[9]
+                out[11] = min((u[2] for u in used), default=np.nan)
+                for k in range(1, n_h + 1):
+                    spectrum[q, ch, k - 1] = _harmonics_moments([u[5][k - 1] for u in used if u[2] >= k])
+            f0 += T
+    out = {"strides": strides, "spectrum": spectrum, "per_sequence": per_seq}
+    if return_sums:
+        out["sums"] = sums
+    return out
+
+
+def gait_harmonics(joints3d, events, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, n_harmonics=20, derivative=2, min_stride=8, max_stride=60,
+                   max_strides=128, joints=GAIT_JOINTS_KINECTV2):
+    """Harmonic ratios per stride in numpy float64 (Smidt et al. 1971, Menz et al. 2003, Bellanca et al. 2013, on trunk accelerations; the rules: DESIGN
+    4.16; the defaults are unvalidated on the model's output): the host statement of GRNet.gait_harmonics, same arguments, a dict of numpy arrays --
+    the same operations in the same order, every sum a cumulative sum.  per_frame (n,4) is gait_regularity's at the same sigma; strides, spectrum and
+    per_sequence: gait_stride_dft's."""
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints,
+                                             lambda: _harmonics_rule_check(fps, n_harmonics, derivative, min_stride, max_stride, max_strides))
+    out = gait_stride_dft(per_frame, events, lengths, exclude, fps, n_harmonics, derivative, min_stride, max_stride, max_strides)
     out["per_frame"] = per_frame
     return out
 
