@@ -1,7 +1,9 @@
 """The host path the calls over sequences lying back to back share (csrc/grnet_seq.cpp, csrc/seq_args.h), as batch_generation.py uses it: different
 calls on ONE handle and one stream with no synchronise and no download between them.  What can go wrong there and in no single call: the front
-of the scratch, which every table upload overwrites with other weights and other offsets; the pinned ring of four slots, which eight uploads wrap;
-and the scratch growing while earlier calls are still in flight (here: at the first gait_kinematics and again at bbox_from_joints2d).
+of the scratch, which every table upload overwrites with other weights and other offsets; the pinned ring of four slots, which the uploads wrap
+several times; and the scratch growing while earlier calls are still in flight (here: at the first gait_kinematics and again at bbox_from_joints2d).
+The six gait calls run as batch_generation.py chains them: kinematics, turns, contacts and harmonics on the device tensor of the gait call's events,
+turns on its rows too, regularity and harmonics with the turns' phase as exclude.
 
 Expected: every output equals, bit for bit, the same call made alone on a second fresh handle with a synchronise after it.  That is derived, not
 a tolerance: the kernels are deterministic (test_gpu_gait.py asserts equal bits for repeated calls), and nothing differs between the two runs but
@@ -12,6 +14,7 @@ import torch
 
 from .helpers import gait_checks as gc
 from .helpers import track_checks as tk
+from .helpers import turn_checks as tc
 
 pytestmark = pytest.mark.gpu
 LENGTHS = [65, 130, 65]
@@ -19,19 +22,20 @@ LENGTHS = [65, 130, 65]
 
 def inputs():
     g = tk.golden()
-    made = [gc.walker(T, theta=0.37 * q, phi=-3.02 - 0.6137 * q) for q, T in enumerate(LENGTHS)]
+    made = [tc.turning_walker(T, ((T // 4, 30, 90.0),) if T == 130 else (), theta0=0.37 * q, phi=-3.02 - 0.6137 * q) for q, T in enumerate(LENGTHS)]
     joints = np.concatenate([j for j, _ in made])
     cam = joints.astype(np.float64) + np.array([0.3, 0.1, 6.0])
     seen = np.ones_like(cam)                                    # (x, y, confidence) in pixels: the walker under a camera of f = 1000 at (960, 540)
     seen[:, :, 0] = 1000.0 * cam[:, :, 0] / cam[:, :, 2] + 960.0
     seen[:, :, 1] = 1000.0 * cam[:, :, 1] / cam[:, :, 2] + 540.0
+    longer = [tc.turning_walker(4200, theta0=0.2), tc.turning_walker(65, theta0=0.9)]
     long_events = np.zeros(1100 + 65, np.int32)                 # heel strikes every 22 frames, the right foot half a stride behind
     long_events[3::22] |= gc.HEEL_L
     long_events[14::22] |= gc.HEEL_R
     return {"kp": np.concatenate([g["t26gaps_kp"], g["t70_kp"]]), "kp_lengths": [26, 70], "joints": joints, "trans": np.concatenate([t for _, t in made]),
             "shifted": joints + np.float32(0.01) * np.arange(3, dtype=np.float32), "seen": seen.astype(np.float32),
             "pairs": [(k, k) for k in range(25)], "long": np.concatenate([gc.walker(1100, theta=0.2)[0], gc.walker(65, theta=0.9)[0]]),
-            "long_events": long_events}
+            "long_events": long_events, "longer": np.concatenate([j for j, _ in longer]), "longer_trans": np.concatenate([t for _, t in longer])}
 
 
 def run(model, x, alone):
@@ -45,6 +49,10 @@ def run(model, x, alone):
     r["track"] = done(model.track_boxes(x["kp"], lengths=x["kp_lengths"], vis_thresh=tk.VIS_THRESH, kernel_size=11, sigma=3.0))
     r["gait"] = done(model.gait_parameters(x["joints"], lengths=LENGTHS, trans=x["trans"], sigma=2.0))
     r["kinematics"] = done(model.gait_kinematics(x["joints"], r["gait"]["events"], lengths=LENGTHS, sigma=2.0))
+    r["turns"] = done(model.gait_turns(x["joints"], r["gait"]["events"], r["gait"]["per_frame"], lengths=LENGTHS, sigma=8.0))
+    r["contacts"] = done(model.gait_contacts(x["joints"], r["gait"]["events"], lengths=LENGTHS))
+    r["regularity"] = done(model.gait_regularity(x["joints"], lengths=LENGTHS, trans=x["trans"], exclude=r["turns"]["phase"]))
+    r["harmonics"] = done(model.gait_harmonics(x["joints"], r["gait"]["events"], lengths=LENGTHS, trans=x["trans"], exclude=r["turns"]["phase"]))
     r["events"] = done(model.op_gait_events(r["gait"]["per_frame"][:, :4], lengths=LENGTHS))
     r["cycles"] = done(model.op_gait_cycles(r["kinematics"]["per_frame"], r["gait"]["events"], lengths=LENGTHS))
     r["median"] = done(model.op_median1d(r["track"]["boxes"][:, 0], lengths=x["kp_lengths"]))
@@ -56,6 +64,9 @@ def run(model, x, alone):
     r["gait0"] = done(model.gait_parameters(x["joints"], lengths=LENGTHS, trans=x["trans"], sigma=0.0))
     # phase 2: a sequence of more than 1024 frames keeps its heel-strike bitmasks in the scratch, behind the table, not in LDS
     r["long"] = done(model.gait_kinematics(x["long"], x["long_events"], lengths=[1100, 65], sigma=2.0))
+    # and one of more than 4096 frames keeps the event bitmasks of gait_parameters and the strike and validity masks of gait_harmonics there
+    r["longer_gait"] = done(model.gait_parameters(x["longer"], lengths=[4200, 65], trans=x["longer_trans"], sigma=2.0))
+    r["longer_harmonics"] = done(model.gait_harmonics(x["longer"], r["longer_gait"]["events"], lengths=[4200, 65], trans=x["longer_trans"]))
     return r
 
 
@@ -112,7 +123,7 @@ def test_calls_in_flight_together_equal_the_same_calls_alone(pkg):
     finally:
         together.close()
         alone.close()
-    assert len(got) == 12
+    assert len(got) == 18
     for call in want:
         for k, w in want[call].items():
             gk = got[call][k]
@@ -123,3 +134,7 @@ def test_calls_in_flight_together_equal_the_same_calls_alone(pkg):
     assert np.isfinite(want["kinematics"]["curves"]).any() and np.isfinite(want["cycles"]["curves"]).any() and np.isfinite(want["long"]["curves"][0]).any()
     assert (want["track"]["status"] == 0).sum() > 50 and np.isfinite(want["bbox"]["box"]).all() and np.isfinite(want["metrics"]["total"][:2]).all()
     assert (want["translation"]["per_frame"][:, 5] == 0).all()
+    assert want["turns"]["per_sequence"][:, 0].tolist() == [0, 1, 0] and (want["turns"]["phase"] != 0).sum() > 10                 # a turn is found
+    assert (want["contacts"]["per_sequence"][:, 3:5].sum(axis=1) > 0).all() and np.isin(want["contacts"]["phase"], (1, 2)).sum() > 10       # a double support is found
+    assert want["harmonics"]["per_sequence"][1, 0, 1] > 0 and want["regularity"]["per_sequence"][1, 0, 0] < 130                 # a stride is used; the turn's frames are left out
+    assert (want["longer_gait"]["events"][4096:4200] != 0).sum() > 10 and want["longer_harmonics"]["per_sequence"][0, 0, 1] > 100      # events and strides behind frame 4096
