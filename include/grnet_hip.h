@@ -860,8 +860,10 @@ int grnet_crop_normalise_cv_maps(grnet_t* h, const unsigned char* images_dev, in
  * up{2,3,4}.{layer}.{bilinear,conv}, cat (the 480-channel backbone output), head.{first,part_feats,heat,smpl_feats,cam_shape}
  * (head.first: the two 480 -> 128 first convolutions side by side), and per HR module stage{2,3,4}.{module}.x{branch} (the branch
  * outputs = the fuse layer's inputs) / .y{branch} (the module's outputs) / .b{branch}.{block}.conv1 (a BasicBlock's first convolution) /
- * .b{branch}.{block} (its output; block 3's is .x{branch}).  Parity tests compare these with the oracle's taps of
- * hrnet.py:469-536 and pare.py:305-336.
+ * .b{branch}.{block} (its output; block 3's is .x{branch}) / fp32 handles only: .d{i}.{j}.{level}, the output of stride-2 convolution
+ * `level` of the fuse layer's down chain from branch j to output i (the first links of the chains from one branch are one launch: one
+ * name per slice; the chain (nb-1, nb-2) is the convolution that finishes output nb-1 and has no such name).  Parity tests compare these
+ * with the oracle's taps of hrnet.py:469-536 and pare.py:305-336.
  * GRNET_EINVAL if n_frames is outside [1, frames of the last forward] (nothing is copied); GRNET_ESTATE if the last forward did not
  * write the tensor to memory (bf16, large calls: a convolution inside a row-walking or chain launch other than its last one, e.g.
  * stem_conv1 from 64 frames on) -- the buffer would hold an earlier forward's values; GRNET_ESTATE as well on a compact-arena handle

@@ -16,7 +16,9 @@ winograd_f43 / winograd_f43_fp32           F(4x4,3x3) on the whole map (zero-pad
                                            stored in the working type; input transform, channel sum (one sequential chain) and output transform in the
                                            working type.  In float64 it reproduces conv_reference to 1e-9 of a rounding of fp32.
 bilinear2x_fp32 / bilinear2x_torch_fp32    the two fp32 evaluations of the upsampling: the two-tap formula with fp32 coordinates, and torch's kernel
-epilogue                                   + bias, + residual, ReLU in fp32 on a linear fp32 result
+epilogue                                   + bias, + residual, ReLU in fp32 on a linear fp32 result; `residual` is one addend or a list of them (added in the
+                                           listed order), `relu` a bool or a mask per output channel (a merged launch, linear below relu_from) -- here and
+                                           in conv_reference / conv_magnitude / forward_check; tests/helpers/fuse_checks.py holds the fuse layers with them
 accepted(yardstick ratio)                  FACTOR x the yardstick's ratio on the same inputs, never below FACTOR.  The yardstick is the larger of the
                                            direct evaluations for the direct, stem, 1x1 and fuse kernels (YARDSTICK), the Winograd emulation for wino4,
                                            wino4w and wino4s.  No element is left out; an element of magnitude 0 must equal the reference exactly.
@@ -66,17 +68,30 @@ def rel_err(a, b):
 
 
 # ----------------------------------------------------------------------------------------------------------------- reference, magnitude
+def addends(residual):
+    """`residual` as the list of a launch's addends, in the order the launch adds them: None, one array, or a list of arrays"""
+    return [] if residual is None else list(residual) if isinstance(residual, (list, tuple)) else [residual]
+
+
+def apply_relu(y, relu):
+    """relu: a bool, or a mask per output channel -- a merged launch is linear below ConvLayer::relu_from and ReLU'd from there on"""
+    if isinstance(relu, (bool, np.bool_)):
+        return np.maximum(y, y.dtype.type(0)) if relu else y
+    mask = np.asarray(relu, bool)
+    assert mask.shape == (y.shape[1],), (mask.shape, y.shape)
+    return np.where(mask[None, :, None, None], np.maximum(y, y.dtype.type(0)), y)
+
+
 def _conv64(x, w, bias, stride, residual, mag):
     w = _t64(w, mag)
     y = F.conv2d(_t64(x, mag), w, None if bias is None else _t64(bias, mag), stride=stride, padding=w.shape[-1] // 2)
-    if residual is not None:
-        y = y + _t64(residual, mag)
+    for r in addends(residual):                                              # float64: the order does not matter; the magnitude adds |r|
+        y = y + _t64(r, mag)
     return y.numpy()
 
 
 def conv_reference(x, w, bias=None, stride=1, residual=None, relu=False):
-    y = _conv64(x, w, bias, stride, residual, False)
-    return np.maximum(y, 0.0) if relu else y
+    return apply_relu(_conv64(x, w, bias, stride, residual, False), relu)
 
 
 def conv_magnitude(x, w, bias=None, stride=1, residual=None):
@@ -212,13 +227,14 @@ def winograd_f43_fp32(x, w):
 
 
 def epilogue(lin, bias=None, residual=None, relu=False):
-    """fl(fl(lin + bias) + residual), ReLU: what follows the sum in fp32."""
+    """fl(fl(lin + bias) + residual), ReLU: what follows the sum in fp32.  Several addends are added in the listed order; relu may be a mask per
+    output channel (apply_relu)."""
     y = np.asarray(lin, np.float32)
     if bias is not None:
         y = y + np.asarray(bias, np.float32)[None, :, None, None]
-    if residual is not None:
-        y = y + np.asarray(residual, np.float32)
-    return np.maximum(y, np.float32(0)) if relu else y
+    for r in addends(residual):
+        y = y + np.asarray(r, np.float32)
+    return apply_relu(y, relu)
 
 
 def accepted(yardstick_ratio):
@@ -277,8 +293,12 @@ class Case:
 def forward_check(family, got, x, w64, shift64, stride=1, residual=None, relu=False):
     """One launch of the forward on its own tapped input x (and residual): w64, shift64 are the BatchNorm-folded weights and shift in float64
     (fold_bn), which is what the reference and the magnitude are computed from; the yardstick's fp32 evaluation takes them rounded to fp32, the
-    Winograd emulation transforms the float64 filter as the weight packers do.  Returns what Case.check returns."""
+    Winograd emulation transforms the float64 filter as the weight packers do.  residual: one addend or a list of them (the reference adds them in
+    float64, the magnitude their absolute values, the fp32 yardstick adds them in the listed order); relu: a bool or a mask per output channel (a
+    merged launch: w64, shift64 are the segments' concatenated).  Returns what Case.check returns."""
     ref, mag = conv_reference(x, w64, shift64, stride, residual, relu), conv_magnitude(x, w64, shift64, stride, residual)
+    if not isinstance(relu, (bool, np.bool_)):
+        relu = np.asarray(relu, bool)
     w32, b32 = w64.astype(np.float32), shift64.astype(np.float32)
     if YARDSTICK[family] == "winograd":
         fp32, name = {"winograd": (winograd_f43(x, w64, np.float32), np.arange(len(w64)))}, "winograd"
@@ -288,7 +308,8 @@ def forward_check(family, got, x, w64, shift64, stride=1, residual=None, relu=Fa
         if ch is not None:
             fp32["sequential"] = (sequential_fp32(x, w32, stride, ch), ch)
             name += "+sequential" + ("" if len(ch) == len(w64) else f"[{len(ch)}/{len(w64)}ch]")
-    y = max(ratio(epilogue(lin, b32[ch], None if residual is None else residual[:, ch], relu), ref[:, ch], mag[:, ch])[0] for lin, ch in fp32.values())
+    on = lambda ch: relu if isinstance(relu, (bool, np.bool_)) else relu[ch]
+    y = max(ratio(epilogue(lin, b32[ch], [r[:, ch] for r in addends(residual)], on(ch)), ref[:, ch], mag[:, ch])[0] for lin, ch in fp32.values())
     r, at = ratio(got, ref, mag)
     return r, at, y, name, accepted(y)
 

@@ -7,7 +7,9 @@ distinct frames tiled (frame k is frame k % 8): every copy of a frame must give 
 on the 8 distinct frames.  Before the checked forward the handle runs a forward of the same size on other frames, so a consumer that reads a buffer
 before its producer has written it reads different numbers and fails.  Which kernel and launch form each size takes is asserted first
 (grnet_conv_kernel_info, grnet_conv_launch_form), so that a plan change cannot quietly move a check onto another kernel.  At 16 frames every convolution launch is also held, element by element,
-to the rule of tests/test_gpu_conv_elements.py on its own tapped input (Checker.conv; tests/helpers/conv_checks.py forward_check)."""
+to the rule of tests/test_gpu_conv_elements.py on its own tapped input (Checker.conv; tests/helpers/conv_checks.py forward_check) -- the 42 launches
+of the eight fuse layers included (Checker.fuse; tests/helpers/fuse_checks.py: the down chains are tapped as "<stage>.<m>.d<i>.<j>.<level>") -- and the
+six bilinear launches likewise (Checker.bilinear)."""
 import ctypes as C
 import hashlib
 
@@ -17,6 +19,7 @@ import torch
 
 from .conftest import rel_err
 from .helpers import conv_checks as cc
+from .helpers import fuse_checks as fc
 from .helpers import smpl_checks as sc
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +62,7 @@ def _tap_names(direct_only=False):
             if not direct_only:
                 names += [f"{stage}.{m}.b{b}.{k}.conv1" for k in range(4)] + [f"{stage}.{m}.b{b}.{k}" for k in range(3)]
             names.append(f"{stage}.{m}.x{b}")
+        names += [f"{stage}.{m}.{t}" for t in fc.down_taps(nb)]          # the down chains of the fuse layer: direct launches, a tap per slice
         names += [f"{stage}.{m}.y{i}" for i in range(nb)]
     if direct_only:
         return names + ["head.smpl_feats", "head.cam_shape"]
@@ -182,6 +186,36 @@ class Checker:
         self.worst[k] = max(self.worst.get(k, 0.0), ratio / bar)
         assert ratio <= bar, (name, fam, ratio, at, bar)
 
+    def bilinear(self, name, g, r, x):
+        self("bilinear", name, g, r)
+        if self.elements:
+            f = slice(0, self.elements)
+            res = cc.bilinear_check(g[f], _np(x)[f])
+            print(fc.bounds_line("forward16", name, "bilinear", "linear", res, cc.where(res[1], "bilinear", {}, g.shape[2])))
+            self._hold("bilinear", name, res)
+
+    def fuse(self, tag, nb, got):
+        """Every launch of the fuse layer of module `tag` on its own tapped inputs, per element: the down chains' stride-2 convolutions (a merged
+        first link as ONE convolution with a ReLU per segment), every output of the grouped launch (fuse_checks.fuse_up_check), and the finishing
+        convolution with its addends.  Measured and printed first, asserted at the end."""
+        w, f = fc.FuseWeights(self.sd, f"{B}{tag}."), slice(0, self.elements)
+        taps = {t: got[f"{tag}.{t}"] for t in [f"x{b}" for b in range(nb)] + [f"y{b}" for b in range(nb)] + fc.down_taps(nb)}
+        held = []
+        for L in fc.fuse_launches(nb):
+            form = {} if L["kind"] == "up" else self.by_key[w.down_key(L["segs"][0] if L["kind"] == "down" else L["seg"])][1]
+            for name, fam, text, g, res, i in fc.check_launch(L, w, taps, f, form.get("family", "fuse")):
+                place = fc.where(res[1], i, nb) if L["kind"] == "up" else cc.where(res[1], fam, form, g.shape[2])
+                print(fc.bounds_line("forward16", f"{tag}.{name}", fam, text, res, place))
+                held.append((fam if L["kind"] != "finish" else fam + " finish", f"{tag}.{name}", res))
+        for fam, name, res in held:
+            self._hold(fam, name, res)
+
+    def _hold(self, fam, name, res):
+        ratio, at, _, _, bar = res
+        k = fam + " elements"
+        self.worst[k] = max(self.worst.get(k, 0.0), ratio / bar)
+        assert ratio <= bar, (name, fam, ratio, at, bar)
+
 
 def _check_direct_stages(ck, oracle, sd, got, base):
     """The stages that hold a direct-kernel launch: stem_conv2, layer1's convolutions, the transitions, the fuse layers and head.cam_shape."""
@@ -212,6 +246,8 @@ def _check_direct_stages(ck, oracle, sd, got, base):
             ys = oracle.hr_fuse([T(f"{tag}.x{b}") for b in range(nb)], sd, f"{B}{tag}.")
             for i in range(nb):
                 ck("fuse", f"{tag}.y{i}", got[f"{tag}.y{i}"], ys[i])
+            if ck.elements:
+                ck.fuse(tag, nb, got)
         hd = "head."
         ck.conv(hd + "smpl_final_layer.weight", "head.cam_shape", got["head.cam_shape"],
                 oracle.conv2d(T("head.smpl_feats"), sd[hd + "smpl_final_layer.weight"], bias=sd[hd + "smpl_final_layer.bias"]),
@@ -239,7 +275,7 @@ def _check_all_stages(ck, oracle, sd, smpl, got, base):
             prev = f"stage4.2.y{br}"
             for l in range(layers):
                 nm, q = f"up{idx}.{l}", f"{B}upsample_stage_{idx}."
-                ck("bilinear", nm + ".bilinear", got[nm + ".bilinear"], oracle.upsample_bilinear2x(T(prev)))
+                ck.bilinear(nm + ".bilinear", got[nm + ".bilinear"], oracle.upsample_bilinear2x(T(prev)), got[prev])
                 ck.conv(q + f"{4 * l + 1}.weight", nm + ".conv", got[nm + ".conv"],
                         oracle.conv_bn(T(nm + ".bilinear"), sd, q + f"{4 * l + 1}.weight", q + f"{4 * l + 2}", relu=True),
                         own=dict(x=got[nm + ".bilinear"], bn=q + f"{4 * l + 2}", relu=True))
@@ -332,6 +368,14 @@ def _assert_forms(n, by_key):
     """The kernels and launch forms each size was chosen for (grnet_conv_kernel_info names, grnet_conv_launch_form fields)."""
     name = lambda key: by_key[key][0]
     form = lambda key: by_key[key][1]
+    for stage, mi, nb in MODULES:                                   # the fuse layers: direct stride-2 convolutions and one grouped launch each
+        w = fc.FuseWeights(None, f"{B}{stage}.{mi}.")
+        for L in fc.fuse_launches(nb):
+            if L["kind"] == "up":
+                assert form(f"{B}{stage}.{mi}.fuse_layers(up)")["family"] == "fuse_up", (stage, mi)
+                continue
+            key = w.down_key(L["segs"][0] if L["kind"] == "down" else L["seg"])
+            assert name(key) == "conv_direct_f32 3x3 s2" and form(key)["family"] == "direct", (key, name(key), form(key))
     for stage, mi, nb in MODULES:
         for b in range(nb):
             c, w = BR[b], 56 >> b
@@ -361,7 +405,8 @@ def _assert_forms(n, by_key):
 @pytest.mark.parametrize("n", SIZES)
 def test_every_fp32_launch_matches_float64_oracle_on_its_own_input(pkg, oracle, synth_weights, synth_smpl, n):
     """(a) the kernel families and launch forms of the size; (b) every convolution launch outside the fuse layers, every fuse layer, the bilinear
-    upsamplings and `cat` on their own tapped inputs; (c) attention pooling, the tail and SMPL from the GPU's own inputs; (d) the 8 distinct frames'
+    upsamplings and `cat` on their own tapped inputs -- at 16 frames also every launch INSIDE the fuse layers (down chains, grouped launch, finishing
+    convolution: Checker.fuse) and the bilinear launches per element; (c) attention pooling, the tail and SMPL from the GPU's own inputs; (d) the 8 distinct frames'
     outputs against oracle.grnet_forward.  Borders and tile seams separately, each slice at the bar of its family."""
     forms, got, differ, base = _run(pkg, n, _tap_names())
     assert not differ, f"copies of a frame differ at {n} frames: {differ}"
@@ -464,6 +509,11 @@ def test_debug_tensor_on_fp32_handles_refuses_frames_it_does_not_hold(pkg):
         torch.cuda.synchronize()
         assert m.debug_tensor("stage4.2.b3.0.conv1", 8).shape == (8, 256, 7, 7)
         assert m.debug_tensor("layer1.0.downsample", 8).shape == (8, 256, 56, 56)
+        # the down chains of the fuse layers, a merged first link slice by slice
+        assert m.debug_tensor("stage4.0.d3.0.2", 8).shape == (8, 256, 7, 7) and m.debug_tensor("stage3.1.d1.0.0", 8).shape == (8, 64, 28, 28)
+        assert m.debug_tensor("stage4.1.d3.1.0", 8).shape == (8, 64, 14, 14)
+        with pytest.raises(pkg._lib.GrnetError, match="code -22.*unknown debug tensor"):
+            m.debug_tensor("stage2.0.d1.0.0", 8)                                 # output 1 of a 2-branch layer is the finishing convolution alone
         for bad in (0, 9):
             with pytest.raises(pkg._lib.GrnetError, match="code -22"):
                 m.debug_tensor("layer1.2.conv2", bad)
@@ -485,5 +535,8 @@ def test_debug_tensor_on_fp32_handles_refuses_frames_it_does_not_hold(pkg):
             with pytest.raises(pkg._lib.GrnetError, match="code -1:.*not written"):
                 m.debug_tensor(name, 64)
         assert m.debug_tensor("stage3.0.x1", 64).shape == (64, 64, 28, 28)
+        for name in ("stage4.0.d3.0.2", "stage3.1.d1.0.0"):                      # taps of the fp32 plan only: unknown names here
+            with pytest.raises(pkg._lib.GrnetError, match="code -22.*unknown debug tensor"):
+                m.debug_tensor(name, 64)
     finally:
         m.close()

@@ -137,6 +137,11 @@ std::vector<View> grnet::hr_fuse_grouped(const std::vector<View>& xs, const std:
     for (int i = 1; i < nb; ++i)
         for (int j = 0; j < i; ++j) { d[i][j] = xs[j]; d_op[i][j] = branch_tail[j]; }
     auto follow_last = [&](int op_idx) { ops.back().follow = op_idx; };
+    // every down-chain tensor is a tap of the fp32 plan, "<stage>.<m>.d<i>.<j>.<level>" (a merged first link: one name per slice)
+    const std::string tag = p.substr(p.find("stage"));
+    auto name_d = [&](int i, int j, int level) {
+        if (dtype == 0) name_view(tag + "d" + std::to_string(i) + "." + std::to_string(j) + "." + std::to_string(level), d[i][j]);
+    };
     // early: chains from branches 0 .. nb-3 (and, for outputs < nb-1, from branch nb-2 too: D_{i,i-1} with i <= nb-2 starts at a branch <= nb-3).
     // The first convolutions of all chains that start at one branch share their input and are ONE launch: the linear one ((j+1, j): the whole chain
     // of output j+1, no ReLU) first, then the ReLU'd first links of the longer chains (ConvLayer::relu_from)
@@ -173,6 +178,7 @@ std::vector<View> grnet::hr_fuse_grouped(const std::vector<View>& xs, const std:
                     d[i][j] = slice(m, off, c);
                     d_op[i][j] = (int)ops.size() - 1;
                     off += c;
+                    name_d(i, j, 0);
                 }
                 members.clear();
             }
@@ -183,6 +189,7 @@ std::vector<View> grnet::hr_fuse_grouped(const std::vector<View>& xs, const std:
                 d[i][j] = conv_bn(d[i][j], key(i, j, level) + "0.weight", key(i, j, level) + "1", last ? kBranchCh[i] : kBranchCh[j], 3, 2, !last);
                 follow_last(d_op[i][j]);
                 d_op[i][j] = (int)ops.size() - 1;
+                name_d(i, j, level);
             }
         }
     // late: the grouped launch for outputs 0 .. nb-2 ...
