@@ -52,6 +52,13 @@ and its bounded form in percent (GRNet.gait_harmonics on the device, DESIGN 4.16
 trunk accelerations; the defaults are unvalidated on the model's output): <outpath>_harmonics.json.  With --gait_turns only straight strides count.
 Reported, never judged.
 
+--gait_entropy (opt-in, needs no --gait) reports how predictable the same four body signals are from one moment to the next: their sample entropy
+(Richman and Moorman 2000), at several scales (Costa et al. 2002) and summed to a complexity index, as the cognitive-impairment gait studies report
+it on a trunk accelerometer (Lamoth et al. 2011).  The device counts the matching pairs of templates (GRNet.gait_entropy); the
+logarithm is pipeline.entropy_rows'.  <outpath>_entropy.json.  These signals are joint positions of a pose model, 400 frames at 20 fps are at the
+short end of what the measure tolerates (Yentes et al. 2013), differencing twice amplifies joint noise, and the defaults are unvalidated on the model's
+output.  With --gait_turns only straight walking counts.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -577,11 +584,73 @@ class WindowHarmonics:
         return path
 
 
+class WindowEntropy:
+    """--gait_entropy: one gait_entropy call per database window on rank 0, one sequence per video, on the joints the window's gather left on the
+    device (model.gait_entropy; on_host, or a model without the method: pipeline.gait_entropy after a download) -- with the window's translations
+    where --trajectory made them, and with --gait_turns' phase as `exclude`, so that only straight walking counts (straight_only).  It needs no
+    events and so no --gait.  Either way the logarithm is pipeline.entropy_rows' on the integer counts.  Per video and channel
+    (pipeline.ENTROPY_CHANNELS) the columns of pipeline.ENTROPY_COLUMNS, per scale the counts (pipeline.ENTROPY_COUNTS) and 'sampen', and
+    'complexity'; null where undefined.  The joints are pipeline.GAIT_JOINTS_KINECTV2.  The defaults are unvalidated on the model's output; the
+    results are reported and never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, sigma=0.0, m=2, fraction=0.2, derivative=2, scales=3, min_templates=50):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_entropy") else model.gait_entropy
+        self.straight_only = bool(straight_only)
+        self.kw = dict(sigma=float(sigma), m=int(m), fraction=float(fraction), derivative=int(derivative), scales=int(scales))
+        self.min_templates = int(min_templates)
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_entropy(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw)
+        out.update(self.pipe.entropy_rows(out["counts"], self.min_templates))
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form):
+            return "none" if v is None else format(v, form)
+        for key, rows, counts, sampen, complexity in zip(keys, out["per_sequence"], out["counts"], out["sampen"], out["complexity"]):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.ENTROPY_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.ENTROPY_COLUMNS, rows[c])}
+                video[name]["scales"] = [dict({col: int(v) for col, v in zip(self.pipe.ENTROPY_COUNTS, counts[c][k])}, sampen=number(sampen[c][k]))
+                                         for k in range(self.kw["scales"])]
+                video[name]["complexity"] = number(complexity[c])
+            self.videos[key] = video
+            sep, bob = video["sep"], video["bob"]
+            pelvis = f", of the pelvis' height {shown(bob['scales'][0]['sampen'], '.3f')} ({shown(bob['complexity'], '.3f')})" if trans is not None else ""
+            print(f"Entropy: video {key}, {sep['scales'][0]['templates']} templates, sample entropy of the ankles' separation {shown(sep['scales'][0]['sampen'], '.3f')} "
+                  f"(complexity index over {self.kw['scales']} scales {shown(sep['complexity'], '.3f')}){pelvis}{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait entropy of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None):
-    """harmonics: {'sigma', 'n_harmonics', 'derivative', 'min_stride', 'max_stride', 'all_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
+                 harmonics=None, entropy=None):
+    """entropy: {'sigma', 'm', 'fraction', 'derivative', 'scales', 'min_templates', 'all_frames', 'on_host', 'out'} (each optional; needs no gait) -- also
+    the sample entropy at several scales and the complexity index of every video (WindowEntropy), written to entropy['out'] (default: outpath with
+    _entropy.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
+    harmonics: {'sigma', 'n_harmonics', 'derivative', 'min_stride', 'max_stride', 'all_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
     takes) -- also the harmonic ratios per stride of every video (WindowHarmonics), written to harmonics['out'] (default: outpath with _harmonics.json);
     with turns only straight strides count unless 'all_frames'; the database gains nothing.
     regularity: {'sigma', 'max_lag', 'min_lag', 'min_peak', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional, with 'fps'; needs no gait, whose
@@ -681,6 +750,9 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     smooth = WindowHarmonics(pipe, model, harmonics.get("on_host", False), not harmonics.get("all_frames", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                              **{k: harmonics[k] for k in ("sigma", "n_harmonics", "derivative", "min_stride", "max_stride") if harmonics.get(k) is not None}) \
         if harmonics is not None and rank == 0 else None
+    rough = WindowEntropy(pipe, model, entropy.get("on_host", False), not entropy.get("all_frames", False),
+                          **{k: entropy[k] for k in ("sigma", "m", "fraction", "derivative", "scales", "min_templates") if entropy.get(k) is not None}) \
+        if entropy is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -739,6 +811,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             steady.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None)
         if smooth is not None and vids:
             smooth.add_window([v[0] for v in vids], *walk.window, fitted, gait_phase)
+        if rough is not None and vids:
+            rough.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -774,6 +848,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         steady.write(regularity.get("out") or osp.splitext(outpath)[0] + "_regularity.json")
     if smooth is not None:
         smooth.write(harmonics.get("out") or osp.splitext(outpath)[0] + "_harmonics.json")
+    if rough is not None:
+        rough.write(entropy.get("out") or osp.splitext(outpath)[0] + "_entropy.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -874,6 +950,18 @@ def main(argv=None):
     p.add_argument("--harmonics_max_stride", type=int, default=None, help="with --gait_harmonics: the longest stride in frames, up to 255 (default 60)")
     p.add_argument("--harmonics_all_frames", action="store_true", help="with --gait_harmonics and --gait_turns: count the strides of the turns too")
     p.add_argument("--harmonics_on_host", action="store_true", help="with --gait_harmonics: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_entropy", action="store_true", help="with --vid_folder (no --gait needed): the sample entropy of four body signals at several scales and their "
+                   "complexity index (Richman and Moorman 2000, Costa et al. 2002, Lamoth et al. 2011): <outpath>_entropy.json, one line per video; quadratic in a "
+                   "video's frames; the defaults are unvalidated on the model's output")
+    p.add_argument("--entropy_out", type=str, default="", help="with --gait_entropy: the JSON file (default: --outpath with _entropy.json)")
+    p.add_argument("--entropy_sigma", type=float, default=None, help="with --gait_entropy: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--entropy_m", type=int, default=None, help="with --gait_entropy: the template length, 1 to 4 (default 2)")
+    p.add_argument("--entropy_r", type=float, default=None, help="with --gait_entropy: the tolerance as a fraction of the signal's SD, above 0 up to 10 (default 0.2)")
+    p.add_argument("--entropy_derivative", type=int, default=None, help="with --gait_entropy: 0 the signal, 1 its velocity, 2 its acceleration (default 2)")
+    p.add_argument("--entropy_scales", type=int, default=None, help="with --gait_entropy: the scales of the coarse-graining, 1 to 8 (default 3)")
+    p.add_argument("--entropy_min_templates", type=int, default=None, help="with --gait_entropy: a scale with fewer valid templates has no sample entropy, at least 1 (default 50)")
+    p.add_argument("--entropy_all_frames", action="store_true", help="with --gait_entropy and --gait_turns: count the frames of the turns too")
+    p.add_argument("--entropy_on_host", action="store_true", help="with --gait_entropy: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -1014,6 +1102,26 @@ def main(argv=None):
         sys.exit("batch_generation.py: --harmonics_max_stride must be within 6 to 255 frames")
     if not 6 <= (8 if a.harmonics_min_stride is None else a.harmonics_min_stride) <= (60 if a.harmonics_max_stride is None else a.harmonics_max_stride):
         sys.exit("batch_generation.py: --harmonics_min_stride must be within 6 to --harmonics_max_stride frames")
+    for flag, given in (("--entropy_out", bool(a.entropy_out)), ("--entropy_sigma", a.entropy_sigma is not None), ("--entropy_m", a.entropy_m is not None),
+                        ("--entropy_r", a.entropy_r is not None), ("--entropy_derivative", a.entropy_derivative is not None), ("--entropy_scales", a.entropy_scales is not None),
+                        ("--entropy_min_templates", a.entropy_min_templates is not None), ("--entropy_all_frames", a.entropy_all_frames),
+                        ("--entropy_on_host", a.entropy_on_host)):
+        if given and not a.gait_entropy:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_entropy, which was not given")
+    if a.gait_entropy and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_entropy needs --vid_folder (the frames whose joints it reads)")
+    if a.entropy_sigma is not None and not (np.isfinite(a.entropy_sigma) and 0 <= a.entropy_sigma <= 16):
+        sys.exit("batch_generation.py: --entropy_sigma must be within 0 to 16")
+    if a.entropy_m is not None and not 1 <= a.entropy_m <= 4:
+        sys.exit("batch_generation.py: --entropy_m must be within 1 to 4")
+    if a.entropy_r is not None and not (np.isfinite(a.entropy_r) and 0 < a.entropy_r <= 10):
+        sys.exit("batch_generation.py: --entropy_r must be above 0 and at most 10")
+    if a.entropy_derivative is not None and not 0 <= a.entropy_derivative <= 2:
+        sys.exit("batch_generation.py: --entropy_derivative must be 0, 1 or 2")
+    if a.entropy_scales is not None and not 1 <= a.entropy_scales <= 8:
+        sys.exit("batch_generation.py: --entropy_scales must be within 1 to 8")
+    if a.entropy_min_templates is not None and a.entropy_min_templates < 1:
+        sys.exit("batch_generation.py: --entropy_min_templates must be at least 1")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -1043,12 +1151,15 @@ def main(argv=None):
     harmonics = {"sigma": a.harmonics_sigma, "n_harmonics": a.harmonics_count, "derivative": a.harmonics_derivative, "min_stride": a.harmonics_min_stride,
                  "max_stride": a.harmonics_max_stride, "all_frames": a.harmonics_all_frames, "on_host": a.harmonics_on_host,
                  "out": a.harmonics_out or None} if a.gait_harmonics else None
+    entropy = {"sigma": a.entropy_sigma, "m": a.entropy_m, "fraction": a.entropy_r, "derivative": a.entropy_derivative, "scales": a.entropy_scales,
+               "min_templates": a.entropy_min_templates, "all_frames": a.entropy_all_frames, "on_host": a.entropy_on_host,
+               "out": a.entropy_out or None} if a.gait_entropy else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
                  **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
                  **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
-                 **({"harmonics": harmonics} if harmonics is not None else {}))
+                 **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}))
 
 
 if __name__ == "__main__":

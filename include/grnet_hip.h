@@ -826,6 +826,36 @@ int grnet_op_gait_stride_dft(grnet_t* h, const double* signals_dev, const int32_
                              const int32_t* frame_offsets_host, int n_seq, double fps, int n_harmonics, int derivative, int min_stride, int max_stride,
                              int max_strides, double* strides_dev, double* spectrum_dev, double* per_seq_dev, void* stream);
 
+/* Sample entropy of the same four body signals at several scales (Richman and Moorman 2000; the coarse-graining of Costa, Goldberger and Peng 2002;
+ * Lamoth et al. 2011, who measure trunk accelerations with a sensor; these signals are joint positions of a pose model, 400 frames are at the short
+ * end of what the measure tolerates and the defaults are unvalidated on its output): the COUNTS of matching template pairs per (sequence, channel,
+ * scale), in 64-bit integers (which is the specification).  joints3d_dev, frame_offsets_host, joints_host, trans_dev and exclude_dev
+ * as grnet_gait_regularity takes them.  Float64 with one rounding per operation in front of the counts:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma.  A frame counts for a channel where its signal is finite and exclude is 0.
+ *   y        the signal differenced `derivative` times, y_(k+1)(t) = y_k(t+1) - y_k(t): valid where the frames t .. t + derivative all count and the
+ *            result is finite; the last `derivative` frames of a sequence are invalid.  From here on an invalid value is NaN.
+ *   spread   n = the valid frames of y, mu = S / n, SD = sqrt(Q / (n - 1)) with S their sum and Q that of (y - mu)(y - mu), both in time order from
+ *            +0.0; r = fraction SD.  NaN where n < 2.
+ *   z_tau    for tau = 1 .. scales and j < N = T div tau: (y(j tau) + ... + y(j tau + tau - 1)) / tau, added in time order; NaN unless all are
+ *            valid and the result is finite.  r is the scale-1 r at every scale.
+ *   counts   template i, 0 <= i < N - m, is valid where z(i) .. z(i + m) all are.  B = the pairs i < j of valid templates with |z(i+k) - z(j+k)| <= r
+ *            for every k < m; A = those of them with |z(i+m) - z(j+m)| <= r too.  No self-matches.  Where r is not > 0, B = A = 0.
+ * per_frame_dev (sum T, 4) float64.  counts_dev (n_seq, 4, scales, 3) int64: [valid templates, B, A].  per_seq_dev (n_seq, 4, 4) float64: [n, mu, SD,
+ * r].  THE LOGARITHM IS THE CALLER'S: SampEn(tau) = ln(B / A) where both are positive (and, as the Python layer holds it, at least 50 templates are
+ * valid), the complexity index their sum over the scales.
+ * A workgroup per (sequence, channel, scale), a lane per template, every pair once; integer counts, no atomics: a sequence's outputs have the same
+ * bits alone or among others.  The work is QUADRATIC in a sequence's frames.  Needs no weights.  At most four launches (three with sigma = 0)
+ * behind one small copy from pinned memory; no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a sequence of more than 32768 frames, sigma outside [0, 16], m outside
+ * [1, 4], fraction not finite or outside (0, 10], derivative outside [0, 2], scales outside [1, 8].  Nothing is refused on the data.
+ * grnet_op_gait_sampen: y, the spread and the counts alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_entropy(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                       const double* trans_dev, const int32_t* exclude_dev, double sigma, int m, double fraction, int derivative, int scales,
+                       double* per_frame_dev, int64_t* counts_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_sampen(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, int m,
+                         double fraction, int derivative, int scales, int64_t* counts_dev, double* per_seq_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

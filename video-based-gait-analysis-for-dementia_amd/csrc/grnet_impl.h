@@ -16,6 +16,7 @@
 //   grnet_contacts.cpp foot contact phases and double support: grnet_gait_contacts and its runs hook
 //   grnet_regularity.cpp gait regularity from the autocorrelation: grnet_gait_regularity and its autocorrelation hook
 //   grnet_harmonics.cpp harmonic ratios per stride: grnet_gait_harmonics and its stride hook
+//   grnet_entropy.cpp  sample entropy at several scales: grnet_gait_entropy and its counting hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

@@ -468,6 +468,15 @@ struct HarRule;                            // gait_harmonics.h: fps, n_harmonics
 hipError_t launch_har_sequences(const int* off, int n_seq, const HarRule& rule, const double* rows, const int* events, const int* exclude, int frames,
                                 unsigned long long* words, size_t mask_words, double* slots, double* strides, double* spectrum, double* per_seq, hipStream_t s);
 
+// Sample entropy of the same four signals at several scales (csrc/gait_entropy_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_entropy.h).  The frame kernel is launch_reg_frames ----
+struct EntRule;                            // gait_entropy.h: m, fraction, derivative, scales
+// two launches on rows (frames,4) and exclude (frames) or null: a workgroup per (sequence, channel) makes y (4,frames), the differenced signal, and
+// per_seq (n_seq,4,4); a workgroup per (sequence, channel, scale) counts (n_seq,4,scales,3) int64.  z_long: (4 * scales,frames) float64 where a
+// sequence has more than kRegLdsFrames frames, else null
+hipError_t launch_ent_sequences(const int* off, int n_seq, const EntRule& rule, const double* rows, const int* exclude, int frames, double* y, double* z_long,
+                                long long* counts, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

@@ -1414,6 +1414,53 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_stride_dft")
         return out
 
+    # ------------------------------------------------------------------ sample entropy at several scales
+    def _entropy_call(self, n, lengths, exclude, m, derivative, scales, what):
+        """(exclude on the device or None, offsets, the counts and per_sequence tensors) of gait_entropy and its hook."""
+        self._whole_frames(m=m, derivative=derivative, scales=scales)
+        if not 1 <= int(scales) <= 8:                              # the size of counts is made of it here
+            raise ValueError(f"scales {scales} outside [1, 8]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"counts": torch.empty(n_seq, 4, int(scales), 3, dtype=torch.int64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, 4, dtype=torch.float64, device=self.device)}
+        return ex, off, out
+
+    def gait_entropy(self, joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, m=2, fraction=0.2, derivative=2, scales=3,
+                     joints=_lib.GAIT_JOINTS_KINECTV2):
+        """The counts behind the sample entropy of every sequence at several scales, on the device (grnet_gait_entropy; the rules, channels and
+        columns: DESIGN 4.17, pipeline.ENTROPY_CHANNELS, ENTROPY_COLUMNS, ENTROPY_COUNTS).  joints3d, lengths, trans, exclude and joints as
+        gait_regularity takes them.  Its four signals, smoothed by sigma frames (0: none, the default; <= 16), are differenced `derivative` times
+        (0 .. 2; 2: the acceleration the papers measure); r = fraction (in (0, 10]) times the SD of the frames that count; for every scale tau = 1
+        .. scales (<= 8) the signal is averaged over tau frames (Costa's coarse-graining, r kept) and every pair of templates of m + 1 values (m in
+        1 .. 4) is compared: B counts the pairs whose first m values lie within r of each other, A those whose next value does too.  A sequence
+        has at most 32 768 frames: the work is quadratic in them.  Returns a dict of device tensors: per_frame (n,4) float64, gait_regularity's
+        bits; counts (n_seq,4,scales,3) int64 = (valid templates, B, A); per_sequence (n_seq,4,4) float64 = (n, mu, SD, r).  The logarithm is
+        pipeline.entropy_rows(counts), on the host.  The defaults are unvalidated on the model's output.  Nothing is refused on the data.  Works
+        before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ex, off, out = self._entropy_call(n, lengths, exclude, m, derivative, scales, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_entropy(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                          None if ex is None else ex.data_ptr(), float(sigma), int(m), float(fraction), int(derivative), int(scales),
+                                          out["per_frame"].data_ptr(), out["counts"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_entropy")
+        return out
+
+    def op_gait_sampen(self, signals, lengths=None, exclude=None, m=2, fraction=0.2, derivative=2, scales=3):
+        """Rules 2 to 7 of gait_entropy alone (grnet_op_gait_sampen): signals (n,4) float64 and exclude (n,) or None, one sequence or `lengths` of
+        them lying back to back -> {counts, per_sequence} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, out = self._entropy_call(x.shape[0], lengths, exclude, m, derivative, scales, "signals")
+        rc = self._lib.grnet_op_gait_sampen(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, int(m), float(fraction),
+                                            int(derivative), int(scales), out["counts"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_sampen")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

@@ -1892,6 +1892,138 @@ def gait_harmonics(joints3d, events, lengths=None, trans=None, exclude=None, fps
     return out
 
 
+# ----------------------------------------------------------------------------- sample entropy at several scales
+ENTROPY_CHANNELS = REGULARITY_CHANNELS
+ENTROPY_COLUMNS = ("n", "mean", "sd", "r")
+ENTROPY_COUNTS = ("templates", "B", "A")
+ENTROPY_MAX_FRAMES = 32768
+
+
+def _entropy_rule_check(m, fraction, derivative, scales):
+    """The refusals of csrc/gait_entropy.h's ent_rule_error, in its words."""
+    if any(int(v) != v for v in (m, derivative, scales)):
+        raise ValueError("m, derivative and scales must be whole numbers")
+    if not 1 <= m <= 4:
+        raise ValueError("m outside [1, 4]")
+    if not np.isfinite(fraction) or not 0 < fraction <= 10:
+        raise ValueError("fraction must be finite and within (0, 10]")
+    if not 0 <= derivative <= 2:
+        raise ValueError("derivative outside [0, 2]")
+    if not 1 <= scales <= 8:
+        raise ValueError("scales outside [1, 8]")
+
+
+def _entropy_lengths_check(lengths):
+    for q, T in enumerate(lengths):
+        if T > ENTROPY_MAX_FRAMES:
+            raise ValueError(f"sequence {q} has {T} frames, more than {ENTROPY_MAX_FRAMES} (the work is quadratic in them)")
+
+
+def entropy_rows(counts, min_templates=50):
+    """Rule 8 of DESIGN 4.17, the one place where the logarithm is taken: counts (..., scales, 3) integers = (valid templates, B, A), from the device
+    or from gait_sampen -> {'sampen': (..., scales) float64 = ln(B / A), NaN where there are fewer than min_templates valid templates or A or B is 0;
+    'complexity': (...) = their sum over the scales in order from +0.0, NaN where one is}."""
+    c = np.asarray(counts)
+    if c.ndim < 2 or c.shape[-1] != 3 or c.dtype.kind not in "iu":
+        raise ValueError(f"counts must be integers of shape (..., scales, 3), got {c.dtype} {c.shape}")
+    if int(min_templates) != min_templates or min_templates < 1:
+        raise ValueError(f"min_templates {min_templates} must be a whole number of at least 1")
+    flat = c.reshape(-1, 3)
+    sampen = np.full(flat.shape[0], np.nan)
+    for k, (templates, B, A) in enumerate(flat.tolist()):      # Python integers: B / A is their correctly rounded quotient
+        if templates >= min_templates and A > 0 and B > 0:
+            sampen[k] = math.log(B / A)
+    sampen = sampen.reshape(c.shape[:-1])
+    complexity = np.cumsum(np.concatenate([np.zeros(sampen.shape[:-1] + (1,)), sampen], axis=-1), axis=-1)[..., -1]
+    return {"sampen": sampen, "complexity": complexity}
+
+
+def gait_sampen(signals, lengths=None, exclude=None, m=2, fraction=0.2, derivative=2, scales=3, min_templates=50):
+    """Rules 2 to 8 of DESIGN 4.17 on given signals: the host statement of GRNet.op_gait_sampen.  signals (n,4) float64, columns ENTROPY_CHANNELS;
+    exclude (n,) or None: a frame whose entry is not 0 does not count.  Returns {'counts': (n_seq,4,scales,3) int64, columns ENTROPY_COUNTS,
+    'per_sequence': (n_seq,4,4), columns ENTROPY_COLUMNS, and entropy_rows' 'sampen' and 'complexity'}.  Every pair of templates is compared, one
+    offset between the two at a time; every sum in time order from +0.0, every comparison false for NaN."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    _entropy_rule_check(m, fraction, derivative, scales)
+    _entropy_lengths_check(lengths)
+    m, fraction, d, scales = int(m), float(fraction), int(derivative), int(scales)
+    counts = np.zeros((len(lengths), 4, scales, 3), np.int64)
+    per_seq = np.full((len(lengths), 4, 4), np.nan)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                y[~np.isfinite(y)] = np.nan
+                ok = np.isfinite(y)
+                count = int(ok.sum())
+                mu = _regularity_sum(y[ok]) / count if count else np.nan
+                e = y[ok] - mu
+                sd = float(np.sqrt(_regularity_sum(e * e) / (count - 1))) if count >= 2 else np.nan
+                r = fraction * sd
+                per_seq[q, ch] = (count, mu, sd, r)
+                for tau in range(1, scales + 1):
+                    N = T // tau
+                    parts = y[:N * tau].reshape(N, tau)
+                    z = parts[:, 0].copy()
+                    for k in range(1, tau):
+                        z = z + parts[:, k]
+                    z = z / float(tau)
+                    z[~np.isfinite(z)] = np.nan
+                    Nt = N - m
+                    if Nt <= 0:
+                        continue
+                    fin = np.isfinite(z)
+                    tv = fin[:Nt].copy()
+                    for k in range(1, m + 1):
+                        tv &= fin[k:k + Nt]
+                    B = A = 0
+                    if r > 0:
+                        for step in range(1, Nt):
+                            w = Nt - step
+                            hit = tv[:w] & tv[step:]
+                            for k in range(m):
+                                hit &= np.abs(z[k:k + w] - z[k + step:k + step + w]) <= r
+                            B += int(hit.sum())
+                            hit &= np.abs(z[m:m + w] - z[m + step:m + step + w]) <= r
+                            A += int(hit.sum())
+                    counts[q, ch, tau - 1] = (int(tv.sum()), B, A)
+            f0 += T
+    out = {"counts": counts, "per_sequence": per_seq}
+    out.update(entropy_rows(counts, min_templates))
+    return out
+
+
+def gait_entropy(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, m=2, fraction=0.2, derivative=2, scales=3, min_templates=50,
+                 joints=GAIT_JOINTS_KINECTV2):
+    """Sample entropy of four body signals at several scales in numpy float64 and Python integers (Richman and Moorman 2000, Costa et al. 2002, Lamoth et
+    al. 2011 on trunk accelerations; the rules: DESIGN 4.17; the defaults are unvalidated on the model's output): the host statement of
+    GRNet.gait_entropy, same arguments, a dict of numpy arrays.  per_frame (n,4) is gait_regularity's at the same sigma; counts, per_sequence, sampen and
+    complexity: gait_sampen's."""
+    def rule_check():
+        _entropy_rule_check(m, fraction, derivative, scales)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check)
+    out = gait_sampen(per_frame, lengths, exclude, m, fraction, derivative, scales, min_templates)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
