@@ -59,6 +59,15 @@ logarithm is pipeline.entropy_rows'.  <outpath>_entropy.json.  These signals are
 short end of what the measure tolerates (Yentes et al. 2013), differencing twice amplifies joint noise, and the defaults are unvalidated on the model's
 output.  With --gait_turns only straight walking counts.  Reported, never judged.
 
+--gait_stability (opt-in, needs no --gait) reports the local dynamic stability of the same four body signals: the rate at which neighbouring states
+of the delay-embedded signal diverge over the next frames, the short-term largest Lyapunov exponent of Rosenstein, Collins and De Luca (1993) that
+the gait literature reports beside variability, harmonic ratio and entropy (Dingwell and Cusumano 2000, Lamoth et al. 2011, Bruijn et al. 2013).
+The device finds every state's nearest neighbour and multiplies up the distances k frames later as a mantissa with an integer exponent
+(GRNet.gait_stability); the logarithm and the slope are pipeline.stability_rows'.  <outpath>_stability.json.  The papers use a trunk
+sensor and 100 and more strides; these are joint positions of a pose model, 400 frames at 20 fps hold some 15 strides, on a walker with 5 mm of joint
+noise the divergence curve saturates within about 5 frames, so that the slope mostly measures the noise, and the defaults are unvalidated on the
+model's output.  With --gait_turns only straight walking counts.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -643,11 +652,76 @@ class WindowEntropy:
         return path
 
 
+class WindowStability:
+    """--gait_stability: one gait_stability call per database window on rank 0, one sequence per video, on the joints the window's gather left on the
+    device (model.gait_stability; on_host, or a model without the method: pipeline.gait_stability after a download) -- with the window's
+    translations where --trajectory made them, and with --gait_turns' phase as `exclude`, so that only straight walking counts (straight_only): a
+    reference before a turn may then find its neighbour after it, which is intended, both being straight walking.  It needs no events and so no
+    --gait.  Either way the logarithm and the slope are pipeline.stability_rows' on the integers and mantissas.  Per video and channel
+    (pipeline.STABILITY_CHANNELS) a 'curve' with, per k, 'n', 'exponent', 'mantissa' and 'divergence', and 'lambda' in 1/s; null where undefined.
+    The joints are pipeline.GAIT_JOINTS_KINECTV2.  The defaults are unvalidated on the model's output; the results are reported and never judged.
+    The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, derivative=1, dim=5, lag=2, theiler=20, horizon=20, fit_lo=0, fit_hi=None, min_pairs=50):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_stability") else model.gait_stability
+        self.straight_only = bool(straight_only)
+        self.kw = dict(sigma=float(sigma), derivative=int(derivative), dim=int(dim), lag=int(lag), theiler=int(theiler), horizon=int(horizon))
+        fit_hi = min(10, int(horizon)) if fit_hi is None else int(fit_hi)      # as the statements take None
+        if not 0 <= int(fit_lo) < fit_hi <= int(horizon):                      # before any inference runs, in pipeline.stability_rows' words
+            raise ValueError(f"the fit window {fit_lo} .. {fit_hi} must hold 0 <= fit_lo < fit_hi <= horizon = {horizon}")
+        self.rows = dict(fps=float(fps), fit_lo=int(fit_lo), fit_hi=fit_hi, min_pairs=int(min_pairs))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_stability(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw, **self.rows)
+        out.update(self.pipe.stability_rows(out["pairs"], out["mant"], **self.rows))
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form):
+            return "none" if v is None else format(v, form)
+        for key, pairs, mant, divergence, lam in zip(keys, out["pairs"], out["mant"], out["divergence"], out["lambda"]):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.STABILITY_CHANNELS):
+                video[name] = {"curve": [dict({col: int(v) for col, v in zip(self.pipe.STABILITY_PAIRS, pairs[c][k])}, mantissa=float(mant[c][k]), divergence=number(divergence[c][k]))
+                                         for k in range(self.kw["horizon"] + 1)],
+                               "lambda": number(lam[c])}
+            self.videos[key] = video
+            sep, bob = video["sep"], video["bob"]
+            pelvis = f", of the pelvis' height {shown(bob['lambda'], '.3f')}" if trans is not None else ""
+            print(f"Stability: video {key}, {sep['curve'][0]['n']} pairs of neighbours, divergence exponent of the ankles' separation {shown(sep['lambda'], '.3f')} a second "
+                  f"over frames {self.rows['fit_lo']} to {self.rows['fit_hi']}{pelvis}{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait stability of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None):
-    """entropy: {'sigma', 'm', 'fraction', 'derivative', 'scales', 'min_templates', 'all_frames', 'on_host', 'out'} (each optional; needs no gait) -- also
+                 harmonics=None, entropy=None, stability=None):
+    """stability: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'horizon', 'fit_lo', 'fit_hi', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional;
+    needs no gait, whose fps it takes where given, else 20) -- also the local dynamic stability of every video (WindowStability), written to
+    stability['out'] (default: outpath with _stability.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
+    entropy: {'sigma', 'm', 'fraction', 'derivative', 'scales', 'min_templates', 'all_frames', 'on_host', 'out'} (each optional; needs no gait) -- also
     the sample entropy at several scales and the complexity index of every video (WindowEntropy), written to entropy['out'] (default: outpath with
     _entropy.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
     harmonics: {'sigma', 'n_harmonics', 'derivative', 'min_stride', 'max_stride', 'all_frames', 'on_host', 'out'} (each optional; needs gait, whose fps it
@@ -753,6 +827,10 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     rough = WindowEntropy(pipe, model, entropy.get("on_host", False), not entropy.get("all_frames", False),
                           **{k: entropy[k] for k in ("sigma", "m", "fraction", "derivative", "scales", "min_templates") if entropy.get(k) is not None}) \
         if entropy is not None and rank == 0 else None
+    apart = WindowStability(pipe, model, stability.get("on_host", False), not stability.get("all_frames", False),
+                            **({"fps": gait["fps"]} if gait is not None and gait.get("fps") is not None else {}),
+                            **{k: stability[k] for k in ("sigma", "derivative", "dim", "lag", "theiler", "horizon", "fit_lo", "fit_hi", "min_pairs") if stability.get(k) is not None}) \
+        if stability is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -813,6 +891,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             smooth.add_window([v[0] for v in vids], *walk.window, fitted, gait_phase)
         if rough is not None and vids:
             rough.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
+        if apart is not None and vids:
+            apart.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -850,6 +930,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         smooth.write(harmonics.get("out") or osp.splitext(outpath)[0] + "_harmonics.json")
     if rough is not None:
         rough.write(entropy.get("out") or osp.splitext(outpath)[0] + "_entropy.json")
+    if apart is not None:
+        apart.write(stability.get("out") or osp.splitext(outpath)[0] + "_stability.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -962,6 +1044,25 @@ def main(argv=None):
     p.add_argument("--entropy_min_templates", type=int, default=None, help="with --gait_entropy: a scale with fewer valid templates has no sample entropy, at least 1 (default 50)")
     p.add_argument("--entropy_all_frames", action="store_true", help="with --gait_entropy and --gait_turns: count the frames of the turns too")
     p.add_argument("--entropy_on_host", action="store_true", help="with --gait_entropy: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_stability", action="store_true", help="with --vid_folder (no --gait needed): the local dynamic stability of four body signals, the short-term "
+                   "divergence exponent of nearest neighbours in the delay-embedded signal (Rosenstein et al. 1993, Dingwell and Cusumano 2000, Lamoth et al. 2011): "
+                   "<outpath>_stability.json, one line per video; in 1/s through --gait_fps where --gait is given, else at 20 frames a second; quadratic in a video's "
+                   "frames; the papers use a trunk sensor and 100+ strides, where these are joint positions of a pose model and 400 frames at 20 fps hold some 15 strides; "
+                   "on a walker with 5 mm of joint noise the divergence curve saturates within about 5 frames, so on such data the slope mostly measures the noise; the "
+                   "defaults are unvalidated on the model's output; reported, never judged")
+    p.add_argument("--stability_out", type=str, default="", help="with --gait_stability: the JSON file (default: --outpath with _stability.json)")
+    p.add_argument("--stability_sigma", type=float, default=None, help="with --gait_stability: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--stability_derivative", type=int, default=None, help="with --gait_stability: 0 the signal, 1 its velocity, 2 its acceleration (default 1, this project's choice)")
+    p.add_argument("--stability_dim", type=int, default=None, help="with --gait_stability: the embedding dimension, 2 to 8 (default 5)")
+    p.add_argument("--stability_lag", type=int, default=None, help="with --gait_stability: the embedding delay in frames, 1 to 16 (default 2)")
+    p.add_argument("--stability_theiler", type=int, default=None, help="with --gait_stability: a neighbour lies more than this many frames away, 0 to 4096 (default 20, about a stride)")
+    p.add_argument("--stability_horizon", type=int, default=None, help="with --gait_stability: the frames a pair of neighbours is followed, 1 to 63 (default 20, one second)")
+    p.add_argument("--stability_fit_lo", type=int, default=None, help="with --gait_stability: the first frame of the slope's window, at least 0 (default 0)")
+    p.add_argument("--stability_fit_hi", type=int, default=None, help="with --gait_stability: the last frame of the slope's window, above --stability_fit_lo and at most "
+                   "--stability_horizon (default 10, or the horizon where that is shorter)")
+    p.add_argument("--stability_min_pairs", type=int, default=None, help="with --gait_stability: a frame of the curve with fewer pairs has no divergence, at least 1 (default 50)")
+    p.add_argument("--stability_all_frames", action="store_true", help="with --gait_stability and --gait_turns: count the frames of the turns too")
+    p.add_argument("--stability_on_host", action="store_true", help="with --gait_stability: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -1122,6 +1223,34 @@ def main(argv=None):
         sys.exit("batch_generation.py: --entropy_scales must be within 1 to 8")
     if a.entropy_min_templates is not None and a.entropy_min_templates < 1:
         sys.exit("batch_generation.py: --entropy_min_templates must be at least 1")
+    for flag, given in (("--stability_out", bool(a.stability_out)), ("--stability_sigma", a.stability_sigma is not None), ("--stability_derivative", a.stability_derivative is not None),
+                        ("--stability_dim", a.stability_dim is not None), ("--stability_lag", a.stability_lag is not None), ("--stability_theiler", a.stability_theiler is not None),
+                        ("--stability_horizon", a.stability_horizon is not None), ("--stability_fit_lo", a.stability_fit_lo is not None),
+                        ("--stability_fit_hi", a.stability_fit_hi is not None), ("--stability_min_pairs", a.stability_min_pairs is not None),
+                        ("--stability_all_frames", a.stability_all_frames), ("--stability_on_host", a.stability_on_host)):
+        if given and not a.gait_stability:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_stability, which was not given")
+    if a.gait_stability and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_stability needs --vid_folder (the frames whose joints it reads)")
+    if a.stability_sigma is not None and not (np.isfinite(a.stability_sigma) and 0 <= a.stability_sigma <= 16):
+        sys.exit("batch_generation.py: --stability_sigma must be within 0 to 16")
+    if a.stability_derivative is not None and not 0 <= a.stability_derivative <= 2:
+        sys.exit("batch_generation.py: --stability_derivative must be 0, 1 or 2")
+    if a.stability_dim is not None and not 2 <= a.stability_dim <= 8:
+        sys.exit("batch_generation.py: --stability_dim must be within 2 to 8")
+    if a.stability_lag is not None and not 1 <= a.stability_lag <= 16:
+        sys.exit("batch_generation.py: --stability_lag must be within 1 to 16")
+    if a.stability_theiler is not None and not 0 <= a.stability_theiler <= 4096:
+        sys.exit("batch_generation.py: --stability_theiler must be within 0 to 4096")
+    if a.stability_horizon is not None and not 1 <= a.stability_horizon <= 63:
+        sys.exit("batch_generation.py: --stability_horizon must be within 1 to 63")
+    if a.stability_fit_lo is not None and a.stability_fit_lo < 0:
+        sys.exit("batch_generation.py: --stability_fit_lo must be at least 0")
+    if a.gait_stability and not (0 if a.stability_fit_lo is None else a.stability_fit_lo) < (min(10, 20 if a.stability_horizon is None else a.stability_horizon) if a.stability_fit_hi is None else a.stability_fit_hi) <= \
+            (20 if a.stability_horizon is None else a.stability_horizon):
+        sys.exit("batch_generation.py: --stability_fit_hi must be above --stability_fit_lo and at most --stability_horizon")
+    if a.stability_min_pairs is not None and a.stability_min_pairs < 1:
+        sys.exit("batch_generation.py: --stability_min_pairs must be at least 1")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -1154,12 +1283,16 @@ def main(argv=None):
     entropy = {"sigma": a.entropy_sigma, "m": a.entropy_m, "fraction": a.entropy_r, "derivative": a.entropy_derivative, "scales": a.entropy_scales,
                "min_templates": a.entropy_min_templates, "all_frames": a.entropy_all_frames, "on_host": a.entropy_on_host,
                "out": a.entropy_out or None} if a.gait_entropy else None
+    stability = {"sigma": a.stability_sigma, "derivative": a.stability_derivative, "dim": a.stability_dim, "lag": a.stability_lag, "theiler": a.stability_theiler,
+                 "horizon": a.stability_horizon, "fit_lo": a.stability_fit_lo, "fit_hi": a.stability_fit_hi, "min_pairs": a.stability_min_pairs,
+                 "all_frames": a.stability_all_frames, "on_host": a.stability_on_host, "out": a.stability_out or None} if a.gait_stability else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
                  **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
                  **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
-                 **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}))
+                 **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
+                 **({"stability": stability} if stability is not None else {}))
 
 
 if __name__ == "__main__":

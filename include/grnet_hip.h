@@ -856,6 +856,38 @@ int grnet_gait_entropy(grnet_t* h, const float* joints3d_dev, int J, const int32
 int grnet_op_gait_sampen(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, int m,
                          double fraction, int derivative, int scales, int64_t* counts_dev, double* per_seq_dev, void* stream);
 
+/* Local dynamic stability of the same four body signals: the short-term largest Lyapunov exponent of Rosenstein, Collins and De Luca (1993), which the
+ * gait literature reports as local dynamic stability (Dingwell and Cusumano 2000; Lamoth et al. 2011; Bruijn et al. 2013 -- on a trunk sensor over
+ * 100 and more strides; these signals are joint positions of a pose model, 400 frames at 20 fps hold some 15 strides, on noisy joints the slope
+ * mostly measures the noise and the defaults are unvalidated on its output): every state's NEAREST NEIGHBOUR and, per k, the product of the squared
+ * distances k frames later as a mantissa with an integer exponent (which is the specification).  joints3d_dev, frame_offsets_host,
+ * joints_host, trans_dev and exclude_dev as grnet_gait_regularity takes them.  Float64 with one rounding per operation; every test is a comparison,
+ * false for NaN:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma.  A frame counts for a channel where its signal is finite and exclude is 0.
+ *   y        grnet_gait_entropy's: the signal differenced `derivative` times (1, velocities, is this project's choice), NaN where invalid.
+ *   points   span = (dim - 1) lag, M = T - span points, point i = y(i), y(i + lag), .., y(i + span), valid iff all are.  E = M - horizon: only the
+ *            points i < E are references or neighbours, so that both can be followed for `horizon` frames.
+ *   D2(a,b)  the sum over k = 0 .. dim - 1 of (y(a + k lag) - y(b + k lag)) squared, added in that order from the first term.  No square root.
+ *   nn(i)    the eligible j with |i - j| > theiler and D2(i, j) > 0 of the smallest D2, among equal ones the smallest j; else -1.
+ *   curve    for k = 0 .. horizon, over the i with nn(i) >= 0 in increasing i: d2 = D2(i + k, nn(i) + k) counts where > 0 and finite; (f, e) =
+ *            frexp(d2); P <- P f (one rounding); (P, e') = frexp(P); S <- S + e + e'; n <- n + 1; from P = 1, S = 0, n = 0.
+ * per_frame_dev (sum T, 4) float64.  nn_dev (sum T, 4) int32, sequence-relative.  pairs_dev (n_seq, 4, horizon + 1, 2) int64: [n, S].  mant_dev
+ * (n_seq, 4, horizon + 1) float64: P.  THE LOGARITHM IS THE CALLER'S: the mean logarithm of the distance at k is (ln P + S ln 2) / (2 n) (as the
+ * Python layer holds it, where n >= 50), and the exponent the least-squares slope of that over k = 0 .. 10 times the frames a second.
+ * A workgroup per (sequence, channel, block of 256 reference points), the blocks sized by the call's longest sequence, a lane per reference point,
+ * the candidates in LDS tiles; then a workgroup per (sequence, channel), a lane per k; no atomics, nothing added across lanes: a sequence's outputs
+ * have the same bits alone or among others.  The work is QUADRATIC in a sequence's frames.  Needs no weights.  At most four launches (three with
+ * sigma = 0) behind one small copy from pinned memory; no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a sequence of more than 32768 frames, sigma outside [0, 16], derivative
+ * outside [0, 2], dim outside [2, 8], lag outside [1, 16], theiler outside [0, 4096], horizon outside [1, 63].  Nothing is refused on the data.
+ * grnet_op_gait_divergence: y, the neighbours and the curve alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_stability(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                         const double* trans_dev, const int32_t* exclude_dev, double sigma, int derivative, int dim, int lag, int theiler, int horizon,
+                         double* per_frame_dev, int32_t* nn_dev, int64_t* pairs_dev, double* mant_dev, void* stream);
+int grnet_op_gait_divergence(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq,
+                             int derivative, int dim, int lag, int theiler, int horizon, int32_t* nn_dev, int64_t* pairs_dev, double* mant_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

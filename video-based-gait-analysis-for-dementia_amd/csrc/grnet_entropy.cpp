@@ -20,17 +20,6 @@ struct EntScratch {
     }
 };
 
-// the entry of both calls behind their own scalars: seq_call with the refusal of a sequence too long between its two halves
-template <class Extra>
-int ent_seq_call(grnet* h, const std::string& name, const int32_t* off, int n_seq, long long unit, double sigma, hipStream_t s, SeqCall* c, Extra extra) {
-    if (int rc = seq_call_check(h, name, off, n_seq, unit)) return rc;
-    const int q = ent_long_sequence(off, n_seq);
-    if (q >= 0)
-        return h->fail(GRNET_EINVAL, name + "sequence " + std::to_string(q) + " has " + std::to_string(off[q + 1] - off[q]) + " frames, more than " +
-                                         std::to_string(kEntMaxFrames) + " (the work is quadratic in them)");
-    return seq_call_upload(h, name, off, n_seq, sigma, extra(off[n_seq]), s, c);
-}
-
 hipError_t sequences(const SeqCall& c, char* at, const EntScratch& sc, int n_seq, int frames, const EntRule& rule, const double* rows, const int32_t* exclude,
                      int64_t* counts, double* per_seq, hipStream_t s) {
     double* z_long = sc.b_z ? reinterpret_cast<double*>(at + sc.b_y) : nullptr;

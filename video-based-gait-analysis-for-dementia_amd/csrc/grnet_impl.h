@@ -17,6 +17,7 @@
 //   grnet_regularity.cpp gait regularity from the autocorrelation: grnet_gait_regularity and its autocorrelation hook
 //   grnet_harmonics.cpp harmonic ratios per stride: grnet_gait_harmonics and its stride hook
 //   grnet_entropy.cpp  sample entropy at several scales: grnet_gait_entropy and its counting hook
+//   grnet_stability.cpp local dynamic stability: grnet_gait_stability and its divergence hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -38,6 +39,7 @@
 
 #include "kernels.h"
 #include "seq_args.h"
+#include "gait_entropy.h"
 
 namespace grnet_detail {
 using namespace grk;
@@ -451,5 +453,16 @@ inline size_t seq_no_extra(int) { return 0; }      // the `extra` of a call that
 template <class Extra>
 int seq_call(grnet* h, const std::string& name, const int32_t* off, int n_seq, long long unit, double sigma, hipStream_t s, SeqCall* c, Extra extra) {
     if (int rc = seq_call_check(h, name, off, n_seq, unit)) return rc;
+    return seq_call_upload(h, name, off, n_seq, sigma, extra(off[n_seq]), s, c);
+}
+// The same for a call whose work is quadratic in a sequence's frames (sample entropy, local dynamic stability, and their hooks): the refusal of a
+// sequence of more than kEntMaxFrames frames (gait_entropy.h's ent_long_sequence) stands between the two halves, in ONE sentence for all of them.
+template <class Extra>
+int ent_seq_call(grnet* h, const std::string& name, const int32_t* off, int n_seq, long long unit, double sigma, hipStream_t s, SeqCall* c, Extra extra) {
+    if (int rc = seq_call_check(h, name, off, n_seq, unit)) return rc;
+    const int q = grk::ent_long_sequence(off, n_seq);
+    if (q >= 0)
+        return h->fail(GRNET_EINVAL, name + "sequence " + std::to_string(q) + " has " + std::to_string(off[q + 1] - off[q]) + " frames, more than " +
+                                         std::to_string(grk::kEntMaxFrames) + " (the work is quadratic in them)");
     return seq_call_upload(h, name, off, n_seq, sigma, extra(off[n_seq]), s, c);
 }

@@ -477,6 +477,15 @@ struct EntRule;                            // gait_entropy.h: m, fraction, deriv
 hipError_t launch_ent_sequences(const int* off, int n_seq, const EntRule& rule, const double* rows, const int* exclude, int frames, double* y, double* z_long,
                                 long long* counts, double* per_seq, hipStream_t s);
 
+// Local dynamic stability of the same four signals (csrc/gait_stability_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_stability.h).  The frame kernel is launch_reg_frames ----
+struct StabRule;                           // gait_stability.h: derivative, dim, lag, theiler, horizon
+// two launches on rows (frames,4) and exclude (frames) or null: a workgroup per (sequence, channel, block of kGaitThreads reference points, the blocks
+// sized by `longest`, the call's longest sequence) finds nn (frames,4) int32; a workgroup per (sequence, channel) walks them into pairs
+// (n_seq,4,horizon+1,2) int64 and mant (n_seq,4,horizon+1).  y_long: (4,frames) float64 where a sequence has more than kRegLdsFrames frames, else null
+hipError_t launch_stab_sequences(const int* off, int n_seq, int longest, const StabRule& rule, const double* rows, const int* exclude, int frames, int* nn,
+                                 double* y_long, long long* pairs, double* mant, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

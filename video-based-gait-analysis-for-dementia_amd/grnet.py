@@ -1461,6 +1461,56 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_sampen")
         return out
 
+    # ------------------------------------------------------------------ local dynamic stability
+    def _stability_call(self, n, lengths, exclude, derivative, dim, lag, theiler, horizon, what):
+        """(exclude on the device or None, offsets, the nn, pairs and mant tensors) of gait_stability and its hook."""
+        self._whole_frames(derivative=derivative, dim=dim, lag=lag, theiler=theiler, horizon=horizon)
+        if not 1 <= int(horizon) <= 63:                            # the size of pairs and mant is made of it here
+            raise ValueError(f"horizon {horizon} outside [1, 63]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"nn": torch.empty(n, 4, dtype=torch.int32, device=self.device),
+               "pairs": torch.empty(n_seq, 4, int(horizon) + 1, 2, dtype=torch.int64, device=self.device),
+               "mant": torch.empty(n_seq, 4, int(horizon) + 1, dtype=torch.float64, device=self.device)}
+        return ex, off, out
+
+    def gait_stability(self, joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, derivative=1, dim=5, lag=2, theiler=20, horizon=20,
+                       joints=_lib.GAIT_JOINTS_KINECTV2):
+        """The integers behind the local dynamic stability of every sequence, on the device (grnet_gait_stability; the rules and channels: DESIGN
+        4.18, pipeline.STABILITY_CHANNELS, STABILITY_PAIRS).  joints3d, lengths, trans, exclude and joints as gait_regularity takes them.  Its four
+        signals, smoothed by sigma frames (0: none, the default; <= 16), are differenced `derivative` times (0 .. 2; 1, velocities, is this
+        project's choice) and embedded with `dim` (2 .. 8) delays of `lag` (1 .. 16) frames; every point that can be followed for `horizon`
+        (1 .. 63) frames gets its nearest neighbour among those more than `theiler` (0 .. 4096) frames away, and for k = 0 .. horizon the squared
+        distances of the pairs k frames later are multiplied up as a mantissa P with an exponent S.  A sequence has at most 32 768 frames: the
+        work is quadratic in them.  Returns a dict of device tensors: per_frame (n,4) float64, gait_regularity's bits; nn (n,4) int32,
+        sequence-relative, -1 where there is none; pairs (n_seq,4,horizon+1,2) int64 = (n, S); mant (n_seq,4,horizon+1) float64 = P.  The
+        logarithm and the slope are pipeline.stability_rows(pairs, mant), on the host.  The papers use a trunk sensor and 100+ strides; the
+        defaults are unvalidated on the model's output, and on noisy joints the slope mostly measures the noise.  Nothing is refused on the data.
+        Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ex, off, out = self._stability_call(n, lengths, exclude, derivative, dim, lag, theiler, horizon, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_stability(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                            None if ex is None else ex.data_ptr(), float(sigma), int(derivative), int(dim), int(lag), int(theiler), int(horizon),
+                                            out["per_frame"].data_ptr(), out["nn"].data_ptr(), out["pairs"].data_ptr(), out["mant"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_stability")
+        return out
+
+    def op_gait_divergence(self, signals, lengths=None, exclude=None, derivative=1, dim=5, lag=2, theiler=20, horizon=20):
+        """Rules 1 (from the differencing on) to 6 of gait_stability alone (grnet_op_gait_divergence): signals (n,4) float64 and exclude (n,) or None,
+        one sequence or `lengths` of them lying back to back -> {nn, pairs, mant} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, out = self._stability_call(x.shape[0], lengths, exclude, derivative, dim, lag, theiler, horizon, "signals")
+        rc = self._lib.grnet_op_gait_divergence(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, int(derivative), int(dim),
+                                                int(lag), int(theiler), int(horizon), out["nn"].data_ptr(), out["pairs"].data_ptr(), out["mant"].data_ptr(),
+                                                self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_divergence")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

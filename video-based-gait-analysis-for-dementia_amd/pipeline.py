@@ -2024,6 +2024,162 @@ def gait_entropy(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, m=
     return out
 
 
+# ----------------------------------------------------------------------------- local dynamic stability
+STABILITY_CHANNELS = REGULARITY_CHANNELS
+STABILITY_PAIRS = ("n", "exponent")
+STABILITY_MAX_FRAMES = ENTROPY_MAX_FRAMES
+
+
+def _stability_rule_check(derivative, dim, lag, theiler, horizon):
+    """The refusals of csrc/gait_stability.h's stab_rule_error, in its words."""
+    if any(int(v) != v for v in (derivative, dim, lag, theiler, horizon)):
+        raise ValueError("derivative, dim, lag, theiler and horizon must be whole numbers")
+    if not 0 <= derivative <= 2:
+        raise ValueError("derivative outside [0, 2]")
+    if not 2 <= dim <= 8:
+        raise ValueError("dim outside [2, 8]")
+    if not 1 <= lag <= 16:
+        raise ValueError("lag outside [1, 16]")
+    if not 0 <= theiler <= 4096:
+        raise ValueError("theiler outside [0, 4096]")
+    if not 1 <= horizon <= 63:
+        raise ValueError("horizon outside [1, 63]")
+
+
+def stability_rows(pairs, mant, fps=20.0, fit_lo=0, fit_hi=10, min_pairs=50):
+    """Rule 7 of DESIGN 4.18, the one place where the logarithm is taken: pairs (..., K+1, 2) integers = (n, S) and mant (..., K+1) float64 = P, from
+    the device or from gait_divergence -> {'divergence': (..., K+1) float64 = (ln P + S ln 2) / (2 n), the mean logarithm of the distance (the 2: the
+    distances are squared), NaN where n < min_pairs; 'lambda': (...) = the least-squares slope of divergence over k = fit_lo .. fit_hi times fps, in
+    1/s, every sum in k order from +0.0, NaN if a point of the window is}."""
+    c, P = np.asarray(pairs), np.asarray(mant, np.float64)
+    if c.ndim < 2 or c.shape[-1] != 2 or c.dtype.kind not in "iu" or P.shape != c.shape[:-1]:
+        raise ValueError(f"pairs must be integers of shape (..., K+1, 2) and mant (..., K+1), got {c.dtype} {c.shape} and {P.shape}")
+    K = c.shape[-2] - 1
+    if int(min_pairs) != min_pairs or min_pairs < 1:
+        raise ValueError(f"min_pairs {min_pairs} must be a whole number of at least 1")
+    if int(fit_lo) != fit_lo or int(fit_hi) != fit_hi or fit_lo < 0 or fit_hi <= fit_lo or fit_hi > K:
+        raise ValueError(f"the fit window {fit_lo} .. {fit_hi} must hold 0 <= fit_lo < fit_hi <= horizon = {K}")
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    fit_lo, fit_hi, fps = int(fit_lo), int(fit_hi), float(fps)
+    flat = np.full(P.size, np.nan)
+    for at, ((n, S), p) in enumerate(zip(c.reshape(-1, 2).tolist(), P.reshape(-1).tolist())):
+        if n >= min_pairs:
+            flat[at] = (math.log(p) + S * math.log(2.0)) / (2 * n)
+    div = flat.reshape(P.shape)
+    rows = div.reshape(-1, K + 1)
+    lam = np.full(rows.shape[0], np.nan)
+    count = float(fit_hi - fit_lo + 1)
+    for at, row in enumerate(rows.tolist()):
+        sk = sv = 0.0
+        for k in range(fit_lo, fit_hi + 1):
+            sk = sk + float(k)
+            sv = sv + row[k]
+        mk, mv = sk / count, sv / count
+        num = den = 0.0
+        for k in range(fit_lo, fit_hi + 1):
+            num = num + (float(k) - mk) * (row[k] - mv)
+            den = den + (float(k) - mk) * (float(k) - mk)
+        lam[at] = (num / den) * fps
+    lam[~np.isfinite(lam)] = np.nan
+    return {"divergence": div, "lambda": lam.reshape(P.shape[:-1])}
+
+
+def _stability_dist2(y, a, b, dim, lag):
+    """D2 of the points a (n,1) and b (1,m) or of two index arrays of one shape: rule 4's order, the first term, then one addition a term."""
+    t = y[a] - y[b]
+    d2 = t * t
+    for c in range(1, dim):
+        t = y[a + c * lag] - y[b + c * lag]
+        d2 = d2 + t * t
+    return d2
+
+
+def gait_divergence(signals, lengths=None, exclude=None, derivative=1, dim=5, lag=2, theiler=20, horizon=20, fps=20.0, fit_lo=0, fit_hi=None, min_pairs=50):
+    """Rules 1 (from the differencing on) to 7 of DESIGN 4.18 on given signals: the host statement of GRNet.op_gait_divergence.  signals (n,4) float64,
+    columns STABILITY_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count.  Returns {'nn': (n,4) int32, the nearest neighbour
+    of every eligible valid point, sequence-relative, else -1; 'pairs': (n_seq,4,horizon+1,2) int64, columns STABILITY_PAIRS; 'mant':
+    (n_seq,4,horizon+1) float64; and stability_rows' 'divergence' and 'lambda'; fit_hi None: 10, or the horizon where that is shorter}.  Every pair of points is compared, a block of references at a time."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    _stability_rule_check(derivative, dim, lag, theiler, horizon)
+    _entropy_lengths_check(lengths)
+    d, dim, lag, w, K = int(derivative), int(dim), int(lag), int(theiler), int(horizon)
+    nn = np.full((n, 4), -1, np.int32)
+    pairs = np.zeros((len(lengths), 4, K + 1, 2), np.int64)
+    mant = np.ones((len(lengths), 4, K + 1))
+    span = (dim - 1) * lag
+    ks = np.arange(K + 1)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            E = T - span - K
+            for ch in range(4):
+                if E <= 0:
+                    break
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                y[~np.isfinite(y)] = np.nan
+                cand = np.arange(E)
+                found = np.full(E, -1, np.int64)
+                for i0 in range(0, E, 512):
+                    ref = np.arange(i0, min(i0 + 512, E))
+                    d2 = _stability_dist2(y, ref[:, None], cand[None, :], dim, lag)
+                    ok = (np.abs(ref[:, None] - cand[None, :]) > w) & (d2 > 0)
+                    best = np.argmin(np.where(ok, d2, np.inf), axis=1)                  # the first of equal minima: the smallest j
+                    late = ~ok[np.arange(len(ref)), best]                               # only infinite candidates, or none
+                    best[late] = np.argmax(ok[late], axis=1)
+                    found[ref] = np.where(ok.any(axis=1), best, -1)
+                nn[f0:f0 + E, ch] = found
+                refs = np.flatnonzero(found >= 0)
+                if not len(refs):
+                    continue
+                d2 = _stability_dist2(y, refs[:, None] + ks[None, :], found[refs][:, None] + ks[None, :], dim, lag)
+                counts = (d2 > 0) & np.isfinite(d2)
+                f, e = np.frexp(np.where(counts, d2, 0.5))
+                P, S = np.ones(K + 1), np.zeros(K + 1, np.int64)
+                for r in range(len(refs)):                     # rule 6: the references in increasing i, one rounding a product
+                    new, e2 = np.frexp(P * f[r])
+                    P = np.where(counts[r], new, P)
+                    S = S + np.where(counts[r], e[r].astype(np.int64) + e2, 0)
+                pairs[q, ch, :, 0] = counts.sum(axis=0)
+                pairs[q, ch, :, 1] = S
+                mant[q, ch] = P
+            f0 += T
+    out = {"nn": nn, "pairs": pairs, "mant": mant}
+    out.update(stability_rows(pairs, mant, fps, fit_lo, min(10, K) if fit_hi is None else fit_hi, min_pairs))
+    return out
+
+
+def gait_stability(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, derivative=1, dim=5, lag=2, theiler=20, horizon=20, fps=20.0, fit_lo=0,
+                   fit_hi=None, min_pairs=50, joints=GAIT_JOINTS_KINECTV2):
+    """Local dynamic stability of four body signals in numpy float64 and Python integers (the short-term largest Lyapunov exponent of Rosenstein,
+    Collins and De Luca 1993; Dingwell and Cusumano 2000, Bruijn et al. 2013 and Lamoth et al. 2011 on trunk sensors over 100+ strides; the rules:
+    DESIGN 4.18; the defaults are unvalidated on the model's output, and on noisy joints the slope mostly measures the noise): the host statement of
+    GRNet.gait_stability, same arguments, a dict of numpy arrays.  per_frame (n,4) is gait_regularity's at the same sigma; nn, pairs, mant, divergence
+    and lambda: gait_divergence's."""
+    def rule_check():
+        _stability_rule_check(derivative, dim, lag, theiler, horizon)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check)
+    out = gait_divergence(per_frame, lengths, exclude, derivative, dim, lag, theiler, horizon, fps, fit_lo, fit_hi, min_pairs)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
