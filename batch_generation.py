@@ -68,6 +68,15 @@ sensor and 100 and more strides; these are joint positions of a pose model, 400 
 noise the divergence curve saturates within about 5 frames, so that the slope mostly measures the noise, and the defaults are unvalidated on the
 model's output.  With --gait_turns only straight walking counts.  Reported, never judged.
 
+--gait_spectrum (opt-in, needs no --gait) reports the frequency domain of the same four body signals: their Welch power spectral density (Welch
+1967) and, in the band 0.5 to 3 Hz, the dominant frequency, the height and the width of that peak, how the power is spread and a third cadence
+beside the events' and the autocorrelation's, as the gait accelerometry studies read them off a trunk sensor (Weiss et al. 2011, Sejdic et al.
+2014).  The device averages the windowed, zero-padded transforms of the segments (GRNet.gait_spectrum); the logarithm of the
+spectral entropy is pipeline.spectrum_rows'.  <outpath>_spectrum.json.  These signals are joint positions of a pose model; at 20 fps and 64-frame
+segments the Hann window alone makes the peak about 0.45 Hz wide at half height, so the width has a floor set by the segment and not by the
+walker, and the defaults are unvalidated on the model's output.  With --gait_turns a turn splits the walk into straight runs.  Reported, never
+judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -714,11 +723,77 @@ class WindowStability:
         return path
 
 
+class WindowSpectrum:
+    """--gait_spectrum: one gait_spectrum call per database window on rank 0, one sequence per video, on the joints the window's gather left on the
+    device (model.gait_spectrum; on_host, or a model without the method: pipeline.gait_spectrum after a download) -- with the window's translations
+    where --trajectory made them, and with --gait_turns' phase as `exclude` (straight_only): a turn then splits the walk into straight runs, and the
+    segments of all of them are averaged.  It needs no events and so no --gait.  Either way the logarithm is pipeline.spectrum_rows' on the psd.
+    Per video and channel (pipeline.SPECTRUM_CHANNELS) the columns of pipeline.SPECTRUM_COLUMNS, 'spectral_entropy', and the 'psd' list; per video
+    the frequency axis 'freqs' in Hz; null where undefined.  The joints are pipeline.GAIT_JOINTS_KINECTV2.  The peak's width has a floor set by the
+    segment length, not by the walker; the defaults are unvalidated on the model's output; the results are reported and never judged.  The database
+    gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, derivative=2, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0, min_segments=2):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_spectrum") else model.gait_spectrum
+        self.straight_only = bool(straight_only)
+        self.kw = dict(fps=float(fps), sigma=float(sigma), derivative=int(derivative), segment=int(segment), hop=int(segment) // 2 if hop is None else int(hop), nfft=int(nfft),
+                       f_lo=float(f_lo), f_hi=float(f_hi), min_segments=int(min_segments))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None, whole=None, steady=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None;
+        whole: WindowGait's videos and steady: WindowRegularity's, for their cadences in the line, or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_spectrum(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw)
+        out.update(self.pipe.spectrum_rows(out["psd"], out["per_sequence"], self.kw["fps"], self.kw["f_lo"], self.kw["f_hi"]))
+        freqs = [k * self.kw["fps"] / self.kw["nfft"] for k in range(self.kw["nfft"] // 2 + 1)]
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        for key, rows, psd, entropy in zip(keys, out["per_sequence"], out["psd"], out["spectral_entropy"]):
+            video = {"straight_only": straight, "freqs": freqs}
+            for c, name in enumerate(self.pipe.SPECTRUM_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.SPECTRUM_COLUMNS, rows[c])}
+                video[name]["spectral_entropy"] = number(entropy[c])
+                video[name]["psd"] = [number(v) for v in psd[c]]
+            self.videos[key] = video
+            sep = video["sep"]
+            events = "" if whole is None or key not in whole else f" (events: {shown(whole[key]['cadence'], '.1f', ' steps/min')})"
+            lags = "" if steady is None or key not in steady else f" (autocorrelation: {shown(steady[key]['sep']['cadence'], '.1f', ' steps/min')})"
+            print(f"Spectrum: video {key}, {int(sep['used'])} segments, cadence {shown(sep['cadence'], '.1f', ' steps/min')} from the spectral peak{events}{lags}, peak width "
+                  f"{shown(sep['peak_width_hz'], '.3f', ' Hz')}, spectral entropy {shown(sep['spectral_entropy'], '.3f')} of the ankles' separation"
+                  f"{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait spectrum of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None):
-    """stability: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'horizon', 'fit_lo', 'fit_hi', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional;
+                 harmonics=None, entropy=None, stability=None, spectrum=None):
+    """spectrum: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
+    needs no gait, whose fps it takes where its own is not given, else 20) -- also the Welch spectrum of every video (WindowSpectrum), written to
+    spectrum['out'] (default: outpath with _spectrum.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
+    stability: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'horizon', 'fit_lo', 'fit_hi', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional;
     needs no gait, whose fps it takes where given, else 20) -- also the local dynamic stability of every video (WindowStability), written to
     stability['out'] (default: outpath with _stability.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
     entropy: {'sigma', 'm', 'fraction', 'derivative', 'scales', 'min_templates', 'all_frames', 'on_host', 'out'} (each optional; needs no gait) -- also
@@ -831,6 +906,10 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                             **({"fps": gait["fps"]} if gait is not None and gait.get("fps") is not None else {}),
                             **{k: stability[k] for k in ("sigma", "derivative", "dim", "lag", "theiler", "horizon", "fit_lo", "fit_hi", "min_pairs") if stability.get(k) is not None}) \
         if stability is not None and rank == 0 else None
+    bands = WindowSpectrum(pipe, model, spectrum.get("on_host", False), not spectrum.get("all_frames", False),
+                           **({"fps": gait["fps"]} if spectrum.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
+                           **{k: spectrum[k] for k in ("fps", "sigma", "derivative", "segment", "hop", "nfft", "f_lo", "f_hi", "min_segments") if spectrum.get(k) is not None}) \
+        if spectrum is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -893,6 +972,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             rough.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if apart is not None and vids:
             apart.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
+        if bands is not None and vids:
+            bands.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None, steady.videos if steady is not None else None)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -932,6 +1013,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         rough.write(entropy.get("out") or osp.splitext(outpath)[0] + "_entropy.json")
     if apart is not None:
         apart.write(stability.get("out") or osp.splitext(outpath)[0] + "_stability.json")
+    if bands is not None:
+        bands.write(spectrum.get("out") or osp.splitext(outpath)[0] + "_spectrum.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -1063,6 +1146,22 @@ def main(argv=None):
     p.add_argument("--stability_min_pairs", type=int, default=None, help="with --gait_stability: a frame of the curve with fewer pairs has no divergence, at least 1 (default 50)")
     p.add_argument("--stability_all_frames", action="store_true", help="with --gait_stability and --gait_turns: count the frames of the turns too")
     p.add_argument("--stability_on_host", action="store_true", help="with --gait_stability: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_spectrum", action="store_true", help="with --vid_folder (no --gait needed): the Welch power spectral density of four body signals and, in the band "
+                   "--spectrum_f_lo to --spectrum_f_hi, its dominant frequency, the peak's height and width, the spread of the power and a cadence (Welch 1967, Weiss et al. "
+                   "2011): <outpath>_spectrum.json, one line per video; in Hz through --gait_fps where given, else at 20 frames a second; with --gait_turns only straight "
+                   "walking counts; the peak's width has a floor set by --spectrum_segment, and the defaults are unvalidated on the model's output")
+    p.add_argument("--spectrum_out", type=str, default="", help="with --gait_spectrum: the JSON file (default: --outpath with _spectrum.json)")
+    p.add_argument("--spectrum_sigma", type=float, default=None, help="with --gait_spectrum: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--spectrum_derivative", type=int, default=None, help="with --gait_spectrum: 0 the signal, 1 its velocity, 2 its acceleration (default 2)")
+    p.add_argument("--spectrum_segment", type=int, default=None, help="with --gait_spectrum: the frames of a segment, even, 8 to 256 (default 64)")
+    p.add_argument("--spectrum_hop", type=int, default=None, help="with --gait_spectrum: the frames between two segments, an eighth of a segment to a whole one (default half)")
+    p.add_argument("--spectrum_nfft", type=int, default=None, help="with --gait_spectrum: the points of the zero-padded transform, even, a segment to 1024 (default 256)")
+    p.add_argument("--spectrum_f_lo", type=float, default=None, help="with --gait_spectrum: the band's lower edge in Hz, above 0 (default 0.5)")
+    p.add_argument("--spectrum_f_hi", type=float, default=None, help="with --gait_spectrum: the band's upper edge in Hz, above --spectrum_f_lo and at most half the frames a second "
+                   "(default 3)")
+    p.add_argument("--spectrum_min_segments", type=int, default=None, help="with --gait_spectrum: a video with fewer segments has no spectrum, at least 1 (default 2)")
+    p.add_argument("--spectrum_all_frames", action="store_true", help="with --gait_spectrum and --gait_turns: count the frames of the turns too")
+    p.add_argument("--spectrum_on_host", action="store_true", help="with --gait_spectrum: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -1099,7 +1198,7 @@ def main(argv=None):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     for flag, given in (("--gait_out", bool(a.gait_out)), ("--gait_fps", a.gait_fps is not None), ("--gait_sigma", a.gait_sigma is not None),
                         ("--gait_window", a.gait_window is not None), ("--gait_min_excursion", a.gait_min_excursion is not None), ("--gait_on_host", a.gait_on_host)):
-        if given and not a.gait and not (flag == "--gait_fps" and a.gait_regularity):
+        if given and not a.gait and not (flag == "--gait_fps" and (a.gait_regularity or a.gait_spectrum)):
             sys.exit(f"batch_generation.py: {flag} belongs to --gait, which was not given")
     if a.gait and not a.vid_folder:
         sys.exit("batch_generation.py: --gait needs --vid_folder (the frames whose joints it reads)")
@@ -1251,6 +1350,33 @@ def main(argv=None):
         sys.exit("batch_generation.py: --stability_fit_hi must be above --stability_fit_lo and at most --stability_horizon")
     if a.stability_min_pairs is not None and a.stability_min_pairs < 1:
         sys.exit("batch_generation.py: --stability_min_pairs must be at least 1")
+    for flag, given in (("--spectrum_out", bool(a.spectrum_out)), ("--spectrum_sigma", a.spectrum_sigma is not None), ("--spectrum_derivative", a.spectrum_derivative is not None),
+                        ("--spectrum_segment", a.spectrum_segment is not None), ("--spectrum_hop", a.spectrum_hop is not None), ("--spectrum_nfft", a.spectrum_nfft is not None),
+                        ("--spectrum_f_lo", a.spectrum_f_lo is not None), ("--spectrum_f_hi", a.spectrum_f_hi is not None),
+                        ("--spectrum_min_segments", a.spectrum_min_segments is not None), ("--spectrum_all_frames", a.spectrum_all_frames),
+                        ("--spectrum_on_host", a.spectrum_on_host)):
+        if given and not a.gait_spectrum:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_spectrum, which was not given")
+    if a.gait_spectrum and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_spectrum needs --vid_folder (the frames whose joints it reads)")
+    if a.spectrum_sigma is not None and not (np.isfinite(a.spectrum_sigma) and 0 <= a.spectrum_sigma <= 16):
+        sys.exit("batch_generation.py: --spectrum_sigma must be within 0 to 16")
+    if a.spectrum_derivative is not None and not 0 <= a.spectrum_derivative <= 2:
+        sys.exit("batch_generation.py: --spectrum_derivative must be 0, 1 or 2")
+    if a.gait_spectrum:
+        seg = 64 if a.spectrum_segment is None else a.spectrum_segment
+        if not 8 <= seg <= 256 or seg % 2:
+            sys.exit("batch_generation.py: --spectrum_segment must be even and within 8 to 256")
+        if a.spectrum_hop is not None and not seg // 8 <= a.spectrum_hop <= seg:
+            sys.exit("batch_generation.py: --spectrum_hop must be within an eighth of --spectrum_segment to the whole of it")
+        nfft = 256 if a.spectrum_nfft is None else a.spectrum_nfft
+        if not seg <= nfft <= 1024 or nfft % 2:
+            sys.exit("batch_generation.py: --spectrum_nfft must be even and within --spectrum_segment to 1024")
+        f_lo, f_hi = 0.5 if a.spectrum_f_lo is None else a.spectrum_f_lo, 3.0 if a.spectrum_f_hi is None else a.spectrum_f_hi
+        if not (np.isfinite(f_lo) and np.isfinite(f_hi) and 0 < f_lo < f_hi <= (20.0 if a.gait_fps is None else a.gait_fps) / 2):
+            sys.exit("batch_generation.py: --spectrum_f_lo and --spectrum_f_hi must obey 0 < f_lo < f_hi <= half the frames a second")
+        if a.spectrum_min_segments is not None and a.spectrum_min_segments < 1:
+            sys.exit("batch_generation.py: --spectrum_min_segments must be at least 1")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -1286,13 +1412,17 @@ def main(argv=None):
     stability = {"sigma": a.stability_sigma, "derivative": a.stability_derivative, "dim": a.stability_dim, "lag": a.stability_lag, "theiler": a.stability_theiler,
                  "horizon": a.stability_horizon, "fit_lo": a.stability_fit_lo, "fit_hi": a.stability_fit_hi, "min_pairs": a.stability_min_pairs,
                  "all_frames": a.stability_all_frames, "on_host": a.stability_on_host, "out": a.stability_out or None} if a.gait_stability else None
+    spectrum = {"fps": a.gait_fps, "sigma": a.spectrum_sigma, "derivative": a.spectrum_derivative, "segment": a.spectrum_segment, "hop": a.spectrum_hop, "nfft": a.spectrum_nfft,
+                "f_lo": a.spectrum_f_lo, "f_hi": a.spectrum_f_hi, "min_segments": a.spectrum_min_segments, "all_frames": a.spectrum_all_frames,
+                "on_host": a.spectrum_on_host, "out": a.spectrum_out or None} if a.gait_spectrum else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
                  **({"kinematics": kinematics} if kinematics is not None else {}), **({"turns": turns} if turns is not None else {}),
                  **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
                  **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
-                 **({"stability": stability} if stability is not None else {}))
+                 **({"stability": stability} if stability is not None else {}),
+                 **({"spectrum": spectrum} if spectrum is not None else {}))
 
 
 if __name__ == "__main__":

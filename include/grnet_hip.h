@@ -888,6 +888,42 @@ int grnet_gait_stability(grnet_t* h, const float* joints3d_dev, int J, const int
 int grnet_op_gait_divergence(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq,
                              int derivative, int dim, int lag, int theiler, int horizon, int32_t* nn_dev, int64_t* pairs_dev, double* mant_dev, void* stream);
 
+/* The Welch power spectral density of the same four body signals (Welch 1967; the band 0.5 to 3 Hz and the width of the dominant peak of Weiss et
+ * al. 2011, the spectral measures of Sejdic et al. 2014 -- on a trunk accelerometer; these signals are joint positions of a pose model, at 20 fps
+ * and 64-frame segments the Hann window alone makes a peak about 0.45 Hz wide at half height, and the defaults are unvalidated on its output): an
+ * averaged, windowed, zero-padded periodogram and thirteen columns read off it (which is the specification).  joints3d_dev,
+ * frame_offsets_host, joints_host, trans_dev and exclude_dev as grnet_gait_regularity takes them.  Float64 with one rounding per operation; sine and
+ * cosine are the harmonics call's own (no library); every test is a comparison, false for NaN:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma.  A frame counts for a channel where its signal is finite and exclude is 0.
+ *   y        grnet_gait_entropy's: the signal differenced `derivative` times (2, accelerations, as the papers measure), NaN where invalid.
+ *   segments of `segment` = L frames, `hop` apart, inside every run of valid y from the run's first frame while the whole segment fits; runs and
+ *            segments in time order.  candidates = their number; used = candidates where >= min_segments, else 0 (psd NaN, the row NaN behind used).
+ *   segment  mu = (sum of y in time order) / L; w_i = 0.5 - 0.5 cos(2 pi i / L); v_i = (y_i - mu) w_i, zero-padded to nfft = N; for k = 0 .. N / 2
+ *            C = sum v_i cos(2 pi k i / N), S = sum v_i sin(..) in rising i from +0.0, the table indexed by (k i) mod N; W2 = sum w_i^2.
+ *   P(k)     (g sum_s (C^2 + S^2)) / ((used fps) W2), g = 2 for 0 < k < N / 2, else 1: scipy.signal.welch(window='hann', detrend='constant',
+ *            scaling='density', nfft=N) of every run, averaged over all segments.
+ *   row      n (valid y), candidates, used, band_power (sum of P fps / N over the bins within [f_lo, f_hi]), total_power (k >= 1), peak_bin (the
+ *            largest positive P of the band, the smallest k of a tie; NaN of none), peak_hz (a parabola through the three bins where the peak is
+ *            one, else the bin), peak_height, peak_width_hz (between the half-height crossings nearest the peak, linear between bins; NaN where a
+ *            side does not cross), dominance (the three bins round the peak inside the band over band_power), centroid_hz, edge_hz (the first bin
+ *            where the running band sum reaches 0.95 of it), cadence (steps a minute: 120 peak_hz on sep, lift and sway, 60 peak_hz on bob).
+ * per_frame_dev (sum T, 4) float64.  psd_dev (n_seq, 4, nfft / 2 + 1) float64.  per_seq_dev (n_seq, 4, 13) float64.  THE LOGARITHM IS THE
+ * CALLER'S: the spectral entropy of the band is taken from psd on the host (as the Python layer does).
+ * One wave per (sequence, channel, block of 64 bins), a lane per bin, the signal, the tables and the segments in LDS; then a wave per (sequence,
+ * channel) for the row; no atomics, nothing added across lanes: a sequence's outputs have the same bits alone or among others.  Needs no weights.
+ * At most four launches (three with sigma = 0) behind one small copy from pinned memory; no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a sequence of more than 32768 frames, sigma outside [0, 16], fps not
+ * positive and finite, derivative outside [0, 2], segment odd or outside [8, 256], hop outside [segment / 8, segment], nfft odd or outside
+ * [segment, 1024], not 0 < f_lo < f_hi <= fps / 2, min_segments outside [1, 2^20].  Nothing is refused on the data.
+ * grnet_op_gait_welch: y, the densities and the rows alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_spectrum(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                        const double* trans_dev, const int32_t* exclude_dev, double fps, double sigma, int derivative, int segment, int hop, int nfft,
+                        double f_lo, double f_hi, int min_segments, double* per_frame_dev, double* psd_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_welch(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                        int derivative, int segment, int hop, int nfft, double f_lo, double f_hi, int min_segments, double* psd_dev, double* per_seq_dev,
+                        void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

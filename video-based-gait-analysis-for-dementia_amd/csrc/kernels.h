@@ -486,6 +486,19 @@ struct StabRule;                           // gait_stability.h: derivative, dim,
 hipError_t launch_stab_sequences(const int* off, int n_seq, int longest, const StabRule& rule, const double* rows, const int* exclude, int frames, int* nn,
                                  double* y_long, long long* pairs, double* mant, hipStream_t s);
 
+// Welch power spectral density of the same four signals (csrc/gait_spectrum_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_spectrum.h).  The frame kernel is launch_reg_frames ----
+struct SpecRule;                           // gait_spectrum.h: fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments
+constexpr int kSpecThreads = 64;           // one wave per (sequence, channel, block of 64 bins): a lane owns a bin
+constexpr int kSpecLdsSegments = 512;      // segments of a sequence whose starts and means the workgroup keeps in LDS (more: the call's scratch)
+int spec_bin_blocks(int nfft);             // the grid's z: blocks of kSpecThreads bins among nfft / 2 + 1
+// two launches on rows (frames,4) and exclude (frames) or null: a wave per (sequence, channel, block of bins) makes psd (n_seq,4,nfft/2+1) and the
+// first three columns of per_seq (n_seq,4,13); a wave per (sequence, channel) the other ten.  y_long: (spec_bin_blocks * 4,frames) float64 where a
+// sequence has more than kRegLdsFrames frames, else null; start_long int32 and mu_long float64 of that shape where a sequence can hold more than
+// kSpecLdsSegments segments (spec_run_segments of its length), else null
+hipError_t launch_spec_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
+                                 double* mu_long, double* psd, double* per_seq, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

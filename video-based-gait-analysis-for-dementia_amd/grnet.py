@@ -1511,6 +1511,60 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_divergence")
         return out
 
+    # ------------------------------------------------------------------ the Welch spectrum
+    def _spectrum_call(self, n, lengths, exclude, derivative, segment, hop, nfft, min_segments, what):
+        """(exclude on the device or None, offsets, hop, the psd and per_sequence tensors) of gait_spectrum and its hook."""
+        if hop is None:
+            hop = segment // 2 if int(segment) == segment else segment
+        self._whole_frames(derivative=derivative, segment=segment, hop=hop, nfft=nfft, min_segments=min_segments)
+        if not 8 <= int(nfft) <= 1024 or int(nfft) % 2:             # the size of psd is made of it here
+            raise ValueError("nfft must be even and within [segment, 1024]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"psd": torch.empty(n_seq, 4, int(nfft) // 2 + 1, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, 13, dtype=torch.float64, device=self.device)}
+        return ex, off, int(hop), out
+
+    def gait_spectrum(self, joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, derivative=2, segment=64, hop=None, nfft=256, f_lo=0.5,
+                      f_hi=3.0, min_segments=2, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """The Welch power spectral density of every sequence's four body signals, on the device (grnet_gait_spectrum; the rules, channels and
+        columns: DESIGN 4.19, pipeline.SPECTRUM_CHANNELS, SPECTRUM_COLUMNS).  joints3d, lengths, trans, exclude and joints as gait_regularity takes
+        them.  Its four signals, smoothed by sigma frames (0: none, the default; <= 16), are differenced `derivative` times (0 .. 2; 2: the
+        acceleration the papers measure); inside every run of frames that count, segments of `segment` frames (even, 8 .. 256) are laid `hop` apart
+        (segment / 8 .. segment; None: segment / 2), each has its mean taken off, is weighted by a periodic Hann window and zero-padded to `nfft`
+        (even, segment .. 1024), and the squared magnitudes of its transform are averaged over the segments, as scipy.signal.welch scales a
+        density; fewer than min_segments segments give NaN.  The row reads the band [f_lo, f_hi] Hz (0 < f_lo < f_hi <= fps / 2): its power, the
+        dominant peak's bin, refined frequency, height and width at half height, the share of the three bins round it, the centroid, the 95 % edge
+        and a cadence (120 or 60 times the peak's frequency by channel).  A sequence has at most 32 768 frames.  Returns a dict of device tensors:
+        per_frame (n,4) float64, gait_regularity's bits; psd (n_seq,4,nfft/2+1) float64; per_sequence (n_seq,4,13) float64.  The spectral entropy
+        is pipeline.spectrum_rows(psd, per_sequence), on the host.  The papers use a trunk accelerometer; the peak's width has a floor set by
+        `segment` (about 0.45 Hz at 20 fps and 64 frames), and the defaults are unvalidated on the model's output.  Nothing is refused on the
+        data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ex, off, hop, out = self._spectrum_call(n, lengths, exclude, derivative, segment, hop, nfft, min_segments, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_spectrum(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                           None if ex is None else ex.data_ptr(), float(fps), float(sigma), int(derivative), int(segment), hop, int(nfft),
+                                           float(f_lo), float(f_hi), int(min_segments), out["per_frame"].data_ptr(), out["psd"].data_ptr(),
+                                           out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_spectrum")
+        return out
+
+    def op_gait_welch(self, signals, lengths=None, exclude=None, fps=20.0, derivative=2, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0, min_segments=2):
+        """Rules 1 (from the differencing on) to 5 of gait_spectrum alone (grnet_op_gait_welch): signals (n,4) float64 and exclude (n,) or None, one
+        sequence or `lengths` of them lying back to back -> {psd, per_sequence} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, hop, out = self._spectrum_call(x.shape[0], lengths, exclude, derivative, segment, hop, nfft, min_segments, "signals")
+        rc = self._lib.grnet_op_gait_welch(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps), int(derivative),
+                                           int(segment), hop, int(nfft), float(f_lo), float(f_hi), int(min_segments), out["psd"].data_ptr(),
+                                           out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_welch")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

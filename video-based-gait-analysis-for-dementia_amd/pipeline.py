@@ -2180,6 +2180,208 @@ def gait_stability(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, 
     return out
 
 
+# ----------------------------------------------------------------------------- the Welch spectrum
+SPECTRUM_CHANNELS = REGULARITY_CHANNELS
+SPECTRUM_COLUMNS = ("n", "candidates", "used", "band_power", "total_power", "peak_bin", "peak_hz", "peak_height", "peak_width_hz", "dominance", "centroid_hz",
+                    "edge_hz", "cadence")
+SPECTRUM_MAX_FRAMES = ENTROPY_MAX_FRAMES
+
+
+def _spectrum_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments):
+    """The refusals of csrc/gait_spectrum.h's spec_rule_error, in its words."""
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if any(int(v) != v for v in (derivative, segment, hop, nfft, min_segments)):
+        raise ValueError("derivative, segment, hop, nfft and min_segments must be whole numbers")
+    if not 0 <= derivative <= 2:
+        raise ValueError("derivative outside [0, 2]")
+    if not 8 <= segment <= 256 or segment % 2:
+        raise ValueError("segment must be even and within [8, 256]")
+    if not segment // 8 <= hop <= segment:
+        raise ValueError("hop outside [segment / 8, segment]")
+    if not segment <= nfft <= 1024 or nfft % 2:
+        raise ValueError("nfft must be even and within [segment, 1024]")
+    if not (np.isfinite(f_lo) and np.isfinite(f_hi) and 0 < f_lo < f_hi <= fps / 2.0):
+        raise ValueError("f_lo and f_hi must obey 0 < f_lo < f_hi <= fps / 2")
+    if not 1 <= min_segments <= 2 ** 20:
+        raise ValueError("min_segments outside [1, 2^20]")
+
+
+def _spectrum_band(fps, nfft, f_lo, f_hi):
+    """spec_band: (k_lo, k_hi) of the bins 0 .. nfft / 2 whose frequency (k fps) / nfft lies in [f_lo, f_hi]; k_lo > k_hi where there is none."""
+    f = (np.arange(nfft // 2 + 1, dtype=np.float64) * float(fps)) / float(nfft)
+    inside = np.flatnonzero((f >= f_lo) & (f <= f_hi))
+    return (int(inside[0]), int(inside[-1])) if inside.size else (nfft // 2 + 1, -1)
+
+
+def _spectrum_row(P, fps, nfft, f_lo, f_hi, odd, n, candidates, used):
+    """spec_row on Python floats, one operation at a time in the header's order."""
+    nan = float("nan")
+    out = [float(n), float(candidates), float(used)] + [nan] * 10
+    if used < 1:
+        return out
+    P = [float(v) for v in P]
+    fps, N, half = float(fps), float(nfft), nfft // 2
+    df = fps / N
+    k_lo, k_hi = _spectrum_band(fps, nfft, f_lo, f_hi)
+    band = total = sum_p = sum_fp = 0.0
+    best = -1
+    for k in range(1, half + 1):
+        total = total + P[k] * df
+    for k in range(k_lo, k_hi + 1):
+        band = band + P[k] * df
+        sum_p = sum_p + P[k]
+        sum_fp = sum_fp + ((float(k) * fps) / N) * P[k]
+        if P[k] > 0.0 and math.isfinite(P[k]) and (best < 0 or P[k] > P[best]):
+            best = k
+    out[3], out[4] = band, total
+    if sum_p > 0.0 and math.isfinite(sum_p):
+        out[10] = sum_fp / sum_p
+    if band > 0.0 and math.isfinite(band):
+        bar, running = 0.95 * band, 0.0
+        for k in range(k_lo, k_hi + 1):
+            running = running + P[k] * df
+            if running >= bar:
+                out[11] = (float(k) * fps) / N
+                break
+    if best < 0:
+        return out
+    b, at = P[best], float(best)
+    if 0 < best < half:
+        a, c = P[best - 1], P[best + 1]
+        den = (a - 2.0 * b) + c
+        if den < 0.0 and b >= a and b >= c:
+            at = float(best) + (0.5 * (a - c)) / den
+    out[5], out[6], out[7] = float(best), (at * fps) / N, b
+    out[12] = (120.0 if odd else 60.0) * out[6]
+    level, left, right = 0.5 * b, nan, nan
+    for j in range(best - 1, -1, -1):
+        if P[j] < level:
+            left = float(j) + (level - P[j]) / (P[j + 1] - P[j])
+            break
+    for j in range(best + 1, half + 1):
+        if P[j] < level:
+            right = float(j - 1) + (P[j - 1] - level) / (P[j - 1] - P[j])
+            break
+    out[8] = ((right - left) * fps) / N
+    three = 0.0
+    for j in range(best - 1, best + 2):
+        if k_lo <= j <= k_hi:
+            three = three + P[j] * df
+    if band > 0.0 and math.isfinite(band):
+        out[9] = three / band
+    return out
+
+
+def spectrum_rows(psd, per_sequence, fps=20.0, f_lo=0.5, f_hi=3.0):
+    """Rule 6 of DESIGN 4.19, the one place where the logarithm is taken: psd (..., nfft / 2 + 1) and per_sequence (..., 13), from the device or from
+    gait_welch -> {'spectral_entropy': (...) float64 = -sum p ln p / ln(bins) over the band's bins, p = P / sum P there; NaN where used is 0, the band
+    has fewer than 2 bins or its power is not positive}.  fps, f_lo and f_hi as the call had them."""
+    P, rows = np.asarray(psd, np.float64), np.asarray(per_sequence, np.float64)
+    if P.ndim < 1 or P.shape[-1] < 5 or rows.shape != P.shape[:-1] + (len(SPECTRUM_COLUMNS),):
+        raise ValueError(f"psd must be (..., nfft / 2 + 1) and per_sequence (..., {len(SPECTRUM_COLUMNS)}) of the same rows, got {P.shape} and {rows.shape}")
+    nfft = 2 * (P.shape[-1] - 1)
+    k_lo, k_hi = _spectrum_band(fps, nfft, f_lo, f_hi)
+    bins = k_hi - k_lo + 1
+    flat, used = P.reshape(-1, P.shape[-1]), rows.reshape(-1, rows.shape[-1])[:, 2]
+    out = np.full(flat.shape[0], np.nan)
+    for e in range(flat.shape[0]):
+        if bins < 2 or not used[e] >= 1:
+            continue
+        band = flat[e, k_lo:k_hi + 1].tolist()
+        total = math.fsum(band)
+        if not (total > 0.0 and math.isfinite(total)):
+            continue
+        h = 0.0
+        for v in band:
+            p = v / total
+            if p > 0.0:
+                h = h - p * math.log(p)
+        out[e] = h / math.log(bins)
+    return {"spectral_entropy": out.reshape(P.shape[:-1])}
+
+
+def gait_welch(signals, lengths=None, exclude=None, fps=20.0, derivative=2, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0, min_segments=2):
+    """Rules 1 (from the differencing on) to 6 of DESIGN 4.19 on given signals: the host statement of GRNet.op_gait_welch.  signals (n,4) float64,
+    columns SPECTRUM_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count; hop None: segment / 2.  Returns {'psd':
+    (n_seq,4,nfft/2+1), 'per_sequence': (n_seq,4,13), columns SPECTRUM_COLUMNS, 'freqs': (nfft/2+1,), and spectrum_rows' 'spectral_entropy'}.  Every
+    sum in rising index from +0.0 (a cumulative sum, or one addition a loop turn), the twiddles harmonics_twiddles' at (k i) mod nfft."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+    _spectrum_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+    _entropy_lengths_check(lengths)
+    fps, d, L, hop, N, min_segments = float(fps), int(derivative), int(segment), int(hop), int(nfft), int(min_segments)
+    half = N // 2
+    sn, cs = harmonics_twiddles(N)
+    w = 0.5 - 0.5 * harmonics_twiddles(L)[1]
+    W2 = float(np.cumsum(np.concatenate([[0.0], w * w]))[-1])
+    kk = np.arange(half + 1, dtype=np.int64)
+    g = np.where((kk > 0) & (kk < half), 2.0, 1.0)
+    psd = np.full((len(lengths), 4, half + 1), np.nan)
+    per_seq = np.full((len(lengths), 4, len(SPECTRUM_COLUMNS)), np.nan)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                y[~np.isfinite(y)] = np.nan
+                ok = np.isfinite(y)
+                edges = np.flatnonzero(np.diff(np.concatenate([[False], ok, [False]]).astype(np.int8)))
+                starts = [t0 for a, e in zip(edges[0::2], edges[1::2]) for t0 in range(int(a), int(e) - L + 1, hop)]
+                candidates = len(starts)
+                used = candidates if candidates >= min_segments else 0
+                if used:
+                    seg = y[np.asarray(starts)[:, None] + np.arange(L)[None, :]]
+                    mu = np.cumsum(np.concatenate([np.zeros((used, 1)), seg], axis=1), axis=1)[:, -1] / float(L)
+                    v = (seg - mu[:, None]) * w[None, :]
+                    C, S = np.zeros((used, half + 1)), np.zeros((used, half + 1))
+                    for i in range(L):
+                        j = (kk * i) % N
+                        C = C + v[:, i, None] * cs[j][None, :]
+                        S = S + v[:, i, None] * sn[j][None, :]
+                    acc = np.cumsum(np.concatenate([np.zeros((1, half + 1)), C * C + S * S], axis=0), axis=0)[-1]
+                    psd[q, ch] = (g * acc) / ((float(used) * fps) * W2)
+                per_seq[q, ch] = _spectrum_row(psd[q, ch], fps, N, f_lo, f_hi, ch < 3, int(ok.sum()), candidates, used)
+            f0 += T
+    out = {"psd": psd, "per_sequence": per_seq, "freqs": (np.arange(half + 1, dtype=np.float64) * fps) / float(N)}
+    out.update(spectrum_rows(psd, per_seq, fps, f_lo, f_hi))
+    return out
+
+
+def gait_spectrum(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, derivative=2, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0,
+                  min_segments=2, joints=GAIT_JOINTS_KINECTV2):
+    """The Welch power spectral density of four body signals in numpy float64 (Welch 1967; Weiss et al. 2011 and Sejdic et al. 2014 on trunk
+    accelerations; the rules: DESIGN 4.19; the defaults are unvalidated on the model's output, and the peak's width has a floor set by the segment
+    length, not by the walker): the host statement of GRNet.gait_spectrum, same arguments, a dict of numpy arrays.  per_frame (n,4) is
+    gait_regularity's at the same sigma; psd, per_sequence, freqs and spectral_entropy: gait_welch's."""
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+
+    def rule_check():
+        _spectrum_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check)
+    out = gait_welch(per_frame, lengths, exclude, fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
