@@ -77,6 +77,15 @@ segments the Hann window alone makes the peak about 0.45 Hz wide at half height,
 walker, and the defaults are unvalidated on the model's output.  With --gait_turns a turn splits the walk into straight runs.  Reported, never
 judged.
 
+--gait_recurrence (opt-in, needs no --gait) reports the recurrence quantification of the same four body signals: every pair of states of the
+delay-embedded signal against one radius, and the diagonal lines of recurrent pairs by their length -- recurrence rate, determinism, mean and longest
+line, divergence and the entropy of the line lengths (Webber and Zbilut 1994, Marwan et al. 2007), which the gait studies report beside harmonic
+ratio, entropy and the Lyapunov exponents (Labini et al. 2012, Riva et al. 2013).  The device counts the pairs and the lines (GRNet.gait_recurrence,
+DESIGN 4.20); the line threshold and the logarithm are pipeline.recurrence_rows'.  <outpath>_recurrence.json.  The papers use a trunk sensor and
+minutes of walking; these are joint positions of a pose model over some 15 strides, the radius is this project's rule (a fraction of the signal's SD,
+not of the phase-space diameter), and the defaults are unvalidated on the model's output.  With --gait_turns only straight walking counts.
+Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -723,6 +732,70 @@ class WindowStability:
         return path
 
 
+class WindowRecurrence:
+    """--gait_recurrence: one gait_recurrence call per database window on rank 0, one sequence per video, on the joints the window's gather left on
+    the device (model.gait_recurrence; on_host, or a model without the method: pipeline.gait_recurrence after a download) -- with the window's
+    translations where --trajectory made them, and with --gait_turns' phase as `exclude`, so that only straight walking counts (straight_only): a
+    point before a turn may then recur with one after it, which is intended, both being straight walking, and a turn ends every line that runs
+    into it.  It needs no events and so no --gait.  Either way the line threshold, the rates and the logarithm are pipeline.recurrence_rows' on the
+    integers.  Per video and channel (pipeline.RECURRENCE_CHANNELS) the columns of pipeline.RECURRENCE_COLUMNS and RECURRENCE_COUNTS, every row of
+    pipeline.RECURRENCE_ROWS, and 'hist', the [length, lines] of the non-empty bins; null where undefined.  The joints are
+    pipeline.GAIT_JOINTS_KINECTV2.  The radius rule is this project's and the defaults are unvalidated on the model's output; the results are
+    reported and never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, sigma=0.0, derivative=1, dim=5, lag=2, theiler=8, radius=0.8, min_line=2, min_points=50):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_recurrence") else model.gait_recurrence
+        self.straight_only = bool(straight_only)
+        self.kw = dict(sigma=float(sigma), derivative=int(derivative), dim=int(dim), lag=int(lag), theiler=int(theiler), radius=float(radius))
+        self.rows = dict(min_line=int(min_line), min_points=int(min_points))
+        pipe.recurrence_rows(np.zeros((1, 6), np.int64), np.zeros((1, pipe.RECURRENCE_BINS), np.int64), **self.rows)      # its refusals, before any inference runs
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_recurrence(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw, **self.rows)
+        out.update(self.pipe.recurrence_rows(out["counts"], out["hist"], **self.rows))
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form):
+            return "none" if v is None else format(v, form)
+        for q, key in enumerate(keys):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.RECURRENCE_CHANNELS):
+                row = {col: number(v) for col, v in zip(self.pipe.RECURRENCE_COLUMNS, out["per_sequence"][q][c])}
+                row.update({col: int(v) for col, v in zip(self.pipe.RECURRENCE_COUNTS, out["counts"][q][c])})
+                for col in self.pipe.RECURRENCE_ROWS:
+                    if col != "longest":                        # the count stays an integer; the row's NaN below min_line shows in 'divergence'
+                        row[col] = int(out[col][q][c]) if col in ("lines", "line_points") else number(out[col][q][c])
+                row["hist"] = [[int(k) + 1, int(out["hist"][q][c][k])] for k in np.flatnonzero(out["hist"][q][c])]
+                video[name] = row
+            self.videos[key] = video
+            sep = video["sep"]
+            print(f"Recurrence: video {key}, {sep['points']} points, recurrence rate {shown(sep['recurrence_rate'], '.3f')}, determinism {shown(sep['determinism'], '.3f')}, "
+                  f"longest line {sep['longest']} of the ankles' separation{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait recurrence of {len(self.videos)} videos to {path}.")
+        return path
+
+
 class WindowSpectrum:
     """--gait_spectrum: one gait_spectrum call per database window on rank 0, one sequence per video, on the joints the window's gather left on the
     device (model.gait_spectrum; on_host, or a model without the method: pipeline.gait_spectrum after a download) -- with the window's translations
@@ -789,8 +862,11 @@ class WindowSpectrum:
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None):
-    """spectrum: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None):
+    """recurrence: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'radius', 'min_line', 'min_points', 'all_frames', 'on_host', 'out'} (each optional;
+    needs no gait) -- also the recurrence quantification of every video (WindowRecurrence), written to recurrence['out'] (default: outpath with
+    _recurrence.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
+    spectrum: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
     needs no gait, whose fps it takes where its own is not given, else 20) -- also the Welch spectrum of every video (WindowSpectrum), written to
     spectrum['out'] (default: outpath with _spectrum.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
     stability: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'horizon', 'fit_lo', 'fit_hi', 'min_pairs', 'all_frames', 'on_host', 'out'} (each optional;
@@ -910,6 +986,9 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                            **({"fps": gait["fps"]} if spectrum.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
                            **{k: spectrum[k] for k in ("fps", "sigma", "derivative", "segment", "hop", "nfft", "f_lo", "f_hi", "min_segments") if spectrum.get(k) is not None}) \
         if spectrum is not None and rank == 0 else None
+    again = WindowRecurrence(pipe, model, recurrence.get("on_host", False), not recurrence.get("all_frames", False),
+                             **{k: recurrence[k] for k in ("sigma", "derivative", "dim", "lag", "theiler", "radius", "min_line", "min_points") if recurrence.get(k) is not None}) \
+        if recurrence is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -974,6 +1053,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             apart.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if bands is not None and vids:
             bands.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None, steady.videos if steady is not None else None)
+        if again is not None and vids:
+            again.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -1015,6 +1096,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         apart.write(stability.get("out") or osp.splitext(outpath)[0] + "_stability.json")
     if bands is not None:
         bands.write(spectrum.get("out") or osp.splitext(outpath)[0] + "_spectrum.json")
+    if again is not None:
+        again.write(recurrence.get("out") or osp.splitext(outpath)[0] + "_recurrence.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -1162,6 +1245,23 @@ def main(argv=None):
     p.add_argument("--spectrum_min_segments", type=int, default=None, help="with --gait_spectrum: a video with fewer segments has no spectrum, at least 1 (default 2)")
     p.add_argument("--spectrum_all_frames", action="store_true", help="with --gait_spectrum and --gait_turns: count the frames of the turns too")
     p.add_argument("--spectrum_on_host", action="store_true", help="with --gait_spectrum: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_recurrence", action="store_true", help="with --vid_folder (no --gait needed): the recurrence quantification of four body signals -- recurrence rate, "
+                   "determinism, mean and longest diagonal line, divergence and line entropy of the delay-embedded signal (Webber and Zbilut 1994, Marwan et al. 2007): "
+                   "<outpath>_recurrence.json, one line per video; quadratic in a video's frames; with --gait_turns only straight walking counts; the radius rule is this "
+                   "project's and the defaults are unvalidated on the model's output")
+    p.add_argument("--recurrence_out", type=str, default="", help="with --gait_recurrence: the JSON file (default: --outpath with _recurrence.json)")
+    p.add_argument("--recurrence_sigma", type=float, default=None, help="with --gait_recurrence: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--recurrence_derivative", type=int, default=None, help="with --gait_recurrence: 0 the signal, 1 its velocity, 2 its acceleration (default 1, as --gait_stability)")
+    p.add_argument("--recurrence_dim", type=int, default=None, help="with --gait_recurrence: the embedding dimension, 2 to 8 (default 5)")
+    p.add_argument("--recurrence_lag", type=int, default=None, help="with --gait_recurrence: the embedding delay in frames, 1 to 16 (default 2)")
+    p.add_argument("--recurrence_radius", type=float, default=None, help="with --gait_recurrence: the radius in SDs of the signal, above 0 and at most 10 (default 0.8); two points "
+                   "recur where their squared distance is at most (radius SD)^2 times the dimension")
+    p.add_argument("--recurrence_theiler", type=int, default=None, help="with --gait_recurrence: a pair's points lie more than this many frames apart, 0 to 4096 (default 8, the "
+                   "default embedding's span)")
+    p.add_argument("--recurrence_min_line", type=int, default=None, help="with --gait_recurrence: the shortest diagonal line that counts, 1 to 255 (default 2)")
+    p.add_argument("--recurrence_min_points", type=int, default=None, help="with --gait_recurrence: a video with fewer valid points has no rates, at least 1 (default 50)")
+    p.add_argument("--recurrence_all_frames", action="store_true", help="with --gait_recurrence and --gait_turns: count the frames of the turns too")
+    p.add_argument("--recurrence_on_host", action="store_true", help="with --gait_recurrence: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -1377,6 +1477,31 @@ def main(argv=None):
             sys.exit("batch_generation.py: --spectrum_f_lo and --spectrum_f_hi must obey 0 < f_lo < f_hi <= half the frames a second")
         if a.spectrum_min_segments is not None and a.spectrum_min_segments < 1:
             sys.exit("batch_generation.py: --spectrum_min_segments must be at least 1")
+    for flag, given in (("--recurrence_out", bool(a.recurrence_out)), ("--recurrence_sigma", a.recurrence_sigma is not None), ("--recurrence_derivative", a.recurrence_derivative is not None),
+                        ("--recurrence_dim", a.recurrence_dim is not None), ("--recurrence_lag", a.recurrence_lag is not None), ("--recurrence_radius", a.recurrence_radius is not None),
+                        ("--recurrence_theiler", a.recurrence_theiler is not None), ("--recurrence_min_line", a.recurrence_min_line is not None),
+                        ("--recurrence_min_points", a.recurrence_min_points is not None), ("--recurrence_all_frames", a.recurrence_all_frames),
+                        ("--recurrence_on_host", a.recurrence_on_host)):
+        if given and not a.gait_recurrence:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_recurrence, which was not given")
+    if a.gait_recurrence and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_recurrence needs --vid_folder (the frames whose joints it reads)")
+    if a.recurrence_sigma is not None and not (np.isfinite(a.recurrence_sigma) and 0 <= a.recurrence_sigma <= 16):
+        sys.exit("batch_generation.py: --recurrence_sigma must be within 0 to 16")
+    if a.recurrence_derivative is not None and not 0 <= a.recurrence_derivative <= 2:
+        sys.exit("batch_generation.py: --recurrence_derivative must be 0, 1 or 2")
+    if a.recurrence_dim is not None and not 2 <= a.recurrence_dim <= 8:
+        sys.exit("batch_generation.py: --recurrence_dim must be within 2 to 8")
+    if a.recurrence_lag is not None and not 1 <= a.recurrence_lag <= 16:
+        sys.exit("batch_generation.py: --recurrence_lag must be within 1 to 16")
+    if a.recurrence_radius is not None and not (np.isfinite(a.recurrence_radius) and 0 < a.recurrence_radius <= 10):
+        sys.exit("batch_generation.py: --recurrence_radius must be above 0 and at most 10")
+    if a.recurrence_theiler is not None and not 0 <= a.recurrence_theiler <= 4096:
+        sys.exit("batch_generation.py: --recurrence_theiler must be within 0 to 4096")
+    if a.recurrence_min_line is not None and not 1 <= a.recurrence_min_line <= 255:
+        sys.exit("batch_generation.py: --recurrence_min_line must be within 1 to 255")
+    if a.recurrence_min_points is not None and a.recurrence_min_points < 1:
+        sys.exit("batch_generation.py: --recurrence_min_points must be at least 1")
     if a.openpose_folder and not a.vid_folder and not a.bbox_out:
         sys.exit("batch_generation.py: --openpose_folder without --vid_folder only writes the boxes: name the file with --bbox_out")
     annos = trajectory = tracks = None
@@ -1415,6 +1540,9 @@ def main(argv=None):
     spectrum = {"fps": a.gait_fps, "sigma": a.spectrum_sigma, "derivative": a.spectrum_derivative, "segment": a.spectrum_segment, "hop": a.spectrum_hop, "nfft": a.spectrum_nfft,
                 "f_lo": a.spectrum_f_lo, "f_hi": a.spectrum_f_hi, "min_segments": a.spectrum_min_segments, "all_frames": a.spectrum_all_frames,
                 "on_host": a.spectrum_on_host, "out": a.spectrum_out or None} if a.gait_spectrum else None
+    recurrence = {"sigma": a.recurrence_sigma, "derivative": a.recurrence_derivative, "dim": a.recurrence_dim, "lag": a.recurrence_lag, "theiler": a.recurrence_theiler,
+                  "radius": a.recurrence_radius, "min_line": a.recurrence_min_line, "min_points": a.recurrence_min_points, "all_frames": a.recurrence_all_frames,
+                  "on_host": a.recurrence_on_host, "out": a.recurrence_out or None} if a.gait_recurrence else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
@@ -1422,7 +1550,7 @@ def main(argv=None):
                  **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
                  **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
                  **({"stability": stability} if stability is not None else {}),
-                 **({"spectrum": spectrum} if spectrum is not None else {}))
+                 **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}))
 
 
 if __name__ == "__main__":

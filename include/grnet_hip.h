@@ -924,6 +924,40 @@ int grnet_op_gait_welch(grnet_t* h, const double* signals_dev, const int32_t* ex
                         int derivative, int segment, int hop, int nfft, double f_lo, double f_hi, int min_segments, double* psd_dev, double* per_seq_dev,
                         void* stream);
 
+/* Recurrence quantification of the same four body signals (Webber and Zbilut 1994; Marwan et al. 2007; on gait Labini et al. 2012 and Riva et al.
+ * 2013 -- on a trunk sensor over minutes of walking; these signals are joint positions of a pose model over some 15 strides, the radius rule is this
+ * project's and the defaults are unvalidated on its output): every pair of points of the delay-embedded signal against one radius, and the runs of
+ * recurrent pairs along each diagonal counted by their length (which is the specification).  joints3d_dev, frame_offsets_host,
+ * joints_host, trans_dev and exclude_dev as grnet_gait_regularity takes them.  Float64 with one rounding per operation; every test is a comparison,
+ * false for NaN:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma.  A frame counts for a channel where its signal is finite and exclude is 0.
+ *   y        grnet_gait_entropy's: the signal differenced `derivative` times (1, velocities, as grnet_gait_stability), NaN where invalid.
+ *   spread   grnet_gait_entropy's n, mu, SD over the valid y, r = radius SD; eps2 = (r r) dim.  Where r is not > 0 nothing is recurrent.
+ *   points   grnet_gait_stability's: span = (dim - 1) lag, M = T - span points, valid iff their dim values all are; points = the valid ones.
+ *   pairs    i < j < M with j - i > theiler; comparable iff both points are valid; recurrent iff comparable and D2(i, j) <= eps2, D2 as
+ *            grnet_gait_stability adds it, no square root.  An infinite D2 is comparable and not recurrent.
+ *   lines    on diagonal s = j - i, theiler < s < M, in rising i: a maximal run of consecutive recurrent pairs is a line of its length; a pair that
+ *            is not recurrent or not comparable ends it; a line at an end of the diagonal counts with the length it has (no border correction).
+ * per_frame_dev (sum T, 4) float64.  per_seq_dev (n_seq, 4, 5) float64: [n, mean, sd, r, eps2].  hist_dev (n_seq, 4, 255) int64: hist[l - 1] lines of
+ * length l = 1 .. 255.  counts_dev (n_seq, 4, 6) int64: [points, comparable, recurrent, long_lines (l >= 256), long_points (the sum of their
+ * lengths), longest (0 with no line)].  Always sum l hist[l - 1] + long_points = recurrent.  THE LINE THRESHOLD AND THE LOGARITHM ARE THE CALLER'S
+ * (INTEGRATION.md states the formulas; the Python layer's pipeline.recurrence_rows takes lines of min_line = 2 and more where points >= 50).
+ * A workgroup per (sequence, channel, part of up to 16), a lane per circular offset, the signal in LDS; line ends go into an LDS histogram by integer
+ * atomic adds, the only atomics: no global and no floating-point atomics, so a sequence's outputs have the same bits alone or among others.  Then a
+ * workgroup per (sequence, channel) adds the parts in part order.  The work is QUADRATIC in a sequence's frames.  Needs no weights.  At most five
+ * launches (four with sigma = 0) behind one small copy from pinned memory; no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a sequence of more than 32768 frames, sigma outside [0, 16], derivative
+ * outside [0, 2], dim outside [2, 8], lag outside [1, 16], theiler outside [0, 4096], radius not finite or outside (0, 10].  Nothing is refused on the
+ * data.
+ * grnet_op_gait_recurrence_counts: y, the spread, the pairs and the rows alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_recurrence(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                          const double* trans_dev, const int32_t* exclude_dev, double sigma, int derivative, int dim, int lag, int theiler, double radius,
+                          double* per_frame_dev, double* per_seq_dev, int64_t* hist_dev, int64_t* counts_dev, void* stream);
+int grnet_op_gait_recurrence_counts(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq,
+                                    int derivative, int dim, int lag, int theiler, double radius, double* per_seq_dev, int64_t* hist_dev,
+                                    int64_t* counts_dev, void* stream);
+
 /* Inference.__getitem__ -- lib/dataset/inference.py:71-87 (get_single_image_crop_demo + ToTensor + Normalize,
  * lib/data_utils/img_utils.py:252-285,355-363; rot = 0): n uint8 HWC frames (n,H,W,3) [one_image_for_all: a single
  * (H,W,3) frame shared by all boxes] and boxes (n,4) [cx,cy,w,h] -> (n,3,224,224) fp32 normalised crops, all device

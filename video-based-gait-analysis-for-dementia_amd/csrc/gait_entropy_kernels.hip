@@ -88,6 +88,12 @@ __global__ __launch_bounds__(kGaitThreads) void ent_count_kernel(const int* __re
 
 }  // namespace
 
+hipError_t launch_ent_spread(const int* off, int n_seq, int derivative, double fraction, const double* rows, const int* exclude, int frames, double* y,
+                             double* per_seq, hipStream_t s) {
+    const EntRule rule{1, fraction, derivative, 1};             // the kernel reads the derivative and the fraction alone
+    return launch_k(ent_spread_kernel, dim3(n_seq, kRegChannels), dim3(kGaitThreads), 0, s, off, rule, rows, exclude, frames, y, per_seq);
+}
+
 hipError_t launch_ent_sequences(const int* off, int n_seq, const EntRule& rule, const double* rows, const int* exclude, int frames, double* y, double* z_long,
                                 long long* counts, double* per_seq, hipStream_t s) {
     hipError_t e = launch_k(ent_spread_kernel, dim3(n_seq, kRegChannels), dim3(kGaitThreads), 0, s, off, rule, rows, exclude, frames, y, per_seq);

@@ -499,6 +499,18 @@ int spec_bin_blocks(int nfft);             // the grid's z: blocks of kSpecThrea
 hipError_t launch_spec_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
                                  double* mu_long, double* psd, double* per_seq, hipStream_t s);
 
+// Recurrence quantification of the same four signals (csrc/gait_recurrence_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_recurrence.h).  The frame kernel is launch_reg_frames ----
+struct RecRule;                            // gait_recurrence.h: derivative, dim, lag, theiler, radius
+// gait_entropy's first launch alone (csrc/gait_entropy_kernels.hip): y (4,frames) and per_seq (n_seq,4,4) = (n, mu, SD, fraction SD)
+hipError_t launch_ent_spread(const int* off, int n_seq, int derivative, double fraction, const double* rows, const int* exclude, int frames, double* y,
+                             double* per_seq, hipStream_t s);
+// three launches on rows (frames,4) and exclude (frames) or null: launch_ent_spread into y and spread (n_seq,4,4); a workgroup per (sequence, channel,
+// part; max_parts: the most parts of a sequence, rec_parts) walks the pairs into partials (sum of the sequences' parts,4,kRecPartCols) int64; a
+// workgroup per (sequence, channel) adds them into per_seq (n_seq,4,5), hist (n_seq,4,255) int64 and counts (n_seq,4,6) int64
+hipError_t launch_rec_sequences(const int* off, int n_seq, int max_parts, const RecRule& rule, const double* rows, const int* exclude, int frames, double* y,
+                                double* spread, long long* partials, double* per_seq, long long* hist, long long* counts, hipStream_t s);
+
 // Joints regressed from vertices with a caller's table (pare.py:70-76; csrc/joint_regress.hip) ----
 constexpr int kJregMaxRows = 64;   // output rows per frame (4 MFMA row tiles)
 constexpr int kJregSlices = 27;    // fixed split of the 6890 vertices: 27 workgroup slices of 256 (4 waves x 64), partials added in slice order

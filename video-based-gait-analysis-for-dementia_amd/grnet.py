@@ -1511,6 +1511,56 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_divergence")
         return out
 
+    # ------------------------------------------------------------------ recurrence quantification
+    def _recurrence_call(self, n, lengths, exclude, derivative, dim, lag, theiler, what):
+        """(exclude on the device or None, offsets, the per_sequence, hist and counts tensors) of gait_recurrence and its hook."""
+        self._whole_frames(derivative=derivative, dim=dim, lag=lag, theiler=theiler)
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"per_sequence": torch.empty(n_seq, 4, 5, dtype=torch.float64, device=self.device),
+               "hist": torch.empty(n_seq, 4, 255, dtype=torch.int64, device=self.device),
+               "counts": torch.empty(n_seq, 4, 6, dtype=torch.int64, device=self.device)}
+        return ex, off, out
+
+    def gait_recurrence(self, joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, derivative=1, dim=5, lag=2, theiler=8, radius=0.8,
+                        joints=_lib.GAIT_JOINTS_KINECTV2):
+        """The integers behind the recurrence quantification of every sequence, on the device (grnet_gait_recurrence; the rules, channels and
+        columns: DESIGN 4.20, pipeline.RECURRENCE_CHANNELS, RECURRENCE_COLUMNS, RECURRENCE_COUNTS, RECURRENCE_BINS).  joints3d, lengths, trans,
+        exclude and joints as gait_regularity takes them.  Its four signals, smoothed by sigma frames (0: none, the default; <= 16), are
+        differenced `derivative` times (0 .. 2; 1, velocities, as gait_stability) and embedded with `dim` (2 .. 8) delays of `lag` (1 .. 16)
+        frames; every pair of valid points more than `theiler` (0 .. 4096) frames apart is comparable, and recurrent where its squared distance
+        is at most eps2 = (radius SD)^2 dim (radius in (0, 10], SD of the frames that count); along every diagonal the runs of recurrent pairs
+        are lines, counted by their length.  A sequence has at most 32 768 frames: the work is quadratic in them.  Returns a dict of device
+        tensors: per_frame (n,4) float64, gait_regularity's bits; per_sequence (n_seq,4,5) float64 = (n, mu, SD, r, eps2); hist (n_seq,4,255)
+        int64, the lines of length 1 .. 255; counts (n_seq,4,6) int64 = (points, comparable, recurrent, long_lines, long_points, longest).  The
+        line threshold, the rates and the logarithm are pipeline.recurrence_rows(counts, hist), on the host.  The papers use a trunk sensor and
+        minutes of walking; the radius rule is this project's and the defaults are unvalidated on the model's output.  Nothing is refused on the
+        data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ex, off, out = self._recurrence_call(n, lengths, exclude, derivative, dim, lag, theiler, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_recurrence(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                             None if ex is None else ex.data_ptr(), float(sigma), int(derivative), int(dim), int(lag), int(theiler), float(radius),
+                                             out["per_frame"].data_ptr(), out["per_sequence"].data_ptr(), out["hist"].data_ptr(), out["counts"].data_ptr(),
+                                             self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_recurrence")
+        return out
+
+    def op_gait_recurrence_counts(self, signals, lengths=None, exclude=None, derivative=1, dim=5, lag=2, theiler=8, radius=0.8):
+        """Rules 1 (from the differencing on) to 6 of gait_recurrence alone (grnet_op_gait_recurrence_counts): signals (n,4) float64 and exclude
+        (n,) or None, one sequence or `lengths` of them lying back to back -> {per_sequence, hist, counts} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, out = self._recurrence_call(x.shape[0], lengths, exclude, derivative, dim, lag, theiler, "signals")
+        rc = self._lib.grnet_op_gait_recurrence_counts(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, int(derivative),
+                                                       int(dim), int(lag), int(theiler), float(radius), out["per_sequence"].data_ptr(), out["hist"].data_ptr(),
+                                                       out["counts"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_recurrence_counts")
+        return out
+
     # ------------------------------------------------------------------ the Welch spectrum (DESIGN 4.19)
     def _spectrum_call(self, n, lengths, exclude, derivative, segment, hop, nfft, min_segments, what):
         """(exclude on the device or None, offsets, hop, the psd and per_sequence tensors) of gait_spectrum and its hook."""

@@ -2180,6 +2180,172 @@ def gait_stability(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, 
     return out
 
 
+# ----------------------------------------------------------------------------- recurrence quantification
+RECURRENCE_CHANNELS = REGULARITY_CHANNELS
+RECURRENCE_COLUMNS = ("n", "mean", "sd", "r", "eps2")
+RECURRENCE_COUNTS = ("points", "comparable", "recurrent", "long_lines", "long_points", "longest")
+RECURRENCE_BINS = 255
+RECURRENCE_MAX_FRAMES = ENTROPY_MAX_FRAMES
+RECURRENCE_ROWS = ("lines", "line_points", "recurrence_rate", "determinism", "mean_line", "longest", "divergence", "line_entropy", "ratio")
+
+
+def _recurrence_rule_check(derivative, dim, lag, theiler, radius):
+    """The refusals of csrc/gait_recurrence.h's rec_rule_error, in its words."""
+    if any(int(v) != v for v in (derivative, dim, lag, theiler)):
+        raise ValueError("derivative, dim, lag and theiler must be whole numbers")
+    if not 0 <= derivative <= 2:
+        raise ValueError("derivative outside [0, 2]")
+    if not 2 <= dim <= 8:
+        raise ValueError("dim outside [2, 8]")
+    if not 1 <= lag <= 16:
+        raise ValueError("lag outside [1, 16]")
+    if not 0 <= theiler <= 4096:
+        raise ValueError("theiler outside [0, 4096]")
+    if not np.isfinite(radius) or not 0 < radius <= 10:
+        raise ValueError("radius must be finite and within (0, 10]")
+
+
+def recurrence_rows(counts, hist, min_line=2, min_points=50):
+    """Rule 7 of DESIGN 4.20, the one place where the line threshold is applied and the logarithm taken: counts (..., 6) integers, columns
+    RECURRENCE_COUNTS, and hist (..., 255) integers, from the device or from gait_recurrence_counts -> a dict of (...) arrays, keys RECURRENCE_ROWS.
+    lines and line_points (int64) count the lines of min_line (1 .. 255) pairs and more, the long ones (256 and more) among them; recurrence_rate =
+    recurrent / comparable; determinism = line_points / recurrent; mean_line = line_points / lines; longest and divergence = 1 / longest, both NaN
+    where longest < min_line; line_entropy = -sum p ln p over the classes l = min_line .. 255 in rising l from +0.0 and ONE further class of all lines
+    of 256 and more; ratio = determinism / recurrence_rate.  Everything but the two integers is NaN where points < min_points or its own denominator
+    is 0.  Python integers and floats: a quotient of two counts is their correctly rounded quotient."""
+    c, h = np.asarray(counts), np.asarray(hist)
+    if c.ndim < 1 or c.shape[-1] != 6 or c.dtype.kind not in "iu" or h.dtype.kind not in "iu" or h.shape != c.shape[:-1] + (RECURRENCE_BINS,):
+        raise ValueError(f"counts must be integers of shape (..., 6) and hist (..., {RECURRENCE_BINS}), got {c.dtype} {c.shape} and {h.dtype} {h.shape}")
+    if int(min_line) != min_line or not 1 <= min_line <= RECURRENCE_BINS:
+        raise ValueError(f"min_line {min_line} must be a whole number within [1, {RECURRENCE_BINS}]")
+    if int(min_points) != min_points or min_points < 1:
+        raise ValueError(f"min_points {min_points} must be a whole number of at least 1")
+    min_line = int(min_line)
+    lead = c.shape[:-1]
+    flat_c, flat_h = c.reshape(-1, 6).tolist(), h.reshape(-1, RECURRENCE_BINS).tolist()
+    nan = float("nan")
+    out = {k: np.zeros(len(flat_c), np.int64) if k in ("lines", "line_points") else np.full(len(flat_c), nan) for k in RECURRENCE_ROWS}
+    for at, ((points, comparable, recurrent, long_lines, long_points, longest), bins) in enumerate(zip(flat_c, flat_h)):
+        lines, line_points = long_lines, long_points
+        for length in range(min_line, RECURRENCE_BINS + 1):
+            lines += bins[length - 1]
+            line_points += length * bins[length - 1]
+        out["lines"][at] = lines
+        out["line_points"][at] = line_points
+        if points < min_points:
+            continue
+        rate = recurrent / comparable if comparable > 0 else nan
+        det = line_points / recurrent if recurrent > 0 else nan
+        out["recurrence_rate"][at] = rate
+        out["determinism"][at] = det
+        if lines > 0:
+            out["mean_line"][at] = line_points / lines
+            acc = 0.0
+            for k in list(bins[min_line - 1:]) + [long_lines]:
+                if k > 0:
+                    p = k / lines
+                    acc = acc + p * math.log(p)
+            out["line_entropy"][at] = -acc
+        if longest >= min_line:
+            out["longest"][at] = float(longest)
+            out["divergence"][at] = 1.0 / longest
+        if rate > 0:                                          # false for NaN
+            out["ratio"][at] = det / rate
+    return {k: v.reshape(lead) for k, v in out.items()}
+
+
+def gait_recurrence_counts(signals, lengths=None, exclude=None, derivative=1, dim=5, lag=2, theiler=8, radius=0.8, min_line=2, min_points=50):
+    """Rules 1 (from the differencing on) to 7 of DESIGN 4.20 on given signals: the host statement of GRNet.op_gait_recurrence_counts.  signals (n,4)
+    float64, columns RECURRENCE_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count.  Returns {'per_sequence': (n_seq,4,5),
+    columns RECURRENCE_COLUMNS; 'hist': (n_seq,4,255) int64, the lines of length 1 .. 255; 'counts': (n_seq,4,6) int64, columns RECURRENCE_COUNTS; and
+    recurrence_rows' (n_seq,4) arrays}.  Every pair of points is compared, one diagonal j - i at a time; the runs of a diagonal are the differences
+    of its recurrent pairs as a boolean vector padded with a False at either end."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    _recurrence_rule_check(derivative, dim, lag, theiler, radius)
+    _entropy_lengths_check(lengths)
+    d, dim, lag, w, radius = int(derivative), int(dim), int(lag), int(theiler), float(radius)
+    per_seq = np.full((len(lengths), 4, 5), np.nan)
+    hist = np.zeros((len(lengths), 4, RECURRENCE_BINS), np.int64)
+    counts = np.zeros((len(lengths), 4, 6), np.int64)
+    span = (dim - 1) * lag
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            M = max(T - span, 0)
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                y[~np.isfinite(y)] = np.nan
+                ok = np.isfinite(y)
+                count = int(ok.sum())
+                mu = _regularity_sum(y[ok]) / count if count else np.nan
+                e = y[ok] - mu
+                sd = float(np.sqrt(_regularity_sum(e * e) / (count - 1))) if count >= 2 else np.nan
+                r = radius * sd
+                eps2 = (r * r) * float(dim)
+                per_seq[q, ch] = (count, mu, sd, r, eps2)
+                if M == 0:
+                    continue
+                pv = ok[:M].copy()
+                for k in range(1, dim):
+                    pv &= ok[k * lag:k * lag + M]
+                lines = np.zeros(T + 1, np.int64)                 # lines[l]: the lines of length l
+                comparable = recurrent = 0
+                for step in range(w + 1, M):
+                    m = M - step
+                    both = pv[:m] & pv[step:]
+                    comparable += int(both.sum())
+                    if not r > 0:
+                        continue
+                    t = y[:m] - y[step:M]
+                    d2 = t * t
+                    for k in range(1, dim):
+                        t = y[k * lag:k * lag + m] - y[k * lag + step:k * lag + M]
+                        d2 = d2 + t * t
+                    hit = both & (d2 <= eps2) & np.isfinite(d2)       # an infinite distance never recurs, whatever eps2
+                    recurrent += int(hit.sum())
+                    edge = np.diff(np.concatenate([[False], hit, [False]]).astype(np.int8))
+                    lines += np.bincount(np.flatnonzero(edge == -1) - np.flatnonzero(edge == 1), minlength=T + 1)
+                long_at = np.flatnonzero(lines[RECURRENCE_BINS + 1:]) + RECURRENCE_BINS + 1
+                hist[q, ch] = lines[1:RECURRENCE_BINS + 1] if T >= RECURRENCE_BINS else np.pad(lines[1:], (0, RECURRENCE_BINS - T))
+                every = np.flatnonzero(lines)
+                counts[q, ch] = (int(pv.sum()), comparable, recurrent, int(lines[long_at].sum()), int((lines[long_at] * long_at).sum()),
+                                 int(every[-1]) if len(every) else 0)
+            f0 += T
+    out = {"per_sequence": per_seq, "hist": hist, "counts": counts}
+    out.update(recurrence_rows(counts, hist, min_line, min_points))
+    return out
+
+
+def gait_recurrence(joints3d, lengths=None, trans=None, exclude=None, sigma=0.0, derivative=1, dim=5, lag=2, theiler=8, radius=0.8, min_line=2,
+                    min_points=50, joints=GAIT_JOINTS_KINECTV2):
+    """Recurrence quantification of four body signals in numpy float64 and Python integers (Webber and Zbilut 1994, Marwan et al. 2007; Labini et al.
+    2012 and Riva et al. 2013 on trunk sensors over minutes of walking; the rules: DESIGN 4.20; the radius rule is this project's and the defaults are
+    unvalidated on the model's output): the host statement of GRNet.gait_recurrence, same arguments, a dict of numpy arrays.  per_frame (n,4) is
+    gait_regularity's at the same sigma; per_sequence, hist, counts and the rows: gait_recurrence_counts'."""
+    def rule_check():
+        _recurrence_rule_check(derivative, dim, lag, theiler, radius)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check)
+    out = gait_recurrence_counts(per_frame, lengths, exclude, derivative, dim, lag, theiler, radius, min_line, min_points)
+    out["per_frame"] = per_frame
+    return out
+
+
 # ----------------------------------------------------------------------------- the Welch spectrum (DESIGN 4.19)
 SPECTRUM_CHANNELS = REGULARITY_CHANNELS
 SPECTRUM_COLUMNS = ("n", "candidates", "used", "band_power", "total_power", "peak_bin", "peak_hz", "peak_height", "peak_width_hz", "dominance", "centroid_hz",
