@@ -86,6 +86,15 @@ minutes of walking; these are joint positions of a pose model over some 15 strid
 not of the phase-space diameter), and the defaults are unvalidated on the model's output.  With --gait_turns only straight walking counts.
 Reported, never judged.
 
+--gait_coordination (opt-in, needs no --gait) reports arm swing and inter-limb coordination, the first measure here that compares two signals: the
+shoulder and the hip flexion of both sides (--gait_kinematics's angles, read without events), their auto and cross spectra by Welch's segments
+(Carter, Knapp and Nuttall 1973), and at the stride frequency the swing amplitude of every limb, the left / right asymmetry of arms and legs, and for
+the six pairs of limbs the coherence, the phase and its deviation from the expected 0 or 180 degrees (Wagenaar and van Emmerik 2000, Plotnik et al.
+2007, Mirelman et al. 2016).  The device makes the spectra and the rows (GRNet.gait_coordination); the amplitudes and asymmetries are
+pipeline.coordination_rows'.  <outpath>_coordination.json.  These are joint-position angles of a pose model over some 15 strides: with K segments
+the coherence of two unrelated signals is about 1 / K (0.09 at the 11 segments of 400 frames), not 0, and the defaults are unvalidated on the
+model's output.  With --gait_turns a turn splits the walk into straight runs.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -859,11 +868,80 @@ class WindowSpectrum:
         return path
 
 
+class WindowCoordination:
+    """--gait_coordination: one gait_coordination call per database window on rank 0, one sequence per video, on the joints the window's gather left
+    on the device (model.gait_coordination; on_host, or a model without the method: pipeline.gait_coordination after a download) -- with
+    --gait_turns' phase as `exclude` (straight_only): a turn then splits the walk into straight runs, and the segments of all of them are averaged.
+    It needs no events and so no --gait.  Either way the amplitudes, asymmetries and the mean phase deviation are pipeline.coordination_rows' on
+    the limbs' and pairs' rows.  Per video and limb (pipeline.COORDINATION_CHANNELS) the columns of pipeline.COORDINATION_LIMB_COLUMNS and
+    'amplitude'; per pair (pipeline.COORDINATION_PAIR_NAMES) the columns of pipeline.COORDINATION_PAIR_COLUMNS; 'arm_asymmetry', 'leg_asymmetry',
+    'arm_leg_ratio', 'phase_deviation_mean'; the frequency axis 'freqs' in Hz; null where undefined.  The joints are
+    pipeline.KINEMATICS_JOINTS_KINECTV2.  With K segments the coherence of unrelated signals is about 1 / K, not 0; the defaults are unvalidated on
+    the model's output; the results are reported and never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, derivative=0, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0, min_segments=4):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_coordination") else model.gait_coordination
+        self.straight_only = bool(straight_only)
+        self.kw = dict(fps=float(fps), sigma=float(sigma), derivative=int(derivative), segment=int(segment), hop=int(segment) // 2 if hop is None else int(hop), nfft=int(nfft),
+                       f_lo=float(f_lo), f_hi=float(f_hi), min_segments=int(min_segments))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, gait_phase=None):
+        """keys[vi], per_video[vi] (T,75), gait_phase[vi] (T,) of WindowTurns or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_coordination(j3.cpu().numpy(), lengths=lengths, exclude=exclude, **self.kw)
+        out.update(self.pipe.coordination_rows(out["limbs"], out["pairs"]))
+        freqs = [k * self.kw["fps"] / self.kw["nfft"] for k in range(self.kw["nfft"] // 2 + 1)]
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        for q, key in enumerate(keys):
+            video = {"straight_only": straight, "freqs": freqs}
+            for c, name in enumerate(self.pipe.COORDINATION_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.COORDINATION_LIMB_COLUMNS, out["limbs"][q, c])}
+                video[name]["amplitude"] = number(out["amplitude"][q, c])
+            for p, name in enumerate(self.pipe.COORDINATION_PAIR_NAMES):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.COORDINATION_PAIR_COLUMNS, out["pairs"][q, p])}
+            for name in ("arm_asymmetry", "leg_asymmetry", "arm_leg_ratio", "phase_deviation_mean"):
+                video[name] = number(out[name][q])
+            self.videos[key] = video
+            arms, legs = video[self.pipe.COORDINATION_PAIR_NAMES[0]], video[self.pipe.COORDINATION_PAIR_NAMES[1]]
+            print(f"Coordination: video {key}, {int(video['arm_left']['used'])} segments, arm swing {shown(video['arm_left']['amplitude'], '.1f')} (left) and "
+                  f"{shown(video['arm_right']['amplitude'], '.1f', ' degrees')} (right), asymmetry {shown(video['arm_asymmetry'], '.1f', ' %')}; arms: coherence "
+                  f"{shown(arms['coherence_peak'], '.3f')}, {shown(arms['phase_deviation'], '.1f', ' degrees')} off antiphase; legs: coherence "
+                  f"{shown(legs['coherence_peak'], '.3f')}, {shown(legs['phase_deviation'], '.1f', ' degrees')} off antiphase"
+                  f"{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait coordination of {len(self.videos)} videos to {path}.")
+        return path
+
+
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None):
-    """recurrence: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'radius', 'min_line', 'min_points', 'all_frames', 'on_host', 'out'} (each optional;
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None):
+    """coordination: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each
+    optional; needs no gait, whose fps it takes where its own is not given, else 20) -- also the arm swing and inter-limb coordination of every video
+    (WindowCoordination), written to coordination['out'] (default: outpath with _coordination.json); with turns only straight walking counts unless
+    'all_frames'; the database gains nothing.
+    recurrence: {'sigma', 'derivative', 'dim', 'lag', 'theiler', 'radius', 'min_line', 'min_points', 'all_frames', 'on_host', 'out'} (each optional;
     needs no gait) -- also the recurrence quantification of every video (WindowRecurrence), written to recurrence['out'] (default: outpath with
     _recurrence.json); with turns only straight walking counts unless 'all_frames'; the database gains nothing.
     spectrum: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
@@ -989,6 +1067,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     again = WindowRecurrence(pipe, model, recurrence.get("on_host", False), not recurrence.get("all_frames", False),
                              **{k: recurrence[k] for k in ("sigma", "derivative", "dim", "lag", "theiler", "radius", "min_line", "min_points") if recurrence.get(k) is not None}) \
         if recurrence is not None and rank == 0 else None
+    limbs = WindowCoordination(pipe, model, coordination.get("on_host", False), not coordination.get("all_frames", False),
+                               **({"fps": gait["fps"]} if coordination.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
+                               **{k: coordination[k] for k in ("fps", "sigma", "derivative", "segment", "hop", "nfft", "f_lo", "f_hi", "min_segments")
+                                  if coordination.get(k) is not None}) \
+        if coordination is not None and rank == 0 else None
     vidnames = sorted(os.listdir(vid_folder), key=vid_sort_key)
     start, n_done = time.time(), 0
     for (wa, wb) in flush_windows(len(vidnames), pipe.MAX_VID):
@@ -1055,6 +1138,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             bands.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None, steady.videos if steady is not None else None)
         if again is not None and vids:
             again.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
+        if limbs is not None and vids:
+            limbs.add_window([v[0] for v in vids], per_video, gait_phase)
         if rank == 0:
             for vi, (key, _, bboxes, _, status) in enumerate(vids):
                 # the reference's db holds the boxes AFTER Inference scaled w,h by 1.1 in place (batch_generation.py:263-266
@@ -1098,6 +1183,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         bands.write(spectrum.get("out") or osp.splitext(outpath)[0] + "_spectrum.json")
     if again is not None:
         again.write(recurrence.get("out") or osp.splitext(outpath)[0] + "_recurrence.json")
+    if limbs is not None:
+        limbs.write(coordination.get("out") or osp.splitext(outpath)[0] + "_coordination.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -1262,6 +1349,27 @@ def main(argv=None):
     p.add_argument("--recurrence_min_points", type=int, default=None, help="with --gait_recurrence: a video with fewer valid points has no rates, at least 1 (default 50)")
     p.add_argument("--recurrence_all_frames", action="store_true", help="with --gait_recurrence and --gait_turns: count the frames of the turns too")
     p.add_argument("--recurrence_on_host", action="store_true", help="with --gait_recurrence: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_coordination", action="store_true", help="with --vid_folder (no --gait needed): arm swing and inter-limb coordination from the shoulder and hip flexion "
+                   "of both sides -- per limb the swing amplitude in the band --coordination_f_lo to --coordination_f_hi, the left / right asymmetry of arms and legs, and per "
+                   "pair of limbs the coherence, the phase and its deviation from the expected 0 or 180 degrees at the stride frequency (Carter et al. 1973, Wagenaar and van "
+                   "Emmerik 2000, Plotnik et al. 2007, Mirelman et al. 2016): <outpath>_coordination.json, one line per video; in Hz through --gait_fps where given, else at 20 "
+                   "frames a second; with --gait_turns only straight walking counts; these are joint-position angles of a pose model over some 15 strides: with K segments "
+                   "the coherence of two unrelated signals is about 1 / K (0.09 at the 11 segments of 400 frames), not 0, and with one segment it is identically 1; the "
+                   "defaults are unvalidated on the model's output, and the numbers are reported, never judged")
+    p.add_argument("--coordination_out", type=str, default="", help="with --gait_coordination: the JSON file (default: --outpath with _coordination.json)")
+    p.add_argument("--coordination_sigma", type=float, default=None, help="with --gait_coordination: sigma in frames of the Gaussian over the four angles, 0 (none) to 16 (default 0)")
+    p.add_argument("--coordination_derivative", type=int, default=None, help="with --gait_coordination: 0 the angle, so that amplitudes are degrees, 1 its velocity, 2 its "
+                   "acceleration (default 0)")
+    p.add_argument("--coordination_segment", type=int, default=None, help="with --gait_coordination: the frames of a segment, even, 8 to 256 (default 64)")
+    p.add_argument("--coordination_hop", type=int, default=None, help="with --gait_coordination: the frames between two segments, an eighth of a segment to a whole one (default half)")
+    p.add_argument("--coordination_nfft", type=int, default=None, help="with --gait_coordination: the points of the zero-padded transform, even, a segment to 1024 (default 256)")
+    p.add_argument("--coordination_f_lo", type=float, default=None, help="with --gait_coordination: the band's lower edge in Hz, above 0 (default 0.5)")
+    p.add_argument("--coordination_f_hi", type=float, default=None, help="with --gait_coordination: the band's upper edge in Hz, above --coordination_f_lo and at most half the "
+                   "frames a second (default 3.0)")
+    p.add_argument("--coordination_min_segments", type=int, default=None, help="with --gait_coordination: a video with fewer segments has no spectra, at least 2 -- the coherence "
+                   "of one segment is 1 whatever the signals are (default 4)")
+    p.add_argument("--coordination_all_frames", action="store_true", help="with --gait_coordination and --gait_turns: count the frames of the turns too")
+    p.add_argument("--coordination_on_host", action="store_true", help="with --gait_coordination: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--outpath", type=str, default=f"data/{time.strftime('%Y%m%d-%H%M%S')}.json")
     p.add_argument("--pretrained_file", type=str, default="checkpoint/max-grnet.pth.tar")
     p.add_argument("--synthetic_weights", action="store_true")
@@ -1298,7 +1406,7 @@ def main(argv=None):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     for flag, given in (("--gait_out", bool(a.gait_out)), ("--gait_fps", a.gait_fps is not None), ("--gait_sigma", a.gait_sigma is not None),
                         ("--gait_window", a.gait_window is not None), ("--gait_min_excursion", a.gait_min_excursion is not None), ("--gait_on_host", a.gait_on_host)):
-        if given and not a.gait and not (flag == "--gait_fps" and (a.gait_regularity or a.gait_spectrum)):
+        if given and not a.gait and not (flag == "--gait_fps" and (a.gait_regularity or a.gait_spectrum or a.gait_coordination)):
             sys.exit(f"batch_generation.py: {flag} belongs to --gait, which was not given")
     if a.gait and not a.vid_folder:
         sys.exit("batch_generation.py: --gait needs --vid_folder (the frames whose joints it reads)")
@@ -1477,6 +1585,34 @@ def main(argv=None):
             sys.exit("batch_generation.py: --spectrum_f_lo and --spectrum_f_hi must obey 0 < f_lo < f_hi <= half the frames a second")
         if a.spectrum_min_segments is not None and a.spectrum_min_segments < 1:
             sys.exit("batch_generation.py: --spectrum_min_segments must be at least 1")
+    for flag, given in (("--coordination_out", bool(a.coordination_out)), ("--coordination_sigma", a.coordination_sigma is not None),
+                        ("--coordination_derivative", a.coordination_derivative is not None), ("--coordination_segment", a.coordination_segment is not None),
+                        ("--coordination_hop", a.coordination_hop is not None), ("--coordination_nfft", a.coordination_nfft is not None),
+                        ("--coordination_f_lo", a.coordination_f_lo is not None), ("--coordination_f_hi", a.coordination_f_hi is not None),
+                        ("--coordination_min_segments", a.coordination_min_segments is not None), ("--coordination_all_frames", a.coordination_all_frames),
+                        ("--coordination_on_host", a.coordination_on_host)):
+        if given and not a.gait_coordination:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_coordination, which was not given")
+    if a.gait_coordination and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_coordination needs --vid_folder (the frames whose joints it reads)")
+    if a.coordination_sigma is not None and not (np.isfinite(a.coordination_sigma) and 0 <= a.coordination_sigma <= 16):
+        sys.exit("batch_generation.py: --coordination_sigma must be within 0 to 16")
+    if a.coordination_derivative is not None and not 0 <= a.coordination_derivative <= 2:
+        sys.exit("batch_generation.py: --coordination_derivative must be 0, 1 or 2")
+    if a.gait_coordination:
+        seg = 64 if a.coordination_segment is None else a.coordination_segment
+        if not 8 <= seg <= 256 or seg % 2:
+            sys.exit("batch_generation.py: --coordination_segment must be even and within 8 to 256")
+        if a.coordination_hop is not None and not seg // 8 <= a.coordination_hop <= seg:
+            sys.exit("batch_generation.py: --coordination_hop must be within an eighth of --coordination_segment to the whole of it")
+        nfft = 256 if a.coordination_nfft is None else a.coordination_nfft
+        if not seg <= nfft <= 1024 or nfft % 2:
+            sys.exit("batch_generation.py: --coordination_nfft must be even and within --coordination_segment to 1024")
+        f_lo, f_hi = 0.5 if a.coordination_f_lo is None else a.coordination_f_lo, 3.0 if a.coordination_f_hi is None else a.coordination_f_hi
+        if not (np.isfinite(f_lo) and np.isfinite(f_hi) and 0 < f_lo < f_hi <= (20.0 if a.gait_fps is None else a.gait_fps) / 2):
+            sys.exit("batch_generation.py: --coordination_f_lo and --coordination_f_hi must obey 0 < f_lo < f_hi <= half the frames a second")
+        if a.coordination_min_segments is not None and not 2 <= a.coordination_min_segments <= 2 ** 20:
+            sys.exit("batch_generation.py: --coordination_min_segments must be at least 2 (the coherence of one segment is 1 whatever the signals are)")
     for flag, given in (("--recurrence_out", bool(a.recurrence_out)), ("--recurrence_sigma", a.recurrence_sigma is not None), ("--recurrence_derivative", a.recurrence_derivative is not None),
                         ("--recurrence_dim", a.recurrence_dim is not None), ("--recurrence_lag", a.recurrence_lag is not None), ("--recurrence_radius", a.recurrence_radius is not None),
                         ("--recurrence_theiler", a.recurrence_theiler is not None), ("--recurrence_min_line", a.recurrence_min_line is not None),
@@ -1543,6 +1679,9 @@ def main(argv=None):
     recurrence = {"sigma": a.recurrence_sigma, "derivative": a.recurrence_derivative, "dim": a.recurrence_dim, "lag": a.recurrence_lag, "theiler": a.recurrence_theiler,
                   "radius": a.recurrence_radius, "min_line": a.recurrence_min_line, "min_points": a.recurrence_min_points, "all_frames": a.recurrence_all_frames,
                   "on_host": a.recurrence_on_host, "out": a.recurrence_out or None} if a.gait_recurrence else None
+    coordination = {"fps": a.gait_fps, "sigma": a.coordination_sigma, "derivative": a.coordination_derivative, "segment": a.coordination_segment, "hop": a.coordination_hop,
+                    "nfft": a.coordination_nfft, "f_lo": a.coordination_f_lo, "f_hi": a.coordination_f_hi, "min_segments": a.coordination_min_segments,
+                    "all_frames": a.coordination_all_frames, "on_host": a.coordination_on_host, "out": a.coordination_out or None} if a.gait_coordination else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
@@ -1550,7 +1689,8 @@ def main(argv=None):
                  **({"contacts": contacts} if contacts is not None else {}), **({"regularity": regularity} if regularity is not None else {}),
                  **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
                  **({"stability": stability} if stability is not None else {}),
-                 **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}))
+                 **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}),
+                 **({"coordination": coordination} if coordination is not None else {}))
 
 
 if __name__ == "__main__":

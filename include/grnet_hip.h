@@ -924,6 +924,45 @@ int grnet_op_gait_welch(grnet_t* h, const double* signals_dev, const int32_t* ex
                         int derivative, int segment, int hop, int nfft, double f_lo, double f_hi, int min_segments, double* psd_dev, double* per_seq_dev,
                         void* stream);
 
+/* Arm swing and inter-limb coordination (the magnitude-squared coherence by Welch's overlapped segments of Carter, Knapp and Nuttall 1973; on arms
+ * and legs in gait Wagenaar and van Emmerik 2000, Plotnik et al. 2007, Mirelman et al. 2016 -- these signals are joint-position angles of a pose
+ * model over some 15 strides: with K segments the coherence of two unrelated signals is about 1 / K, 0.09 at the 11 segments of 400 frames, and with
+ * one segment it is identically 1; the defaults are unvalidated on the model's output and the numbers are reported, never judged): the auto and
+ * cross spectra of four limb angles and the rows read off them (which is the specification).  joints3d_dev, frame_offsets_host and
+ * exclude_dev as grnet_gait_spectrum takes them, joints_host the 16 indices of grnet_gait_kinematics.  Float64 with one rounding per operation; sine,
+ * cosine and arctangent are the library's own (no libm); every test is a comparison, false for NaN:
+ *   signals  arm_left, arm_right, leg_left, leg_right in degrees: the shoulder and the hip flexion of grnet_gait_kinematics, its per-frame
+ *            columns 8, 9, 0 and 1 in every bit at the same sigma (default 0).
+ *   y        each signal differenced `derivative` times (default 0: amplitudes are degrees).  A frame counts iff ALL FOUR values are finite and
+ *            exclude is 0: one mask for the call, so every limb and every pair is estimated on the same segments.  n = such frames.
+ *   segments grnet_gait_spectrum's rule on that one mask: `segment`, `hop`, candidates, used (0 below min_segments, which is 2 .. 2^20, default 4).
+ *   bin      per channel c the segment's C_c and S_c as grnet_gait_spectrum makes them; over the segments in order from +0.0: A_c += C_c C_c + S_c
+ *            S_c and, for the pairs (a, b) = (0,1), (2,3), (0,3), (1,2), (0,2), (1,3): Re += C_a C_b + S_a S_b, Im += S_a C_b - C_a S_b -- the
+ *            sign of scipy.signal.csd(a, b), conj(X_a) X_b: a positive phase means b leads a.  Every sum is scaled as P(k) is, the sign passes.
+ *   limbs    grnet_gait_spectrum's thirteen columns of each auto row; cadence = 120 peak_hz (a limb swings once a stride).
+ *   pairs    used; peak_bin: the bin of [f_lo, f_hi] with the largest positive finite M2 = Re Re + Im Im, the smallest k of a tie (NaN of none, and
+ *            every column behind it); peak_hz = (k fps) / nfft; cross_amplitude = sqrt(M2); coherence_peak = M2 / (P_aa P_bb) where the product
+ *            is positive and finite, NOT clamped; phase_peak = atan2(Im, Re) in degrees; phase_deviation = |phase| for an arm with the other
+ *            side's leg (pairs 2 and 3), |180 - |phase|| for the four pairs expected in antiphase; lag_seconds = phase_peak / (360 peak_hz);
+ *            coherence_band: the mean of the defined coherences over the band's bins in rising k from +0.0; coherence_bins: their number.
+ * THE REST IS THE CALLER'S (as the Python layer does it, pipeline.coordination_rows): amplitude = sqrt(2 band_power) per limb, arm and leg
+ * asymmetry = 100 |L - R| / (0.5 (L + R)), arm_leg_ratio = (0.5 (arm_left + arm_right)) / (0.5 (leg_left + leg_right)), phase_deviation_mean over
+ * the pairs where it is defined; NaN where a denominator is not positive.
+ * per_frame_dev (sum T, 4) float64.  auto_dev (n_seq, 4, nfft / 2 + 1).  cross_dev (n_seq, 6, nfft / 2 + 1, 2): Re, Im.  limbs_dev (n_seq, 4, 13).
+ * pairs_dev (n_seq, 6, 10).  One wave per (sequence, block of 64 bins), a lane per bin for all four channels and all six pairs, the signals, the
+ * tables and the segments in LDS; then a wave per (sequence, row); no atomics, nothing added across lanes: a sequence's outputs have the same bits
+ * alone or among others.  Needs no weights.  At most four launches (three with sigma = 0) behind one small copy from pinned memory; no host
+ * synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): what grnet_gait_spectrum refuses, with the 16-joint table and
+ * min_segments outside [2, 2^20] (one segment is refused by the rule).  Nothing is refused on the data.
+ * grnet_op_gait_cross_welch: y, the densities and the rows alone (test hook) on signals_dev float64 (sum T, 4). */
+int grnet_gait_coordination(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                            const int32_t* exclude_dev, double fps, double sigma, int derivative, int segment, int hop, int nfft, double f_lo, double f_hi,
+                            int min_segments, double* per_frame_dev, double* auto_dev, double* cross_dev, double* limbs_dev, double* pairs_dev, void* stream);
+int grnet_op_gait_cross_welch(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                              int derivative, int segment, int hop, int nfft, double f_lo, double f_hi, int min_segments, double* auto_dev,
+                              double* cross_dev, double* limbs_dev, double* pairs_dev, void* stream);
+
 /* Recurrence quantification of the same four body signals (Webber and Zbilut 1994; Marwan et al. 2007; on gait Labini et al. 2012 and Riva et al.
  * 2013 -- on a trunk sensor over minutes of walking; these signals are joint positions of a pose model over some 15 strides, the radius rule is this
  * project's and the defaults are unvalidated on its output): every pair of points of the delay-embedded signal against one radius, and the runs of

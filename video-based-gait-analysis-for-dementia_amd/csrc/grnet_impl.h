@@ -20,6 +20,7 @@
 //   grnet_stability.cpp local dynamic stability: grnet_gait_stability and its divergence hook
 //   grnet_spectrum.cpp the Welch spectrum: grnet_gait_spectrum and its density hook
 //   grnet_recurrence.cpp recurrence quantification: grnet_gait_recurrence and its counting hook
+//   grnet_coordination.cpp arm swing and inter-limb coordination: grnet_gait_coordination and its cross-spectrum hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

@@ -499,6 +499,19 @@ int spec_bin_blocks(int nfft);             // the grid's z: blocks of kSpecThrea
 hipError_t launch_spec_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
                                  double* mu_long, double* psd, double* per_seq, hipStream_t s);
 
+// Arm swing and inter-limb coordination: auto and cross spectra of the two shoulder and the two hip flexions (csrc/gait_coordination_kernels.hip,
+// compiled without fma contraction; the arithmetic: csrc/gait_coordination.h).  The workgroup is gait_spectrum's wave of kSpecThreads ----
+constexpr int kCoordLdsFrames = 1024;      // frames of a sequence whose four differenced columns the workgroup keeps in LDS (more: the call's scratch)
+constexpr int kCoordLdsSegments = 128;     // segments of a sequence whose starts and four means each the workgroup keeps in LDS (more: the call's scratch)
+// one lane per frame: arm_left, arm_right, leg_left, leg_right into per_frame (frames,4), or, raw not null (a Gaussian follows), into raw (4,frames)
+hipError_t launch_coord_frames(const float* joints, int J, int frames, const KinTable& tab, double* raw, double* per_frame, hipStream_t s);
+// two launches on rows (frames,4) and exclude (frames) or null: a wave per (sequence, block of bins) makes au (n_seq,4,nfft/2+1), cr
+// (n_seq,6,nfft/2+1,2) and the first columns of limbs (n_seq,4,13) and pairs (n_seq,6,10); a wave per (sequence, row) the others.  y_long:
+// (spec_bin_blocks * 4 * frames) float64 where a sequence has more than kCoordLdsFrames frames, else null; start_long (spec_bin_blocks * frames) int32
+// and mu_long (spec_bin_blocks * 4 * frames) float64 where a sequence can hold more than kCoordLdsSegments segments, else null
+hipError_t launch_coord_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
+                                  double* mu_long, double* au, double* cr, double* limbs, double* pairs, hipStream_t s);
+
 // Recurrence quantification of the same four signals (csrc/gait_recurrence_kernels.hip, compiled without fma contraction; the arithmetic:
 // csrc/gait_recurrence.h).  The frame kernel is launch_reg_frames ----
 struct RecRule;                            // gait_recurrence.h: derivative, dim, lag, theiler, radius

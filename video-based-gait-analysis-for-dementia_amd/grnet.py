@@ -1615,6 +1615,64 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_welch")
         return out
 
+    # ------------------------------------------------------------------ arm swing and inter-limb coordination
+    def _coordination_call(self, n, lengths, exclude, derivative, segment, hop, nfft, min_segments, what):
+        """(exclude on the device or None, offsets, hop, the auto, cross, limbs and pairs tensors) of gait_coordination and its hook."""
+        if hop is None:
+            hop = segment // 2 if int(segment) == segment else segment
+        self._whole_frames(derivative=derivative, segment=segment, hop=hop, nfft=nfft, min_segments=min_segments)
+        if not 8 <= int(nfft) <= 1024 or int(nfft) % 2:             # the sizes of auto and cross are made of it here
+            raise ValueError("nfft must be even and within [segment, 1024]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq, bins = len(off) - 1, int(nfft) // 2 + 1
+        out = {"auto": torch.empty(n_seq, 4, bins, dtype=torch.float64, device=self.device),
+               "cross": torch.empty(n_seq, 6, bins, 2, dtype=torch.float64, device=self.device),
+               "limbs": torch.empty(n_seq, 4, 13, dtype=torch.float64, device=self.device),
+               "pairs": torch.empty(n_seq, 6, 10, dtype=torch.float64, device=self.device)}
+        return ex, off, int(hop), out
+
+    def gait_coordination(self, joints3d, lengths=None, exclude=None, fps=20.0, sigma=0.0, derivative=0, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0,
+                          min_segments=4, joints=_lib.KINEMATICS_JOINTS_KINECTV2):
+        """Arm swing and inter-limb coordination of every sequence, on the device (grnet_gait_coordination; the rules, channels, pairs and columns:
+        DESIGN 4.21, pipeline.COORDINATION_CHANNELS, COORDINATION_PAIRS, COORDINATION_LIMB_COLUMNS, COORDINATION_PAIR_COLUMNS).  joints3d, lengths,
+        exclude and joints (16 indices) as gait_kinematics and gait_spectrum take them.  The shoulder flexion left / right and the hip flexion left /
+        right in degrees, gait_kinematics's bits at the same sigma (0: none, the default; <= 16), are differenced `derivative` times (0 .. 2; 0:
+        amplitudes are degrees); a frame counts iff all four values are finite, so every limb and pair is estimated on the same segments, laid,
+        windowed and transformed as gait_spectrum's (`segment`, `hop`, `nfft`); fewer than min_segments (2 .. 2^20) give NaN, and one segment is
+        refused because its coherence is 1 whatever the signals are.  Returns a dict of device tensors: per_frame (n,4) float64; auto
+        (n_seq,4,nfft/2+1) densities; cross (n_seq,6,nfft/2+1,2), real and imaginary part of conj(X_a) X_b, scipy.signal.csd(a, b)'s sign: a
+        positive phase means b leads a; limbs (n_seq,4,13), gait_spectrum's columns with cadence = 120 peak_hz; pairs (n_seq,6,10): at the bin of
+        [f_lo, f_hi] with the largest cross magnitude its frequency, magnitude, coherence (not clamped), phase in degrees, the phase's deviation
+        from the expected 0 or 180, the lag in seconds, and the band's mean coherence.  The amplitudes and asymmetries are
+        pipeline.coordination_rows(limbs, pairs), on the host.  With K segments the coherence of unrelated signals is about 1 / K (0.09 at the 11
+        segments of 400 frames), not 0; the defaults are unvalidated on the model's output, and the numbers are reported, never judged.  A sequence
+        has at most 32 768 frames.  Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.KINEMATICS_JOINTS_KINECTV2, _KIN_JOINT_NAMES)
+        ex, off, hop, out = self._coordination_call(n, lengths, exclude, derivative, segment, hop, nfft, min_segments, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_coordination(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if ex is None else ex.data_ptr(),
+                                               float(fps), float(sigma), int(derivative), int(segment), hop, int(nfft), float(f_lo), float(f_hi),
+                                               int(min_segments), out["per_frame"].data_ptr(), out["auto"].data_ptr(), out["cross"].data_ptr(),
+                                               out["limbs"].data_ptr(), out["pairs"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_coordination")
+        return out
+
+    def op_gait_cross_welch(self, signals, lengths=None, exclude=None, fps=20.0, derivative=0, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0,
+                            min_segments=4):
+        """Rules 2 to 7 of gait_coordination alone (grnet_op_gait_cross_welch): signals (n,4) float64 and exclude (n,) or None, one sequence or
+        `lengths` of them lying back to back -> {auto, cross, limbs, pairs} on the device."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, hop, out = self._coordination_call(x.shape[0], lengths, exclude, derivative, segment, hop, nfft, min_segments, "signals")
+        rc = self._lib.grnet_op_gait_cross_welch(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps),
+                                                 int(derivative), int(segment), hop, int(nfft), float(f_lo), float(f_hi), int(min_segments),
+                                                 out["auto"].data_ptr(), out["cross"].data_ptr(), out["limbs"].data_ptr(), out["pairs"].data_ptr(),
+                                                 self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_cross_welch")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

@@ -2548,6 +2548,225 @@ def gait_spectrum(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, si
     return out
 
 
+# ----------------------------------------------------------------------------- arm swing and inter-limb coordination
+COORDINATION_CHANNELS = ("arm_left", "arm_right", "leg_left", "leg_right")      # gait_kinematics's channels 8, 9, 0, 1: shoulder and hip flexion
+COORDINATION_KINEMATICS_COLUMNS = (8, 9, 0, 1)
+COORDINATION_PAIRS = ((0, 1), (2, 3), (0, 3), (1, 2), (0, 2), (1, 3))
+COORDINATION_PAIR_NAMES = ("arm_left__arm_right", "leg_left__leg_right", "arm_left__leg_right", "arm_right__leg_left", "arm_left__leg_left",
+                           "arm_right__leg_right")
+COORDINATION_EXPECTED_PHASE = (180.0, 180.0, 0.0, 0.0, 180.0, 180.0)          # degrees: an arm swings with the other side's leg
+COORDINATION_LIMB_COLUMNS = SPECTRUM_COLUMNS
+COORDINATION_PAIR_COLUMNS = ("used", "peak_bin", "peak_hz", "cross_amplitude", "coherence_peak", "phase_peak", "phase_deviation", "lag_seconds",
+                             "coherence_band", "coherence_bins")
+COORDINATION_ROWS = ("amplitude", "arm_asymmetry", "leg_asymmetry", "arm_leg_ratio", "phase_deviation_mean")
+COORDINATION_MAX_FRAMES = ENTROPY_MAX_FRAMES
+
+
+def _coordination_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments):
+    """The refusals of csrc/gait_coordination.h's coord_rule_error, in its words: spec_rule_error's, and one segment is refused."""
+    _spectrum_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, 2)
+    if int(min_segments) != min_segments:
+        raise ValueError("derivative, segment, hop, nfft and min_segments must be whole numbers")
+    if not 2 <= min_segments <= 2 ** 20:
+        raise ValueError("min_segments outside [2, 2^20]")
+
+
+def _coordination_pair_row(Paa, Pbb, Re, Im, fps, nfft, f_lo, f_hi, antiphase, used):
+    """coord_pair_row on Python floats, one operation at a time in the header's order."""
+    nan = float("nan")
+    out = [float(used)] + [nan] * 9
+    if used < 1:
+        return out
+    fps, N = float(fps), float(nfft)
+    k_lo, k_hi = _spectrum_band(fps, nfft, f_lo, f_hi)
+    best, bins, top, total = -1, 0, 0.0, 0.0
+    for k in range(k_lo, k_hi + 1):
+        re, im = float(Re[k]), float(Im[k])
+        m2, den = re * re + im * im, float(Paa[k]) * float(Pbb[k])
+        if m2 > 0.0 and math.isfinite(m2) and (best < 0 or m2 > top):
+            best, top = k, m2
+        if den > 0.0 and math.isfinite(den):
+            total = total + m2 / den
+            bins += 1
+    if best < 0:
+        return out
+    hz, den = (float(best) * fps) / N, float(Paa[best]) * float(Pbb[best])
+    phase = float(gait_atan2(float(Im[best]), float(Re[best]))) * KINEMATICS_DEGREES
+    out[1], out[2], out[3] = float(best), hz, math.sqrt(top)
+    if den > 0.0 and math.isfinite(den):
+        out[4] = top / den
+    out[5] = phase
+    out[6] = abs(180.0 - abs(phase)) if antiphase else abs(phase)
+    out[7] = phase / (360.0 * hz)
+    if bins > 0:
+        out[8] = total / float(bins)
+    out[9] = float(bins)
+    return out
+
+
+def coordination_rows(limbs, pairs):
+    """Rule 8 of DESIGN 4.21, the one function the device path and the host path call: limbs (..., 4, 13) and pairs (..., 6, 10), from the device or
+    from gait_cross_welch -> {'amplitude': (..., 4) = sqrt(2 band_power), the amplitude of the sinusoid with the band's power (degrees at derivative
+    0); 'arm_asymmetry', 'leg_asymmetry': (...) = 100 |L - R| / (0.5 (L + R)); 'arm_leg_ratio': (...) = (0.5 (arm_left + arm_right)) / (0.5
+    (leg_left + leg_right)); 'phase_deviation_mean': (...) over the pairs whose phase_deviation is defined}.  NaN where a denominator is not positive."""
+    L, P = np.asarray(limbs, np.float64), np.asarray(pairs, np.float64)
+    if L.ndim < 2 or L.shape[-2:] != (4, len(COORDINATION_LIMB_COLUMNS)) or P.shape != L.shape[:-2] + (6, len(COORDINATION_PAIR_COLUMNS)):
+        raise ValueError(f"limbs must be (..., 4, 13) and pairs (..., 6, 10) of the same sequences, got {L.shape} and {P.shape}")
+    lead = L.shape[:-2]
+    flat_l, flat_p = L.reshape(-1, 4, L.shape[-1]), P.reshape(-1, 6, P.shape[-1])
+    n = flat_l.shape[0]
+    amp, arm, leg, ratio, dev = np.full((n, 4), np.nan), np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan)
+    for e in range(n):
+        a = [math.sqrt(2.0 * float(v)) if float(v) >= 0.0 else float("nan") for v in flat_l[e, :, 3]]
+        amp[e] = a
+        den_arm, den_leg = 0.5 * (a[0] + a[1]), 0.5 * (a[2] + a[3])
+        if den_arm > 0.0:
+            arm[e] = (100.0 * abs(a[0] - a[1])) / den_arm
+        if den_leg > 0.0:
+            leg[e] = (100.0 * abs(a[2] - a[3])) / den_leg
+            ratio[e] = den_arm / den_leg
+        total, count = 0.0, 0
+        for v in flat_p[e, :, 6].tolist():
+            if not math.isnan(v):
+                total, count = total + v, count + 1
+        if count > 0:
+            dev[e] = total / float(count)
+    return {"amplitude": amp.reshape(lead + (4,)), "arm_asymmetry": arm.reshape(lead), "leg_asymmetry": leg.reshape(lead), "arm_leg_ratio": ratio.reshape(lead),
+            "phase_deviation_mean": dev.reshape(lead)}
+
+
+def gait_cross_welch(signals, lengths=None, exclude=None, fps=20.0, derivative=0, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0, min_segments=4):
+    """Rules 2 to 8 of DESIGN 4.21 on given signals: the host statement of GRNet.op_gait_cross_welch.  signals (n,4) float64, columns
+    COORDINATION_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count; hop None: segment / 2.  A frame counts iff all four
+    differenced values are finite: ONE mask, so every limb and every pair is estimated on the same segments.  Returns {'auto': (n_seq,4,nfft/2+1)
+    densities, 'cross': (n_seq,6,nfft/2+1,2) real and imaginary part of conj(X_a) X_b (scipy.signal.csd(a, b)'s sign: a positive phase means b leads
+    a) of COORDINATION_PAIRS, 'limbs': (n_seq,4,13), columns COORDINATION_LIMB_COLUMNS, 'pairs': (n_seq,6,10), columns COORDINATION_PAIR_COLUMNS,
+    'freqs': (nfft/2+1,), and coordination_rows' values}.  Every sum in rising index from +0.0, the twiddles harmonics_twiddles' at (k i) mod nfft."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+    _coordination_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+    _entropy_lengths_check(lengths)
+    fps, d, L, hop, N, min_segments = float(fps), int(derivative), int(segment), int(hop), int(nfft), int(min_segments)
+    half = N // 2
+    sn, cs = harmonics_twiddles(N)
+    w = 0.5 - 0.5 * harmonics_twiddles(L)[1]
+    W2 = float(np.cumsum(np.concatenate([[0.0], w * w]))[-1])
+    kk = np.arange(half + 1, dtype=np.int64)
+    g = np.where((kk > 0) & (kk < half), 2.0, 1.0)
+    n_seq = len(lengths)
+    auto, cross = np.full((n_seq, 4, half + 1), np.nan), np.full((n_seq, 6, half + 1, 2), np.nan)
+    limbs, pairs = np.full((n_seq, 4, len(COORDINATION_LIMB_COLUMNS)), np.nan), np.full((n_seq, 6, len(COORDINATION_PAIR_COLUMNS)), np.nan)
+
+    def total(values):
+        return np.cumsum(np.concatenate([np.zeros((1, half + 1)), values], axis=0), axis=0)[-1]
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            ys = []
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                ys.append(y)
+            ok = np.isfinite(ys[0]) & np.isfinite(ys[1]) & np.isfinite(ys[2]) & np.isfinite(ys[3])
+            edges = np.flatnonzero(np.diff(np.concatenate([[False], ok, [False]]).astype(np.int8)))
+            starts = [t0 for a, e in zip(edges[0::2], edges[1::2]) for t0 in range(int(a), int(e) - L + 1, hop)]
+            candidates = len(starts)
+            used = candidates if candidates >= min_segments else 0
+            if used:
+                C, S = [], []
+                for ch in range(4):
+                    seg = ys[ch][np.asarray(starts)[:, None] + np.arange(L)[None, :]]
+                    mu = np.cumsum(np.concatenate([np.zeros((used, 1)), seg], axis=1), axis=1)[:, -1] / float(L)
+                    v = (seg - mu[:, None]) * w[None, :]
+                    Cc, Sc = np.zeros((used, half + 1)), np.zeros((used, half + 1))
+                    for i in range(L):
+                        j = (kk * i) % N
+                        Cc = Cc + v[:, i, None] * cs[j][None, :]
+                        Sc = Sc + v[:, i, None] * sn[j][None, :]
+                    C.append(Cc)
+                    S.append(Sc)
+                    auto[q, ch] = (g * total(Cc * Cc + Sc * Sc)) / ((float(used) * fps) * W2)
+                for p, (a, b) in enumerate(COORDINATION_PAIRS):
+                    cross[q, p, :, 0] = (g * total(C[a] * C[b] + S[a] * S[b])) / ((float(used) * fps) * W2)
+                    cross[q, p, :, 1] = (g * total(S[a] * C[b] - C[a] * S[b])) / ((float(used) * fps) * W2)
+            for ch in range(4):
+                limbs[q, ch] = _spectrum_row(auto[q, ch], fps, N, f_lo, f_hi, True, int(ok.sum()), candidates, used)
+            for p, (a, b) in enumerate(COORDINATION_PAIRS):
+                pairs[q, p] = _coordination_pair_row(auto[q, a], auto[q, b], cross[q, p, :, 0], cross[q, p, :, 1], fps, N, f_lo, f_hi,
+                                                     COORDINATION_EXPECTED_PHASE[p] == 180.0, used)
+            f0 += T
+    out = {"auto": auto, "cross": cross, "limbs": limbs, "pairs": pairs, "freqs": (np.arange(half + 1, dtype=np.float64) * fps) / float(N)}
+    out.update(coordination_rows(limbs, pairs))
+    return out
+
+
+def _coordination_signals(joints3d, lengths, sigma, joints, rule_check):
+    """(the sequences' lengths, per_frame (n,4)) of gait_coordination: rule 1 of DESIGN 4.21, gait_kinematics's operations for its channels 8, 9, 0
+    and 1 alone.  rule_check() refuses the caller's own scalars, behind the joint table and before sigma, as the C ABI does."""
+    j3 = _widened(joints3d, "joints3d")
+    n, J = j3.shape[:2]
+    lengths = _sequence_lengths(n, lengths)
+    tab = _joint_table(joints, 16, J, _KIN_JOINT_NAMES)
+    rule_check()
+    _sigma_check(sigma)
+    p = [j3[:, i] for i in tab]
+    per_frame = np.full((n, 4), np.nan)
+    with np.errstate(all="ignore"):
+        l, u = p[2] - p[3], p[1] - p[0]
+        c = _kin_cross(l, u)
+        nc, nl = np.sqrt(_kin_dot(c, c)), np.sqrt(_kin_dot(l, l))
+        valid = (nc > 0) & np.isfinite(nc) & (nl > 0) & np.isfinite(nl)
+        f, side = c / np.where(valid, nc, 1.0)[:, None], l / np.where(valid, nl, 1.0)[:, None]
+        w = _kin_cross(f, side)
+        for s in (0, 1):
+            d, arm = p[4 + s] - p[2 + s], p[12 + s] - p[10 + s]
+            per_frame[:, 0 + s] = np.where(valid, gait_atan2(_kin_dot(arm, f), -_kin_dot(arm, w)) * KINEMATICS_DEGREES, np.nan)
+            per_frame[:, 2 + s] = np.where(valid, gait_atan2(_kin_dot(d, f), -_kin_dot(d, w)) * KINEMATICS_DEGREES, np.nan)
+        if sigma > 0:
+            a = 0
+            for T in lengths:
+                for k in range(4):
+                    per_frame[a:a + T, k] = gauss_filter1d(per_frame[a:a + T, k].copy(), sigma)
+                a += T
+    return lengths, per_frame
+
+
+def gait_coordination(joints3d, lengths=None, exclude=None, fps=20.0, sigma=0.0, derivative=0, segment=64, hop=None, nfft=256, f_lo=0.5, f_hi=3.0,
+                      min_segments=4, joints=KINEMATICS_JOINTS_KINECTV2):
+    """Arm swing and inter-limb coordination in numpy float64 (Carter, Knapp and Nuttall 1973 on the coherence by Welch's segments; Wagenaar and van
+    Emmerik 2000, Plotnik et al. 2007 and Mirelman et al. 2016 on arms and legs in gait; the rules: DESIGN 4.21): the host statement of
+    GRNet.gait_coordination, same arguments, a dict of numpy arrays.  per_frame (n,4): shoulder flexion left / right and hip flexion left / right in
+    degrees, the bits of gait_kinematics's per_frame[:, (8, 9, 0, 1)] at the same sigma; auto, cross, limbs, pairs, freqs and the host rows:
+    gait_cross_welch's.  The signals are joint-position angles of a pose model over some 15 strides: with K segments the coherence of two unrelated
+    signals is about 1 / K (0.09 at the 11 segments of 400 frames), not 0.  The defaults are unvalidated on the model's output; the numbers are
+    reported, never judged."""
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+
+    def rule_check():
+        _coordination_rule_check(fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _coordination_signals(joints3d, lengths, sigma, joints, rule_check)
+    out = gait_cross_welch(per_frame, lengths, exclude, fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
+    out["per_frame"] = per_frame
+    return out
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
