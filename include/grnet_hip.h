@@ -279,6 +279,16 @@ int grnet_op_conv2d_adds(grnet_t* h, const float* in_dev, int n, int cin, int hg
                          float* out_dev, int tile_hint, void* stream);
 /* (a bf16 handle runs the bf16 path's NHWC kernel between two layout conversions: c a multiple of 8) */
 int grnet_op_bilinear2x(grnet_t* h, const float* in_dev, int n, int c, int hgt, int wid, float* out_dev, void* stream);
+/* The attention pooling alone -- KeypointAttention.forward, lib/models/layers/keypoint_attention.py:42-48 (softmax of every joint's heat map over the
+ * 3136 positions, then the matmul with the features), called twice on the same heat maps at lib/models/pare.py:331-332 -- through the forward's own
+ * two launches: the pooling kernel of the handle's path (seven ranges of 448 positions, each against its own maximum) and the front of the regressor
+ * tail that merges the ranges.  heat_dev (n,25,56,56) with channel 0 the background (never read into a result), feat_a_dev (n,128,56,56),
+ * feat_b_dev (n,64,56,56): f32 NCHW; plf_out_dev (n,128,24) and csf_out_dev (n,64,24): f32, out[c][j] = sum_p softmax(heat[1 + j])[p] feat[c][p].
+ * A bf16 handle rounds the three maps to NHWC bf16 buffers with the plan's channel strides first, as grnet_op_bilinear2x does.  Workspace and the
+ * tail's other outputs are scratch of the call; any n >= 1.  Needs finalized weights (the tail runs whole); synchronises `stream`.
+ * GRNET_EINVAL, with nothing written, for a NULL pointer or n < 1. */
+int grnet_op_attention_pool(grnet_t* h, const float* heat_dev, const float* feat_a_dev, const float* feat_b_dev, int n, float* plf_out_dev,
+                            float* csf_out_dev, void* stream);
 /* bf16 handles: a chain of nconv (even, <= 8) 3x3 stride-1 convolutions c -> c on (n,c,wid,wid) maps as ONE launch with the frame resident in LDS
  * (csrc/conv_bf16_chain.hip) -- convolutions 2k, 2k+1 are conv1 / conv2 of BasicBlock k (lib/models/hrnet.py:43-59: conv-BN-ReLU, conv-BN, + block
  * input, ReLU; four of them are one branch of a HighResolutionModule, hrnet.py:141-187).  (c, wid) in {(64,28), (128,14), (256,7)}; (32,56) runs

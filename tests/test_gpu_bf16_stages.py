@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from .conftest import rel_err
+from .helpers import pool_checks as pc
 from .test_gpu_bf16_roll import _close_up_to_ties, _rb
 from .test_gpu_conv_bf16 import _close_up_to_rounding_ties
 
@@ -244,6 +245,15 @@ def test_stages_equal_oracle_on_their_own_inputs(pkg, oracle, synth_weights, n):
         e = rel_err(got[k], oracle.keypoint_attention(got[feat], attn))
         worst["attn_pool"] = max(worst.get("attn_pool", 0.0), e / 1e-4)
         assert e <= 1e-4, (k, e)
+    # ... and element by element on the 8 distinct frames: the one bf16-path launch whose output is fp32, so the float64 pooling of the tapped bf16 maps
+    # has no rounding tie to allow for -- the rule of tests/test_gpu_pool_elements.py (tests/helpers/pool_checks.py), printed first, then asserted
+    case = pc.tapped_case(got["head.heat"], got["head.smpl_feats"], got["head.cam_shape"])
+    held = pc.check("bf16", case, {k: got[k] for k in pc.OUTPUTS})
+    for output, r, yard, accepted, place in held:
+        print(pc.bounds_line("bf16", f"forward{n}", case["n"], output, r, yard, accepted, place))
+    for output, (ratio, at), yard, accepted, _ in held:
+        worst["attn_pool elements"] = max(worst.get("attn_pool elements", 0.0), ratio / accepted)
+        assert accepted <= pc.FACTOR * pc.YARD_CEILING["bf16"] and ratio <= accepted, (output, ratio, at, yard, accepted)
     # the fp32 tail from the GPU's pooled features: the fp32 path's parity bar (tests/test_gpu_parity.py, 1e-3 of the tensor's scale)
     for k, e in _tail_errors(oracle, sd, got).items():
         worst["tail"] = max(worst.get("tail", 0.0), e / 1e-3)

@@ -9,7 +9,8 @@ before its producer has written it reads different numbers and fails.  Which ker
 (grnet_conv_kernel_info, grnet_conv_launch_form), so that a plan change cannot quietly move a check onto another kernel.  At 16 frames every convolution launch is also held, element by element,
 to the rule of tests/test_gpu_conv_elements.py on its own tapped input (Checker.conv; tests/helpers/conv_checks.py forward_check) -- the 42 launches
 of the eight fuse layers included (Checker.fuse; tests/helpers/fuse_checks.py: the down chains are tapped as "<stage>.<m>.d<i>.<j>.<level>") -- and the
-six bilinear launches likewise (Checker.bilinear)."""
+six bilinear launches likewise (Checker.bilinear); the attention pooling with the merge that finishes it is held on all 8 distinct frames to the rule of
+tests/test_gpu_pool_elements.py on its tapped heat and feature maps (Checker.pool; tests/helpers/pool_checks.py)."""
 import ctypes as C
 import hashlib
 
@@ -20,6 +21,7 @@ import torch
 from .conftest import rel_err
 from .helpers import conv_checks as cc
 from .helpers import fuse_checks as fc
+from .helpers import pool_checks as pc
 from .helpers import smpl_checks as sc
 
 pytestmark = pytest.mark.gpu
@@ -210,6 +212,17 @@ class Checker:
         for fam, name, res in held:
             self._hold(fam, name, res)
 
+    def pool(self, got):
+        """head.heat / head.smpl_feats / head.cam_shape -> point_local_feat / cam_shape_feats on the 8 distinct frames, per element: within
+        max(4, 4 x yardstick) roundings of the element's magnitude of the float64 pooling of the tapped maps.  Printed first, asserted at the end."""
+        case = pc.tapped_case(got["head.heat"], got["head.smpl_feats"], got["head.cam_shape"])
+        res = pc.check("f32", case, {k: got[k] for k in pc.OUTPUTS})
+        for output, r, yard, accepted, place in res:
+            print(pc.bounds_line("f32", "forward16", case["n"], output, r, yard, accepted, place))
+        for output, (ratio, at), yard, accepted, _ in res:
+            self.worst["attn_pool elements"] = max(self.worst.get("attn_pool elements", 0.0), ratio / accepted)
+            assert accepted <= pc.FACTOR * pc.YARD_CEILING["f32"] and ratio <= accepted, (output, ratio, at, yard, accepted)
+
     def _hold(self, fam, name, res):
         ratio, at, _, _, bar = res
         k = fam + " elements"
@@ -303,6 +316,8 @@ def _check_all_stages(ck, oracle, sd, smpl, got, base):
         attn = got["head.heat"][:, 1:]
         for k, feat in (("point_local_feat", "head.smpl_feats"), ("cam_shape_feats", "head.cam_shape")):
             ck("attn_pool", k, got[k], oracle.keypoint_attention(got[feat], attn).reshape(got[k].shape))
+        if ck.elements:
+            ck.pool(got)
         # the tail from the GPU's pooled features
         rot6d, shape, cam = oracle.head_tail(got["point_local_feat"], got["cam_shape_feats"], sd)
     rotmat = oracle.rot6d_to_rotmat(rot6d).reshape(-1, 24, 3, 3)

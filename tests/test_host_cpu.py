@@ -43,6 +43,14 @@ def test_exchange_entry_points_refuse_bad_arguments(pkg):
         pkg._lib.check_comm(lib, lib.grnet_comm_create(C.byref(h), ident, 0, 0, 0), "grnet_comm_create")
 
 
+def test_attention_pool_hook_refuses_null_arguments_before_the_gpu_is_touched(pkg):
+    lib = pkg._lib.load()
+    assert lib.grnet_op_attention_pool(None, None, None, None, 1, None, None, None) == -22
+    header = open(os.path.join(ROOT, "include", "grnet_hip.h")).read()
+    at = header.index("int grnet_op_attention_pool(")
+    assert "keypoint_attention.py:42-48" in header[at - 1500:at] and "pare.py:331-332" in header[at - 1500:at]      # the entry cites what it computes
+
+
 def test_outputs_struct_matches_header(pkg):
     header = open(os.path.join(ROOT, "include", "grnet_hip.h")).read()
     body = header[header.index("typedef struct grnet_outputs {"):header.index("} grnet_outputs_t;")]

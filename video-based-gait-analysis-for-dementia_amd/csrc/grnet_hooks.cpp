@@ -331,4 +331,37 @@ int grnet_op_bilinear2x(grnet_t* h, const float* in_dev, int n, int c, int hgt, 
     return 0;
 }
 
+int grnet_op_attention_pool(grnet_t* h, const float* heat_dev, const float* feat_a_dev, const float* feat_b_dev, int n, float* plf_out_dev, float* csf_out_dev,
+                            void* stream) {
+    if (!h || !heat_dev || !feat_a_dev || !feat_b_dev || !plf_out_dev || !csf_out_dev || n < 1) return GRNET_EINVAL;
+    if (!h->finalized) return h->fail(GRNET_ESTATE, "grnet_op_attention_pool before grnet_finalize_weights");      // the tail behind the merge reads the regressor's weights
+    DeviceGuard guard(h->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    constexpr int P = 56 * 56;
+    HookBuffers mem;
+    // the pooling workspace and the tail's other outputs (rot6d 144 | shape 10 | cam 3 | rotmat 216 | theta 85 per frame): scratch of this call
+    float *ws = mem.alloc<float>(softmax_pool_ws_floats(n) * 4), *tail = mem.alloc<float>((size_t)n * (144 + 10 + 3 + 216 + 85) * 4);
+    if (!ws || !tail) return h->fail(GRNET_ENOMEM, "hipMalloc failed");
+    hipError_t e;
+    if (h->dtype == 1) {                                       // bf16 handle: the maps as the plan keeps them (NHWC bf16, the 25 heat channels in 32), then the bf16 path's kernel
+        const int hc = h->v_heat.ctot, cta = h->v_smpl_feats.ctot, ctb = h->v_csmap.ctot;
+        if (hc < 32 || cta < 128 || ctb < 64) return h->fail(GRNET_ESTATE, "grnet_op_attention_pool: the plan's channel strides do not hold the maps");
+        void *xh = mem.alloc((size_t)n * P * hc * 2), *xa = mem.alloc((size_t)n * P * cta * 2), *xb = mem.alloc((size_t)n * P * ctb * 2);
+        if (!xh || !xa || !xb) return h->fail(GRNET_ENOMEM, "hipMalloc failed");
+        e = launch_nchw_f32_to_nhwc_bf16(heat_dev, xh, n, 25, 56, 56, hc, s);
+        if (e == hipSuccess) e = launch_nchw_f32_to_nhwc_bf16(feat_a_dev, xa, n, 128, 56, 56, cta, s);
+        if (e == hipSuccess) e = launch_nchw_f32_to_nhwc_bf16(feat_b_dev, xb, n, 64, 56, 56, ctb, s);
+        if (e == hipSuccess) e = launch_softmax_pool_bf16(xh, hc, xa, 128, cta, xb, 64, ctb, ws, n, P, s);
+    } else {
+        e = launch_softmax_pool(heat_dev, 25, feat_a_dev, 128, feat_b_dev, 64, plf_out_dev, csf_out_dev, ws, n, P, s);
+    }
+    float* t = tail;
+    if (e == hipSuccess)
+        e = launch_head_tail(ws, true, plf_out_dev, csf_out_dev, h->tailw, t, t + (size_t)n * 144, t + (size_t)n * 154, t + (size_t)n * 157, t + (size_t)n * 373, n, s);
+    hipError_t e2 = hipStreamSynchronize(s);
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, std::string("attention pool: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return h->fail(GRNET_EHIP, std::string("attention pool kernels: ") + hipGetErrorString(e2));
+    return 0;
+}
+
 }  // extern "C"

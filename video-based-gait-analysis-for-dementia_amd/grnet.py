@@ -1833,6 +1833,19 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_bilinear2x")
         return out
 
+    def op_attention_pool(self, heat, feat_a, feat_b):
+        """The attention pooling alone, through the forward's pooling kernel and the merge at the front of the tail (grnet_op_attention_pool):
+        heat (n,25,56,56), feat_a (n,128,56,56), feat_b (n,64,56,56) f32 -> (point_local_feat (n,128,24), cam_shape_feats (n,64,24)) f32."""
+        n = heat.shape[0]
+        assert tuple(heat.shape) == (n, 25, 56, 56) and tuple(feat_a.shape) == (n, 128, 56, 56) and tuple(feat_b.shape) == (n, 64, 56, 56)
+        heat, feat_a, feat_b = (t.to(torch.float32).contiguous() for t in (heat, feat_a, feat_b))
+        plf = torch.empty(n, 128, 24, dtype=torch.float32, device=heat.device)
+        csf = torch.empty(n, 64, 24, dtype=torch.float32, device=heat.device)
+        stream = self._stream(heat.device)
+        rc = self._lib.grnet_op_attention_pool(self._h, heat.data_ptr(), feat_a.data_ptr(), feat_b.data_ptr(), n, plf.data_ptr(), csf.data_ptr(), stream)
+        _lib.check(self._lib, self._h, rc, "grnet_op_attention_pool")
+        return plf, csf
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.grnet_destroy(self._h)
