@@ -95,6 +95,16 @@ pipeline.coordination_rows'.  <outpath>_coordination.json.  These are joint-posi
 the coherence of two unrelated signals is about 1 / K (0.09 at the 11 segments of 400 frames), not 0, and the defaults are unvalidated on the
 model's output.  With --gait_turns a turn splits the walk into straight runs.  Reported, never judged.
 
+--gait_balance (opt-in, with --gait) reports where the feet land on the floor and where the body's mass is relative to them, without a camera
+model: a foot on the ground stands still in the world, so the vector between the ankles just after a heel strike is a footprint-to-footprint
+vector, and the centre of mass (Winter's segment masses laid on the kinectv2 joints, a layout of this project's that is unvalidated) relative to
+the planted ankle gives its velocity over the ground.  Per video the footprints chained strike after strike, stride length, step length and step
+width against the line of progression (as a walkway defines them, Webster et al. 2005), the speed over the ground, and Hof's margin of stability
+at foot placement, forward and sideways (Hof, Gagey and Halbertsma 2005; Mehdizadeh et al. 2020 report it from video in dementia)
+(GRNet.gait_balance on the device): <outpath>_balance.json, and 'footprints_phase' in the database.  THE FLOOR IS THE x-z PLANE OF A
+LEVEL, FIXED CAMERA; the stance ankle creeps forward at heel rise; a margin of a few centimetres carries about two of noise per step at 5 mm of
+joint noise.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -503,6 +513,55 @@ class WindowContacts:
         with open(path, "w") as f:
             json.dump(self.videos, f, indent=1, allow_nan=False)
         print(f"Save contacts of {len(self.videos)} videos to {path}.")
+        return path
+
+
+class WindowBalance:
+    """--gait_balance: one gait_balance call per database window on rank 0, directly after WindowGait's, on the same joints and on the events that
+    call returned (model.gait_balance; on_host, or a model without the method: pipeline.gait_balance after a download).  Per video the columns of
+    pipeline.BALANCE_COLUMNS plus 'step_table', the list of its stored steps keyed by pipeline.BALANCE_STEP_COLUMNS.  The joints are
+    pipeline.GAIT_JOINTS_KINECTV2, the segments pipeline.BALANCE_SEGMENTS_KINECTV2, fps is WindowGait's.  The floor is the x-z plane of a level, fixed
+    camera; the segment layout is unvalidated; nothing is judged."""
+
+    def __init__(self, pipe, model, on_host, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_balance") else model.gait_balance
+        self.kw = dict(fps=float(fps), gravity=float(gravity), window=int(window), settle=int(settle), max_step=int(max_step))
+        self.videos = {}
+
+    def add_window(self, keys, j3, lengths, events):
+        """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths and the events (sum T,) -> per video the
+        stance side of every frame's step (T,) int8: +1 left, -1 right, 0 none."""
+        if not keys:
+            return []
+        if self.device_call is not None:
+            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, lengths=lengths, **self.kw).items()}
+        else:
+            ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
+            out = self.pipe.gait_balance(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+
+        def number(v):
+            return float(v) if np.isfinite(v) else None          # a NaN is undefined; an asymmetry over a zero mean is infinite: null too, the file is strict JSON
+
+        def shown(v, form, unit):
+            return "none" if v is None else format(v, form) + unit
+        phases, a = [], 0
+        for key, T, row, table in zip(keys, lengths, out["per_sequence"], out["steps"]):
+            phases.append(out["per_frame"][a:a + T, 6].astype(np.int8))
+            video = {name: number(v) for name, v in zip(self.pipe.BALANCE_COLUMNS, row)}
+            video["step_table"] = [{name: number(v) for name, v in zip(self.pipe.BALANCE_STEP_COLUMNS, step)} for step in table if not np.isnan(step[0])]
+            self.videos[key] = video
+            print(f"Balance: video {key}, {int(row[1])} steps in {int(row[2])} chains, stride length {shown(video['stride_length_mean'], '.3f', ' m')}, step width "
+                  f"{shown(video['step_width_mean'], '.3f', ' m')}, ground speed {shown(video['ground_speed'], '.3f', ' m/s')}, margin of stability forward "
+                  f"{shown(video['mos_ap_mean'], '.3f', ' m')}, sideways {shown(video['mos_ml_mean'], '.3f', ' m')}.")
+            a += T
+        return phases
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save balance of {len(self.videos)} videos to {path}.")
         return path
 
 
@@ -936,8 +995,11 @@ class WindowCoordination:
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None):
-    """coordination: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None):
+    """balance: {'gravity', 'window', 'settle', 'max_step', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the footprints,
+    stride length, step width, ground speed and margins of stability of every video (WindowBalance), written to balance['out'] (default: outpath with
+    _balance.json); the database gains 'footprints_phase' (N,) int8 (the stance side of the frame's step: +1 left, -1 right, 0 none).
+    coordination: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each
     optional; needs no gait, whose fps it takes where its own is not given, else 20) -- also the arm swing and inter-limb coordination of every video
     (WindowCoordination), written to coordination['out'] (default: outpath with _coordination.json); with turns only straight walking counts unless
     'all_frames'; the database gains nothing.
@@ -1044,6 +1106,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     stands = WindowContacts(pipe, model, contacts.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                             **{k: contacts[k] for k in ("sigma", "fraction", "speed", "reach", "max_frames") if contacts.get(k) is not None}) \
         if contacts is not None and rank == 0 else None
+    if balance is not None and gait is None:
+        raise ValueError("balance needs gait: it runs on the events of that call")
+    prints = WindowBalance(pipe, model, balance.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
+                           **{k: balance[k] for k in ("gravity", "window", "settle", "max_step") if balance.get(k) is not None}) \
+        if balance is not None and rank == 0 else None
     steady = WindowRegularity(pipe, model, regularity.get("on_host", False), not regularity.get("all_frames", False),
                               **({"fps": gait["fps"]} if regularity.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
                               **{k: regularity[k] for k in ("fps", "sigma", "max_lag", "min_lag", "min_peak", "min_pairs") if regularity.get(k) is not None}) \
@@ -1122,6 +1189,7 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             metrics.add_window([v[0] for v in vids], per_video)
         fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
         gait_events = walk.add_window([v[0] for v in vids], per_video, fitted) if walk is not None else None
+        footprints_phase = prints.add_window([v[0] for v in vids], *walk.window) if prints is not None and vids else None
         if angles is not None and vids:
             angles.add_window([v[0] for v in vids], *walk.window)
         gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
@@ -1154,6 +1222,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                     extra["gait_phase"] = gait_phase[vi]
                 if gait_support is not None:
                     extra["gait_support"] = gait_support[vi]
+                if footprints_phase is not None:
+                    extra["footprints_phase"] = footprints_phase[vi]
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -1185,6 +1255,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         again.write(recurrence.get("out") or osp.splitext(outpath)[0] + "_recurrence.json")
     if limbs is not None:
         limbs.write(coordination.get("out") or osp.splitext(outpath)[0] + "_coordination.json")
+    if prints is not None:
+        prints.write(balance.get("out") or osp.splitext(outpath)[0] + "_balance.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -1262,6 +1334,18 @@ def main(argv=None):
     p.add_argument("--contacts_max_duration", type=float, default=None, help="with --gait_contacts: the longest double support in seconds, made frames through --gait_fps "
                    "(default 1.0); a longer run is standing")
     p.add_argument("--contacts_on_host", action="store_true", help="with --gait_contacts: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_balance", action="store_true", help="with --gait: the footprints chained strike after strike (a foot on the ground stands still in the world), stride "
+                   "length, step length and step width against the line of progression, the speed over the ground, and the margin of stability at foot placement forward "
+                   "and sideways (Hof et al. 2005) from a centre of mass of Winter's segment masses: 'footprints_phase' (N,) in the database, <outpath>_balance.json, one "
+                   "line per video; the floor is the x-z plane of a level, fixed camera, and the segment layout is unvalidated")
+    p.add_argument("--balance_out", type=str, default="", help="with --gait_balance: the JSON file (default: --outpath with _balance.json)")
+    p.add_argument("--balance_window", type=int, default=None, help="with --gait_balance: the centre of mass's velocity is the slope over this many frames before the landing, "
+                   "1 to 16 (default 4)")
+    p.add_argument("--balance_settle", type=int, default=None, help="with --gait_balance: the vector between the ankles is read this many frames after the heel strike, 0 to 4 "
+                   "(default 1: the strike's extremum may fall on the frame before the landing)")
+    p.add_argument("--balance_max_step", type=int, default=None, help="with --gait_balance: two heel strikes further apart than this many frames are no step (default 30)")
+    p.add_argument("--balance_gravity", type=float, default=None, help="with --gait_balance: metres a second squared; the joints are SMPL metres (default 9.81)")
+    p.add_argument("--balance_on_host", action="store_true", help="with --gait_balance: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--gait_regularity", action="store_true", help="with --vid_folder (no --gait needed): step and stride regularity, symmetry and a cadence WITHOUT events, "
                    "from the autocorrelation of four body signals (Moe-Nilssen and Helbostad 2004): <outpath>_regularity.json, one line per video; takes "
                    "--gait_fps where given; with --gait_turns only straight walking counts; the defaults are unvalidated on the model's output")
@@ -1466,6 +1550,20 @@ def main(argv=None):
         sys.exit("batch_generation.py: --contacts_fraction and --contacts_speed must not be negative, and not both zero")
     if a.contacts_reach is not None and not 0 <= a.contacts_reach <= 8:
         sys.exit("batch_generation.py: --contacts_reach must be within 0 to 8 frames")
+    if a.gait_balance and not a.gait:
+        sys.exit("batch_generation.py: --gait_balance belongs to --gait, which was not given (it runs on the events of that call)")
+    for flag, given in (("--balance_out", bool(a.balance_out)), ("--balance_window", a.balance_window is not None), ("--balance_settle", a.balance_settle is not None),
+                        ("--balance_max_step", a.balance_max_step is not None), ("--balance_gravity", a.balance_gravity is not None), ("--balance_on_host", a.balance_on_host)):
+        if given and not a.gait_balance:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_balance, which was not given")
+    if a.balance_window is not None and not 1 <= a.balance_window <= 16:
+        sys.exit("batch_generation.py: --balance_window must be within 1 to 16 frames")
+    if a.balance_settle is not None and not 0 <= a.balance_settle <= 4:
+        sys.exit("batch_generation.py: --balance_settle must be within 0 to 4 frames")
+    if a.balance_max_step is not None and not a.balance_max_step >= 1:
+        sys.exit("batch_generation.py: --balance_max_step must be at least 1 frame")
+    if a.balance_gravity is not None and not (np.isfinite(a.balance_gravity) and a.balance_gravity > 0):
+        sys.exit("batch_generation.py: --balance_gravity must be a positive number of metres a second squared")
     contact_frames = None
     if a.gait_contacts:
         longest = 1.0 if a.contacts_max_duration is None else a.contacts_max_duration
@@ -1682,6 +1780,8 @@ def main(argv=None):
     coordination = {"fps": a.gait_fps, "sigma": a.coordination_sigma, "derivative": a.coordination_derivative, "segment": a.coordination_segment, "hop": a.coordination_hop,
                     "nfft": a.coordination_nfft, "f_lo": a.coordination_f_lo, "f_hi": a.coordination_f_hi, "min_segments": a.coordination_min_segments,
                     "all_frames": a.coordination_all_frames, "on_host": a.coordination_on_host, "out": a.coordination_out or None} if a.gait_coordination else None
+    balance = {"gravity": a.balance_gravity, "window": a.balance_window, "settle": a.balance_settle, "max_step": a.balance_max_step, "on_host": a.balance_on_host,
+               "out": a.balance_out or None} if a.gait_balance else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
@@ -1690,7 +1790,7 @@ def main(argv=None):
                  **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
                  **({"stability": stability} if stability is not None else {}),
                  **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}),
-                 **({"coordination": coordination} if coordination is not None else {}))
+                 **({"coordination": coordination} if coordination is not None else {}), **({"balance": balance} if balance is not None else {}))
 
 
 if __name__ == "__main__":

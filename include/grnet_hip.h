@@ -973,6 +973,57 @@ int grnet_op_gait_cross_welch(grnet_t* h, const double* signals_dev, const int32
                               int derivative, int segment, int hop, int nfft, double f_lo, double f_hi, int min_segments, double* auto_dev,
                               double* cross_dev, double* limbs_dev, double* pairs_dev, void* stream);
 
+/* Footprints on the floor, the centre of mass over them and the margin of stability at foot placement (Hof, Gagey and Halbertsma 2005; the segment
+ * masses after Winter 2009 and Dempster 1955; stride length and step width on the footprints against the line of progression, as a walkway such as
+ * GAITRite defines them, Webster et al. 2005) WITHOUT A CAMERA MODEL (which is the specification).  The joints are root-relative,
+ * but a foot on the ground stands still in the world: at a heel strike both feet are down, so the vector from the stance ankle to the landing one
+ * is a world vector, and while foot X is planted COM - ankle_X is the world path of the COM up to a constant.  THE FLOOR IS THE x-z PLANE OF A
+ * LEVEL, FIXED CAMERA (x right, y down, z away); the stance ankle creeps forward at heel rise, which biases speed and margins; the segment layout
+ * on these joints is this project's and UNVALIDATED; a margin of a few centimetres carries about two of noise per step (DESIGN.md 4.22 has the
+ * figures).  Numbers are reported, never judged.
+ * joints3d_dev float32 (sum T, J, 3), frame_offsets_host and joints_host as for grnet_gait_parameters (all 8 indices are checked; entries 4 and 5,
+ * the ankles, are read); events_dev int32 (sum T): its events, of which bits 0 and 1, the heel strikes, are read.  segments_host int32 (n_seg, 2):
+ * proximal and distal joint; seg_weights_host float64 (n_seg, 2): mass and the COM's fraction from the proximal joint; 1 <= n_seg <= 16.
+ * Everything is float64, one rounding per operation, float32 widened first; every test is a comparison, false for NaN; sums run in the stated order
+ * from +0.0.
+ *   1 COM     per component c = (sum_i m_i (P_i + p_i (D_i - P_i))) / (sum_i m_i), both sums in table order; rL = c - left ankle, rR = c - right ankle
+ *   2 marks   the frames with a heel-strike bit, in time order; a frame with both bits is a mark and a strike of neither foot
+ *   3 step    consecutive marks (t1 of foot X, t2 of foot Y) with X != Y, window <= t2 - t1 <= max_step, tb = t2 + settle inside the sequence, rX
+ *             finite on all of [t1, t2], b = rX(tb) - rY(tb) finite, and rule 4's sp positive and finite and l > 0
+ *   4 margin  k_i = i - window / 2.0, i = 0 .. window; N = sum k_i rX(t2 - window + i) (x and z), D = sum k_i k_i; v = (N / D) fps;
+ *             sp = sqrt(v_x^2 + v_z^2); a = (v_x / sp, v_z / sp); left = (-a_z, a_x); l = -rX_y(t2); w0 = sqrt(gravity / l);
+ *             xi = (rX_x(t2) + v_x / w0, rX_z(t2) + v_z / w0); MoS_AP = (b_x - xi_x) a_x + (b_z - xi_z) a_z;
+ *             MoS_ML = s_Y ((b_x - xi_x) left_x + (b_z - xi_z) left_z), s_Y = +1 where Y is the left foot, -1 where the right
+ *   5 chains  a chain is a maximal run of consecutive pairs that are steps; G_0 = +0, G_{j+1} = G_j + b_j per component in time order, ONE lane
+ *   6 strides of a step j >= 1 of its chain: q = G_{j+1} - G_{j-1} (x, z), L = sqrt(q_x^2 + q_z^2), counted where L > 0, p = q / L, step length
+ *             b_j . p, step width |b_j . (-p_z, p_x)|
+ *   7 path    W(t) = G_j + rX(t) of the step with the largest t1 <= t among those whose [t1, t2] holds t
+ *   8 excursions of a step j >= 1 over the frames t1 of step j - 1 .. t2 of step j (each frame on the stance of rule 7's step): max - min of W_y,
+ *             and (where L > 0) of (W_x - G_{j-1,x}) (-p_z) + (W_z - G_{j-1,z}) p_x
+ * per_frame_dev (sum T, 8) float64 = [c (3), W (3; NaN outside a step), stance side +1 left / -1 right / 0 none, chain number or NaN].
+ * steps_dev (n_seq, max_steps, 15) float64 in time order: [t1, t2, s_Y, chain, G_{j+1} (3), stride length, step length, step width, sp, MoS_AP,
+ * MoS_ML, vertical excursion, lateral excursion]; rows past the count are NaN, steps past max_steps are counted, chained and used in the row but
+ * not stored.
+ * per_seq_dev (n_seq, 24) float64: [0] strikes (marks with one bit); [1] steps; [2] chains; [3] strides; then mean and SD of [4, 5] stride length,
+ * [6, 7] step length, [8, 9] step width; [10] 100 |L - R| / (0.5 (L + R)) of the mean step length by landing side; [11, 12] sp; [13] ground
+ * speed (sum sqrt(b_x^2 + b_z^2)) / (sum (t2 - t1) / fps) over all steps; [14, 15] MoS_AP; [16, 17] MoS_ML; [18, 19] mean MoS_ML of left and of
+ * right landings; [20, 21] vertical and [22, 23] lateral excursion.  Means are sums in time order over the count of values that are not NaN, SDs
+ * two-pass with ddof = 0; a column is NaN where its count is 0.
+ * No filter or search crosses a sequence; fixed orders, no atomics: a sequence's outputs have the same bits whether it travels alone or with others.
+ * Needs no weights.  Three launches behind one small copy from pinned memory, whatever n_seq and T; no host synchronisation; the scratch is the box
+ * calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer, J < 1, a table or segment index outside [0, J),
+ * n_seq outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, n_seg outside [1, 16], a mass not positive and finite, a
+ * non-finite fraction, fps or gravity not positive and finite, window outside [1, 16], settle outside [0, 4], max_step < 1, max_steps outside
+ * [1, 1024].
+ * grnet_op_gait_balance_steps: rules 2 to 8 alone (test hook) on rel_dev float64 (sum T, 9) = [c, rL, rR]. */
+int grnet_gait_balance(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                       const int32_t* events_dev, const int32_t* segments_host, const double* seg_weights_host, int n_seg, double fps, double gravity,
+                       int window, int settle, int max_step, int max_steps, double* per_frame_dev, double* steps_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_balance_steps(grnet_t* h, const double* rel_dev, const int32_t* events_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                                double gravity, int window, int settle, int max_step, int max_steps, double* per_frame_dev, double* steps_dev,
+                                double* per_seq_dev, void* stream);
+
 /* Recurrence quantification of the same four body signals (Webber and Zbilut 1994; Marwan et al. 2007; on gait Labini et al. 2012 and Riva et al.
  * 2013 -- on a trunk sensor over minutes of walking; these signals are joint positions of a pose model over some 15 strides, the radius rule is this
  * project's and the defaults are unvalidated on its output): every pair of points of the delay-embedded signal against one radius, and the runs of

@@ -26,6 +26,11 @@ TRACK_PAD = {"zero": 0, "edge": 1}
 GAIT_JOINTS_KINECTV2 = (0, 20, 12, 16, 14, 18, 15, 19)         # pelvis, spine-shoulder, left hip, right hip, left ankle, right ankle, left foot, right foot
 # pelvis, spine-shoulder, then left and right hip, knee, ankle, foot, shoulder, elbow, wrist
 KINEMATICS_JOINTS_KINECTV2 = (0, 20, 12, 16, 13, 17, 14, 18, 15, 19, 4, 8, 5, 9, 6, 10)
+# (proximal joint, distal joint, mass, the COM's fraction from the proximal joint): Winter's whole-body fractions laid on the kinectv2 joints --
+# trunk, head and neck, then left and right upper arm, forearm, hand, thigh, shank, foot.  The layout is this project's choice and unvalidated.
+BALANCE_SEGMENTS_KINECTV2 = ((0, 20, 0.497, 0.5), (20, 3, 0.081, 1.0), (4, 5, 0.028, 0.436), (8, 9, 0.028, 0.436), (5, 6, 0.016, 0.430), (9, 10, 0.016, 0.430),
+                             (6, 7, 0.006, 0.506), (10, 11, 0.006, 0.506), (12, 13, 0.100, 0.433), (16, 17, 0.100, 0.433), (13, 14, 0.0465, 0.433),
+                             (17, 18, 0.0465, 0.433), (14, 15, 0.0145, 0.5), (18, 19, 0.0145, 0.5))
 OPT_USE_GRAPH, OPT_CONV_TILE, OPT_MULTI_LANE, OPT_WINOGRAD, OPT_BF16_CHAIN, OPT_GRU_MODE, OPT_BF16_MIN_FRAMES = 1, 2, 3, 7, 8, 9, 10
 
 
@@ -177,6 +182,11 @@ EXPORTS = {
                                           C.c_void_p]),
     "grnet_op_gait_cross_welch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "grnet_gait_balance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "grnet_op_gait_balance_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_op_procrustes":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "grnet_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "grnet_comm_probe": (C.c_int, []),

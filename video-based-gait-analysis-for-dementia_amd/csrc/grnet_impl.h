@@ -21,6 +21,7 @@
 //   grnet_spectrum.cpp the Welch spectrum: grnet_gait_spectrum and its density hook
 //   grnet_recurrence.cpp recurrence quantification: grnet_gait_recurrence and its counting hook
 //   grnet_coordination.cpp arm swing and inter-limb coordination: grnet_gait_coordination and its cross-spectrum hook
+//   grnet_balance.cpp  footprints, centre of mass and margin of stability: grnet_gait_balance and its steps hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

@@ -512,6 +512,22 @@ hipError_t launch_coord_frames(const float* joints, int J, int frames, const Kin
 hipError_t launch_coord_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
                                   double* mu_long, double* au, double* cr, double* limbs, double* pairs, hipStream_t s);
 
+// Footprints, centre of mass and margin of stability (csrc/gait_balance_kernels.hip, compiled without fma contraction; the arithmetic:
+// csrc/gait_balance.h).  The sequence kernel's workgroup is the gait call's kGaitThreads ----
+struct BalanceRule;                        // gait_balance.h: fps, gravity, window, settle, max_step, max_steps
+struct BalanceSegments;                    // gait_balance.h: the segment table, at most 16 rows, a kernel argument
+constexpr int kBalanceLdsStrikes = 1024;   // marks (frames with a heel strike) of a sequence whose list the workgroup keeps in LDS: 4 KB (more: the call's scratch)
+constexpr int kBalanceMaskSets = 3;        // left and right heel strikes, and the marks in front of each word
+// one lane per frame: rel (frames,9) = [c, c - left ankle, c - right ankle]; tab: its ankles (entries 4 and 5) are read
+hipError_t launch_balance_frames(const float* joints, int J, int frames, const GaitTable& tab, const BalanceSegments& seg, double* rel, hipStream_t s);
+// one workgroup per sequence on rel (frames,9) and the gait call's events (frames): steps (n_seq,max_steps,15), per_seq (n_seq,24); words:
+// kBalanceMaskSets * mask_words (gait_mask_words), list (frames) int32 and pairs (frames,20) float64 of scratch, which launch_balance_path reads
+hipError_t launch_balance_steps(const int* off, int n_seq, const BalanceRule& rule, const double* rel, const int* events, unsigned long long* words,
+                                size_t mask_words, int* list, double* pairs, double* steps, double* per_seq, hipStream_t s);
+// one lane per frame behind launch_balance_steps, on its words and pairs: per_frame (frames,8)
+hipError_t launch_balance_path(const int* off, int n_seq, int frames, const double* rel, const unsigned long long* words, size_t mask_words,
+                               const double* pairs, double* per_frame, hipStream_t s);
+
 // Recurrence quantification of the same four signals (csrc/gait_recurrence_kernels.hip, compiled without fma contraction; the arithmetic:
 // csrc/gait_recurrence.h).  The frame kernel is launch_reg_frames ----
 struct RecRule;                            // gait_recurrence.h: derivative, dim, lag, theiler, radius

@@ -1673,6 +1673,56 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_cross_welch")
         return out
 
+    # ------------------------------------------------------------------ footprints, centre of mass and margin of stability
+    def _balance_call(self, n, lengths, events, window, settle, max_step, max_steps, what):
+        """(events on the device, offsets, the three output tensors) of gait_balance and its hook."""
+        ev = self._events_input(n, events)
+        self._whole_frames(window=window, settle=settle, max_step=max_step, max_steps=max_steps)
+        if not 1 <= int(max_steps) <= 1024:
+            raise ValueError(f"max_steps {max_steps} outside [1, 1024]")      # the step table is allocated here: a size the C ABI would refuse is refused first
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        out = {"per_frame": torch.empty(n, 8, dtype=torch.float64, device=self.device),
+               "steps": torch.empty(n_seq, int(max_steps), 15, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 24, dtype=torch.float64, device=self.device)}
+        return ev, off, out
+
+    def gait_balance(self, joints3d, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256,
+                     segments=_lib.BALANCE_SEGMENTS_KINECTV2, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """Footprints on the floor, the centre of mass over them and the margin of stability at foot placement of every sequence on the device
+        (grnet_gait_balance; the rules and the columns: DESIGN 4.22, pipeline.BALANCE_COLUMNS).  Called after gait_parameters on the same joints3d,
+        lengths and joints, with its `events` (taken as int32).  segments: rows of (proximal joint, distal joint, mass, the COM's fraction from the
+        proximal joint), at most 16.  A foot on the ground stands still in the world: the vector between the ankles `settle` frames after a heel
+        strike is a footprint-to-footprint vector, and the COM relative to the planted ankle, fitted over the last `window` + 1 frames of a step,
+        gives its velocity.  THE FLOOR IS THE x-z PLANE OF A LEVEL, FIXED CAMERA; the segment layout is unvalidated; a margin of a few centimetres
+        carries about two of noise per step.  Returns a dict of device tensors: per_frame (n,8) float64 [c, W, stance side, chain]; steps
+        (n_seq,max_steps,15) float64; per_sequence (n_seq,24) float64.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        seg = np.asarray(segments, np.float64)
+        if seg.ndim != 2 or seg.shape[1] != 4 or seg.shape[0] < 1 or not np.array_equal(seg[:, :2], np.floor(seg[:, :2])) or np.abs(seg[:, :2]).max() >= 2**31:
+            raise ValueError(f"segments must be rows of (proximal joint, distal joint, mass, fraction), got shape {seg.shape}")
+        pairs, weights = np.ascontiguousarray(seg[:, :2], np.int32), np.ascontiguousarray(seg[:, 2:])
+        ev, off, out = self._balance_call(n, lengths, events, window, settle, max_step, max_steps, "joints3d")
+        rc = self._lib.grnet_gait_balance(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), ev.data_ptr(), _i32p(pairs),
+                                          weights.ctypes.data_as(C.POINTER(C.c_double)), int(seg.shape[0]), float(fps), float(gravity), int(window),
+                                          int(settle), int(max_step), int(max_steps), out["per_frame"].data_ptr(), out["steps"].data_ptr(),
+                                          out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_balance")
+        return out
+
+    def op_gait_balance_steps(self, rel, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256):
+        """Rules 2 to 8 of gait_balance alone (grnet_op_gait_balance_steps): rel (n,9) float64 = [c, rL, rR] and events (n,), one sequence or
+        `lengths` of them lying back to back -> {per_frame, steps, per_sequence} on the device."""
+        x = self._rows_input(rel, "rel", (9,), torch.float64)
+        ev, off, out = self._balance_call(x.shape[0], lengths, events, window, settle, max_step, max_steps, "rel")
+        rc = self._lib.grnet_op_gait_balance_steps(self._h, x.data_ptr(), ev.data_ptr(), _i32p(off), len(off) - 1, float(fps), float(gravity), int(window),
+                                                   int(settle), int(max_step), int(max_steps), out["per_frame"].data_ptr(), out["steps"].data_ptr(),
+                                                   out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_balance_steps")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import netspec
-from ._lib import GAIT_JOINTS_KINECTV2, KINEMATICS_JOINTS_KINECTV2
+from ._lib import BALANCE_SEGMENTS_KINECTV2, GAIT_JOINTS_KINECTV2, KINEMATICS_JOINTS_KINECTV2
 
 IMAGENET_MEAN = np.array([0.485, 0.456, 0.406], np.float32)
 IMAGENET_STD = np.array([0.229, 0.224, 0.225], np.float32)
@@ -2764,6 +2764,178 @@ def gait_coordination(joints3d, lengths=None, exclude=None, fps=20.0, sigma=0.0,
     lengths, per_frame = _coordination_signals(joints3d, lengths, sigma, joints, rule_check)
     out = gait_cross_welch(per_frame, lengths, exclude, fps, derivative, segment, hop, nfft, f_lo, f_hi, min_segments)
     out["per_frame"] = per_frame
+    return out
+
+
+# ----------------------------------------------------------------------------- footprints, centre of mass and margin of stability
+# BALANCE_SEGMENTS_KINECTV2 (imported above): rows of (proximal joint, distal joint, mass, the COM's fraction from the proximal joint)
+BALANCE_FRAME_COLUMNS = ("com_x", "com_y", "com_z", "path_x", "path_y", "path_z", "stance_side", "chain")
+BALANCE_STEP_COLUMNS = ("t1", "t2", "landing_side", "chain", "footprint_x", "footprint_y", "footprint_z", "stride_length", "step_length", "step_width",
+                        "com_speed", "mos_ap", "mos_ml", "vertical_excursion", "lateral_excursion")
+BALANCE_COLUMNS = ("strikes", "steps", "chains", "strides", "stride_length_mean", "stride_length_sd", "step_length_mean", "step_length_sd",
+                   "step_width_mean", "step_width_sd", "step_length_asymmetry", "com_speed_mean", "com_speed_sd", "ground_speed", "mos_ap_mean",
+                   "mos_ap_sd", "mos_ml_mean", "mos_ml_sd", "mos_ml_left", "mos_ml_right", "vertical_excursion_mean", "vertical_excursion_sd",
+                   "lateral_excursion_mean", "lateral_excursion_sd")
+
+
+def _balance_rule_check(fps, gravity, window, settle, max_step, max_steps):
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if not np.isfinite(gravity) or not gravity > 0:
+        raise ValueError("gravity must be positive and finite")
+    if int(window) != window or int(settle) != settle or int(max_step) != max_step or int(max_steps) != max_steps:
+        raise ValueError("window, settle, max_step and max_steps must be whole numbers")
+    if not 1 <= window <= 16:
+        raise ValueError(f"window {window} outside [1, 16]")
+    if not 0 <= settle <= 4:
+        raise ValueError(f"settle {settle} outside [0, 4]")
+    if max_step < 1:
+        raise ValueError(f"max_step {max_step} < 1")
+    if not 1 <= max_steps <= 1024:
+        raise ValueError(f"max_steps {max_steps} outside [1, 1024]")
+
+
+def _balance_segments(segments, J):
+    """(proximal (n_seg,), distal (n_seg,), mass (n_seg,), fraction (n_seg,)) of a segment table, checked as the C ABI checks it."""
+    seg = np.asarray(segments, np.float64)
+    if seg.ndim != 2 or seg.shape[1] != 4 or not 1 <= seg.shape[0] <= 16:
+        raise ValueError(f"segments must be 1 to 16 rows of (proximal joint, distal joint, mass, fraction), got shape {seg.shape}")
+    idx = seg[:, :2]
+    if not np.array_equal(idx, np.floor(idx)) or idx.min() < 0 or idx.max() >= J:
+        raise ValueError(f"a segment joint lies outside [0, {J})")
+    if not (np.isfinite(seg[:, 2]).all() and (seg[:, 2] > 0).all()):
+        raise ValueError("a segment mass is not positive and finite")
+    if not np.isfinite(seg[:, 3]).all():
+        raise ValueError("a segment fraction is not finite")
+    return idx[:, 0].astype(np.int64), idx[:, 1].astype(np.int64), seg[:, 2], seg[:, 3]
+
+
+def gait_balance_steps(rel, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256):
+    """Rules 2 to 8 of DESIGN 4.22 on given rel (n,9) float64 = [c, rL, rR]: the host statement of GRNet.op_gait_balance_steps.  events (n,) as
+    gait_parameters returned them (bits 0 and 1 are read).  Returns {'per_frame': (n,8), columns BALANCE_FRAME_COLUMNS, 'steps': (n_seq,max_steps,15),
+    columns BALANCE_STEP_COLUMNS, 'per_sequence': (n_seq,24), columns BALANCE_COLUMNS}; every sum in the stated order from +0.0, every comparison false
+    for NaN.  The pairs of a sequence are handled side by side, the footprints are np.cumsum (one addition after the other) along each chain."""
+    x = np.asarray(rel, np.float64)
+    if x.ndim != 2 or x.shape[1] != 9 or x.shape[0] < 1:
+        raise ValueError(f"rel must be (n,9) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64) & (GAIT_HEEL_L | GAIT_HEEL_R)
+    lengths = _sequence_lengths(n, lengths)
+    _balance_rule_check(fps, gravity, window, settle, max_step, max_steps)
+    fps, gravity, w, settle, max_step, max_steps = float(fps), float(gravity), int(window), int(settle), int(max_step), int(max_steps)
+    per_frame = np.full((n, 8), np.nan)
+    per_frame[:, :3] = x[:, :3]
+    per_frame[:, 6] = 0.0
+    steps = np.full((len(lengths), max_steps, 15), np.nan)
+    per_seq = np.full((len(lengths), 24), np.nan)
+    k = np.arange(w + 1, dtype=np.float64) - w / 2.0
+    D = _gait_sum(k * k)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            r, e, out = x[f0:f0 + T], ev[f0:f0 + T], per_frame[f0:f0 + T]
+            R = np.stack([r[:, 3:6], r[:, 6:9]])                # R[0] = rL, R[1] = rR
+            bad = np.concatenate([np.zeros((2, 1), np.int64), np.cumsum(~np.isfinite(R).all(axis=2), axis=1)], axis=1)
+            marks = np.flatnonzero(e)
+            feet = e[marks]
+            t1, t2, X, Y = marks[:-1], marks[1:], feet[:-1], feet[1:]
+            ok = (X != 3) & (Y != 3) & (X != Y) & (t2 - t1 >= w) & (t2 - t1 <= max_step) & (t2 + settle <= T - 1)
+            ix, iy, tb = (X == GAIT_HEEL_R).astype(np.int64), (Y == GAIT_HEEL_R).astype(np.int64), np.minimum(t2 + settle, T - 1)
+            ok &= bad[ix, t2 + 1] - bad[ix, t1] == 0
+            b = R[ix, tb] - R[iy, tb]
+            ok &= np.isfinite(b).all(axis=1)
+            N = np.zeros((len(t1), 3))
+            for i in range(w + 1):
+                N = N + k[i] * R[ix, np.maximum(t2 - w + i, 0)]
+            v = (N / D) * fps
+            sp = np.sqrt(v[:, 0] * v[:, 0] + v[:, 2] * v[:, 2])
+            ok &= (sp > 0) & np.isfinite(sp)
+            ax, az = v[:, 0] / sp, v[:, 2] / sp
+            lx, lz = -az, ax
+            at2 = R[ix, t2]
+            ell = -at2[:, 1]
+            ok &= ell > 0
+            w0 = np.sqrt(gravity / ell)
+            dx, dz = b[:, 0] - (at2[:, 0] + v[:, 0] / w0), b[:, 2] - (at2[:, 2] + v[:, 2] / w0)
+            sY = np.where(Y == GAIT_HEEL_L, 1.0, -1.0)
+            ap, ml = dx * ax + dz * az, sY * (dx * lx + dz * lz)
+            rows, chain = [], -1                               # every step's 15 columns in time order
+            for a, behind in _turn_runs_of(ok):                # a chain: a maximal run of consecutive pairs that are steps
+                chain += 1
+                m = behind - a
+                G = np.cumsum(np.concatenate([np.zeros((1, 3)), b[a:behind]]), axis=0)      # G_0 .. G_m
+                table = np.full((m, 15), np.nan)
+                table[:, 0], table[:, 1], table[:, 2], table[:, 3], table[:, 4:7] = t1[a:behind], t2[a:behind], sY[a:behind], chain, G[1:]
+                table[:, 10], table[:, 11], table[:, 12] = sp[a:behind], ap[a:behind], ml[a:behind]
+                qx, qz = G[2:, 0] - G[:-2, 0], G[2:, 2] - G[:-2, 2]
+                L = np.sqrt(qx * qx + qz * qz)
+                has = L > 0
+                px, pz = qx / L, qz / L
+                bx, bz = b[a + 1:behind, 0], b[a + 1:behind, 2]
+                table[1:, 7] = np.where(has, L, np.nan)
+                table[1:, 8] = np.where(has, bx * px + bz * pz, np.nan)
+                table[1:, 9] = np.where(has, np.abs(bx * (-pz) + bz * px), np.nan)
+                for j in range(m):
+                    foot, lo, hi = ix[a + j], t1[a + j], t2[a + j]
+                    out[lo:hi + 1, 3:6] = G[j] + R[foot, lo:hi + 1]                # a later step overwrites the frame it shares: the largest t1
+                    out[lo:hi + 1, 6], out[lo:hi + 1, 7] = -sY[a + j], chain
+                    if j >= 1:
+                        W = np.concatenate([G[j - 1] + R[ix[a + j - 1], t1[a + j - 1]:lo], G[j] + R[foot, lo:hi + 1]])
+                        table[j, 13] = (W[:, 1].max() - W[:, 1].min()) + 0.0       # + 0.0: a spread of zeros of either sign is +0.0
+                        if has[j - 1]:
+                            lat = (W[:, 0] - G[j - 1, 0]) * (-pz[j - 1]) + (W[:, 2] - G[j - 1, 2]) * px[j - 1]
+                            table[j, 14] = (lat.max() - lat.min()) + 0.0
+                rows.extend(table)
+            rows = np.asarray(rows).reshape(-1, 15)
+            steps[q, :min(len(rows), max_steps)] = rows[:max_steps]
+            row = per_seq[q]
+            row[0], row[1], row[2] = np.count_nonzero(feet != 3), len(rows), chain + 1
+            row[3] = np.count_nonzero(~np.isnan(rows[:, 7]))
+            for col, src in zip((4, 6, 8, 11, 14, 16, 20, 22), (7, 8, 9, 10, 11, 12, 13, 14)):
+                values = rows[:, src]
+                row[col], row[col + 1] = _gait_mean_sd(values[~np.isnan(values)])
+            side = []
+            for src in (8, 12):
+                for sign in (1.0, -1.0):
+                    values = rows[rows[:, 2] == sign, src]
+                    values = values[~np.isnan(values)]
+                    side.append(_gait_sum(values) / len(values) if len(values) else np.nan)
+            if not np.isnan(side[0]) and not np.isnan(side[1]):
+                row[10] = (100.0 * abs(side[0] - side[1])) / (0.5 * (side[0] + side[1]))
+            row[18], row[19] = side[2], side[3]
+            if len(rows):
+                bs = b[ok]
+                row[13] = _gait_sum(np.sqrt(bs[:, 0] * bs[:, 0] + bs[:, 2] * bs[:, 2])) / _gait_sum((rows[:, 1] - rows[:, 0]) / fps)
+            f0 += T
+    return {"per_frame": per_frame, "steps": steps, "per_sequence": per_seq}
+
+
+def gait_balance(joints3d, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256,
+                 segments=BALANCE_SEGMENTS_KINECTV2, joints=GAIT_JOINTS_KINECTV2):
+    """Footprints on the floor, the centre of mass over them and the margin of stability at foot placement from 3D joints in numpy float64 (Hof, Gagey
+    and Halbertsma 2005; Winter 2009; the rules: DESIGN 4.22): the host statement of GRNet.gait_balance, same arguments, a dict of numpy arrays -- the
+    same operations in the same order.  joints3d (n,J,3) as gait_parameters takes them; events: its events; joints: its table, of which the two
+    ankles are read; segments: rows of (proximal joint, distal joint, mass, fraction).  THE FLOOR IS THE x-z PLANE OF A LEVEL, FIXED CAMERA; the
+    segment layout is unvalidated; the numbers are reported, never judged.  Also returns 'rel' (n,9) = [c, rL, rR]."""
+    j3 = _widened(joints3d, "joints3d")
+    n, J = j3.shape[:2]
+    lengths = _sequence_lengths(n, lengths)
+    tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
+    _balance_rule_check(fps, gravity, window, settle, max_step, max_steps)
+    prox, dist, mass, frac = _balance_segments(segments, J)
+    with np.errstate(all="ignore"):
+        num, den = np.zeros((n, 3)), 0.0
+        for i in range(len(mass)):
+            P, Dj = j3[:, prox[i]], j3[:, dist[i]]
+            num = num + mass[i] * (P + frac[i] * (Dj - P))
+            den = den + mass[i]
+        c = num / den
+        rel = np.concatenate([c, c - j3[:, tab[4]], c - j3[:, tab[5]]], axis=1)
+    out = gait_balance_steps(rel, events, lengths, fps, gravity, window, settle, max_step, max_steps)
+    out["rel"] = rel
     return out
 
 
