@@ -105,6 +105,14 @@ at foot placement, forward and sideways (Hof, Gagey and Halbertsma 2005; Mehdiza
 LEVEL, FIXED CAMERA; the stance ankle creeps forward at heel rise; a margin of a few centimetres carries about two of noise per step at 5 mm of
 joint noise.  Reported, never judged.
 
+--gait_bootstrap (opt-in, with --gait) puts an interval on the step and stride numbers: the samples behind them (one row per step and per stride,
+GRNet.gait_step_tables) are resampled with replacement --bootstrap_replicates times (Efron 1979; --bootstrap_block 2 keeps a left and a right step
+together, the circular block bootstrap of Politis and Romano 1992), and the --bootstrap_level percentile interval of every mean, SD and CV is read
+off the replicates (GRNet.bootstrap_table on the device).  With --gait_turns the same over straight walking alone, with
+--gait_balance over its step table.  <outpath>_bootstrap.json; the database gains nothing.  A PERCENTILE INTERVAL FROM SOME 15 STRIDES UNDER-COVERS
+(about 0.91 where 0.95 is asked), and the steps of one walk are serially correlated, which a block length addresses only partly.  Reported, never
+judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -437,10 +445,12 @@ class WindowTurns:
         if not keys:
             return []
         if self.device_call is not None:
-            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, gait_rows, lengths=lengths, **self.kw).items()}
+            made = self.device_call(j3, events, gait_rows, lengths=lengths, **self.kw)
+            out = {k: v.cpu().numpy() for k, v in made.items()}
         else:
             ev, rows = (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in (events, gait_rows))
-            out = self.pipe.gait_turns(j3.cpu().numpy(), ev, rows, lengths=lengths, **self.kw)
+            made = out = self.pipe.gait_turns(j3.cpu().numpy(), ev, rows, lengths=lengths, **self.kw)
+        self.phase = made["phase"]                             # for WindowBootstrap: the phase as this call returned it
 
         def number(v):
             return None if np.isnan(v) else float(v)
@@ -535,10 +545,12 @@ class WindowBalance:
         if not keys:
             return []
         if self.device_call is not None:
-            out = {k: v.cpu().numpy() for k, v in self.device_call(j3, events, lengths=lengths, **self.kw).items()}
+            made = self.device_call(j3, events, lengths=lengths, **self.kw)
+            out = {k: v.cpu().numpy() for k, v in made.items()}
         else:
             ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
-            out = self.pipe.gait_balance(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+            made = out = self.pipe.gait_balance(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+        self.tables = (made["steps"], made["per_sequence"])    # for WindowBootstrap: the step table and the rows as this call returned them
 
         def number(v):
             return float(v) if np.isfinite(v) else None          # a NaN is undefined; an asymmetry over a zero mean is infinite: null too, the file is strict JSON
@@ -562,6 +574,115 @@ class WindowBalance:
         with open(path, "w") as f:
             json.dump(self.videos, f, indent=1, allow_nan=False)
         print(f"Save balance of {len(self.videos)} videos to {path}.")
+        return path
+
+
+class WindowBootstrap:
+    """--gait_bootstrap: per database window on rank 0, after WindowGait's call (and WindowTurns' and WindowBalance's, where those ran), the step and
+    stride tables of that call's events and rows (model.gait_step_tables) and the bootstrap of their columns (model.bootstrap_table; on_host, or a
+    model without the methods: the pipeline's statements after a download).  Streams: 0 the steps (step time, length, width), 1 the strides (stride
+    time); with a phase of WindowTurns 2 and 3 the same over straight walking alone; 4 WindowBalance's step table (stride length, step length, step
+    width, MoS forward and sideways), its count made int32 on the device.  Per video and parameter: estimate (the sample's own value), lo, median and
+    hi of the `level` percent percentile interval, replicates (those that are not NaN) and n (the rows resampled); 'truncated', which names every
+    table that found more rows than it stores (max_rows, the balance call's max_steps) with both counts -- its first n rows are resampled, its
+    estimate is theirs and not the whole clip's column, and a line says so; the step and stride tables; the
+    cadence as 60 / hi .. 60 / lo of the step-time mean, labelled as derived.  A percentile interval from some 15 strides under-covers, and steps
+    within a walk are serially correlated (block = 2 keeps a left and a right step together); nothing is judged."""
+    STEP_NAMES, STRIDE_NAMES = ("step_time", "step_length", "step_width"), ("stride_time",)
+    BALANCE_COLUMNS, BALANCE_NAMES = (7, 8, 9, 11, 12), ("stride_length", "footprint_step_length", "footprint_step_width", "mos_ap", "mos_ml")
+
+    def __init__(self, pipe, model, on_host, fps=20.0, replicates=2000, level=95.0, block=1, seed=0, max_rows=256):
+        if int(replicates) != replicates or not 1 <= replicates <= 4096:
+            raise ValueError(f"replicates {replicates} outside [1, 4096]")
+        if not (np.isfinite(level) and 0 < level < 100):
+            raise ValueError(f"level {level} outside (0, 100) percent")
+        self.pipe = pipe
+        on_device = not on_host and hasattr(model, "gait_step_tables") and hasattr(model, "bootstrap_table")
+        self.device_call = model.bootstrap_table if on_device else None
+        self.tables_call = model.gait_step_tables if on_device else pipe.gait_step_tables
+        tail = int(round((100.0 - float(level)) * 50.0))       # basis points below the interval
+        self.kw = dict(B=int(replicates), block=int(block), seed=int(seed), quantiles=(tail, 5000, 10000 - tail))
+        self.fps, self.level, self.max_rows = float(fps), float(level), int(max_rows)
+        self.videos = {}
+
+    def _rows(self, table, counts, cols, stream):
+        """(n_seq, n_cols, 3, 5) numpy of one bootstrap call: per statistic [estimate, f, lo, median, hi]."""
+        if self.device_call is not None:
+            return self.device_call(table, counts, cols, stream=stream, **self.kw)["out"].cpu().numpy()
+        return self.pipe.bootstrap_table(table, counts, cols, stream=stream, **self.kw)["out"]
+
+    def add_window(self, keys, lengths, events, gait_rows, phase=None, balance=None):
+        """keys[vi], the videos' lengths and what WindowGait kept of its call: the events (sum T,) and the per-frame rows (sum T,7); phase (sum T,):
+        what WindowTurns kept, or None; balance: WindowBalance's (steps, per_sequence), or None."""
+        if not keys:
+            return
+        if self.device_call is None:
+            events, gait_rows, phase = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in (events, gait_rows, phase))
+            balance = None if balance is None else tuple(x.cpu().numpy() if hasattr(x, "cpu") else x for x in balance)
+
+        def host(x):
+            return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+        def number(v):
+            return float(v) if np.isfinite(v) else None          # a NaN is undefined, a CV over a zero mean infinite: null, the file is strict JSON
+
+        found = {}                                              # name -> (out (n_seq,3,5), rows resampled (n_seq,), rows found (n_seq,))
+        listed = None
+        for prefix, straight, streams in (("", False, (0, 1)),) + ((("straight_", True, (2, 3)),) if phase is not None else ()):
+            t = self.tables_call(events, gait_rows, lengths=lengths, fps=self.fps, max_rows=self.max_rows, phase=phase if straight else None, straight_only=straight)
+            counts = t["counts"]
+            seen = host(counts)
+            n = np.minimum(seen, self.max_rows)
+            for names, table, k, cols, stream in ((self.STEP_NAMES, t["steps"], 0, (3, 4, 5), streams[0]), (self.STRIDE_NAMES, t["strides"], 1, (3,), streams[1])):
+                out = self._rows(table, counts[:, k].contiguous() if hasattr(counts, "contiguous") else np.ascontiguousarray(counts[:, k]), cols, stream)
+                for i, name in enumerate(names):
+                    found[prefix + name] = (out[:, i], n[:, k], seen[:, k])
+            if not straight:
+                listed = (host(t["steps"]), host(t["strides"]))
+        if balance is not None:
+            steps, per_seq = balance
+            if hasattr(per_seq, "to"):
+                import torch
+                counts = per_seq[:, 1].to(torch.int32)         # the count of steps, made int32 on the device
+            else:
+                counts = np.asarray(per_seq[:, 1], np.int32)
+            out = self._rows(steps, counts, self.BALANCE_COLUMNS, 4)
+            seen = host(counts)
+            n = np.minimum(seen, steps.shape[1])
+            for i, name in enumerate(self.BALANCE_NAMES):
+                found[name] = (out[:, i], n, seen)
+        for vi, key in enumerate(keys):
+            par, cut = {}, {}
+            for name, (out, n, seen) in found.items():
+                if seen[vi] > n[vi]:                            # more rows than the table stores: the first n are resampled, and the estimate is theirs
+                    cut[name] = {"found": int(seen[vi]), "n": int(n[vi])}
+                for s, stat in enumerate(self.pipe.BOOTSTRAP_STATISTICS):
+                    est, f, lo, mid, hi = out[vi, s]
+                    par[f"{name}_{stat}"] = {"estimate": number(est), "lo": number(lo), "median": number(mid), "hi": number(hi), "replicates": int(f), "n": int(n[vi])}
+            step = par["step_time_mean"]
+            cadence = {"estimate": None if not step["estimate"] else 60.0 / step["estimate"], "lo": None if not step["hi"] else 60.0 / step["hi"],
+                       "hi": None if not step["lo"] else 60.0 / step["lo"], "derived": "60 / step_time_mean: lo from its hi, hi from its lo; not resampled itself"}
+            self.videos[key] = {"replicates": self.kw["B"], "level": self.level, "block": self.kw["block"], "seed": self.kw["seed"], "method": "percentile",
+                                "parameters": par, "cadence": cadence, "truncated": cut,
+                                "step_table": [{c: number(v) for c, v in zip(self.pipe.STEP_TABLE_COLUMNS, row)} for row in listed[0][vi] if not np.isnan(row[0])],
+                                "stride_table": [{c: number(v) for c, v in zip(self.pipe.STRIDE_TABLE_COLUMNS, row)} for row in listed[1][vi] if not np.isnan(row[0])]}
+
+            def shown(p, form, unit):
+                if p["estimate"] is None:
+                    return "none"
+                ends = "none" if p["lo"] is None or p["hi"] is None else f"{format(p['lo'], form)} to {format(p['hi'], form)}"
+                return f"{format(p['estimate'], form)}{unit} ({ends})"
+            print(f"Bootstrap: video {key}, stride time {shown(par['stride_time_mean'], '.3f', ' s')}, stride-time CV {shown(par['stride_time_cv'], '.2f', ' %')}: "
+                  f"{self.level:g} % percentile intervals of {self.kw['B']} replicates over {par['stride_time_mean']['n']} strides.")
+            if cut:
+                print(f"Bootstrap: video {key}: " + ", ".join(f"{name} has {c['found']} rows of which the first {c['n']} are resampled" for name, c in cut.items()) +
+                      ": these estimates are not the whole clip's columns.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save bootstrap intervals of {len(self.videos)} videos to {path}.")
         return path
 
 
@@ -995,8 +1116,11 @@ class WindowCoordination:
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None):
-    """balance: {'gravity', 'window', 'settle', 'max_step', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the footprints,
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None, bootstrap=None):
+    """bootstrap: {'replicates', 'level', 'block', 'seed', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the percentile
+    intervals of the step and stride parameters of every video (WindowBootstrap; with turns also over straight walking alone, with balance also of
+    its step table), written to bootstrap['out'] (default: outpath with _bootstrap.json); the database gains nothing.
+    balance: {'gravity', 'window', 'settle', 'max_step', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the footprints,
     stride length, step width, ground speed and margins of stability of every video (WindowBalance), written to balance['out'] (default: outpath with
     _balance.json); the database gains 'footprints_phase' (N,) int8 (the stance side of the frame's step: +1 left, -1 right, 0 none).
     coordination: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_lo', 'f_hi', 'min_segments', 'all_frames', 'on_host', 'out'} (each
@@ -1111,6 +1235,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     prints = WindowBalance(pipe, model, balance.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                            **{k: balance[k] for k in ("gravity", "window", "settle", "max_step") if balance.get(k) is not None}) \
         if balance is not None and rank == 0 else None
+    if bootstrap is not None and gait is None:
+        raise ValueError("bootstrap needs gait: it resamples the steps and strides of that call")
+    bars = WindowBootstrap(pipe, model, bootstrap.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
+                           **{k: bootstrap[k] for k in ("replicates", "level", "block", "seed") if bootstrap.get(k) is not None}) \
+        if bootstrap is not None and rank == 0 else None
     steady = WindowRegularity(pipe, model, regularity.get("on_host", False), not regularity.get("all_frames", False),
                               **({"fps": gait["fps"]} if regularity.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
                               **{k: regularity[k] for k in ("fps", "sigma", "max_lag", "min_lag", "min_peak", "min_pairs") if regularity.get(k) is not None}) \
@@ -1194,6 +1323,9 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             angles.add_window([v[0] for v in vids], *walk.window)
         gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
         gait_support = stands.add_window([v[0] for v in vids], *walk.window) if stands is not None and vids else None
+        if bars is not None and vids:
+            bars.add_window([v[0] for v in vids], walk.window[1], walk.window[2], walk.rows, rounds.phase if rounds is not None else None,
+                            prints.tables if prints is not None else None)
         if steady is not None and vids:
             steady.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None)
         if smooth is not None and vids:
@@ -1257,6 +1389,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         limbs.write(coordination.get("out") or osp.splitext(outpath)[0] + "_coordination.json")
     if prints is not None:
         prints.write(balance.get("out") or osp.splitext(outpath)[0] + "_balance.json")
+    if bars is not None:
+        bars.write(bootstrap.get("out") or osp.splitext(outpath)[0] + "_bootstrap.json")
     if comm is not None:
         torch.cuda.synchronize()
         comm.close()
@@ -1346,6 +1480,17 @@ def main(argv=None):
     p.add_argument("--balance_max_step", type=int, default=None, help="with --gait_balance: two heel strikes further apart than this many frames are no step (default 30)")
     p.add_argument("--balance_gravity", type=float, default=None, help="with --gait_balance: metres a second squared; the joints are SMPL metres (default 9.81)")
     p.add_argument("--balance_on_host", action="store_true", help="with --gait_balance: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_bootstrap", action="store_true", help="with --gait: percentile intervals of the step and stride parameters (mean, SD and CV of step time, step "
+                   "length, step width and stride time; with --gait_turns also over straight walking alone, with --gait_balance also of stride length, step length, "
+                   "step width and the margins of stability) by resampling the steps and strides with replacement on the device.  An interval from some 15 strides "
+                   "under-covers (about 0.91 where 0.95 is asked) and the steps of a walk are serially correlated; reported, never judged")
+    p.add_argument("--bootstrap_out", type=str, default="", help="with --gait_bootstrap: the JSON file (default: --outpath with _bootstrap.json)")
+    p.add_argument("--bootstrap_replicates", type=int, default=None, help="with --gait_bootstrap: the resamples B, 1 to 4096 (default 2000)")
+    p.add_argument("--bootstrap_level", type=float, default=None, help="with --gait_bootstrap: the interval's level in percent (default 95: the 2.5 and 97.5 percent points)")
+    p.add_argument("--bootstrap_block", type=int, default=None, help="with --gait_bootstrap: rows are drawn in circular blocks of this many consecutive ones, 1 to 1024; 2 keeps "
+                   "a left and a right step together (default 1, the plain bootstrap)")
+    p.add_argument("--bootstrap_seed", type=int, default=None, help="with --gait_bootstrap: the generator's seed, 0 to 2^64 - 1 (default 0); equal seeds give equal files")
+    p.add_argument("--bootstrap_on_host", action="store_true", help="with --gait_bootstrap: the numpy statement instead of the GPU kernels (the same bits)")
     p.add_argument("--gait_regularity", action="store_true", help="with --vid_folder (no --gait needed): step and stride regularity, symmetry and a cadence WITHOUT events, "
                    "from the autocorrelation of four body signals (Moe-Nilssen and Helbostad 2004): <outpath>_regularity.json, one line per video; takes "
                    "--gait_fps where given; with --gait_turns only straight walking counts; the defaults are unvalidated on the model's output")
@@ -1556,6 +1701,20 @@ def main(argv=None):
                         ("--balance_max_step", a.balance_max_step is not None), ("--balance_gravity", a.balance_gravity is not None), ("--balance_on_host", a.balance_on_host)):
         if given and not a.gait_balance:
             sys.exit(f"batch_generation.py: {flag} belongs to --gait_balance, which was not given")
+    if a.gait_bootstrap and not a.gait:
+        sys.exit("batch_generation.py: --gait_bootstrap belongs to --gait, which was not given (it resamples the steps and strides of that call)")
+    for flag, given in (("--bootstrap_out", bool(a.bootstrap_out)), ("--bootstrap_replicates", a.bootstrap_replicates is not None), ("--bootstrap_level", a.bootstrap_level is not None),
+                        ("--bootstrap_block", a.bootstrap_block is not None), ("--bootstrap_seed", a.bootstrap_seed is not None), ("--bootstrap_on_host", a.bootstrap_on_host)):
+        if given and not a.gait_bootstrap:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_bootstrap, which was not given")
+    if a.bootstrap_replicates is not None and not 1 <= a.bootstrap_replicates <= 4096:
+        sys.exit("batch_generation.py: --bootstrap_replicates must be within 1 to 4096")
+    if a.bootstrap_level is not None and not (np.isfinite(a.bootstrap_level) and 0 < a.bootstrap_level < 100):
+        sys.exit("batch_generation.py: --bootstrap_level must lie between 0 and 100 percent")
+    if a.bootstrap_block is not None and not 1 <= a.bootstrap_block <= 1024:
+        sys.exit("batch_generation.py: --bootstrap_block must be within 1 to 1024 rows")
+    if a.bootstrap_seed is not None and not 0 <= a.bootstrap_seed < 2**64:
+        sys.exit("batch_generation.py: --bootstrap_seed must be within 0 to 2^64 - 1")
     if a.balance_window is not None and not 1 <= a.balance_window <= 16:
         sys.exit("batch_generation.py: --balance_window must be within 1 to 16 frames")
     if a.balance_settle is not None and not 0 <= a.balance_settle <= 4:
@@ -1782,6 +1941,8 @@ def main(argv=None):
                     "all_frames": a.coordination_all_frames, "on_host": a.coordination_on_host, "out": a.coordination_out or None} if a.gait_coordination else None
     balance = {"gravity": a.balance_gravity, "window": a.balance_window, "settle": a.balance_settle, "max_step": a.balance_max_step, "on_host": a.balance_on_host,
                "out": a.balance_out or None} if a.gait_balance else None
+    bootstrap = {"replicates": a.bootstrap_replicates, "level": a.bootstrap_level, "block": a.bootstrap_block, "seed": a.bootstrap_seed, "on_host": a.bootstrap_on_host,
+                 "out": a.bootstrap_out or None} if a.gait_bootstrap else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
                  synthetic_weights=a.synthetic_weights, max_frames=a.max_frames, dtype=a.dtype, chunk=a.chunk, exchange=a.exchange, full_arena=a.full_arena, annos=annos,
                  gt_path=a.gt_path or None, metrics_out=a.metrics_out or None, metrics_on_host=a.metrics_on_host, trajectory=trajectory, tracks=tracks, gait=gait,
@@ -1790,7 +1951,8 @@ def main(argv=None):
                  **({"harmonics": harmonics} if harmonics is not None else {}), **({"entropy": entropy} if entropy is not None else {}),
                  **({"stability": stability} if stability is not None else {}),
                  **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}),
-                 **({"coordination": coordination} if coordination is not None else {}), **({"balance": balance} if balance is not None else {}))
+                 **({"coordination": coordination} if coordination is not None else {}), **({"balance": balance} if balance is not None else {}),
+                 **({"bootstrap": bootstrap} if bootstrap is not None else {}))
 
 
 if __name__ == "__main__":

@@ -1024,6 +1024,50 @@ int grnet_op_gait_balance_steps(grnet_t* h, const double* rel_dev, const int32_t
                                 double gravity, int window, int settle, int max_step, int max_steps, double* per_frame_dev, double* steps_dev,
                                 double* per_seq_dev, void* stream);
 
+/* The samples behind the gait call's step and stride columns, one row per step and per stride (which is the specification).
+ * events_dev int32 (sum T) and per_frame_dev float64 (sum T, 7) as grnet_gait_parameters returned them, frame_offsets_host as there; phase_dev int32
+ * (sum T): the per-frame phase of grnet_gait_turns, or null.  With phase_dev and straight_only != 0 only the steps and strides are listed that the
+ * straight columns of grnet_gait_turns count: no frame of [opening strike, closing strike] has a phase other than 0.
+ *   step    consecutive heel strikes in time order (the left foot first where both strike in one frame) on different feet, pt and t with the landing
+ *           foot F: [pt, t, F (0 left, 1 right), (t - pt) / fps, row_t[F] - row_t[1 - F], row_t[4]]
+ *   stride  consecutive heel strikes t0, t1 of one foot: [t0, t1, foot, (t1 - t0) / fps]; the left foot's strides first, then the right foot's
+ * steps_dev (n_seq, max_rows, 6), strides_dev (n_seq, max_rows, 4) float64, NaN rows past the count; counts_dev int32 (n_seq, 2): the steps and the
+ * strides found -- those past max_rows are counted, not stored.  Mean, SD and CV of these columns in row order ARE columns 5, 6, 8 .. 14 of the gait
+ * call's row (straight-only: of the turn call's straight columns) in every bit.
+ * One launch behind one small copy from pinned memory, a workgroup per sequence, no atomics, no host synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer other than phase_dev, straight_only without
+ * phase_dev, fps not positive and finite, max_rows outside [1, 1024], n_seq outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase. */
+int grnet_gait_step_tables(grnet_t* h, const int32_t* events_dev, const double* per_frame_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                           int max_rows, const int32_t* phase_dev, int straight_only, double* steps_dev, double* strides_dev, int32_t* counts_dev, void* stream);
+
+/* Nonparametric bootstrap of the mean, the SD and the CV of columns of a per-step table (Efron 1979; with block > 1 the circular block bootstrap of
+ * Politis and Romano 1992; DESIGN.md 4.23, which is the specification).  A PERCENTILE INTERVAL FROM SOME 15 STRIDES UNDER-COVERS (about 0.91 where 0.95
+ * is asked), steps within a walk are serially correlated, which block addresses only partly (2 keeps a left and a right step
+ * together); numbers are reported, never judged.
+ * table_dev float64 (n_seq, max_rows, C): any table of this layout -- the two above, grnet_gait_balance's steps; counts_dev int32 (n_seq): the rows n
+ * of each sequence, a count above max_rows is read as max_rows (below 0 as 0); cols_host int32 (n_cols): the columns to resample; quantiles_host int32
+ * (n_q) in basis points.
+ *   generator  uint64, wrapping: G = 0x9E3779B97F4A7C15; mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB,
+ *              z ^ z >> 31; u(seed, stream, r, j) = mix(mix(mix(seed + G (stream + 1)) + G (r + 1)) + G (j + 1)); index(u, n) = ((u >> 32) n) >> 32,
+ *              whose bias is below n / 2^32: stated, not corrected
+ *   resample   by rows -- all columns of a replicate share the indices.  Replicate 0 is the sample, idx(p) = p; replicate r = 1 .. B has idx(p) =
+ *              (index(u(seed, stream, r, p / block), n) + p % block) % n, p = 0 .. n - 1.  The draws do not depend on the sequence's place in the
+ *              call: a sequence has the same bits alone or among others, and TWO SEQUENCES WITH EQUAL n GET EQUAL INDICES
+ *   statistics per replicate and column in float64, one rounding per operation, over p in order from +0.0, skipping NaN values, m the count kept:
+ *              mean = S / m, SD = sqrt(sum (x - mean)^2 / m), CV = (100 SD) / mean; all NaN where m = 0
+ *   selection  per statistic the replicates 1 .. B that are not NaN, ordered by (value under <, then replicate number), f their count; a quantile q is
+ *              the element of rank (q (f - 1)) / 10000 by integer division, NaN where f = 0
+ * out_dev float64 (n_seq, n_cols, 3, 2 + n_q): per statistic [replicate 0, f, the quantiles]; replicates_dev float64 (n_seq, n_cols, 3, B): the
+ * replicates 1 .. B, or null.
+ * One launch whatever n_seq, a workgroup per (sequence, column, statistic), lanes over replicates; no atomics, no float sum across lanes, no scratch, no host
+ * synchronisation.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null pointer other than replicates_dev (quantiles_host may be
+ * null where n_q is 0), n_seq outside [1, 8192], max_rows outside [1, 1024], C outside [1, 16], n_cols outside [1, 8], a column outside [0, C), B
+ * outside [1, 4096], block outside [1, 1024], stream_id outside [0, 65535], n_q outside [0, 5], a quantile outside [0, 10000]. */
+int grnet_bootstrap_table(grnet_t* h, const double* table_dev, const int32_t* counts_dev, int n_seq, int max_rows, int C, const int32_t* cols_host, int n_cols,
+                          int B, int block, uint64_t seed, int stream_id, const int32_t* quantiles_host, int n_q, double* out_dev, double* replicates_dev,
+                          void* stream);
+
 /* Recurrence quantification of the same four body signals (Webber and Zbilut 1994; Marwan et al. 2007; on gait Labini et al. 2012 and Riva et al.
  * 2013 -- on a trunk sensor over minutes of walking; these signals are joint positions of a pose model over some 15 strides, the radius rule is this
  * project's and the defaults are unvalidated on its output): every pair of points of the delay-embedded signal against one radius, and the runs of

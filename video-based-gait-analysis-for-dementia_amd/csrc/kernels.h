@@ -528,6 +528,20 @@ hipError_t launch_balance_steps(const int* off, int n_seq, const BalanceRule& ru
 hipError_t launch_balance_path(const int* off, int n_seq, int frames, const double* rel, const unsigned long long* words, size_t mask_words,
                                const double* pairs, double* per_frame, hipStream_t s);
 
+// The gait call's per-step and per-stride tables and bootstrap intervals of a per-step table (csrc/gait_bootstrap_kernels.hip, compiled without fma
+// contraction; the arithmetic and the generator: csrc/gait_bootstrap.h).  The table kernel's workgroup is the gait call's kGaitThreads
+// and its LDS masks are kGaitLdsWords long ----
+struct BootRule;                           // gait_bootstrap.h: the table's shape, the columns, B, block, seed, stream and the quantiles, a kernel argument
+constexpr int kStepMaskSets = 3;           // left and right heel strikes, and the frames that are not straight
+constexpr int kBootThreads = 1024;         // lanes of the bootstrap's workgroup: each takes the replicates lane, lane + 1024, ...
+constexpr int kBootRounds = 5;             // replicates of a lane at most: 0 .. 4096 over 1024 lanes
+// one workgroup per sequence on the gait call's events (frames) and rows (frames,7); phase (frames) or null (null: every step and stride is listed):
+// steps (n_seq,max_rows,6), strides (n_seq,max_rows,4), counts (n_seq,2); words: kStepMaskSets * mask_words (gait_mask_words) of scratch
+hipError_t launch_step_tables(const int* off, int n_seq, const int* events, const int* phase, const double* per_frame, double fps, int max_rows,
+                              unsigned long long* words, size_t mask_words, double* steps, double* strides, int* counts, hipStream_t s);
+// one workgroup per (sequence, column, statistic) on table (n_seq,max_rows,C) and counts (n_seq): out (n_seq,n_cols,3,2 + n_q), replicates (n_seq,n_cols,3,B) or null
+hipError_t launch_bootstrap(const double* table, const int* counts, int n_seq, const BootRule& rule, double* out, double* replicates, hipStream_t s);
+
 // Recurrence quantification of the same four signals (csrc/gait_recurrence_kernels.hip, compiled without fma contraction; the arithmetic:
 // csrc/gait_recurrence.h).  The frame kernel is launch_reg_frames ----
 struct RecRule;                            // gait_recurrence.h: derivative, dim, lag, theiler, radius

@@ -1723,6 +1723,70 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_balance_steps")
         return out
 
+    # ------------------------------------------------------------------ step and stride tables, bootstrap intervals
+    def gait_step_tables(self, events, per_frame, lengths=None, fps=20.0, max_rows=256, phase=None, straight_only=False):
+        """The samples behind gait_parameters' step and stride columns of every sequence on the device (grnet_gait_step_tables; DESIGN 4.23,
+        pipeline.STEP_TABLE_COLUMNS, pipeline.STRIDE_TABLE_COLUMNS).  events (sum T,) and per_frame (sum T,7): what gait_parameters returned, taken
+        as int32 and float64; phase (sum T,): gait_turns' phase, with straight_only the steps and strides its straight columns count are listed
+        alone.  Returns a dict of device tensors: steps (n_seq,max_rows,6) float64 [t_prev, t, landing foot, step time, step length, step width];
+        strides (n_seq,max_rows,4) float64 [t0, t1, foot, stride time], the left foot's first; counts (n_seq,2) int32 -- rows past max_rows are
+        counted, not stored, rows past the count are NaN.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        rows = self._rows_input(per_frame, "per_frame", (7,), torch.float64)
+        n = rows.shape[0]
+        ev = self._events_input(n, events)
+        ph = None
+        if phase is not None:
+            ph = torch.as_tensor(phase).to(self.device, torch.int32).contiguous()
+            if tuple(ph.shape) != (n,):
+                raise ValueError(f"phase must be ({n},), got {tuple(ph.shape)}")
+        if straight_only and ph is None:
+            raise ValueError("straight_only needs a phase")
+        self._whole_frames(max_rows=max_rows)
+        if not 1 <= int(max_rows) <= 1024:
+            raise ValueError(f"max_rows {max_rows} outside [1, 1024]")      # the tables are allocated here: a size the C ABI would refuse is refused first
+        off = self._sequence_offsets(n, lengths, "per_frame")
+        n_seq = len(off) - 1
+        out = {"steps": torch.empty(n_seq, int(max_rows), 6, dtype=torch.float64, device=self.device),
+               "strides": torch.empty(n_seq, int(max_rows), 4, dtype=torch.float64, device=self.device),
+               "counts": torch.empty(n_seq, 2, dtype=torch.int32, device=self.device)}
+        rc = self._lib.grnet_gait_step_tables(self._h, ev.data_ptr(), rows.data_ptr(), _i32p(off), n_seq, float(fps), int(max_rows),
+                                              None if ph is None else ph.data_ptr(), int(bool(straight_only)), out["steps"].data_ptr(),
+                                              out["strides"].data_ptr(), out["counts"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_step_tables")
+        return out
+
+    def bootstrap_table(self, table, counts, cols, B=2000, block=1, seed=0, stream=0, quantiles=(250, 5000, 9750), return_replicates=False):
+        """Bootstrap of mean, SD and CV of columns of a per-step table on the device (grnet_bootstrap_table; the generator, the resampling, the
+        statistics and the selection: DESIGN 4.23).  table (n_seq,max_rows,C) float64 with C <= 16 -- gait_step_tables' steps or strides,
+        gait_balance's steps; counts (n_seq,) int32: the rows of each sequence (above max_rows: max_rows); cols: at most 8 columns; B in [1, 4096]
+        replicates of rows drawn in circular blocks of `block`; quantiles in basis points, at most 5.  Returns a dict of device tensors: out
+        (n_seq,n_cols,3,2 + n_q) float64, per statistic (mean, SD, CV) [the sample's own, the count f of replicates that are not NaN, the quantiles];
+        with return_replicates, replicates (n_seq,n_cols,3,B).  Two sequences with equal counts get equal indices; a sequence has the same bits alone
+        or among others.  A percentile interval from some 15 strides under-covers.  Works before finalize().  Nothing synchronises."""
+        t = torch.as_tensor(table)
+        if t.dim() != 3 or min(t.shape) < 1:
+            raise ValueError(f"table must be (n_seq,max_rows,C), got {tuple(t.shape)}")
+        t = t.to(self.device, torch.float64).contiguous()
+        n_seq, max_rows, width = t.shape
+        cnt = torch.as_tensor(counts).to(self.device, torch.int32).contiguous()
+        if tuple(cnt.shape) != (n_seq,):
+            raise ValueError(f"counts must be ({n_seq},), got {tuple(cnt.shape)}")
+        pick, q = np.asarray(cols, np.int64).reshape(-1), np.asarray(quantiles, np.int64).reshape(-1)
+        self._whole_frames(B=B, block=block, seed=seed, stream=stream)
+        if not 1 <= pick.size <= 8 or q.size > 5 or not 1 <= int(B) <= 4096:
+            raise ValueError(f"cols must name 1 to 8 columns, quantiles at most 5 and B lie in [1, 4096], got {pick.size}, {q.size} and {B}")      # the outputs are allocated here
+        if np.abs(pick).max() >= 2**31 or (q.size and np.abs(q).max() >= 2**31) or not 0 <= int(seed) < 2**64 or abs(int(stream)) >= 2**31 or abs(int(block)) >= 2**31:
+            raise ValueError("cols, quantiles, stream and block must fit 32 bits and seed 64")
+        pick, q = np.ascontiguousarray(pick, np.int32), np.ascontiguousarray(q, np.int32)
+        out = {"out": torch.empty(n_seq, pick.size, 3, 2 + q.size, dtype=torch.float64, device=self.device)}
+        if return_replicates:
+            out["replicates"] = torch.empty(n_seq, pick.size, 3, int(B), dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_bootstrap_table(self._h, t.data_ptr(), cnt.data_ptr(), n_seq, max_rows, width, _i32p(pick), int(pick.size), int(B), int(block),
+                                             int(seed), int(stream), _i32p(q) if q.size else None, int(q.size), out["out"].data_ptr(),
+                                             out["replicates"].data_ptr() if return_replicates else None, self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_bootstrap_table")
+        return out
+
     # ------------------------------------------------------------------ the 3D skeleton view (demo.py --skeleton_view)
     def spin_joints(self, joints29, verts, joints="spin49"):
         """The joints of smooth_pose without the filter and without an SMPL pass (grnet_spin_joints): joints29 (n,29,3) and verts (n,6890,3) as a

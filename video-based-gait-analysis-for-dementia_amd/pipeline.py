@@ -2939,6 +2939,179 @@ def gait_balance(joints3d, events, lengths=None, fps=20.0, gravity=9.81, window=
     return out
 
 
+# ----------------------------------------------------------------------------- step and stride tables, bootstrap intervals
+STEP_TABLE_COLUMNS = ("t_prev", "t", "landing_foot", "step_time", "step_length", "step_width")
+STRIDE_TABLE_COLUMNS = ("t0", "t1", "foot", "stride_time")
+BOOTSTRAP_STATISTICS = ("mean", "sd", "cv")
+BOOTSTRAP_OUT_COLUMNS = ("estimate", "replicates")            # then one column per quantile
+_BOOT_GOLDEN, _BOOT_M1, _BOOT_M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+def gait_step_tables(events, per_frame, lengths=None, fps=20.0, max_rows=256, phase=None, straight_only=False):
+    """The samples behind gait_parameters' step and stride columns in numpy float64: the host statement of GRNet.gait_step_tables, same
+    arguments, a dict of numpy arrays.  events (n,) and per_frame (n,7) as gait_parameters returned them; phase (n,): gait_turns' phase -- with
+    straight_only only the steps and strides with no frame of [opening strike, closing strike] in a phase other than 0 are listed.  steps
+    (n_seq,max_rows,6), columns STEP_TABLE_COLUMNS, in time order; strides (n_seq,max_rows,4), columns STRIDE_TABLE_COLUMNS, the left foot's first;
+    counts (n_seq,2) int32: rows past max_rows are counted, not stored; rows past the count are NaN."""
+    rows = np.asarray(per_frame, np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 7 or rows.shape[0] < 1:
+        raise ValueError(f"per_frame must be (n,7) with n >= 1, got {rows.shape}")
+    n = rows.shape[0]
+    ev = np.asarray(events)
+    if ev.shape != (n,):
+        raise ValueError(f"events must be ({n},), got {ev.shape}")
+    ev = ev.astype(np.int64)
+    ph = None
+    if phase is not None:
+        ph = np.asarray(phase)
+        if ph.shape != (n,):
+            raise ValueError(f"phase must be ({n},), got {ph.shape}")
+    if straight_only and ph is None:
+        raise ValueError("straight_only needs a phase")
+    lengths = _sequence_lengths(n, lengths)
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if int(max_rows) != max_rows or not 1 <= max_rows <= 1024:
+        raise ValueError(f"max_rows {max_rows} outside [1, 1024]")
+    fps, max_rows = float(fps), int(max_rows)
+    steps = np.full((len(lengths), max_rows, 6), np.nan)
+    strides = np.full((len(lengths), max_rows, 4), np.nan)
+    counts = np.zeros((len(lengths), 2), np.int32)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            e, r = ev[a:a + T], rows[a:a + T]
+            busy = np.concatenate([[0], np.cumsum(ph[a:a + T] != TURN_STRAIGHT)]) if straight_only else np.zeros(T + 1, np.int64)
+            heel = [np.flatnonzero(e & GAIT_HEEL_L), np.flatnonzero(e & GAIT_HEEL_R)]
+            strikes = sorted([(int(t), 0) for t in heel[0]] + [(int(t), 1) for t in heel[1]])      # time order, the left foot first within a frame
+            found = [(t1, t2, f2) for (t1, f1), (t2, f2) in zip(strikes[:-1], strikes[1:]) if f1 != f2 and busy[t2 + 1] == busy[t1]]
+            for i, (t1, t2, f2) in enumerate(found[:max_rows]):
+                steps[q, i] = t1, t2, f2, float(t2 - t1) / fps, r[t2, f2] - r[t2, 1 - f2], r[t2, 4]
+            pairs = [(int(t1), int(t2), foot) for foot in (0, 1) for t1, t2 in zip(heel[foot][:-1], heel[foot][1:]) if busy[int(t2) + 1] == busy[int(t1)]]
+            for i, (t1, t2, foot) in enumerate(pairs[:max_rows]):
+                strides[q, i] = t1, t2, foot, float(t2 - t1) / fps
+            counts[q] = len(found), len(pairs)
+            a += T
+    return {"steps": steps, "strides": strides, "counts": counts}
+
+
+def bootstrap_mix(z):
+    """splitmix64's output function on a numpy uint64 array (Steele, Lea and Flood 2014): integers alone, wrapping."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(z, np.uint64)
+        z = (z ^ (z >> np.uint64(30))) * _BOOT_M1
+        z = (z ^ (z >> np.uint64(27))) * _BOOT_M2
+        return z ^ (z >> np.uint64(31))
+
+
+def bootstrap_u(seed, stream, r, j):
+    """u(seed, stream, r, j) = mix(mix(mix(seed + G (stream + 1)) + G (r + 1)) + G (j + 1)) in uint64, wrapping; r and j broadcast."""
+    with np.errstate(over="ignore"):
+        one = np.uint64(1)
+        key = bootstrap_mix(np.array(int(seed) % 2**64, np.uint64) + _BOOT_GOLDEN * (np.uint64(int(stream)) + one))
+        key = bootstrap_mix(key + _BOOT_GOLDEN * (np.asarray(r).astype(np.uint64) + one))
+        return bootstrap_mix(key + _BOOT_GOLDEN * (np.asarray(j).astype(np.uint64) + one))
+
+
+def bootstrap_index(u, n):
+    """((u >> 32) n) >> 32: an index below n whose bias is below n / 2^32 -- stated, not corrected."""
+    return ((np.asarray(u, np.uint64) >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)
+
+
+def bootstrap_indices(n, B, block=1, seed=0, stream=0):
+    """(B + 1, n) int64: row 0 is the sample itself, row r = 1 .. B the circular block bootstrap idx(p) = (index(u(seed, stream, r, p / block), n) +
+    p % block) % n.  Nothing here depends on which sequence asks: two sequences with equal n get equal indices."""
+    p = np.arange(n, dtype=np.int64)
+    idx = np.empty((B + 1, n), np.int64)
+    idx[0] = p
+    if n:
+        start = bootstrap_index(bootstrap_u(seed, stream, np.arange(1, B + 1)[:, None], (p // block)[None, :]), n).astype(np.int64)
+        idx[1:] = (start + p % block) % n
+    return idx
+
+
+def _bootstrap_rule_check(max_rows, C, cols, B, block, seed, stream, quantiles):
+    if not 1 <= max_rows <= 1024:
+        raise ValueError(f"max_rows {max_rows} outside [1, 1024]")
+    if not 1 <= C <= 16:
+        raise ValueError(f"C {C} outside [1, 16]")
+    if not 1 <= len(cols) <= 8:
+        raise ValueError(f"n_cols {len(cols)} outside [1, 8]")
+    if any(int(c) != c or not 0 <= c < C for c in cols):
+        raise ValueError(f"column outside [0, {C})")
+    if int(B) != B or not 1 <= B <= 4096:
+        raise ValueError(f"B {B} outside [1, 4096]")
+    if int(block) != block or not 1 <= block <= 1024:
+        raise ValueError(f"block {block} outside [1, 1024]")
+    if int(seed) != seed or not 0 <= seed < 2**64:
+        raise ValueError(f"seed {seed} outside [0, 2^64)")
+    if int(stream) != stream or not 0 <= stream <= 65535:
+        raise ValueError(f"stream {stream} outside [0, 65535]")
+    if len(quantiles) > 5:
+        raise ValueError(f"n_q {len(quantiles)} outside [0, 5]")
+    if any(int(v) != v or not 0 <= v <= 10000 for v in quantiles):
+        raise ValueError("quantile outside [0, 10000] basis points")
+
+
+def bootstrap_select(values, quantiles):
+    """[f, the quantiles] of one statistic's replicates 1 .. B: those that are not NaN in the order (value under <, then replicate number) -- a stable
+    sort, under which -0 and +0 tie -- f their count, a quantile of q basis points the element of rank (q (f - 1)) // 10000, NaN where f = 0."""
+    v = np.asarray(values, np.float64)
+    kept = v[~np.isnan(v)]
+    kept = kept[np.argsort(kept, kind="stable")]
+    return [float(kept.size)] + [kept[(int(q) * (kept.size - 1)) // 10000] if kept.size else np.nan for q in quantiles]
+
+
+def bootstrap_table(table, counts, cols, B=2000, block=1, seed=0, stream=0, quantiles=(250, 5000, 9750), return_replicates=False):
+    """Nonparametric bootstrap of mean, SD and CV of columns of a per-step table in numpy float64 (Efron 1979; block > 1: the circular block bootstrap
+    of Politis and Romano 1992; the rules: DESIGN 4.23): the host statement of GRNet.bootstrap_table, same arguments, a dict of numpy arrays.  table
+    (n_seq,max_rows,C); counts (n_seq,): the rows of each sequence, above max_rows read as max_rows.  Rows are resampled: all columns of a replicate
+    share the indices (bootstrap_indices).  Per replicate and column, over the rows in order from +0.0 and skipping NaN values (m kept): mean = S / m,
+    SD = sqrt(sum (x - mean)^2 / m), CV = (100 SD) / mean, NaN where m = 0 -- gait_strides' operations in its order, every sum a cumulative sum.  out
+    (n_seq,n_cols,3,2 + n_q): per statistic [replicate 0, f, the quantiles] (bootstrap_select); replicates (n_seq,n_cols,3,B) on request.  A
+    PERCENTILE INTERVAL FROM SOME 15 STRIDES UNDER-COVERS, and steps within a walk are serially correlated; the numbers are reported, never judged."""
+    t = np.asarray(table, np.float64)
+    if t.ndim != 3 or min(t.shape) < 1:
+        raise ValueError(f"table must be (n_seq,max_rows,C), got {t.shape}")
+    n_seq, max_rows, C = t.shape
+    cnt = np.asarray(counts)
+    if cnt.shape != (n_seq,):
+        raise ValueError(f"counts must be ({n_seq},), got {cnt.shape}")
+    cols, quantiles = [v for v in np.asarray(cols).reshape(-1).tolist()], [v for v in np.asarray(quantiles).reshape(-1).tolist()]
+    _bootstrap_rule_check(max_rows, C, cols, B, block, seed, stream, quantiles)
+    cols, quantiles, B, block = [int(c) for c in cols], [int(v) for v in quantiles], int(B), int(block)
+    out = np.full((n_seq, len(cols), 3, 2 + len(quantiles)), np.nan)
+    reps = np.full((n_seq, len(cols), 3, B), np.nan)
+    made = {}
+    with np.errstate(all="ignore"):
+        for q in range(n_seq):
+            n = int(min(max(int(cnt[q]), 0), max_rows))
+            if n not in made:
+                made[n] = bootstrap_indices(n, B, block, seed, stream)
+            for k, c in enumerate(cols):
+                stats = np.full((B + 1, 3), np.nan)
+                if n:
+                    x = t[q, :n, c][made[n]]                      # (B + 1, n)
+                    gone = np.isnan(x)
+                    m = (n - gone.sum(axis=1)).astype(np.float64)
+                    some = m > 0
+                    # both sums begin at +0.0 (the column of zeros in front: -0.0 alone sums to +0.0), so a sum is never -0.0 and a skipped value,
+                    # which adds +0.0 here, changes no bit of it
+                    zero = np.zeros((B + 1, 1))
+                    mean = np.cumsum(np.concatenate([zero, np.where(gone, 0.0, x)], axis=1), axis=1)[:, -1] / m
+                    d = np.where(gone, 0.0, x - mean[:, None])
+                    sd = np.sqrt(np.cumsum(np.concatenate([zero, d * d], axis=1), axis=1)[:, -1] / m)
+                    stats[:, 0], stats[:, 1], stats[:, 2] = np.where(some, mean, np.nan), np.where(some, sd, np.nan), np.where(some, (100.0 * sd) / mean, np.nan)
+                for s in range(3):
+                    out[q, k, s, 0] = stats[0, s]
+                    out[q, k, s, 1:] = bootstrap_select(stats[1:, s], quantiles)
+                    reps[q, k, s] = stats[1:, s]
+    result = {"out": out}
+    if return_replicates:
+        result["replicates"] = reps
+    return result
+
+
 def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
