@@ -77,6 +77,14 @@ segments the Hann window alone makes the peak about 0.45 Hz wide at half height,
 walker, and the defaults are unvalidated on the model's output.  With --gait_turns a turn splits the walk into straight runs.  Reported, never
 judged.
 
+--gait_smoothness (opt-in, needs no --gait) reports the movement smoothness of the same four body signals, per segment of ongoing walking: the
+spectral arc length (SPARC) of the speed profile's zero-padded magnitude spectrum and the log dimensionless jerk (LDLJ) of Balasubramanian et al.
+2015, as Beck et al. 2018 apply them to gait.  The device makes every segment's magnitudes, band and arc length and the dimensionless jerk
+(GRNet.gait_smoothness); the logarithm is pipeline.smoothness_rows'.  <outpath>_smoothness.json.  These signals are joint positions of
+a pose model at 20 fps, where the cut-off of 10 Hz is the Nyquist frequency; a segment's rectangular window alone gives a noiseless sinusoid SPARC
+about -4 at 64 frames, with 5 mm of joint noise a good part of the number is the noise, and the defaults are unvalidated on the model's output.
+With --gait_turns a turn splits the walk into straight runs.  Reported, never judged.
+
 --gait_recurrence (opt-in, needs no --gait) reports the recurrence quantification of the same four body signals: every pair of states of the
 delay-embedded signal against one radius, and the diagonal lines of recurrent pairs by their length -- recurrence rate, determinism, mean and longest
 line, divergence and the entropy of the line lengths (Webber and Zbilut 1994, Marwan et al. 2007), which the gait studies report beside harmonic
@@ -1048,6 +1056,68 @@ class WindowSpectrum:
         return path
 
 
+class WindowSmoothness:
+    """--gait_smoothness: one gait_smoothness call per database window on rank 0, one sequence per video, on the joints the window's gather left on
+    the device (model.gait_smoothness; on_host, or a model without the method: pipeline.gait_smoothness after a download) -- with the window's
+    translations where --trajectory made them, and with --gait_turns' phase as `exclude` (straight_only): a turn then splits the walk into straight
+    runs, and every run's segments count.  It needs no events and so no --gait.  Either way the logarithm of the jerk is pipeline.smoothness_rows'.
+    Per video and channel (pipeline.SMOOTHNESS_CHANNELS) the columns of pipeline.SMOOTHNESS_COLUMNS, 'ldlj_mean', 'ldlj_sd' and the list 'segments'
+    (start, sparc, last_hz, ldlj); null where undefined.  The joints are pipeline.GAIT_JOINTS_KINECTV2.  THE INPUTS ARE JOINT POSITIONS OF A POSE
+    MODEL AT 20 FPS, where 10 Hz is the Nyquist frequency; a segment's rectangular window alone sets a floor (SPARC about -4 at 64 frames) and with
+    5 mm of joint noise a good part of the number is the noise; the defaults are unvalidated on the model's output; the results are reported and
+    never judged.  The database gains nothing."""
+
+    def __init__(self, pipe, model, on_host, straight_only, fps=20.0, sigma=0.0, derivative=1, segment=64, hop=None, nfft=1024, f_cut=None, amplitude=0.05,
+                 min_segments=2):
+        self.pipe = pipe
+        self.device_call = None if on_host or not hasattr(model, "gait_smoothness") else model.gait_smoothness
+        self.straight_only = bool(straight_only)
+        self.kw = dict(fps=float(fps), sigma=float(sigma), derivative=int(derivative), segment=int(segment), hop=int(segment) // 2 if hop is None else int(hop), nfft=int(nfft),
+                       f_cut=min(10.0, float(fps) / 2.0) if f_cut is None else float(f_cut), amplitude=float(amplitude), min_segments=int(min_segments))
+        self.videos = {}
+
+    def add_window(self, keys, per_video, fitted=None, gait_phase=None):
+        """keys[vi], per_video[vi] (T,75), fitted[vi] = (trans (T,3), ...) of WindowTrajectory or None, gait_phase[vi] (T,) of WindowTurns or None."""
+        import torch
+        if not keys:
+            return
+        lengths = [int(per_video[vi].shape[0]) for vi in range(len(keys))]
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0)
+        trans = None if fitted is None else np.concatenate([np.asarray(f[0], np.float64) for f in fitted], 0)
+        straight = self.straight_only and gait_phase is not None
+        exclude = np.concatenate([np.asarray(ph, np.int32) for ph in gait_phase], 0) if straight else None
+        if self.device_call is not None:
+            out = {k: v if isinstance(v, np.ndarray) else v.cpu().numpy() for k, v in self.device_call(j3, lengths=lengths, trans=trans, exclude=exclude, **self.kw).items()}
+        else:
+            out = self.pipe.gait_smoothness(j3.cpu().numpy(), lengths=lengths, trans=trans, exclude=exclude, **self.kw)
+        out.update(self.pipe.smoothness_rows(out["per_segment"], out["per_sequence"], out["slot_offsets"]))
+        at = out["slot_offsets"]
+
+        def number(v):
+            return None if np.isnan(v) else float(v)
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        for q, (key, rows) in enumerate(zip(keys, out["per_sequence"])):
+            video = {"straight_only": straight}
+            for c, name in enumerate(self.pipe.SMOOTHNESS_CHANNELS):
+                video[name] = {col: number(v) for col, v in zip(self.pipe.SMOOTHNESS_COLUMNS, rows[c])}
+                video[name]["ldlj_mean"], video[name]["ldlj_sd"] = number(out["ldlj_mean"][q, c]), number(out["ldlj_sd"][q, c])
+                video[name]["segments"] = [{"start": int(seg[c, 0]), "sparc": number(seg[c, 1]), "last_hz": number(seg[c, 3] * self.kw["fps"] / self.kw["nfft"]), "ldlj": number(ldlj[c])}
+                                           for seg, ldlj in zip(out["per_segment"][at[q]:at[q + 1]], out["ldlj"][at[q]:at[q + 1]]) if not np.isnan(seg[c, 0])]
+            self.videos[key] = video
+            sep = video["sep"]
+            print(f"Smoothness: video {key}, {int(sep['used'])} segments, SPARC {shown(sep['sparc_mean'], '.2f')} (SD {shown(sep['sparc_sd'], '.2f')}), LDLJ "
+                  f"{shown(sep['ldlj_mean'], '.2f')} of the ankles' separation{', straight walking only' if straight else ''}.")
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save gait smoothness of {len(self.videos)} videos to {path}.")
+        return path
+
+
 class WindowCoordination:
     """--gait_coordination: one gait_coordination call per database window on rank 0, one sequence per video, on the joints the window's gather left
     on the device (model.gait_coordination; on_host, or a model without the method: pipeline.gait_coordination after a download) -- with
@@ -1116,8 +1186,12 @@ class WindowCoordination:
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None, bootstrap=None):
-    """bootstrap: {'replicates', 'level', 'block', 'seed', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the percentile
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None, bootstrap=None, smoothness=None):
+    """smoothness: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_cut', 'amplitude', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
+    needs no gait, whose fps it takes where its own is not given, else 20) -- also the spectral arc length and the log dimensionless jerk of every video
+    (WindowSmoothness), written to smoothness['out'] (default: outpath with _smoothness.json); with turns only straight walking counts unless
+    'all_frames'; the database gains nothing.
+    bootstrap: {'replicates', 'level', 'block', 'seed', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the percentile
     intervals of the step and stride parameters of every video (WindowBootstrap; with turns also over straight walking alone, with balance also of
     its step table), written to bootstrap['out'] (default: outpath with _bootstrap.json); the database gains nothing.
     balance: {'gravity', 'window', 'settle', 'max_step', 'on_host', 'out'} (each optional; needs gait, whose fps it takes) -- also the footprints,
@@ -1260,6 +1334,11 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                            **({"fps": gait["fps"]} if spectrum.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
                            **{k: spectrum[k] for k in ("fps", "sigma", "derivative", "segment", "hop", "nfft", "f_lo", "f_hi", "min_segments") if spectrum.get(k) is not None}) \
         if spectrum is not None and rank == 0 else None
+    fluent = WindowSmoothness(pipe, model, smoothness.get("on_host", False), not smoothness.get("all_frames", False),
+                              **({"fps": gait["fps"]} if smoothness.get("fps") is None and gait is not None and gait.get("fps") is not None else {}),
+                              **{k: smoothness[k] for k in ("fps", "sigma", "derivative", "segment", "hop", "nfft", "f_cut", "amplitude", "min_segments")
+                                 if smoothness.get(k) is not None}) \
+        if smoothness is not None and rank == 0 else None
     again = WindowRecurrence(pipe, model, recurrence.get("on_host", False), not recurrence.get("all_frames", False),
                              **{k: recurrence[k] for k in ("sigma", "derivative", "dim", "lag", "theiler", "radius", "min_line", "min_points") if recurrence.get(k) is not None}) \
         if recurrence is not None and rank == 0 else None
@@ -1336,6 +1415,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             apart.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if bands is not None and vids:
             bands.add_window([v[0] for v in vids], per_video, fitted, gait_phase, walk.videos if walk is not None else None, steady.videos if steady is not None else None)
+        if fluent is not None and vids:
+            fluent.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if again is not None and vids:
             again.add_window([v[0] for v in vids], per_video, fitted, gait_phase)
         if limbs is not None and vids:
@@ -1383,6 +1464,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         apart.write(stability.get("out") or osp.splitext(outpath)[0] + "_stability.json")
     if bands is not None:
         bands.write(spectrum.get("out") or osp.splitext(outpath)[0] + "_spectrum.json")
+    if fluent is not None:
+        fluent.write(smoothness.get("out") or osp.splitext(outpath)[0] + "_smoothness.json")
     if again is not None:
         again.write(recurrence.get("out") or osp.splitext(outpath)[0] + "_recurrence.json")
     if limbs is not None:
@@ -1561,6 +1644,23 @@ def main(argv=None):
     p.add_argument("--spectrum_min_segments", type=int, default=None, help="with --gait_spectrum: a video with fewer segments has no spectrum, at least 1 (default 2)")
     p.add_argument("--spectrum_all_frames", action="store_true", help="with --gait_spectrum and --gait_turns: count the frames of the turns too")
     p.add_argument("--spectrum_on_host", action="store_true", help="with --gait_spectrum: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--gait_smoothness", action="store_true", help="with --vid_folder (no --gait needed): the movement smoothness of four body signals, per segment of ongoing walking: "
+                   "the spectral arc length (SPARC) and the log dimensionless jerk (LDLJ) of Balasubramanian et al. 2015: <outpath>_smoothness.json, one line per video; in Hz "
+                   "through --gait_fps where given, else at 20 frames a second; with --gait_turns only straight walking counts; THE INPUTS ARE JOINT POSITIONS OF A POSE MODEL "
+                   "AT 20 FPS, where the cut-off of 10 Hz is the Nyquist frequency; a segment's rectangular window alone gives a noiseless sinusoid SPARC about -4 at 64 "
+                   "frames, with 5 mm of joint noise a good part of the number is the noise, and THE DEFAULTS ARE UNVALIDATED on the model's output")
+    p.add_argument("--smoothness_out", type=str, default="", help="with --gait_smoothness: the JSON file (default: --outpath with _smoothness.json)")
+    p.add_argument("--smoothness_sigma", type=float, default=None, help="with --gait_smoothness: sigma in frames of the Gaussian over the four signals, 0 (none) to 16 (default 0)")
+    p.add_argument("--smoothness_derivative", type=int, default=None, help="with --gait_smoothness: 0 the signal, 1 its velocity, 2 its acceleration (default 1: a speed profile)")
+    p.add_argument("--smoothness_segment", type=int, default=None, help="with --gait_smoothness: the frames of a segment, even, 8 to 256 (default 64)")
+    p.add_argument("--smoothness_hop", type=int, default=None, help="with --gait_smoothness: the frames between two segments, an eighth of a segment to a whole one (default half)")
+    p.add_argument("--smoothness_nfft", type=int, default=None, help="with --gait_smoothness: the points of the zero-padded transform, even, a segment to 4096 (default 1024)")
+    p.add_argument("--smoothness_cutoff", type=float, default=None, help="with --gait_smoothness: the highest frequency of the arc in Hz, above 0 and at most half the frames a "
+                   "second (default: 10, or half the frames a second where that is less)")
+    p.add_argument("--smoothness_amplitude", type=float, default=None, help="with --gait_smoothness: the normalised magnitude that bounds the band, above 0 to 1 (default 0.05)")
+    p.add_argument("--smoothness_min_segments", type=int, default=None, help="with --gait_smoothness: a video with fewer segments has no row, at least 1 (default 2)")
+    p.add_argument("--smoothness_all_frames", action="store_true", help="with --gait_smoothness and --gait_turns: count the frames of the turns too")
+    p.add_argument("--smoothness_on_host", action="store_true", help="with --gait_smoothness: the numpy float64 statement instead of the GPU kernels")
     p.add_argument("--gait_recurrence", action="store_true", help="with --vid_folder (no --gait needed): the recurrence quantification of four body signals -- recurrence rate, "
                    "determinism, mean and longest diagonal line, divergence and line entropy of the delay-embedded signal (Webber and Zbilut 1994, Marwan et al. 2007): "
                    "<outpath>_recurrence.json, one line per video; quadratic in a video's frames; with --gait_turns only straight walking counts; the radius rule is this "
@@ -1635,7 +1735,7 @@ def main(argv=None):
         sys.exit("batch_generation.py: --focal_length must be a positive number of pixels")
     for flag, given in (("--gait_out", bool(a.gait_out)), ("--gait_fps", a.gait_fps is not None), ("--gait_sigma", a.gait_sigma is not None),
                         ("--gait_window", a.gait_window is not None), ("--gait_min_excursion", a.gait_min_excursion is not None), ("--gait_on_host", a.gait_on_host)):
-        if given and not a.gait and not (flag == "--gait_fps" and (a.gait_regularity or a.gait_spectrum or a.gait_coordination)):
+        if given and not a.gait and not (flag == "--gait_fps" and (a.gait_regularity or a.gait_spectrum or a.gait_coordination or a.gait_smoothness)):
             sys.exit(f"batch_generation.py: {flag} belongs to --gait, which was not given")
     if a.gait and not a.vid_folder:
         sys.exit("batch_generation.py: --gait needs --vid_folder (the frames whose joints it reads)")
@@ -1842,6 +1942,35 @@ def main(argv=None):
             sys.exit("batch_generation.py: --spectrum_f_lo and --spectrum_f_hi must obey 0 < f_lo < f_hi <= half the frames a second")
         if a.spectrum_min_segments is not None and a.spectrum_min_segments < 1:
             sys.exit("batch_generation.py: --spectrum_min_segments must be at least 1")
+    for flag, given in (("--smoothness_out", bool(a.smoothness_out)), ("--smoothness_sigma", a.smoothness_sigma is not None),
+                        ("--smoothness_derivative", a.smoothness_derivative is not None), ("--smoothness_segment", a.smoothness_segment is not None),
+                        ("--smoothness_hop", a.smoothness_hop is not None), ("--smoothness_nfft", a.smoothness_nfft is not None),
+                        ("--smoothness_cutoff", a.smoothness_cutoff is not None), ("--smoothness_amplitude", a.smoothness_amplitude is not None),
+                        ("--smoothness_min_segments", a.smoothness_min_segments is not None), ("--smoothness_all_frames", a.smoothness_all_frames),
+                        ("--smoothness_on_host", a.smoothness_on_host)):
+        if given and not a.gait_smoothness:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_smoothness, which was not given")
+    if a.gait_smoothness and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_smoothness needs --vid_folder (the frames whose joints it reads)")
+    if a.smoothness_sigma is not None and not (np.isfinite(a.smoothness_sigma) and 0 <= a.smoothness_sigma <= 16):
+        sys.exit("batch_generation.py: --smoothness_sigma must be within 0 to 16")
+    if a.smoothness_derivative is not None and not 0 <= a.smoothness_derivative <= 2:
+        sys.exit("batch_generation.py: --smoothness_derivative must be 0, 1 or 2")
+    if a.gait_smoothness:
+        seg = 64 if a.smoothness_segment is None else a.smoothness_segment
+        if not 8 <= seg <= 256 or seg % 2:
+            sys.exit("batch_generation.py: --smoothness_segment must be even and within 8 to 256")
+        if a.smoothness_hop is not None and not seg // 8 <= a.smoothness_hop <= seg:
+            sys.exit("batch_generation.py: --smoothness_hop must be within an eighth of --smoothness_segment to the whole of it")
+        nfft = 1024 if a.smoothness_nfft is None else a.smoothness_nfft
+        if not seg <= nfft <= 4096 or nfft % 2:
+            sys.exit("batch_generation.py: --smoothness_nfft must be even and within --smoothness_segment to 4096")
+        if a.smoothness_cutoff is not None and not (np.isfinite(a.smoothness_cutoff) and 0 < a.smoothness_cutoff <= (20.0 if a.gait_fps is None else a.gait_fps) / 2):
+            sys.exit("batch_generation.py: --smoothness_cutoff must obey 0 < cutoff <= half the frames a second")
+        if a.smoothness_amplitude is not None and not 0 < a.smoothness_amplitude <= 1:
+            sys.exit("batch_generation.py: --smoothness_amplitude must be above 0 and at most 1")
+        if a.smoothness_min_segments is not None and a.smoothness_min_segments < 1:
+            sys.exit("batch_generation.py: --smoothness_min_segments must be at least 1")
     for flag, given in (("--coordination_out", bool(a.coordination_out)), ("--coordination_sigma", a.coordination_sigma is not None),
                         ("--coordination_derivative", a.coordination_derivative is not None), ("--coordination_segment", a.coordination_segment is not None),
                         ("--coordination_hop", a.coordination_hop is not None), ("--coordination_nfft", a.coordination_nfft is not None),
@@ -1933,6 +2062,9 @@ def main(argv=None):
     spectrum = {"fps": a.gait_fps, "sigma": a.spectrum_sigma, "derivative": a.spectrum_derivative, "segment": a.spectrum_segment, "hop": a.spectrum_hop, "nfft": a.spectrum_nfft,
                 "f_lo": a.spectrum_f_lo, "f_hi": a.spectrum_f_hi, "min_segments": a.spectrum_min_segments, "all_frames": a.spectrum_all_frames,
                 "on_host": a.spectrum_on_host, "out": a.spectrum_out or None} if a.gait_spectrum else None
+    smoothness = {"fps": a.gait_fps, "sigma": a.smoothness_sigma, "derivative": a.smoothness_derivative, "segment": a.smoothness_segment, "hop": a.smoothness_hop,
+                  "nfft": a.smoothness_nfft, "f_cut": a.smoothness_cutoff, "amplitude": a.smoothness_amplitude, "min_segments": a.smoothness_min_segments,
+                  "all_frames": a.smoothness_all_frames, "on_host": a.smoothness_on_host, "out": a.smoothness_out or None} if a.gait_smoothness else None
     recurrence = {"sigma": a.recurrence_sigma, "derivative": a.recurrence_derivative, "dim": a.recurrence_dim, "lag": a.recurrence_lag, "theiler": a.recurrence_theiler,
                   "radius": a.recurrence_radius, "min_line": a.recurrence_min_line, "min_points": a.recurrence_min_points, "all_frames": a.recurrence_all_frames,
                   "on_host": a.recurrence_on_host, "out": a.recurrence_out or None} if a.gait_recurrence else None
@@ -1952,7 +2084,7 @@ def main(argv=None):
                  **({"stability": stability} if stability is not None else {}),
                  **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}),
                  **({"coordination": coordination} if coordination is not None else {}), **({"balance": balance} if balance is not None else {}),
-                 **({"bootstrap": bootstrap} if bootstrap is not None else {}))
+                 **({"bootstrap": bootstrap} if bootstrap is not None else {}), **({"smoothness": smoothness} if smoothness is not None else {}))
 
 
 if __name__ == "__main__":

@@ -1068,6 +1068,49 @@ int grnet_bootstrap_table(grnet_t* h, const double* table_dev, const int32_t* co
                           int B, int block, uint64_t seed, int stream_id, const int32_t* quantiles_host, int n_q, double* out_dev, double* replicates_dev,
                           void* stream);
 
+/* Movement smoothness of the same four body signals: the spectral arc length (SPARC) and the dimensionless jerk of Balasubramanian, Melendez-Calderon,
+ * Roby-Brami and Burdet 2015, per segment of ongoing walking (on gait: Beck et al. 2018 -- with a sensor at 100 Hz and more; THESE SIGNALS ARE JOINT
+ * POSITIONS OF A POSE MODEL AT 20 FPS, WHERE THE CUT-OFF OF 10 HZ IS THE NYQUIST FREQUENCY; A SEGMENT CUT OUT OF WALKING HAS A RECTANGULAR WINDOW,
+ * WHOSE LEAKAGE ALONE GIVES A NOISELESS SINUSOID SPARC = -3.96 +- 0.30 AT 64 FRAMES; WITH 5 MM OF JOINT NOISE A GOOD PART OF THE NUMBER IS THE NOISE;
+ * THE DEFAULTS ARE UNVALIDATED ON THE MODEL'S OUTPUT: DESIGN 4.24, which is the specification).  joints3d_dev, frame_offsets_host, joints_host,
+ * trans_dev and exclude_dev as grnet_gait_regularity takes them.  Float64 with one rounding per operation; sine and cosine are the harmonics call's
+ * own (no library); every test is a comparison, false for NaN:
+ *   signals  grnet_gait_regularity's, the same bits at the same sigma: x.  y: x differenced `derivative` times (1: SPARC is defined on a speed
+ *            profile), grnet_gait_entropy's, NaN where a frame it reads does not count.
+ *   segments grnet_gait_spectrum's on the validity of y: `segment` = L (even, 8 .. 256), `hop`, candidates, used (0 below min_segments).  A
+ *            sequence of T frames has slots = (T - L) / hop + 1 slots (0 where T < L), the most it can hold; the slots of the sequences lie back to
+ *            back (grnet_gait_smoothness_slots gives the prefix sums).  Nothing is capped or truncated.
+ *   M_k      of one segment, no mean taken off and no window: C = sum y_i cos(2 pi k i / N), S = sum y_i sin(..) in rising i from +0.0, nfft = N
+ *            (even, L .. 4096), the table indexed by (k i) mod N; M_k = sqrt(C C + S S) for k = 0 .. k_c, the largest k with (k fps) / N <= f_cut
+ *            (0 < f_cut <= fps / 2).  M_max: the largest, at the smallest k of a tie (peak_bin).  Not positive and finite: the row is NaN behind start.
+ *   sparc    m_k = M_k / M_max; k_first, k_last the first and the last k with m_k >= amplitude (in (0, 1]); u = 1 / (k_last - k_first);
+ *            sparc = 0 - sum_{k_first <= k < k_last} sqrt(u u + (m_(k+1) - m_k)^2) in rising k from +0.0; 0.0 where k_first = k_last.
+ *   dj       on x of the same L frames: v_i = x_(i+1) - x_i, j_i = ((x_(i+3) - 3 x_(i+2)) + 3 x_(i+1)) - x_i, v_peak = max |v_i|,
+ *            dj = ((sum j_i j_i) (L - 1)^3) / (v_peak v_peak), NaN where v_peak is not positive.  fps cancels.  THE LOGARITHM IS THE CALLER'S:
+ *            ldlj = -ln(dj) is taken on the host (as the Python layer does).
+ *   row      n (valid y), candidates, used, defined (segments with a finite sparc), sparc_mean, sparc_sd (sqrt(sum d^2 / defined)), sparc_min,
+ *            sparc_max, last_hz_mean (the mean of (k_last fps) / N), dj_defined; NaN behind used where used is 0.
+ * per_frame_dev (sum T, 4) float64.  per_segment_dev (sum slots, 4, 8) float64: start, sparc, k_first, k_last, peak_bin, peak_magnitude, dj, v_peak;
+ * NaN everywhere behind the candidates; written whatever used is; may be null where there is no slot.  per_seq_dev (n_seq, 4, 10) float64.
+ * A wave per (sequence, channel) lays the segments; a workgroup per (slot, channel), a lane per bin, makes a row; a wave per (sequence, channel)
+ * reads the sequence's row off them; no atomics; across lanes only a maximum, a first and a last index are joined: a sequence's outputs have the same
+ * bits alone or among others.  Needs no weights.  At most five launches (four with sigma = 0) behind one small copy from pinned memory; no host
+ * synchronisation; the scratch is the box calls'.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null required pointer, J < 1, a table index outside [0, J), n_seq
+ * outside [1, 8192], frame_offsets[0] != 0, offsets that do not increase, a sequence of more than 32768 frames, sigma outside [0, 16], fps not
+ * positive and finite, derivative outside [0, 2], segment odd or outside [8, 256], hop outside [segment / 8, segment], min_segments outside
+ * [1, 2^20], nfft odd or outside [segment, 4096], not 0 < f_cut <= fps / 2, amplitude outside (0, 1].  Nothing is refused on the data.
+ * grnet_op_gait_sparc: y, the segments and the rows alone (test hook) on signals_dev float64 (sum T, 4).
+ * grnet_gait_smoothness_slots: host only, no handle: slots_host[q] = the slots in front of sequence q, slots_host[n_seq] all of them; GRNET_EINVAL
+ * for a null pointer, n_seq < 1, offsets that do not increase from 0, segment or hop outside their limits. */
+int grnet_gait_smoothness(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                          const double* trans_dev, const int32_t* exclude_dev, double fps, double sigma, int derivative, int segment, int hop, int nfft,
+                          double f_cut, double amplitude, int min_segments, double* per_frame_dev, double* per_segment_dev, double* per_seq_dev, void* stream);
+int grnet_op_gait_sparc(grnet_t* h, const double* signals_dev, const int32_t* exclude_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
+                        int derivative, int segment, int hop, int nfft, double f_cut, double amplitude, int min_segments, double* per_segment_dev,
+                        double* per_seq_dev, void* stream);
+int grnet_gait_smoothness_slots(const int32_t* frame_offsets_host, int n_seq, int segment, int hop, int64_t* slots_host);
+
 /* Recurrence quantification of the same four body signals (Webber and Zbilut 1994; Marwan et al. 2007; on gait Labini et al. 2012 and Riva et al.
  * 2013 -- on a trunk sensor over minutes of walking; these signals are joint positions of a pose model over some 15 strides, the radius rule is this
  * project's and the defaults are unvalidated on its output): every pair of points of the delay-embedded signal against one radius, and the runs of

@@ -23,6 +23,7 @@
 //   grnet_coordination.cpp arm swing and inter-limb coordination: grnet_gait_coordination and its cross-spectrum hook
 //   grnet_balance.cpp  footprints, centre of mass and margin of stability: grnet_gait_balance and its steps hook
 //   grnet_bootstrap.cpp the gait call's step and stride tables and bootstrap intervals of a per-step table: grnet_gait_step_tables, grnet_bootstrap_table
+//   grnet_smoothness.cpp movement smoothness: grnet_gait_smoothness, its slot count and its arc-length hook
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"

@@ -499,6 +499,19 @@ int spec_bin_blocks(int nfft);             // the grid's z: blocks of kSpecThrea
 hipError_t launch_spec_sequences(const int* off, int n_seq, const SpecRule& rule, const double* rows, const int* exclude, int frames, double* y_long, int* start_long,
                                  double* mu_long, double* psd, double* per_seq, hipStream_t s);
 
+// Movement smoothness of the same four signals: spectral arc length and dimensionless jerk per segment (csrc/gait_smoothness_kernels.hip, compiled
+// without fma contraction; the arithmetic: csrc/gait_smoothness.h).  The frame kernel is launch_reg_frames ----
+struct SmoRule;                            // gait_smoothness.h: fps, derivative, segment, hop, nfft, f_cut, amplitude, min_segments
+constexpr int kSmoWave = 64;               // one wave per (sequence, channel) lays the segments, and one reads the sequence's row off them
+constexpr int kSmoThreads = 256;           // one workgroup per (slot, channel): a lane owns a bin, in rounds of this width
+size_t smo_lds_bytes(const SmoRule& rule, int kc, int form);      // the segment kernel's dynamic LDS
+// three launches (two where slots is 0) on rows (frames,4) and exclude (frames) or null: a wave per (sequence, channel) writes `start` of every slot
+// of per_seg (slots,4,8), NaN behind the candidates, the first three columns of per_seq (n_seq,4,10) and, as scratch, tw (2 nfft float64: sine and
+// cosine of har_twiddle(j, nfft)), slot_seq (slots) and slot_base (n_seq) int32; a workgroup per (slot, channel) the other seven columns of its row;
+// a wave per (sequence, channel) the other seven of per_seq.  kc: smo_cut_bin(rule).  form: where the segment kernel reads its twiddles (0: tw)
+hipError_t launch_smo_sequences(const int* off, int n_seq, int slots, const SmoRule& rule, int kc, int form, const double* rows, const int* exclude, double* tw,
+                                int* slot_seq, int* slot_base, double* per_seg, double* per_seq, hipStream_t s);
+
 // Arm swing and inter-limb coordination: auto and cross spectra of the two shoulder and the two hip flexions (csrc/gait_coordination_kernels.hip,
 // compiled without fma contraction; the arithmetic: csrc/gait_coordination.h).  The workgroup is gait_spectrum's wave of kSpecThreads ----
 constexpr int kCoordLdsFrames = 1024;      // frames of a sequence whose four differenced columns the workgroup keeps in LDS (more: the call's scratch)

@@ -1615,6 +1615,78 @@ class GRNet:
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_welch")
         return out
 
+    # ------------------------------------------------------------------ movement smoothness
+    @staticmethod
+    def smoothness_slots(lengths, segment=64, hop=None):
+        """The prefix sums of the slots of sequences of `lengths` frames (grnet_gait_smoothness_slots' formula): a sequence of T frames has
+        (T - segment) // hop + 1 slots, 0 where T < segment.  (n_seq + 1,) int64."""
+        if hop is None:
+            hop = segment // 2
+        at = np.zeros(len(lengths) + 1, np.int64)
+        at[1:] = np.cumsum([(int(T) - int(segment)) // int(hop) + 1 if int(T) >= int(segment) else 0 for T in lengths])
+        return at
+
+    def _smoothness_call(self, n, lengths, exclude, fps, derivative, segment, hop, nfft, f_cut, min_segments, what):
+        """(exclude on the device or None, offsets, hop, f_cut, the per_segment and per_sequence tensors, slot_offsets) of gait_smoothness and its hook."""
+        if hop is None:
+            hop = segment // 2 if int(segment) == segment else segment
+        if f_cut is None:
+            f_cut = min(10.0, float(fps) / 2.0)
+        self._whole_frames(derivative=derivative, segment=segment, hop=hop, nfft=nfft, min_segments=min_segments)
+        if not 8 <= int(segment) <= 256 or int(segment) % 2:        # the size of per_segment is made of these here
+            raise ValueError("segment must be even and within [8, 256]")
+        if not int(segment) // 8 <= int(hop) <= int(segment):
+            raise ValueError("hop outside [segment / 8, segment]")
+        ex = self._exclude_input(n, exclude)
+        off = self._sequence_offsets(n, lengths, what)
+        n_seq = len(off) - 1
+        slots = self.smoothness_slots(np.diff(off), int(segment), int(hop))
+        out = {"per_segment": torch.empty(int(slots[-1]), 4, 8, dtype=torch.float64, device=self.device),
+               "per_sequence": torch.empty(n_seq, 4, 10, dtype=torch.float64, device=self.device), "slot_offsets": slots}
+        return ex, off, int(hop), float(f_cut), out
+
+    def gait_smoothness(self, joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, derivative=1, segment=64, hop=None, nfft=1024, f_cut=None,
+                        amplitude=0.05, min_segments=2, joints=_lib.GAIT_JOINTS_KINECTV2):
+        """The movement smoothness of every sequence's four body signals, per segment of ongoing walking, on the device (grnet_gait_smoothness; the
+        rules, channels and columns: DESIGN 4.24, pipeline.SMOOTHNESS_CHANNELS, SMOOTHNESS_SEGMENT_COLUMNS, SMOOTHNESS_COLUMNS).  joints3d, lengths,
+        trans, exclude and joints as gait_regularity takes them.  Its four signals, smoothed by sigma frames (0: none, the default; <= 16), are
+        differenced `derivative` times (0 .. 2; 1: the speed profile the measure is defined on); inside every run of frames that count, segments of
+        `segment` frames (even, 8 .. 256) are laid `hop` apart (segment / 8 .. segment; None: segment / 2).  Each segment, with no mean taken off
+        and no window, is zero-padded to `nfft` (even, segment .. 4096) and the magnitudes of its transform up to f_cut Hz (0 < f_cut <= fps / 2;
+        None: min(10, fps / 2)) are divided by the largest; the spectral arc length (SPARC; Balasubramanian et al. 2015) is minus the length of that
+        curve between the first and the last bin at or above `amplitude` (in (0, 1]), the band's width scaled to 1.  The dimensionless jerk of the
+        same frames of the undifferenced signal stands beside it; its logarithm (LDLJ) is pipeline.smoothness_rows', on the host.  Fewer than
+        min_segments segments give a NaN row; the segment rows are written whatever it is.  A sequence has at most 32 768 frames.  Returns a dict:
+        per_frame (n,4) float64, gait_regularity's bits; per_segment (slots,4,8) float64, the sequences' slots back to back, NaN behind each one's
+        candidates; per_sequence (n_seq,4,10) float64 -- device tensors -- and slot_offsets (n_seq+1,) int64 numpy.  THE INPUTS ARE JOINT
+        POSITIONS OF A POSE MODEL AT 20 FPS, where 10 Hz is the Nyquist frequency; A SEGMENT'S RECTANGULAR WINDOW ALONE gives a noiseless sinusoid
+        SPARC = -3.96 +- 0.30 at 64 frames, and with 5 mm of joint noise a good part of the number is the noise; THE DEFAULTS ARE UNVALIDATED on the
+        model's output.  Nothing is refused on the data.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
+        n = j.shape[0]
+        table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
+        t = self._trans_input(n, trans)
+        ex, off, hop, f_cut, out = self._smoothness_call(n, lengths, exclude, fps, derivative, segment, hop, nfft, f_cut, min_segments, "joints3d")
+        out["per_frame"] = torch.empty(n, 4, dtype=torch.float64, device=self.device)
+        rc = self._lib.grnet_gait_smoothness(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), None if t is None else t.data_ptr(),
+                                             None if ex is None else ex.data_ptr(), float(fps), float(sigma), int(derivative), int(segment), hop, int(nfft),
+                                             f_cut, float(amplitude), int(min_segments), out["per_frame"].data_ptr(), out["per_segment"].data_ptr() or None,
+                                             out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_gait_smoothness")
+        return out
+
+    def op_gait_sparc(self, signals, lengths=None, exclude=None, fps=20.0, derivative=1, segment=64, hop=None, nfft=1024, f_cut=None, amplitude=0.05,
+                      min_segments=2):
+        """Rules 1 (from the differencing on) to 7 of gait_smoothness alone (grnet_op_gait_sparc): signals (n,4) float64 and exclude (n,) or None, one
+        sequence or `lengths` of them lying back to back -> {per_segment, per_sequence} on the device and slot_offsets."""
+        x = self._rows_input(signals, "signals", (4,), torch.float64)
+        ex, off, hop, f_cut, out = self._smoothness_call(x.shape[0], lengths, exclude, fps, derivative, segment, hop, nfft, f_cut, min_segments, "signals")
+        rc = self._lib.grnet_op_gait_sparc(self._h, x.data_ptr(), None if ex is None else ex.data_ptr(), _i32p(off), len(off) - 1, float(fps), int(derivative),
+                                           int(segment), hop, int(nfft), f_cut, float(amplitude), int(min_segments), out["per_segment"].data_ptr() or None,
+                                           out["per_sequence"].data_ptr(), self._stream())
+        _lib.check(self._lib, self._h, rc, "grnet_op_gait_sparc")
+        return out
+
     # ------------------------------------------------------------------ arm swing and inter-limb coordination (DESIGN 4.21)
     def _coordination_call(self, n, lengths, exclude, derivative, segment, hop, nfft, min_segments, what):
         """(exclude on the device or None, offsets, hop, the auto, cross, limbs and pairs tensors) of gait_coordination and its hook."""

@@ -2548,6 +2548,213 @@ def gait_spectrum(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, si
     return out
 
 
+# ----------------------------------------------------------------------------- movement smoothness
+SMOOTHNESS_CHANNELS = REGULARITY_CHANNELS
+SMOOTHNESS_SEGMENT_COLUMNS = ("start", "sparc", "k_first", "k_last", "peak_bin", "peak_magnitude", "dj", "v_peak")
+SMOOTHNESS_COLUMNS = ("n", "candidates", "used", "defined", "sparc_mean", "sparc_sd", "sparc_min", "sparc_max", "last_hz_mean", "dj_defined")
+SMOOTHNESS_MAX_FRAMES = ENTROPY_MAX_FRAMES
+
+
+def _smoothness_rule_check(fps, derivative, segment, hop, nfft, f_cut, amplitude, min_segments):
+    """The refusals of csrc/gait_smoothness.h's smo_rule_error, in its words and its order."""
+    if not np.isfinite(fps) or not fps > 0:
+        raise ValueError("fps must be positive and finite")
+    if any(int(v) != v for v in (derivative, segment, hop, nfft, min_segments)):
+        raise ValueError("derivative, segment, hop, nfft and min_segments must be whole numbers")
+    _spectrum_rule_check(fps, derivative, segment, hop, segment, fps / 4.0, fps / 2.0, min_segments)
+    if not segment <= nfft <= 4096 or nfft % 2:
+        raise ValueError("nfft must be even and within [segment, 4096]")
+    if not (np.isfinite(f_cut) and 0 < f_cut <= fps / 2.0):
+        raise ValueError("f_cut must obey 0 < f_cut <= fps / 2")
+    if not 0 < amplitude <= 1:
+        raise ValueError("amplitude must be within (0, 1]")
+
+
+def smoothness_slots(lengths, segment=64, hop=None):
+    """The prefix sums of the slots of sequences of `lengths` frames lying back to back: a sequence of T frames has (T - segment) // hop + 1 slots, the
+    most it can hold (0 where T < segment).  (n_seq + 1,) int64: grnet_gait_smoothness_slots' formula."""
+    if hop is None:
+        hop = segment // 2
+    at = np.zeros(len(lengths) + 1, np.int64)
+    at[1:] = np.cumsum([(int(T) - int(segment)) // int(hop) + 1 if int(T) >= int(segment) else 0 for T in lengths])
+    return at
+
+
+def _smoothness_row(rows, fps, nfft, n, candidates, used):
+    """smo_row on Python floats: rows the (candidates, 8) slot rows of one (sequence, channel) in time order."""
+    nan = float("nan")
+    out = [float(n), float(candidates), float(used)] + [nan] * 7
+    if used < 1:
+        return out
+    fps, N = float(fps), float(nfft)
+    defined = dj_defined = 0
+    S = H = lo = hi = 0.0
+    for row in rows:
+        sparc, last, dj = float(row[1]), float(row[3]), float(row[6])
+        if math.isfinite(dj):
+            dj_defined += 1
+        if not math.isfinite(sparc):
+            continue
+        if defined == 0 or sparc < lo:
+            lo = sparc
+        if defined == 0 or sparc > hi:
+            hi = sparc
+        S = S + sparc
+        H = H + (last * fps) / N
+        defined += 1
+    out[3], out[9] = float(defined), float(dj_defined)
+    if defined < 1:
+        return out
+    mean, Q = S / float(defined), 0.0
+    for row in rows:
+        sparc = float(row[1])
+        if math.isfinite(sparc):
+            d = sparc - mean
+            Q = Q + d * d
+    out[4], out[5], out[6], out[7], out[8] = mean, math.sqrt(Q / float(defined)), lo, hi, H / float(defined)
+    return out
+
+
+def smoothness_rows(per_segment, per_sequence, slot_offsets):
+    """Rule 8 of DESIGN 4.24, the one place where the logarithm is taken: per_segment (slots,4,8), per_sequence (n_seq,4,10) and slot_offsets
+    (n_seq+1,), from the device or from gait_sparc -> {'ldlj': (slots,4) float64 = -ln(dj), the log dimensionless jerk of every slot, NaN where dj is
+    not positive and finite; 'ldlj_mean', 'ldlj_sd': (n_seq,4) over a sequence's slots in time order from +0.0, the SD sqrt(sum d^2 / n); NaN where
+    used is 0 or no slot has one}."""
+    seg, rows, at = np.asarray(per_segment, np.float64), np.asarray(per_sequence, np.float64), np.asarray(slot_offsets, np.int64)
+    if seg.ndim != 3 or seg.shape[1:] != (4, len(SMOOTHNESS_SEGMENT_COLUMNS)) or rows.ndim != 3 or rows.shape[1:] != (4, len(SMOOTHNESS_COLUMNS)):
+        raise ValueError(f"per_segment must be (slots,4,{len(SMOOTHNESS_SEGMENT_COLUMNS)}) and per_sequence (n_seq,4,{len(SMOOTHNESS_COLUMNS)}), got {seg.shape} and {rows.shape}")
+    if at.shape != (rows.shape[0] + 1,) or at[0] != 0 or at[-1] != seg.shape[0] or (np.diff(at) < 0).any():
+        raise ValueError(f"slot_offsets must be the {rows.shape[0] + 1} prefix sums of per_segment's {seg.shape[0]} slots")
+    ldlj = np.full(seg.shape[:2], np.nan)
+    mean, sd = np.full(rows.shape[:2], np.nan), np.full(rows.shape[:2], np.nan)
+    for s in range(seg.shape[0]):
+        for ch in range(4):
+            dj = float(seg[s, ch, 6])
+            if dj > 0.0 and math.isfinite(dj):
+                ldlj[s, ch] = -math.log(dj)
+    for q in range(rows.shape[0]):
+        for ch in range(4):
+            if not rows[q, ch, 2] >= 1:
+                continue
+            have = [float(v) for v in ldlj[at[q]:at[q + 1], ch] if math.isfinite(v)]
+            if not have:
+                continue
+            S = 0.0
+            for v in have:
+                S = S + v
+            m, Q = S / float(len(have)), 0.0
+            for v in have:
+                Q = Q + (v - m) * (v - m)
+            mean[q, ch], sd[q, ch] = m, math.sqrt(Q / float(len(have)))
+    return {"ldlj": ldlj, "ldlj_mean": mean, "ldlj_sd": sd}
+
+
+def gait_sparc(signals, lengths=None, exclude=None, fps=20.0, derivative=1, segment=64, hop=None, nfft=1024, f_cut=None, amplitude=0.05, min_segments=2):
+    """Rules 1 (from the differencing on) to 8 of DESIGN 4.24 on given signals: the host statement of GRNet.op_gait_sparc.  signals (n,4) float64,
+    columns SMOOTHNESS_CHANNELS; exclude (n,) or None: a frame whose entry is not 0 does not count; hop None: segment / 2; f_cut None: min(10, fps / 2).
+    Returns {'per_segment': (slots,4,8), columns SMOOTHNESS_SEGMENT_COLUMNS, 'per_sequence': (n_seq,4,10), columns SMOOTHNESS_COLUMNS, 'slot_offsets':
+    (n_seq+1,) int64, and smoothness_rows' 'ldlj', 'ldlj_mean', 'ldlj_sd'}.  Every sum in rising index from +0.0 (a cumulative sum, or one addition a
+    loop turn), the twiddles harmonics_twiddles' at (k i) mod nfft."""
+    x = np.asarray(signals, np.float64)
+    if x.ndim != 2 or x.shape[1] != 4 or x.shape[0] < 1:
+        raise ValueError(f"signals must be (n,4) with n >= 1, got {x.shape}")
+    n = x.shape[0]
+    lengths = _sequence_lengths(n, lengths)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude)
+        if ex.shape != (n,):
+            raise ValueError(f"exclude must be ({n},), got {ex.shape}")
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+    if f_cut is None:
+        f_cut = min(10.0, float(fps) / 2.0)
+    _smoothness_rule_check(fps, derivative, segment, hop, nfft, f_cut, amplitude, min_segments)
+    _entropy_lengths_check(lengths)
+    fps, d, L, hop, N, min_segments, amplitude = float(fps), int(derivative), int(segment), int(hop), int(nfft), int(min_segments), float(amplitude)
+    freqs = (np.arange(N // 2 + 1, dtype=np.float64) * fps) / float(N)
+    kc = int(np.flatnonzero(freqs <= f_cut)[-1])
+    sn, cs = harmonics_twiddles(N)
+    kk = np.arange(kc + 1, dtype=np.int64)
+    l1 = float(L - 1)
+    cube = (l1 * l1) * l1
+    at = smoothness_slots(lengths, L, hop)
+    per_seg = np.full((int(at[-1]), 4, len(SMOOTHNESS_SEGMENT_COLUMNS)), np.nan)
+    per_seq = np.full((len(lengths), 4, len(SMOOTHNESS_COLUMNS)), np.nan)
+    f0 = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            for ch in range(4):
+                s = x[f0:f0 + T, ch]
+                valid = np.isfinite(s)
+                if ex is not None:
+                    valid &= ex[f0:f0 + T] == 0
+                y = np.where(valid, s, np.nan)
+                for _ in range(d):
+                    y = np.concatenate([y[1:] - y[:-1], [np.nan]])
+                y[~np.isfinite(y)] = np.nan
+                ok = np.isfinite(y)
+                edges = np.flatnonzero(np.diff(np.concatenate([[False], ok, [False]]).astype(np.int8)))
+                starts = [t0 for a, e in zip(edges[0::2], edges[1::2]) for t0 in range(int(a), int(e) - L + 1, hop)]
+                candidates = len(starts)
+                used = candidates if candidates >= min_segments else 0
+                rows = per_seg[at[q]:at[q] + candidates, ch]
+                if candidates:
+                    seg = y[np.asarray(starts)[:, None] + np.arange(L)[None, :]]
+                    C, S = np.zeros((candidates, kc + 1)), np.zeros((candidates, kc + 1))
+                    for i in range(L):
+                        j = (kk * i) % N
+                        C = C + seg[:, i, None] * cs[j][None, :]
+                        S = S + seg[:, i, None] * sn[j][None, :]
+                    M = np.sqrt(C * C + S * S)
+                for e, t0 in enumerate(starts):
+                    rows[e, 0] = float(t0)
+                    peak = int(np.argmax(np.where(np.isnan(M[e]), -1.0, M[e])))      # the largest, at the smallest k of a tie; a NaN is never it
+                    top = float(M[e, peak])
+                    if not (top > 0.0 and math.isfinite(top)):
+                        continue
+                    m = M[e] / top
+                    band = np.flatnonzero(m >= amplitude)
+                    ka, kb = int(band[0]), int(band[-1])
+                    sparc = 0.0
+                    if kb > ka:
+                        u = 1.0 / float(kb - ka)
+                        step = m[ka + 1:kb + 1] - m[ka:kb]
+                        sparc = 0.0 - float(np.cumsum(np.concatenate([[0.0], np.sqrt(u * u + step * step)]))[-1])
+                    xs = s[t0:t0 + L]
+                    v_peak = float(np.max(np.abs(xs[1:] - xs[:-1])))
+                    jerk = ((xs[3:] - 3.0 * xs[2:-1]) + 3.0 * xs[1:-2]) - xs[:-3]
+                    J = float(np.cumsum(np.concatenate([[0.0], jerk * jerk]))[-1])
+                    dj = (J * cube) / (v_peak * v_peak) if v_peak > 0.0 else float("nan")
+                    rows[e, 1:] = (sparc, float(ka), float(kb), float(peak), top, dj, v_peak)
+                per_seq[q, ch] = _smoothness_row(rows, fps, N, int(ok.sum()), candidates, used)
+            f0 += T
+    out = {"per_segment": per_seg, "per_sequence": per_seq, "slot_offsets": at}
+    out.update(smoothness_rows(per_seg, per_seq, at))
+    return out
+
+
+def gait_smoothness(joints3d, lengths=None, trans=None, exclude=None, fps=20.0, sigma=0.0, derivative=1, segment=64, hop=None, nfft=1024, f_cut=None,
+                    amplitude=0.05, min_segments=2, joints=GAIT_JOINTS_KINECTV2):
+    """Movement smoothness of four body signals in numpy float64: the spectral arc length and the dimensionless jerk of every segment (Balasubramanian
+    et al. 2015; on gait Beck et al. 2018; the rules: DESIGN 4.24).  THE INPUTS ARE JOINT POSITIONS OF A POSE MODEL AT 20 FPS, where the cut-off of
+    10 Hz is the Nyquist frequency; A SEGMENT'S RECTANGULAR WINDOW ALONE gives a noiseless sinusoid SPARC = -3.96 +- 0.30 at 64 frames; with 5 mm of
+    joint noise a good part of the number is the noise; THE DEFAULTS ARE UNVALIDATED on the model's output.  The host statement of
+    GRNet.gait_smoothness, same arguments, a dict of numpy arrays.  per_frame (n,4) is gait_regularity's at the same sigma; the rest is gait_sparc's."""
+    if hop is None:
+        hop = segment // 2 if int(segment) == segment else segment
+    if f_cut is None:
+        f_cut = min(10.0, float(fps) / 2.0)
+
+    def rule_check():
+        _smoothness_rule_check(fps, derivative, segment, hop, nfft, f_cut, amplitude, min_segments)
+        _entropy_lengths_check(_sequence_lengths(np.asarray(joints3d).shape[0], lengths))
+    lengths, per_frame = _regularity_signals(joints3d, lengths, trans, sigma, joints, rule_check)
+    out = gait_sparc(per_frame, lengths, exclude, fps, derivative, segment, hop, nfft, f_cut, amplitude, min_segments)
+    out["per_frame"] = per_frame
+    return out
+
+
 # ----------------------------------------------------------------------------- arm swing and inter-limb coordination (DESIGN 4.21)
 COORDINATION_CHANNELS = ("arm_left", "arm_right", "leg_left", "leg_right")      # gait_kinematics's channels 8, 9, 0, 1: shoulder and hip flexion
 COORDINATION_KINEMATICS_COLUMNS = (8, 9, 0, 1)
