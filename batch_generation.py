@@ -121,6 +121,15 @@ off the replicates (GRNet.bootstrap_table on the device).  With --g
 (about 0.91 where 0.95 is asked), and the steps of one walk are serially correlated, which a block length addresses only partly.  Reported, never
 judged.
 
+--gait_body (opt-in, needs no --gait) reports what the joints cannot: the volume, the centre of mass, the central second moments per unit volume and
+the surface area of the SMPL mesh of every frame, exact sums over the 13 776 triangles of the closed surface (the divergence theorem; Mirtich 1996,
+Eberly 2002).  The vertices are read where the forward left them, on the rank that ran it (GRNet.mesh_moments); eleven doubles per frame
+ride the window's one all-gather.  Per video the mean volume, its CV, the mass at --body_density (985 kg/m^3), the radii of gyration, and how far the
+mesh's centre of mass lies from the one --gait_balance uses (Winter's segment masses on the kinectv2 joints): <outpath>_body.json, 'body_com' and
+'body_volume' in the database.  --balance_com mesh hands that centre to --gait_balance in place of the table's.  UNIFORM DENSITY IS AN ASSUMPTION
+(lungs and bone are not uniform, 985 kg/m^3 is a whole-body textbook figure); THE MESH IS A STATISTICAL BODY SHAPE, NOT THE SUBJECT'S; the model
+predicts betas PER FRAME, so the volume's CV across a video measures the model's consistency, not the subject.  Reported, never judged.
+
 Video decoding (ffmpeg) is out of scope: --vid_folder holds one sub-folder of extracted frames per video.
 Image frames are cropped + normalised on the GPU (grnet_crop_normalise); .npy frames are ready crops.
 
@@ -547,17 +556,21 @@ class WindowBalance:
         self.kw = dict(fps=float(fps), gravity=float(gravity), window=int(window), settle=int(settle), max_step=int(max_step))
         self.videos = {}
 
-    def add_window(self, keys, j3, lengths, events):
+    def add_window(self, keys, j3, lengths, events, com=None):
         """keys[vi] and what WindowGait kept of its call: the window's joints (sum T,25,3), the videos' lengths and the events (sum T,) -> per video the
-        stance side of every frame's step (T,) int8: +1 left, -1 right, 0 none."""
+        stance side of every frame's step (T,) int8: +1 left, -1 right, 0 none.  com (--balance_com mesh): WindowBody's centres of the window (sum T,3)
+        float64, handed to the call as they are, in place of the segment table's."""
         if not keys:
             return []
+        more = {} if com is None else {"com": com}
         if self.device_call is not None:
-            made = self.device_call(j3, events, lengths=lengths, **self.kw)
+            made = self.device_call(j3, events, lengths=lengths, **self.kw, **more)
             out = {k: v.cpu().numpy() for k, v in made.items()}
         else:
             ev = events.cpu().numpy() if hasattr(events, "cpu") else np.asarray(events)
-            made = out = self.pipe.gait_balance(j3.cpu().numpy(), ev, lengths=lengths, **self.kw)
+            if com is not None:
+                more = {"com": com.cpu().numpy() if hasattr(com, "cpu") else np.asarray(com)}
+            made = out = self.pipe.gait_balance(j3.cpu().numpy(), ev, lengths=lengths, **self.kw, **more)
         self.tables = (made["steps"], made["per_sequence"])    # for WindowBootstrap: the step table and the rows as this call returned them
 
         def number(v):
@@ -582,6 +595,57 @@ class WindowBalance:
         with open(path, "w") as f:
             json.dump(self.videos, f, indent=1, allow_nan=False)
         print(f"Save balance of {len(self.videos)} videos to {path}.")
+        return path
+
+
+class WindowBody:
+    """--gait_body: the mesh's volume, centre of mass and second moments of every frame were made on the rank that ran the forward,
+    directly behind it (pipeline.run_on_frames(body=True): model.mesh_moments on the vertices where they lie), and came to rank 0 inside the
+    window's one all-gather.  Here, on rank 0, pipeline.body_rows makes of them per video the columns of pipeline.BODY_COLUMNS -- one host function:
+    the rows are downloaded for the database anyway.  The offsets are against DESIGN 4.22 rule 1's centre of mass (Winter's segment masses on the
+    kinectv2 joints) on the same frames.  UNIFORM DENSITY IS AN ASSUMPTION; the mesh is a statistical body shape, not the subject's; the model
+    predicts betas per frame, so the volume's CV measures the model's consistency, not the subject; nothing is judged."""
+
+    def __init__(self, pipe, density=985.0):
+        self.pipe = pipe
+        self.density = float(density)
+        self.videos = {}
+
+    def add_window(self, keys, per_video, rows):
+        """keys[vi], per_video[vi] (T,75) and rows[vi] (T,11) float64, the videos of one window -> per video (body_com (T,3) float32, body_volume (T,)
+        float32).  Keeps `com`, the window's (sum T,3) float64 centres where the rows lie, for WindowBalance (--balance_com mesh)."""
+        import torch
+        if not keys:
+            return []
+        lengths = [int(rows[vi].shape[0]) for vi in range(len(keys))]
+        both = torch.cat([rows[vi] for vi in range(len(keys))], 0)
+        self.com = both[:, 1:4].contiguous()
+        host = both.cpu().numpy()
+        j3 = torch.cat([per_video[vi].reshape(-1, 25, 3) for vi in range(len(keys))], 0).cpu().numpy()
+        table = self.pipe.body_rows(host, j3, lengths, density=self.density)
+
+        def number(v):
+            return float(v) if np.isfinite(v) else None          # a NaN is undefined: null, the file is strict JSON
+
+        def shown(v, form, unit=""):
+            return "none" if v is None else format(v, form) + unit
+        made, a = [], 0
+        for key, T, row in zip(keys, lengths, table):
+            made.append((host[a:a + T, 1:4].astype(np.float32), host[a:a + T, 0].astype(np.float32)))
+            video = {name: number(v) for name, v in zip(self.pipe.BODY_COLUMNS, row)}
+            video["density"] = self.density
+            self.videos[key] = video
+            print(f"Body: video {key}, {int(row[1])} of {int(row[0])} frames with a volume, volume {shown(video['volume_mean'], '.4f', ' m^3')}, CV "
+                  f"{shown(None if video['volume_cv'] is None else 100.0 * video['volume_cv'], '.2f', ' %')}, mass {shown(video['mass'], '.1f', ' kg')} at "
+                  f"{self.density:g} kg/m^3, centre of mass {shown(video['com_distance_mean'], '.3f', ' m')} from the segment table's.")
+            a += T
+        return made
+
+    def write(self, path):
+        import json
+        with open(path, "w") as f:
+            json.dump(self.videos, f, indent=1, allow_nan=False)
+        print(f"Save body measures of {len(self.videos)} videos to {path}.")
         return path
 
 
@@ -1186,8 +1250,14 @@ class WindowCoordination:
 def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weights=False, max_frames=128, dtype="f32", chunk=None,
                  model_factory=None, backend="nccl", exchange="torch", full_arena=False, annos=None, gt_path=None, metrics_out=None,
                  metrics_on_host=False, trajectory=None, tracks=None, gait=None, kinematics=None, turns=None, contacts=None, regularity=None,
-                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None, bootstrap=None, smoothness=None):
-    """smoothness: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_cut', 'amplitude', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
+                 harmonics=None, entropy=None, stability=None, spectrum=None, recurrence=None, coordination=None, balance=None, bootstrap=None, smoothness=None,
+                 body=None):
+    """body: {'density', 'on_host', 'out'} (each optional; needs no gait) -- also the volume, centre of mass, central second moments and area of the mesh of
+    every frame, made on the rank that ran the forward, directly behind it (pipeline.run_on_frames(body=True); 'on_host': the numpy
+    statement after a download) and carried to rank 0 as 22 further float32 words of each row of the window's one all-gather; per video the columns of
+    pipeline.BODY_COLUMNS (WindowBody), written to body['out'] (default: outpath with _body.json); the database gains 'body_com' (N,3) float32 and
+    'body_volume' (N,) float32.  With balance['com'] == 'mesh' the balance call takes these centres in place of the segment table's (needs body).
+    smoothness: {'fps', 'sigma', 'derivative', 'segment', 'hop', 'nfft', 'f_cut', 'amplitude', 'min_segments', 'all_frames', 'on_host', 'out'} (each optional;
     needs no gait, whose fps it takes where its own is not given, else 20) -- also the spectral arc length and the log dimensionless jerk of every video
     (WindowSmoothness), written to smoothness['out'] (default: outpath with _smoothness.json); with turns only straight walking counts unless
     'all_frames'; the database gains nothing.
@@ -1309,6 +1379,13 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
     prints = WindowBalance(pipe, model, balance.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
                            **{k: balance[k] for k in ("gravity", "window", "settle", "max_step") if balance.get(k) is not None}) \
         if balance is not None and rank == 0 else None
+    if balance is not None and balance.get("com", "table") not in ("table", "mesh"):
+        raise ValueError("balance['com'] is 'table' or 'mesh'")
+    mesh_com = balance is not None and balance.get("com", "table") == "mesh"
+    if mesh_com and body is None:
+        raise ValueError("balance['com'] == 'mesh' needs body: the centres of mass are made there")
+    shape = WindowBody(pipe, **({"density": body["density"]} if body.get("density") is not None else {})) if body is not None and rank == 0 else None
+    width = 75 if body is None else 75 + 22                    # a row of the all-gather: the joints, then the 11 doubles as 22 float32 words
     if bootstrap is not None and gait is None:
         raise ValueError("bootstrap needs gait: it resamples the steps and strides of that call")
     bars = WindowBootstrap(pipe, model, bootstrap.get("on_host", False), **({"fps": gait["fps"]} if gait.get("fps") is not None else {}),
@@ -1389,15 +1466,25 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
             # run_on_frames scales the boxes it is given by 1.1 in place (as Inference.__init__ does, inference.py:48):
             # hand it a copy of the UNSCALED rows; the database rows are scaled once below, on every rank alike
             # the joints stay on the device: no host synchronisation per work item, one all-gather per window
-            kp = pipe.run_on_frames(model, vids[vi][1], np.arange(lo, hi) + vids[vi][3], vids[vi][2][lo:hi].copy(), device=dev, batch_size=chunk, on_device=True)["kp_3d"]
-            mine.append(kp.reshape(hi - lo, 75))
-        local = torch.cat(mine, 0) if mine else torch.zeros(0, 75, device=dev)
-        per_video = harness.gather_work_items(items, local, 75, world, rank, dist, dev, comm=comm)
+            if body is None:
+                kp = pipe.run_on_frames(model, vids[vi][1], np.arange(lo, hi) + vids[vi][3], vids[vi][2][lo:hi].copy(), device=dev, batch_size=chunk, on_device=True)["kp_3d"]
+                mine.append(kp.reshape(hi - lo, 75))
+                continue
+            made = pipe.run_on_frames(model, vids[vi][1], np.arange(lo, hi) + vids[vi][3], vids[vi][2][lo:hi].copy(), device=dev, batch_size=chunk, on_device=True,
+                                      body=True, body_on_host=bool(body.get("on_host", False)))
+            mine.append(torch.cat([made["kp_3d"].reshape(hi - lo, 75), made["body"].contiguous().view(torch.float32).reshape(hi - lo, 22)], 1))
+        local = torch.cat(mine, 0) if mine else torch.zeros(0, width, device=dev)
+        per_video = harness.gather_work_items(items, local, width, world, rank, dist, dev, comm=comm)
+        body_rows = None
+        if body is not None:                                   # the doubles viewed back, bit for bit (a copy: a view needs an even offset); the joints as every other stage takes them
+            body_rows = {vi: rows[:, 75:].clone(memory_format=torch.contiguous_format).view(torch.float64) for vi, rows in per_video.items()}
+            per_video = {vi: rows[:, :75].contiguous() for vi, rows in per_video.items()}
         if metrics is not None:
             metrics.add_window([v[0] for v in vids], per_video)
         fitted = traj.add_window([v[0] for v in vids], per_video) if traj is not None else None
         gait_events = walk.add_window([v[0] for v in vids], per_video, fitted) if walk is not None else None
-        footprints_phase = prints.add_window([v[0] for v in vids], *walk.window) if prints is not None and vids else None
+        body_made = shape.add_window([v[0] for v in vids], per_video, body_rows) if shape is not None and vids else None
+        footprints_phase = prints.add_window([v[0] for v in vids], *walk.window, **({"com": shape.com} if mesh_com else {})) if prints is not None and vids else None
         if angles is not None and vids:
             angles.add_window([v[0] for v in vids], *walk.window)
         gait_phase = rounds.add_window([v[0] for v in vids], *walk.window, walk.rows, walk.videos) if rounds is not None and vids else None
@@ -1437,6 +1524,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
                     extra["gait_support"] = gait_support[vi]
                 if footprints_phase is not None:
                     extra["footprints_phase"] = footprints_phase[vi]
+                if body_made is not None:
+                    extra["body_com"], extra["body_volume"] = body_made[vi]
                 db.add(key, bboxes, per_video[vi].cpu().numpy().reshape(-1, 25, 3), **extra)
                 n_done += bboxes.shape[0]
             if wb < len(vidnames):
@@ -1472,6 +1561,8 @@ def prepare_data(fv, vid_folder, outpath, pretrained_file=None, synthetic_weight
         limbs.write(coordination.get("out") or osp.splitext(outpath)[0] + "_coordination.json")
     if prints is not None:
         prints.write(balance.get("out") or osp.splitext(outpath)[0] + "_balance.json")
+    if shape is not None:
+        shape.write(body.get("out") or osp.splitext(outpath)[0] + "_body.json")
     if bars is not None:
         bars.write(bootstrap.get("out") or osp.splitext(outpath)[0] + "_bootstrap.json")
     if comm is not None:
@@ -1563,6 +1654,14 @@ def main(argv=None):
     p.add_argument("--balance_max_step", type=int, default=None, help="with --gait_balance: two heel strikes further apart than this many frames are no step (default 30)")
     p.add_argument("--balance_gravity", type=float, default=None, help="with --gait_balance: metres a second squared; the joints are SMPL metres (default 9.81)")
     p.add_argument("--balance_on_host", action="store_true", help="with --gait_balance: the numpy float64 statement instead of the GPU kernels")
+    p.add_argument("--balance_com", type=str, default=None, choices=("table", "mesh"), help="with --gait_balance: the centre of mass it rests on: table = Winter's segment masses on "
+                   "the kinectv2 joints (default), mesh = the mesh's own of --gait_body, which must be given")
+    p.add_argument("--gait_body", action="store_true", help="with --vid_folder (no --gait needed): volume, centre of mass, central second moments and area of the SMPL mesh of every "
+                   "frame, exact sums over its closed surface, made where the vertices lie: 'body_com' (N,3) and 'body_volume' (N,) in the database, <outpath>_body.json, one "
+                   "'Body:' line per video.  Uniform density is an assumption; the mesh is a statistical body shape, not the subject's.  Reported, never judged")
+    p.add_argument("--body_out", type=str, default="", help="with --gait_body: the JSON file (default: --outpath with _body.json)")
+    p.add_argument("--body_density", type=float, default=None, help="with --gait_body: kilograms a cubic metre for the mass column (default 985, a whole-body textbook figure)")
+    p.add_argument("--body_on_host", action="store_true", help="with --gait_body: the numpy float64 statement after a download instead of the GPU kernel")
     p.add_argument("--gait_bootstrap", action="store_true", help="with --gait: percentile intervals of the step and stride parameters (mean, SD and CV of step time, step "
                    "length, step width and stride time; with --gait_turns also over straight walking alone, with --gait_balance also of stride length, step length, "
                    "step width and the margins of stability) by resampling the steps and strides with replacement on the device.  An interval from some 15 strides "
@@ -1971,6 +2070,17 @@ def main(argv=None):
             sys.exit("batch_generation.py: --smoothness_amplitude must be above 0 and at most 1")
         if a.smoothness_min_segments is not None and a.smoothness_min_segments < 1:
             sys.exit("batch_generation.py: --smoothness_min_segments must be at least 1")
+    for flag, given in (("--body_out", bool(a.body_out)), ("--body_density", a.body_density is not None), ("--body_on_host", a.body_on_host)):
+        if given and not a.gait_body:
+            sys.exit(f"batch_generation.py: {flag} belongs to --gait_body, which was not given")
+    if a.gait_body and not a.vid_folder:
+        sys.exit("batch_generation.py: --gait_body needs --vid_folder (the frames whose meshes it reads)")
+    if a.body_density is not None and not (np.isfinite(a.body_density) and a.body_density > 0):
+        sys.exit("batch_generation.py: --body_density must be a positive number of kilograms a cubic metre")
+    if a.balance_com is not None and not a.gait_balance:
+        sys.exit("batch_generation.py: --balance_com belongs to --gait_balance, which was not given")
+    if a.balance_com == "mesh" and not a.gait_body:
+        sys.exit("batch_generation.py: --balance_com mesh needs --gait_body, which was not given (the mesh's centre of mass is made there)")
     for flag, given in (("--coordination_out", bool(a.coordination_out)), ("--coordination_sigma", a.coordination_sigma is not None),
                         ("--coordination_derivative", a.coordination_derivative is not None), ("--coordination_segment", a.coordination_segment is not None),
                         ("--coordination_hop", a.coordination_hop is not None), ("--coordination_nfft", a.coordination_nfft is not None),
@@ -2072,7 +2182,8 @@ def main(argv=None):
                     "nfft": a.coordination_nfft, "f_lo": a.coordination_f_lo, "f_hi": a.coordination_f_hi, "min_segments": a.coordination_min_segments,
                     "all_frames": a.coordination_all_frames, "on_host": a.coordination_on_host, "out": a.coordination_out or None} if a.gait_coordination else None
     balance = {"gravity": a.balance_gravity, "window": a.balance_window, "settle": a.balance_settle, "max_step": a.balance_max_step, "on_host": a.balance_on_host,
-               "out": a.balance_out or None} if a.gait_balance else None
+               "out": a.balance_out or None, **({"com": a.balance_com} if a.balance_com is not None else {})} if a.gait_balance else None
+    body = {"density": a.body_density, "on_host": a.body_on_host, "out": a.body_out or None} if a.gait_body else None
     bootstrap = {"replicates": a.bootstrap_replicates, "level": a.bootstrap_level, "block": a.bootstrap_block, "seed": a.bootstrap_seed, "on_host": a.bootstrap_on_host,
                  "out": a.bootstrap_out or None} if a.gait_bootstrap else None
     prepare_data(fv=a.bbox_path, vid_folder=a.vid_folder, outpath=a.outpath, pretrained_file=a.pretrained_file,
@@ -2084,7 +2195,8 @@ def main(argv=None):
                  **({"stability": stability} if stability is not None else {}),
                  **({"spectrum": spectrum} if spectrum is not None else {}), **({"recurrence": recurrence} if recurrence is not None else {}),
                  **({"coordination": coordination} if coordination is not None else {}), **({"balance": balance} if balance is not None else {}),
-                 **({"bootstrap": bootstrap} if bootstrap is not None else {}), **({"smoothness": smoothness} if smoothness is not None else {}))
+                 **({"bootstrap": bootstrap} if bootstrap is not None else {}), **({"smoothness": smoothness} if smoothness is not None else {}),
+                 **({"body": body} if body is not None else {}))
 
 
 if __name__ == "__main__":

@@ -1023,6 +1023,37 @@ int grnet_gait_balance(grnet_t* h, const float* joints3d_dev, int J, const int32
 int grnet_op_gait_balance_steps(grnet_t* h, const double* rel_dev, const int32_t* events_dev, const int32_t* frame_offsets_host, int n_seq, double fps,
                                 double gravity, int window, int settle, int max_step, int max_steps, double* per_frame_dev, double* steps_dev,
                                 double* per_seq_dev, void* stream);
+/* grnet_gait_balance on a centre of mass the caller brings: com_dev float64 (sum T, 3), e.g. columns 1 to 3 of grnet_mesh_moments' rows, in place of
+ * the segment table.  Rule 1 becomes [c, c - left ankle, c - right ankle] with that c; rules 2 to 8, the outputs, the launches and every other
+ * refusal are grnet_gait_balance's.  A frame whose c is NaN is a frame without a centre of mass, as there. */
+int grnet_gait_balance_com(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                           const int32_t* events_dev, const double* com_dev, double fps, double gravity, int window, int settle, int max_step, int max_steps,
+                           double* per_frame_dev, double* steps_dev, double* per_seq_dev, void* stream);
+
+/* Volume, centre of mass, central second moments and surface area of the closed mesh of every frame (which is the specification).
+ * verts_dev float32 (n, 6890, 3): the vertices a forward call left on the device; the face table is grnet_load_faces'.  Float64 throughout, one
+ * rounding per operation, every comparison false for NaN.  Per frame: the origin o is the vertex the table's first index names, every corner is
+ * taken relative to it; a face with corners a, b, c gives d = a . (b x c), s = a + b + c and the eleven terms d, d s_k, d (a_k a_l + b_k b_l +
+ * c_k c_l + s_k s_l) for xx, yy, zz, xy, xz, yz, and |(b - a) x (c - a)|; column l of 1024 adds the terms of faces l, l + 1024, ... in rising order
+ * from +0.0, and the columns are reduced by the fixed tree col[l] += col[l + h], h = 512 .. 1.
+ * rows_dev float64 (n, 11): [0] volume = S0 / 6 in cubic metres; [1..3] the centre of mass o + S_k / (4 S0); [4..9] the central second moments per
+ * unit volume S_kl / (20 S0) - m_k m_l in square metres, xx, yy, zz, xy, xz, yz (the covariance of a UNIFORM mass distribution); [10] the area
+ * S10 / 2.  Where S0 > 0 is false (a mesh turned inside out, a degenerate one, a NaN) columns 1 to 9 are NaN, volume and area are stored as they
+ * come.  A non-finite vertex the table names makes its frame's row NaN by the arithmetic alone; one the table does not name changes nothing.
+ * sums_dev float64 (n, 11) or NULL: S0 .. S10.
+ * UNIFORM DENSITY IS AN ASSUMPTION; THE MESH IS A STATISTICAL BODY SHAPE, NOT THE SUBJECT'S; the numbers are reported, never judged.
+ * One launch, a workgroup per frame; fixed orders, no atomics: a frame has the same bits alone or among others.  Needs no weights: works before
+ * grnet_finalize.  No host synchronisation.
+ * GRNET_EINVAL (with a message, nothing is launched, the outputs stay untouched): a null verts_dev or rows_dev, n < 1, a face table that is not a
+ * closed, consistently oriented surface (the message carries the count of grnet_faces_closed).  GRNET_ESTATE: no face table loaded.
+ * grnet_op_mesh_moments: the same with the form of the gather named (timing hook): 0 the corners read from global memory, 1 the frame's vertices
+ * staged in LDS first.  The bits do not depend on it.
+ * grnet_faces_closed: host only.  *unmatched_edges_host = how many of the table's 3 F directed edges (i, j) share their pair with another edge,
+ * have no reverse edge (j, i), or join a vertex to itself; 0 for a closed, consistently oriented surface.  Counted (a sort of 3 F keys) at the first
+ * call after grnet_load_faces and kept. */
+int grnet_mesh_moments(grnet_t* h, const float* verts_dev, int n, double* rows_dev, double* sums_dev, void* stream);
+int grnet_op_mesh_moments(grnet_t* h, const float* verts_dev, int n, double* rows_dev, double* sums_dev, int form, void* stream);
+int grnet_faces_closed(grnet_t* h, int* unmatched_edges_host);
 
 /* The samples behind the gait call's step and stride columns, one row per step and per stride (which is the specification).
  * events_dev int32 (sum T) and per_frame_dev float64 (sum T, 7) as grnet_gait_parameters returned them, frame_offsets_host as there; phase_dev int32

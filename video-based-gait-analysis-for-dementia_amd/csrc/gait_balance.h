@@ -3,6 +3,7 @@
 // (-ffp-contract=off): every operation below rounds once, in the order the parentheses show.  Every test is a comparison that is false for NaN.
 //
 // balance_com       -- rule 1 of ONE frame: c, rL = c - left ankle, rR = c - right ankle, the nine values of a row of `rel`.
+// balance_rel_of    -- the same row from a centre of mass the caller brings (grnet_gait_balance_com).
 // A MARK is a frame whose events carry a heel-strike bit; the sequence's marks in time order are a list of (frame << 2 | bits).  A frame with both
 // bits is a mark that is a strike of neither foot: no pair with it is a step.
 // balance_marks_before / balance_mark_count -- a mark's place in the list from the two heel-strike bitmasks and the marks in front of each word.
@@ -77,6 +78,15 @@ GRK_TRANS_HD void balance_com(const float* rows, const BalanceSegments& seg, int
         rel[a] = c;
         rel[3 + a] = c - (double)rows[3 * lankle + a];
         rel[6 + a] = c - (double)rows[3 * rankle + a];
+    }
+}
+
+// rule 1 with a given c (3 values): [c, c - left ankle, c - right ankle]
+GRK_TRANS_HD void balance_rel_of(const float* rows, const double* c, int lankle, int rankle, double* rel) {
+    for (int a = 0; a < 3; ++a) {
+        rel[a] = c[a];
+        rel[3 + a] = c[a] - (double)rows[3 * lankle + a];
+        rel[6 + a] = c[a] - (double)rows[3 * rankle + a];
     }
 }
 

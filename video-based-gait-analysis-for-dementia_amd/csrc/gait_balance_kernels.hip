@@ -21,7 +21,8 @@
 //
 // balance_path_kernel   -- ONE LANE PER FRAME: its sequence by bisection in the offsets, the marks in front of it from the words, rule 7.
 //
-// The hook grnet_op_gait_balance_steps launches the last two on a caller's [c, rL, rR].
+// The hook grnet_op_gait_balance_steps launches the last two on a caller's [c, rL, rR].  grnet_gait_balance_com launches balance_com_frames_kernel
+// in place of the first: the caller's c (the mesh's centre of mass), the ankles subtracted.
 #include "kernels.h"
 #include "device.h"
 #include "gait_balance.h"
@@ -35,6 +36,16 @@ __global__ __launch_bounds__(256) void balance_frames_kernel(const float* __rest
     if (f >= frames) return;
     double r[kBalanceRelCols];
     balance_com(joints + (size_t)f * J * 3, seg, lankle, rankle, r);
+    for (int k = 0; k < kBalanceRelCols; ++k) rel[(size_t)f * kBalanceRelCols + k] = r[k];
+}
+
+// rule 1 with the caller's centre of mass in place of the segment table's (grnet_gait_balance_com): ONE LANE PER FRAME
+__global__ __launch_bounds__(256) void balance_com_frames_kernel(const float* __restrict__ joints, int J, int frames, int lankle, int rankle,
+                                                                 const double* __restrict__ com, double* __restrict__ rel) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= frames) return;
+    double r[kBalanceRelCols];
+    balance_rel_of(joints + (size_t)f * J * 3, com + (size_t)f * 3, lankle, rankle, r);
     for (int k = 0; k < kBalanceRelCols; ++k) rel[(size_t)f * kBalanceRelCols + k] = r[k];
 }
 
@@ -128,6 +139,10 @@ __global__ __launch_bounds__(256) void balance_path_kernel(const int* __restrict
 
 hipError_t launch_balance_frames(const float* joints, int J, int frames, const GaitTable& tab, const BalanceSegments& seg, double* rel, hipStream_t s) {
     return launch_k(balance_frames_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, joints, J, frames, tab.j[4], tab.j[5], seg, rel);
+}
+
+hipError_t launch_balance_com_frames(const float* joints, int J, int frames, const GaitTable& tab, const double* com, double* rel, hipStream_t s) {
+    return launch_k(balance_com_frames_kernel, dim3((frames + 255) / 256), dim3(256), 0, s, joints, J, frames, tab.j[4], tab.j[5], com, rel);
 }
 
 hipError_t launch_balance_steps(const int* off, int n_seq, const BalanceRule& rule, const double* rel, const int* events, unsigned long long* words,

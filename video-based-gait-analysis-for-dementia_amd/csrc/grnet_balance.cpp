@@ -1,5 +1,6 @@
 // Footprints, centre of mass and margin of stability behind the C ABI (kernels: gait_balance_kernels.hip, arithmetic: gait_balance.h, rules: DESIGN
-// 4.22): grnet_gait_balance and the hook that runs rules 2 to 8 alone.  Neither reads a weight or the arena.  Their scratch and their table of
+// 4.22): grnet_gait_balance, grnet_gait_balance_com (the same call on a centre of mass the caller brings) and the hook that runs rules 2 to 8
+// alone.  None reads a weight or the arena.  Their scratch and their table of
 // offsets are seq_call's (grnet_seq.cpp): the call returns without waiting for the device.  The segment table travels as a kernel argument.
 #include "grnet_impl.h"
 #include "gait_balance.h"
@@ -50,6 +51,35 @@ int grnet_gait_balance(grnet_t* h, const float* joints3d_dev, int J, const int32
         return rc;
     const int frames = frame_offsets_host[n_seq];
     hipError_t e = launch_balance_frames(joints3d_dev, J, frames, tab, seg, at.rel(c.behind), s);
+    if (e == hipSuccess)
+        e = launch_balance_steps(c.off, n_seq, rule, at.rel(c.behind), events_dev, at.words(c.behind), at.mask_words, at.list(c.behind), at.pairs(c.behind), steps_dev,
+                                 per_seq_dev, s);
+    if (e == hipSuccess) e = launch_balance_path(c.off, n_seq, frames, at.rel(c.behind), at.words(c.behind), at.mask_words, at.pairs(c.behind), per_frame_dev, s);
+    if (e != hipSuccess) return h->fail(GRNET_EHIP, name + hipGetErrorString(e));
+    return 0;
+}
+
+int grnet_gait_balance_com(grnet_t* h, const float* joints3d_dev, int J, const int32_t* frame_offsets_host, int n_seq, const int32_t* joints_host,
+                           const int32_t* events_dev, const double* com_dev, double fps, double gravity, int window, int settle, int max_step, int max_steps,
+                           double* per_frame_dev, double* steps_dev, double* per_seq_dev, void* stream) {
+    if (!h) return GRNET_EINVAL;
+    const std::string name = "grnet_gait_balance_com: ";
+    if (!joints3d_dev || !frame_offsets_host || !joints_host || !events_dev || !com_dev || !per_frame_dev || !steps_dev || !per_seq_dev)
+        return h->fail(GRNET_EINVAL, name + "null pointer (joints3d_dev, frame_offsets_host, joints_host, events_dev, com_dev, per_frame_dev, steps_dev and "
+                                            "per_seq_dev are all needed)");
+    GaitTable tab{};
+    std::string why = joint_table_take(joints_host, 8, J, tab.j);
+    const BalanceRule rule{fps, gravity, window, settle, max_step, max_steps};
+    if (why.empty()) why = rule_text(balance_rule_error(rule));
+    if (!why.empty()) return h->fail(GRNET_EINVAL, name + why);
+    BalanceScratch at;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SeqCall c;
+    if (int rc = seq_call(h, name, frame_offsets_host, n_seq, std::max(3LL * J, (long long)kBalancePairCols), 0., s, &c,
+                          [&](int frames) { return at.plan(frames, n_seq, true); }))
+        return rc;
+    const int frames = frame_offsets_host[n_seq];
+    hipError_t e = launch_balance_com_frames(joints3d_dev, J, frames, tab, com_dev, at.rel(c.behind), s);      // the caller's c; the steps and the path as grnet_gait_balance
     if (e == hipSuccess)
         e = launch_balance_steps(c.off, n_seq, rule, at.rel(c.behind), events_dev, at.words(c.behind), at.mask_words, at.list(c.behind), at.pairs(c.behind), steps_dev,
                                  per_seq_dev, s);

@@ -24,6 +24,7 @@
 //   grnet_balance.cpp  footprints, centre of mass and margin of stability: grnet_gait_balance and its steps hook
 //   grnet_bootstrap.cpp the gait call's step and stride tables and bootstrap intervals of a per-step table: grnet_gait_step_tables, grnet_bootstrap_table
 //   grnet_smoothness.cpp movement smoothness: grnet_gait_smoothness, its slot count and its arc-length hook
+//   grnet_body.cpp     mesh volume, centre of mass and second moments: grnet_mesh_moments, its form hook, grnet_faces_closed
 //   grnet.cpp          the rest of the C ABI of include/grnet_hip.h
 #pragma once
 #include "../../include/grnet_hip.h"
@@ -264,6 +265,10 @@ struct grnet {
     RasterMesh rmesh{};
     void* rmesh_block = nullptr;
     void* raster_ws = nullptr;
+    // grnet_mesh_moments / grnet_faces_closed: the table as grnet_load_faces took it, and its directed edges that are duplicated or lack their
+    // reverse (DESIGN 4.25 rule 5; < 0: not counted since the table was loaded) -- grnet_body.cpp
+    std::vector<int32_t> faces_host;
+    long long faces_unmatched = -1;
     // grnet_render_segments: the segment table of a call goes to the device through pinned host memory, a ring of kSegStageSlots tables each with
     // the event recorded behind its copy, so the call enqueues and returns (grnet_skeleton.cpp)
     static constexpr int kSegStageSlots = 4;

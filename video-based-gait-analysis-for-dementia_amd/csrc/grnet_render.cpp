@@ -107,6 +107,8 @@ void grnet::faces_clear() {
     (void)hipFree(rmesh_block);
     rmesh_block = nullptr;
     rmesh = RasterMesh{};
+    faces_host.clear();
+    faces_unmatched = -1;
 }
 
 extern "C" {
@@ -123,6 +125,8 @@ int grnet_load_faces(grnet_t* h, const int32_t* faces_host, int n_faces) {
     h->faces_clear();                                       // a failure above leaves the table loaded before in place
     h->rmesh = m;
     h->rmesh_block = block;
+    h->faces_host.assign(faces_host, faces_host + (size_t)3 * n_faces);      // for the closed-surface rule of grnet_mesh_moments, counted at its first call
+    h->faces_unmatched = -1;
     return 0;
 }
 

@@ -540,6 +540,8 @@ hipError_t launch_balance_steps(const int* off, int n_seq, const BalanceRule& ru
 // one lane per frame behind launch_balance_steps, on its words and pairs: per_frame (frames,8)
 hipError_t launch_balance_path(const int* off, int n_seq, int frames, const double* rel, const unsigned long long* words, size_t mask_words,
                                const double* pairs, double* per_frame, hipStream_t s);
+// launch_balance_frames with the caller's centre of mass com (frames,3) in place of the segment table: rel (frames,9) = [com, com - left ankle, com - right ankle]
+hipError_t launch_balance_com_frames(const float* joints, int J, int frames, const GaitTable& tab, const double* com, double* rel, hipStream_t s);
 
 // The gait call's per-step and per-stride tables and bootstrap intervals of a per-step table (csrc/gait_bootstrap_kernels.hip, compiled without fma
 // contraction; the arithmetic and the generator: csrc/gait_bootstrap.h).  The table kernel's workgroup is the gait call's kGaitThreads
@@ -620,6 +622,13 @@ hipError_t launch_raster_lines_cover(const RasterChunk& c, const RasterView& v, 
 hipError_t launch_raster_lines_resolve(const RasterChunk& c, const RasterView& v, const RasterMesh& m, RasterWork w, unsigned char* images, hipStream_t s);
 // the wireframe's depth clear alone, over `slots` depth images and their bounding boxes: the skeleton view's clear
 hipError_t launch_raster_lines_clear(const RasterView& v, RasterWork w, int slots, hipStream_t s);
+
+// Volume, centre of mass, central second moments and area of the closed mesh (csrc/mesh_moments_kernels.hip, compiled without fma contraction; the
+// arithmetic: csrc/mesh_moments.h) ----
+constexpr int kMeshFormDirect = 0, kMeshFormStaged = 1;     // the corners gathered from global memory / from a copy of the frame in LDS: the same bits
+constexpr int kMeshFormDefault = kMeshFormDirect;           // the faster one on an MI355X (profiles/mesh_moments_times.txt)
+// one workgroup per frame on verts (n,m.n_verts,3) and the table of m: rows (n,11), sums (n,11) or null
+hipError_t launch_mesh_moments(const float* verts, int n, const RasterMesh& m, int form, double* rows, double* sums, hipStream_t s);
 
 // The 3D skeleton view of demo.py --skeleton_view (demo.py:303-361, lib/utils/vis.py:571-587; csrc/skeleton_kernels.hip) ----
 // Wide line segments between projected points, ALL skeletons aimed at an image in ONE depth image.  A launch group is up to kRasterSlots

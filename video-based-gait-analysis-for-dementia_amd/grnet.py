@@ -1760,7 +1760,7 @@ class GRNet:
         return ev, off, out
 
     def gait_balance(self, joints3d, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256,
-                     segments=_lib.BALANCE_SEGMENTS_KINECTV2, joints=_lib.GAIT_JOINTS_KINECTV2):
+                     segments=None, joints=_lib.GAIT_JOINTS_KINECTV2, com=None):
         """Footprints on the floor, the centre of mass over them and the margin of stability at foot placement of every sequence on the device
         (grnet_gait_balance; the rules and the columns: DESIGN 4.22, pipeline.BALANCE_COLUMNS).  Called after gait_parameters on the same joints3d,
         lengths and joints, with its `events` (taken as int32).  segments: rows of (proximal joint, distal joint, mass, the COM's fraction from the
@@ -1768,11 +1768,25 @@ class GRNet:
         strike is a footprint-to-footprint vector, and the COM relative to the planted ankle, fitted over the last `window` + 1 frames of a step,
         gives its velocity.  THE FLOOR IS THE x-z PLANE OF A LEVEL, FIXED CAMERA; the segment layout is unvalidated; a margin of a few centimetres
         carries about two of noise per step.  Returns a dict of device tensors: per_frame (n,8) float64 [c, W, stance side, chain]; steps
-        (n_seq,max_steps,15) float64; per_sequence (n_seq,24) float64.  Works before finalize(): no weight is read.  Nothing synchronises."""
+        (n_seq,max_steps,15) float64; per_sequence (n_seq,24) float64.  Works before finalize(): no weight is read.  Nothing synchronises.
+        segments: None stands for BALANCE_SEGMENTS_KINECTV2.  com (n,3), taken as float64 on the device: the centre of mass of every frame in
+        place of the segment table's -- columns 1 to 3 of mesh_moments' rows (grnet_gait_balance_com); together with segments it is refused."""
         j = self._rows_input(joints3d, "joints3d", (None, 3), torch.float32)
         n = j.shape[0]
         table = self._joint_table(joints, _lib.GAIT_JOINTS_KINECTV2, _GAIT_JOINT_NAMES)
-        seg = np.asarray(segments, np.float64)
+        if com is not None:
+            if segments is not None:
+                raise ValueError("segments and com are two sources of the centre of mass: give one")
+            c = self._rows_input(com, "com", (3,), torch.float64)
+            if c.shape[0] != n:
+                raise ValueError(f"com must be ({n},3), got {tuple(c.shape)}")
+            ev, off, out = self._balance_call(n, lengths, events, window, settle, max_step, max_steps, "joints3d")
+            rc = self._lib.grnet_gait_balance_com(self._h, j.data_ptr(), j.shape[1], _i32p(off), len(off) - 1, _i32p(table), ev.data_ptr(), c.data_ptr(), float(fps),
+                                                  float(gravity), int(window), int(settle), int(max_step), int(max_steps), out["per_frame"].data_ptr(),
+                                                  out["steps"].data_ptr(), out["per_sequence"].data_ptr(), self._stream())
+            _lib.check(self._lib, self._h, rc, "grnet_gait_balance_com")
+            return out
+        seg = np.asarray(_lib.BALANCE_SEGMENTS_KINECTV2 if segments is None else segments, np.float64)
         if seg.ndim != 2 or seg.shape[1] != 4 or seg.shape[0] < 1 or not np.array_equal(seg[:, :2], np.floor(seg[:, :2])) or np.abs(seg[:, :2]).max() >= 2**31:
             raise ValueError(f"segments must be rows of (proximal joint, distal joint, mass, fraction), got shape {seg.shape}")
         pairs, weights = np.ascontiguousarray(seg[:, :2], np.int32), np.ascontiguousarray(seg[:, 2:])
@@ -1794,6 +1808,36 @@ class GRNet:
                                                    out["per_sequence"].data_ptr(), self._stream())
         _lib.check(self._lib, self._h, rc, "grnet_op_gait_balance_steps")
         return out
+
+    # ------------------------------------------------------------------ mesh volume, centre of mass and second moments
+    def faces_closed(self):
+        """How many directed edges of the loaded face table are duplicated, lack their reverse edge or join a vertex to itself
+        (grnet_faces_closed; host only, counted once per load_faces): 0 for a closed, consistently oriented surface, the only kind mesh_moments takes."""
+        count = C.c_int(-1)
+        _lib.check(self._lib, self._h, self._lib.grnet_faces_closed(self._h, C.byref(count)), "grnet_faces_closed")
+        return int(count.value)
+
+    def mesh_moments(self, verts, return_sums=False, form=None):
+        """Volume, centre of mass, central second moments per unit volume and area of the closed mesh of every frame on the device
+        (grnet_mesh_moments; the rules and the columns: DESIGN 4.25, pipeline.MESH_MOMENT_COLUMNS).  verts (n,6890,3), any float dtype, taken as
+        float32 on the device: what forward() returned as 'verts'.  Needs load_faces (load_smpl loads the table of SMPL_NEUTRAL.npz).  Returns
+        rows (n,11) float64 on the device; with return_sums (rows, sums (n,11)).  Where the signed volume is not positive the nine columns of the
+        centre and the moments are NaN.  UNIFORM DENSITY IS AN ASSUMPTION; the mesh is a statistical body shape, not the subject's.  form: None,
+        or 0 / 1 to name the kernel's gather (grnet_op_mesh_moments: the same bits).  Works before finalize().  Nothing synchronises."""
+        v = torch.as_tensor(verts)
+        if v.dim() != 3 or v.shape[0] < 1 or tuple(v.shape[1:]) != (netspec.NUM_VERTS, 3) or not v.dtype.is_floating_point:
+            raise ValueError(f"verts must be a float (n,{netspec.NUM_VERTS},3) tensor with n >= 1, got {v.dtype} {tuple(v.shape)}")
+        v = v.to(self.device, torch.float32).contiguous()
+        n = v.shape[0]
+        rows = torch.empty(n, 11, dtype=torch.float64, device=self.device)
+        sums = torch.empty(n, 11, dtype=torch.float64, device=self.device) if return_sums else None
+        sums_ptr = sums.data_ptr() if return_sums else None
+        if form is None:
+            rc, what = self._lib.grnet_mesh_moments(self._h, v.data_ptr(), n, rows.data_ptr(), sums_ptr, self._stream()), "grnet_mesh_moments"
+        else:
+            rc, what = self._lib.grnet_op_mesh_moments(self._h, v.data_ptr(), n, rows.data_ptr(), sums_ptr, int(form), self._stream()), "grnet_op_mesh_moments"
+        _lib.check(self._lib, self._h, rc, what)
+        return (rows, sums) if return_sums else rows
 
     # ------------------------------------------------------------------ step and stride tables, bootstrap intervals (DESIGN 4.23)
     def gait_step_tables(self, events, per_frame, lengths=None, fps=20.0, max_rows=256, phase=None, straight_only=False):

@@ -3017,6 +3017,19 @@ def _balance_segments(segments, J):
     return idx[:, 0].astype(np.int64), idx[:, 1].astype(np.int64), seg[:, 2], seg[:, 3]
 
 
+def balance_table_com(j3, segments=BALANCE_SEGMENTS_KINECTV2):
+    """Rule 1 of DESIGN 4.22 alone: the centre of mass (n,3) float64 of widened joints j3 (n,J,3) from a segment table."""
+    n, J = j3.shape[:2]
+    prox, dist, mass, frac = _balance_segments(segments, J)
+    with np.errstate(all="ignore"):
+        num, den = np.zeros((n, 3)), 0.0
+        for i in range(len(mass)):
+            P, Dj = j3[:, prox[i]], j3[:, dist[i]]
+            num = num + mass[i] * (P + frac[i] * (Dj - P))
+            den = den + mass[i]
+        return num / den
+
+
 def gait_balance_steps(rel, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256):
     """Rules 2 to 8 of DESIGN 4.22 on given rel (n,9) float64 = [c, rL, rR]: the host statement of GRNet.op_gait_balance_steps.  events (n,) as
     gait_parameters returned them (bits 0 and 1 are read).  Returns {'per_frame': (n,8), columns BALANCE_FRAME_COLUMNS, 'steps': (n_seq,max_steps,15),
@@ -3121,33 +3134,185 @@ def gait_balance_steps(rel, events, lengths=None, fps=20.0, gravity=9.81, window
 
 
 def gait_balance(joints3d, events, lengths=None, fps=20.0, gravity=9.81, window=4, settle=1, max_step=30, max_steps=256,
-                 segments=BALANCE_SEGMENTS_KINECTV2, joints=GAIT_JOINTS_KINECTV2):
+                 segments=None, joints=GAIT_JOINTS_KINECTV2, com=None):
     """Footprints on the floor, the centre of mass over them and the margin of stability at foot placement from 3D joints in numpy float64 (Hof, Gagey
     and Halbertsma 2005; Winter 2009; the rules: DESIGN 4.22): the host statement of GRNet.gait_balance, same arguments, a dict of numpy arrays -- the
     same operations in the same order.  joints3d (n,J,3) as gait_parameters takes them; events: its events; joints: its table, of which the two
     ankles are read; segments: rows of (proximal joint, distal joint, mass, fraction).  THE FLOOR IS THE x-z PLANE OF A LEVEL, FIXED CAMERA; the
-    segment layout is unvalidated; the numbers are reported, never judged.  Also returns 'rel' (n,9) = [c, rL, rR]."""
+    segment layout is unvalidated; the numbers are reported, never judged.  Also returns 'rel' (n,9) = [c, rL, rR].  segments: None stands for
+    BALANCE_SEGMENTS_KINECTV2.  com (n,3) float64: the centre of mass of every frame in place of the segment table's (the mesh's, DESIGN 4.25: columns
+    1 to 3 of mesh_moments' rows); together with segments it is refused."""
     j3 = _widened(joints3d, "joints3d")
     n, J = j3.shape[:2]
     lengths = _sequence_lengths(n, lengths)
     tab = _joint_table(joints, 8, J, _GAIT_JOINT_NAMES)
     _balance_rule_check(fps, gravity, window, settle, max_step, max_steps)
-    prox, dist, mass, frac = _balance_segments(segments, J)
+    if com is not None:
+        if segments is not None:
+            raise ValueError("segments and com are two sources of the centre of mass: give one")
+        c = np.asarray(com, np.float64)
+        if c.shape != (n, 3):
+            raise ValueError(f"com must be ({n},3), got {c.shape}")
+    else:
+        c = balance_table_com(j3, BALANCE_SEGMENTS_KINECTV2 if segments is None else segments)
     with np.errstate(all="ignore"):
-        num, den = np.zeros((n, 3)), 0.0
-        for i in range(len(mass)):
-            P, Dj = j3[:, prox[i]], j3[:, dist[i]]
-            num = num + mass[i] * (P + frac[i] * (Dj - P))
-            den = den + mass[i]
-        c = num / den
         rel = np.concatenate([c, c - j3[:, tab[4]], c - j3[:, tab[5]]], axis=1)
     out = gait_balance_steps(rel, events, lengths, fps, gravity, window, settle, max_step, max_steps)
     out["rel"] = rel
     return out
 
 
+# ----------------------------------------------------------------------------- mesh volume, centre of mass and second moments (DESIGN 4.25)
+MESH_MOMENT_COLUMNS = ("volume", "com_x", "com_y", "com_z", "c_xx", "c_yy", "c_zz", "c_xy", "c_xz", "c_yz", "area")
+MESH_COLUMNS = 1024                                              # NCOL of rule 3
+_MESH_SECOND = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))
+BODY_COLUMNS = ("frames", "frames_valid", "volume_mean", "volume_sd", "volume_cv", "mass", "area_mean", "gyration_x_mean", "gyration_y_mean",
+                "gyration_z_mean", "com_offset_x_mean", "com_offset_y_mean", "com_offset_z_mean", "com_distance_mean", "com_distance_max")
+BODY_DENSITY = 985.0                                             # kg / m^3: a whole-body textbook figure, an assumption
+
+
+def _faces_table(faces, V=None):
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise ValueError(f"faces must be an integer (F,3) table, got {f.dtype} {f.shape}")
+    if f.shape[0] < 1:
+        raise ValueError(f"n_faces {f.shape[0]} < 1")
+    f = f.astype(np.int64)
+    if V is not None:
+        bad = np.flatnonzero((f.reshape(-1) < 0) | (f.reshape(-1) >= V))
+        if bad.size:
+            raise ValueError(f"face {bad[0] // 3} names vertex {f.reshape(-1)[bad[0]]}, outside [0, {V})")
+    return f
+
+
+def faces_closed(faces, V=netspec.NUM_VERTS):
+    """Rule 5 of DESIGN 4.25, the host statement of GRNet.faces_closed: how many of the 3 F directed edges (i, j) of an (F,3) table share their
+    pair with another edge, have no reverse edge (j, i), or join a vertex to itself.  0: a closed, consistently oriented surface."""
+    f = _faces_table(faces, V)
+    i, j = f.reshape(-1), np.roll(f, -1, axis=1).reshape(-1)
+    keys, back = i * V + j, j * V + i
+    uniq, counts = np.unique(keys, return_counts=True)
+    twice = counts[np.searchsorted(uniq, keys)] > 1
+    at = np.minimum(np.searchsorted(uniq, back), len(uniq) - 1)
+    answered = (uniq[at] == back) & (i != j)
+    return int(np.count_nonzero(twice | ~answered))
+
+
+def mesh_face_terms(a, b, c):
+    """Rule 2 of DESIGN 4.25 on corners a, b, c (...,3) float64 relative to the origin: the eleven terms (...,11)."""
+    ax, ay, az = a[..., 0], a[..., 1], a[..., 2]
+    bx, by, bz = b[..., 0], b[..., 1], b[..., 2]
+    cx, cy, cz = c[..., 0], c[..., 1], c[..., 2]
+    d = (ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz)) + az * (bx * cy - by * cx)
+    s = (a + b) + c
+    t = np.empty(a.shape[:-1] + (11,))
+    t[..., 0] = d
+    for k in range(3):
+        t[..., 1 + k] = d * s[..., k]
+    for q, (k, l) in enumerate(_MESH_SECOND):
+        t[..., 4 + q] = d * (((a[..., k] * a[..., l] + b[..., k] * b[..., l]) + c[..., k] * c[..., l]) + s[..., k] * s[..., l])
+    u, w = b - a, c - a
+    nx, ny, nz = u[..., 1] * w[..., 2] - u[..., 2] * w[..., 1], u[..., 2] * w[..., 0] - u[..., 0] * w[..., 2], u[..., 0] * w[..., 1] - u[..., 1] * w[..., 0]
+    t[..., 10] = np.sqrt((nx * nx + ny * ny) + nz * nz)
+    return t
+
+
+def mesh_column_sums(terms):
+    """Rule 3 of DESIGN 4.25 on terms (n,F,K): column l of 1024 adds faces l, l + 1024, ... in rising order from +0.0, then the tree
+    col[l] += col[l + h] for l < h, h = 512 .. 1 -> (n,K)."""
+    n, F, K = terms.shape
+    col = np.zeros((n, MESH_COLUMNS, K))
+    for lo in range(0, F, MESH_COLUMNS):
+        step = terms[:, lo:lo + MESH_COLUMNS]
+        col[:, :step.shape[1]] = col[:, :step.shape[1]] + step
+    h = MESH_COLUMNS // 2
+    while h >= 1:
+        col[:, :h] = col[:, :h] + col[:, h:2 * h]
+        h //= 2
+    return col[:, 0].copy()
+
+
+def mesh_rows_of(sums, origin):
+    """Rule 4 of DESIGN 4.25: sums (n,11) and origins (n,3) -> rows (n,11), columns MESH_MOMENT_COLUMNS."""
+    S = np.asarray(sums, np.float64)
+    rows = np.full((S.shape[0], 11), np.nan)
+    S0 = S[:, 0]
+    has = S0 > 0
+    m = S[:, 1:4] / (4.0 * S0)[:, None]
+    E = S[:, 4:10] / (20.0 * S0)[:, None]
+    rows[:, 0] = S0 / 6.0
+    rows[:, 1:4] = np.where(has[:, None], origin + m, np.nan)
+    for q, (k, l) in enumerate(_MESH_SECOND):
+        rows[:, 4 + q] = np.where(has, E[:, q] - m[:, k] * m[:, l], np.nan)
+    rows[:, 10] = S[:, 10] / 2.0
+    return rows
+
+
+def mesh_moments(verts, faces, return_sums=False, chunk=16):
+    """Volume, centre of mass, central second moments per unit volume and area of a closed mesh in numpy float64: the host statement
+    of GRNet.mesh_moments -- the same operations in the same order, so the same bits.  verts (n,V,3), rounded to float32 and widened; faces (F,3),
+    which must be a closed, consistently oriented surface over [0, V) (faces_closed).  Returns rows (n,11), columns MESH_MOMENT_COLUMNS; with
+    return_sums also the sums (n,11).  UNIFORM DENSITY IS AN ASSUMPTION; the numbers are reported, never judged."""
+    v = _widened(verts, "verts")
+    f = _faces_table(faces, v.shape[1])
+    bad = faces_closed(f, v.shape[1])
+    if bad:
+        raise ValueError(f"the face table is not a closed, consistently oriented surface: {bad} directed edges are duplicated or lack their reverse edge")
+    sums, origin = np.empty((v.shape[0], 11)), v[:, f[0, 0]].copy()
+    with np.errstate(all="ignore"):
+        for lo in range(0, v.shape[0], chunk):
+            x = v[lo:lo + chunk]
+            o = origin[lo:lo + chunk, None, :]
+            sums[lo:lo + chunk] = mesh_column_sums(mesh_face_terms(x[:, f[:, 0]] - o, x[:, f[:, 1]] - o, x[:, f[:, 2]] - o))
+        rows = mesh_rows_of(sums, origin)
+    return (rows, sums) if return_sums else rows
+
+
+def body_rows(rows, joints3d, lengths=None, density=BODY_DENSITY, segments=BALANCE_SEGMENTS_KINECTV2, joints=GAIT_JOINTS_KINECTV2):
+    """Per video the columns BODY_COLUMNS from mesh_moments' rows (n,11) and the joints (n,J,3) of the same frames, on the host: a
+    frame is valid where its nine columns of centre and moments are finite; volume, area and the radii of gyration sqrt(C_kk) are means over the
+    valid frames, volume_sd two-pass with ddof 0, volume_cv = sd / mean, mass = density * volume_mean; com_offset and com_distance are the mesh's
+    centre of mass minus DESIGN 4.22 rule 1's (the segment table's on the same joints) over the valid frames where that one is finite too.  Sums run in
+    time order from +0.0; a value is NaN where its count is 0.  joints: gait_balance's table, checked as there.  Returns (n_seq,15)."""
+    r = np.asarray(rows, np.float64)
+    if r.ndim != 2 or r.shape[1] != 11 or r.shape[0] < 1:
+        raise ValueError(f"rows must be (n,11) with n >= 1, got {r.shape}")
+    j3 = _widened(joints3d, "joints3d")
+    if j3.shape[0] != r.shape[0]:
+        raise ValueError(f"joints3d has {j3.shape[0]} frames, rows {r.shape[0]}")
+    lengths = _sequence_lengths(r.shape[0], lengths)
+    _joint_table(joints, 8, j3.shape[1], _GAIT_JOINT_NAMES)
+    if not np.isfinite(density) or not density > 0:
+        raise ValueError("density must be positive and finite")
+    table = balance_table_com(j3, segments)
+    out = np.full((len(lengths), len(BODY_COLUMNS)), np.nan)
+    a = 0
+    with np.errstate(all="ignore"):
+        for q, T in enumerate(lengths):
+            x, c = r[a:a + T], table[a:a + T]
+            a += T
+            valid = np.isfinite(x[:, 1:10]).all(axis=1) & np.isfinite(x[:, 0]) & np.isfinite(x[:, 10])
+            y = x[valid]
+            row = out[q]
+            row[0], row[1] = T, len(y)
+            row[2], row[3] = _gait_mean_sd(y[:, 0])
+            if len(y):
+                row[4], row[5] = row[3] / row[2], float(density) * row[2]
+                row[6] = _gait_sum(y[:, 10]) / len(y)
+                for k in range(3):
+                    row[7 + k] = _gait_sum(np.sqrt(y[:, 4 + k])) / len(y)
+            both = valid & np.isfinite(c).all(axis=1)
+            d = x[both, 1:4] - c[both]
+            if len(d):
+                for k in range(3):
+                    row[10 + k] = _gait_sum(d[:, k]) / len(d)
+                dist = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+                row[13], row[14] = _gait_sum(dist) / len(dist), float(dist.max())
+    return out
+
+
 # ----------------------------------------------------------------------------- step and stride tables, bootstrap intervals (DESIGN 4.23)
-STEP_TABLE_COLUMNS = ("t_prev", "t", "landing_foot", "step_time", "step_length", "step_width")
+STEP_TABLE_COLUMNS =("t_prev", "t", "landing_foot", "step_time", "step_length", "step_width")
 STRIDE_TABLE_COLUMNS = ("t0", "t1", "foot", "stride_time")
 BOOTSTRAP_STATISTICS = ("mean", "sd", "cv")
 BOOTSTRAP_OUT_COLUMNS = ("estimate", "replicates")            # then one column per quantile
@@ -3319,26 +3484,42 @@ def bootstrap_table(table, counts, cols, B=2000, block=1, seed=0, stream=0, quan
     return result
 
 
-def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False):
+def run_on_frames(model, image_folder, frames, bboxes, device="cuda", batch_size=None, on_device=False, body=False, body_on_host=False):
     """batch_generation.py:289-371: one batch per video (batch_size = max(n_frames, 400)), kp_3d -> kinectv2.  ``bboxes`` is scaled
     by 1.1 IN PLACE, as the reference's Inference.__init__ does to the caller's array (inference.py:48).  Image files are cropped
     and normalised by the HIP kernel (grnet_crop_normalise, row f1); .npy files hold ready crops.
     on_device: return {"kp_3d": (n,25,3) float32 tensor on ``device``} and never synchronise with the host (the multi-GPU driver
-    keeps every work item's joints on the device until its single all-gather); default: the reference's numpy array."""
+    keeps every work item's joints on the device until its single all-gather); default: the reference's numpy array.
+    body: also return "body", the (n,11) float64 rows of DESIGN 4.25 (MESH_MOMENT_COLUMNS) -- model.mesh_moments on the vertices of each forward call
+    where they lie, a tensor on ``device`` (on_device) or a numpy array; body_on_host, or a model without the method: mesh_moments here, on
+    model.faces, after a download of the vertices."""
     ds = InferenceFrames(image_folder, frames, bboxes, scale=1.1)
-    joints = []
+    joints, moments = [], []
     sel = torch.as_tensor(np.asarray(netspec.SPIN2_TO_KINECTV2), dtype=torch.long, device=device) if on_device else None
     for batch in ds.batches(batch_size or max(len(frames), MAX_SEQLEN), model=model):
         x = torch.as_tensor(batch, dtype=torch.float32).unsqueeze(0).to(device)
         out = model(x)[-1]
+        if body:
+            verts = out["verts"].detach().reshape(-1, netspec.NUM_VERTS, 3)
+            if body_on_host or not hasattr(model, "mesh_moments"):
+                rows = torch.as_tensor(mesh_moments(verts.cpu().numpy(), model.faces), dtype=torch.float64, device=device)
+            else:
+                rows = model.mesh_moments(verts)
+            moments.append(rows if on_device else rows.cpu().numpy())
         if on_device:
             joints.append(out["kp_3d"].detach().squeeze(0).index_select(1, sel).to(torch.float32))
             continue
         j = out["kp_3d"].detach().cpu().squeeze(0).numpy()
         joints.append(spin2_to_kinectv2(j).astype(np.float32))
     if on_device:
-        return {"kp_3d": torch.cat(joints, 0) if joints else torch.zeros(0, 25, 3, dtype=torch.float32, device=device)}
-    return {"kp_3d": np.concatenate(joints, 0) if joints else np.zeros((0, 25, 3), np.float32)}
+        made = {"kp_3d": torch.cat(joints, 0) if joints else torch.zeros(0, 25, 3, dtype=torch.float32, device=device)}
+        if body:
+            made["body"] = torch.cat(moments, 0) if moments else torch.zeros(0, 11, dtype=torch.float64, device=device)
+        return made
+    made = {"kp_3d": np.concatenate(joints, 0) if joints else np.zeros((0, 25, 3), np.float32)}
+    if body:
+        made["body"] = np.concatenate(moments, 0) if moments else np.zeros((0, 11))
+    return made
 
 
 class BatchDb:
